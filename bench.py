@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- BASELINE.json metric: "stereo frames/sec + DWO Schur ms @ 50 KF / 20k pts".
 
-One JSON line on rank 0.  Two timed regions per run, each K steps, barrier + synchronize on both
+One JSON line on rank 0.  Two timed regions (B with --full only), each K steps, barrier + synchronize on both
 sides, max over ranks:
   A. front-end: a step = one pass of the per-frame hot path (pyramid, device-resident dense tracking
      with the f32 conversion + Sobel taps of preprocessing fused into its gathers, dense point cloud, grid FAST, guided ZNSSD matching of 2000 candidate points)
@@ -14,6 +14,10 @@ sides, max over ranks:
 with HIP events on its own stream; `roofline_frontend` lists the front-end kernels the same way.
 `cpu_baseline` is the CPU oracle (a port of the reference's CPU path) timed on the host cores of
 this box on a bounded sample; it is the checker's code used as a baseline, never the product.
+
+A plain run times region A alone and prints the headline (metric, value, ms_per_step, ...); region B,
+the rooflines, the CPU baseline and every other row run with --full.  --dump-outputs DIR writes what
+the last timed step of region A computed (dump_outputs below).
 """
 import argparse
 import json
@@ -78,6 +82,51 @@ def dry_launch(args, world, rank):
     dist.destroy_process_group()
 
 
+def _flat_fields(s):
+    """a ctypes result structure as a flat list of floats, padding left out (every field here is an int32 or a double: exact in float64)"""
+    import ctypes as C
+    out = []
+    for name, _ in s._fields_:
+        if name.startswith("pad"):
+            continue
+        v = getattr(s, name)
+        if isinstance(v, C.Structure):
+            out += _flat_fields(v)
+        elif isinstance(v, C.Array):
+            out += [float(x) for x in v]
+        else:
+            out.append(float(v))
+    return out
+
+
+def dump_outputs(dirname, fe, n_streams, n_sample=64):
+    """--dump-outputs: what the last timed step handed back, as a caller of svs_frontend_process_frames receives it.  Every stream: refined pose,
+    tracking flag and FrameResult scalars.  A fixed sample of streams (seeded): match records, gated points and the three dense clouds -- all streams'
+    records and clouds would be ~180 MB.  Integer fields are stored as float64 (exact)."""
+    os.makedirs(dirname, exist_ok=True)
+    T, ok = fe.poses()
+    sample = np.sort(np.random.default_rng(0).choice(n_streams, min(n_sample, n_streams), replace=False))
+    arrays = {"poses": T.astype(np.float64), "tracking_ok": ok.astype(np.float64), "sample_streams": sample.astype(np.float64)}
+    scalars, match, gated = [], [], []
+    in_sample = set(int(b) for b in sample)
+    for b in range(n_streams):
+        res, m, g = fe.results(b)
+        scalars.append(_flat_fields(res))
+        if b in in_sample:
+            match.append(np.concatenate([np.stack([m[k].astype(np.float64) for k in ("status", "u", "v", "znssd")], 1), m["obs"], m["xyz_actkey"]], 1))
+            gated.append(np.concatenate([np.stack([g[k].astype(np.float64) for k in ("accepted", "is_new")], 1), g["uv_pyr"], g["curkey_uv_pyr"]], 1))
+    arrays["frame_results"] = np.asarray(scalars, np.float64)
+    arrays["match_records_sample"] = np.concatenate(match)          # status u v znssd obs[3] xyz_actkey[3], sampled streams in order
+    arrays["gated_points_sample"] = np.concatenate(gated)           # accepted is_new uv_pyr[2] curkey_uv_pyr[2]
+    for l in range(3):
+        arrays[f"cloud_level{l}_sample"] = np.stack([fe.cloud_host(l, int(b)) for b in sample]).astype(np.float32)
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= 64 << 20, f"--dump-outputs: {total} bytes"
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, name + ".npy"), a)
+    print(f"bench: {len(arrays)} arrays, {total / 1e6:.1f} MB written to {dirname}", file=sys.stderr)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -90,7 +139,12 @@ def main():
     ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baseline leg")
     ap.add_argument("--dry-launch", action="store_true", help="launcher check (tests, no GPU): bring up --gpus ranks over gloo, exchange one message, print who answered")
     ap.add_argument("--quick", action="store_true", help="kernel A/B runs: the front-end headline, its stage times and the accept-test rows only (not the contract's line)")
+    ap.add_argument("--full", action="store_true", help="everything beyond the headline: stage times, accept-test and schedule A/Bs, stereo input, latency mode, "
+                                                        "other batches and frame sizes, full-resolution tracker, Schur rows, rooflines, CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step computed as DIR/<name>.npy (float32 / float64)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     # `python bench.py --gpus N` IS the multi-GPU command: when no launcher has set the rank environment, this process becomes the launcher and starts one rank per
     # GPU through torch.distributed.run (the driver's explicit `python -m torch.distributed.run ... bench.py --gpus N` finds WORLD_SIZE set and falls through)
@@ -179,6 +233,7 @@ def main():
     I34 = np.hstack([np.eye(3), np.zeros((3, 1))]).reshape(12)
 
     def make_inputs(cam_, npair, with_right=True):
+        from concurrent.futures import ThreadPoolExecutor
         mrng = np.random.default_rng(77)
         T_prev_l, T_cur_l = [], []
         for p in range(npair):
@@ -188,17 +243,22 @@ def main():
             T_rel_p = synth.pose(R_rel, np.array([mrng.normal(0, 0.003), mrng.normal(0, 0.002), -step]))     # camera moves forward: points come closer
             T_prev_l.append(T_p)
             T_cur_l.append(synth.pose_mul(T_rel_p, T_p))
-        rp = [scene.render(cam_, T_prev_l[p], seed=100 + p) for p in range(npair)]
-        rc = [scene.render(cam_, T_cur_l[p], seed=200 + p) for p in range(npair)]
         T_right = synth.pose(np.eye(3), np.array([-cam_["b"], 0.0, 0.0]))      # right camera of the stereo rig (for the block matcher)
         nr = min(npair, 4) if with_right else 0
-        rr = [scene.render(cam_, synth.pose_mul(T_right, T_cur_l[p]), seed=1000 + p)[0] for p in range(nr)]
-        rrp = [scene.render(cam_, synth.pose_mul(T_right, T_prev_l[p]), seed=1100 + p)[0] for p in range(nr)]
+        # every render is a pure function of (pose, seed): rendered on a few host threads (NumPy releases the GIL), the same bytes as one after the other
+        jobs = ([(T_prev_l[p], 100 + p) for p in range(npair)] + [(T_cur_l[p], 200 + p) for p in range(npair)] +
+                [(synth.pose_mul(T_right, T_cur_l[p]), 1000 + p) for p in range(nr)] + [(synth.pose_mul(T_right, T_prev_l[p]), 1100 + p) for p in range(nr)])
+        with ThreadPoolExecutor(max(1, min(16, len(os.sched_getaffinity(0))))) as ex:
+            rend = list(ex.map(lambda j: scene.render(cam_, j[0], seed=j[1]), jobs))
+        rp, rc = rend[:npair], rend[npair:2 * npair]
+        rr = [r[0] for r in rend[2 * npair:2 * npair + nr]]
+        rrp = [r[0] for r in rend[2 * npair + nr:]]
         return dict(cam=cam_, npair=npair, T_prev_list=T_prev_l, T_cur_list=T_cur_l, rend_prev=rp, rend_cur=rc, rend_right=rr, rend_right_prev=rrp,
                     T_AB=[synth.pose_mul(T_cur_l[p], synth.pose_inv(T_prev_l[p])) for p in range(npair)],      # T_B_from_A: the motion between a stream's two frames
                     pts_of_pair={})
 
-    INP = make_inputs(synth.CAM_DEFAULT, NPAIR)
+    extended = args.full or args.quick                       # a plain run does only what the headline needs (the right images feed the stereo-input rows)
+    INP = make_inputs(synth.CAM_DEFAULT, NPAIR, with_right=extended)
     cam, T_prev_list, T_cur_list, rend_prev, rend_cur, rend_right, rend_right_prev, T_AB, pts_of_pair = (INP[k] for k in (
         "cam", "T_prev_list", "T_cur_list", "rend_prev", "rend_cur", "rend_right", "rend_right_prev", "T_AB", "pts_of_pair"))
     n_per_level = (int(args.points * 0.6), int(args.points * 0.3), args.points - int(args.points * 0.6) - int(args.points * 0.3))
@@ -336,11 +396,29 @@ def main():
     oc = OneCall(B)
     _probe_windows('front end created')
     t_front = max_over_ranks(timed_steps(oc, W + (W & 1), K))          # even warm-up: the timed region starts with a frame-B step
+    fps = world * B * K / t_front
+    headline = {
+        "metric": "stereo frames/sec + DWO Schur ms @ 50 KF / 20k pts",
+        "value": round(fps, 2), "unit": "frames/s", "n_gpus": world, "steps": K, "warmup": W,
+        "ms_per_step": round(t_front / K * 1e3, 4), "higher_is_better": True, "scaling": "weak",
+        "vs_baseline": None, "dtype": "u8/int32 (FAST, ZNSSD), f32+f64 (dense tracking), f64 (Schur)",
+        "data": "synthetic",
+    }
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, oc.fe, B)
     if os.environ.get("SVS_BENCH_REPEAT"):          # run-to-run spread of the headline inside ONE process: the same K steps again, N times
         print(json.dumps({"repeat_ms_per_step": [round(t_front / K * 1e3, 4)] + [round(timed_steps(oc, 0, K) / K * 1e3, 4) for _ in range(int(os.environ["SVS_BENCH_REPEAT"]))]}), flush=True)
     if os.environ.get("SVS_BENCH_TRACE_STOP"):      # kernel timelines (tools/timeline.py over a rocprofv3 trace): the trace ends with the headline's own steps
         print(json.dumps({"trace_stop": True, "ms_per_step": round(t_front / K * 1e3, 4)}))
         oc.close()
+        return
+    if not extended:                                # the plain run: the headline line and nothing else (the rows below are behind --full)
+        oc.close()
+        if rank == 0:
+            print(json.dumps(headline))
+        if use_dist:
+            dist.barrier()
+            dist.destroy_process_group()
         return
     # the tracker's accept test: by default it takes the reference's decisions -- f64 sums where they can decide `float chi2 - float new_chi2 > 0`,
     # the reference's sequential float sums (formed bit for bit, in parallel: csrc/seqsum.h) where they cannot.  How many such sums a frame needs, and what the same
@@ -363,7 +441,6 @@ def main():
     t_front_stream_order = max_over_ranks(timed_steps(oc, 2, K))
     ctx.set_option("trk_balance", 1)
     timed_steps(oc, 2, 0)
-    fps = world * B * K / t_front
     # what the last step left: poses, matches, dense sweeps (checked against the true motion: the bench is not timing a diverged tracker)
     T_all, ok_all = oc.fe.poses()
     f_last = oc.k & 1
@@ -1062,11 +1139,7 @@ def main():
 
     if rank == 0:
         out = {
-            "metric": "stereo frames/sec + DWO Schur ms @ 50 KF / 20k pts",
-            "value": round(fps, 2), "unit": "frames/s", "n_gpus": world, "steps": K, "warmup": W,
-            "ms_per_step": round(t_front / K * 1e3, 4), "higher_is_better": True, "scaling": "weak",
-            "vs_baseline": None, "dtype": "u8/int32 (FAST, ZNSSD), f32+f64 (dense tracking), f64 (Schur)",
-            "data": "synthetic",
+            **headline,
             "value_stereo_input": round(fps_stereo, 2),
             "config": {"workload": "configs[1]+[3]: `value` = frames/s WITH THE DISPARITY IMAGE GIVEN (have_disp_img, RGB-D style input); with stereo input -- cv::StereoBM "
                                    "block matching inside the step -- it is `value_stereo_input` (about half).  StereoFrontend::processFrame as ONE library call for a "

@@ -4,12 +4,12 @@ tag=${1:-r2}
 out=gpurun_out/$tag
 mkdir -p $out
 export TMPDIR=/tmp
-timeout 500 python bench.py > $out/bench.log 2> $out/bench.err
+timeout 500 python bench.py --full > $out/bench.log 2> $out/bench.err
 echo "bench rc=$?"
-timeout 400 rocprofv3 --kernel-trace --stats -d $out/trace -o trace -- python bench.py --steps 10 --warmup 3 --no-cpu > $out/trace.log 2>&1
+timeout 400 rocprofv3 --kernel-trace --stats -d $out/trace -o trace -- python bench.py --full --steps 10 --warmup 3 --no-cpu > $out/trace.log 2>&1
 echo "trace rc=$?"
 for c in FETCH_SIZE WRITE_SIZE; do
-  timeout 400 rocprofv3 --kernel-trace --pmc $c -d $out/pmc_$c -o pmc -- python bench.py --steps 3 --warmup 1 --no-cpu > $out/pmc_$c.log 2>&1
+  timeout 400 rocprofv3 --kernel-trace --pmc $c -d $out/pmc_$c -o pmc -- python bench.py --full --steps 3 --warmup 1 --no-cpu > $out/pmc_$c.log 2>&1
   echo "pmc $c rc=$?"
 done
 # the full-resolution tracker on its own (64 streams per launch only, so that the per-launch average is the batched launch)

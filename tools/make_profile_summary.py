@@ -71,7 +71,7 @@ def main(bench_log, trace_db, fetch_db, write_db, out, title="Round 1", notes=No
               f"  = {rf['achieved']:.1f} GB/s = {100*rf['frac']:.2f} % of 8 TB/s; PMC traffic {(rf['traffic'] or 0)/1e6:.1f} MB per launch (section 3).\n"
               "  The kernel is not byte-bound; see section 4.\n")
     md.append("## 2. rocprofv3 --kernel-trace --stats (same build)\n")
-    md.append("Command: `cd /tmp && export TMPDIR=/tmp && rocprofv3 --kernel-trace --stats -d gpurun_out/<dir> -o <name> -- python bench.py --steps 10 --warmup 3 --no-cpu`\n")
+    md.append("Command: `rocprofv3 --kernel-trace --stats -d <dir> -o <name> -- python bench.py --full --steps 10 --warmup 3 --no-cpu`\n")
     if geo:
         md.append(f"Per kernel and launch geometry (grid y = {B} rows are the batched front-end, y = 1 the latency-mode launches):\n")
         md.append("| kernel | grid (x,y) | calls | avg us | min us |\n|---|---|---:|---:|---:|")
@@ -85,7 +85,7 @@ def main(bench_log, trace_db, fetch_db, write_db, out, title="Round 1", notes=No
     md.append("Totals:\n")
     md.append(capture(rocpd_summary.main, trace_db))
     md.append("\n## 3. PMC counters (HBM traffic), separate passes\n")
-    md.append("Commands: `rocprofv3 --pmc FETCH_SIZE --kernel-trace -- python bench.py --steps 3 --warmup 1 --no-cpu` and the same with\n"
+    md.append("Commands: `rocprofv3 --pmc FETCH_SIZE --kernel-trace -- python bench.py --full --steps 3 --warmup 1 --no-cpu` and the same with\n"
               "`--pmc WRITE_SIZE` (two runs; FETCH_SIZE and WRITE_SIZE do not fit one pass, MI355X_MICROARCH.md \"rocprofv3 PMC slots\").\n"
               "Units are KB per launch.  On gfx950 FETCH_SIZE under-reports wide coalesced reads by exactly 2x (same guide), so the\n"
               "corrected column doubles it; for narrow/gather patterns the factor is uncalibrated and the raw value is the lower bound.\n")

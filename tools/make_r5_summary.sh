@@ -15,7 +15,7 @@ md += "\n## 6. The drop-in `SlamGraph::optimize` call (set_problem device route 
 md += open(src + 'trace_dropin_summary.txt').read()
 md += "\n```\n" + "\n".join(l for l in open(src + 'trace_dropin.log').read().splitlines() if l.startswith('host_marshal') or l.startswith('window')) + "\n```\n"
 t = json.loads([l for l in open(src + 'torchrun_bench.json').read().splitlines() if l.startswith('{')][-1])
-md += "\n## 7. `python -m torch.distributed.run --nproc-per-node 1 ... bench.py --gpus 1` (world size 1: the library-owned RCCL communicator and the one-shot P2P transport both run their code paths)\n\n"
+md += "\n## 7. `python -m torch.distributed.run --nproc-per-node 1 ... bench.py --full --gpus 1` (world size 1: the library-owned RCCL communicator and the one-shot P2P transport both run their code paths)\n\n"
 md += "* RCCL: `" + json.dumps(t['config']['collective']) + "`\n* one-shot P2P transport (`svs_comm_create_p2p`): `" + json.dumps(t['schur']['one_shot_p2p_transport']) + "`\n* value " + str(t['value']) + " frames/s, optimize " + str(t['schur']['ms_per_optimize']) + " ms\n"
 md += "\n## 8. `__amd_rocclr_copyBuffer` launches in the traced run (section 2)\n\nThe traced command now contains rows that are host-IO by definition and did not exist in round 3's trace: the two-threads row (600 + 64 latency-mode frames with host images in and records out: 6 copies per frame, about 4 000; 120 + optimizes with state restore, about 700), the latency rows (about 110 host-IO frames, about 700) and the drop-in BA rows (6 - 8 staged pieces per call).  The per-stream setup copies of a 512-stream batch that round 3's verdict counted (about 2 000 per batch object) are gone: `svs_frontend_keep_keyframes` / `svs_frontend_set_candidates_all` are one staged upload per call (2 + 4 copies per batch object).\n"
 md += "\n## 9. Block matching alone, per kernel: `rocprofv3 --kernel-trace --stats -- python tools/time_stereo.py 512` (512 pairs of 640 x 480)\n\n" + open(src + 'stereo_kernels.txt').read()

@@ -11,7 +11,7 @@ for grp in "TA_TA_BUSY_sum TA_ADDR_STALLED_BY_TC_CYCLES_sum TA_DATA_STALLED_BY_T
            "TD_TD_BUSY_sum TD_TC_STALL_sum TD_LOAD_WAVEFRONT_sum TCP_TOTAL_READ_sum" \
            "TCP_UTCL1_TRANSLATION_MISS_sum TCP_UTCL1_TRANSLATION_HIT_sum TCP_UTCL1_REQUEST_sum TCP_TCR_TCP_STALL_CYCLES_sum"; do
   i=$((i+1))
-  timeout 200 rocprofv3 --kernel-trace --pmc $grp -d $out/g$i -o pmc -- python bench.py --steps 1 --warmup 1 --no-cpu > $out/g$i.log 2>&1
+  timeout 200 rocprofv3 --kernel-trace --pmc $grp -d $out/g$i -o pmc -- python bench.py --full --steps 1 --warmup 1 --no-cpu > $out/g$i.log 2>&1
   echo "group $i rc=$?"
   python tools/pmc_any.py "$sub" $(find $out/g$i -name "*.db") > $out/g$i.txt 2>&1
   rm -rf $out/g$i
