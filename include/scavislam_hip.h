@@ -131,7 +131,7 @@ int svs_ctx_sync(svs_ctx *ctx);
    blocks in XCD-contiguous order; 0: the dispatcher's round robin),
    "trk_flat" (default 1: batches of more than one stream per CU run the flat tracker kernel -- the sweep inlined, the LM state in LDS; 0: the
    round-5 kernel, same bits), "trk_split" (default 10: in such batches a stream still iterating after that many trials on the finest level is
-   finished by a second launch with up to eight workgroups per stream -- same accept decisions, poses equal to 1e-12; 0: one launch).
+   finished by a second launch with eight workgroups per stream -- same accept decisions, poses equal to 1e-12, a stream's bits independent of the rest of its batch; 0: one launch).
    A context and every handle made from it are used by ONE thread at a time. */
 int svs_ctx_set_option(svs_ctx *ctx, const char *name, int value);
 /* The accept test of the quarter-grid tracker: DenseTracker::denseTrackingCpu accepts an LM step iff `float chi2 - float new_chi2 > 0` on two sums accumulated

@@ -1114,34 +1114,23 @@ __device__ __noinline__ void track_solve_call() {
 // the long streams from the last frame does not work (correlation -0.18 in the bench).  So the first launch (CONT = 0) runs every stream with one workgroup as before, but a
 // stream that has taken K trials on level 0 and is still not done PARKS: its LM state -- the accepted pose, H,b of the accepted pass, the sums the accept test carries,
 // the term buffers (they are in global memory already) -- goes to global memory, its index to a list, and the workgroup exits.  The second launch (CONT = 1) takes the list:
-// every parked stream is resumed by NW workgroups (NW = what fits the device for the number of parked streams, decided on the device) that share each sweep exactly like
-// the latency mode does (partial sums through write-through words + one arrival counter, the leader forms the exact float sums and publishes the decision).  A trial of a
-// parked stream then takes ~30 us instead of ~170.  K is a constant, so which sweeps run in which form is a function of the data alone: deterministic results; the
-// partial sums of a shared sweep are added in another order than the one-workgroup sweep's, so H,b differ from the unsplit run in their last bits (pose 1e-12), while the
-// accept decisions are the reference's either way (exact float sums of the terms).
+// every parked stream is resumed by CONT_MAX_NWG = 8 workgroups that share each sweep exactly like the latency mode does (partial sums through write-through words + one
+// arrival counter, the leader forms the exact float sums and publishes the decision).  A trial of a parked stream then takes ~30 us instead of ~170.  The launch has
+// slots / 8 groups of eight siblings; a group resumes the parked streams y, y + groups, ... one after the other, so more parked streams than fit at once wait for a
+// group instead of getting fewer workgroups.  K and the eight are constants, so which sweeps run in which form, and the order every partial sum is added in, are a
+// function of the stream's own data alone: its result does not depend on the other streams of the batch, the batch size, "trk_cont_slots" or the device's CU count.
+// The partial sums of a shared sweep are added in another order than the one-workgroup sweep's, so H,b differ from the unsplit run in their last bits (pose 1e-12),
+// while the accept decisions are the reference's either way (exact float sums of the terms).
 struct TrkPark { TrkState ts; double T[12], H[27], Tj[36]; };
-struct TrackCont { TrkPark *park; int *list; unsigned *count; int K; int slots; };      // K < 0: no parking; slots: resident workgroup slots of the device for the second launch
+struct TrackCont { TrkPark *park; int *list; unsigned *count; int K; int slots; };      // K < 0: no parking; slots: resident workgroup slots of the device for the second launch (its concurrency, not its results)
 constexpr int CONT_MAX_NWG = 8;
-template <bool U8SRC, bool BAL, int CONT>      // CONT 0: first launch (BAL: grid order from the table); 1: the continuation (grid = CONT_MAX_NWG x batch, blockIdx.y = index into the list)
-__global__ __launch_bounds__(TRK_THREADS, TRK_MINW_BIG) void dense_track_batch_kernel(TrackArgs A, double *__restrict__ T_io, int *__restrict__ passes_out, TrackMulti G, TrackCont C) {
-  constexpr bool MULTI = CONT == 1;
+// one stream of a big batch: the whole LM loop (MULTI = false: first launch, one workgroup) or the rest of a parked stream (MULTI: workgroup wg of the stream's
+// CONT_MAX_NWG).  Every word the siblings of a stream exchange -- partials, arrival counter, failure flag, hand-over words -- belongs to the STREAM (slot), and each
+// parked stream is resumed exactly once, so nothing needs resetting between the streams one group of siblings resumes in turn.
+template <bool U8SRC, bool MULTI>
+__device__ __forceinline__ void track_batch_stream(const TrackArgs &A, double *__restrict__ T_io, int *__restrict__ passes_out, const TrackMulti &G, const TrackCont &C,
+                                                   const int slot, const int wg, const int nwg) {
   constexpr int TM = SVS_TRK_LAZY ? (MULTI ? 2 : 1) : 0;
-  int slot = blockIdx.x, wg = 0, nwg = 1;
-  if constexpr (BAL && !MULTI) {
-    const int e = G.map[blockIdx.x];
-    if (e < 0 || (e & 15) != 0) return;      // idle workgroup / a sibling entry of a table made for the split variant
-    slot = e >> 4;
-  }
-  if constexpr (MULTI) {
-    const int n_parked = (int)*C.count;
-    if ((int)blockIdx.y >= n_parked) return;
-    // workgroups per parked stream: as many as are resident together (all of a stream's workgroups wait for each other; siblings are neighbours in the grid)
-    nwg = C.slots / n_parked;
-    nwg = nwg >= 8 ? 8 : (nwg >= 4 ? 4 : (nwg >= 2 ? 2 : 1));
-    wg = blockIdx.x;
-    if (wg >= nwg) return;
-    slot = C.list[blockIdx.y];
-  }
   const int tid = threadIdx.x;
   __shared__ bool s_failed;
   float *const tb0 = G.terms ? G.terms + (size_t)slot * 2 * G.terms_b : nullptr;
@@ -1317,6 +1306,26 @@ __global__ __launch_bounds__(TRK_THREADS, TRK_MINW_BIG) void dense_track_batch_k
   if (tid == 0 && G.seq_stats && g_ts.n_exact) {
     atomicAdd(G.seq_stats, g_ts.n_exact);
     if (SVS_TRK_LAZY && g_seq_sh.fell_back) atomicAdd(G.seq_stats + 1, 1u);
+  }
+}
+template <bool U8SRC, bool BAL, int CONT>      // CONT 0: first launch (BAL: grid order from the table); 1: the continuation (grid = CONT_MAX_NWG x groups: launch_batch_tracker)
+__global__ __launch_bounds__(TRK_THREADS, TRK_MINW_BIG) void dense_track_batch_kernel(TrackArgs A, double *__restrict__ T_io, int *__restrict__ passes_out, TrackMulti G, TrackCont C) {
+  if constexpr (CONT == 0) {
+    int slot = blockIdx.x;
+    if constexpr (BAL) {
+      const int e = G.map[blockIdx.x];
+      if (e < 0 || (e & 15) != 0) return;      // idle workgroup / a sibling entry of a table made for the split variant
+      slot = e >> 4;
+    }
+    track_batch_stream<U8SRC, false>(A, T_io, passes_out, G, C, slot, 0, 1);
+  } else {
+    // every parked stream gets CONT_MAX_NWG workgroups, whatever else parked: the split of its sweeps, and so the order its partial sums are added in, is that of the
+    // stream alone.  Group y of siblings (the CONT_MAX_NWG workgroups of grid row y, neighbours in the dispatch order) resumes list entries y, y + groups, ...
+    const int n_parked = (int)*C.count;
+    for (int p = blockIdx.y; p < n_parked; p += gridDim.y) {
+      track_batch_stream<U8SRC, true>(A, T_io, passes_out, G, C, C.list[p], blockIdx.x, CONT_MAX_NWG);
+      __syncthreads();                             // (the next stream's state overwrites this one's in LDS)
+    }
   }
 }
 
@@ -1632,11 +1641,13 @@ static int launch_batch_tracker(svs_ctx *ctx, const TrackArgs &A, bool u8src, do
   else hipLaunchKernelGGL((dense_track_batch_kernel<false, BAL, 0>), dim3(grid), dim3(TRK_THREADS), 0, ctx->stream, A, d_T_io, d_passes_out, G, C);
   SVS_LAUNCH_CHECK(ctx);
   if (C.K < 0) return SVS_OK;
-  // the parked streams, several workgroups each: they wait for each other inside the launch -- through the spin gate like every launch of that kind (common.h)
+  // the parked streams, CONT_MAX_NWG workgroups each: they wait for each other inside the launch -- through the spin gate like every launch of that kind (common.h).
+  // groups x CONT_MAX_NWG <= slots workgroups: all resident together, so every sibling a workgroup waits for is running (and a wait is only ever on a sibling)
+  const int groups = std::max(1, std::min(batch, C.slots / CONT_MAX_NWG));
   SvsSpinScope gate(ctx);
   if (gate.rc) return gate.rc;
-  if (u8src) hipLaunchKernelGGL((dense_track_batch_kernel<true, false, 1>), dim3(CONT_MAX_NWG, batch), dim3(TRK_THREADS), 0, ctx->stream, A, d_T_io, d_passes_out, G, C);
-  else hipLaunchKernelGGL((dense_track_batch_kernel<false, false, 1>), dim3(CONT_MAX_NWG, batch), dim3(TRK_THREADS), 0, ctx->stream, A, d_T_io, d_passes_out, G, C);
+  if (u8src) hipLaunchKernelGGL((dense_track_batch_kernel<true, false, 1>), dim3(CONT_MAX_NWG, groups), dim3(TRK_THREADS), 0, ctx->stream, A, d_T_io, d_passes_out, G, C);
+  else hipLaunchKernelGGL((dense_track_batch_kernel<false, false, 1>), dim3(CONT_MAX_NWG, groups), dim3(TRK_THREADS), 0, ctx->stream, A, d_T_io, d_passes_out, G, C);
   SVS_LAUNCH_CHECK(ctx);
   return gate.leave();
 }

@@ -509,8 +509,9 @@ def test_dense_tracking_latency_mode_other_workgroup_counts(gpu_ctx, nwg):
 
 def test_dense_tracking_big_batch_continuation_launch(gpu_ctx):
     """A batch of more than one stream per CU runs the flat tracker kernel, and with "trk_split" = K its streams that are still iterating after K trials on the finest
-    level PARK and are finished by a second launch with 1 / 2 / 4 / 8 workgroups per stream (dense.hip: the continuation launch).  300 streams over 8 scenes, K = 0 (off),
-    1, 3, 5, 8: however many streams park and however many workgroups resume them, EVERY stream's accept / reject record equals the oracle's to the end, the poses agree with
+    level PARK and are finished by a second launch with eight workgroups per stream (dense.hip: the continuation launch; when more streams park than its groups of eight
+    can take at once, a group resumes several in turn).  300 streams over 8 scenes, K = 0 (off), 1, 3, 5, 8: however many streams park, EVERY stream's accept / reject
+    record equals the oracle's to the end, the poses agree with
     the oracle to 1e-9 and with the unsplit run to 1e-12, no stream reports a failed hand-over, and the replicas of a scene inside one batch are bit-equal."""
     import oracle as O
     from scavislam_amd import synth
