@@ -606,14 +606,23 @@ class StereoFrontend:
     def _img(a, dtype):
         return None if a is None else np.ascontiguousarray(a, dtype)
 
+    def _host(self, a, dtype, strided):
+        """(array, row stride in elements) of one host image.  strided=False: a contiguous copy, rows w apart.  strided=True: the caller's [h, w] view passed as it
+        lies, rows a.strides[0] bytes apart in a wider buffer (a cv::Mat with a padded step), no copy"""
+        w = self.cam["w"]
+        if a is None or not strided:
+            return self._img(a, dtype), w
+        assert a.dtype == dtype and a.shape == (self.cam["h"], w) and a.strides[1] == a.itemsize and a.strides[0] % a.itemsize == 0, "a [h, w] view with unit column step"
+        return a, a.strides[0] // a.itemsize
+
     @staticmethod
     def _ptr(a):
         return a.ctypes.data if a is not None else None
 
-    def processFirstFrame(self, left=None, right=None, disp=None):
-        left, right, disp = self._img(left, np.uint8), self._img(right, np.uint8), self._img(disp, np.float32)
-        w = self.cam["w"]
-        self.ctx.check(self.ctx.lib.svs_frontend_first_frame(self.h, self._ptr(left), w, self._ptr(right), w, self._ptr(disp), w))
+    def processFirstFrame(self, left=None, right=None, disp=None, strided=False):
+        """strided: the images are [h, w] views into padded buffers, handed over with their row strides (see _host)"""
+        (left, ls), (right, rs), (disp, ds) = self._host(left, np.uint8, strided), self._host(right, np.uint8, strided), self._host(disp, np.float32, strided)
+        self.ctx.check(self.ctx.lib.svs_frontend_first_frame(self.h, self._ptr(left), ls, self._ptr(right), rs, self._ptr(disp), ds))
 
     def keepKeyframe(self, slot, T_kf_from_w, stream=0):
         T = np.ascontiguousarray(T_kf_from_w, np.float64).reshape(12)
@@ -653,18 +662,16 @@ class StereoFrontend:
         mk = lambda ptr, ct, dt: np.ctypeslib.as_array(C.cast(ptr, C.POINTER(ct)), shape=(h, w)).view(dt)
         return mk(p[0], C.c_uint8, np.uint8), mk(p[1], C.c_uint8, np.uint8), mk(p[2], C.c_float, np.float32)
 
-    def prefetchFrame(self, left, right=None, disp=None):
-        left, right, disp = self._img(left, np.uint8), self._img(right, np.uint8), self._img(disp, np.float32)
-        w = self.cam["w"]
+    def prefetchFrame(self, left, right=None, disp=None, strided=False):
+        (left, ls), (right, rs), (disp, ds) = self._host(left, np.uint8, strided), self._host(right, np.uint8, strided), self._host(disp, np.float32, strided)
         self._keep = (left, right, disp)
-        self.ctx.check(self.ctx.lib.svs_frontend_prefetch_frame(self.h, self._ptr(left), w, self._ptr(right), w, self._ptr(disp), w))
+        self.ctx.check(self.ctx.lib.svs_frontend_prefetch_frame(self.h, self._ptr(left), ls, self._ptr(right), rs, self._ptr(disp), ds))
 
-    def submitFrame(self, left, T_cur_from_actkey, T_actkey_from_w, right=None, disp=None):
-        left, right, disp = self._img(left, np.uint8), self._img(right, np.uint8), self._img(disp, np.float32)
-        w = self.cam["w"]
+    def submitFrame(self, left, T_cur_from_actkey, T_actkey_from_w, right=None, disp=None, strided=False):
+        (left, ls), (right, rs), (disp, ds) = self._host(left, np.uint8, strided), self._host(right, np.uint8, strided), self._host(disp, np.float32, strided)
         Tc = np.ascontiguousarray(T_cur_from_actkey, np.float64).reshape(12)
         Ta = np.ascontiguousarray(T_actkey_from_w, np.float64).reshape(12)
-        self.ctx.check(self.ctx.lib.svs_frontend_submit_frame(self.h, self._ptr(left), w, self._ptr(right), w, self._ptr(disp), w, Tc.ctypes.data, Ta.ctypes.data, 1, 1))
+        self.ctx.check(self.ctx.lib.svs_frontend_submit_frame(self.h, self._ptr(left), ls, self._ptr(right), rs, self._ptr(disp), ds, Tc.ctypes.data, Ta.ctypes.data, 1, 1))
 
     def waitFrame(self):
         res = capi.FrameResult()
@@ -673,16 +680,15 @@ class StereoFrontend:
         self.ctx.check(self.ctx.lib.svs_frontend_wait_frame(self.h, C.byref(res), m.ctypes.data, g.ctypes.data))
         return res, m, g
 
-    def processFrame(self, left, T_cur_from_actkey, T_actkey_from_w, right=None, disp=None):
-        """returns (FrameResult, MATCH_RESULT_DTYPE[n], GATED_POINT_DTYPE[n]); left=None: the frame was prefetched"""
-        left, right, disp = self._img(left, np.uint8), self._img(right, np.uint8), self._img(disp, np.float32)
-        w = self.cam["w"]
+    def processFrame(self, left, T_cur_from_actkey, T_actkey_from_w, right=None, disp=None, strided=False):
+        """returns (FrameResult, MATCH_RESULT_DTYPE[n], GATED_POINT_DTYPE[n]); left=None: the frame was prefetched.  strided: see processFirstFrame"""
+        (left, ls), (right, rs), (disp, ds) = self._host(left, np.uint8, strided), self._host(right, np.uint8, strided), self._host(disp, np.float32, strided)
         Tc = np.ascontiguousarray(T_cur_from_actkey, np.float64).reshape(12)
         Ta = np.ascontiguousarray(T_actkey_from_w, np.float64).reshape(12)
         res = capi.FrameResult()
         m = np.zeros(self.n_points[0], MATCH_RESULT_DTYPE)
         g = np.zeros(self.n_points[0], GATED_POINT_DTYPE)
-        self.ctx.check(self.ctx.lib.svs_frontend_process_frame(self.h, self._ptr(left), w, self._ptr(right), w, self._ptr(disp), w, Tc.ctypes.data, Ta.ctypes.data,
+        self.ctx.check(self.ctx.lib.svs_frontend_process_frame(self.h, self._ptr(left), ls, self._ptr(right), rs, self._ptr(disp), ds, Tc.ctypes.data, Ta.ctypes.data,
                                                                C.byref(res), m.ctypes.data, g.ctypes.data))
         return res, m, g
 

@@ -22,15 +22,22 @@ def n_cu():
 _FRAMES = {}
 
 
-def seq_frames():
-    """(image, disparity) of the frames of the default sequence the streams use, rendered once per process; + the trajectory"""
-    if "f" not in _FRAMES:
+def seq_frames(cam=None):
+    """(image, disparity) of the frames of the default sequence the streams use, rendered once per process and camera; + the trajectory.  cam: another
+    camera (dict f, cx, cy, b, w, h) on the same trajectory, frames rendered the way seq_common.frames renders them; None: the default camera"""
+    key = "default" if cam is None else tuple(sorted(cam.items()))
+    if key not in _FRAMES:
         import seq_common
         from scavislam_amd import synth
         n = FIRST + N_OFFSETS + N_TRACKED
-        _FRAMES["f"] = list(seq_common.frames("default", n))
-        _FRAMES["traj"] = synth.trajectory_there_and_back(seq_common.N_FRAMES, seq_common.TURN)[:n]
-    return _FRAMES["f"], _FRAMES["traj"]
+        traj = synth.trajectory_there_and_back(seq_common.N_FRAMES, seq_common.TURN)[:n]
+        if cam is None:
+            f = list(seq_common.frames("default", n))
+        else:
+            sc = synth.Scene(2011)
+            f = [sc.render(cam, traj[i], seed=i) for i in range(n)]
+        _FRAMES[key] = (f, traj)
+    return _FRAMES[key]
 
 
 def hostile_frame(kind, img):
@@ -64,14 +71,14 @@ def stream_spec(b, seed=0):
     return dict(o=o, sizes=sizes, kind=kind, counts=counts, length=length, seed=int(rng.integers(1 << 30)))
 
 
-def make_streams(B, seed=0, specs=None):
+def make_streams(B, seed=0, specs=None, cam=None):
     """B pairwise distinct streams (or the given specs).  Per stream: the two keyframes' images / disparities / poses (slot 1 = the active keyframe), the first
     frame and its pose relative to the active keyframe, N_TRACKED frames to track (image, disparity) with their motion guess T_cur_from_actkey (and, for the
     first one, the same guess relative to the first frame: the bare tracker's start pose), T_actkey_from_w, the candidate list in matchAndTrack's order with its
-    group ends (active keyframe's new points | the neighbour's | the neighbourhood) and each record's list (the reference's list_of)."""
+    group ends (active keyframe's new points | the neighbour's | the neighbourhood) and each record's list (the reference's list_of).  cam: see seq_frames."""
     from scavislam_amd import synth
-    F, traj = seq_frames()
-    cam = synth.CAM_DEFAULT
+    F, traj = seq_frames(cam)
+    cam = synth.CAM_DEFAULT if cam is None else cam
     own = specs is None
     specs = [stream_spec(b, seed) for b in range(B)] if own else specs
     out = []

@@ -431,10 +431,10 @@ def test_dense_tracking_lm_trajectory_many_scenes(gpu_ctx, B):
     dtp.computeDensePointCloudCpu(I.reshape(12))
     dt = DenseTracker(ctx, cur)
     dt.ref_dense_points = dtp.ref_dense_points
-    n0 = ctx.get_stat("trk_exact_sums")
+    n0, f0 = ctx.get_stat("trk_exact_sums"), ctx.get_stat("trk_exact_fallbacks")      # (the context's counters: other modules' frames may have taken the chain)
     T, passes = dt.denseTrackingCpu(prev.pyr, I.reshape(12), from_u8=True)
     recs = dt.lm_records()
-    assert ctx.get_stat("trk_exact_sums") > n0 and ctx.get_stat("trk_exact_fallbacks") == 0
+    assert ctx.get_stat("trk_exact_sums") > n0 and ctx.get_stat("trk_exact_fallbacks") == f0
     n_float = 0
     refs = {}
     for b in range(B):
@@ -548,10 +548,11 @@ def test_dense_tracking_big_batch_continuation_launch(gpu_ctx):
     try:
         for K in (0, 1, 3, 5, 8):
             ctx.set_option("trk_split", K)
+            f0 = ctx.get_stat("trk_exact_fallbacks")
             T, passes = dt.denseTrackingCpu(prev.pyr, I.reshape(12), from_u8=True)
             recs = dt.lm_records()
             assert (passes > 0).all(), f"K = {K}: dense_passes = -1 (a sibling workgroup of a parked stream never arrived)"
-            assert ctx.get_stat("trk_exact_fallbacks") == 0
+            assert ctx.get_stat("trk_exact_fallbacks") == f0
             for b in range(B):
                 T_ref, passes_ref, rec_ref = refs[b % NS]
                 if b < 2 * NS or b >= B - NS:
