@@ -31,7 +31,7 @@ extern "C" {
 /* ABI version: bumped whenever a struct of this header grows or a signature changes (round 3 grew svs_pose_opt_params / svs_match_args and put a `stream`
    argument into svs_frontend_device_view without one -- INTEGRATION.md section 6).  A caller checks svs_api_version() == SVS_API_VERSION once, zero-initialises
    every parameter struct (or takes it from the *_default() initialisers) and sets only the fields it knows. */
-#define SVS_API_VERSION 7
+#define SVS_API_VERSION 8
 int svs_api_version(void);             /* the SVS_API_VERSION the loaded library was built with */
 
 enum {
@@ -591,6 +591,16 @@ int svs_ba_set_option(svs_ba *ba, const char *name, int value);
 int svs_ba_reset_state(svs_ba *ba, const double *h_poses, const double *h_psi);
 int svs_ba_reduced_system(svs_ba *ba, double lambda, double *h_Hred /* (6P)^2 full sym */,
                           double *h_bred /* 6P */, double *h_chi2);
+/* the layout the next Schur and back-substitution launches take: waves per workgroup (4..8; the one svs_ba_set_problem laid the wave chunks out
+   for, option "nw", or the smallest that gets the grid down to one workgroup per CU) and whether the Schur pass accumulates in the big LDS
+   pool (one workgroup per CU, 22-pose window; always at 5..8 waves) or the small one (two per CU, 16 poses: four waves with more workgroups than CUs) */
+int svs_ba_schur_layout(svs_ba *ba, int32_t *waves_per_workgroup, int32_t *big_pool);
+/* one LM trial at `lambda` from the caller's pose step h_xp (6P, the caller's pose order) instead of the solve's: the Schur pass at the current
+   state, trial poses exp(x_p) T, then the back-substitution x_l = D^-1 (b_l - W^T x_p) with the trial chi2 -- the kernels svs_ba_optimize runs
+   around its solve, without graph or speculation.  Out (each optional): trial poses [P][12], trial landmarks [L][3], trial chi2 (edges +
+   constraints), landmark share of the LM scale sum x_l . (lambda x_l + b_l).  The optimizer's current state is left unchanged. */
+int svs_ba_trial(svs_ba *ba, double lambda, const double *h_xp, double *h_poses_trial, double *h_psi_trial, double *h_chi2_trial,
+                 double *h_scale_l);
 /* what the last svs_ba_set_problem led to: solve_kind 0 = global-memory blocked Cholesky, 1 = LDS-window pipeline, 2 = fused
    register-resident elimination (one front), 3 = the same with two fronts, 4 = multi-workgroup blocked Cholesky (one block row per step, trailing matrix in global memory; option "no_tile_solve"), 5 = multi-workgroup
    tile-resident blocked Cholesky (24 x 24 tiles owned by workgroups in LDS: the default for wide envelopes); envelope_rows = widest filled block row of the reduced

@@ -395,6 +395,21 @@ def ba_optimize(poses, psi, edges, cons, cam, prm):
     return poses, psi, st
 
 
+def ba_trial(poses, psi, edges, cons, cam, prm, lam, xp):
+    """One LM trial from the pose step xp [P,6]: (trial poses [P,12], trial psi [L,3], trial chi2, landmark share of the scale)."""
+    poses, psi, edges, cons = _ba_args(poses, psi, edges, cons)
+    xp = np.ascontiguousarray(xp, np.float64).reshape(-1)
+    assert xp.size == 6 * len(poses)
+    poses_t, psi_t = np.zeros_like(poses), np.zeros_like(psi)
+    chi2, scl = C.c_double(), C.c_double()
+    L = lib()
+    L.svs_ref_ba_trial.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                   C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.svs_ref_ba_trial(len(poses), _p(poses), len(psi), _p(psi), len(edges), _p(edges), len(cons), _p(cons), C.byref(cam), C.byref(prm),
+                       float(lam), _p(xp), _p(poses_t), _p(psi_t), C.byref(chi2), C.byref(scl))
+    return poses_t, psi_t, chi2.value, scl.value
+
+
 # ---- stereo block matching (oracle/stereo.c) ---------------------------------------------------
 def stereo_prefilter(img, cap=31):
     img = np.ascontiguousarray(img, np.uint8)

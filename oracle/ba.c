@@ -423,6 +423,55 @@ int svs_ref_ba_reduced_system_mt(int threads, int P, const double *poses, int L,
   return 0;
 }
 
+/* One LM trial behind the solve (OptimizationAlgorithmLevenberg::solve): x_l = Dinv (b_l - W^T x_p) from the built
+   system S and the Schur pass's Dinv (skipped when the solve failed: x_l keeps its last value), the update T <- exp(x_p) T,
+   psi <- psi + x_l (oplus, anchored_points.cpp:53-58,78-83) into poses_out / psi_out (may alias poses / psi), *scale += the landmark
+   terms x_l . (lambda x_l + b_l) in landmark order; returns chi2 at the trial state */
+static double ba_trial_step(const ba_sys *S, const int *start, const int *idx, const double *Dinv, int P, const double *poses, int L,
+                            const double *psi, int E, const svs_ba_edge *edges, int C, const svs_ba_constraint *cons, const svs_cam *cam,
+                            const svs_ba_params *prm, double lambda, const double *xp, int fail, double *xl, double *poses_out,
+                            double *psi_out, double *scale) {
+  if (!fail) {
+    /* x_l = Dinv (b_l - W^T x_p) */
+    for (int l = 0; l < L; ++l) {
+      double c[3] = {S->bl[3 * l], S->bl[3 * l + 1], S->bl[3 * l + 2]};
+      for (int k = start[l]; k < start[l + 1]; ++k) {
+        int e = idx[k];
+        const double *Wo = S->Wobs + 18 * (size_t)e, *Wa = S->Wanc + 18 * (size_t)e;
+        const double *xo = xp + 6 * edges[e].pose, *xa = xp + 6 * edges[e].anchor;
+        for (int j = 0; j < 3; ++j) { double s = 0; for (int i = 0; i < 6; ++i) s += Wo[3 * i + j] * xo[i] + Wa[3 * i + j] * xa[i]; c[j] -= s; }
+      }
+      if (start[l + 1] > start[l]) m3_vec(Dinv + 9 * (size_t)l, c, xl + 3 * (size_t)l);
+      else { xl[3 * l] = xl[3 * l + 1] = xl[3 * l + 2] = 0; }
+    }
+  }
+  /* update (oplus): T <- exp(d) T ; psi <- psi + d   (anchored_points.cpp:53-58,78-83) */
+  for (int p = 0; p < P; ++p) { double Ex[12]; se3_exp(xp + 6 * p, Ex); pose_mul(Ex, poses + 12 * p, poses_out + 12 * p); }
+  for (int i = 0; i < 3 * L; ++i) psi_out[i] = psi[i] + xl[i];
+  for (int j = 0; j < 3 * L; ++j) *scale += xl[j] * (lambda * xl[j] + S->bl[j]);
+  return svs_ref_ba_chi2(P, poses_out, L, psi_out, E, edges, C, cons, cam, prm);
+}
+
+int svs_ref_ba_trial(int P, const double *poses, int L, const double *psi, int E, const svs_ba_edge *edges, int C,
+                     const svs_ba_constraint *cons, const svs_cam *cam, const svs_ba_params *prm, double lambda, const double *xp,
+                     double *poses_trial, double *psi_trial, double *chi2_trial, double *scale_l) {
+  const int n = 6 * P;
+  ba_sys S = sys_alloc(P, L, E);
+  int *start = (int *)malloc(sizeof(int) * ((size_t)L + 1)), *idx = (int *)malloc(sizeof(int) * (size_t)(E ? E : 1));
+  landmark_csr(L, E, edges, start, idx);
+  double *Hred = (double *)malloc(sizeof(double) * (size_t)n * n), *bred = (double *)malloc(sizeof(double) * n);
+  double *xl = (double *)calloc(3 * (size_t)(L ? L : 1), sizeof(double)), *Dinv = (double *)malloc(sizeof(double) * 9 * (size_t)(L ? L : 1));
+  build_system(&S, poses, psi, edges, C, cons, cam, prm);
+  schur_reduce(&S, edges, start, idx, lambda, Hred, bred, Dinv);
+  double scl = 0;
+  const double chi = ba_trial_step(&S, start, idx, Dinv, P, poses, L, psi, E, edges, C, cons, cam, prm, lambda, xp, 0, xl, poses_trial, psi_trial, &scl);
+  if (chi2_trial) *chi2_trial = chi;
+  if (scale_l) *scale_l = scl;
+  free(start); free(idx); free(Hred); free(bred); free(xl); free(Dinv);
+  sys_free(&S);
+  return 0;
+}
+
 int svs_ref_ba_optimize(int P, double *poses, int L, double *psi, int E, const svs_ba_edge *edges,
                         int C, const svs_ba_constraint *cons, const svs_cam *cam,
                         const svs_ba_params *prm, svs_ba_stats *stats) {
@@ -450,29 +499,11 @@ int svs_ref_ba_optimize(int P, double *poses, int L, double *psi, int E, const s
       memcpy(psi_bak, psi, sizeof(double) * 3 * (size_t)L);
       schur_reduce(&S, edges, start, idx, lambda, Hred, bred, Dinv);
       int fail = chol_solve(n, Hred, bred, xp);
-      if (!fail) {
-        /* x_l = Dinv (b_l - W^T x_p) */
-        for (int l = 0; l < L; ++l) {
-          double c[3] = {S.bl[3 * l], S.bl[3 * l + 1], S.bl[3 * l + 2]};
-          for (int k = start[l]; k < start[l + 1]; ++k) {
-            int e = idx[k];
-            const double *Wo = S.Wobs + 18 * (size_t)e, *Wa = S.Wanc + 18 * (size_t)e;
-            const double *xo = xp + 6 * edges[e].pose, *xa = xp + 6 * edges[e].anchor;
-            for (int j = 0; j < 3; ++j) { double s = 0; for (int i = 0; i < 6; ++i) s += Wo[3 * i + j] * xo[i] + Wa[3 * i + j] * xa[i]; c[j] -= s; }
-          }
-          if (start[l + 1] > start[l]) m3_vec(Dinv + 9 * (size_t)l, c, xl + 3 * (size_t)l);
-          else { xl[3 * l] = xl[3 * l + 1] = xl[3 * l + 2] = 0; }
-        }
-      }
-      /* update (oplus): T <- exp(d) T ; psi <- psi + d   (anchored_points.cpp:53-58,78-83) */
-      for (int p = 0; p < P; ++p) { double Ex[12]; se3_exp(xp + 6 * p, Ex); pose_mul(Ex, poses + 12 * p, poses + 12 * p); }
-      for (int i = 0; i < 3 * L; ++i) psi[i] += xl[i];
-      tempChi = svs_ref_ba_chi2(P, poses, L, psi, E, edges, C, cons, cam, prm);
-      if (fail) tempChi = DBL_MAX;
-      rho = currentChi - tempChi;
       double scale = 0;
       for (int j = 0; j < n; ++j) scale += xp[j] * (lambda * xp[j] + S.bp[j]);
-      for (int j = 0; j < 3 * L; ++j) scale += xl[j] * (lambda * xl[j] + S.bl[j]);
+      tempChi = ba_trial_step(&S, start, idx, Dinv, P, poses, L, psi, E, edges, C, cons, cam, prm, lambda, xp, fail, xl, poses, psi, &scale);
+      if (fail) tempChi = DBL_MAX;
+      rho = currentChi - tempChi;
       scale += 1e-3;
       rho /= scale;
       ++st.trials;

@@ -300,6 +300,12 @@ int svs_ref_ba_reduced_system_mt(int threads, int P, const double *poses, int L,
 int svs_ref_ba_optimize(int P, double *poses, int L, double *psi, int E,
                         const svs_ba_edge *edges, int C, const svs_ba_constraint *cons,
                         const svs_cam *cam, const svs_ba_params *prm, svs_ba_stats *stats);
+/* one LM trial of svs_ref_ba_optimize from a given pose step xp [6P]: the system at (poses, psi) with damping lambda, x_l = Dinv (b_l - W^T x_p),
+   trial state poses_trial [P][12] = exp(x_p) T, psi_trial [L][3] = psi + x_l, chi2 at the trial state, and the landmark share of the LM scale
+   sum x_l . (lambda x_l + b_l) (svs_ref_ba_optimize adds the pose share and 1e-3) */
+int svs_ref_ba_trial(int P, const double *poses, int L, const double *psi, int E, const svs_ba_edge *edges, int C,
+                     const svs_ba_constraint *cons, const svs_cam *cam, const svs_ba_params *prm, double lambda, const double *xp,
+                     double *poses_trial, double *psi_trial, double *chi2_trial, double *scale_l);
 
 /* ---- motion-only pose refinement: PoseOptimizer::calcFastMotionOnly, pose_optimizer.h:134-298 -------------- */
 typedef struct {

@@ -212,6 +212,22 @@ class SlamGraphOptimizer:
         self.ctx.check(self.ctx.lib.svs_ba_reduced_system(self.h, float(lam), H.ctypes.data, b.ctypes.data, chi2.ctypes.data))
         return H, b, float(chi2[0])
 
+    def schur_layout(self):
+        """(waves per workgroup, big LDS pool) of the next Schur / back-substitution launches (svs_ba_schur_layout)"""
+        nw, big = C.c_int32(), C.c_int32()
+        self.ctx.check(self.ctx.lib.svs_ba_schur_layout(self.h, C.byref(nw), C.byref(big)))
+        return nw.value, bool(big.value)
+
+    def trial(self, lam, xp):
+        """one LM trial from the pose step xp [P,6] (svs_ba_trial): trial poses [P,12], trial landmarks [L,3], trial chi2, landmark share of
+        the scale; the current state is left as it is"""
+        xp = np.ascontiguousarray(xp, np.float64).reshape(-1)
+        assert xp.size == 6 * self.P
+        poses, psi, chi2, scl = np.zeros((self.P, 12)), np.zeros((self.L, 3)), np.zeros(1), np.zeros(1)
+        self.ctx.check(self.ctx.lib.svs_ba_trial(self.h, float(lam), xp.ctypes.data, poses.ctypes.data, psi.ctypes.data, chi2.ctypes.data,
+                                                 scl.ctypes.data))
+        return poses, psi, float(chi2[0]), float(scl[0])
+
     def set_option(self, name, value):
         """experiment / test switches of this optimizer (svs_ba_set_option)"""
         self.ctx.check(self.ctx.lib.svs_ba_set_option(self.h, name.encode(), int(value)))

@@ -185,6 +185,8 @@ _SIGS = {
     "svs_ba_reset_state": [C.c_void_p, C.c_void_p, C.c_void_p],
     "svs_ba_reduced_system": [C.c_void_p, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p],
     "svs_ba_info": [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)],
+    "svs_ba_schur_layout": [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)],
+    "svs_ba_trial": [C.c_void_p, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
     "svs_ba_order_info": [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_void_p],
     "svs_ba_set_timing": [C.c_void_p, C.c_int],
     "svs_ba_set_option": [C.c_void_p, C.c_char_p, C.c_int],
@@ -202,7 +204,7 @@ _SIGS = {
     "svs_ba_graph_stats": [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)],
 }
 EXPORTS = sorted(list(_SIGS) + ["svs_ctx_stream", "svs_last_error", "svs_api_version", "svs_pose_opt_params_default"])
-API_VERSION = 7      # SVS_API_VERSION of include/scavislam_hip.h this binding was written against
+API_VERSION = 8      # SVS_API_VERSION of include/scavislam_hip.h this binding was written against
 
 
 def load():

@@ -63,6 +63,12 @@ __global__ void ba_lm_kernel(BaDev B, int it) {
   ba_lm_decide(B, it);
 }
 
+// trial poses exp(x_p) T from a given x_p (svs_ba_trial): what every solve's epilogue does after its own solution
+__global__ void ba_trial_poses_kernel(BaDev B) {
+  const int p = blockIdx.x * blockDim.x + threadIdx.x;
+  if (p < B.P) d_se3_exp_mul(B.x + 6 * (size_t)p, B.poses + 12 * (size_t)p, B.poses_trial + 12 * (size_t)p);
+}
+
 }  // namespace
 
 // Small host-side worker pool for the per-call marshalling (svs_ba_set_problem): the phases are passes over the 64-byte
@@ -236,6 +242,12 @@ static BaDev make_dev(const svs_ba *ba, double lambda, int cur = -1, double *ctl
   B.wide_split = 16;
   return B;
 }
+// layout of the Schur and back-substitution launches: waves per workgroup (the one svs_ba_set_problem laid the chunks out for, else pick_nw) and, at
+// four waves, the LDS pool (big: one workgroup per CU, WIN_BIG poses; small: two per CU, WIN poses).  Five to eight waves always take the big pool.
+static int schur_nw(const svs_ba *ba) {
+  return (ba->nw_sched > 0 && ba->opt.nw < 4 && !ba->opt.nw4) ? ba->nw_sched : pick_nw(ba->n_chunks, ba->ctx->n_cu, ba->opt);
+}
+static bool schur_big_pool(const svs_ba *ba, int nw) { return nw != 4 || div_up(ba->n_chunks, nw) <= ba->ctx->n_cu; }
 
 // Small uploads go through one pinned staging area: an asynchronous copy from pageable memory makes the runtime wait for
 // the stream (it has to reuse its own bounce buffer), which would serialise the host behind the big edge DMA.  The area is
@@ -921,7 +933,7 @@ static int launch_reduce(svs_ba *ba, double lambda, int cur = -1, double *ctl = 
   if (timeline) SVS_HIP(ctx, hipMalloc(&B.dbg, sizeof(long long) * DBG_W * (size_t)B.n_chunks));
   int dbg_nw = 1;
   if (B.n_chunks > 0) {
-    const int nw = (ba->nw_sched > 0 && ba->opt.nw < 4 && !ba->opt.nw4) ? ba->nw_sched : pick_nw(B.n_chunks, ctx->n_cu, ba->opt);
+    const int nw = schur_nw(ba);
     const int xc = B.fuse_cons ? B.C : 0;      // pose-pose constraints in extra workgroups of the same launch
     const int n_wg = div_up(B.n_chunks, nw);
     dbg_nw = nw;
@@ -931,7 +943,7 @@ static int launch_reduce(svs_ba *ba, double lambda, int cur = -1, double *ctl = 
       case 7: hipLaunchKernelGGL((ba_landmark_kernel<0, 7, 2>), dim3(n_wg + xc), dim3(448), 0, ctx->stream, B); break;
       case 8: hipLaunchKernelGGL((ba_landmark_kernel<0, 8, 2>), dim3(n_wg + xc), dim3(512), 0, ctx->stream, B); break;
       default:
-        if (n_wg <= ctx->n_cu) hipLaunchKernelGGL((ba_landmark_kernel<0, 4, 2>), dim3(n_wg + xc), dim3(256), 0, ctx->stream, B);      // one workgroup per CU: LDS to spare
+        if (schur_big_pool(ba, 4)) hipLaunchKernelGGL((ba_landmark_kernel<0, 4, 2>), dim3(n_wg + xc), dim3(256), 0, ctx->stream, B);      // one workgroup per CU: LDS to spare
         else hipLaunchKernelGGL((ba_landmark_kernel<0, 4, 1>), dim3(n_wg + xc), dim3(256), 0, ctx->stream, B);                         // two per CU must fit
         break;
     }
@@ -986,6 +998,28 @@ static int launch_reduce(svs_ba *ba, double lambda, int cur = -1, double *ctl = 
   return SVS_OK;
 }
 
+// back-substitution x_l = D^-1 (b_l - W^T x_p), trial landmarks, trial chi2 and the landmark share of the scale (MODE 1 kernels), behind the
+// constraints' trial chi2 (stand-alone kernel or, with fused constraints, extra workgroups of this launch)
+static int launch_backsub(svs_ba *ba, const BaDev &B) {
+  svs_ctx *ctx = ba->ctx;
+  if (B.n_chunks > 0) {
+    // the same waves per workgroup as the Schur pass: one workgroup per CU where that is possible (403 four-wave workgroups left some CUs
+    // with two and others with one: 19.6 us; 231 seven-wave ones: 17.0 us at 50 KF / 20k)
+    const int nw = schur_nw(ba);
+    const int xc = B.fuse_cons ? B.C : 0;
+    switch (nw) {
+      case 5: hipLaunchKernelGGL((ba_landmark_kernel<1, 5>), dim3(div_up(B.n_chunks, 5) + xc), dim3(320), 0, ctx->stream, B); break;
+      case 6: hipLaunchKernelGGL((ba_landmark_kernel<1, 6>), dim3(div_up(B.n_chunks, 6) + xc), dim3(384), 0, ctx->stream, B); break;
+      case 7: hipLaunchKernelGGL((ba_landmark_kernel<1, 7>), dim3(div_up(B.n_chunks, 7) + xc), dim3(448), 0, ctx->stream, B); break;
+      case 8: hipLaunchKernelGGL((ba_landmark_kernel<1, 8>), dim3(div_up(B.n_chunks, 8) + xc), dim3(512), 0, ctx->stream, B); break;
+      default: hipLaunchKernelGGL((ba_landmark_kernel<1, 4>), dim3(div_up(B.n_chunks, 4) + xc), dim3(256), 0, ctx->stream, B); break;
+    }
+    SVS_LAUNCH_CHECK(ctx);
+  }
+  if (B.n_wide > 0) { hipLaunchKernelGGL(ba_wide_landmark_kernel<1>, dim3(B.n_wide), dim3(WIDE_THREADS), 0, ctx->stream, B); SVS_LAUNCH_CHECK(ctx); }
+  return SVS_OK;
+}
+
 extern "C" int svs_ba_reduced_system(svs_ba *ba, double lambda, double *h_Hred, double *h_bred, double *h_chi2) {
   svs_ctx *ctx = ba ? ba->ctx : nullptr;
   SVS_REQUIRE(ctx, ba && ba->d_red && ba->problem_valid);
@@ -1006,6 +1040,53 @@ extern "C" int svs_ba_reduced_system(svs_ba *ba, double lambda, double *h_Hred, 
   SVS_HIP(ctx, hipStreamSynchronize(ctx->stream));
   if (h_chi2) { double t = 0; for (int i = 0; i < SC_SLOTS; ++i) t += chi_slots[i]; *h_chi2 = t; }
   (void)hipFree(d_full); (void)hipFree(d_b);
+  return SVS_OK;
+}
+
+extern "C" int svs_ba_schur_layout(svs_ba *ba, int32_t *waves_per_workgroup, int32_t *big_pool) {
+  svs_ctx *ctx = ba ? ba->ctx : nullptr;
+  SVS_REQUIRE(ctx, ba && ba->problem_valid);
+  const int nw = schur_nw(ba);
+  if (waves_per_workgroup) *waves_per_workgroup = nw;
+  if (big_pool) *big_pool = schur_big_pool(ba, nw) ? 1 : 0;
+  return SVS_OK;
+}
+
+// One LM trial from a caller's x_p: the Schur pass at lambda (as svs_ba_reduced_system), the trial poses exp(x_p) T, then what enqueue_trial launches
+// behind the solve.  The current state stays as it was: the trial buffers get the current state back, d_x is not touched.
+extern "C" int svs_ba_trial(svs_ba *ba, double lambda, const double *h_xp, double *h_poses_trial, double *h_psi_trial, double *h_chi2_trial,
+                            double *h_scale_l) {
+  svs_ctx *ctx = ba ? ba->ctx : nullptr;
+  SVS_REQUIRE(ctx, ba && ba->d_red && ba->problem_valid && h_xp);
+  SVS_DEVICE(ctx);
+  const int P = ba->P, L = ba->L, cur = ba->cur;
+  // landmarks without edges keep their value in the trial buffer (the MODE 1 kernels only write the others)
+  if (L) SVS_HIP(ctx, hipMemcpyAsync(ba->d_psi[1 - cur], ba->d_psi[cur], sizeof(double) * 3 * (size_t)L, hipMemcpyDeviceToDevice, ctx->stream));
+  int rc = launch_reduce(ba, lambda);
+  if (rc) return rc;
+  BaDev B = make_dev(ba, lambda);
+  struct DevBuf { double *p = nullptr; ~DevBuf() { if (p) (void)hipFree(p); } } xp;      // x_p of the caller (d_x stays as the last solve left it)
+  SVS_HIP(ctx, hipMalloc(&xp.p, sizeof(double) * 6 * (size_t)P));
+  B.x = xp.p;
+  SVS_HIP(ctx, hipMemcpyAsync(xp.p, h_xp, sizeof(double) * 6 * (size_t)P, hipMemcpyHostToDevice, ctx->stream));
+  if (B.n_chunks == 0) SVS_HIP(ctx, hipMemsetAsync(ba->d_scal, 0, sizeof(double) * SC_N, ctx->stream));      // else zeroed by the Schur kernel
+  hipLaunchKernelGGL(ba_trial_poses_kernel, dim3(div_up(P, 64)), dim3(64), 0, ctx->stream, B);
+  SVS_LAUNCH_CHECK(ctx);
+  if (B.C > 0 && !B.fuse_cons) { hipLaunchKernelGGL(ba_constraint_kernel<1>, dim3(B.C), dim3(64), 0, ctx->stream, B); SVS_LAUNCH_CHECK(ctx); }
+  rc = launch_backsub(ba, B);
+  if (rc) return rc;
+  double scal[SC_N] = {};
+  if (h_poses_trial) SVS_HIP(ctx, hipMemcpyAsync(h_poses_trial, B.poses_trial, sizeof(double) * 12 * (size_t)P, hipMemcpyDeviceToHost, ctx->stream));
+  if (h_psi_trial && L) SVS_HIP(ctx, hipMemcpyAsync(h_psi_trial, B.psi_trial, sizeof(double) * 3 * (size_t)L, hipMemcpyDeviceToHost, ctx->stream));
+  SVS_HIP(ctx, hipMemcpyAsync(scal, ba->d_scal, sizeof(scal), hipMemcpyDeviceToHost, ctx->stream));
+  // the trial buffers back to the current state
+  SVS_HIP(ctx, hipMemcpyAsync(B.poses_trial, B.poses, sizeof(double) * 12 * (size_t)P, hipMemcpyDeviceToDevice, ctx->stream));
+  if (L) SVS_HIP(ctx, hipMemcpyAsync(B.psi_trial, B.psi, sizeof(double) * 3 * (size_t)L, hipMemcpyDeviceToDevice, ctx->stream));
+  SVS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  double chi = 0, scl = 0;
+  for (int i = 0; i < SC_SLOTS; ++i) { chi += scal[SC_CHI + i]; scl += scal[SC_SCL + i]; }      // folded in slot order, as ba_lm_decide does
+  if (h_chi2_trial) *h_chi2_trial = chi;
+  if (h_scale_l) *h_scale_l = scl;
   return SVS_OK;
 }
 
@@ -1077,21 +1158,8 @@ static int enqueue_trial(svs_ba *ba, double lambda, int cur, double *ctl, hipEve
   if (ba->timing) SVS_HIP(ctx, hipEventRecord(ev[3], ctx->stream));
   if (B.C > 0 && !B.fuse_cons) { hipLaunchKernelGGL(ba_constraint_kernel<1>, dim3(B.C), dim3(64), 0, ctx->stream, B); SVS_LAUNCH_CHECK(ctx); }
   if (ba->timing) SVS_HIP(ctx, hipEventRecord(ev[5], ctx->stream));
-  if (B.n_chunks > 0) {
-    // the same waves per workgroup as the Schur pass: one workgroup per CU where that is possible (403 four-wave workgroups left some CUs
-    // with two and others with one: 19.6 us; 231 seven-wave ones: 17.0 us at 50 KF / 20k)
-    const int nw = (ba->nw_sched > 0 && ba->opt.nw < 4 && !ba->opt.nw4) ? ba->nw_sched : pick_nw(B.n_chunks, ctx->n_cu, ba->opt);
-    const int xc = B.fuse_cons ? B.C : 0;
-    switch (nw) {
-      case 5: hipLaunchKernelGGL((ba_landmark_kernel<1, 5>), dim3(div_up(B.n_chunks, 5) + xc), dim3(320), 0, ctx->stream, B); break;
-      case 6: hipLaunchKernelGGL((ba_landmark_kernel<1, 6>), dim3(div_up(B.n_chunks, 6) + xc), dim3(384), 0, ctx->stream, B); break;
-      case 7: hipLaunchKernelGGL((ba_landmark_kernel<1, 7>), dim3(div_up(B.n_chunks, 7) + xc), dim3(448), 0, ctx->stream, B); break;
-      case 8: hipLaunchKernelGGL((ba_landmark_kernel<1, 8>), dim3(div_up(B.n_chunks, 8) + xc), dim3(512), 0, ctx->stream, B); break;
-      default: hipLaunchKernelGGL((ba_landmark_kernel<1, 4>), dim3(div_up(B.n_chunks, 4) + xc), dim3(256), 0, ctx->stream, B); break;
-    }
-    SVS_LAUNCH_CHECK(ctx);
-  }
-  if (B.n_wide > 0) { hipLaunchKernelGGL(ba_wide_landmark_kernel<1>, dim3(B.n_wide), dim3(WIDE_THREADS), 0, ctx->stream, B); SVS_LAUNCH_CHECK(ctx); }
+  rc = launch_backsub(ba, B);
+  if (rc) return rc;
   if (ba->timing) SVS_HIP(ctx, hipEventRecord(ev[4], ctx->stream));
   if (allreduce) { rc = allreduce(ba->d_scal + SC_CHI, 2 * SC_SLOTS, user); if (rc) { ctx->err = "allreduce callback failed"; return SVS_ERR_INVALID; } }
   return SVS_OK;

@@ -108,9 +108,9 @@ def test_optimize_rejected_steps_and_termination(gpu_ctx):
 
 
 def test_optimize_full_size_properties(gpu_ctx):
-    """BASELINE size (50 KF / 20k landmarks, ~100k edges): too slow to diff against a Python model,
-    so check size-independent properties: (1) the solution of the reduced system satisfies the FULL
-    normal equations through the oracle's chi2 (cost decreases exactly as reported), (2) sharding the
+    """BASELINE size (50 KF / 20k landmarks, ~100k edges; the Schur pass runs seven waves per workgroup): (0) the reduced system
+    equals the C oracle's (O.ba_reduced_system) under the bar of test_reduced_system_matches_oracle, (1) the solution of the reduced
+    system satisfies the FULL normal equations through the oracle's chi2 (cost decreases exactly as reported), (2) sharding the
     landmarks over 2, 4 and 8 pseudo-ranks (8 = BASELINE configs[3]'s own shape: 313 chunks of 64 landmarks dealt
     to 8 shards) and summing the partial reduced systems reproduces the single-GPU system to 1e-10 (linearity of
     the Schur reduction over landmarks)."""
@@ -125,6 +125,10 @@ def test_optimize_full_size_properties(gpu_ctx):
     opt = SlamGraphOptimizer(ctx, stream)
     opt.copyDataToG2o(prob["poses"], prob["psi"], prob["edges"], prob["cons"], cam, prm)
     H, b, chi2 = opt.reduced_system(50.0)
+    H_ref, b_ref = O.ba_reduced_system(prob["poses"], prob["psi"], prob["edges"], prob["cons"], cam, prm, 50.0)
+    np.testing.assert_allclose(H, H_ref, rtol=0, atol=1e-10 * np.abs(H_ref).max())
+    np.testing.assert_allclose(b, b_ref, rtol=0, atol=1e-10 * np.abs(b_ref).max())
+    np.testing.assert_allclose(chi2, O.ba_chi2(prob["poses"], prob["psi"], prob["edges"], prob["cons"], cam, prm), rtol=1e-12)
     n = H.shape[0]
     for world in (2, 4, 8):
         Hs, bs, cs = np.zeros_like(H), np.zeros_like(b), 0.0
