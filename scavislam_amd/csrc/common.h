@@ -118,7 +118,7 @@ int svs_dense_track_cpu_sem_work(svs_ctx *ctx, const svs_dense_track_args *a, do
 int svs_pyr_down_u8_copy(svs_ctx *ctx, const uint8_t *d_src, int w, int h, int sstride, size_t s_bstride, uint8_t *d_dst, int dstride, size_t d_bstride,
                          uint8_t *d_copy, int cstride, size_t c_bstride, int batch);
 // internal (not exported through the header): svs_process_matched_points with the record count of the new-feature lists per stream, on the device
-// the work a stream's refinement workgroup does after its LM loop when the front end fuses the stages (dense.hip: motion_only_fused_kernel<true>)
+// the work a stream's refinement workgroup does after its LM loop when the front end fuses the stages (motion.hip: motion_only_fused_kernel<true>)
 struct svs_mo_tail {
   const svs_candidate_point *pts; size_t pts_b; const int32_t *n_new; float mre; svs_gated_point *gated; size_t gated_b; svs_point_stats *ptstats;      // processMatchedPoints' gate
   const float *disp; int ds; size_t disp_b; svs_cam cams[3]; float *cloud[3]; size_t cloud_b[3];                                                     // computeDensePointCloudCpu, 3 levels
@@ -130,7 +130,7 @@ int svs_process_matched_points_dev(svs_ctx *ctx, const svs_match_result *d_resul
                                    size_t pts_bstride, const int32_t *d_n_new_records, const svs_cam *cam, const double *d_T, float max_reproj_error,
                                    svs_gated_point *d_gated, size_t gated_bstride, svs_point_stats *d_stats, int batch);
 
-// internal: the dense clouds of the three levels in one launch (dense.hip)
+// internal: the dense clouds of the three levels in one launch (motion.hip)
 int svs_pointcloud_cpu_sem_levels(svs_ctx *ctx, const float *d_disp, int disp_stride, size_t disp_bstride, const svs_cam *cams, const double *d_T, float *const *d_cloud,
                                   const size_t *cloud_bstride, int batch);
 

@@ -1,7 +1,7 @@
 // dense.hip -- dense (direct) SE3 tracking for gfx950.
-// Replaces DenseTracker::denseTrackingCpu / computeDensePointCloudCpu
-// (dense_tracking.cpp:222-423; the parity target, SURVEY.md section 0 last row).  The CUDA build's
-// full-resolution tracker (GpuTracker, denseTrackingGpu) lives in dense_full.hip.
+// Replaces DenseTracker::denseTrackingCpu (dense_tracking.cpp:222-391; the parity target, SURVEY.md section 0
+// last row).  The CUDA build's full-resolution tracker (GpuTracker, denseTrackingGpu) lives in dense_full.hip,
+// computeDensePointCloudCpu (the clouds this tracker reads) in motion.hip, the 6x6 LM step in lm6.h.
 //
 // MI355X-first design:
 //  * per-sample work is a gather (cloud, 4-tap bilinear of cur/dx/dy) + 27 accumulators; the
@@ -12,12 +12,9 @@
 //    workgroup per camera stream iterates chi2 / H,b / 6x6 solve / SE3 exp / accept-reject with
 //    LDS broadcasts, so a frame costs one launch instead of ~90 launch+sync+D2H round trips.
 #include "common.h"
+#include "lm6.h"
 #include "seqsum.h"
 #include <algorithm>
-
-#ifndef SVS_TRK_LAZY
-#define SVS_TRK_LAZY 1      // (0: build experiments only -- the tracker kernel of rounds 1-4, accept test on the f64 sums alone)
-#endif
 
 namespace {
 
@@ -264,140 +261,6 @@ __global__ void dense_finalize_kernel(const double *__restrict__ partials, int n
 }
 
 // ---- device-resident LM (whole denseTrackingCpu) ---------------------------------------------
-// 6x6 solve by Gaussian elimination with partial pivoting (stands in for Eigen's ldlt(), as in the oracle).  Fully unrolled
-// with compile-time indices: the row exchange is a chain of predicated swaps, so the augmented matrix lives in registers
-// (a dynamically indexed copy would sit in scratch memory, and this runs on one lane while the workgroup waits).
-__device__ void d_solve6(const double *A, const double *b, double *x) {
-  double M[6][7];
-#pragma unroll
-  for (int i = 0; i < 6; ++i) {
-#pragma unroll
-    for (int j = 0; j < 6; ++j) M[i][j] = A[i * 6 + j];
-    M[i][6] = b[i];
-  }
-#pragma unroll
-  for (int k = 0; k < 6; ++k) {
-    int p = k;
-    double best = fabs(M[k][k]);
-#pragma unroll
-    for (int i = k + 1; i < 6; ++i) { const double v = fabs(M[i][k]); if (v > best) { best = v; p = i; } }
-#pragma unroll
-    for (int i = k + 1; i < 6; ++i) {
-      const bool sw = p == i;
-#pragma unroll
-      for (int j = k; j < 7; ++j) { const double a = M[k][j], c = M[i][j]; M[k][j] = sw ? c : a; M[i][j] = sw ? a : c; }
-    }
-    const double piv = M[k][k];
-#pragma unroll
-    for (int i = k + 1; i < 6; ++i) {
-      const double f = M[i][k] / piv;
-#pragma unroll
-      for (int j = k; j < 7; ++j) M[i][j] -= f * M[k][j];
-    }
-  }
-#pragma unroll
-  for (int i = 5; i >= 0; --i) {
-    double s_ = M[i][6];
-#pragma unroll
-    for (int j = i + 1; j < 6; ++j) s_ -= M[i][j] * x[j];
-    x[i] = s_ / M[i][i];
-  }
-}
-__device__ void d_se3_exp_mul(const double *x, const double *T, double *Tn) {   // Tn = exp(x) * T
-  const double *w = x + 3;
-  double th2 = w[0] * w[0] + w[1] * w[1] + w[2] * w[2], th = sqrt(th2);
-  double W[9] = {0, -w[2], w[1], w[2], 0, -w[0], -w[1], w[0], 0}, W2[9], R[9], V[9];
-  for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) W2[3 * i + j] = W[3 * i] * W[j] + W[3 * i + 1] * W[3 + j] + W[3 * i + 2] * W[6 + j];
-  double a, b;
-  if (th < 1e-10) { a = 1.0 - th2 / 6.0; b = 0.5 - th2 / 24.0; } else { a = sin(th) / th; b = (1.0 - cos(th)) / th2; }
-  for (int i = 0; i < 9; ++i) R[i] = a * W[i] + b * W2[i];
-  R[0] += 1; R[4] += 1; R[8] += 1;
-  if (th < 1e-10) { for (int i = 0; i < 9; ++i) V[i] = R[i]; }
-  else {
-    double c = (1.0 - cos(th)) / th2, d = (th - sin(th)) / (th2 * th);
-    for (int i = 0; i < 9; ++i) V[i] = c * W[i] + d * W2[i];
-    V[0] += 1; V[4] += 1; V[8] += 1;
-  }
-  double t[3];
-  for (int i = 0; i < 3; ++i) t[i] = V[3 * i] * x[0] + V[3 * i + 1] * x[1] + V[3 * i + 2] * x[2];
-  for (int i = 0; i < 3; ++i) {
-    for (int j = 0; j < 4; ++j) Tn[4 * i + j] = R[3 * i] * T[j] + R[3 * i + 1] * T[4 + j] + R[3 * i + 2] * T[8 + j];
-    Tn[4 * i + 3] += t[i];
-  }
-}
-
-__device__ __forceinline__ double mo2_bcast(double v, int src_lane) {      // src_lane is a compile-time constant after unrolling
-  const int lo = __builtin_amdgcn_readlane(__double2loint(v), src_lane), hi = __builtin_amdgcn_readlane(__double2hiint(v), src_lane);
-  return __hiloint2double(hi, lo);
-}
-// A x = b for a symmetric positive definite 6x6 system on seven lanes of a wave: lane c < 6 holds column c of A in col[0..6), lane 6 holds b.
-// Gauss-Jordan, the multipliers of a step broadcast from the pivot column's lane; no pivoting (the reference's ldlt() pivots, which an SPD matrix
-// does not need).  Every lane returns x in x[0..6).
-__device__ __forceinline__ void wave_solve6(const double (&col)[6], double (&x)[6]) {
-  double a[6];
-#pragma unroll
-  for (int r = 0; r < 6; ++r) a[r] = col[r];
-#pragma unroll
-  for (int k = 0; k < 6; ++k) {
-    const double ip = 1.0 / mo2_bcast(a[k], k);
-    const double ak = a[k] * ip;               // row k of this lane's column, scaled
-#pragma unroll
-    for (int r = 0; r < 6; ++r) {
-      if (r == k) continue;
-      const double m = mo2_bcast(a[r], k);     // element (r, k) of the pivot column
-      a[r] -= m * ak;
-    }
-    a[k] = ak;
-  }
-#pragma unroll
-  for (int r = 0; r < 6; ++r) x[r] = mo2_bcast(a[r], 6);
-}
-// exp(x) * T with everything in registers (d_se3_exp_mul above is an out-of-line call on arrays in scratch memory)
-__device__ __forceinline__ void mo2_exp_mul(const double (&x)[6], const double (&T)[12], double (&Tn)[12]) {
-  const double w0 = x[3], w1 = x[4], w2 = x[5];
-  const double th2 = w0 * w0 + w1 * w1 + w2 * w2, th = sqrt(th2);
-  // a = sin(th) / th, b = c = (1 - cos th) / th^2, d = (th - sin th) / th^3.  An LM step rotates by far less than half a radian: there the three
-  // are even power series in th^2 (9 terms: remainder < 1e-22), no square root, no division, no libm call on the chain of the trial
-  double a, b, c, d;
-  if (th2 < 0.25) {
-    // Horner in th^2 with the coefficients 1 / (k + 1)! written out (a table would live in scratch memory)
-#define SVS_IF(k) (1.0 / k)
-    const double t = th2;
-    a = 1.0 - t * (SVS_IF(6.) - t * (SVS_IF(120.) - t * (SVS_IF(5040.) - t * (SVS_IF(362880.) - t * (SVS_IF(39916800.) - t * (SVS_IF(6227020800.) - t * (SVS_IF(1307674368000.) -
-        t * (SVS_IF(355687428096000.) - t * SVS_IF(121645100408832000.)))))))));
-    b = SVS_IF(2.) - t * (SVS_IF(24.) - t * (SVS_IF(720.) - t * (SVS_IF(40320.) - t * (SVS_IF(3628800.) - t * (SVS_IF(479001600.) - t * (SVS_IF(87178291200.) -
-        t * (SVS_IF(20922789888000.) - t * (SVS_IF(6402373705728000.) - t * SVS_IF(2432902008176640000.)))))))));
-    d = SVS_IF(6.) - t * (SVS_IF(120.) - t * (SVS_IF(5040.) - t * (SVS_IF(362880.) - t * (SVS_IF(39916800.) - t * (SVS_IF(6227020800.) - t * (SVS_IF(1307674368000.) -
-        t * (SVS_IF(355687428096000.) - t * (SVS_IF(121645100408832000.) - t * SVS_IF(51090942171709440000.)))))))));
-#undef SVS_IF
-    c = b;
-  } else {
-    double sn, cs;
-    sincos(th, &sn, &cs);
-    const double ith2 = 1.0 / th2;
-    a = sn / th; b = (1.0 - cs) * ith2; c = b; d = (th - sn) * ith2 / th;
-  }
-  // W = hat(w), W2 = W * W
-  const double W[9] = {0, -w2, w1, w2, 0, -w0, -w1, w0, 0};
-  double W2[9], R[9], V[9];
-#pragma unroll
-  for (int i = 0; i < 3; ++i)
-#pragma unroll
-    for (int j = 0; j < 3; ++j) W2[3 * i + j] = W[3 * i] * W[j] + W[3 * i + 1] * W[3 + j] + W[3 * i + 2] * W[6 + j];
-#pragma unroll
-  for (int i = 0; i < 9; ++i) { R[i] = a * W[i] + b * W2[i]; V[i] = c * W[i] + d * W2[i]; }
-  R[0] += 1; R[4] += 1; R[8] += 1;
-  V[0] += 1; V[4] += 1; V[8] += 1;
-#pragma unroll
-  for (int i = 0; i < 3; ++i) {
-    const double t = V[3 * i] * x[0] + V[3 * i + 1] * x[1] + V[3 * i + 2] * x[2];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) Tn[4 * i + j] = R[3 * i] * T[j] + R[3 * i + 1] * T[4 + j] + R[3 * i + 2] * T[8 + j];
-    Tn[4 * i + 3] += t;
-  }
-}
-
-
 struct TrackArgs {
   LevelArgs lv[3];
   size_t cloud_b[3], prev_b[3], f_b[3], c8_b[3];
@@ -405,21 +268,11 @@ struct TrackArgs {
   svs_dense_lm_record *rec; int rec_cap; int32_t *n_rec;      // optional accept / reject record of the loop
 };
 
-#ifndef SVS_TRK_THREADS
-#define SVS_TRK_THREADS 512
-#endif
-#ifndef SVS_TRK_UNROLL
-#define SVS_TRK_UNROLL 1
-#endif
-#ifndef SVS_TRK_MINW_BIG
-#define SVS_TRK_MINW_BIG 4      // waves per SIMD the big-batch instantiations are built for (4: 128 VGPRs, two 512-lane workgroups per CU)
-#endif
-#ifndef SVS_TRK_T_SCALAR
-#define SVS_TRK_T_SCALAR 1
-#endif
-constexpr int TRK_THREADS = SVS_TRK_THREADS;
-constexpr int TRK_MINW_BIG = SVS_TRK_MINW_BIG;
-constexpr int TRK_UNROLL = SVS_TRK_UNROLL;
+// tuning constants, as measured (profiles/r3_notes.md, r5_notes.md)
+constexpr int TRK_THREADS = 512;      // lanes per workgroup
+constexpr int TRK_MINW_BIG = 4;       // waves per SIMD the big-batch instantiations are built for (4: 128 VGPRs, two 512-lane workgroups per CU)
+constexpr int TRK_UNROLL = 1;         // samples per lane and trip of the sweep (2: the 128-register build spills 126 registers)
+constexpr bool TRK_T_SCALAR = true;   // the pose of a sweep in scalar registers instead of 24 vector registers
 
 template <bool JAC, bool U8SRC, int TM = 0, class LA = LevelArgs>
 __device__ __forceinline__ void track_pass(const LA &L, const double *T_in, double (*s_part)[NSUM + 1], double *s_out, const float *ip_lut,
@@ -429,7 +282,7 @@ __device__ __forceinline__ void track_pass(const LA &L, const double *T_in, doub
   double T[12];
 #pragma unroll
   for (int i = 0; i < 12; ++i)
-    T[i] = SVS_TRK_T_SCALAR ? __hiloint2double(__builtin_amdgcn_readfirstlane(__double2hiint(T_in[i])), __builtin_amdgcn_readfirstlane(__double2loint(T_in[i]))) : T_in[i];
+    T[i] = TRK_T_SCALAR ? __hiloint2double(__builtin_amdgcn_readfirstlane(__double2hiint(T_in[i])), __builtin_amdgcn_readfirstlane(__double2loint(T_in[i]))) : T_in[i];
   Acc a;
   a.zero();
   // TRK_UNROLL samples per lane per trip (independent gather chains in flight); the next trip's stored points and
@@ -501,7 +354,7 @@ __device__ __forceinline__ T *uni_ptr(T *p) {
   return (T *)(((unsigned long long)hi << 32) | lo);
 }
 template <bool U8SRC, int TM>
-__device__ __noinline__ void track_pass_call() {
+__device__ __forceinline__ void track_pass_from_lds() {      // a sweep with its operands out of g_pa, into scalar registers
   LevelArgsG L;
   L.cloud = (const SVS_AS1 float *)uni_ptr(g_pa.L.cloud); L.prev = (const SVS_AS1 uint8_t *)uni_ptr(g_pa.L.prev);
   L.cur = (const SVS_AS1 float *)uni_ptr(g_pa.L.cur); L.dx = (const SVS_AS1 float *)uni_ptr(g_pa.L.dx); L.dy = (const SVS_AS1 float *)uni_ptr(g_pa.L.dy);
@@ -512,6 +365,8 @@ __device__ __noinline__ void track_pass_call() {
   const int nwg = uni_i32(g_pa.nwg), first = uni_i32(g_pa.wg) * TRK_THREADS + (int)threadIdx.x;
   track_pass<true, U8SRC, TM, LevelArgsG>(L, g_pa.T, g_s_part, g_s_out, g_iplut, first, nwg, uni_ptr(g_pa.t_buf));
 }
+template <bool U8SRC, int TM>
+__device__ __noinline__ void track_pass_call() { track_pass_from_lds<U8SRC, TM>(); }
 
 // "trk_seq_chi2": the reference's `float chi2`, summed the way the reference sums it -- one f32 accumulator, samples in row-major order (dense_tracking.cpp:229-262,
 // 341-367).  Near convergence chi2 - new_chi2 is below the rounding noise of these 19 200-term sums, so the accept test of the last LM steps of a level is decided by
@@ -786,9 +641,112 @@ __device__ __forceinline__ NearSums shared_near_sums(const float *t_old, const f
 #if defined(__HIP_DEVICE_COMPILE__) && !defined(__gfx950__) && !defined(__gfx942__)
 #error "dense.hip: the relaxed-atomic + s_waitcnt vmcnt(0) hand-off is only valid on gfx950 / gfx942"
 #endif
-struct TrackMulti { double *part; unsigned *bar; int fail_off; double *bcast;
-                    const int *map; const unsigned char *nwg_of;
-                    float *terms; size_t terms_b; unsigned *seq_stats; int terms_only; int *work16; };      // work16 (optional, flat kernel): [batch] the stream's passes counted as 16 / 4 / 1 per sweep of level 0 / 1 / 2      // the float terms of the accepted and of the trial pass, [batch][2][terms_b] (null: accept test on the f64 sums alone); [0] exact sums formed, [1] fallbacks to the chain      // BAL only: workgroup -> (stream << 4 | part), workgroups per stream      // bcast [batch][16]: the pose after the coarsest level + a ready word (zeroed before the launch)      // [batch][2][nwg][32]; [batch] arrival counters + [batch] failure flags at bar + fail_off (zeroed before the launch)
+struct TrackMulti {
+  double *part;                                   // [batch][2][nwg][32] partial sums of the shared sweeps, by sweep parity (latency mode: [batch][2][nwg][64] flagged words)
+  unsigned *bar; int fail_off;                    // [batch] arrival counters + [batch] failure flags at bar + fail_off (zeroed before the launch)
+  double *bcast;                                  // [batch][16]: the pose after the coarsest level + a ready word (zeroed before the launch)
+  const int *map; const unsigned char *nwg_of;    // BAL only: workgroup -> (stream << 4 | part), workgroups per stream
+  float *terms; size_t terms_b;                   // the float terms of the accepted and of the trial pass, [batch][2][terms_b] (null: accept test on the f64 sums alone)
+  unsigned *seq_stats;                            // [0] exact sums formed, [1] fallbacks to the chain
+  int terms_only;                                 // kernel A/B: the stores of the terms without the sums
+  int *work16;                                    // (optional, flat kernel): [batch] the stream's passes counted as 16 / 4 / 1 per sweep of level 0 / 1 / 2
+};
+
+// ---- the LM step, written once: both tracker kernels below (the round-5 kernel with its sweep as a call, the flat kernel of big batches) inline these ----------------
+// the operands of a stream's sweeps of one level: the level's cloud and images at the stream's batch offsets
+template <bool U8SRC>
+__device__ __forceinline__ LevelArgs stream_level(const TrackArgs &A, int level, int slot) {
+  LevelArgs L = A.lv[level];
+  L.cloud += slot * A.cloud_b[level]; L.prev += slot * A.prev_b[level];
+  if (U8SRC) L.cur8 += slot * A.c8_b[level];
+  else { L.cur += slot * A.f_b[level]; L.dx += slot * A.f_b[level]; L.dy += slot * A.f_b[level]; }
+  return L;
+}
+// the solve of an iteration, on seven lanes of wave 0 (called with threadIdx.x < 64): H.ldlt().solve(-Jres), undamped (dense_tracking.cpp:332) + exp(x) * T.
+// All four in LDS: sH = H (packed upper by column) and b of the accepted pass, sT = the accepted pose -> sTn = the trial pose, sx = the step
+__device__ __forceinline__ void track_solve(const double (&sH)[27], const double (&sT)[12], double (&sTn)[12], double (&sx)[6]) {
+  const int lane = threadIdx.x;
+  double col[6], x[6], Tc[12], Tn[12];
+#pragma unroll
+  for (int r = 0; r < 6; ++r) {
+    const int lo = r < lane ? r : lane, hi = r < lane ? lane : r;      // packed upper by column: (lo, hi) at hi (hi + 1) / 2 + lo
+    col[r] = lane < 6 ? sH[hi * (hi + 1) / 2 + lo] : (lane == 6 ? -sH[21 + r] : (r == 0 ? 1.0 : 0.0));
+  }
+  wave_solve6(col, x);
+#pragma unroll
+  for (int i = 0; i < 12; ++i) Tc[i] = sT[i];
+  mo2_exp_mul(x, Tc, Tn);
+  if (lane < 12) {
+    double v = Tn[0];
+#pragma unroll
+    for (int i = 1; i < 12; ++i) v = lane == i ? Tn[i] : v;
+    sTn[lane] = v;
+  }
+  if (lane < 6) {
+    double v = x[0];
+#pragma unroll
+    for (int i = 1; i < 6; ++i) v = lane == i ? x[i] : v;
+    sx[lane] = v;
+  }
+}
+// g_s_out[0..NSUM] <- the sums of all nwg workgroups of a stream, added in workgroup order.  buf: the [nwg][32] partials of this sweep's parity; sweep: the sweeps the
+// stream has shared so far (target of its arrival counter); s_failed (LDS): a sibling never arrived.  Write-through 8-byte words + one arrival counter (relaxed, agent
+// scope) + vmcnt(0): no fence that would write an XCD's whole L2 back -- valid on gfx950 / gfx942 only, see the #error above
+__device__ __forceinline__ void sum_workgroups(const TrackMulti &G, int slot, double *buf, int wg, int nwg, int &sweep, bool &s_failed) {
+  if (threadIdx.x <= NSUM) __hip_atomic_store(buf + wg * 32 + threadIdx.x, g_s_out[threadIdx.x], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();
+  ++sweep;
+  if (threadIdx.x == 0) {
+    __hip_atomic_fetch_add(G.bar + slot, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const unsigned target = (unsigned)sweep * (unsigned)nwg;
+    long spin = 0;
+    for (; spin < (1l << 24) && __hip_atomic_load(G.bar + slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < target; ++spin) __builtin_amdgcn_s_sleep(1);
+    // a sibling workgroup never arrived (they are not all resident: the device is shared with other work).  Summing what is
+    // there would let the replicated LM bookkeeping diverge silently: raise the stream's failure flag instead -- every
+    // workgroup sees it at its next barrier at the latest, the pose is left as it came in and passes_out reports -1.
+    if (spin >= (1l << 24)) __hip_atomic_store(G.bar + G.fail_off + slot, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    s_failed = __hip_atomic_load(G.bar + G.fail_off + slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0;
+  }
+  __syncthreads();
+  if (threadIdx.x <= NSUM) {
+    double acc = 0;
+    for (int w = 0; w < nwg; ++w) acc += __hip_atomic_load(buf + w * 32 + threadIdx.x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    g_s_out[threadIdx.x] = acc;
+  }
+  __syncthreads();
+}
+// The accept test of a trial: S_old / S_new = the f64 sums of the float terms of the accepted / the trial pass (nv_*: samples that contributed one), tb0 = the stream's two
+// term buffers (null: none; the accepted pass's is number cur, the trial's the other one), chi2 = the accepted pass's chi2 as the loop carries it.  The reference compares two float sums of n terms each:
+// |sum_float - sum_exact| <= ((1 + 2^-24)^(n - 1) - 1) sum_exact.  Outside that band the f64 sums decide as the float sums would; inside it (a near-tie) the float sums
+// are formed, bit for bit (exact_seq_sum_f32): the trial's, and the accepted pass's unless the loop carries it (seq_old, seq_old_ok).  counted: the near-tie takes part
+// in the stream's count of such events (n_decisions, n_old_sums: what the workgroups that share the sums wait for, shared_near_sums).  failed: a sibling never published
+struct TrkVerdict { bool accept, failed; float chi2, new_chi2; };
+template <bool MULTI>
+__device__ __forceinline__ TrkVerdict track_accept(const TrackMulti &G, int slot, double S_old, double S_new, int nv_old, int nv_new, const float *tb0, int cur,
+                                                   int n_lvl, bool counted, int wg, int nwg, float chi2, float &seq_old, bool &seq_old_ok,
+                                                   unsigned &n_decisions, unsigned &n_old_sums, unsigned &n_exact) {
+  TrkVerdict V{false, false, chi2, 0.f};
+  const double gam = 1.0001 * (double)max(nv_old, nv_new) * 5.9604644775390625e-08 + 1e-12;
+  const bool near = tb0 && !G.terms_only && !(fabs(S_old - S_new) > gam * (S_old + S_new));      // (terms_only: kernel A/B -- the stores without the sums)
+  if (near) {
+    if (counted) { ++n_decisions; if (!seq_old_ok) ++n_old_sums; }
+    const NearSums ns = shared_near_sums<MULTI>(tb0 + (size_t)cur * G.terms_b, tb0 + (size_t)(cur ^ 1) * G.terms_b, n_lvl, wg, nwg, !seq_old_ok, seq_old, n_decisions, n_old_sums,
+                                                MULTI ? G.bcast + (size_t)slot * 16 : nullptr, MULTI ? G.bar + G.fail_off + slot : nullptr, n_exact);
+    if (ns.failed) { V.failed = true; return V; }
+    seq_old = ns.seq_old;
+    seq_old_ok = true;
+    V.chi2 = seq_old; V.new_chi2 = ns.seq_new;
+    V.accept = (double)V.chi2 - (double)V.new_chi2 > 0;
+    if (V.accept) seq_old = ns.seq_new;
+  } else {
+    V.new_chi2 = (float)S_new;
+    V.accept = S_old > S_new;
+    if (V.accept) seq_old_ok = false;
+  }
+  return V;
+}
+
 // MINW = minimum waves per SIMD the register allocation must allow: 2 (<= 256 VGPRs; the kernel takes 147: one 8-wave
 // workgroup per CU) when there is at most one stream per CU, 4 (<= 128 VGPRs, a few spills, two workgroups per CU) for
 // bigger batches, where the second resident workgroup hides the first one's dependent chains: 0.55 -> 0.45 ms per 256 streams.
@@ -808,11 +766,8 @@ __global__ __launch_bounds__(TRK_THREADS, MINW) void dense_track_cpu_sem_kernel(
   float (&s_iplut)[256] = g_iplut;
   __shared__ double s_T[12], s_Tn[12], s_x[6], s_H[27], s_Tj[3][12];
   __shared__ bool s_failed;
-  if (threadIdx.x == 0) { s_failed = false; if (!SEQ && SVS_TRK_LAZY) g_seq_sh.fell_back = 0; }
-#ifdef SVS_SCRATCH_PROBE                 // (build experiment: does the SIZE of a kernel's scratch allocation cost anything when nothing touches it?)
-  if (passes_out == reinterpret_cast<int *>(1)) { volatile int big[SVS_SCRATCH_PROBE]; for (int i = 0; i < SVS_SCRATCH_PROBE; ++i) big[i] = i; T_io[0] = big[threadIdx.x % SVS_SCRATCH_PROBE]; }
-#endif
-  constexpr int TM = SEQ ? 1 : (SVS_TRK_LAZY ? (MULTI ? 2 : 1) : 0);      // the terms of a pass: plain stores, or past the caches when sibling workgroups read them
+  if (threadIdx.x == 0) { s_failed = false; if (!SEQ) g_seq_sh.fell_back = 0; }
+  constexpr int TM = SEQ ? 1 : (MULTI ? 2 : 1);      // the terms of a pass: plain stores, or past the caches when sibling workgroups read them
   unsigned n_exact = 0, n_decisions = 0, n_old_sums = 0;      // exact float sums formed by this workgroup; near-ties of this stream so far / those of them that needed the accepted pass's sum as well (shared_near_sums)
   const int slot = BAL ? (bal_entry >> 4) : (MULTI ? blockIdx.y : blockIdx.x), wg = BAL ? (bal_entry & 15) : (MULTI ? blockIdx.x : 0);
   const int nwg = !MULTI ? 1 : (BAL ? (int)G.nwg_of[slot] : (int)gridDim.x);
@@ -857,30 +812,7 @@ __global__ __launch_bounds__(TRK_THREADS, MINW) void dense_track_cpu_sem_kernel(
       }
       return;
     }
-    // write-through 8-byte words + one arrival counter (relaxed, agent scope): no fence that would write an XCD's whole L2 back
-    double *buf = G.part + ((size_t)slot * 2 + (sweep & 1)) * (BAL ? 4 : nwg) * 32;
-    if (threadIdx.x <= NSUM) __hip_atomic_store(buf + wg * 32 + threadIdx.x, s_out[threadIdx.x], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    ++sweep;
-    if (threadIdx.x == 0) {
-      __hip_atomic_fetch_add(G.bar + slot, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      const unsigned target = (unsigned)sweep * (unsigned)nwg;
-      long spin = 0;
-      for (; spin < (1l << 24) && __hip_atomic_load(G.bar + slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < target; ++spin) __builtin_amdgcn_s_sleep(1);
-      // a sibling workgroup never arrived (they are not all resident: the device is shared with other work).  Summing what is
-      // there would let the replicated LM bookkeeping diverge silently: raise the stream's failure flag instead -- every
-      // workgroup sees it at its next barrier at the latest, the pose is left as it came in and passes_out reports -1.
-      if (spin >= (1l << 24)) __hip_atomic_store(G.bar + G.fail_off + slot, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      s_failed = __hip_atomic_load(G.bar + G.fail_off + slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0;
-    }
-    __syncthreads();
-    if (threadIdx.x <= NSUM) {
-      double acc = 0;
-      for (int w = 0; w < nwg; ++w) acc += __hip_atomic_load(buf + w * 32 + threadIdx.x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      s_out[threadIdx.x] = acc;
-    }
-    __syncthreads();
+    sum_workgroups(G, slot, G.part + ((size_t)slot * 2 + (sweep & 1)) * 4 * 32, wg, nwg, sweep, s_failed);      // (BAL: up to four workgroups per stream)
   };
   if (threadIdx.x < 12) s_T[threadIdx.x] = T_io[(size_t)slot * 12 + threadIdx.x];
   for (int i = threadIdx.x; i < 256; i += TRK_THREADS) s_iplut[i] = (float)((1. / 255.) * i);
@@ -911,10 +843,7 @@ __global__ __launch_bounds__(TRK_THREADS, MINW) void dense_track_cpu_sem_kernel(
       continue;
     }
     const int lnwg = solo ? 1 : nwg;
-    LevelArgs L = A.lv[level];
-    L.cloud += slot * A.cloud_b[level]; L.prev += slot * A.prev_b[level];
-    if (U8SRC) L.cur8 += slot * A.c8_b[level];
-    else { L.cur += slot * A.f_b[level]; L.dx += slot * A.f_b[level]; L.dy += slot * A.f_b[level]; }
+    const LevelArgs L = stream_level<U8SRC>(A, level, slot);
     const int n_lvl = (L.cam.w / 4) * (L.cam.h / 4);
     // the operands of this level's sweeps (track_pass_call): the level, which workgroups share it; pose and term buffer follow before each sweep
     __syncthreads();
@@ -954,31 +883,7 @@ __global__ __launch_bounds__(TRK_THREADS, MINW) void dense_track_cpu_sem_kernel(
     bool stop = false;
     for (int it = 0; it < 15 && !stop; ++it) {
       if (threadIdx.x >= 64 && threadIdx.x < 76) s_Tj[level][threadIdx.x - 64] = s_T[threadIdx.x - 64];   // the reference's H,b pass of this iteration ran at s_T
-      if (threadIdx.x < 64) {                        // H.ldlt().solve(-Jres): undamped (dense_tracking.cpp:332) -- on seven lanes of wave 0
-        const int lane = threadIdx.x;
-        double col[6], x[6], Tc[12], Tn[12];
-#pragma unroll
-        for (int r = 0; r < 6; ++r) {
-          const int lo = r < lane ? r : lane, hi = r < lane ? lane : r;      // packed upper by column: (lo, hi) at hi (hi + 1) / 2 + lo
-          col[r] = lane < 6 ? s_H[hi * (hi + 1) / 2 + lo] : (lane == 6 ? -s_H[21 + r] : (r == 0 ? 1.0 : 0.0));
-        }
-        wave_solve6(col, x);
-#pragma unroll
-        for (int i = 0; i < 12; ++i) Tc[i] = s_T[i];
-        mo2_exp_mul(x, Tc, Tn);
-        if (lane < 12) {
-          double v = Tn[0];
-#pragma unroll
-          for (int i = 1; i < 12; ++i) v = lane == i ? Tn[i] : v;
-          s_Tn[lane] = v;
-        }
-        if (lane < 6) {
-          double v = x[0];
-#pragma unroll
-          for (int i = 1; i < 6; ++i) v = lane == i ? x[i] : v;
-          s_x[lane] = v;
-        }
-      }
+      if (threadIdx.x < 64) track_solve(s_H, s_T, s_Tn, s_x);
       __syncthreads();
       sweep_at(s_Tn, tb[cur ^ 1]);      // new_chi2 (:335-367) + H,b for the next iteration
       if (!solo) all_workgroups();
@@ -992,29 +897,11 @@ __global__ __launch_bounds__(TRK_THREADS, MINW) void dense_track_cpu_sem_kernel(
         new_chi2 = seq_chi2_f32(tb[0], n_lvl);
         accept = (double)chi2 - (double)new_chi2 > 0;
       } else {
-        // the reference compares two float sums of n terms each: |sum_float - sum_exact| <= ((1 + 2^-24)^(n - 1) - 1) sum_exact.  Outside that band the f64 sums
-        // decide as the float sums would; inside it the float sums are formed, bit for bit (exact_seq_sum_f32)
-        const double gam = 1.0001 * (double)max(nv_old, nv_new) * 5.9604644775390625e-08 + 1e-12;
-        const bool near = SVS_TRK_LAZY && tb[0] && !G.terms_only && !(fabs(S_old - S_new) > gam * (S_old + S_new));      // (terms_only: kernel A/B -- the stores without the sums)
-        if (near) {
-          float seq_new = 0.f;
-          {
-            const bool shared = MULTI && !solo;      // (the coarsest level of a shared stream is run by its leader alone: its near-ties are not counted, the siblings never see them)
-            if (shared) { ++n_decisions; if (!seq_old_ok) ++n_old_sums; }
-            const NearSums ns = shared_near_sums<MULTI>(tb[cur], tb[cur ^ 1], n_lvl, shared ? wg : 0, shared ? nwg : 1, !seq_old_ok, seq_old, n_decisions, n_old_sums,
-                                                        MULTI ? G.bcast + (size_t)slot * 16 : nullptr, MULTI ? G.bar + G.fail_off + slot : nullptr, n_exact);
-            if (ns.failed) { s_failed = true; failed = true; break; }
-            seq_old = ns.seq_old; seq_new = ns.seq_new;
-          }
-          seq_old_ok = true;
-          chi2 = seq_old; new_chi2 = seq_new;
-          accept = (double)chi2 - (double)new_chi2 > 0;
-          if (accept) seq_old = seq_new;
-        } else {
-          new_chi2 = (float)S_new;
-          accept = S_old > S_new;
-          if (accept) seq_old_ok = false;
-        }
+        const bool shared = MULTI && !solo;      // (the coarsest level of a shared stream is run by its leader alone: its near-ties are not counted, the siblings never see them)
+        const TrkVerdict V = track_accept<MULTI>(G, slot, S_old, S_new, nv_old, nv_new, tb[0], cur, n_lvl, shared, shared ? wg : 0, shared ? nwg : 1,
+                                                 chi2, seq_old, seq_old_ok, n_decisions, n_old_sums, n_exact);
+        if (V.failed) { s_failed = true; failed = true; break; }
+        accept = V.accept; chi2 = V.chi2; new_chi2 = V.new_chi2;
         if (accept) { S_old = S_new; nv_old = nv_new; cur ^= 1; }
       }
       if (A.rec && wg == 0 && threadIdx.x == 0 && n_rec < A.rec_cap) A.rec[(size_t)slot * A.rec_cap + n_rec] = svs_dense_lm_record{level, accept ? 1 : 0, chi2, new_chi2};
@@ -1049,7 +936,7 @@ __global__ __launch_bounds__(TRK_THREADS, MINW) void dense_track_cpu_sem_kernel(
   if (A.T_jac && threadIdx.x < 36) A.T_jac[(size_t)slot * 36 + threadIdx.x] = s_Tj[threadIdx.x / 12][threadIdx.x % 12];
   if (threadIdx.x == 0 && G.seq_stats && n_exact) {
     atomicAdd(G.seq_stats, n_exact);
-    if (SVS_TRK_LAZY && g_seq_sh.fell_back) atomicAdd(G.seq_stats + 1, 1u);
+    if (g_seq_sh.fell_back) atomicAdd(G.seq_stats + 1, 1u);
   }
 }
 
@@ -1068,46 +955,10 @@ struct TrkState {
   unsigned n_exact;
 };
 __shared__ TrkState g_ts;
-template <bool U8SRC, int TM>
-__device__ __forceinline__ void track_pass_from_lds() {      // the body of track_pass_call, inlined: operands out of g_pa into scalar registers
-  LevelArgsG L;
-  L.cloud = (const SVS_AS1 float *)uni_ptr(g_pa.L.cloud); L.prev = (const SVS_AS1 uint8_t *)uni_ptr(g_pa.L.prev);
-  L.cur = (const SVS_AS1 float *)uni_ptr(g_pa.L.cur); L.dx = (const SVS_AS1 float *)uni_ptr(g_pa.L.dx); L.dy = (const SVS_AS1 float *)uni_ptr(g_pa.L.dy);
-  L.cur8 = (const SVS_AS1 uint8_t *)uni_ptr(g_pa.L.cur8);
-  L.pstride = uni_i32(g_pa.L.pstride); L.fstride = uni_i32(g_pa.L.fstride); L.c8stride = uni_i32(g_pa.L.c8stride);
-  L.cam.f = uni_f64(g_pa.L.cam.f); L.cam.cx = uni_f64(g_pa.L.cam.cx); L.cam.cy = uni_f64(g_pa.L.cam.cy); L.cam.b = 0;
-  L.cam.w = uni_i32(g_pa.L.cam.w); L.cam.h = uni_i32(g_pa.L.cam.h);
-  const int nwg = uni_i32(g_pa.nwg), first = uni_i32(g_pa.wg) * TRK_THREADS + (int)threadIdx.x;
-  track_pass<true, U8SRC, TM, LevelArgsG>(L, g_pa.T, g_s_part, g_s_out, g_iplut, first, nwg, uni_ptr(g_pa.t_buf));
-}
-// the solve of an iteration, on wave 0 (seven lanes): H.ldlt().solve(-Jres), undamped (dense_tracking.cpp:332) + exp(x) * T.  A function of its own, called by ONE
-// wave: its 70-odd live doubles are not part of the kernel's allocation, and whatever it saves on entry it saves for 64 lanes, not 512.
+// the solve of an iteration (track_solve) as a function of its own, called by ONE wave: its 70-odd live doubles are not part of the kernel's allocation, and whatever it
+// saves on entry it saves for 64 lanes, not 512.
 __shared__ double g_sT[12], g_sTn[12], g_sx[6], g_sH[27], g_sTj[3][12];
-__device__ __noinline__ void track_solve_call() {
-  const int lane = threadIdx.x;
-  double col[6], x[6], Tc[12], Tn[12];
-#pragma unroll
-  for (int r = 0; r < 6; ++r) {
-    const int lo = r < lane ? r : lane, hi = r < lane ? lane : r;      // packed upper by column: (lo, hi) at hi (hi + 1) / 2 + lo
-    col[r] = lane < 6 ? g_sH[hi * (hi + 1) / 2 + lo] : (lane == 6 ? -g_sH[21 + r] : (r == 0 ? 1.0 : 0.0));
-  }
-  wave_solve6(col, x);
-#pragma unroll
-  for (int i = 0; i < 12; ++i) Tc[i] = g_sT[i];
-  mo2_exp_mul(x, Tc, Tn);
-  if (lane < 12) {
-    double v = Tn[0];
-#pragma unroll
-    for (int i = 1; i < 12; ++i) v = lane == i ? Tn[i] : v;
-    g_sTn[lane] = v;
-  }
-  if (lane < 6) {
-    double v = x[0];
-#pragma unroll
-    for (int i = 1; i < 6; ++i) v = lane == i ? x[i] : v;
-    g_sx[lane] = v;
-  }
-}
+__device__ __noinline__ void track_solve_call() { track_solve(g_sH, g_sT, g_sTn, g_sx); }
 // ---- the tail of a big batch: the CONTINUATION launch ("trk_split", VERDICT round 5 item 2 iii) ------------------------------------------------------------------
 // All streams of a big batch are resident at once (two workgroups per CU) and the launch lasts as long as its longest stream: 16.75 level-0 sweeps in the bench's batch
 // against a mean of 8.7 -- and the last sweeps of a stream are the ones whose accept test needs the exact float sums, one after the other on the critical path.  Predicting
@@ -1130,18 +981,12 @@ constexpr int CONT_MAX_NWG = 8;
 template <bool U8SRC, bool MULTI>
 __device__ __forceinline__ void track_batch_stream(const TrackArgs &A, double *__restrict__ T_io, int *__restrict__ passes_out, const TrackMulti &G, const TrackCont &C,
                                                    const int slot, const int wg, const int nwg) {
-  constexpr int TM = SVS_TRK_LAZY ? (MULTI ? 2 : 1) : 0;
+  constexpr int TM = MULTI ? 2 : 1;
   const int tid = threadIdx.x;
   __shared__ bool s_failed;
   float *const tb0 = G.terms ? G.terms + (size_t)slot * 2 * G.terms_b : nullptr;
   // level set-up (one lane): the operands of the level's sweeps
-  auto set_level = [&](int level) {
-    LevelArgs L = A.lv[level];
-    L.cloud += slot * A.cloud_b[level]; L.prev += slot * A.prev_b[level];
-    if (U8SRC) L.cur8 += slot * A.c8_b[level];
-    else { L.cur += slot * A.f_b[level]; L.dx += slot * A.f_b[level]; L.dy += slot * A.f_b[level]; }
-    g_pa.L = L; g_pa.wg = wg; g_pa.nwg = nwg;
-  };
+  auto set_level = [&](int level) { g_pa.L = stream_level<U8SRC>(A, level, slot); g_pa.wg = wg; g_pa.nwg = nwg; };
   auto enter_level = [&](int level) {          // ... the first sweep of the level at the accepted pose into term buffer 0
     set_level(level);
     g_pa.t_buf = tb0;
@@ -1169,30 +1014,10 @@ __device__ __forceinline__ void track_batch_stream(const TrackArgs &A, double *_
     if (tid == 0) set_level(g_ts.level);
     __syncthreads();
   }
-  // MULTI: g_s_out <- the sums of all workgroups of the stream, added in workgroup order (dense_track_cpu_sem_kernel::all_workgroups: relaxed agent-scope words + vmcnt(0)
-  // + one arrival counter, valid on gfx950 / gfx942 only -- see the #error above)
+  // MULTI: g_s_out <- the sums of all workgroups of the stream, added in workgroup order
   auto all_workgroups = [&]() {
     if (nwg == 1) return;
-    double *buf = G.part + ((size_t)slot * 2 + (sweep & 1)) * CONT_MAX_NWG * 32;
-    if (tid <= NSUM) __hip_atomic_store(buf + wg * 32 + tid, g_s_out[tid], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    ++sweep;
-    if (tid == 0) {
-      __hip_atomic_fetch_add(G.bar + slot, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      const unsigned target = (unsigned)sweep * (unsigned)nwg;
-      long spin = 0;
-      for (; spin < (1l << 24) && __hip_atomic_load(G.bar + slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < target; ++spin) __builtin_amdgcn_s_sleep(1);
-      if (spin >= (1l << 24)) __hip_atomic_store(G.bar + G.fail_off + slot, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      s_failed = __hip_atomic_load(G.bar + G.fail_off + slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0;
-    }
-    __syncthreads();
-    if (tid <= NSUM) {
-      double acc = 0;
-      for (int w = 0; w < nwg; ++w) acc += __hip_atomic_load(buf + w * 32 + tid, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      g_s_out[tid] = acc;
-    }
-    __syncthreads();
+    sum_workgroups(G, slot, G.part + ((size_t)slot * 2 + (sweep & 1)) * CONT_MAX_NWG * 32, wg, nwg, sweep, s_failed);
   };
   bool failed = false, parked = false;
   bool resume = MULTI;                             // the continuation enters the loop behind a step: solve first
@@ -1220,33 +1045,13 @@ __device__ __forceinline__ void track_batch_stream(const TrackArgs &A, double *_
       } else {                                       // new_chi2 (:335-367) + H,b for the next iteration
         const double S_old = g_ts.S_old, S_new = g_s_out[27];
         const int nv_old = g_ts.nv_old, nv_new = (int)g_s_out[NSUM];
-        float chi2 = g_ts.chi2, new_chi2, seq_old = g_ts.seq_old;
-        int seq_old_ok = g_ts.seq_old_ok;
+        float seq_old = g_ts.seq_old;
+        bool seq_old_ok = g_ts.seq_old_ok != 0;
         unsigned n_exact = 0;
-        bool accept;
-        // the reference compares two float sums of n terms each: |sum_float - sum_exact| <= ((1 + 2^-24)^(n - 1) - 1) sum_exact.  Outside that band the f64 sums decide as
-        // the float sums would; inside it the float sums are formed, bit for bit (exact_seq_sum_f32)
-        const double gam = 1.0001 * (double)max(nv_old, nv_new) * 5.9604644775390625e-08 + 1e-12;
-        const bool near = SVS_TRK_LAZY && tb0 && !G.terms_only && !(fabs(S_old - S_new) > gam * (S_old + S_new));
-        if (near) {
-          float seq_new = 0.f;
-          {
-            ++n_decisions;
-            if (!seq_old_ok) ++n_old_sums;
-            const NearSums ns = shared_near_sums<MULTI>(tb0 + (size_t)cur * G.terms_b, tb0 + (size_t)(cur ^ 1) * G.terms_b, n_lvl, wg, nwg, !seq_old_ok, seq_old, n_decisions, n_old_sums,
-                                                        MULTI ? G.bcast + (size_t)slot * 16 : nullptr, MULTI ? G.bar + G.fail_off + slot : nullptr, n_exact);
-            if (ns.failed) { if (tid == 0) s_failed = true; failed = true; break; }
-            seq_old = ns.seq_old; seq_new = ns.seq_new;
-          }
-          seq_old_ok = 1;
-          chi2 = seq_old; new_chi2 = seq_new;
-          accept = (double)chi2 - (double)new_chi2 > 0;
-          if (accept) seq_old = seq_new;
-        } else {
-          new_chi2 = (float)S_new;
-          accept = S_old > S_new;
-          if (accept) seq_old_ok = 0;
-        }
+        const TrkVerdict V = track_accept<MULTI>(G, slot, S_old, S_new, nv_old, nv_new, tb0, cur, n_lvl, true, wg, nwg, g_ts.chi2, seq_old, seq_old_ok, n_decisions, n_old_sums, n_exact);
+        if (V.failed) { if (tid == 0) s_failed = true; failed = true; break; }
+        const bool accept = V.accept;
+        const float chi2 = V.chi2, new_chi2 = V.new_chi2;
         double mx = -1;
         for (int q = 0; q < 6; ++q) mx = fmax(mx, fabs(g_sx[q]));
         const int it = g_ts.it + 1;
@@ -1258,7 +1063,7 @@ __device__ __forceinline__ void track_batch_stream(const TrackArgs &A, double *_
         }
         if (tid == 0) {
           if (accept) { g_ts.S_old = S_new; g_ts.nv_old = nv_new; g_ts.cur = cur ^ 1; g_ts.chi2 = new_chi2; }
-          g_ts.seq_old = seq_old; g_ts.seq_old_ok = seq_old_ok; g_ts.it = it; g_ts.n_exact += n_exact;
+          g_ts.seq_old = seq_old; g_ts.seq_old_ok = seq_old_ok ? 1 : 0; g_ts.it = it; g_ts.n_exact += n_exact;
           ++g_ts.passes; ++g_ts.n_rec; g_ts.work16 += 16 >> (2 * level);
           if (A.rec && wg == 0 && n_rec < A.rec_cap) A.rec[(size_t)slot * A.rec_cap + n_rec] = svs_dense_lm_record{level, accept ? 1 : 0, chi2, new_chi2};
         }
@@ -1305,7 +1110,7 @@ __device__ __forceinline__ void track_batch_stream(const TrackArgs &A, double *_
   if (A.T_jac && tid < 36) A.T_jac[(size_t)slot * 36 + tid] = g_sTj[tid / 12][tid % 12];
   if (tid == 0 && G.seq_stats && g_ts.n_exact) {
     atomicAdd(G.seq_stats, g_ts.n_exact);
-    if (SVS_TRK_LAZY && g_seq_sh.fell_back) atomicAdd(G.seq_stats + 1, 1u);
+    if (g_seq_sh.fell_back) atomicAdd(G.seq_stats + 1, 1u);
   }
 }
 template <bool U8SRC, bool BAL, int CONT>      // CONT 0: first launch (BAL: grid order from the table); 1: the continuation (grid = CONT_MAX_NWG x groups: launch_batch_tracker)
@@ -1374,96 +1179,9 @@ __global__ __launch_bounds__(256) void residual_image_cpu_sem_kernel(LevelArgs L
   reinterpret_cast<float4 *>(rimg + slot * rimg_b)[i] = o;
 }
 
-// computeDensePointCloudCpu (dense_tracking.cpp:393-423)
-// TQ = [Ti;0 0 0 1] * Q, Ti = inverse of the pose, Q = [1 0 0 -cx; 0 1 0 -cy; 0 0 0 f; 0 0 1/b 0] (stereo_camera.cpp:24-34), evaluated with the same term order
-// as a dense 4x4 product
-__device__ __forceinline__ void cloud_TQ(const double (&T)[12], const svs_cam &cam, double (&TQ)[16]) {
-  double Ti[12];
-#pragma unroll
-  for (int r = 0; r < 3; ++r)
-#pragma unroll
-    for (int c = 0; c < 3; ++c) Ti[4 * r + c] = T[4 * c + r];
-#pragma unroll
-  for (int r = 0; r < 3; ++r) Ti[4 * r + 3] = -(Ti[4 * r] * T[3] + Ti[4 * r + 1] * T[7] + Ti[4 * r + 2] * T[11]);
-  const double Q[16] = {1, 0, 0, -cam.cx, 0, 1, 0, -cam.cy, 0, 0, 0, cam.f, 0, 0, 1.0 / cam.b, 0};
-#pragma unroll
-  for (int r = 0; r < 4; ++r)
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-      double s = 0;
-#pragma unroll
-      for (int k = 0; k < 4; ++k) { double tik = r < 3 ? Ti[4 * r + k] : (k == 3 ? 1.0 : 0.0); s += tik * Q[4 * k + c]; }
-      TQ[4 * r + c] = s;
-    }
-}
-// quarter-grid sample i of one stream's level: disp = the stream's level-0 disparity image, cloud = the stream's cloud of this level
-__device__ __forceinline__ void cloud_sample(const float *__restrict__ disp, int ds, int cw, int level, const double (&TQ)[16], int i, float *__restrict__ cloud) {
-  const int u = i % cw, v = i / cw;
-  const double inv_factor = 1.0 / (double)(1 << level);
-  const float d = (float)(disp[(size_t)((v * 4) << level) * ds + ((u * 4) << level)] * inv_factor);
-  float4 o;
-  if (d <= 0) o = make_float4(0.f, 0.f, 0.f, -1.f);
-  else {
-    const double q[4] = {(double)(u * 4), (double)(v * 4), (double)d, 1.0};
-    double r[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) r[k] = TQ[4 * k] * q[0] + TQ[4 * k + 1] * q[1] + TQ[4 * k + 2] * q[2] + TQ[4 * k + 3] * q[3];
-    o = make_float4((float)(r[0] / r[3]), (float)(r[1] / r[3]), (float)(r[2] / r[3]), 1.f);
-  }
-  reinterpret_cast<float4 *>(cloud)[i] = o;
-}
-__global__ __launch_bounds__(256) void pointcloud_cpu_sem_kernel(const float *__restrict__ disp, int ds, size_t disp_b, svs_cam cam,
-                                                                 int level, const double *__restrict__ Tarr,
-                                                                 float *__restrict__ cloud, size_t cloud_b) {
-  const int slot = blockIdx.y;
-  const int cw = cam.w / 4, ch = cam.h / 4;
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= cw * ch) return;
-  double T[12], TQ[16];
-#pragma unroll
-  for (int k = 0; k < 12; ++k) T[k] = Tarr[(size_t)slot * 12 + k];
-  cloud_TQ(T, cam, TQ);
-  cloud_sample(disp + slot * disp_b, ds, cw, level, TQ, i, cloud + slot * cloud_b);
-}
-
-// the three levels' clouds of a frame in ONE launch (latency mode: three launches of 75 / 19 / 5 blocks each paid a launch gap); the same per-sample function: identical bits
-struct CloudLevels { svs_cam cam[3]; float *cloud[3]; size_t cloud_b[3]; int blocks[3]; };
-__global__ __launch_bounds__(256) void pointcloud_cpu_sem_levels_kernel(const float *__restrict__ disp, int ds, size_t disp_b, CloudLevels Q, const double *__restrict__ Tarr) {
-  const int slot = blockIdx.y;
-  int bx = blockIdx.x, level = 0;
-  if (bx >= Q.blocks[0]) { bx -= Q.blocks[0]; level = 1; if (bx >= Q.blocks[1]) { bx -= Q.blocks[1]; level = 2; } }
-  const svs_cam cam = level == 0 ? Q.cam[0] : (level == 1 ? Q.cam[1] : Q.cam[2]);
-  float *cloud = level == 0 ? Q.cloud[0] : (level == 1 ? Q.cloud[1] : Q.cloud[2]);
-  const size_t cloud_b = level == 0 ? Q.cloud_b[0] : (level == 1 ? Q.cloud_b[1] : Q.cloud_b[2]);
-  const int cw = cam.w / 4, ch = cam.h / 4;
-  const int i = bx * 256 + threadIdx.x;
-  if (i >= cw * ch) return;
-  double T[12], TQ[16];
-#pragma unroll
-  for (int k = 0; k < 12; ++k) T[k] = Tarr[(size_t)slot * 12 + k];
-  cloud_TQ(T, cam, TQ);
-  cloud_sample(disp + slot * disp_b, ds, cw, level, TQ, i, cloud + slot * cloud_b);
-}
 
 }  // namespace
 
-// internal (frontend.hip): computeDensePointCloudCpu of all three levels, one launch
-int svs_pointcloud_cpu_sem_levels(svs_ctx *ctx, const float *d_disp, int disp_stride, size_t disp_bstride, const svs_cam *cams, const double *d_T, float *const *d_cloud,
-                                  const size_t *cloud_bstride, int batch) {
-  SVS_REQUIRE(ctx, ctx && d_disp && cams && d_T && d_cloud && cloud_bstride && batch >= 1);
-  SVS_DEVICE(ctx);
-  CloudLevels Q;
-  int total = 0;
-  for (int l = 0; l < 3; ++l) {
-    SVS_REQUIRE(ctx, cams[l].w % 4 == 0 && cams[l].h % 4 == 0 && d_cloud[l]);
-    Q.cam[l] = cams[l]; Q.cloud[l] = d_cloud[l]; Q.cloud_b[l] = cloud_bstride[l];
-    Q.blocks[l] = div_up((cams[l].w / 4) * (cams[l].h / 4), 256);
-    total += Q.blocks[l];
-  }
-  hipLaunchKernelGGL(pointcloud_cpu_sem_levels_kernel, dim3(total, batch), dim3(256), 0, ctx->stream, d_disp, disp_stride, disp_bstride, Q, d_T);
-  SVS_LAUNCH_CHECK(ctx);
-  return SVS_OK;
-}
 
 static int ensure_scratch(svs_ctx *ctx, double **p, size_t count) {      // ctx-owned (common.h)
   void *v = nullptr;
@@ -1472,18 +1190,6 @@ static int ensure_scratch(svs_ctx *ctx, double **p, size_t count) {      // ctx-
   return rc;
 }
 
-extern "C" int svs_pointcloud_cpu_sem(svs_ctx *ctx, const float *d_disp, int disp_stride, size_t disp_bstride,
-                                      const svs_cam *cam, int level, const double *d_T, float *d_cloud,
-                                      size_t cloud_bstride, int batch) {
-  SVS_REQUIRE(ctx, ctx && d_disp && cam && d_T && d_cloud && level >= 0 && level < 3 && batch >= 1);
-  SVS_DEVICE(ctx);
-  SVS_REQUIRE(ctx, cam->w % 4 == 0 && cam->h % 4 == 0);            // dense_tracking.cpp:45-46 asserts
-  int n = (cam->w / 4) * (cam->h / 4);
-  hipLaunchKernelGGL(pointcloud_cpu_sem_kernel, dim3(div_up(n, 256), batch), dim3(256), 0, ctx->stream, d_disp, disp_stride,
-                     disp_bstride, *cam, level, d_T, d_cloud, cloud_bstride);
-  SVS_LAUNCH_CHECK(ctx);
-  return SVS_OK;
-}
 
 extern "C" int svs_dense_pass_cpu_sem(svs_ctx *ctx, const float *d_cloud, size_t cloud_bstride, const uint8_t *d_prev_u8,
                                       int pstride, size_t p_bstride, const float *d_cur, const float *d_dx,
@@ -1632,13 +1338,20 @@ static int cont_setup(svs_ctx *ctx, int batch, TrackMulti &G, TrackCont &C) {
   SVS_HIP(ctx, hipMemsetAsync(G.bar, 0, sizeof(double) * (n_bar + n_bc + n_cnt), ctx->stream));
   return SVS_OK;
 }
+// a tracker kernel for the source of the current image (u8src: the u8 level images, else the f32 pyramids): K<true, ...> or K<false, ...>, both from ONE list of the
+// remaining template arguments (in parentheses) and ONE argument list; TRK_THREADS lanes per workgroup, on the context's stream
+#define TRK_ARGS(...) __VA_ARGS__
+#define TRK_LAUNCH(u8src, K, TAIL, grid, ...)                                                                              \
+  do {                                                                                                                     \
+    if (u8src) hipLaunchKernelGGL((K<true, TRK_ARGS TAIL>), grid, dim3(TRK_THREADS), 0, ctx->stream, __VA_ARGS__);         \
+    else hipLaunchKernelGGL((K<false, TRK_ARGS TAIL>), grid, dim3(TRK_THREADS), 0, ctx->stream, __VA_ARGS__);              \
+  } while (0)
 // the first launch of a big batch (grid: one workgroup per stream / the balanced table) and, with "trk_split", its continuation
 template <bool BAL>
 static int launch_batch_tracker(svs_ctx *ctx, const TrackArgs &A, bool u8src, double *d_T_io, int32_t *d_passes_out, int batch, int grid, TrackMulti G) {
   TrackCont C{nullptr, nullptr, nullptr, -1, 0};
   if (ctx->trk_split > 0) { const int rc = cont_setup(ctx, batch, G, C); if (rc) return rc; }
-  if (u8src) hipLaunchKernelGGL((dense_track_batch_kernel<true, BAL, 0>), dim3(grid), dim3(TRK_THREADS), 0, ctx->stream, A, d_T_io, d_passes_out, G, C);
-  else hipLaunchKernelGGL((dense_track_batch_kernel<false, BAL, 0>), dim3(grid), dim3(TRK_THREADS), 0, ctx->stream, A, d_T_io, d_passes_out, G, C);
+  TRK_LAUNCH(u8src, dense_track_batch_kernel, (BAL, 0), dim3(grid), A, d_T_io, d_passes_out, G, C);
   SVS_LAUNCH_CHECK(ctx);
   if (C.K < 0) return SVS_OK;
   // the parked streams, CONT_MAX_NWG workgroups each: they wait for each other inside the launch -- through the spin gate like every launch of that kind (common.h).
@@ -1646,8 +1359,7 @@ static int launch_batch_tracker(svs_ctx *ctx, const TrackArgs &A, bool u8src, do
   const int groups = std::max(1, std::min(batch, C.slots / CONT_MAX_NWG));
   SvsSpinScope gate(ctx);
   if (gate.rc) return gate.rc;
-  if (u8src) hipLaunchKernelGGL((dense_track_batch_kernel<true, false, 1>), dim3(CONT_MAX_NWG, groups), dim3(TRK_THREADS), 0, ctx->stream, A, d_T_io, d_passes_out, G, C);
-  else hipLaunchKernelGGL((dense_track_batch_kernel<false, false, 1>), dim3(CONT_MAX_NWG, groups), dim3(TRK_THREADS), 0, ctx->stream, A, d_T_io, d_passes_out, G, C);
+  TRK_LAUNCH(u8src, dense_track_batch_kernel, (false, 1), dim3(CONT_MAX_NWG, groups), A, d_T_io, d_passes_out, G, C);
   SVS_LAUNCH_CHECK(ctx);
   return gate.leave();
 }
@@ -1687,8 +1399,7 @@ int svs_dense_track_cpu_sem_balanced(svs_ctx *ctx, const TrackArgs &A, bool u8sr
     SVS_HIP(ctx, hipMemsetAsync(S.flags, 0, sizeof(double) * S.n_flags, ctx->stream));      // arrival counters, failure flags, hand-over words
     SvsSpinScope gate(ctx);
     if (gate.rc) return gate.rc;
-    if (u8src) hipLaunchKernelGGL((dense_track_cpu_sem_kernel<true, true, TRK_MINW_BIG, false, true>), dim3(S.grid), dim3(TRK_THREADS), 0, ctx->stream, A, d_T_io, d_passes_out, G);
-    else hipLaunchKernelGGL((dense_track_cpu_sem_kernel<false, true, TRK_MINW_BIG, false, true>), dim3(S.grid), dim3(TRK_THREADS), 0, ctx->stream, A, d_T_io, d_passes_out, G);
+    TRK_LAUNCH(u8src, dense_track_cpu_sem_kernel, (true, TRK_MINW_BIG, false, true), dim3(S.grid), A, d_T_io, d_passes_out, G);
     SVS_LAUNCH_CHECK(ctx);
     if (int grc = gate.leave()) return grc;
   } else if (ctx->trk_flat) {       // order only: one workgroup per stream, nothing waits for anything -- the flat kernel (round 6), bit-identical to the one below
@@ -1696,8 +1407,7 @@ int svs_dense_track_cpu_sem_balanced(svs_ctx *ctx, const TrackArgs &A, bool u8sr
     if (int lrc = launch_batch_tracker<true>(ctx, A, u8src, d_T_io, d_passes_out, batch, S.grid, G)) return lrc;
     return bal_assign(ctx, S, batch, A.rec, A.rec_cap, A.n_rec, true);
   } else {
-    if (u8src) hipLaunchKernelGGL((dense_track_cpu_sem_kernel<true, false, TRK_MINW_BIG, false, true>), dim3(S.grid), dim3(TRK_THREADS), 0, ctx->stream, A, d_T_io, d_passes_out, G);
-    else hipLaunchKernelGGL((dense_track_cpu_sem_kernel<false, false, TRK_MINW_BIG, false, true>), dim3(S.grid), dim3(TRK_THREADS), 0, ctx->stream, A, d_T_io, d_passes_out, G);
+    TRK_LAUNCH(u8src, dense_track_cpu_sem_kernel, (false, TRK_MINW_BIG, false, true), dim3(S.grid), A, d_T_io, d_passes_out, G);
   }
   SVS_LAUNCH_CHECK(ctx);
   return bal_assign(ctx, S, batch, A.rec, A.rec_cap, A.n_rec);
@@ -1770,8 +1480,7 @@ int svs_dense_track_cpu_sem_work(svs_ctx *ctx, const svs_dense_track_args *a, do
   G.terms = terms; G.terms_b = t_b; G.seq_stats = static_cast<unsigned *>(ctx->seq_stats); G.terms_only = ctx->trk_lazy_chi2 == 2;
   if (t_buf) {
     G.part = reinterpret_cast<double *>(t_buf); G.fail_off = (int)t_b;
-    if (u8src) hipLaunchKernelGGL((dense_track_cpu_sem_kernel<true, false, 2, true>), dim3(batch), dim3(TRK_THREADS), 0, ctx->stream, A, d_T_io, d_passes_out, G);
-    else hipLaunchKernelGGL((dense_track_cpu_sem_kernel<false, false, 2, true>), dim3(batch), dim3(TRK_THREADS), 0, ctx->stream, A, d_T_io, d_passes_out, G);
+    TRK_LAUNCH(u8src, dense_track_cpu_sem_kernel, (false, 2, true), dim3(batch), A, d_T_io, d_passes_out, G);
   } else if (nwg >= 2) {
     double *scratch = nullptr;
     const size_t n_part = (size_t)batch * 2 * nwg * 64;      // per stream, parity and workgroup: 58 (+ 6) flagged 8-byte words (all_workgroups)
@@ -1787,8 +1496,7 @@ int svs_dense_track_cpu_sem_work(svs_ctx *ctx, const svs_dense_track_args *a, do
     SVS_HIP(ctx, hipMemsetAsync(scratch, 0, sizeof(double) * n_clear, ctx->stream));      // flagged words, failure flags, hand-over words: one clear
     SvsSpinScope gate(ctx, nwg * batch);      // the workgroups of a stream wait for each other: one such launch on the device at a time (common.h); one stream: priority lane
     if (gate.rc) return gate.rc;
-    if (u8src) hipLaunchKernelGGL((dense_track_cpu_sem_kernel<true, true, 2>), dim3(nwg, batch), dim3(TRK_THREADS), 0, ctx->stream, A, d_T_io, d_passes_out, G);
-    else hipLaunchKernelGGL((dense_track_cpu_sem_kernel<false, true, 2>), dim3(nwg, batch), dim3(TRK_THREADS), 0, ctx->stream, A, d_T_io, d_passes_out, G);
+    TRK_LAUNCH(u8src, dense_track_cpu_sem_kernel, (true, 2), dim3(nwg, batch), A, d_T_io, d_passes_out, G);
     SVS_LAUNCH_CHECK(ctx);
     if (int grc = gate.leave()) return grc;
   } else if (d_bal_state && ctx->trk_balance && batch >= 2 * ctx->n_cu && batch <= BAL_MAX_STREAMS && A.rec && A.n_rec) {
@@ -1796,11 +1504,9 @@ int svs_dense_track_cpu_sem_work(svs_ctx *ctx, const svs_dense_track_args *a, do
   } else if (((batch > ctx->n_cu && ctx->trk_regs != 1) || ctx->trk_regs == 2) && ctx->trk_flat) {
     if (int lrc = launch_batch_tracker<false>(ctx, A, u8src, d_T_io, d_passes_out, batch, batch, G)) return lrc;
   } else if ((batch > ctx->n_cu && ctx->trk_regs != 1) || ctx->trk_regs == 2) {      // trk_regs: tests / experiments, latched at svs_ctx_create
-    if (u8src) hipLaunchKernelGGL((dense_track_cpu_sem_kernel<true, false, TRK_MINW_BIG>), dim3(batch), dim3(TRK_THREADS), 0, ctx->stream, A, d_T_io, d_passes_out, G);
-    else hipLaunchKernelGGL((dense_track_cpu_sem_kernel<false, false, TRK_MINW_BIG>), dim3(batch), dim3(TRK_THREADS), 0, ctx->stream, A, d_T_io, d_passes_out, G);
+    TRK_LAUNCH(u8src, dense_track_cpu_sem_kernel, (false, TRK_MINW_BIG), dim3(batch), A, d_T_io, d_passes_out, G);
   } else {
-    if (u8src) hipLaunchKernelGGL((dense_track_cpu_sem_kernel<true, false, 2>), dim3(batch), dim3(TRK_THREADS), 0, ctx->stream, A, d_T_io, d_passes_out, G);
-    else hipLaunchKernelGGL((dense_track_cpu_sem_kernel<false, false, 2>), dim3(batch), dim3(TRK_THREADS), 0, ctx->stream, A, d_T_io, d_passes_out, G);
+    TRK_LAUNCH(u8src, dense_track_cpu_sem_kernel, (false, 2), dim3(batch), A, d_T_io, d_passes_out, G);
   }
   SVS_LAUNCH_CHECK(ctx);
   return SVS_OK;
@@ -1844,604 +1550,6 @@ extern "C" int svs_dense_residual_image_cpu_sem(svs_ctx *ctx, const float *d_clo
   else
     hipLaunchKernelGGL(residual_image_cpu_sem_kernel<false>, dim3(div_up(n, 256), batch), dim3(256), 0, ctx->stream, L, cloud_bstride, p_bstride,
                        f_bstride, c8_bstride, d_T, T_bstride, d_res_img4, res_bstride);
-  SVS_LAUNCH_CHECK(ctx);
-  return SVS_OK;
-}
-
-// ---- motion-only pose refinement: PoseOptimizer<SE3,6,IdObs<3>,3>::calcFastMotionOnly ---------------------------
-// (pose_optimizer.h:134-298, called at stereo_frontend.cpp:1058-1063 right behind the guided matcher).  One workgroup
-// per camera stream runs the whole LM loop on the device: observations are the status-OK entries of the matcher's
-// result array (= TrackData::obs_list / point_list, in list order); every pass is a strided sweep over them with a
-// wave-shuffle + LDS reduction of the 21 + 6 normal-equation sums (or chi2 / max error); one lane solves the 6x6 system.
-namespace {
-
-__device__ __forceinline__ double mo_kernel(double delta, double b) {      // pseudo-Huber cost, pose_optimizer.h:426-435
-  const double a = fabs(delta);
-  return a < b ? delta * delta : 2 * b * a - b * b;
-}
-// f = obs - map_uvu(T xyz) (stereo_camera.cpp:37-44); J = SE3XYZ_STEREO::frameJac (transformations.h:424-447) if wanted
-template <bool JAC>
-__device__ __forceinline__ void mo_residual(const double *T, const svs_match_result &o, const svs_cam &cam, double *f, double *J) {
-  const double *q = o.xyz_actkey;
-  const double x = T[0] * q[0] + T[1] * q[1] + T[2] * q[2] + T[3];
-  const double y = T[4] * q[0] + T[5] * q[1] + T[6] * q[2] + T[7];
-  const double z = T[8] * q[0] + T[9] * q[1] + T[10] * q[2] + T[11];
-  const double fl = cam.f;
-  f[0] = o.obs[0] - (x / z * fl + cam.cx);
-  f[1] = o.obs[1] - (y / z * fl + cam.cy);
-  f[2] = o.obs[2] - ((x - cam.b) / z * fl + cam.cx);
-  if (JAC) {
-    const double ibz = 1. / z, ibz2 = 1. / (z * z);
-    const double A = -fl * ibz, B = -fl * ibz, C = fl * x * ibz2, D = fl * y * ibz2, E = fl * (x - cam.b) * ibz2;
-    J[0] = A; J[1] = 0; J[2] = C; J[3] = y * C; J[4] = z * A - x * C; J[5] = -y * A;
-    J[6] = 0; J[7] = B; J[8] = D; J[9] = -z * B + y * D; J[10] = -x * D; J[11] = x * B;
-    J[12] = A; J[13] = 0; J[14] = E; J[15] = y * E; J[16] = z * A - x * E; J[17] = -y * A;
-  }
-}
-__device__ __forceinline__ double mo_weighted_sq(double *f, int robust, double b) {
-  if (robust) {
-    const double nrm = fmax(1e-10, sqrt(f[0] * f[0] + f[1] * f[1] + f[2] * f[2]));
-    const double w = sqrt(mo_kernel(nrm, b)) / nrm;
-    f[0] *= w; f[1] *= w; f[2] *= w;
-  }
-  return f[0] * f[0] + f[1] * f[1] + f[2] * f[2];
-}
-
-constexpr int MO_THREADS = 256;
-// block reduction of N doubles per thread: sums for k < n_sum, maxima for the rest.  Result in s_red[0..N) (all threads may read)
-template <int N>
-__device__ __forceinline__ void mo_reduce(double (&v)[N], int n_sum, double *s_red) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int k = 0; k < N; ++k) {
-    double x = v[k];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { const double y = __shfl_xor(x, o, 64); x = k < n_sum ? x + y : fmax(x, y); }
-    if (lane == 0) s_red[wave * N + k] = x;
-  }
-  __syncthreads();
-  if (threadIdx.x < N) {
-    const int k = threadIdx.x;
-    double x = s_red[k];
-    for (int w = 1; w < MO_THREADS / 64; ++w) x = k < n_sum ? x + s_red[w * N + k] : fmax(x, s_red[w * N + k]);
-    s_red[(MO_THREADS / 64) * N + k] = x;
-  }
-  __syncthreads();
-#pragma unroll
-  for (int k = 0; k < N; ++k) v[k] = s_red[(MO_THREADS / 64) * N + k];
-  __syncthreads();
-}
-
-__global__ __launch_bounds__(MO_THREADS) void motion_only_kernel(const svs_match_result *__restrict__ res, int n, size_t res_bstride, svs_cam cam,
-                                                                 svs_pose_opt_params prm, double *__restrict__ T_io, svs_pose_opt_stats *__restrict__ stats) {
-  __shared__ double s_red[(MO_THREADS / 64 + 1) * 28];
-  __shared__ double s_T[12], s_Tn[12], s_B[6];
-  const int tid = threadIdx.x, slot = blockIdx.x;
-  res += (size_t)slot * res_bstride;
-  if (tid < 12) s_T[tid] = T_io[12 * slot + tid];
-  __syncthreads();
-  // initial residuals: chi2, max error, number of observations, max diag(J^T J)
-  double chi2, max_err, mu, nu = 2;
-  int num_obs;
-  {
-    double v[4] = {0, 0, 0, 0};      // chi2, num_obs | max_err, norm_max_A
-    for (int i = tid; i < n; i += MO_THREADS) {
-      if (res[i].status != 0) continue;
-      double f[3], J[18];
-      mo_residual<true>(s_T, res[i], cam, f, J);
-#pragma unroll
-      for (int c = 0; c < 6; ++c) v[3] = fmax(v[3], fabs(J[c] * J[c] + J[6 + c] * J[6 + c] + J[12 + c] * J[12 + c]));
-      v[0] += mo_weighted_sq(f, prm.robust_kernel, prm.kernel_param);
-      v[1] += 1.0;
-      v[2] = fmax(v[2], fmax(fabs(f[0]), fmax(fabs(f[1]), fabs(f[2]))));
-    }
-    mo_reduce<4>(v, 2, s_red);
-    chi2 = v[0]; num_obs = (int)v[1]; max_err = v[2];
-    mu = prm.initial_mu == -1 ? prm.tau * v[3] : prm.initial_mu;
-  }
-  const double initial_chi2 = chi2;
-  int status = num_obs == 0 ? 1 : (num_obs < prm.min_obs ? 3 : 0), trial = 0;
-  bool stop = status != 0;
-  for (int ig = 0; ig < prm.num_iter && !stop; ++ig) {
-    double rho = 0;
-    do {
-      double v[27];      // 21 unique of sum J^T J (upper, row-major), 6 of sum J^T (w f)
-#pragma unroll
-      for (int k = 0; k < 27; ++k) v[k] = 0;
-      for (int i = tid; i < n; i += MO_THREADS) {
-        if (res[i].status != 0) continue;
-        double f[3], J[18];
-        mo_residual<true>(s_T, res[i], cam, f, J);
-        mo_weighted_sq(f, prm.robust_kernel, prm.kernel_param);
-        int k = 0;
-#pragma unroll
-        for (int r = 0; r < 6; ++r) {
-#pragma unroll
-          for (int c = r; c < 6; ++c) v[k++] += J[r] * J[c] + J[6 + r] * J[6 + c] + J[12 + r] * J[12 + c];
-          v[21 + r] += J[r] * f[0] + J[6 + r] * f[1] + J[12 + r] * f[2];
-        }
-      }
-      mo_reduce<27>(v, 27, s_red);
-      if (tid == 0) {
-        double A[36], B[6], delta[6];
-        int k = 0;
-        for (int r = 0; r < 6; ++r)
-          for (int c = r; c < 6; ++c) { A[6 * r + c] = A[6 * c + r] = v[k++]; }
-        for (int r = 0; r < 6; ++r) { A[7 * r] += mu; B[r] = -v[21 + r]; s_B[r] = B[r]; }
-        d_solve6(A, B, delta);                                 // A.ldlt().solve(B)
-        double Tn[12];
-        d_se3_exp_mul(delta, s_T, Tn);                         // prediction.add: exp(delta) * T
-        for (int i = 0; i < 12; ++i) s_Tn[i] = Tn[i];
-      }
-      __syncthreads();
-      double w[2] = {0, 0};      // new chi2 | new max error
-      for (int i = tid; i < n; i += MO_THREADS) {
-        if (res[i].status != 0) continue;
-        double f[3];
-        mo_residual<false>(s_Tn, res[i], cam, f, nullptr);
-        w[0] += mo_weighted_sq(f, prm.robust_kernel, prm.kernel_param);
-        w[1] = fmax(w[1], fmax(fabs(f[0]), fmax(fabs(f[1]), fabs(f[2]))));
-      }
-      mo_reduce<2>(w, 1, s_red);
-      const double new_chi2 = w[0];
-      if (isnan(new_chi2)) { status = 2; stop = true; break; }      // the reference throws here
-      rho = chi2 - new_chi2;
-      if (rho > 0) {
-        if (tid < 12) s_T[tid] = s_Tn[tid];
-        chi2 = new_chi2; max_err = w[1];
-        double bm = -1;
-        for (int c = 0; c < 6; ++c) bm = fmax(bm, fabs(s_B[c]));
-        stop = bm <= 1e-10;
-        const double q = 2 * rho - 1, sc = 1 - q * q * q;
-        mu *= fmax(1. / 3., sc);
-        nu = 2.; trial = 0;
-      } else {
-        mu *= nu; nu *= 2.; ++trial;
-        if (trial == 5) stop = true;
-      }
-      __syncthreads();
-    } while (!(rho > 0 || stop));
-  }
-  if (tid < 12) T_io[12 * slot + tid] = s_T[tid];
-  if (tid == 0) {
-    svs_pose_opt_stats st;
-    st.initial_chi2 = initial_chi2; st.chi2 = chi2; st.max_err = max_err; st.num_obs = num_obs; st.status = status;
-    stats[slot] = st;
-  }
-}
-
-
-
-// ---- the same loop, restructured for latency (round 3) ---------------------------------------------------------------------------
-// The kernel above walks the matcher's record array (status test + 64-byte record from global memory per observation) twice per LM
-// trial and solves on one lane: 202 us for ~850 observations at B = 1.  Here:
-//  * the status-OK records are compacted ONCE (order-preserving: ballots + a wave prefix) into an index list in LDS, and every thread keeps
-//    up to MO2_RC observations in registers for the whole loop (observations beyond MO2_RC * MO2_THREADS are re-read through the list);
-//  * ONE sweep per LM trial: chi2 / max error at the trial pose and the normal equations at the same pose share their residuals, so the
-//    reference's "new chi2" pass and the next iteration's J^T J pass are one (a rejected trial keeps the stored system and only re-damps);
-//  * 28 sums per wave by recursive halving (32 exchanges instead of 168 butterflies), two block barriers per trial;
-//  * the 6x6 solve runs on seven lanes of wave 0 (lane = column of [A + mu I | B], Gauss-Jordan with readlane broadcasts; the matrix is
-//    symmetric positive definite, so no pivoting is needed where the reference's ldlt() pivots), exp(delta) * T on the same wave.
-// Same LM schedule and stopping rules as pose_optimizer.h:134-298; sums in a different order and one reciprocal instead of five divisions
-// per residual => the pose agrees with the oracle to ~1e-12 (test bar 1e-9).
-// Round 5: 256 lanes and six observations per lane in registers (rounds 3-4: 512 and four).  The kernel needs ~235 vector registers whatever its width, i.e. two
-// waves per SIMD: a 512-lane workgroup had a CU to itself and a batch of 512 streams ran as two rounds of a latency-bound loop (<= 15 dependent LM iterations, two
-// barriers and a 6 x 6 solve on one wave each); two 256-lane workgroups share a CU and the serial parts of one stream hide behind the sweeps of the other:
-// 0.32 -> 0.22 ms per 512 streams.
-#ifndef SVS_MO2_THREADS
-#define SVS_MO2_THREADS 256
-#endif
-#ifndef SVS_MO2_RC
-#define SVS_MO2_RC 6
-#endif
-constexpr int MO2_THREADS = SVS_MO2_THREADS, MO2_RC = SVS_MO2_RC, MO2_WAVES = MO2_THREADS / 64;
-struct MoObs { double o[3], q[3]; };
-
-template <bool FIRST, bool JAC = true>      // JAC = false: chi2 and max error only (the sweep of a trial that is expected to be rejected)
-__device__ __forceinline__ void mo2_terms(const double (&T)[12], const MoObs &ob, const svs_cam &cam, int robust, double kb, double (&x)[32], double &max_err,
-                                          double &max_diag) {
-  static_assert(JAC || !FIRST, "the first sweep needs the Jacobian");
-  const double *q = ob.q;
-  const double X = T[0] * q[0] + T[1] * q[1] + T[2] * q[2] + T[3];
-  const double Y = T[4] * q[0] + T[5] * q[1] + T[6] * q[2] + T[7];
-  const double Z = T[8] * q[0] + T[9] * q[1] + T[10] * q[2] + T[11];
-  const double fl = cam.f, iz = 1.0 / Z, fiz = fl * iz, Xb = X - cam.b;
-  double f0 = ob.o[0] - (X * fiz + cam.cx), f1 = ob.o[1] - (Y * fiz + cam.cy), f2 = ob.o[2] - (Xb * fiz + cam.cx);
-  // frameJac (transformations.h:424-447): rows (A 0 C yC zA-xC -yA), (0 A D -zA+yD -xD xA), (A 0 E yE zA-xE -yA) with A = -f/z, C = f x/z^2, ...
-  const double A = -fiz, C = fiz * X * iz, D = fiz * Y * iz, E = fiz * Xb * iz;
-  const double a3 = Y * C, a4 = Z * A - X * C, a5 = -Y * A;      // row 0, columns 3..5
-  const double b3 = Y * D - Z * A, b4 = -X * D, b5 = X * A;      // row 1
-  const double c3 = Y * E, c4 = Z * A - X * E;                   // row 2 (column 5 = a5)
-  if (FIRST) {
-    const double AA = A * A;
-    double m = fmax(AA + AA, AA);
-    m = fmax(m, C * C + D * D + E * E);
-    m = fmax(m, a3 * a3 + b3 * b3 + c3 * c3);
-    m = fmax(m, a4 * a4 + b4 * b4 + c4 * c4);
-    m = fmax(m, a5 * a5 + b5 * b5 + a5 * a5);
-    max_diag = fmax(max_diag, m);
-  }
-  // pseudo-Huber weight (pose_optimizer.h:169-175,426-435): f *= sqrt(k(|f|)) / |f|, chi2 += |w f|^2 = k(|f|)
-  const double ss = f0 * f0 + f1 * f1 + f2 * f2;
-  double chi = ss;
-  if (robust) {
-    const double nrm = fmax(1e-10, sqrt(ss));
-    if (nrm >= kb) {                                             // outliers only: inside the kernel width the weight is sqrt(n^2) / n = 1
-      const double k = 2 * kb * nrm - kb * kb, w = sqrt(k) / nrm;
-      f0 *= w; f1 *= w; f2 *= w;
-      chi = f0 * f0 + f1 * f1 + f2 * f2;
-    }
-  }
-  x[27] += chi;
-  max_err = fmax(max_err, fmax(fabs(f0), fmax(fabs(f1), fabs(f2))));
-  if constexpr (!JAC) return;
-  // J^T J, upper triangle row-major (21) -- the structural zeros of frameJac are not multiplied out -- and J^T (w f) (6)
-  x[0] += A * A + A * A;          x[1] += 0.0;                     x[2] += A * C + A * E;
-  x[3] += A * a3 + A * c3;        x[4] += A * a4 + A * c4;         x[5] += A * a5 + A * a5;
-  x[6] += A * A;                  x[7] += A * D;                   x[8] += A * b3;
-  x[9] += A * b4;                 x[10] += A * b5;
-  x[11] += C * C + D * D + E * E; x[12] += C * a3 + D * b3 + E * c3; x[13] += C * a4 + D * b4 + E * c4;
-  x[14] += C * a5 + D * b5 + E * a5;
-  x[15] += a3 * a3 + b3 * b3 + c3 * c3; x[16] += a3 * a4 + b3 * b4 + c3 * c4; x[17] += a3 * a5 + b3 * b5 + c3 * a5;
-  x[18] += a4 * a4 + b4 * b4 + c4 * c4; x[19] += a4 * a5 + b4 * b5 + c4 * a5;
-  x[20] += a5 * a5 + b5 * b5 + a5 * a5;
-  x[21] += A * f0 + A * f2;       x[22] += A * f1;                 x[23] += C * f0 + D * f1 + E * f2;
-  x[24] += a3 * f0 + b3 * f1 + c3 * f2; x[25] += a4 * f0 + b4 * f1 + c4 * f2; x[26] += a5 * f0 + b5 * f1 + a5 * f2;
-}
-// value id held by lane `lane` (< 32) after the recursive halving of mo2_wave_reduce
-__device__ __forceinline__ int mo2_id(int lane) { return ((lane & 1) << 4) | ((lane & 2) << 2) | (lane & 4) | ((lane & 8) >> 2) | ((lane & 16) >> 4); }
-__device__ __forceinline__ double mo2_wave_reduce(double (&x)[32]) {
-  const int lane = threadIdx.x & 63;
-#pragma unroll
-  for (int step = 0; step < 5; ++step) {
-    const int half = 16 >> step, bit = 1 << step;
-    const bool up = (lane & bit) != 0;
-#pragma unroll
-    for (int k = 0; k < half; ++k) {
-      // the two candidates are pinned as VALUES: left alone, the optimiser turns "select of two array elements" into one load at a selected address
-      // before the loops are unrolled -- and the accumulator array then lives (and is stored after every observation) in scratch memory
-      double lo = x[k], hi = x[k + half];
-      asm volatile("" : "+v"(lo), "+v"(hi));
-      const double send = up ? lo : hi;
-      const double keep = up ? hi : lo;
-      x[k] = keep + __shfl_xor(send, bit, 64);
-    }
-  }
-  return x[0] + __shfl_xor(x[0], 32, 64);
-}
-
-// one sweep over the observations at pose T: per-wave sums -> s_part[wave]
-template <bool FIRST>
-__device__ __forceinline__ void mo2_sweep(const double (&T)[12], const MoObs (&ob)[MO2_RC], int n_ok, const int *s_idx, const svs_match_result *__restrict__ res,
-                                          const svs_cam &cam, int robust, double kb, double (*s_part)[32]) {
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  double x[32];
-#pragma unroll
-  for (int i = 0; i < 32; ++i) x[i] = 0.0;
-  double me = 0.0, md = 0.0;
-#pragma unroll
-  for (int k = 0; k < MO2_RC; ++k)
-    if (tid + k * MO2_THREADS < n_ok) mo2_terms<FIRST>(T, ob[k], cam, robust, kb, x, me, md);
-  for (int j = tid + MO2_RC * MO2_THREADS; j < n_ok; j += MO2_THREADS) {
-    const svs_match_result &r = res[s_idx[j]];
-    MoObs t;
-#pragma unroll
-    for (int c = 0; c < 3; ++c) { t.o[c] = r.obs[c]; t.q[c] = r.xyz_actkey[c]; }
-    mo2_terms<FIRST>(T, t, cam, robust, kb, x, me, md);
-  }
-  const double v = mo2_wave_reduce(x);
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) { me = fmax(me, __shfl_xor(me, o, 64)); if (FIRST) md = fmax(md, __shfl_xor(md, o, 64)); }
-  const int id = mo2_id(lane);
-  if (lane < 32 && id < 28) s_part[wave][id] = v;
-  if (lane == 0) { s_part[wave][28] = me; s_part[wave][29] = md; }
-}
-
-// chi2 (and the largest residual) at pose T only -> s_part[wave][27], [28].  Bit-identical to what mo2_sweep leaves there: the same per-lane terms in the same
-// order, and the butterfly below adds them in the association mo2_wave_reduce's halving gives element 27 (own + partner over lane distances 1, 2, 4, 8, 16, 32).
-__device__ __forceinline__ void mo2_sweep_chi2(const double (&T)[12], const MoObs (&ob)[MO2_RC], int n_ok, const int *s_idx, const svs_match_result *__restrict__ res,
-                                               const svs_cam &cam, int robust, double kb, double (*s_part)[32]) {
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  double x[32];
-  x[27] = 0.0;
-  double me = 0.0, md = 0.0;
-#pragma unroll
-  for (int k = 0; k < MO2_RC; ++k)
-    if (tid + k * MO2_THREADS < n_ok) mo2_terms<false, false>(T, ob[k], cam, robust, kb, x, me, md);
-  for (int j = tid + MO2_RC * MO2_THREADS; j < n_ok; j += MO2_THREADS) {
-    const svs_match_result &r = res[s_idx[j]];
-    MoObs t;
-#pragma unroll
-    for (int c = 0; c < 3; ++c) { t.o[c] = r.obs[c]; t.q[c] = r.xyz_actkey[c]; }
-    mo2_terms<false, false>(T, t, cam, robust, kb, x, me, md);
-  }
-  double v = x[27];
-#pragma unroll
-  for (int o = 1; o <= 32; o <<= 1) v += __shfl_xor(v, o, 64);
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) me = fmax(me, __shfl_xor(me, o, 64));
-  if (lane == 0) { s_part[wave][27] = v; s_part[wave][28] = me; }
-}
-
-// the gate of one stream, run by 256 lanes (tid < 256) of a workgroup: s_cnt [18], s_sum [4] in LDS; the caller has a barrier in front of it
-__device__ __forceinline__ void gate_stream(const svs_match_result *__restrict__ res, const svs_candidate_point *__restrict__ pts, int n, int n_new, const svs_cam &cam,
-                                            const double (&T)[12], float mre, svs_gated_point *__restrict__ out, svs_point_stats *__restrict__ st, int tid, int *s_cnt,
-                                            double *s_sum) {
-  if (tid < 18) s_cnt[tid] = 0;
-  __syncthreads();
-  const int half_w = (int)(cam.w * 0.5), half_h = (int)(cam.h * 0.5);
-  const float third = (float)(1. / 3.);
-  const int third_w = (int)(cam.w * third), third_h = (int)(cam.h * third);
-  const int tt_w = (int)(cam.w * 2 * third), tt_h = (int)(cam.h * 2 * third);
-  double len = 0;
-  for (int i = tid; i < n && tid < 256; i += 256) {
-    svs_gated_point g{};
-    if (res[i].status == 0) {
-      atomicAdd(&s_cnt[17], 1);
-      double d[3];
-      mo_residual<false>(T, res[i], cam, d, nullptr);          // uvu - se3xyz_stereo_.map(T_cur_from_actkey_, point)
-      const int level = pts[i].anchor_level;
-      const int factor = 1 << level;                             // zeroFromPyr_i(1, anchor_level)
-      if (fabs(d[0]) < mre * factor && fabs(d[1]) < mre * factor && fabs(d[2]) < 3. * mre) {
-        const double *uvu = res[i].obs, *q = res[i].xyz_actkey;
-        const int i2 = uvu[0] < half_w ? 0 : 1, j2 = uvu[1] < half_h ? 0 : 1;
-        const int i3 = uvu[0] < third_w ? 0 : (uvu[0] < tt_w ? 1 : 2), j3 = uvu[1] < third_h ? 0 : (uvu[1] < tt_h ? 1 : 2);
-        atomicAdd(&s_cnt[i2 * 2 + j2], 1);
-        atomicAdd(&s_cnt[4 + i3 * 3 + j3], 1);
-        atomicAdd(&s_cnt[13 + level], 1);
-        atomicAdd(&s_cnt[16], 1);
-        const double inv = 1.0 / (double)factor;                 // exact power of two: x * inv == x / factor
-        g.accepted = 1;
-        g.is_new = i < n_new ? 1 : 0;
-        g.uv_pyr[0] = uvu[0] * inv; g.uv_pyr[1] = uvu[1] * inv;
-        g.curkey_uv_pyr[0] = (q[0] / q[2] * cam.f + cam.cx) * inv;
-        g.curkey_uv_pyr[1] = (q[1] / q[2] * cam.f + cam.cy) * inv;
-        const double dx = g.uv_pyr[0] - g.curkey_uv_pyr[0], dy = g.uv_pyr[1] - g.curkey_uv_pyr[1];
-        len += sqrt(dx * dx + dy * dy);
-      }
-    }
-    out[i] = g;
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) len += __shfl_xor(len, o, 64);
-  if ((tid & 63) == 0 && tid < 256) s_sum[tid >> 6] = len;
-  __syncthreads();
-  if (tid < 4) st->num_points_grid2x2[tid] = s_cnt[tid];
-  else if (tid < 13) st->num_points_grid3x3[tid - 4] = s_cnt[tid];
-  else if (tid < 16) st->num_matched_points[tid - 13] = s_cnt[tid];
-  else if (tid == 16) st->num_track_points = s_cnt[16];
-  else if (tid == 17) st->num_obs = s_cnt[17];
-  else if (tid == 18) { st->pad_[0] = st->pad_[1] = 0; st->sum_track_length = (s_sum[0] + s_sum[1]) + (s_sum[2] + s_sum[3]); }
-}
-// TAIL: processMatchedPoints' gate and the three dense clouds of a stream run at the end of its refinement workgroup instead of in four launches of their own --
-// the streams that converge early do that work while the slow ones still iterate (the stage lasts as long as its slowest stream: <= 15 dependent iterations),
-// and four launches per frame disappear.  Same device functions as the stand-alone kernels, the gate on the same 256 lanes: identical bits.
-using MoTail = svs_mo_tail;      // common.h
-template <bool TAIL>
-__global__ __launch_bounds__(MO2_THREADS) void motion_only_fused_kernel(const svs_match_result *__restrict__ res, int n, size_t res_bstride, svs_cam cam,
-                                                                        svs_pose_opt_params prm, double *__restrict__ T_io,
-                                                                        svs_pose_opt_stats *__restrict__ stats, MoTail Q, int spec) {
-  extern __shared__ int s_idx[];                   // [n]: indices of the status-OK records, in list order
-  __shared__ double s_part[MO2_WAVES][32];         // per wave: 28 sums (21 of J^T J, 6 of J^T w f, chi2), max error, max diag
-  __shared__ double s_Tn[12], s_Tc[12];        // trial pose / accepted pose (the latter is wave 0's)
-  __shared__ int s_wcnt[8][MO2_WAVES];
-  __shared__ int s_conv;                           // |B|_inf <= 1e-10 at the pose the pending step was taken from
-  // TAIL (batches): the streams in the grid order of the tracker (by the last frame's LM work: replicas / neighbours of the caller's order dealt evenly over the XCDs)
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, slot = TAIL && Q.order ? (Q.order[blockIdx.x] >> 4) : (int)blockIdx.x;
-  res += (size_t)slot * res_bstride;
-  // ---- compaction of obs_list / point_list (the OK records, in order).  Eight chunks per round: their status words are requested together
-  // (one memory round trip instead of eight), one barrier per round
-  int n_ok = 0;
-  for (int base = 0; base < n; base += 8 * MO2_THREADS) {
-    int st[8];
-#pragma unroll
-    for (int c = 0; c < 8; ++c) { const int i = base + c * MO2_THREADS + tid; st[c] = i < n ? res[i].status : 1; }
-    unsigned long long m[8];
-#pragma unroll
-    for (int c = 0; c < 8; ++c) { m[c] = __ballot(st[c] == 0); if (lane == 0) s_wcnt[c][wave] = __popcll(m[c]); }
-    __syncthreads();
-#pragma unroll
-    for (int c = 0; c < 8; ++c) {
-      int off = n_ok, tot = 0;
-#pragma unroll
-      for (int w = 0; w < MO2_WAVES; ++w) { const int k = s_wcnt[c][w]; off += w < wave ? k : 0; tot += k; }
-      if (st[c] == 0) s_idx[off + __popcll(m[c] & ((1ull << lane) - 1ull))] = base + c * MO2_THREADS + tid;
-      n_ok += tot;
-    }
-    __syncthreads();
-  }
-  MoObs ob[MO2_RC];
-#pragma unroll
-  for (int k = 0; k < MO2_RC; ++k) {
-    const int j = tid + k * MO2_THREADS;
-    if (j < n_ok) {
-      const svs_match_result &r = res[s_idx[j]];
-#pragma unroll
-      for (int c = 0; c < 3; ++c) { ob[k].o[c] = r.obs[c]; ob[k].q[c] = r.xyz_actkey[c]; }
-    }
-  }
-  auto total = [&](int id) { double s = s_part[0][id]; for (int w = 1; w < MO2_WAVES; ++w) s += s_part[w][id]; return s; };
-  auto total_max = [&](int id) { double s = s_part[0][id]; for (int w = 1; w < MO2_WAVES; ++w) s = fmax(s, s_part[w][id]); return s; };
-  // the pose of a sweep is wave-uniform: read once, moved to scalar registers (24 SGPRs instead of 24 VGPRs per lane)
-  auto uniform_pose = [&](const double *p, double (&T)[12]) {
-#pragma unroll
-    for (int i = 0; i < 12; ++i) {
-      const double v = p[i];
-      T[i] = __hiloint2double(__builtin_amdgcn_readfirstlane(__double2hiint(v)), __builtin_amdgcn_readfirstlane(__double2loint(v)));
-    }
-  };
-  double Tn[12];
-  uniform_pose(T_io + 12 * slot, Tn);
-  if (tid < 12) s_Tc[tid] = T_io[12 * slot + tid];
-  mo2_sweep<true>(Tn, ob, n_ok, s_idx, res, cam, prm.robust_kernel, prm.kernel_param, s_part);
-  __syncthreads();                                 // (A) sums of the sweep are in s_part
-  const int num_obs = n_ok;
-  double chi2 = total(27), max_err = total_max(28), mu = prm.initial_mu == -1 ? prm.tau * total_max(29) : prm.initial_mu, nu = 2;
-  const double initial_chi2 = chi2;
-  int status = num_obs == 0 ? 1 : (num_obs < prm.min_obs ? 3 : 0), trial = 0;
-  bool stop = status != 0;
-  // wave 0, lane c < 6: column c of the stored J^T J; lane 6: -J^T w f
-  double col[6] = {0, 0, 0, 0, 0, 0};
-  auto load_system = [&]() {
-    if (wave == 0 && lane < 7) {
-#pragma unroll
-      for (int r = 0; r < 6; ++r) {
-        const int a = r < lane ? r : lane, b = r < lane ? lane : r;      // upper-triangular index of (r, lane)
-        col[r] = lane < 6 ? total(a * (13 - a) / 2 + (b - a)) : -total(21 + r);
-      }
-    }
-  };
-  load_system();
-  // Two barriers per LM trial: (B) the trial pose is in s_Tn and every wave has read the sums of the sweep before; (A) the new sums are in s_part.
-  for (int ig = 0; ig < prm.num_iter && !stop; ++ig) {
-    double rho = 0;
-    do {
-      if (wave == 0) {
-        // (A + mu I) delta = B on lanes 0..6 (wave_solve6)
-        double a[6], bmax = 0, delta[6];
-#pragma unroll
-        for (int r = 0; r < 6; ++r) a[r] = col[r] + (r == lane ? mu : 0.0);
-#pragma unroll
-        for (int r = 0; r < 6; ++r) bmax = fmax(bmax, fabs(mo2_bcast(col[r], 6)));
-        wave_solve6(a, delta);
-        double Tc[12], Tx[12];
-#pragma unroll
-        for (int i = 0; i < 12; ++i) Tc[i] = s_Tc[i];
-        mo2_exp_mul(delta, Tc, Tx);                  // prediction.add: exp(delta) * T (every lane of the wave, same values)
-        if (lane < 12) {
-          double v = Tx[0];
-#pragma unroll
-          for (int i = 1; i < 12; ++i) v = lane == i ? Tx[i] : v;
-          s_Tn[lane] = v;
-        }
-        if (lane == 0) s_conv = bmax <= 1e-10 ? 1 : 0;
-      }
-      __syncthreads();                               // (B)
-      uniform_pose(s_Tn, Tn);
-      const int conv = s_conv;
-      // A trial that follows a rejection is almost always rejected too (every refinement ends in five rejections in a row at the noise floor of its chi2: a third
-      // of all sweeps), and a rejected trial's Jacobian sums are never used: such a trial gets a chi2-only sweep ("mo_spec"); should it be accepted after all, the
-      // full sweep at the same pose follows.  Either way the sums the loop goes on with are those of the full sweep: identical bits.
-      const bool lean = spec != 0 && trial >= 1;
-      if (lean) mo2_sweep_chi2(Tn, ob, n_ok, s_idx, res, cam, prm.robust_kernel, prm.kernel_param, s_part);
-      else mo2_sweep<false>(Tn, ob, n_ok, s_idx, res, cam, prm.robust_kernel, prm.kernel_param, s_part);
-      __syncthreads();                               // (A)
-      const double new_chi2 = total(27), new_max = total_max(28);
-      if (isnan(new_chi2)) { status = 2; stop = true; break; }      // the reference throws here
-      rho = chi2 - new_chi2;
-      if (rho > 0 && lean) {
-        __syncthreads();                             // every lane has read the totals
-        mo2_sweep<false>(Tn, ob, n_ok, s_idx, res, cam, prm.robust_kernel, prm.kernel_param, s_part);
-        __syncthreads();
-      }
-      if (rho > 0) {
-        if (tid < 12) s_Tc[tid] = s_Tn[tid];         // wave 0 only: it is the one that reads s_Tc (next solve) and rewrites s_Tn (after it)
-        chi2 = new_chi2; max_err = new_max;
-        load_system();
-        stop = conv != 0;                            // |B|_inf <= 1e-10 at the pose the accepted step started from
-        const double q = 2 * rho - 1, sc = 1 - q * q * q;
-        mu *= fmax(1. / 3., sc);
-        nu = 2.; trial = 0;
-      } else {
-        mu *= nu; nu *= 2.; ++trial;
-        if (trial == 5) stop = true;
-      }
-    } while (!(rho > 0 || stop));
-  }
-  if (tid < 12) T_io[12 * slot + tid] = s_Tc[tid];
-  if (tid == 0) {
-    svs_pose_opt_stats st;
-    st.initial_chi2 = initial_chi2; st.chi2 = chi2; st.max_err = max_err; st.num_obs = num_obs; st.status = status;
-    stats[slot] = st;
-  }
-  if constexpr (TAIL) {
-    __shared__ int s_gcnt[18];
-    __shared__ double s_gsum[4];
-    __syncthreads();                                 // s_Tc is final
-    double T[12];
-#pragma unroll
-    for (int i = 0; i < 12; ++i) T[i] = s_Tc[i];
-    gate_stream(res, Q.pts + slot * Q.pts_b, n, Q.n_new[slot], cam, T, Q.mre, Q.gated + slot * Q.gated_b, Q.ptstats + slot, tid, s_gcnt, s_gsum);
-#pragma unroll 1
-    for (int l = 0; l < 3; ++l) {
-      double TQ[16];
-      cloud_TQ(T, Q.cams[l], TQ);
-      const int cw = Q.cams[l].w / 4, n_px = cw * (Q.cams[l].h / 4);
-      const float *disp = Q.disp + slot * Q.disp_b;
-      float *cloud = Q.cloud[l] + slot * Q.cloud_b[l];
-      for (int i = tid; i < n_px; i += MO2_THREADS) cloud_sample(disp, Q.ds, cw, l, TQ, i, cloud);
-    }
-  }
-}
-
-}  // namespace
-// ---- StereoFrontend::processMatchedPoints (stereo_frontend.cpp:834-974), data-parallel part ---------------------------
-// One workgroup per stream sweeps the matcher records: reprojection gate at the refined pose, the 2x2 / 3x3 / per-level
-// counters (LDS atomics), the pyramid-level positions the host needs for point_tree and the draw lists, and the
-// track-length sum.  The host-side remainder (building new_point_list / track_point_list) walks the flags.
-namespace {
-__global__ __launch_bounds__(256) void gate_matched_kernel(const svs_match_result *__restrict__ res, const svs_candidate_point *__restrict__ pts, int n,
-                                                           size_t res_b, size_t pts_b, int n_new, const int32_t *__restrict__ n_new_arr, svs_cam cam,
-                                                           const double *__restrict__ Tarr, float mre, svs_gated_point *__restrict__ out, size_t out_b,
-                                                           svs_point_stats *__restrict__ stats) {
-  __shared__ int s_cnt[18];          // 4 + 9 + 3 + num_track + num_obs
-  __shared__ double s_sum[4];
-  const int tid = threadIdx.x, slot = blockIdx.x;
-  if (n_new_arr) n_new = n_new_arr[slot];
-  double T[12];
-#pragma unroll
-  for (int k = 0; k < 12; ++k) T[k] = Tarr[12 * slot + k];
-  gate_stream(res + slot * res_b, pts + slot * pts_b, n, n_new, cam, T, mre, out + slot * out_b, stats + slot, tid, s_cnt, s_sum);
-}
-}  // namespace
-
-extern "C" int svs_process_matched_points(svs_ctx *ctx, const svs_match_result *d_results, const svs_candidate_point *d_pts, int n,
-                                          size_t res_bstride, size_t pts_bstride, int n_new_records, const svs_cam *cam, const double *d_T,
-                                          float max_reproj_error, svs_gated_point *d_gated, size_t gated_bstride, svs_point_stats *d_stats,
-                                          int batch) {
-  SVS_REQUIRE(ctx, ctx && cam && d_T && d_stats && batch >= 1 && n >= 0 && (n == 0 || (d_results && d_pts && d_gated)));
-  SVS_DEVICE(ctx);
-  hipLaunchKernelGGL(gate_matched_kernel, dim3(batch), dim3(256), 0, ctx->stream, d_results, d_pts, n, res_bstride, pts_bstride, n_new_records,
-                     (const int32_t *)nullptr, *cam, d_T, max_reproj_error, d_gated, gated_bstride, d_stats);
-  SVS_LAUNCH_CHECK(ctx);
-  return SVS_OK;
-}
-// the same with one record count of the new-feature lists PER STREAM, on the device (frontend.hip: streams carry different candidate lists)
-int svs_process_matched_points_dev(svs_ctx *ctx, const svs_match_result *d_results, const svs_candidate_point *d_pts, int n, size_t res_bstride,
-                                   size_t pts_bstride, const int32_t *d_n_new_records, const svs_cam *cam, const double *d_T, float max_reproj_error,
-                                   svs_gated_point *d_gated, size_t gated_bstride, svs_point_stats *d_stats, int batch) {
-  SVS_REQUIRE(ctx, ctx && cam && d_T && d_stats && d_n_new_records && batch >= 1 && n >= 0 && (n == 0 || (d_results && d_pts && d_gated)));
-  SVS_DEVICE(ctx);
-  hipLaunchKernelGGL(gate_matched_kernel, dim3(batch), dim3(256), 0, ctx->stream, d_results, d_pts, n, res_bstride, pts_bstride, 0, d_n_new_records, *cam, d_T,
-                     max_reproj_error, d_gated, gated_bstride, d_stats);
-  SVS_LAUNCH_CHECK(ctx);
-  return SVS_OK;
-}
-
-// calcFastMotionOnly + processMatchedPoints' gate + the three dense clouds of every stream in ONE launch (frontend.hip; see MoTail).  Returns SVS_ERR_UNSUPPORTED
-// when the fused refinement kernel does not apply (the caller then takes the separate launches).
-int svs_motion_only_gate_cloud(svs_ctx *ctx, const svs_match_result *d_results, int n, size_t res_bstride, const svs_cam *cam, const svs_pose_opt_params *prm,
-                               double *d_T_io, svs_pose_opt_stats *d_stats, const svs_mo_tail *tail, int batch) {
-  SVS_REQUIRE(ctx, ctx && cam && prm && d_T_io && d_stats && tail && batch >= 1 && n >= 1 && d_results);
-  SVS_DEVICE(ctx);
-  if ((size_t)n * sizeof(int) > 48 * 1024 || ctx->mo_legacy) return SVS_ERR_UNSUPPORTED;
-  for (int l = 0; l < 3; ++l) SVS_REQUIRE(ctx, tail->cams[l].w % 4 == 0 && tail->cams[l].h % 4 == 0 && tail->cloud[l]);
-  hipLaunchKernelGGL(motion_only_fused_kernel<true>, dim3(batch), dim3(MO2_THREADS), (size_t)n * sizeof(int), ctx->stream, d_results, n, res_bstride, *cam, *prm, d_T_io,
-                     d_stats, *tail, ctx->mo_spec);
-  SVS_LAUNCH_CHECK(ctx);
-  return SVS_OK;
-}
-
-extern "C" int svs_motion_only(svs_ctx *ctx, const svs_match_result *d_results, int n, size_t res_bstride, const svs_cam *cam,
-                               const svs_pose_opt_params *prm, double *d_T_io, svs_pose_opt_stats *d_stats, int batch) {
-  SVS_REQUIRE(ctx, ctx && cam && prm && d_T_io && d_stats && batch >= 1 && n >= 0 && (n == 0 || d_results));
-  SVS_DEVICE(ctx);
-  // the record-walking kernel stays for candidate lists whose index list does not fit LDS, and as the A/B partner ("mo_legacy")
-  if ((size_t)n * sizeof(int) <= 48 * 1024 && !ctx->mo_legacy)
-    hipLaunchKernelGGL(motion_only_fused_kernel<false>, dim3(batch), dim3(MO2_THREADS), (size_t)std::max(n, 1) * sizeof(int), ctx->stream, d_results, n, res_bstride, *cam,
-                       *prm, d_T_io, d_stats, MoTail{}, ctx->mo_spec);
-  else
-    hipLaunchKernelGGL(motion_only_kernel, dim3(batch), dim3(MO_THREADS), 0, ctx->stream, d_results, n, res_bstride, *cam, *prm, d_T_io, d_stats);
   SVS_LAUNCH_CHECK(ctx);
   return SVS_OK;
 }

@@ -27,6 +27,7 @@
 //    rounding through f64 is innocuous for a quotient of two f32 numbers, and a 2^-52 perturbation cannot reach an f32
 //    rounding boundary, which a quotient of two 24-bit numbers misses by >= 2^-49 relative).
 #include "common.h"
+#include "lm6.h"      // d_solve6, d_se3_exp_mul: the LM step runs on one lane
 #include <algorithm>
 
 namespace {
@@ -283,66 +284,6 @@ __device__ __forceinline__ void full_sweep(const FullLevel &L, const M34 &T, int
   }
 }
 
-// ---- 6x6 solve + SE3 exp (as in dense.hip; the LM step runs on one lane) -----------------------------------------
-__device__ void f_solve6(const double *A, const double *b, double *x) {
-  double M[6][7];
-#pragma unroll
-  for (int i = 0; i < 6; ++i) {
-#pragma unroll
-    for (int j = 0; j < 6; ++j) M[i][j] = A[i * 6 + j];
-    M[i][6] = b[i];
-  }
-#pragma unroll
-  for (int k = 0; k < 6; ++k) {
-    int p = k;
-    double best = fabs(M[k][k]);
-#pragma unroll
-    for (int i = k + 1; i < 6; ++i) { const double v = fabs(M[i][k]); if (v > best) { best = v; p = i; } }
-#pragma unroll
-    for (int i = k + 1; i < 6; ++i) {
-      const bool sw = p == i;
-#pragma unroll
-      for (int j = k; j < 7; ++j) { const double a = M[k][j], c = M[i][j]; M[k][j] = sw ? c : a; M[i][j] = sw ? a : c; }
-    }
-    const double piv = M[k][k];
-#pragma unroll
-    for (int i = k + 1; i < 6; ++i) {
-      const double f = M[i][k] / piv;
-#pragma unroll
-      for (int j = k; j < 7; ++j) M[i][j] -= f * M[k][j];
-    }
-  }
-#pragma unroll
-  for (int i = 5; i >= 0; --i) {
-    double s_ = M[i][6];
-#pragma unroll
-    for (int j = i + 1; j < 6; ++j) s_ -= M[i][j] * x[j];
-    x[i] = s_ / M[i][i];
-  }
-}
-__device__ void f_se3_exp_mul(const double *x, const double *T, double *Tn) {   // Tn = exp(x) * T
-  const double *w = x + 3;
-  double th2 = w[0] * w[0] + w[1] * w[1] + w[2] * w[2], th = sqrt(th2);
-  double W[9] = {0, -w[2], w[1], w[2], 0, -w[0], -w[1], w[0], 0}, W2[9], R[9], V[9];
-  for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) W2[3 * i + j] = W[3 * i] * W[j] + W[3 * i + 1] * W[3 + j] + W[3 * i + 2] * W[6 + j];
-  double a, b;
-  if (th < 1e-10) { a = 1.0 - th2 / 6.0; b = 0.5 - th2 / 24.0; } else { a = sin(th) / th; b = (1.0 - cos(th)) / th2; }
-  for (int i = 0; i < 9; ++i) R[i] = a * W[i] + b * W2[i];
-  R[0] += 1; R[4] += 1; R[8] += 1;
-  if (th < 1e-10) { for (int i = 0; i < 9; ++i) V[i] = R[i]; }
-  else {
-    double c = (1.0 - cos(th)) / th2, d = (th - sin(th)) / (th2 * th);
-    for (int i = 0; i < 9; ++i) V[i] = c * W[i] + d * W2[i];
-    V[0] += 1; V[4] += 1; V[8] += 1;
-  }
-  double t[3];
-  for (int i = 0; i < 3; ++i) t[i] = V[3 * i] * x[0] + V[3 * i + 1] * x[1] + V[3 * i + 2] * x[2];
-  for (int i = 0; i < 3; ++i) {
-    for (int j = 0; j < 4; ++j) Tn[4 * i + j] = R[3 * i] * T[j] + R[3 * i + 1] * T[4 + j] + R[3 * i + 2] * T[8 + j];
-    Tn[4 * i + 3] += t[i];
-  }
-}
-
 // ---- cross-workgroup words: write-through stores / L1-bypassing loads, agent scope --------------------------------
 __device__ __forceinline__ void st_agent(double *p, double v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 __device__ __forceinline__ double ld_agent(const double *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
@@ -510,8 +451,8 @@ __global__ __launch_bounds__(FULL_THREADS, FULL_MINW) void dense_track_full_kern
         for (int c = 0; c < 6; ++c) for (int r = 0; r <= c; ++r) { H[6 * r + c] = s_H[k]; H[6 * c + r] = s_H[k]; ++k; }
         for (int q = 0; q < 6; ++q) H[7 * q] += mu * H[7 * q];
         for (int q = 0; q < 6; ++q) nb[q] = -s_b[q];
-        f_solve6(H, nb, x);
-        f_se3_exp_mul(x, s_T, Tn);
+        d_solve6(H, nb, x);
+        d_se3_exp_mul(x, s_T, Tn);
         for (int q = 0; q < 12; ++q) s_Teval[q] = Tn[q];
       }
       s_ctl[0] = lvl;

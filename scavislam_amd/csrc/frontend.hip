@@ -1,7 +1,7 @@
 // frontend.hip -- one call per camera frame: the data-parallel part of StereoFrontend::processFrame
 // (stereo_frontend.cpp:183-306), for ONE stream with host buffers in and out (the way stereo_slam's main loop calls it,
 // stereo_slam.cpp:705) or for a BATCH of independent camera streams whose frames are already in device memory.  Chains the
-// kernels of image.hip / dense.hip / dense_full.hip / stereo.hip / fast.hip / match.hip on the context's stream without a host
+// kernels of image.hip / dense.hip / motion.hip / dense_full.hip / stereo.hip / fast.hip / match.hip on the context's stream without a host
 // round trip in between:
 //   upload (pinned staging, optionally prefetched on a copy stream while the frame before is processed)
 //   -> FrameGrabber::preprocessing (u8 pyramid; CUDA build: + f32 pyramid and derivatives)       frame_grabber.cpp:285-336
