@@ -22,7 +22,7 @@ constexpr int NSUM = 28;   // 21 H + 6 b + chi2 ; n_valid kept separately
 
 struct Acc {
   double v[NSUM];
-  long long n;
+  int n;      // samples that contributed (a lane sees a few dozen per sweep; block_reduce widens it)
   __device__ __forceinline__ void zero() {
 #pragma unroll
     for (int i = 0; i < NSUM; ++i) v[i] = 0;
@@ -75,27 +75,71 @@ __device__ __forceinline__ uint32_t load_u32_unaligned(const SVS_AS1 uint8_t *p)
 // the results are bit-identical to reading the f32 pyramids -- at 1/8 of the HBM traffic (the f32
 // path touches ~half of three 4 B/px images per pass for a 1/16 sampling grid).  In-frame samples
 // (border 2) never need the REFLECT_101 border rule.
-template <class P>
-__device__ __forceinline__ void taps_u8(P img, int stride, float u, float v, float &ic, float &gx, float &gy) {
+// The four rows of a sample's 4 x 4 neighbourhood, one dword each, in two steps: taps_u8_issue puts the four requests in flight, taps_u8_wait makes them usable.
+// What the caller places between the two runs under ONE memory round trip.  TapRows::w must not be touched in between (tools/tracker_loop_isa.py checks the ISA).
+struct TapRows { uint32_t w[4]; };
+constexpr bool TRK_TAPS_ASM = true;
+// ASM: the loads as one inline-asm statement and the wait as a second one that names all four destinations (the form seq_load_run uses for its ten loads).  Left to
+// the compiler, the flat tracker kernel at its 128-register limit waited for row 0 -- and with it for the store and the prefetch in front of it -- before it issued
+// rows 1..3 into row 0's register: two dependent round trips per sample (profiles/tracker_taps.md).  The base comes from scalar registers (the stream's image, and
+// the same moved down by one, two and three rows), the one vector operand is the 32-bit offset of row 0: no destination can alias an address still to be read.
+template <bool ASM, class P>
+__device__ __forceinline__ void taps_u8_issue(P img, int stride, float u, float v, TapRows &t) {
+  const int xi = (int)floorf(u), yi = (int)floorf(v);
+  // 32-bit offsets from the stream's (scalar) image pointer: the tap loads take the base from scalar registers and the sweep spends no 64-bit multiply-adds
+  // (quarter rate) on addresses.  In-frame samples (border 2) keep yi - 1 >= 1 and xi - 1 >= 1: the offsets are non-negative and far below 2^31; rows and
+  // strides are below 2^24 (offsets_fit_24: the host refuses anything else), so the product is a 24-bit multiply (full rate; v_mul_lo_u32 is quarter rate)
+  const unsigned o0 = __umul24(yi - 1, stride) + (unsigned)(xi - 1);
+  __builtin_amdgcn_sched_barrier(0);
+  if constexpr (ASM) {
+    // (image and stride are the stream's: the same in every lane.  Where the compiler cannot see that -- the level came through memory -- they are read from lane 0)
+    const unsigned long long bv = (unsigned long long)img;
+    const unsigned long long b0 = ((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(bv >> 32)) << 32) | (unsigned)__builtin_amdgcn_readfirstlane((int)bv);
+    const unsigned long long rs = (unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane(stride);
+    asm("global_load_dword %0, %4, %5\n\t"
+        "global_load_dword %1, %4, %6\n\t"
+        "global_load_dword %2, %4, %7\n\t"
+        "global_load_dword %3, %4, %8"
+        : "=&v"(t.w[0]), "=&v"(t.w[1]), "=&v"(t.w[2]), "=&v"(t.w[3])
+        : "v"(o0), "s"(b0), "s"(b0 + rs), "s"(b0 + 2 * rs), "s"(b0 + 3 * rs));
+    // (neither volatile nor a "memory" clobber: nothing writes the image while the tracker runs, the wait below is tied to the loads through their registers, and the
+    // scheduling fences keep both where they are written)
+  } else {
+#pragma unroll
+    for (int r = 0; r < 4; ++r) t.w[r] = load_u32_unaligned(img + (o0 + (unsigned)(r * stride)));
+  }
+  __builtin_amdgcn_sched_barrier(0);
+}
+template <bool ASM>
+__device__ __forceinline__ void taps_u8_wait(TapRows &t) {
+  __builtin_amdgcn_sched_barrier(0);
+  if constexpr (ASM) {
+    // (the four are the youngest requests of the lane, so the count that covers them is zero.  The compiler does not count them: a wait of its own in between
+    // would be for something older and only wait longer -- the caller puts nothing there that reads memory)
+    asm("s_waitcnt vmcnt(0)" : "+v"(t.w[0]), "+v"(t.w[1]), "+v"(t.w[2]), "+v"(t.w[3]));
+    __builtin_amdgcn_sched_barrier(0);
+  }
+}
+__device__ __forceinline__ void taps_u8_finish(const TapRows &t, float u, float v, float &ic, float &gx, float &gy) {
   const float sc = (float)(1. / 255.);
   const float x = floorf(u), y = floorf(v);
   const float sx = u - x, sy = v - y;
   const float wx0 = 1 - sx, wx1 = sx, wy0 = 1 - sy, wy1 = sy;
-  const int xi = (int)x, yi = (int)y;
   float f[4][4];
-  // 32-bit offsets from the stream's (scalar) image pointer: the tap loads take the base from scalar registers and the sweep spends no 64-bit multiply-adds
-  // (quarter rate) on addresses.  In-frame samples (border 2) keep yi - 1 >= 1 and xi - 1 >= 1: the offsets are non-negative and far below 2^31
-  const unsigned o0 = (unsigned)((yi - 1) * stride + (xi - 1));
 #pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    const uint32_t w4 = load_u32_unaligned(img + (o0 + (unsigned)(r * stride)));
+  for (int r = 0; r < 4; ++r)
 #pragma unroll
-    for (int c = 0; c < 4; ++c) f[r][c] = (float)((w4 >> (8 * c)) & 0xff) * sc;
-  }
+    for (int c = 0; c < 4; ++c) f[r][c] = (float)((t.w[r] >> (8 * c)) & 0xff) * sc;
   const float w00 = wx0 * wy0, w01 = wx0 * wy1, w10 = wx1 * wy0, w11 = wx1 * wy1;   // v00=(x,y) v01=(x,y+1) v10=(x+1,y) v11
   ic = w00 * f[1][1] + w01 * f[2][1] + w10 * f[1][2] + w11 * f[2][2];
   gx = w00 * (f[1][2] - f[1][0]) + w01 * (f[2][2] - f[2][0]) + w10 * (f[1][3] - f[1][1]) + w11 * (f[2][3] - f[2][1]);
   gy = w00 * (f[2][1] - f[0][1]) + w01 * (f[3][1] - f[1][1]) + w10 * (f[2][2] - f[0][2]) + w11 * (f[3][2] - f[1][2]);
+}
+template <class P>
+__device__ __forceinline__ void taps_u8(P img, int stride, float u, float v, float &ic, float &gx, float &gy) {
+  TapRows t;
+  taps_u8_issue<false>(img, stride, u, v, t);
+  taps_u8_finish(t, u, v, ic, gx, gy);
 }
 
 // loop body of dense_tracking.cpp:229-261 (chi2) / :278-331 (H, b), one sample.
@@ -107,8 +151,8 @@ struct SampleIn { float4 c4; uint8_t prev; };
 template <class LA>
 __device__ __forceinline__ SampleIn sample_load(const LA &L, int u, int v, int cw, bool in_range) {
   SampleIn s;
-  s.c4 = in_range ? load_f4(L.cloud + 4u * (unsigned)(v * cw + u)) : make_float4(0.f, 0.f, 1.f, -1.f);
-  s.prev = L.prev[(unsigned)(((in_range ? v : 0) * 4) * L.pstride + (in_range ? u : 0) * 4)];
+  s.c4 = in_range ? load_f4(L.cloud + 4u * (__umul24(v, cw) + (unsigned)u)) : make_float4(0.f, 0.f, 1.f, -1.f);
+  s.prev = L.prev[__umul24((in_range ? v : 0) * 4, L.pstride) + (unsigned)((in_range ? u : 0) * 4)];
   return s;
 }
 // x / z and y / z share their denominator, and the Jacobian needs 1 / z again: one refined reciprocal serves all three.
@@ -149,10 +193,24 @@ __device__ __forceinline__ void sample_cpu_sem(const LA &L, const double *T, con
   if (!ok) { uvx = 2.f; uvy = 2.f; }                       // safe tap position, contribution masked below
   // (float)((1./255.) * u8): a double product rounded once (dense_tracking.cpp:290-293), NOT the f32 product convertTo
   // uses for the current image -- the tracker kernel keeps the 256 possible values in LDS (3 f64-rate instructions less)
+  // u8 source: the four row loads go out here, all of them before anything waits; what follows down to taps_u8_wait needs none of them and runs under their
+  // round trip -- the look-up of ip and the part of the Jacobian that depends on the pose alone (~25 f64 instructions)
   const float ip = ip_lut ? ip_lut[in.prev] : (float)((1. / 255.) * in.prev);
+  TapRows taps;
+  if constexpr (U8SRC) taps_u8_issue<TRK_TAPS_ASM>(L.cur8, L.c8stride, uvx, uvy, taps);
+  const double zs = ok ? z : 1.0, xs = ok ? x : 0.0, ys = ok ? y : 0.0;
+  // transformations.h:117-139 frame_jac_xyz2uv.  One reciprocal instead of eight f64 divisions and
+  // fused multiply-adds in the 27 accumulations: the pass is f64-issue bound on its CU, and H/b only
+  // need 1e-9 relative agreement with the serial oracle (uv above stays division-exact because the
+  // in-frame test and the tap addresses must match bit for bit).
+  // (every fused multiply-add written out: left to the compiler's contraction the two instantiations of this function -- f32 pyramids / u8 source -- fused
+  // different pairs, and their sums, which the tests hold bit-identical, drifted apart with every unrelated change to the kernel)
+  const double f = L.cam.f, iz = ok ? rz : 1.0, iz2 = iz * iz, fx = f * iz, xz = xs * iz2 * f, yz = ys * iz2 * f;
   float ic, g8x = 0.f, g8y = 0.f;
-  if (U8SRC) taps_u8(L.cur8, L.c8stride, uvx, uvy, ic, g8x, g8y);
+  if constexpr (U8SRC) { taps_u8_wait<TRK_TAPS_ASM>(taps); taps_u8_finish(taps, uvx, uvy, ic, g8x, g8y); }
   else ic = interp32f(L.cur, L.fstride, uvx, uvy);
+  const double r0[6] = {-fx, 0, xz, xz * ys, -__builtin_fma(xz, xs, f), ys * fx};
+  const double r1[6] = {0, -fx, yz, __builtin_fma(yz, ys, f), -(yz * xs), -(xs * fx)};
   float res = ip - ic;
   // dense_tracking.cpp:299-300 `if (res > 0.1) res = 0.1; if (res < -0.1) res = -0.1;` on a float res: the comparisons are made in double against the double 0.1,
   // which lies between 0.1f and the float below it, so `res > 0.1` is `res >= 0.1f` and the assignment stores 0.1f -- min / max with +-0.1f, bit for bit
@@ -166,17 +224,7 @@ __device__ __forceinline__ void sample_cpu_sem(const LA &L, const double *T, con
   if (JAC) {
     const float gx = ok ? (float)(0.5 * (U8SRC ? g8x : interp32f(L.dx, L.fstride, uvx, uvy))) : 0.f;
     const float gy = ok ? (float)(0.5 * (U8SRC ? g8y : interp32f(L.dy, L.fstride, uvx, uvy))) : 0.f;
-    const double zs = ok ? z : 1.0, xs = ok ? x : 0.0, ys = ok ? y : 0.0;
-    // transformations.h:117-139 frame_jac_xyz2uv.  One reciprocal instead of eight f64 divisions and
-    // fused multiply-adds in the 27 accumulations: the pass is f64-issue bound on its CU, and H/b only
-    // need 1e-9 relative agreement with the serial oracle (uv above stays division-exact because the
-    // in-frame test and the tap addresses must match bit for bit).
     {
-      // (every fused multiply-add written out: left to the compiler's contraction the two instantiations of this function -- f32 pyramids / u8 source -- fused
-      // different pairs, and their sums, which the tests hold bit-identical, drifted apart with every unrelated change to the kernel)
-      const double f = L.cam.f, iz = ok ? rz : 1.0, iz2 = iz * iz, fx = f * iz, xz = xs * iz2 * f, yz = ys * iz2 * f;
-      const double r0[6] = {-fx, 0, xz, xz * ys, -__builtin_fma(xz, xs, f), ys * fx};
-      const double r1[6] = {0, -fx, yz, __builtin_fma(yz, ys, f), -(yz * xs), -(xs * fx)};
       double J[6];
       J[0] = gx * r0[0];
       J[1] = gy * r1[1];
@@ -275,8 +323,11 @@ constexpr int TRK_UNROLL = 1;         // samples per lane and trip of the sweep 
 constexpr bool TRK_T_SCALAR = true;   // the pose of a sweep in scalar registers instead of 24 vector registers
 
 template <bool JAC, bool U8SRC, int TM = 0, class LA = LevelArgs>
-__device__ __forceinline__ void track_pass(const LA &L, const double *T_in, double (*s_part)[NSUM + 1], double *s_out, const float *ip_lut,
+__device__ __forceinline__ void track_pass(const LA &L_in, const double *T_in, double (*s_part)[NSUM + 1], double *s_out, const float *ip_lut,
                                            int first, int nwg, float *t_buf = nullptr) {      // first = wg * TRK_THREADS + tid; nwg workgroups share the sweep; t_buf: the pass's terms (TM), or null
+  // a copy of the sweep's own: where the caller's level lives in memory (the latency-mode kernel hands it to a lambda by reference) the scheduling fences around the
+  // tap loads would make every trip read it again
+  const LA L = L_in;
   const int cw = L.cam.w / 4, ch = L.cam.h / 4, n = cw * ch;
   // the pose of a sweep is the same in every lane: kept in scalar registers (24 vector registers less over the whole sweep -- the kernel is built for 128)
   double T[12];
@@ -304,17 +355,22 @@ __device__ __forceinline__ void track_pass(const LA &L, const double *T_in, doub
   // trip would be the youngest entry when the next trip waits for its prefetched operands at the top of the loop -- a full write round trip exposed per trip
   // (measured: + 18 % on the sweep); issued here it retires under the projection arithmetic and the tap loads that follow.
   // (the buffer's address space spelled out: the pointer comes out of a two-entry array indexed by the LM loop, and a flat store would tie the loop's LDS waits to memory)
+  // Its address is the buffer (uniform: a scalar base, moved back by one trip) plus a 32-bit byte offset formed from the sample index the loop carries anyway --
+  // no 64-bit pointer per lane to keep and advance (terms of a pass: far below 2^30)
   typedef __attribute__((address_space(1))) float *gptr_t;
+  typedef __attribute__((address_space(1))) char *gptr_c;
   static_assert(TM == 0 || TRK_UNROLL == 1, "the deferred term store keeps one term per lane");
   float pend_t = 0.f;
-  gptr_t pend_p = (gptr_t)t_buf + first - STEP;
+  const gptr_c pend_base = (gptr_c)(gptr_t)t_buf - 4 * (long)STEP;
   bool pend = false;
-  auto flush = [&]() {
+  int i = first;
+  auto flush = [&]() {      // the term of sample i - STEP
+    const gptr_t pend_p = (gptr_t)(pend_base + 4u * (unsigned)i);
     if constexpr (TM == 1) { if (pend) *pend_p = pend_t; }
     if constexpr (TM == 2) { if (pend) __hip_atomic_store(pend_p, pend_t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
   };
-  for (int i = first; i < n; i += STEP) {
-    if constexpr (TM != 0) { flush(); pend_p += STEP; pend = t_buf != nullptr; }
+  for (; i < n; i += STEP) {
+    if constexpr (TM != 0) { flush(); pend = t_buf != nullptr; }
     SampleIn cur[TRK_UNROLL];
 #pragma unroll
     for (int q = 0; q < TRK_UNROLL; ++q) {
@@ -1183,6 +1239,11 @@ __global__ __launch_bounds__(256) void residual_image_cpu_sem_kernel(LevelArgs L
 }  // namespace
 
 
+// the sample offsets are formed with 24-bit multiplies (sample_load, taps_u8_issue): rows, columns and row strides of a level stay below 2^24
+static bool offsets_fit_24(const svs_cam &cam, int pstride, int c8stride) {
+  const int lim = 1 << 24;
+  return cam.w > 0 && cam.h > 0 && cam.w < lim && cam.h < lim && pstride >= 0 && pstride < lim && c8stride >= 0 && c8stride < lim;
+}
 static int ensure_scratch(svs_ctx *ctx, double **p, size_t count) {      // ctx-owned (common.h)
   void *v = nullptr;
   const int rc = svs_ctx_scratch(ctx, count * sizeof(double), &v);
@@ -1199,6 +1260,7 @@ extern "C" int svs_dense_pass_cpu_sem(svs_ctx *ctx, const float *d_cloud, size_t
   SVS_DEVICE(ctx);
   SVS_REQUIRE(ctx, !do_jac || (d_dx && d_dy));
   SVS_REQUIRE(ctx, cam->w % 4 == 0 && cam->h % 4 == 0);
+  SVS_REQUIRE(ctx, offsets_fit_24(*cam, pstride, 0));
   LevelArgs L{d_cloud, d_prev_u8, d_cur, d_dx, d_dy, pstride, fstride, *cam, nullptr, 0};
   int n = (cam->w / 4) * (cam->h / 4);
   int nblocks = std::min(div_up(n, 256), 256);
@@ -1443,6 +1505,7 @@ int svs_dense_track_cpu_sem_work(svs_ctx *ctx, const svs_dense_track_args *a, do
     SVS_REQUIRE(ctx, a->d_cloud[l] && a->d_prev_u8[l]);
     SVS_REQUIRE(ctx, u8src ? a->d_cur_u8[l] != nullptr : (a->d_cur[l] && a->d_dx[l] && a->d_dy[l]));
     SVS_REQUIRE(ctx, a->cam_vec[l].w % 4 == 0 && a->cam_vec[l].h % 4 == 0);
+    SVS_REQUIRE(ctx, offsets_fit_24(a->cam_vec[l], a->pstride[l], u8src ? a->c8stride[l] : 0));
     A.lv[l] = LevelArgs{a->d_cloud[l], a->d_prev_u8[l], a->d_cur[l], a->d_dx[l], a->d_dy[l], a->pstride[l], a->fstride[l], a->cam_vec[l],
                         a->d_cur_u8[l], a->c8stride[l]};
     A.cloud_b[l] = a->cloud_bstride[l]; A.prev_b[l] = a->p_bstride[l]; A.f_b[l] = a->f_bstride[l]; A.c8_b[l] = a->c8_bstride[l];
@@ -1542,6 +1605,7 @@ extern "C" int svs_dense_residual_image_cpu_sem(svs_ctx *ctx, const float *d_clo
   SVS_REQUIRE(ctx, ctx && d_cloud && d_prev_u8 && (d_cur || d_cur_u8) && cam && d_T && d_res_img4 && batch >= 1);
   SVS_DEVICE(ctx);
   SVS_REQUIRE(ctx, cam->w % 4 == 0 && cam->h % 4 == 0);
+  SVS_REQUIRE(ctx, offsets_fit_24(*cam, pstride, d_cur_u8 ? c8stride : 0));
   LevelArgs L{d_cloud, d_prev_u8, d_cur, nullptr, nullptr, pstride, fstride, *cam, d_cur_u8, c8stride};
   const int n = (cam->w / 4) * (cam->h / 4);
   if (d_cur_u8)
