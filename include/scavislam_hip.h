@@ -506,6 +506,38 @@ int svs_frontend_recompute_cloud(svs_frontend *fe, const double *T_cur_from_actk
 int svs_frontend_device_view(svs_frontend *fe, int stream, const uint8_t **d_pyr_last, int32_t *stride, const float **d_disp, const float **d_cloud,
                              svs_fast **fast);
 
+/* ---- between the camera and processFrame: the three per-pixel input conversions of FrameGrabber::processNextFrame (frame_grabber.cpp:125-186), for a
+   caller whose frames are raw (lens-distorted, colour, or depth instead of disparity).  Bit-exact to the OpenCV 2.4 semantics restated in
+   tests/rectify_model.py.  The outputs are meant for the buffers svs_frontend_input_view hands out, followed by
+   svs_frontend_first_frames / svs_frontend_process_frames with in == NULL (any n_streams, 1 included). ------------------------------------------*/
+/* cv::initUndistortRectifyMap(K, dist, R, Knew, (w, h), CV_16SC2, map1, map2) as intializeRectifier() calls it (frame_grabber-impl.cpp:93-134): K, R, Knew
+   row-major 3 x 3, dist = (k1, k2, p1, p2, k3) = cam.dist_*1..5.  map_xy [h][w][2] int16 (x0, y0), map_frac [h][w] uint16 (fx = frac & 31, fy = frac >> 5).
+   Host only: needs neither a context nor a device.  f64 in a fixed operation order; an entry can differ from OpenCV's own by 1/32 px at a rounding tie (it
+   accumulates along a row and inverts by LU), which is why svs_rectify_create takes MAPS: a host that has OpenCV passes rect_map_left_[0] / [1] as they are */
+int svs_rectify_build_maps(const double *K, const double *dist, const double *R, const double *Knew, int w, int h, int16_t *map_xy, uint16_t *map_frac);
+typedef struct svs_rectify svs_rectify;
+/* w x h frames (w a multiple of 4, both <= 2046), at most max_batch streams per call.  Maps are HOST pointers in the layout above, copied (repacked) here;
+   map_frac > 1023 anywhere: SVS_ERR_INVALID.  NULL maps for a side: conversion / copy only, no remap (data/newcollege.cfg: colour, already rectified).
+   NULL right maps and never a right image: the disparity-given case */
+int svs_rectify_create(svs_ctx *ctx, int w, int h, int max_batch, const int16_t *h_left_xy, const uint16_t *h_left_frac, const int16_t *h_right_xy,
+                       const uint16_t *h_right_frac, svs_rectify **out);
+int svs_rectify_destroy(svs_rectify *r);
+typedef struct {                       /* raw frames of all streams in device memory: stream b at + b * bstride; strides in BYTES */
+  const uint8_t *d_left; int32_t lstride; size_t l_bstride;
+  int32_t left_channels;               /* 1: gray; 3: interleaved B, G, R -> cv::cvtColor(CV_BGR2GRAY) (framepipe.color_img, frame_grabber.cpp:140-147) */
+  const uint8_t *d_right; int32_t rstride; size_t r_bstride;   /* gray; NULL: no right image */
+  void *ready_event;                   /* as in svs_frames_dev: NULL, or the hipEvent_t behind whatever produces the frames */
+} svs_raw_frames_dev;
+/* rectifyFrame() (frame_grabber.cpp:245-256) for every stream: cv::remap(CV_INTER_LINEAR, BORDER_CONSTANT 0) of left and right through the handle's maps,
+   colour conversion of the left image fused in.  ASYNCHRONOUS on the context's stream.  Output strides in elements, multiples of 4, pointers 4-byte aligned;
+   d_right_out NULL exactly when raw->d_right is.  Correct for ANY map (a tap outside the source reads 0, decided per tap); fast for smooth lens maps */
+int svs_rectify_frames(svs_rectify *r, const svs_raw_frames_dev *raw, uint8_t *d_left_out, int lstride, size_t l_bstride, uint8_t *d_right_out, int rstride,
+                       size_t r_bstride, int n_batch);
+/* depthToDisp() (frame_grabber-impl.cpp:136-152, stereo_camera.cpp:55-59; framepipe.depth_img, frame_grabber.cpp:163-170): 16-bit depth (1/5000 m) -> float
+   disparity with cam->f and cam->b; cam->w x cam->h pixels per stream, strides in elements.  depth 0 gives +inf, as the reference does.  ASYNCHRONOUS */
+int svs_depth_to_disp(svs_ctx *ctx, const svs_cam *cam, const uint16_t *d_depth16, int stride, size_t bstride, float *d_disp, int dstride, size_t d_bstride,
+                      int n_batch);
+
 /* ---- multi-GPU: the library-owned collective of the landmark-sharded back-end.  The reference has no
    distributed code; one process per GPU each creates a context and a communicator (RCCL, bound at run time) --------------*/
 typedef struct { char bytes[128]; } svs_unique_id;      /* = ncclUniqueId */

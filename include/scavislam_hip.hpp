@@ -11,6 +11,7 @@
 //   GpuTracker / DenseTrackerGpu <- gpu/dense_tracking.cuh:281-342, DenseTracker::denseTrackingGpu (dense_tracking.cpp:60-215)
 //   StereoFrontend  <- StereoFrontend::processFrame / processFirstFrame, scavislam/stereo_frontend.h:88-95 (one call per frame)
 //   SlamGraphBA     <- SlamGraph::optimize, scavislam/slam_graph.hpp:457-462
+//   FrameRectifier  <- FrameGrabber<StereoCamera>::intializeRectifier / rectifyFrame / depthToDisp, scavislam/frame_grabber.cpp:245-256, frame_grabber-impl.cpp:93-152
 //   Communicator    <- (no reference counterpart) landmark-sharded optimize over RCCL, SURVEY.md 8e
 //
 // One svs_ctx per calling thread (front-end on main, re-registration matcher/FAST + optimize on
@@ -18,6 +19,7 @@
 #ifndef SCAVISLAM_HIP_HPP
 #define SCAVISLAM_HIP_HPP
 
+#include <cmath>
 #include <cstdint>
 #include <cstdio>
 #include <algorithm>
@@ -558,6 +560,62 @@ class StereoFrontend {
   svs_frontend *fe_;
   bool ok_;
   int n_ = 0;
+};
+
+// The per-pixel input conversions of FrameGrabber<StereoCamera> (frame_grabber.cpp:125-186, frame_grabber-impl.cpp:93-152) on device frames of n streams:
+// intializeRectifier() builds the CV_16SC2 maps on the host the way the reference calls cv::initUndistortRectifyMap (R = SO3::exp(cam.rot*_left / _right),
+// new camera matrix = the camera matrix for both sides); rectifyFrame() is cv::cvtColor + cv::remap; depthToDisp() the depth-camera case.
+class FrameRectifier {
+ public:
+  FrameRectifier(const Context &c, const svs_cam &cam, int max_batch = 1) : ctx_(c), cam_(cam), max_batch_(max_batch), rect_(nullptr) {}
+  ~FrameRectifier() { if (rect_) svs_rectify_destroy(rect_); }
+  FrameRectifier(const FrameRectifier &) = delete;
+  FrameRectifier &operator=(const FrameRectifier &) = delete;
+  // SO3::exp of a rotation vector, row-major
+  static void rodrigues(const double rv[3], double R[9]) {
+    const double th2 = rv[0] * rv[0] + rv[1] * rv[1] + rv[2] * rv[2], th = std::sqrt(th2);
+    const double A = th < 1e-12 ? 1.0 : std::sin(th) / th, B = th < 1e-12 ? 0.0 : (1.0 - std::cos(th)) / (th * th);
+    const double Kx[9] = {0.0, -rv[2], rv[1], rv[2], 0.0, -rv[0], -rv[1], rv[0], 0.0};
+    for (int r = 0; r < 3; ++r)
+      for (int c = 0; c < 3; ++c) {
+        double k2 = 0.0;
+        for (int k = 0; k < 3; ++k) k2 += Kx[3 * r + k] * Kx[3 * k + c];
+        R[3 * r + c] = (r == c ? 1.0 : 0.0) + A * Kx[3 * r + c] + B * k2;
+      }
+  }
+  // rot_* : cam.rot{x,y,z}_left / _right; dist_* : cam.dist_left1..5 / cam.dist_right1..5 (k1, k2, p1, p2, k3).  with_right = false: a left image only
+  // (framepipe.disp_img / depth_img)
+  bool intializeRectifier(const double rot_left[3], const double dist_left[5], const double rot_right[3], const double dist_right[5], bool with_right = true) {
+    const double K[9] = {cam_.f, 0.0, cam_.cx, 0.0, cam_.f, cam_.cy, 0.0, 0.0, 1.0};
+    const size_t n = (size_t)cam_.w * cam_.h;
+    std::vector<int16_t> xy[2];
+    std::vector<uint16_t> fr[2];
+    for (int s = 0; s < (with_right ? 2 : 1); ++s) {
+      double R[9];
+      rodrigues(s ? rot_right : rot_left, R);
+      xy[s].resize(2 * n); fr[s].resize(n);
+      if (!ctx_.check(svs_rectify_build_maps(K, s ? dist_right : dist_left, R, K, cam_.w, cam_.h, xy[s].data(), fr[s].data()))) return false;
+    }
+    return setMaps(xy[0].data(), fr[0].data(), with_right ? xy[1].data() : nullptr, with_right ? fr[1].data() : nullptr);
+  }
+  // maps made elsewhere (rect_map_left_[0] / [1], rect_map_right_[0] / [1] of a host that has OpenCV); NULL for a side: conversion / copy only
+  bool setMaps(const int16_t *left_xy, const uint16_t *left_frac, const int16_t *right_xy, const uint16_t *right_frac) {
+    if (rect_) { svs_rectify_destroy(rect_); rect_ = nullptr; }
+    return ctx_.check(svs_rectify_create(ctx_.get(), cam_.w, cam_.h, max_batch_, left_xy, left_frac, right_xy, right_frac, &rect_));
+  }
+  // rectifyFrame() (+ the colour conversion of processNextFrame) into e.g. the buffers StereoFrontend's input view hands out; asynchronous
+  bool rectifyFrame(const svs_raw_frames_dev &raw, uint8_t *d_left, int lstride, size_t l_bstride, uint8_t *d_right, int rstride, size_t r_bstride, int n_batch = 1) {
+    return rect_ && ctx_.check(svs_rectify_frames(rect_, &raw, d_left, lstride, l_bstride, d_right, rstride, r_bstride, n_batch));
+  }
+  bool depthToDisp(const uint16_t *d_depth16, int stride, size_t bstride, float *d_disp, int dstride, size_t d_bstride, int n_batch = 1) const {
+    return ctx_.check(svs_depth_to_disp(ctx_.get(), &cam_, d_depth16, stride, bstride, d_disp, dstride, d_bstride, n_batch));
+  }
+
+ private:
+  const Context &ctx_;
+  svs_cam cam_;
+  int max_batch_;
+  svs_rectify *rect_;
 };
 
 // One rank of a landmark-sharded back-end: rank 0 calls uniqueId() and distributes it (MPI_Bcast, a TCP store, a file); every rank then constructs

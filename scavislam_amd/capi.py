@@ -85,6 +85,13 @@ class MatchArgs(C.Structure):
                 ("kf_bstride", C.c_size_t), ("pts_bstride", C.c_size_t), ("out_bstride", C.c_size_t)]
 
 
+class RawFramesDev(C.Structure):
+    """svs_raw_frames_dev: raw camera frames of all streams in device memory (strides in bytes)"""
+    _fields_ = [("d_left", C.c_void_p), ("lstride", C.c_int32), ("l_bstride", C.c_size_t), ("left_channels", C.c_int32),
+                ("d_right", C.c_void_p), ("rstride", C.c_int32), ("r_bstride", C.c_size_t),
+                ("ready_event", C.c_void_p)]
+
+
 _SIGS = {
     "svs_ctx_create": [C.c_int, C.c_void_p, C.POINTER(C.c_void_p)],
     "svs_ctx_destroy": [C.c_void_p],
@@ -171,6 +178,11 @@ _SIGS = {
                                    C.POINTER(FrameResult), C.c_void_p, C.c_void_p],
     "svs_frontend_recompute_cloud": [C.c_void_p, C.c_void_p],
     "svs_frontend_device_view": [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
+    "svs_rectify_build_maps": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p],
+    "svs_rectify_create": [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)],
+    "svs_rectify_destroy": [C.c_void_p],
+    "svs_rectify_frames": [C.c_void_p, C.POINTER(RawFramesDev), C.c_void_p, C.c_int, C.c_size_t, C.c_void_p, C.c_int, C.c_size_t, C.c_int],
+    "svs_depth_to_disp": [C.c_void_p, C.POINTER(Cam), C.c_void_p, C.c_int, C.c_size_t, C.c_void_p, C.c_int, C.c_size_t, C.c_int],
     "svs_ba_create": [C.c_void_p, C.POINTER(C.c_void_p)],
     "svs_ba_destroy": [C.c_void_p],
     "svs_ba_set_problem": [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p,

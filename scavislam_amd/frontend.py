@@ -12,8 +12,9 @@ stereo_frontend.cpp), device memory held in torch tensors:
   DenseTrackerGpu.denseTrackingGpu / computeDensePointCloudGpu            dense_tracking.cpp:60-215
   StereoMatcher.calcDisparityCpu         <- StereoFrontend::calcDisparityCpu  stereo_frontend.cpp:620-653
   PoseOptimizer.calcFastMotionOnly       <- BA_SE3_XYZ_STEREO::calcFastMotionOnly  pose_optimizer.h:134-298
+  FrameGrabber.intializeRectifier / rectifyFrame / depthToDisp  <- FrameGrabber<StereoCamera>  frame_grabber.cpp:125-186,245-256, frame_grabber-impl.cpp:93-152
 
-The HIP library does all the arithmetic; nothing here computes on the CPU.
+The HIP library does all the arithmetic; nothing here computes on the CPU (the rectification maps are built once, on the host, by the library).
 """
 import ctypes as C
 
@@ -832,6 +833,96 @@ class StereoMatcher:
         if self.h:
             self.ctx.lib.svs_stereo_destroy(self.h)
             self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class FrameGrabber:
+    """The per-pixel input conversions of FrameGrabber<StereoCamera>::processNextFrame (frame_grabber.cpp:125-186) on device frames of up to `max_batch`
+    streams: colour to gray (framepipe.color_img, :140-147), rectifyFrame() (:245-256) through the maps of intializeRectifier()
+    (frame_grabber-impl.cpp:93-134), depthToDisp() (frame_grabber-impl.cpp:136-152).  The results are written where the caller says -- e.g. into the buffers
+    StereoFrontend.inputView() hands out, followed by processFirstFrames() / processFrames() without frames.  The maps are built on the host by the library
+    (svs_rectify_build_maps); the rotation vectors go to matrices here (SO3::exp), as in the reference."""
+
+    def __init__(self, ctx, cam, max_batch=1):
+        self.ctx, self.cam, self.max_batch = ctx, cam, max_batch
+        self.h = None
+
+    @staticmethod
+    def rodrigues(rv):
+        rv = np.asarray(rv, np.float64)
+        th = float(np.sqrt(rv @ rv))
+        Kx = np.array([[0.0, -rv[2], rv[1]], [rv[2], 0.0, -rv[0]], [-rv[1], rv[0], 0.0]])
+        if th < 1e-12:
+            return np.eye(3) + Kx
+        return np.eye(3) + (np.sin(th) / th) * Kx + ((1.0 - np.cos(th)) / (th * th)) * (Kx @ Kx)
+
+    @staticmethod
+    def build_maps(cam, rot, dist):
+        """cv::initUndistortRectifyMap as intializeRectifier() calls it for one side: R = SO3::exp(rot), new camera matrix = camera matrix,
+        dist = cam.dist_*1..5 -> (map_xy int16 [h, w, 2], map_frac uint16 [h, w]).  Host only, no device needed"""
+        lib = capi.load()
+        w, h = cam["w"], cam["h"]
+        K = np.array([cam["f"], 0.0, cam["cx"], 0.0, cam["f"], cam["cy"], 0.0, 0.0, 1.0])
+        R = np.ascontiguousarray(FrameGrabber.rodrigues(rot)).reshape(9)
+        d = np.ascontiguousarray(dist, np.float64).reshape(5)
+        xy, fr = np.zeros((h, w, 2), np.int16), np.zeros((h, w), np.uint16)
+        rc = lib.svs_rectify_build_maps(K.ctypes.data, d.ctypes.data, R.ctypes.data, K.ctypes.data, w, h, xy.ctypes.data, fr.ctypes.data)
+        if rc:
+            raise capi.SvsError(f"svs_rectify_build_maps: status {rc}")
+        return xy, fr
+
+    def intializeRectifier(self, rot_left, dist_left, rot_right=None, dist_right=None):
+        """rot_right None: a left image only (framepipe.disp_img / depth_img)"""
+        self.setMaps(self.build_maps(self.cam, rot_left, dist_left), None if rot_right is None else self.build_maps(self.cam, rot_right, dist_right))
+
+    def setMaps(self, left=None, right=None):
+        """(map_xy, map_frac) per side, e.g. rect_map_left_[0] / [1] of a host that has OpenCV; None: conversion / copy only for that side"""
+        self.close()
+        a = [None] * 4
+        for s, m in enumerate((left, right)):
+            if m is not None:
+                xy, fr = np.ascontiguousarray(m[0], np.int16), np.ascontiguousarray(m[1], np.uint16)
+                assert xy.shape == (self.cam["h"], self.cam["w"], 2) and fr.shape == (self.cam["h"], self.cam["w"])
+                a[2 * s], a[2 * s + 1] = xy, fr
+        h = C.c_void_p()
+        self.ctx.call("svs_rectify_create", self.cam["w"], self.cam["h"], self.max_batch, *[x.ctypes.data if x is not None else None for x in a], C.byref(h))
+        self.h = h
+        self.ctx.children.add(self)
+
+    @staticmethod
+    def _dst(o):
+        """(pointer, row stride, stream stride) in elements: a triple as StereoFrontend.inputView() gives it, or a torch tensor [B][h][stride]"""
+        if o is None:
+            return None, 0, 0
+        return (o.data_ptr(), o.stride(1), o.stride(0)) if torch.is_tensor(o) else (o[0], o[1], o[2])
+
+    def rectifyFrame(self, left, out_left, right=None, out_right=None, ready_event=None, n_batch=None):
+        """left: u8 tensor [B][h][w] (gray) or [B][h][w][3] (B, G, R); right: u8 [B][h][w] or None; rows and streams may be padded (the tensor's strides are
+        passed on).  Asynchronous on the context's stream"""
+        raw = capi.RawFramesDev()
+        raw.d_left, raw.lstride, raw.l_bstride, raw.left_channels = left.data_ptr(), left.stride(1), left.stride(0), 3 if left.dim() == 4 else 1
+        if right is not None:
+            raw.d_right, raw.rstride, raw.r_bstride = right.data_ptr(), right.stride(1), right.stride(0)
+        if ready_event is not None:
+            raw.ready_event = ready_event.cuda_event
+        (pl, sl, bl), (pr, sr, br) = self._dst(out_left), self._dst(out_right)
+        self.ctx.check(self.ctx.lib.svs_rectify_frames(self.h, C.byref(raw), pl, sl, bl, pr, sr, br, n_batch or left.shape[0]))
+
+    def depthToDisp(self, depth16, out_disp, n_batch=None):
+        """depth16: 16-bit tensor [B][h][stride] (1/5000 m; int16 storage is read as uint16); out_disp: f32 destination (see _dst).  0 gives +inf, as the reference does"""
+        camc = Cam(self.cam["f"], self.cam["cx"], self.cam["cy"], self.cam["b"], self.cam["w"], self.cam["h"])
+        pd, sd, bd = self._dst(out_disp)
+        self.ctx.call("svs_depth_to_disp", C.byref(camc), depth16.data_ptr(), depth16.stride(1), depth16.stride(0), pd, sd, bd, n_batch or depth16.shape[0])
+
+    def close(self):
+        if self.h and self.ctx.h:
+            self.ctx.lib.svs_rectify_destroy(self.h)
+        self.h = None
 
     def __del__(self):
         try:
