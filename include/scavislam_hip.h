@@ -31,7 +31,7 @@ extern "C" {
 /* ABI version: bumped whenever a struct of this header grows or a signature changes (round 3 grew svs_pose_opt_params / svs_match_args and put a `stream`
    argument into svs_frontend_device_view without one -- INTEGRATION.md section 6).  A caller checks svs_api_version() == SVS_API_VERSION once, zero-initialises
    every parameter struct (or takes it from the *_default() initialisers) and sets only the fields it knows. */
-#define SVS_API_VERSION 8
+#define SVS_API_VERSION 9
 int svs_api_version(void);             /* the SVS_API_VERSION the loaded library was built with */
 
 enum {
@@ -537,6 +537,61 @@ int svs_rectify_frames(svs_rectify *r, const svs_raw_frames_dev *raw, uint8_t *d
    disparity with cam->f and cam->b; cam->w x cam->h pixels per stream, strides in elements.  depth 0 gives +inf, as the reference does.  ASYNCHRONOUS */
 int svs_depth_to_disp(svs_ctx *ctx, const svs_cam *cam, const uint16_t *d_depth16, int stride, size_t bstride, float *d_disp, int dstride, size_t d_bstride,
                       int n_batch);
+
+/* ---- loop closure: the geometric check of PlaceRecognizer (placerecognizer.cpp:175-202) = cv::BFMatcher(NORM_L2).match + RanSaC<SE3Model>::compute
+   (ransac.cpp:28-137, ransac_models.cpp:27-81,138-181, stereo_camera.cpp:36-52) for a batch of (query place, train place) pairs.  Descriptors come from any
+   extractor (SURF, the bag of words and Sim3Model / MONO stay with the caller).  Semantics restated in tests/loop_model.py (not pinned).
+   The handle holds a device-resident store of places, the counterpart of location_map_. -------------------------------------------------------------------*/
+typedef struct svs_loop svs_loop;
+/* desc_dim 64 or 128 floats per descriptor; at most max_desc descriptors per place (<= 2^21), max_places slots, max_hyp (<= 256) hypotheses per check,
+   max_checks checks per call.  cam: the level-0 StereoCamera */
+int svs_loop_create(svs_ctx *ctx, const svs_cam *cam, int desc_dim, int max_desc, int max_places, int max_hyp, int max_checks, svs_loop **out);
+int svs_loop_destroy(svs_loop *l);
+/* Place::descriptors [n][desc_dim], uvu_0_vec [n][3]; xyz_vec [n][3] = cam.unmap_uvu(uvu) is formed on the device (f64, as written in stereo_camera.cpp:46-52:
+   sd = (u0 - u2) / b; z = f / sd; x = ((u0 - cx) / f) * z; y = ((u1 - cy) / f) * z) unless h_xyz is given.  Host arrays are staged before the call returns; the
+   upload is ASYNCHRONOUS on the context's stream.  n < 1 or a bad slot: SVS_ERR_INVALID; n > max_desc: SVS_ERR_CAPACITY; any uvu with uvu[0] - uvu[2] <= 0 and
+   no h_xyz: SVS_ERR_INVALID (addLocation keeps disp > 0 only, placerecognizer.cpp:230).  A failed call leaves the slot as it was */
+int svs_loop_set_place(svs_loop *l, int slot, int n, const float *h_desc, const double *h_uvu, const double *h_xyz);
+typedef struct {
+  int32_t query_slot, train_slot;
+  int32_t n_hyp;                       /* numRansac (100 at placerecognizer.cpp:190); 1 .. max_hyp */
+  double pixel_thr;                    /* 2.5 (ransac.hpp:43) */
+  uint64_t seed;                       /* of the device's draws; unused with h_samples */
+  const int32_t *h_samples;            /* [n_hyp][3] match indices (e.g. the reference's own Sample::uniform stream), or NULL: the device draws */
+} svs_loop_check;
+typedef struct {
+  int32_t n_matches;                   /* = descriptors of the query place */
+  int32_t n_inliers;                   /* of the final pass; the caller applies > 30 (placerecognizer.cpp:198) */
+  int32_t best_hyp;                    /* -1: none */
+  int32_t n_invalid_hyp;
+  double T_query_from_train[12];       /* [R | t] row-major; the identity when best_hyp == -1 */
+} svs_loop_result;
+/* n_checks geometric checks in one call (two launches, one upload, one download); BLOCKING: the results are on the host when it returns.
+   Matching: match i has queryIdx = i and trainIdx = argmin_j |q_i - t_j|^2 (d2 = (|q|^2 + |t|^2) - 2 q.t in f32, clamped at 0; the lowest j wins an exact tie;
+   no cross-check); distance = sqrt(d2).
+   Samples: a hypothesis is three distinct match indices with pairwise distinct train indices (ransac.cpp:68-96; the query indices are the match indices).
+   With h_samples the caller's triples are taken as they are, and one that breaks the rule (or leaves [0, n_matches)) makes its hypothesis invalid.  Otherwise
+   draw number d = 0, 1, ... of hypothesis h (every draw counts, rejected ones too) is
+       idx = mulhi32(splitmix64(seed ^ ((uint64)h << 32 | d)) >> 32, n_matches)             mulhi32(a, b) = (uint32)(((uint64)a * b) >> 32)
+       splitmix64(z): z += 0x9E3779B97F4A7C15; z = (z ^ z >> 30) * 0xBF58476D1CE4E5B9; z = (z ^ z >> 27) * 0x94D049BB133111EB; return z ^ z >> 31
+   with the reference's rejection structure: element 0 is one draw; element 1 is redrawn alone while it equals element 0; element 2 is redrawn alone while it
+   equals element 0 or 1; then, if two of the three train indices are equal, the triple starts again at element 0.  The reference loops forever when no valid
+   triple exists; here a hypothesis that would need a 65th draw is invalid.  An invalid hypothesis scores nothing, is never selected, is reported as -1 -1 -1
+   and counted in n_invalid_hyp.
+   Fit (SE3Model::calc_motion): p0 = unmap_uvu of the three query observations, p1 = the three train points, centroids with * (1.0 / 3.0), H = sum p1 p0^T,
+   R = V U^T of its SVD (f64), V.col(2) negated when det R < 0, t = c0 - R c1.
+   Score (belowThreshold): match i is an inlier of T when the three residuals of map_uvu(R x + t) against the query's uvu each have square < pixel_thr^2 (NaN and
+   infinity compare false).  The best hypothesis is the first with the strictly greatest count, from bestinl = 0; without one, best_hyp = -1 and T stays the
+   identity -- the final pass is still made with it (ransac.cpp:126-135).  n_matches < 3: n_inliers = 0, best_hyp = -1, identity, every hypothesis invalid.
+   Outputs (each optional, HOST): h_results [n_checks]; h_train_idx, h_distance, h_inlier (the final pass, in match order) [n_checks][max_desc];
+   h_samples_out [n_checks][max_hyp][3]; h_hyp_inliers [n_checks][max_hyp] -- behind a check's n_matches (n_hyp) the rows hold -1 (indices) and 0.
+   A check's outputs are a function of that check alone: bit-identical whatever else is in the batch, and on every repetition.
+   Bad or empty slots, n_hyp < 1: SVS_ERR_INVALID; n_hyp > max_hyp, n_checks > max_checks: SVS_ERR_CAPACITY -- before anything is launched */
+int svs_loop_check_batch(svs_loop *l, int n_checks, const svs_loop_check *checks, svs_loop_result *h_results, int32_t *h_train_idx, float *h_distance,
+                         uint8_t *h_inlier, int32_t *h_samples_out, int32_t *h_hyp_inliers);
+/* profiling: bracket the two stages of every svs_loop_check_batch with events; ms[2] = distance stage, RANSAC stage of the last call */
+int svs_loop_set_timing(svs_loop *l, int on);
+int svs_loop_stage_times(svs_loop *l, float *ms);
 
 /* ---- multi-GPU: the library-owned collective of the landmark-sharded back-end.  The reference has no
    distributed code; one process per GPU each creates a context and a communicator (RCCL, bound at run time) --------------*/

@@ -618,6 +618,55 @@ class FrameRectifier {
   svs_rectify *rect_;
 };
 
+// PlaceRecognizer's geometric check (placerecognizer.cpp:175-202) on device-resident places: addPlace() is where addLocation hands a Place over
+// (location_map_.insert, :299), geometricCheck() is the BFMatcher + RanSaC<SE3Model>::compute(100, ...) pair and the inliers > 30 test.  Detection, SURF and the
+// bag of words stay with the caller.
+struct DetectedLoop { int query_keyframe_id, loop_keyframe_id; double T_query_from_loop[12]; };      // T: [R | t] row-major
+class PlaceRecognizerGeom {
+ public:
+  PlaceRecognizerGeom(const Context &c, const svs_cam &stereo_cam, int desc_dim = 64, int max_desc = 2048, int max_places = 64, int num_ransac = 100)
+      : ctx_(c), loop_(nullptr), num_ransac_(num_ransac), pixel_thr_(2.5), seed_(0), keyframe_id_(max_places > 0 ? max_places : 0, -1) {
+    std::memset(&last_, 0, sizeof last_);
+    ok_ = c.check(svs_loop_create(c.get(), &stereo_cam, desc_dim, max_desc, max_places, num_ransac, 1, &loop_));
+  }
+  ~PlaceRecognizerGeom() { if (loop_) svs_loop_destroy(loop_); }
+  PlaceRecognizerGeom(const PlaceRecognizerGeom &) = delete;
+  PlaceRecognizerGeom &operator=(const PlaceRecognizerGeom &) = delete;
+  bool ok() const { return ok_; }
+  svs_loop *get() const { return loop_; }
+  // Place::descriptors [n][desc_dim], uvu_0_vec [n][3], xyz_vec [n][3] (NULL: cam.unmap_uvu on the device)
+  bool addPlace(int slot, int keyframe_id, int n, const float *descriptors, const double *uvu_0_vec, const double *xyz_vec = nullptr) {
+    if (!ok_ || !ctx_.check(svs_loop_set_place(loop_, slot, n, descriptors, uvu_0_vec, xyz_vec))) return false;
+    keyframe_id_[slot] = keyframe_id;
+    return true;
+  }
+  void setSeed(uint64_t seed) { seed_ = seed; }
+  void setPixelThreshold(double thr) { pixel_thr_ = thr; }
+  // true when inliers.size() > 30: *loop is what monitor.addLoop() takes
+  bool geometricCheck(int query_slot, int train_slot, DetectedLoop *loop) {
+    svs_loop_check ck;
+    ck.query_slot = query_slot; ck.train_slot = train_slot; ck.n_hyp = num_ransac_; ck.pixel_thr = pixel_thr_; ck.seed = seed_++; ck.h_samples = nullptr;
+    if (!ok_ || !ctx_.check(svs_loop_check_batch(loop_, 1, &ck, &last_, nullptr, nullptr, nullptr, nullptr, nullptr))) return false;
+    if (loop) {
+      loop->query_keyframe_id = keyframe_id_[query_slot];
+      loop->loop_keyframe_id = keyframe_id_[train_slot];
+      std::memcpy(loop->T_query_from_loop, last_.T_query_from_train, sizeof last_.T_query_from_train);
+    }
+    return last_.n_inliers > 30;
+  }
+  const svs_loop_result &lastResult() const { return last_; }
+
+ private:
+  const Context &ctx_;
+  svs_loop *loop_;
+  int num_ransac_;
+  double pixel_thr_;
+  uint64_t seed_;
+  std::vector<int> keyframe_id_;
+  svs_loop_result last_;
+  bool ok_;
+};
+
 // One rank of a landmark-sharded back-end: rank 0 calls uniqueId() and distributes it (MPI_Bcast, a TCP store, a file); every rank then constructs
 // the communicator and attaches it to its SlamGraphBA with attach().  svs_ba_optimize all-reduces over RCCL on the context's stream.
 class Communicator {

@@ -8,7 +8,7 @@ import ctypes as C
 import os
 import weakref
 
-from .ctypes_types import BaParams, BaStats, Cam, FastGrid, PoseOptParams, PoseOptStats, StereoParams
+from .ctypes_types import BaParams, BaStats, Cam, FastGrid, LoopCheck, LoopResult, PoseOptParams, PoseOptStats, StereoParams
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SVS_LIB_PATH") or os.path.join(_HERE, "libscavislam_hip.so")   # override = kernel A/B experiments only
@@ -183,6 +183,12 @@ _SIGS = {
     "svs_rectify_destroy": [C.c_void_p],
     "svs_rectify_frames": [C.c_void_p, C.POINTER(RawFramesDev), C.c_void_p, C.c_int, C.c_size_t, C.c_void_p, C.c_int, C.c_size_t, C.c_int],
     "svs_depth_to_disp": [C.c_void_p, C.POINTER(Cam), C.c_void_p, C.c_int, C.c_size_t, C.c_void_p, C.c_int, C.c_size_t, C.c_int],
+    "svs_loop_create": [C.c_void_p, C.POINTER(Cam), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)],
+    "svs_loop_destroy": [C.c_void_p],
+    "svs_loop_set_place": [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p],
+    "svs_loop_check_batch": [C.c_void_p, C.c_int, C.POINTER(LoopCheck), C.POINTER(LoopResult), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
+    "svs_loop_set_timing": [C.c_void_p, C.c_int],
+    "svs_loop_stage_times": [C.c_void_p, C.c_void_p],
     "svs_ba_create": [C.c_void_p, C.POINTER(C.c_void_p)],
     "svs_ba_destroy": [C.c_void_p],
     "svs_ba_set_problem": [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
@@ -216,7 +222,7 @@ _SIGS = {
     "svs_ba_graph_stats": [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)],
 }
 EXPORTS = sorted(list(_SIGS) + ["svs_ctx_stream", "svs_last_error", "svs_api_version", "svs_pose_opt_params_default"])
-API_VERSION = 8      # SVS_API_VERSION of include/scavislam_hip.h this binding was written against
+API_VERSION = 9      # SVS_API_VERSION of include/scavislam_hip.h this binding was written against
 
 
 def load():

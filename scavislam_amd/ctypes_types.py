@@ -120,3 +120,14 @@ assert GATED_POINT_DTYPE.itemsize == 40
 POINT_STATS_DTYPE = np.dtype([("num_points_grid2x2", "<i4", 4), ("num_points_grid3x3", "<i4", 9), ("num_matched_points", "<i4", 3),
                               ("num_track_points", "<i4"), ("num_obs", "<i4"), ("pad_", "<i4", 2), ("sum_track_length", "<f8")])
 assert POINT_STATS_DTYPE.itemsize == 88
+
+
+class LoopCheck(C.Structure):
+    """svs_loop_check: one geometric check (PlaceRecognizer::geometricCheck, placerecognizer.cpp:175-202)."""
+    _fields_ = [("query_slot", C.c_int32), ("train_slot", C.c_int32), ("n_hyp", C.c_int32), ("pixel_thr", C.c_double), ("seed", C.c_uint64),
+                ("h_samples", C.c_void_p)]
+
+
+class LoopResult(C.Structure):
+    _fields_ = [("n_matches", C.c_int32), ("n_inliers", C.c_int32), ("best_hyp", C.c_int32), ("n_invalid_hyp", C.c_int32),
+                ("T_query_from_train", C.c_double * 12)]
