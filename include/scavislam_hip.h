@@ -506,6 +506,83 @@ int svs_frontend_recompute_cloud(svs_frontend *fe, const double *T_cur_from_actk
 int svs_frontend_device_view(svs_frontend *fe, int stream, const uint8_t **d_pyr_last, int32_t *stride, const float **d_disp, const float **d_cloud,
                              svs_fast **fast);
 
+/* ---- new-point seeding of a keyframe: replaces StereoFrontend::addNewPoints / addMorePoints / addMorePointsToOtherFrame (stereo_frontend.cpp:682-823).
+   Semantics restated in tests/seed_model.py.  Per problem and per level l = 0 .. n_levels-1 the level's FAST corners (x, y) are
+   walked in a visiting order; n_l starts at n0[l]; with W x H the level-0 size (cam.w, cam.h), R = clearance, a corner is taken iff
+     1. d = (double)disp[(y << l) * stride + (x << l)] * (1.0 / 2^l) > 0          (interpolateDisparity, maths_utils.cpp:38-44; NaN: not taken)
+     2. 1 <= x << l < W - 1 and 1 <= y << l < H - 1                                  (isInFrame(uvi, 1); the device tests this first and reads no disparity outside)
+     3. add_flags[i * 3 + j] != 0, i (j) = 0 / 1 / 2 by x << l (y << l) < third, < twothird, else, with third = (int)(W * (float)(1. / 3.)),
+        twothird = (int)(W * 2 * (float)(1. / 3.)) evaluated in float as the reference does (:738-742), likewise for H
+     4. no point p of the level's point tree has x - R <= p.x < x + R + 1 and y - R <= p.y < y + R + 1   (isWindowEmpty, quadtree.h:713-754, cv::Rect_::contains);
+        the tree holds the caller's tree points of this level and the corners taken so far in this call.  The bounds are integers, so the test is exact on
+        floor(p): the device keeps one occupancy bit per pixel of the level image (ceil(W / 2^l) x ceil(H / 2^l)) in LDS
+   and then: anchor_obs_pyr = (x, y, x - d); xyz_cur = unmap_uvu(cam, anchor_obs_pyr * 2^l) as written in stereo_camera.cpp:46-52 (sd = (u0 - u2) / b; z = f / sd;
+   x = ((u0 - cx) / f) * z; y = ((u1 - cy) / f) * z); xyz_anchor = T_newkey_from_cur * xyz_cur, row i = ((T[4i] x + T[4i+1] y) + T[4i+2] z) + T[4i+3], no contraction;
+   anchor_level = l; kf_index as given; point_id = first_point_id + k for the k-th corner taken in the call, level 0's first (getNewUniqueId); the corner enters
+   the tree; ++n_l, and the level ends once n_l > (num_max_points >> l) (:815-818) -- a level that starts above its cap still takes exactly one corner.
+   The records leave in the order of the reference's newpoint_map[kf] list, which is push_front: the REVERSE of the order they were taken in.
+   Departures from the reference: its QuadTree::insert drops a point closer than delta = 1 to the occupant of its leaf, the device keeps it (positions the front
+   end produces are integers at their level, where this cannot occur); a tree point whose floor lies outside the level image is ignored (the reference asserts).
+   Visiting order, per level: either the caller's list of indices into the level's corner list (svs_fast_download order; an index outside the list is skipped), or
+   generated from a 64-bit seed and the corner list alone -- never from the problem's place in the batch: with h(x) = splitmix64(seed ^ x) (the mixer of
+   svs_loop_check_batch above), the corner with list index i in cell c of level l (cells as svs_fast_download counts them) has a = h(1 << 62 | l << 32 | i),
+   j = the number of corners i' of its cell with (a', i') < (a, i), b = h(2 << 62 | l << 48 | j << 16 | c); the corners are visited in ascending (j, b, c): round j
+   takes one corner from every cell that still has one, the cells in a per-round hashed order -- even coverage before density, which is what the reference's
+   QuadTree::EquiIter is for (its own order comes from VisionTools::Sample::uniform, third-party code). -------------------------------------------------------*/
+typedef struct {
+  int32_t clearance;          /* params_.newpoint_clearance (2); 0 .. 31 */
+  int32_t num_max_points;     /* ui.num_max_points (300) */
+  int32_t min_num_points;     /* ui.min_num_points (25): svs_frontend_seed_keyframes sets add_flags[k] = num_points_grid3x3[k] <= this (:322-331) */
+  int32_t n_levels;           /* USE_N_LEVELS_FOR_MATCHING (3); 1 .. 3 */
+} svs_seed_params;
+void svs_seed_params_default(svs_seed_params *p);      /* 2 / 300 / 25 / 3 */
+typedef struct {              /* one problem of svs_seed_points; lives in DEVICE memory */
+  double T_newkey_from_cur[12];
+  uint64_t seed;              /* of the generated order */
+  int32_t add_flags[9];       /* [i * 3 + j] */
+  int32_t n0[3];              /* (*num_points)[l] on entry, >= 0 */
+  int32_t n_tree;             /* tree points of this problem */
+  int32_t kf_index, first_point_id;
+  int32_t use_order;          /* 1: the caller's index lists (n_order[l] entries at d_order[l]); 0: generated from the seed */
+  int32_t n_order[3];
+  int32_t pad_;
+} svs_seed_problem;
+typedef struct {              /* all pointers DEVICE; problem b at + b * (its batch stride) elements */
+  const int16_t *d_xy[3]; size_t xy_bstride[3]; int32_t xy_cap[3];      /* corners (x, y) of level l in svs_fast_download order; at most xy_cap[l] are read */
+  const int32_t *d_n[3]; size_t n_bstride[3];                            /* their number */
+  const int32_t *d_cell_count[3]; size_t cell_bstride[3]; int32_t n_cells[3];      /* corners per cell (generated order only); n_cells <= SVS_MAX_CELLS */
+  const float *d_disp; int32_t disp_stride; size_t disp_bstride;
+  svs_cam cam;                                                           /* the level-0 StereoCamera */
+  const svs_seed_problem *d_prob;                                        /* [batch] */
+  const double *d_tree_xy; const int32_t *d_tree_level; size_t tree_bstride;       /* tree points [batch][tree_bstride]: (x, y) at their level, the level */
+  const int32_t *d_order[3]; size_t order_bstride[3];                    /* the caller's visiting orders (problems with use_order) */
+  int32_t batch;
+} svs_seed_args;
+/* `batch` independent problems, ASYNCHRONOUS on the context's stream.  d_out [batch][cap] records in list order, d_n_new [batch][3] the number taken per level
+   (records of a problem: their sum).  cap < sum over the levels of (num_max_points >> l) + 1 -- the most a problem can produce: SVS_ERR_CAPACITY, nothing is written.
+   A generated order needs xy_cap[l] <= 8192.  A problem's outputs are a function of that problem alone */
+int svs_seed_points(svs_ctx *ctx, const svs_seed_args *a, const svs_seed_params *prm, svs_candidate_point *d_out, int cap, int32_t *d_n_new);
+enum { SVS_SEED_FIRST = 0,   /* addNewPoints (:682-704): empty tree, every flag set, n0 = 0 */
+       SVS_SEED_MORE = 1 };  /* addMorePoints behind addNewKeyframe (:316-331, :422-427): the tree holds the accepted gate records of the last step (uv_pyr at the
+                                candidate's anchor_level), n0 = its num_matched_points, flags from its num_points_grid3x3.  SVS_ERR_INVALID unless the last
+                                frame call was a step (not a first frame) and no candidate list was set since: the records must be that step's */
+typedef struct {
+  int32_t stream, mode;
+  int32_t kf_index, first_point_id;
+  double T_newkey_from_cur[12];        /* the identity for addNewPoints / addMorePoints */
+  uint64_t seed;
+  const int32_t *h_order[3];           /* HOST; all NULL: generated order.  Otherwise n_order[l] indices per level (a NULL level is not visited) */
+  int32_t n_order[3];
+  int32_t pad_;
+} svs_seed_request;
+/* the same from the front end's own device state, for n requests (several streams, or several keyframes of one): the corners of the last detection, the disparity
+   of the frame processed last, the gate records and point statistics of the last step.  Ordered behind that step on the context's stream; one staged upload of
+   the requests, one download of all records (with more than 1 MiB of output rows the counts come first and the records follow as one strided copy of the
+   longest list's width; what a row of h_out holds behind its own records is then unspecified).  BLOCKING.  h_out [n][cap_per_request], h_n_new [n][3].  Works for the one-stream and the batch front end.
+   Building the candidate lists from the records stays with the caller (stereo_frontend.cpp:265-296) */
+int svs_frontend_seed_keyframes(svs_frontend *fe, int n, const svs_seed_request *req, const svs_seed_params *prm, svs_candidate_point *h_out, int cap_per_request,
+                                int32_t *h_n_new);
+
 /* ---- between the camera and processFrame: the three per-pixel input conversions of FrameGrabber::processNextFrame (frame_grabber.cpp:125-186), for a
    caller whose frames are raw (lens-distorted, colour, or depth instead of disparity).  Bit-exact to the OpenCV 2.4 semantics restated in
    tests/rectify_model.py.  The outputs are meant for the buffers svs_frontend_input_view hands out, followed by

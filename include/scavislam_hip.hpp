@@ -553,9 +553,43 @@ class StereoFrontend {
     corners->resize((size_t)n);
     return true;
   }
+  // addNewPoints / addMorePoints / addMorePointsToOtherFrame (stereo_frontend.cpp:682-823) on the state the frame processed last left on the device:
+  // new_keyframe_id -> the records' kf_index, first_point_id = the id getNewUniqueId would hand out next; *newpoints = newpoint_map[new_keyframe_id] in list order,
+  // num_points[l] += the points taken on level l (the reference's *num_points; addNewPoints starts from 0).  The visiting order is generated from `seed`
+  // (scavislam_hip.h); prm == NULL: the reference's defaults (clearance 2, ui.num_max_points 300, ui.min_num_points 25, 3 levels)
+  static svs_seed_params seedParams() { svs_seed_params p; svs_seed_params_default(&p); return p; }
+  bool addNewPoints(int new_keyframe_id, int first_point_id, uint64_t seed, std::vector<svs_candidate_point> *newpoints, int32_t num_points[3],
+                    const svs_seed_params *prm = nullptr) {
+    for (int l = 0; l < 3; ++l) num_points[l] = 0;
+    return seed_(SVS_SEED_FIRST, new_keyframe_id, nullptr, first_point_id, seed, newpoints, num_points, prm);
+  }
+  bool addMorePoints(int new_keyframe_id, int first_point_id, uint64_t seed, std::vector<svs_candidate_point> *newpoints, int32_t num_points[3],
+                     const svs_seed_params *prm = nullptr) {
+    return seed_(SVS_SEED_MORE, new_keyframe_id, nullptr, first_point_id, seed, newpoints, num_points, prm);
+  }
+  bool addMorePointsToOtherFrame(int new_keyframe_id, const double T_newkey_from_cur[12], int first_point_id, uint64_t seed,
+                                 std::vector<svs_candidate_point> *newpoints, int32_t num_points[3], const svs_seed_params *prm = nullptr) {
+    return seed_(SVS_SEED_MORE, new_keyframe_id, T_newkey_from_cur, first_point_id, seed, newpoints, num_points, prm);
+  }
   svs_frontend *handle() const { return fe_; }
 
  private:
+  bool seed_(int mode, int kf, const double *T, int first_point_id, uint64_t seed, std::vector<svs_candidate_point> *out, int32_t num_points[3],
+             const svs_seed_params *prm) {
+    const svs_seed_params p = prm ? *prm : seedParams();
+    svs_seed_request q;
+    std::memset(&q, 0, sizeof q);
+    q.stream = 0; q.mode = mode; q.kf_index = kf; q.first_point_id = first_point_id; q.seed = seed;
+    for (int i = 0; i < 12; ++i) q.T_newkey_from_cur[i] = T ? T[i] : (i % 5 == 0 ? 1.0 : 0.0);
+    int cap = 0;
+    for (int l = 0; l < p.n_levels; ++l) cap += (p.num_max_points >> l) + 1;
+    out->resize((size_t)cap);
+    int32_t n[3] = {0, 0, 0};
+    if (!ctx_.check(svs_frontend_seed_keyframes(fe_, 1, &q, &p, out->data(), cap, n))) { out->clear(); return false; }
+    out->resize((size_t)(n[0] + n[1] + n[2]));
+    for (int l = 0; l < 3; ++l) num_points[l] += n[l];
+    return true;
+  }
   const Context &ctx_;
   svs_frontend *fe_;
   bool ok_;

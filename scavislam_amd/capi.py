@@ -8,7 +8,7 @@ import ctypes as C
 import os
 import weakref
 
-from .ctypes_types import BaParams, BaStats, Cam, FastGrid, LoopCheck, LoopResult, PoseOptParams, PoseOptStats, StereoParams
+from .ctypes_types import BaParams, BaStats, Cam, FastGrid, LoopCheck, LoopResult, PoseOptParams, PoseOptStats, SeedArgs, SeedParams, SeedRequest, StereoParams
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SVS_LIB_PATH") or os.path.join(_HERE, "libscavislam_hip.so")   # override = kernel A/B experiments only
@@ -183,6 +183,8 @@ _SIGS = {
     "svs_rectify_destroy": [C.c_void_p],
     "svs_rectify_frames": [C.c_void_p, C.POINTER(RawFramesDev), C.c_void_p, C.c_int, C.c_size_t, C.c_void_p, C.c_int, C.c_size_t, C.c_int],
     "svs_depth_to_disp": [C.c_void_p, C.POINTER(Cam), C.c_void_p, C.c_int, C.c_size_t, C.c_void_p, C.c_int, C.c_size_t, C.c_int],
+    "svs_seed_points": [C.c_void_p, C.POINTER(SeedArgs), C.POINTER(SeedParams), C.c_void_p, C.c_int, C.c_void_p],
+    "svs_frontend_seed_keyframes": [C.c_void_p, C.c_int, C.POINTER(SeedRequest), C.POINTER(SeedParams), C.c_void_p, C.c_int, C.c_void_p],
     "svs_loop_create": [C.c_void_p, C.POINTER(Cam), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)],
     "svs_loop_destroy": [C.c_void_p],
     "svs_loop_set_place": [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p],
@@ -221,7 +223,7 @@ _SIGS = {
                             C.POINTER(C.c_int32)],
     "svs_ba_graph_stats": [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)],
 }
-EXPORTS = sorted(list(_SIGS) + ["svs_ctx_stream", "svs_last_error", "svs_api_version", "svs_pose_opt_params_default"])
+EXPORTS = sorted(list(_SIGS) + ["svs_ctx_stream", "svs_last_error", "svs_api_version", "svs_pose_opt_params_default", "svs_seed_params_default"])
 API_VERSION = 9      # SVS_API_VERSION of include/scavislam_hip.h this binding was written against
 
 
@@ -248,6 +250,8 @@ def load():
         lib.svs_api_version.restype = C.c_int
         lib.svs_pose_opt_params_default.argtypes = [C.c_void_p]
         lib.svs_pose_opt_params_default.restype = None
+        lib.svs_seed_params_default.argtypes = [C.c_void_p]
+        lib.svs_seed_params_default.restype = None
         if lib.svs_api_version() != API_VERSION:
             raise SvsError(f"{LIB_PATH} was built with SVS_API_VERSION {lib.svs_api_version()}, this binding expects {API_VERSION}: rebuild (__graft_entry__.build())")
         _LIB = lib

@@ -563,3 +563,11 @@ FastView svs_fast_view_internal(const svs_fast *f) {
   }
   return v;
 }
+
+// internal accessor for seed.hip
+FastListView svs_fast_list_view_internal(const svs_fast *f) {
+  FastListView v{};
+  v.n_levels = f->P.n_levels; v.batch = f->batch; v.cap = f->P.cap; v.level_total = f->P.level_total; v.count = f->P.count; v.ncell_total = f->P.ncell_total;
+  for (int l = 0; l < f->P.n_levels; ++l) { v.xy[l] = f->P.lv[l].xy; v.cell_base[l] = f->P.lv[l].cell_base; v.ncell[l] = f->P.lv[l].gx * f->P.lv[l].gy; }
+  return v;
+}

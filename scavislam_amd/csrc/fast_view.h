@@ -9,3 +9,10 @@ struct FastView {
   int w[SVS_NUM_PYR_LEVELS], h[SVS_NUM_PYR_LEVELS]; int n_levels;
 };
 FastView svs_fast_view_internal(const svs_fast *f);
+// the ordered corner lists of the last detection (seed.hip): level l of slot s at xy[l] + s * cap * 2, its length (not clamped to cap) at level_total[s * n_levels + l],
+// its per-cell counts at count[s * ncell_total + cell_base[l] + c]
+struct FastListView {
+  const int16_t *xy[SVS_NUM_PYR_LEVELS]; int cap; const int *level_total; const int *count; int ncell_total;
+  int cell_base[SVS_NUM_PYR_LEVELS], ncell[SVS_NUM_PYR_LEVELS]; int n_levels, batch;
+};
+FastListView svs_fast_list_view_internal(const svs_fast *f);

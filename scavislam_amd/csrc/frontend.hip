@@ -17,6 +17,8 @@
 // point seeding.  The object owns the device copies of the previous frame (pyramid + reference cloud), the keyframes it was
 // told to keep (Frame::clone, keyframes.h:72-83), the candidate points (ap_map) and the FAST threshold state -- per stream.
 #include "common.h"
+#include "fast_view.h"
+#include "seed.h"
 #include <string.h>
 #include <algorithm>
 #include <vector>
@@ -156,6 +158,10 @@ struct svs_frontend {
   // optional stage timing (svs_frontend_set_timing): events between the stages of the last call
   bool timing = false;
   hipEvent_t ev_stage[SVS_FRONTEND_STAGES + 1] = {};
+  // new-point seeding (svs_frontend_seed_keyframes): records the last step's gate wrote per stream; -1 while they do not describe the candidate list (no step
+  // since the last first frame, or the list was replaced behind the step), staging blocks grown on demand
+  int n_gated = -1;
+  uint8_t *h_seed = nullptr, *d_seed = nullptr; size_t h_seed_bytes = 0, d_seed_bytes = 0;
 };
 constexpr int REC_CAP = 64;
 
@@ -195,6 +201,8 @@ extern "C" int svs_frontend_destroy(svs_frontend *fe) {
   }
   if (fe->h_out) (void)hipHostFree(fe->h_out);
   if (fe->h_cand_stage) (void)hipHostFree(fe->h_cand_stage);
+  if (fe->h_seed) (void)hipHostFree(fe->h_seed);
+  if (fe->d_seed) (void)hipFree(fe->d_seed);
   if (fe->d_rec) (void)hipFree(fe->d_rec);
   if (fe->d_nrec) (void)hipFree(fe->d_nrec);
   if (fe->d_trk_work) (void)hipFree(fe->d_trk_work);
@@ -341,6 +349,7 @@ extern "C" int svs_frontend_set_candidates_grouped(svs_frontend *fe, int stream,
   SVS_HIP(ctx, hipStreamSynchronize(ctx->stream));      // h_pts may be pageable and reused by the caller
   fe->n_points[stream] = n; fe->n_new_records[stream] = h_group_end[n_groups - 2];
   fe->n_launch = *std::max_element(fe->n_points.begin(), fe->n_points.end());
+  fe->n_gated = -1;      // the last step's gate records no longer belong to the list on the device
   fe->max_groups_used = std::max(fe->max_groups_used, n_groups);
   return SVS_OK;
 }
@@ -441,6 +450,7 @@ extern "C" int svs_frontend_set_candidates_all(svs_frontend *fe, const svs_candi
   SVS_HIP(ctx, hipStreamSynchronize(ctx->stream));
   for (int b = 0; b < B; ++b) { fe->n_points[b] = h_n[b]; fe->n_new_records[b] = nn[b]; }
   fe->n_launch = *std::max_element(fe->n_points.begin(), fe->n_points.end());
+  fe->n_gated = -1;      // the last step's gate records no longer belong to the list on the device
   fe->max_groups_used = std::max(fe->max_groups_used, n_groups);
   return SVS_OK;
 }
@@ -702,6 +712,7 @@ int frontend_chain(svs_frontend *fe, bool first, DispView dv, bool ext_frames = 
   STAGE_MARK(8);
   if (pipe) { SVS_HIP(ctx, hipEventRecord(fe->ev_late[par], ctx->stream)); ++fe->pipe_run; }
   fe->last_disp = dv.p; fe->last_dstride = dv.stride; fe->last_dbstride = dv.bstride;
+  fe->n_gated = first ? -1 : n;
   return SVS_OK;
 }
 void frontend_rotate(svs_frontend *fe) {
@@ -995,5 +1006,112 @@ extern "C" int svs_frontend_dense_records(svs_frontend *fe, int stream, svs_dens
   SVS_HIP(ctx, hipStreamSynchronize(ctx->stream));
   const int k = std::min(std::min((int)*n, cap), REC_CAP);
   if (k > 0) SVS_HIP(ctx, hipMemcpy(h_rec, fe->d_rec + (size_t)stream * REC_CAP, sizeof(svs_dense_lm_record) * (size_t)k, hipMemcpyDeviceToHost));
+  return SVS_OK;
+}
+
+/* addNewPoints / addMorePoints (stereo_frontend.cpp:682-823) for n requests from the device state the last first_frame(s) / process_frame(s) call left behind:
+   the corner lists of its detection, its disparity, and for SVS_SEED_MORE its gate records and point statistics (seed.hip).  One staged upload (problems, streams,
+   the callers' orders), the kernels, one download (counts and records). */
+extern "C" int svs_frontend_seed_keyframes(svs_frontend *fe, int n, const svs_seed_request *req, const svs_seed_params *prm, svs_candidate_point *h_out,
+                                           int cap_per_request, int32_t *h_n_new) {
+  svs_ctx *ctx = fe ? fe->ctx : nullptr;
+  SVS_REQUIRE(ctx, fe && n >= 0 && (n == 0 || (req && h_out && h_n_new)) && prm && fe->have_prev && !fe->submitted && fe->last_disp);
+  SVS_REQUIRE(ctx, prm->n_levels >= 1 && prm->n_levels <= fe->prm.n_levels && prm->num_max_points >= 0 && prm->num_max_points <= 65536);
+  if (cap_per_request < svs_seed_max_records(prm)) {
+    ctx->err = "svs_frontend_seed_keyframes: cap_per_request below the sum over the levels of (num_max_points >> l) + 1";
+    return SVS_ERR_CAPACITY;
+  }
+  if (n == 0) return SVS_OK;
+  const FastListView fv = svs_fast_list_view_internal(fe->fast);
+  size_t ob[3] = {0, 0, 0};      // the callers' order lists of a level are staged [n][ob[l]]
+  bool any_generated = false;
+  for (int r = 0; r < n; ++r) {
+    const svs_seed_request &q = req[r];
+    SVS_REQUIRE(ctx, q.stream >= 0 && q.stream < fe->B && (q.mode == SVS_SEED_FIRST || q.mode == SVS_SEED_MORE));
+    SVS_REQUIRE(ctx, q.mode != SVS_SEED_MORE || fe->n_gated >= 0);      // gate records and point statistics of a step on the list that is still on the device
+    const bool own = q.h_order[0] || q.h_order[1] || q.h_order[2];
+    any_generated = any_generated || !own;
+    for (int l = 0; l < prm->n_levels && own; ++l) {
+      SVS_REQUIRE(ctx, q.n_order[l] >= 0 && q.n_order[l] <= (1 << 24));
+      if (q.h_order[l]) ob[l] = std::max(ob[l], (size_t)q.n_order[l]);
+    }
+  }
+  SVS_DEVICE(ctx);
+  // staging block: problems | streams | orders of level 0, 1, 2 ; device block: the same, then counts [n][3] (padded to 64 bytes) | records [n][cap]
+  auto up64 = [](size_t v) { return (v + 63) & ~(size_t)63; };
+  const size_t off_slot = up64(sizeof(svs_seed_problem) * (size_t)n);
+  size_t off_ord[3], in_bytes = up64(off_slot + sizeof(int32_t) * (size_t)n);
+  for (int l = 0; l < 3; ++l) { off_ord[l] = in_bytes; in_bytes = up64(in_bytes + sizeof(int32_t) * ob[l] * (size_t)n); }
+  const size_t off_cnt = in_bytes, off_rec = up64(off_cnt + sizeof(int32_t) * 3 * (size_t)n);
+  const size_t out_bytes = (off_rec - off_cnt) + sizeof(svs_candidate_point) * (size_t)cap_per_request * (size_t)n, d_bytes = off_cnt + out_bytes;
+  // small results go home in one copy through the pinned block; big ones as the counts, then one strided copy of the longest list's width into the caller's array
+  const bool one_copy = out_bytes <= ((size_t)1 << 20);
+  const size_t h_bytes = std::max(in_bytes, one_copy ? out_bytes : off_rec - off_cnt);
+  if (fe->h_seed_bytes < h_bytes || fe->d_seed_bytes < d_bytes) SVS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  if (fe->h_seed_bytes < h_bytes) {
+    if (fe->h_seed) (void)hipHostFree(fe->h_seed);
+    fe->h_seed = nullptr; fe->h_seed_bytes = 0;
+    SVS_HIP(ctx, hipHostMalloc(reinterpret_cast<void **>(&fe->h_seed), h_bytes, hipHostMallocDefault));
+    fe->h_seed_bytes = h_bytes;
+  }
+  if (fe->d_seed_bytes < d_bytes) {
+    if (fe->d_seed) (void)hipFree(fe->d_seed);
+    fe->d_seed = nullptr; fe->d_seed_bytes = 0;
+    SVS_HIP(ctx, hipMalloc(reinterpret_cast<void **>(&fe->d_seed), d_bytes));
+    fe->d_seed_bytes = d_bytes;
+  }
+  svs_seed_problem *hp = reinterpret_cast<svs_seed_problem *>(fe->h_seed);
+  int32_t *hs = reinterpret_cast<int32_t *>(fe->h_seed + off_slot);
+  for (int r = 0; r < n; ++r) {
+    const svs_seed_request &q = req[r];
+    svs_seed_problem p{};
+    for (int i = 0; i < 12; ++i) p.T_newkey_from_cur[i] = q.T_newkey_from_cur[i];
+    p.seed = q.seed; p.kf_index = q.kf_index; p.first_point_id = q.first_point_id;
+    const bool more = q.mode == SVS_SEED_MORE;
+    for (int k = 0; k < 9; ++k) p.add_flags[k] = 1;
+    for (int l = 0; l < 3; ++l) p.n0[l] = more ? -1 : 0;      // -1: counts and flags from the stream's point statistics on the device
+    p.n_tree = more ? fe->n_gated : 0;
+    p.use_order = (q.h_order[0] || q.h_order[1] || q.h_order[2]) ? 1 : 0;
+    for (int l = 0; l < prm->n_levels && p.use_order; ++l) {
+      p.n_order[l] = q.h_order[l] ? q.n_order[l] : 0;
+      if (p.n_order[l]) __builtin_memcpy(fe->h_seed + off_ord[l] + sizeof(int32_t) * ob[l] * (size_t)r, q.h_order[l], sizeof(int32_t) * (size_t)p.n_order[l]);
+    }
+    hp[r] = p; hs[r] = q.stream;
+  }
+  SVS_HIP(ctx, hipMemcpyAsync(fe->d_seed, fe->h_seed, in_bytes, hipMemcpyHostToDevice, ctx->stream));
+  svs_seed_args a{};
+  for (int l = 0; l < prm->n_levels; ++l) {
+    a.d_xy[l] = fv.xy[l]; a.xy_bstride[l] = (size_t)fv.cap * 2; a.xy_cap[l] = fv.cap;
+    a.d_n[l] = fv.level_total + l; a.n_bstride[l] = (size_t)fv.n_levels;
+    a.d_cell_count[l] = fv.count + fv.cell_base[l]; a.cell_bstride[l] = (size_t)fv.ncell_total; a.n_cells[l] = fv.ncell[l];
+    a.d_order[l] = ob[l] ? reinterpret_cast<const int32_t *>(fe->d_seed + off_ord[l]) : nullptr; a.order_bstride[l] = ob[l];
+  }
+  a.d_disp = fe->last_disp; a.disp_stride = fe->last_dstride; a.disp_bstride = fe->last_dbstride;
+  a.cam = fe->cams[0];
+  a.d_prob = reinterpret_cast<const svs_seed_problem *>(fe->d_seed);
+  a.batch = n;
+  SeedFrontendSrc fs{};
+  fs.slot_of = reinterpret_cast<const int32_t *>(fe->d_seed + off_slot);
+  fs.gated = fe->d_gated; fs.pts = fe->d_pts; fs.res = fe->d_res; fs.rec_b = (size_t)fe->max_points; fs.stats = fe->d_ptstats;
+  if (int rc = svs_seed_launch(ctx, &a, prm, &fs, any_generated, reinterpret_cast<svs_candidate_point *>(fe->d_seed + off_rec), cap_per_request,
+                               reinterpret_cast<int32_t *>(fe->d_seed + off_cnt)))
+    return rc;
+  SVS_HIP(ctx, hipMemcpyAsync(fe->h_seed, fe->d_seed + off_cnt, one_copy ? out_bytes : off_rec - off_cnt, hipMemcpyDeviceToHost, ctx->stream));
+  SVS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  __builtin_memcpy(h_n_new, fe->h_seed, sizeof(int32_t) * 3 * (size_t)n);
+  int longest = 0;
+  for (int r = 0; r < n; ++r) longest = std::max(longest, h_n_new[3 * r] + h_n_new[3 * r + 1] + h_n_new[3 * r + 2]);
+  SVS_REQUIRE(ctx, longest <= cap_per_request);
+  if (one_copy) {
+    const svs_candidate_point *rec = reinterpret_cast<const svs_candidate_point *>(fe->h_seed + (off_rec - off_cnt));
+    for (int r = 0; r < n; ++r) {
+      const int m = h_n_new[3 * r] + h_n_new[3 * r + 1] + h_n_new[3 * r + 2];
+      if (m > 0) __builtin_memcpy(h_out + (size_t)r * cap_per_request, rec + (size_t)r * cap_per_request, sizeof(svs_candidate_point) * (size_t)m);
+    }
+  } else if (longest > 0) {      // (behind a request's own count the caller's rows receive what the device block held there: unspecified)
+    const size_t pitch = sizeof(svs_candidate_point) * (size_t)cap_per_request;
+    SVS_HIP(ctx, hipMemcpy2DAsync(h_out, pitch, fe->d_seed + off_rec, pitch, sizeof(svs_candidate_point) * (size_t)longest, (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+    SVS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  }
   return SVS_OK;
 }

@@ -131,3 +131,42 @@ class LoopCheck(C.Structure):
 class LoopResult(C.Structure):
     _fields_ = [("n_matches", C.c_int32), ("n_inliers", C.c_int32), ("best_hyp", C.c_int32), ("n_invalid_hyp", C.c_int32),
                 ("T_query_from_train", C.c_double * 12)]
+
+
+class SeedParams(C.Structure):
+    """svs_seed_params: params_.newpoint_clearance, ui.num_max_points, ui.min_num_points, USE_N_LEVELS_FOR_MATCHING (stereo_frontend.cpp:319-331, :735-749)."""
+    _fields_ = [("clearance", C.c_int32), ("num_max_points", C.c_int32), ("min_num_points", C.c_int32), ("n_levels", C.c_int32)]
+
+    @classmethod
+    def reference(cls, clearance=2, num_max_points=300, min_num_points=25, n_levels=3):
+        return cls(clearance, num_max_points, min_num_points, n_levels)
+
+    def max_records(self):
+        """the most one problem can produce = the smallest output capacity the library accepts"""
+        return sum((self.num_max_points >> l) + 1 for l in range(self.n_levels))
+
+
+# svs_seed_problem: one problem of svs_seed_points (device memory)
+SEED_PROBLEM_DTYPE = np.dtype([("T_newkey_from_cur", "<f8", 12), ("seed", "<u8"), ("add_flags", "<i4", 9), ("n0", "<i4", 3), ("n_tree", "<i4"),
+                               ("kf_index", "<i4"), ("first_point_id", "<i4"), ("use_order", "<i4"), ("n_order", "<i4", 3), ("pad_", "<i4")])
+assert SEED_PROBLEM_DTYPE.itemsize == 184
+
+
+class SeedArgs(C.Structure):
+    """svs_seed_args: device pointers of a batch of seeding problems"""
+    _fields_ = [("d_xy", C.c_void_p * 3), ("xy_bstride", C.c_size_t * 3), ("xy_cap", C.c_int32 * 3),
+                ("d_n", C.c_void_p * 3), ("n_bstride", C.c_size_t * 3),
+                ("d_cell_count", C.c_void_p * 3), ("cell_bstride", C.c_size_t * 3), ("n_cells", C.c_int32 * 3),
+                ("d_disp", C.c_void_p), ("disp_stride", C.c_int32), ("disp_bstride", C.c_size_t),
+                ("cam", Cam), ("d_prob", C.c_void_p),
+                ("d_tree_xy", C.c_void_p), ("d_tree_level", C.c_void_p), ("tree_bstride", C.c_size_t),
+                ("d_order", C.c_void_p * 3), ("order_bstride", C.c_size_t * 3), ("batch", C.c_int32)]
+
+
+SEED_FIRST, SEED_MORE = 0, 1
+
+
+class SeedRequest(C.Structure):
+    """svs_seed_request: one new keyframe of one stream for svs_frontend_seed_keyframes"""
+    _fields_ = [("stream", C.c_int32), ("mode", C.c_int32), ("kf_index", C.c_int32), ("first_point_id", C.c_int32),
+                ("T_newkey_from_cur", C.c_double * 12), ("seed", C.c_uint64), ("h_order", C.c_void_p * 3), ("n_order", C.c_int32 * 3), ("pad_", C.c_int32)]

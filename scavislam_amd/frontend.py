@@ -765,6 +765,33 @@ class StereoFrontend:
         T = np.ascontiguousarray(np.broadcast_to(T, (self.n_streams, 12)))
         self.ctx.check(self.ctx.lib.svs_frontend_recompute_cloud(self.h, T.ctypes.data))
 
+    def seedKeyframes(self, requests, params=None, cap=None):
+        """addNewPoints / addMorePoints (stereo_frontend.cpp:682-823) for a list of new keyframes from the state the last frame left on the device.
+        requests: dicts with stream, mode (SEED_FIRST / SEED_MORE), kf_index, first_point_id and optionally T_newkey_from_cur (default: identity), seed,
+        order (three index arrays into the levels' corner lists; absent: the generated order).  Returns a list of (CANDIDATE_DTYPE records in the
+        reference's list order, counts per level)."""
+        from .ctypes_types import SeedParams, SeedRequest
+        prm = params or SeedParams.reference(n_levels=min(3, self.params.n_levels or 3))
+        cap = prm.max_records() if cap is None else int(cap)
+        n = len(requests)
+        req = (SeedRequest * max(n, 1))()
+        keep = []
+        for r, q in zip(req, requests):
+            r.stream, r.mode, r.kf_index, r.first_point_id = int(q.get("stream", 0)), int(q["mode"]), int(q.get("kf_index", 0)), int(q.get("first_point_id", 0))
+            T = np.ascontiguousarray(q.get("T_newkey_from_cur", np.hstack([np.eye(3), np.zeros((3, 1))])), np.float64).reshape(12)
+            for i in range(12):
+                r.T_newkey_from_cur[i] = T[i]
+            r.seed = int(q.get("seed", 0)) & 0xFFFFFFFFFFFFFFFF
+            if q.get("order") is not None:
+                for l, o in enumerate(q["order"]):
+                    o = np.ascontiguousarray(o, np.int32)
+                    keep.append(o)
+                    r.h_order[l], r.n_order[l] = o.ctypes.data, len(o)
+        out = np.zeros((max(n, 1), max(cap, 1)), CANDIDATE_DTYPE)
+        cnt = np.zeros((max(n, 1), 3), np.int32)
+        self.ctx.check(self.ctx.lib.svs_frontend_seed_keyframes(self.h, n, req, C.byref(prm), out.ctypes.data, cap, cnt.ctypes.data))
+        return [(out[r, :int(cnt[r].sum())].copy(), cnt[r].copy()) for r in range(n)]
+
     def cloud_host(self, level, stream=0):
         """reference cloud (quarter grid; full resolution in the CUDA build) the last frame left for the next one"""
         clouds = (C.c_void_p * 3)()
