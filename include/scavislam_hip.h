@@ -142,7 +142,9 @@ int svs_ctx_set_option(svs_ctx *ctx, const char *name, int value);
    Host-side counters of the spin gate (kernels whose workgroups wait for each other inside one launch -- latency-mode trackers, multi-workgroup solves -- are kept from
    starving each other across the contexts of a process; DenseTracker / SlamGraph::optimize on two threads, stereo_slam.cpp:196, backend.cpp:157-224):
    "spin_lane_launches" launches of this context that skipped the gate (<= 16 workgroups AND provably fitting beside everything of that kind in flight),
-   "spin_gated_launches" launches that went through it. */
+   "spin_gated_launches" launches that went through it.
+   What the handles of the whole PROCESS hold right now (host-side, exact): "live_device_bytes" / "live_pinned_bytes" device / pinned memory owned by contexts and
+   handles (not the caller's svs_malloc blocks), "live_sync_objects" events + streams the library created + recorded graphs. */
 int svs_ctx_get_stat(svs_ctx *ctx, const char *name, long long *out);
 void *svs_ctx_stream(svs_ctx *ctx);
 const char *svs_last_error(svs_ctx *ctx);

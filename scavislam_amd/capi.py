@@ -286,7 +286,8 @@ class Context:
         self.call("svs_ctx_set_option", name.encode(), int(value))
 
     def get_stat(self, name):
-        """counters of the context (svs_ctx_get_stat): "trk_exact_sums", "trk_exact_fallbacks"; blocking"""
+        """counters of the context (svs_ctx_get_stat): "trk_exact_sums", "trk_exact_fallbacks" (blocking), "spin_lane_launches", "spin_gated_launches";
+        of the whole process: "live_device_bytes", "live_pinned_bytes", "live_sync_objects" (what contexts and handles hold right now)"""
         v = C.c_longlong(0)
         self.call("svs_ctx_get_stat", name.encode(), C.byref(v))
         return int(v.value)

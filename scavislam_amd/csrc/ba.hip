@@ -147,82 +147,68 @@ struct svs_ba {
   svs_comm *comm = nullptr;             // library-owned collective of sharded runs (svs_ba_set_comm)
   bool problem_valid = false;           // set by a COMPLETED svs_ba_set_problem / svs_ba_window_update; every other entry point requires it
   // ---- persistent window (svs_ba_window_*): every observation handed over since the last reset stays on the device ----
-  svs_ba_edge *w_store = nullptr; size_t w_n = 0, w_cap = 0;           // observation store, ids in .point / .pose, arrival order
-  int *w_pose_tab = nullptr, *w_point_tab = nullptr; size_t w_pose_tab_n = 0, w_point_tab_n = 0;      // id -> window index (-1: not in the window)
-  void *w_work = nullptr; size_t w_work_bytes = 0;                      // per-call work arrays (grow-only)
+  DevBuf<svs_ba_edge> w_store; size_t w_n = 0;                         // observation store, ids in .point / .pose, arrival order
+  DevBuf<int> w_pose_tab, w_point_tab;                                  // id -> window index (-1: not in the window), as many entries as the block holds
+  DevBuf<void> w_work;                                                  // per-call work arrays (grow-only)
   std::vector<svs_ba_constraint> w_cons_idx;
-  void *w_in = nullptr; size_t w_in_bytes = 0;                          // device mirror of the block a window_update call brings (ids, state, new observations, constraints)
-  unsigned char *w_hback = nullptr; size_t w_hback_bytes = 0;           // pinned read-back (counters, landmark lengths, pattern)
+  DevBuf<void> w_in;                                                    // device mirror of the block a window_update call brings (ids, state, new observations, constraints)
+  PinnedBuf<unsigned char> w_hback;                                     // pinned read-back (counters, landmark lengths, pattern)
   int P = 0, L = 0, E = 0, C = 0, n_chunks = 0, n_wide = 0, add_pose_terms = 1;
   std::vector<int> w_chunk_nlm;                       // landmarks per wave chunk (set_problem work vector)
   int nw_sched = 0;                                   // waves per Schur workgroup the chunk list was laid out for (0: chosen at launch)
   svs_cam cam{};
   svs_ba_params prm{};
-  double *d_poses[2] = {nullptr, nullptr}, *d_psi[2] = {nullptr, nullptr};
+  DevBuf<double> d_poses[2], d_psi[2];
   int cur = 0;
-  svs_ba_edge *d_edges = nullptr;
-  int *d_chunk_start = nullptr, *d_chunk_len = nullptr;
-  svs_ba_constraint *d_cons = nullptr;
-  double *d_red = nullptr;     // [nblk*36][bp 6P][bs 6P][chi2]
+  DevBuf<svs_ba_edge> d_edges;
+  DevBuf<int> d_chunk_start, d_chunk_len;
+  DevBuf<svs_ba_constraint> d_cons;
+  DevBuf<double> d_red;        // [nblk*36][bp 6P][bs 6P][chi2]
   size_t red_count = 0;
-  double *d_x = nullptr, *d_scal = nullptr, *d_linv = nullptr;
-  int *d_rowmax = nullptr, *d_colmin = nullptr;
-  double *d_upanel = nullptr;           // [P][R][36] panel rows of the LDS-window solve
+  DevBuf<double> d_x, d_scal, d_linv;
+  DevBuf<int> d_rowmax, d_colmin;
+  DevBuf<double> d_upanel;              // [P][R][36] panel rows of the LDS-window solve
   int env_R = 0;                        // max envelope row length + 1 (0 = unknown)
   // fill-reducing order of the pose blocks for the solve (what LinearSolverCSparse's block ordering does for the reference, slam_graph.cpp:1063-1074):
   // solver row k <-> pose perm[k].  The Schur kernels keep writing the system in the caller's pose order; when the order pays, the solve runs on a permuted
   // copy (ba_permute_system_kernel) and its x / trial poses are scattered back (ba_unpermute_kernel).  env_R_natural = the envelope without it.
   bool perm_active = false; int env_R_natural = 0;
-  int *d_perm = nullptr; double *d_perm_sys = nullptr; size_t cap_perm_sys = 0;      // [P]; H' + bp' + bs' + poses' + trial poses' + x'
+  DevBuf<int> d_perm; DevBuf<double> d_perm_sys;      // [P]; H' + bp' + bs' + poses' + trial poses' + x'
   std::vector<int> h_perm;
   bool use_lds_solve = false, use_fused_solve = false; size_t lds_solve_smem = 0;
   bool timing = false;                         // hipEvent brackets around the three dominant kernels of every trial (svs_ba_set_timing / svs_ba_kernel_times)
   int fuse_lds_panel = 0;                      // the fused solve keeps its back-substitution panel in LDS (ensure_profile)
   int fuse_P1 = 0;    // two-front fused solve: rows of the reversed front (0 = single front), launch counter for its flags
-  int *d_rowmax2 = nullptr; size_t cap_rowmax2 = 0; double *d_xfer = nullptr; unsigned *d_flags = nullptr;
-  unsigned *d_gridbar = nullptr; int grid_G = 0;      // multi-workgroup solve: arrival counter + failure flag, number of workgroups (0 = not used)
-  double *d_tilews = nullptr; size_t cap_tilews = 0; int tiles_G = 0, tiles_S = 0, tiles_tpw = 0, tiles_gq = 0, tiles_ncm = 0;      // tile-resident variant of it (ba_solve_tiles.inc): workspace, grid, tile rows, own tiles per workgroup (tiles_G = 0: not used)
+  DevBuf<int> d_rowmax2; DevBuf<double> d_xfer; DevBuf<unsigned> d_flags;
+  DevBuf<unsigned> d_gridbar; int grid_G = 0;      // multi-workgroup solve: arrival counter + failure flag, number of workgroups (0 = not used)
+  DevBuf<double> d_tilews; int tiles_G = 0, tiles_S = 0, tiles_tpw = 0, tiles_gq = 0, tiles_ncm = 0;      // tile-resident variant of it (ba_solve_tiles.inc): workspace, grid, tile rows, own tiles per workgroup (tiles_G = 0: not used)
   // The all-accepted optimize of a resident window has a FIXED launch topology -- control upload, num_iters x (clear, Schur, [permute,] solve, [unpermute,] back-substitute,
   // decide), control read-back: ~25 stream operations, ~5 us of host time each, i.e. the ceiling of windows in flight (6 k windows / s in bench.py where the kernels
   // would allow 10 k).  It is captured ONCE per (problem layout, current state buffer) and replayed with one hipGraphLaunch (slam_graph.cpp:312-355 = one call).
-  struct Graph { hipGraphExec_t exec = nullptr; uint64_t sig = 0, seen = 0; };      // seen: the signature of the last call that ran kernel by kernel
+  struct Graph { owned::GraphExec exec; uint64_t sig = 0, seen = 0; };      // seen: the signature of the last call that ran kernel by kernel
   Graph graph[2];                              // by ba->cur at the start of the call
   long long n_graph_launches = 0, n_graph_captures = 0;
-  double *d_ctl = nullptr, *h_ctl = nullptr;   // LM control block of the speculative path (device + pinned host mirror)
+  DevBuf<double> d_ctl; PinnedBuf<double> h_ctl;      // LM control block of the speculative path (device + pinned host mirror)
   int ctl_iters = 0;
-  std::vector<hipEvent_t> spec_ev;      // 6 events per speculative trial
-  double *h_scal = nullptr;             // pinned host mirror of d_scal (the per-trial read-back must not go through a pageable staging copy)
-  double *d_pattern = nullptr;          // [P*P] structural indicator (all-reduced in sharded runs)
+  std::vector<owned::Event> spec_ev;    // 6 events per speculative trial
+  PinnedBuf<double> h_scal;             // pinned host mirror of d_scal (the per-trial read-back must not go through a pageable staging copy)
+  DevBuf<double> d_pattern;             // [P*P] structural indicator (all-reduced in sharded runs)
   std::vector<double> h_pattern;
-  // persistent host work arrays / pinned staging of set_problem, device capacities (grow-only)
+  // persistent host work arrays / pinned staging of set_problem (grow-only)
   std::vector<int> w_anchor, w_nobs, w_pos, w_off, w_aoff, w_alist, w_order, w_cs, w_cl;
   std::vector<int> w_cnt;                      // [workers][L] per-worker landmark counts -> start offsets
   std::vector<uint64_t> w_keys, w_ent;         // per edge: (point, pose) / per slot: (pose, source index)
-  unsigned char *h_stage = nullptr; size_t h_stage_cap = 0, h_stage_used = 0;      // pinned staging of the small per-call uploads
-  unsigned char *h_state = nullptr; size_t h_state_cap = 0;                         // pinned landing area of svs_ba_get_state
+  PinnedBuf<unsigned char> h_stage; size_t h_stage_used = 0;                        // pinned staging of the small per-call uploads
+  PinnedBuf<unsigned char> h_state;                                                 // pinned landing area of svs_ba_get_state
   std::vector<int32_t> w_ids_p, w_ids_l, w_ids_a;      // svs_ba_set_problem's device route: identity ids, anchors by point
   HostPool *pool = nullptr;                    // marshalling workers: ONE pool per process, shared by all optimizers (created on first use)
   std::vector<double> w_pat_local;
-  svs_ba_edge *h_edges = nullptr; size_t h_edges_cap = 0;
-  size_t cap_poses[2] = {0, 0}, cap_psi[2] = {0, 0}, cap_edges = 0, cap_cs = 0, cap_cl = 0, cap_cons = 0, cap_red = 0, cap_x = 0, cap_scal = 0,
-         cap_linv = 0, cap_rowmax = 0, cap_colmin = 0, cap_pattern = 0, cap_upanel = 0;
+  PinnedBuf<svs_ba_edge> h_edges;
   bool profile_ready = false;
-  hipEvent_t ev[6] = {};
+  owned::Event ev[6];
   float t_reduce = 0, t_solve = 0, t_backsub = 0;
   int n_reduce = 0;
-  void free_all() {
-    for (int i = 0; i < 2; ++i) { if (d_poses[i]) (void)hipFree(d_poses[i]); if (d_psi[i]) (void)hipFree(d_psi[i]); d_poses[i] = d_psi[i] = nullptr; }
-    if (d_edges) (void)hipFree(d_edges); if (d_chunk_start) (void)hipFree(d_chunk_start); if (d_chunk_len) (void)hipFree(d_chunk_len);
-    if (d_cons) (void)hipFree(d_cons); if (d_red) (void)hipFree(d_red); if (d_x) (void)hipFree(d_x); if (d_scal) (void)hipFree(d_scal);
-    if (d_linv) (void)hipFree(d_linv);
-    if (d_rowmax) (void)hipFree(d_rowmax); if (d_colmin) (void)hipFree(d_colmin); if (d_pattern) (void)hipFree(d_pattern);
-    if (d_upanel) (void)hipFree(d_upanel); d_upanel = nullptr; env_R = 0; use_lds_solve = false;
-    d_rowmax = d_colmin = nullptr; d_pattern = nullptr; profile_ready = false;
-    d_edges = nullptr; d_chunk_start = d_chunk_len = nullptr; d_cons = nullptr; d_red = d_x = d_scal = d_linv = nullptr;
-    cap_poses[0] = cap_poses[1] = cap_psi[0] = cap_psi[1] = cap_edges = cap_cs = cap_cl = cap_cons = cap_red = cap_x = cap_scal = cap_linv = cap_rowmax =
-        cap_colmin = cap_pattern = cap_upanel = 0;
-    if (h_edges) { (void)hipHostFree(h_edges); h_edges = nullptr; h_edges_cap = 0; }
-  }
+  ~svs_ba() { (void)hipStreamSynchronize(ctx->stream); }      // (before the members go)
 };
 
 static BaDev make_dev(const svs_ba *ba, double lambda, int cur = -1, double *ctl = nullptr) {
@@ -249,25 +235,23 @@ static int schur_nw(const svs_ba *ba) {
 }
 static bool schur_big_pool(const svs_ba *ba, int nw) { return nw != 4 || div_up(ba->n_chunks, nw) <= ba->ctx->n_cu; }
 
+// the device buffers of the problem persist across calls and only grow, with a quarter to spare (the window changes by about one keyframe per call)
+template <class T> static hipError_t ba_grow(DevBuf<T> &b, size_t bytes) { return b.reserve(bytes, bytes + bytes / 4 + 256); }
 // Small uploads go through one pinned staging area: an asynchronous copy from pageable memory makes the runtime wait for
 // the stream (it has to reuse its own bounce buffer), which would serialise the host behind the big edge DMA.  The area is
 // reset by svs_ba_set_problem after its initial stream synchronisation.
 static int stage_reserve(svs_ba *ba, size_t bytes) {
   svs_ctx *ctx = ba->ctx;
-  if (bytes <= ba->h_stage_cap) return SVS_OK;
+  if (bytes <= ba->h_stage.bytes()) return SVS_OK;
   SVS_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  if (ba->h_stage) (void)hipHostFree(ba->h_stage);
-  ba->h_stage = nullptr; ba->h_stage_cap = 0;
-  const size_t want = bytes + bytes / 4 + 4096;
-  SVS_HIP(ctx, hipHostMalloc((void **)&ba->h_stage, want, hipHostMallocDefault));
-  ba->h_stage_cap = want;
+  SVS_HIP(ctx, ba->h_stage.reserve(bytes, bytes + bytes / 4 + 4096));
   return SVS_OK;
 }
 static int stage_upload(svs_ba *ba, void *d_dst, const void *h_src, size_t bytes) {
   svs_ctx *ctx = ba->ctx;
   if (bytes == 0) return SVS_OK;
   const size_t off = (ba->h_stage_used + 63) & ~(size_t)63;
-  if (off + bytes > ba->h_stage_cap) {      // should not happen (reserved up front): fall back to the pageable copy
+  if (off + bytes > ba->h_stage.bytes()) {      // should not happen (reserved up front): fall back to the pageable copy
     SVS_HIP(ctx, hipMemcpyAsync(d_dst, h_src, bytes, hipMemcpyHostToDevice, ctx->stream));
     return SVS_OK;
   }
@@ -284,7 +268,7 @@ static int stage_upload(svs_ba *ba, void *d_dst, const void *h_src, size_t bytes
 
 extern "C" int svs_ba_create(svs_ctx *ctx, svs_ba **out) {
   SVS_REQUIRE(ctx, ctx && out);
-  svs_ba *ba = new svs_ba();
+  std::unique_ptr<svs_ba> ba(new svs_ba());
   ba->ctx = ctx;
   SVS_DEVICE(ctx);
   {
@@ -296,37 +280,12 @@ extern "C" int svs_ba_create(svs_ctx *ctx, svs_ba **out) {
     o.debug = num("SVS_BA_DEBUG", 0, 2, 0); o.nw = num("SVS_BA_NW", 4, 8, 0); o.p1 = num("SVS_BA_P1", 0, SOLVE_MAX_P, -1);
     o.group = num("SVS_BA_GROUP", 1, WIN, 0); o.host_threads = num("SVS_HOST_THREADS", 1, 64, 0);
   }
-  for (auto &e : ba->ev) SVS_HIP(ctx, hipEventCreate(&e));
-  *out = ba;
+  for (auto &e : ba->ev) SVS_HIP(ctx, e.create());
+  *out = ba.release();
   return SVS_OK;
 }
 extern "C" int svs_ba_destroy(svs_ba *ba) {
   if (!ba) return SVS_OK;
-  (void)hipStreamSynchronize(ba->ctx->stream);
-  if (ba->h_scal) { (void)hipHostFree(ba->h_scal); ba->h_scal = nullptr; }
-  if (ba->h_ctl) { (void)hipHostFree(ba->h_ctl); ba->h_ctl = nullptr; }
-  if (ba->h_stage) { (void)hipHostFree(ba->h_stage); ba->h_stage = nullptr; ba->h_stage_cap = 0; }
-  if (ba->h_state) { (void)hipHostFree(ba->h_state); ba->h_state = nullptr; ba->h_state_cap = 0; }
-  if (ba->d_ctl) { (void)hipFree(ba->d_ctl); ba->d_ctl = nullptr; }
-  if (ba->d_rowmax2) (void)hipFree(ba->d_rowmax2);
-  if (ba->d_perm) (void)hipFree(ba->d_perm);
-  if (ba->d_perm_sys) (void)hipFree(ba->d_perm_sys);
-  if (ba->d_xfer) (void)hipFree(ba->d_xfer);
-  if (ba->d_flags) (void)hipFree(ba->d_flags);
-  if (ba->d_gridbar) (void)hipFree(ba->d_gridbar);
-  if (ba->d_tilews) (void)hipFree(ba->d_tilews);
-  if (ba->w_store) (void)hipFree(ba->w_store);
-  if (ba->w_pose_tab) (void)hipFree(ba->w_pose_tab);
-  if (ba->w_point_tab) (void)hipFree(ba->w_point_tab);
-  if (ba->w_work) (void)hipFree(ba->w_work);
-  if (ba->w_in) (void)hipFree(ba->w_in);
-  if (ba->w_hback) (void)hipHostFree(ba->w_hback);
-  for (auto &e : ba->spec_ev) if (e) (void)hipEventDestroy(e);
-  ba->spec_ev.clear();
-  for (auto &g : ba->graph) if (g.exec) { (void)hipGraphExecDestroy(g.exec); g.exec = nullptr; }
-  ba->free_all();
-  ba->pool = nullptr;                   // shared, not owned
-  for (auto &e : ba->ev) if (e) (void)hipEventDestroy(e);
   delete ba;
   return SVS_OK;
 }
@@ -558,21 +517,7 @@ extern "C" int svs_ba_set_problem(svs_ba *ba, int P, const double *h_poses, int 
   // edge slots: landmarks in that order, each with its observers ascending (insertion sort inside the landmark's slots)
   lm_pos.assign(L, -1); lm_off.assign(lm_order.size() + 1, 0);
   for (size_t k = 0; k < lm_order.size(); ++k) { lm_pos[lm_order[k]] = (int)k; lm_off[k + 1] = lm_off[k] + n_obs[lm_order[k]]; }
-  if ((size_t)E > ba->h_edges_cap) {
-    if (ba->h_edges) (void)hipHostFree(ba->h_edges);
-    ba->h_edges_cap = (size_t)E + (size_t)E / 4 + 64;
-    SVS_HIP(ctx, hipHostMalloc((void **)&ba->h_edges, sizeof(svs_ba_edge) * ba->h_edges_cap, hipHostMallocDefault));
-  }
-  // device buffers persist across calls and only grow (the window changes by about one keyframe per call)
-  auto ensure = [&](void **ptr, size_t *cap, size_t bytes) -> hipError_t {
-    if (bytes <= *cap && *ptr) return hipSuccess;
-    if (*ptr) (void)hipFree(*ptr);
-    *ptr = nullptr; *cap = 0;
-    const size_t want = bytes + bytes / 4 + 256;
-    hipError_t e = hipMalloc(ptr, want);
-    if (e == hipSuccess) *cap = want;
-    return e;
-  };
+  if (sizeof(svs_ba_edge) * (size_t)E > ba->h_edges.bytes()) SVS_HIP(ctx, ba->h_edges.alloc((size_t)E + (size_t)E / 4 + 64));
   t_2 = now();
   svs_ba_edge *sorted = ba->h_edges;      // pinned: the upload is a plain DMA, no pageable staging copy
   for_range(E, [&](int t, int i0, int i1) {            // pass 2, compact arrays only: every edge takes its slot (same worker ranges as pass 1)
@@ -621,7 +566,7 @@ extern "C" int svs_ba_set_problem(svs_ba *ba, int P, const double *h_poses, int 
   t_3 = now();
   // gather the records into slot order (sequential writes into the pinned buffer, each record read once) in a few
   // sub-ranges, each uploaded as soon as it is complete: the DMA of one overlaps the gather of the next
-  SVS_HIP(ctx, ensure((void **)&ba->d_edges, &ba->cap_edges, sizeof(svs_ba_edge) * (size_t)std::max(E, 1)));
+  SVS_HIP(ctx, ba_grow(ba->d_edges, sizeof(svs_ba_edge) * (size_t)std::max(E, 1)));
   {
     const int n_sub = par ? 4 : 1;
     for (int sb = 0; sb < n_sub; ++sb) {
@@ -650,8 +595,8 @@ extern "C" int svs_ba_set_problem(svs_ba *ba, int P, const double *h_poses, int 
   const size_t nblk = (size_t)P * (P + 1) / 2;
   ba->red_count = nblk * 36 + 12 * (size_t)P + SC_SLOTS;
   for (int k = 0; k < 2; ++k) {
-    SVS_HIP(ctx, ensure((void **)&ba->d_poses[k], &ba->cap_poses[k], sizeof(double) * 12 * (size_t)P));
-    SVS_HIP(ctx, ensure((void **)&ba->d_psi[k], &ba->cap_psi[k], sizeof(double) * 3 * (size_t)std::max(L, 1)));
+    SVS_HIP(ctx, ba_grow(ba->d_poses[k], sizeof(double) * 12 * (size_t)P));
+    SVS_HIP(ctx, ba_grow(ba->d_psi[k], sizeof(double) * 3 * (size_t)std::max(L, 1)));
   }
   { int rc = stage_upload(ba, ba->d_poses[0], h_poses, sizeof(double) * 12 * (size_t)P); if (rc) return rc; }
   SVS_HIP(ctx, hipMemcpyAsync(ba->d_poses[1], ba->d_poses[0], sizeof(double) * 12 * (size_t)P, hipMemcpyDeviceToDevice, ctx->stream));
@@ -659,16 +604,16 @@ extern "C" int svs_ba_set_problem(svs_ba *ba, int P, const double *h_poses, int 
     int rc = stage_upload(ba, ba->d_psi[0], h_psi, sizeof(double) * 3 * (size_t)L); if (rc) return rc;
     SVS_HIP(ctx, hipMemcpyAsync(ba->d_psi[1], ba->d_psi[0], sizeof(double) * 3 * (size_t)L, hipMemcpyDeviceToDevice, ctx->stream));
   }
-  SVS_HIP(ctx, ensure((void **)&ba->d_chunk_start, &ba->cap_cs, sizeof(int) * (size_t)std::max(ba->n_chunks + ba->n_wide, 1)));
-  SVS_HIP(ctx, ensure((void **)&ba->d_chunk_len, &ba->cap_cl, sizeof(int) * (size_t)std::max(ba->n_chunks + ba->n_wide, 1)));
-  SVS_HIP(ctx, ensure((void **)&ba->d_cons, &ba->cap_cons, sizeof(svs_ba_constraint) * (size_t)std::max(C, 1)));
-  SVS_HIP(ctx, ensure((void **)&ba->d_red, &ba->cap_red, sizeof(double) * ba->red_count));
-  SVS_HIP(ctx, ensure((void **)&ba->d_x, &ba->cap_x, sizeof(double) * 6 * (size_t)P));
-  SVS_HIP(ctx, ensure((void **)&ba->d_scal, &ba->cap_scal, sizeof(double) * SC_N));
-  SVS_HIP(ctx, ensure((void **)&ba->d_linv, &ba->cap_linv, sizeof(double) * 36 * (size_t)P));
-  SVS_HIP(ctx, ensure((void **)&ba->d_rowmax, &ba->cap_rowmax, sizeof(int) * (size_t)P));
-  SVS_HIP(ctx, ensure((void **)&ba->d_colmin, &ba->cap_colmin, sizeof(int) * (size_t)P));
-  SVS_HIP(ctx, ensure((void **)&ba->d_pattern, &ba->cap_pattern, sizeof(double) * (size_t)P * P));
+  SVS_HIP(ctx, ba_grow(ba->d_chunk_start, sizeof(int) * (size_t)std::max(ba->n_chunks + ba->n_wide, 1)));
+  SVS_HIP(ctx, ba_grow(ba->d_chunk_len, sizeof(int) * (size_t)std::max(ba->n_chunks + ba->n_wide, 1)));
+  SVS_HIP(ctx, ba_grow(ba->d_cons, sizeof(svs_ba_constraint) * (size_t)std::max(C, 1)));
+  SVS_HIP(ctx, ba_grow(ba->d_red, sizeof(double) * ba->red_count));
+  SVS_HIP(ctx, ba_grow(ba->d_x, sizeof(double) * 6 * (size_t)P));
+  SVS_HIP(ctx, ba_grow(ba->d_scal, sizeof(double) * SC_N));
+  SVS_HIP(ctx, ba_grow(ba->d_linv, sizeof(double) * 36 * (size_t)P));
+  SVS_HIP(ctx, ba_grow(ba->d_rowmax, sizeof(int) * (size_t)P));
+  SVS_HIP(ctx, ba_grow(ba->d_colmin, sizeof(int) * (size_t)P));
+  SVS_HIP(ctx, ba_grow(ba->d_pattern, sizeof(double) * (size_t)P * P));
   if (!cs.empty()) {
     int rc = stage_upload(ba, ba->d_chunk_start, cs.data(), sizeof(int) * cs.size()); if (rc) return rc;
     rc = stage_upload(ba, ba->d_chunk_len, cl.data(), sizeof(int) * cl.size()); if (rc) return rc;
@@ -786,13 +731,10 @@ static int ensure_profile(svs_ba *ba, svs_allreduce_fn allreduce, void *user) {
       rowmax = rm_p;
       pat = pp;      // (the two-front profile below reads the pattern of the order the solve runs in)
       const size_t nblk_p = (size_t)P * (P + 1) / 2, n_sys = nblk_p * 36 + 12 * (size_t)P + 24 * (size_t)P + 6 * (size_t)P;
-      if (!ba->d_perm || ba->cap_perm_sys < sizeof(double) * n_sys) {
-        if (ba->d_perm) (void)hipFree(ba->d_perm);
-        if (ba->d_perm_sys) (void)hipFree(ba->d_perm_sys);
-        ba->d_perm = nullptr; ba->d_perm_sys = nullptr;
-        SVS_HIP(ctx, hipMalloc(&ba->d_perm, sizeof(int) * SOLVE_MAX_P));
-        SVS_HIP(ctx, hipMalloc(&ba->d_perm_sys, sizeof(double) * n_sys));
-        ba->cap_perm_sys = sizeof(double) * n_sys;
+      if (!ba->d_perm || ba->d_perm_sys.bytes() < sizeof(double) * n_sys) {
+        ba->d_perm.reset(); ba->d_perm_sys.reset();
+        SVS_HIP(ctx, ba->d_perm.alloc(SOLVE_MAX_P));
+        SVS_HIP(ctx, ba->d_perm_sys.alloc(n_sys));
       }
       { int rc = stage_upload(ba, ba->d_perm, order.data(), sizeof(int) * P); if (rc) return rc; }
     }
@@ -847,26 +789,17 @@ static int ensure_profile(svs_ba *ba, svs_allreduce_fn allreduce, void *user) {
     if (ba->lds_solve_smem + extra <= 158 * 1024) { ba->fuse_lds_panel = 1; ba->lds_solve_smem += extra; }
   }
   if (ba->use_fused_solve) {
-    if (!ba->d_rowmax2 || ba->cap_rowmax2 < sizeof(int) * rm2.size()) {
-      if (ba->d_rowmax2) (void)hipFree(ba->d_rowmax2);
-      ba->cap_rowmax2 = sizeof(int) * rm2.size() + 256;
-      SVS_HIP(ctx, hipMalloc(&ba->d_rowmax2, ba->cap_rowmax2));
-    }
+    SVS_HIP(ctx, ba->d_rowmax2.reserve(sizeof(int) * rm2.size(), sizeof(int) * rm2.size() + 256));
     { int rc = stage_upload(ba, ba->d_rowmax2, rm2.data(), sizeof(int) * rm2.size()); if (rc) return rc; }
     if (!ba->d_xfer) {
-      SVS_HIP(ctx, hipMalloc(&ba->d_xfer, sizeof(double) * (FUSE_SLOTS * FUSE_SLOTS * 36 + 2 * FUSE_SLOTS * 6)));
-      SVS_HIP(ctx, hipMalloc(&ba->d_flags, sizeof(unsigned) * 4));
+      SVS_HIP(ctx, ba->d_xfer.alloc(FUSE_SLOTS * FUSE_SLOTS * 36 + 2 * FUSE_SLOTS * 6));
+      SVS_HIP(ctx, ba->d_flags.alloc(4));
       SVS_HIP(ctx, hipMemsetAsync(ba->d_flags, 0, sizeof(unsigned) * 4, ctx->stream));
     }
   }
   if (ba->use_lds_solve) {
     const size_t up_count = 2 * (36 * (size_t)P * std::max(R, FUSE_SLOTS) + 128);      // per front: panel rows + write sink + zero block of the fused kernel
-    if (sizeof(double) * up_count > ba->cap_upanel || !ba->d_upanel) {
-      if (ba->d_upanel) { (void)hipFree(ba->d_upanel); ba->d_upanel = nullptr; ba->cap_upanel = 0; }
-      const size_t want = sizeof(double) * (up_count + up_count / 4);
-      SVS_HIP(ctx, hipMalloc(&ba->d_upanel, want));
-      ba->cap_upanel = want;
-    }
+    SVS_HIP(ctx, ba->d_upanel.reserve(sizeof(double) * up_count, sizeof(double) * (up_count + up_count / 4)));
     // the fused kernel's zero block sits right behind the P x 10 panel rows of each front (position depends on P): clear sink + zero block
     SVS_HIP(ctx, hipMemsetAsync(ba->d_upanel + (up_count / 2 - 128), 0, sizeof(double) * 128, ctx->stream));
     SVS_HIP(ctx, hipMemsetAsync(ba->d_upanel + (up_count - 128), 0, sizeof(double) * 128, ctx->stream));
@@ -885,9 +818,7 @@ static int ensure_profile(svs_ba *ba, svs_allreduce_fn allreduce, void *user) {
     const long tile_rows = (long)R * (R + 1) / 2 * 6;
     ba->grid_G = (int)std::max(8l, std::min((long)ctx->n_cu, (tile_rows + 4 * SOLVE_THREADS - 1) / (4 * SOLVE_THREADS)));
     if (ba->opt.grid_g > 0) ba->grid_G = std::min(ba->opt.grid_g, ctx->n_cu);      // experiments only
-    if (!ba->d_gridbar) {
-      SVS_HIP(ctx, hipMalloc(&ba->d_gridbar, sizeof(unsigned) * (32 * GRID_NBAR + 4)));
-    }
+    if (!ba->d_gridbar) SVS_HIP(ctx, ba->d_gridbar.alloc(32 * GRID_NBAR + 4));
     const size_t smem_g = sizeof(double) * ((size_t)P * 36 + 36 + 6 * (size_t)P);
     if (smem_g > 64 * 1024) SVS_HIP(ctx, hipFuncSetAttribute((const void *)ba_solve_grid_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem_g));
     // the tile-resident blocked Cholesky where its tiles fit the workgroups' LDS (ba_solve_tiles.inc); the kernel above otherwise (and as the A/B switch "no_tile_solve")
@@ -907,12 +838,7 @@ static int ensure_profile(svs_ba *ba, svs_allreduce_fn allreduce, void *user) {
       if (tpw <= TS_MAXT && ncm <= 2 * TS_MAXT && ts_lds_bytes(tpw, ncm) <= 158 * 1024 &&
           hipFuncSetAttribute((const void *)ba_solve_tiles_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ts_lds_bytes(tpw, ncm)) == hipSuccess) {
         const size_t want = sizeof(double) * ts_ws_doubles(S);
-        if (!ba->d_tilews || ba->cap_tilews < want) {
-          if (ba->d_tilews) (void)hipFree(ba->d_tilews);
-          ba->d_tilews = nullptr; ba->cap_tilews = 0;
-          SVS_HIP(ctx, hipMalloc(&ba->d_tilews, want + want / 4));
-          ba->cap_tilews = want + want / 4;
-        }
+        SVS_HIP(ctx, ba->d_tilews.reserve(want, want + want / 4));
         ba->tiles_G = G; ba->tiles_S = S; ba->tiles_tpw = tpw; ba->tiles_gq = gq; ba->tiles_ncm = ncm;
       }
     }
@@ -922,7 +848,7 @@ static int ensure_profile(svs_ba *ba, svs_allreduce_fn allreduce, void *user) {
 }
 
 // buildSystem + Schur reduction at the current state (MODE 0 kernels)
-static int launch_reduce(svs_ba *ba, double lambda, int cur = -1, double *ctl = nullptr, hipEvent_t *ev = nullptr) {
+static int launch_reduce(svs_ba *ba, double lambda, int cur = -1, double *ctl = nullptr, const owned::Event *ev = nullptr) {
   svs_ctx *ctx = ba->ctx;
   BaDev B = make_dev(ba, lambda, cur, ctl);
   if (!ev) ev = ba->ev;
@@ -930,7 +856,8 @@ static int launch_reduce(svs_ba *ba, double lambda, int cur = -1, double *ctl = 
   if (B.C > 0 && !B.fuse_cons) { hipLaunchKernelGGL(ba_constraint_kernel<0>, dim3(B.C), dim3(64), 0, ctx->stream, B); SVS_LAUNCH_CHECK(ctx); }
   if (ba->timing) SVS_HIP(ctx, hipEventRecord(ev[0], ctx->stream));     // brackets the landmark (Schur) kernel alone
   const bool timeline = ba->opt.debug >= 2 && B.n_chunks > 0;
-  if (timeline) SVS_HIP(ctx, hipMalloc(&B.dbg, sizeof(long long) * DBG_W * (size_t)B.n_chunks));
+  DevBuf<long long> dbg;
+  if (timeline) SVS_HIP(ctx, dbg.alloc(DBG_W * (size_t)B.n_chunks, &B.dbg));
   int dbg_nw = 1;
   if (B.n_chunks > 0) {
     const int nw = schur_nw(ba);
@@ -955,7 +882,7 @@ static int launch_reduce(svs_ba *ba, double lambda, int cur = -1, double *ctl = 
     std::vector<long long> h(DBG_W * (size_t)B.n_chunks);
     SVS_HIP(ctx, hipMemcpyAsync(h.data(), B.dbg, sizeof(long long) * h.size(), hipMemcpyDeviceToHost, ctx->stream));
     SVS_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    (void)hipFree(B.dbg);
+    dbg.reset();
     long long t0 = h[0], t1 = h[DBG_N - 1];
     for (int c = 0; c < B.n_chunks; ++c) { t0 = std::min(t0, h[(size_t)DBG_W * c]); t1 = std::max(t1, h[(size_t)DBG_W * c + DBG_N - 1]); }
     double ph[DBG_N] = {}, phmax[DBG_N] = {}, s_start = 0, mx_start = 0, mx_dur = 0;
@@ -1028,10 +955,10 @@ extern "C" int svs_ba_reduced_system(svs_ba *ba, double lambda, double *h_Hred, 
   if (rc) return rc;
   BaDev B = make_dev(ba, lambda);
   const int n = 6 * ba->P;
-  double *d_full = nullptr, *d_b = nullptr;
-  SVS_HIP(ctx, hipMalloc(&d_full, sizeof(double) * (size_t)n * n));
-  SVS_HIP(ctx, hipMalloc(&d_b, sizeof(double) * n));
-  hipLaunchKernelGGL(ba_expand_kernel, dim3(256), dim3(256), 0, ctx->stream, B, d_full, d_b);
+  DevBuf<double> d_full, d_b;
+  SVS_HIP(ctx, d_full.alloc((size_t)n * n));
+  SVS_HIP(ctx, d_b.alloc(n));
+  hipLaunchKernelGGL(ba_expand_kernel, dim3(256), dim3(256), 0, ctx->stream, B, d_full.get(), d_b.get());
   SVS_LAUNCH_CHECK(ctx);
   if (h_Hred) SVS_HIP(ctx, hipMemcpyAsync(h_Hred, d_full, sizeof(double) * (size_t)n * n, hipMemcpyDeviceToHost, ctx->stream));
   if (h_bred) SVS_HIP(ctx, hipMemcpyAsync(h_bred, d_b, sizeof(double) * n, hipMemcpyDeviceToHost, ctx->stream));
@@ -1039,7 +966,6 @@ extern "C" int svs_ba_reduced_system(svs_ba *ba, double lambda, double *h_Hred, 
   if (h_chi2) SVS_HIP(ctx, hipMemcpyAsync(chi_slots, B.chi2_cur, sizeof(chi_slots), hipMemcpyDeviceToHost, ctx->stream));
   SVS_HIP(ctx, hipStreamSynchronize(ctx->stream));
   if (h_chi2) { double t = 0; for (int i = 0; i < SC_SLOTS; ++i) t += chi_slots[i]; *h_chi2 = t; }
-  (void)hipFree(d_full); (void)hipFree(d_b);
   return SVS_OK;
 }
 
@@ -1065,10 +991,10 @@ extern "C" int svs_ba_trial(svs_ba *ba, double lambda, const double *h_xp, doubl
   int rc = launch_reduce(ba, lambda);
   if (rc) return rc;
   BaDev B = make_dev(ba, lambda);
-  struct DevBuf { double *p = nullptr; ~DevBuf() { if (p) (void)hipFree(p); } } xp;      // x_p of the caller (d_x stays as the last solve left it)
-  SVS_HIP(ctx, hipMalloc(&xp.p, sizeof(double) * 6 * (size_t)P));
-  B.x = xp.p;
-  SVS_HIP(ctx, hipMemcpyAsync(xp.p, h_xp, sizeof(double) * 6 * (size_t)P, hipMemcpyHostToDevice, ctx->stream));
+  DevBuf<double> xp;      // x_p of the caller (d_x stays as the last solve left it)
+  SVS_HIP(ctx, xp.alloc(6 * (size_t)P));
+  B.x = xp;
+  SVS_HIP(ctx, hipMemcpyAsync(xp, h_xp, sizeof(double) * 6 * (size_t)P, hipMemcpyHostToDevice, ctx->stream));
   if (B.n_chunks == 0) SVS_HIP(ctx, hipMemsetAsync(ba->d_scal, 0, sizeof(double) * SC_N, ctx->stream));      // else zeroed by the Schur kernel
   hipLaunchKernelGGL(ba_trial_poses_kernel, dim3(div_up(P, 64)), dim3(64), 0, ctx->stream, B);
   SVS_LAUNCH_CHECK(ctx);
@@ -1091,7 +1017,7 @@ extern "C" int svs_ba_trial(svs_ba *ba, double lambda, const double *h_xp, doubl
 }
 
 // enqueue one LM trial on the ctx stream: system at the current state, solve, trial state, trial chi2 + scale
-static int enqueue_trial(svs_ba *ba, double lambda, int cur, double *ctl, hipEvent_t *ev, size_t smem_fallback, svs_allreduce_fn allreduce, void *user) {
+static int enqueue_trial(svs_ba *ba, double lambda, int cur, double *ctl, const owned::Event *ev, size_t smem_fallback, svs_allreduce_fn allreduce, void *user) {
   svs_ctx *ctx = ba->ctx;
   // (re)build at the current state with this lambda; the state only changes on accept, so a
   // rebuilt system equals g2o's "restore diagonal + add new lambda"
@@ -1164,7 +1090,7 @@ static int enqueue_trial(svs_ba *ba, double lambda, int cur, double *ctl, hipEve
   if (allreduce) { rc = allreduce(ba->d_scal + SC_CHI, 2 * SC_SLOTS, user); if (rc) { ctx->err = "allreduce callback failed"; return SVS_ERR_INVALID; } }
   return SVS_OK;
 }
-static int add_trial_times(svs_ba *ba, hipEvent_t *ev) {
+static int add_trial_times(svs_ba *ba, const owned::Event *ev) {
   svs_ctx *ctx = ba->ctx;
   float ms;
   if (!ba->timing) return SVS_OK;
@@ -1209,14 +1135,12 @@ static int optimize_begin(svs_ba *ba, svs_allreduce_fn allreduce, void *user, Op
     const int n_it = prm.num_iters;
     const size_t n_ctl = 8 + 8 * (size_t)n_it;
     if (ba->ctl_iters < n_it) {
-      if (ba->d_ctl) (void)hipFree(ba->d_ctl);
-      if (ba->h_ctl) (void)hipHostFree(ba->h_ctl);
-      ba->d_ctl = ba->h_ctl = nullptr;
-      SVS_HIP(ctx, hipMalloc(&ba->d_ctl, sizeof(double) * n_ctl));
-      SVS_HIP(ctx, hipHostMalloc((void **)&ba->h_ctl, sizeof(double) * n_ctl, hipHostMallocDefault));
+      ba->d_ctl.reset(); ba->h_ctl.reset();
+      SVS_HIP(ctx, ba->d_ctl.alloc(n_ctl));
+      SVS_HIP(ctx, ba->h_ctl.alloc(n_ctl));
       ba->ctl_iters = n_it;
     }
-    while (ba->spec_ev.size() < 6 * (size_t)n_it) { hipEvent_t e; SVS_HIP(ctx, hipEventCreate(&e)); ba->spec_ev.push_back(e); }
+    while (ba->spec_ev.size() < 6 * (size_t)n_it) { owned::Event e; SVS_HIP(ctx, e.create()); ba->spec_ev.push_back(std::move(e)); }
     for (size_t i = 0; i < n_ctl; ++i) ba->h_ctl[i] = 0.0;
     ba->h_ctl[0] = lambda;
     auto enqueue_all = [&]() -> int {
@@ -1243,17 +1167,17 @@ static int optimize_begin(svs_ba *ba, svs_allreduce_fn allreduce, void *user, Op
     { BaDev B0 = make_dev(ba, lambda, ba->cur, ba->d_ctl); mix(&B0, sizeof B0); }
     const uint64_t cfg[] = {(uint64_t)ba->P, (uint64_t)ba->nw_sched, (uint64_t)ba->opt.nw, (uint64_t)ba->opt.nw4, (uint64_t)ba->use_fused_solve, (uint64_t)ba->use_lds_solve,
                             (uint64_t)ba->fuse_P1, (uint64_t)ba->fuse_lds_panel, (uint64_t)ba->lds_solve_smem, (uint64_t)ba->env_R, (uint64_t)ba->perm_active, (uint64_t)n_it,
-                            (uint64_t)smem, (uint64_t)ba->red_count, (uint64_t)(uintptr_t)ba->d_x, (uint64_t)(uintptr_t)ba->d_upanel, (uint64_t)(uintptr_t)ba->d_rowmax2,
-                            (uint64_t)(uintptr_t)ba->d_rowmax, (uint64_t)(uintptr_t)ba->d_linv, (uint64_t)(uintptr_t)ba->d_colmin, (uint64_t)(uintptr_t)ba->d_perm,
-                            (uint64_t)(uintptr_t)ba->d_perm_sys, (uint64_t)(uintptr_t)ba->d_xfer, (uint64_t)(uintptr_t)ba->d_flags, (uint64_t)(uintptr_t)ba->d_ctl,
-                            (uint64_t)(uintptr_t)ba->h_ctl, (uint64_t)(uintptr_t)ba->d_red, (uint64_t)(uintptr_t)ba->d_scal, (uint64_t)(uintptr_t)ctx->stream};
+                            (uint64_t)smem, (uint64_t)ba->red_count, (uint64_t)(uintptr_t)ba->d_x.get(), (uint64_t)(uintptr_t)ba->d_upanel.get(), (uint64_t)(uintptr_t)ba->d_rowmax2.get(),
+                            (uint64_t)(uintptr_t)ba->d_rowmax.get(), (uint64_t)(uintptr_t)ba->d_linv.get(), (uint64_t)(uintptr_t)ba->d_colmin.get(), (uint64_t)(uintptr_t)ba->d_perm.get(),
+                            (uint64_t)(uintptr_t)ba->d_perm_sys.get(), (uint64_t)(uintptr_t)ba->d_xfer.get(), (uint64_t)(uintptr_t)ba->d_flags.get(), (uint64_t)(uintptr_t)ba->d_ctl.get(),
+                            (uint64_t)(uintptr_t)ba->h_ctl.get(), (uint64_t)(uintptr_t)ba->d_red.get(), (uint64_t)(uintptr_t)ba->d_scal.get(), (uint64_t)(uintptr_t)ctx->stream};
     mix(cfg, sizeof cfg);
     svs_ba::Graph &G = ba->graph[ba->cur & 1];
     // a layout is recorded when it comes back: a sliding window whose observation count changes with every call (svs_ba_window_update) would otherwise pay a recording
     // (capture + instantiation, ~0.2 ms) per call and never replay it
     if ((!G.exec || G.sig != sig) && G.seen != sig) { G.seen = sig; return enqueue_all(); }
     if (!G.exec || G.sig != sig) {
-      if (G.exec) { (void)hipGraphExecDestroy(G.exec); G.exec = nullptr; }
+      G.exec.reset();
       hipGraph_t graph = nullptr;
       SVS_HIP(ctx, hipStreamBeginCapture(ctx->stream, hipStreamCaptureModeRelaxed));
       const int rc = enqueue_all();
@@ -1264,9 +1188,9 @@ static int optimize_begin(svs_ba *ba, svs_allreduce_fn allreduce, void *user, Op
         ba->opt.no_graph = 1;
         return rc ? rc : enqueue_all();
       }
-      const hipError_t e_inst = hipGraphInstantiate(&G.exec, graph, nullptr, nullptr, 0);
+      const hipError_t e_inst = G.exec.instantiate(graph);
       (void)hipGraphDestroy(graph);
-      if (e_inst != hipSuccess) { G.exec = nullptr; (void)hipGetLastError(); ba->opt.no_graph = 1; return enqueue_all(); }
+      if (e_inst != hipSuccess) { (void)hipGetLastError(); ba->opt.no_graph = 1; return enqueue_all(); }
       G.sig = sig;
       ++ba->n_graph_captures;
     }
@@ -1321,7 +1245,7 @@ static int optimize_finish(svs_ba *ba, OptRun &R, svs_ba_stats *stats) {
       if (skip) { skip = false; continue; }      // `continue` in a do-while jumps to the condition: the speculative phase ran this trial
       int rc = enqueue_trial(ba, lambda, -1, nullptr, ba->ev, smem, allreduce, user);
       if (rc) return rc;
-      if (!ba->h_scal) SVS_HIP(ctx, hipHostMalloc((void **)&ba->h_scal, sizeof(double) * SC_N, hipHostMallocDefault));
+      if (!ba->h_scal) SVS_HIP(ctx, ba->h_scal.alloc(SC_N));
       double *h = ba->h_scal;
       SVS_HIP(ctx, hipMemcpyAsync(h, ba->d_scal, sizeof(double) * SC_N, hipMemcpyDeviceToHost, ctx->stream));
       SVS_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -1408,13 +1332,7 @@ extern "C" int svs_ba_get_state(svs_ba *ba, double *h_poses, double *h_psi) {
   // both arrays land in a pinned area of the library's own, the two copies back to back, ONE wait; then a host copy into the caller's (pageable) arrays.  Straight
   // into pageable memory every copy is a synchronous, staged transfer of its own: 40 us of host turn-around between them in the drop-in call's timeline
   const size_t nb_poses = h_poses ? sizeof(double) * 12 * (size_t)ba->P : 0, nb_psi = (h_psi && ba->L) ? sizeof(double) * 3 * (size_t)ba->L : 0;
-  if (nb_poses + nb_psi > ba->h_state_cap) {
-    if (ba->h_state) (void)hipHostFree(ba->h_state);
-    ba->h_state = nullptr; ba->h_state_cap = 0;
-    const size_t want = (nb_poses + nb_psi) + (nb_poses + nb_psi) / 4 + 4096;
-    SVS_HIP(ctx, hipHostMalloc((void **)&ba->h_state, want, hipHostMallocDefault));
-    ba->h_state_cap = want;
-  }
+  if (nb_poses + nb_psi > ba->h_state.bytes()) SVS_HIP(ctx, ba->h_state.alloc_bytes((nb_poses + nb_psi) + (nb_poses + nb_psi) / 4 + 4096));
   if (nb_poses) SVS_HIP(ctx, hipMemcpyAsync(ba->h_state, ba->d_poses[ba->cur], nb_poses, hipMemcpyDeviceToHost, ctx->stream));
   if (nb_psi) SVS_HIP(ctx, hipMemcpyAsync(ba->h_state + nb_poses, ba->d_psi[ba->cur], nb_psi, hipMemcpyDeviceToHost, ctx->stream));
   SVS_HIP(ctx, hipStreamSynchronize(ctx->stream));

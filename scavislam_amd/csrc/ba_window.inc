@@ -269,13 +269,8 @@ extern "C" int svs_ba_window_forget_keyframes(svs_ba *ba, const int32_t *h_pose_
   size_t off = 0;
   auto take = [&](size_t bytes) { const size_t o = off; off = (off + bytes + 255) & ~(size_t)255; return o; };
   const size_t o_ids = take(sizeof(int) * ids.size()), o_tc = take(sizeof(int) * n_tiles), o_tot = take(sizeof(int)), o_out = take(sizeof(svs_ba_edge) * N);
-  if (off > ba->w_work_bytes || !ba->w_work) {
-    if (ba->w_work) (void)hipFree(ba->w_work);
-    ba->w_work = nullptr; ba->w_work_bytes = 0;
-    if (hipMalloc(&ba->w_work, off + off / 2) != hipSuccess) { ctx->err = "svs_ba_window_forget_keyframes: out of device memory"; return SVS_ERR_CAPACITY; }
-    ba->w_work_bytes = off + off / 2;
-  }
-  char *W = static_cast<char *>(ba->w_work);
+  if (ba->w_work.reserve(off, off + off / 2) != hipSuccess) { ctx->err = "svs_ba_window_forget_keyframes: out of device memory"; return SVS_ERR_CAPACITY; }
+  char *W = static_cast<char *>(ba->w_work.get());
   int *d_ids = (int *)(W + o_ids), *d_tc = (int *)(W + o_tc), *d_tot = (int *)(W + o_tot);
   svs_ba_edge *d_out = (svs_ba_edge *)(W + o_out);
   int num = 0;
@@ -323,16 +318,8 @@ static int window_update_impl(svs_ba *ba, int P, const int32_t *h_pose_ids, cons
   }
   SVS_HIP(ctx, hipStreamSynchronize(ctx->stream));
   ba->h_stage_used = 0;
-  auto grow = [&](void **ptr, size_t *cap, size_t bytes, bool keep, size_t keep_bytes) -> int {
-    if (bytes <= *cap && *ptr) return SVS_OK;
-    void *np = nullptr;
-    const size_t want = bytes + bytes / 2 + 4096;
-    SVS_HIP(ctx, hipMalloc(&np, want));
-    if (keep && *ptr && keep_bytes) SVS_HIP(ctx, hipMemcpy(np, *ptr, keep_bytes, hipMemcpyDeviceToDevice));
-    if (*ptr) (void)hipFree(*ptr);
-    *ptr = np; *cap = want;
-    return SVS_OK;
-  };
+  // the window's own blocks grow by half: a new block first (the old contents move over where they are still needed), then the old one goes
+  auto win_grow = [](auto &b, size_t bytes, size_t keep_bytes = 0) { return b.reserve_keep(bytes, bytes + bytes / 2 + 4096, keep_bytes); };
   // ---- ONE block for everything the call brings: pose ids | point ids | anchor ids | poses | points | new observations | constraints -----------------
   size_t ioff = 0;
   auto itake = [&](size_t bytes) { const size_t o = ioff; ioff = (ioff + bytes + 255) & ~(size_t)255; return o; };
@@ -340,9 +327,9 @@ static int window_update_impl(svs_ba *ba, int P, const int32_t *h_pose_ids, cons
                i_poses = itake(sizeof(double) * 12 * (size_t)P), i_psi = itake(sizeof(double) * 3 * (size_t)L), i_obs = itake(sizeof(svs_ba_edge) * (size_t)n_new),
                i_cons = itake(sizeof(svs_ba_constraint) * (size_t)C);
   { int rc = stage_reserve(ba, ioff + sizeof(int) * (((size_t)ba->w_n + n_new) / 8 + 8 * (size_t)P) + 16384); if (rc) return rc; }
-  { int rc = grow(&ba->w_in, &ba->w_in_bytes, ioff + 256, false, 0); if (rc) return rc; }
+  SVS_HIP(ctx, win_grow(ba->w_in, ioff + 256));
   {
-    char *hs = reinterpret_cast<char *>(ba->h_stage);
+    char *hs = reinterpret_cast<char *>(ba->h_stage.get());
     std::memcpy(hs + i_pids, h_pose_ids, sizeof(int) * (size_t)P);
     if (L) { std::memcpy(hs + i_lids, h_point_ids, sizeof(int) * (size_t)L); std::memcpy(hs + i_aids, h_anchor_pose_ids, sizeof(int) * (size_t)L); }
     std::memcpy(hs + i_poses, h_poses, sizeof(double) * 12 * (size_t)P);
@@ -351,7 +338,7 @@ static int window_update_impl(svs_ba *ba, int P, const int32_t *h_pose_ids, cons
     ba->h_stage_used = ioff;
     // everything but the observations leaves now (one copy: the observation slot lies between psi and the constraints and travels in pieces below)
     SVS_HIP(ctx, hipMemcpyAsync(ba->w_in, hs, i_obs, hipMemcpyHostToDevice, ctx->stream));
-    if (C) SVS_HIP(ctx, hipMemcpyAsync(static_cast<char *>(ba->w_in) + i_cons, hs + i_cons, ioff - i_cons, hipMemcpyHostToDevice, ctx->stream));
+    if (C) SVS_HIP(ctx, hipMemcpyAsync(static_cast<char *>(ba->w_in.get()) + i_cons, hs + i_cons, ioff - i_cons, hipMemcpyHostToDevice, ctx->stream));
     // the observation records: pieces of ~1 MB, each copied to the pinned block (and range-checked) by the worker pool and sent while the next one is being
     // copied -- one core moves ~10 GB/s, the link 50: a single memcpy of the 4 MB of a 50 KF / 20 k window was half of this call
     if (n_new) {
@@ -378,7 +365,7 @@ static int window_update_impl(svs_ba *ba, int P, const int32_t *h_pose_ids, cons
         };
         if (pool) pool->run(body); else body(0, 1);
         if (bad.load()) break;
-        SVS_HIP(ctx, hipMemcpyAsync(static_cast<char *>(ba->w_in) + i_obs + c0 * rec, hs + i_obs + c0 * rec, (c1 - c0) * rec, hipMemcpyHostToDevice, ctx->stream));
+        SVS_HIP(ctx, hipMemcpyAsync(static_cast<char *>(ba->w_in.get()) + i_obs + c0 * rec, hs + i_obs + c0 * rec, (c1 - c0) * rec, hipMemcpyHostToDevice, ctx->stream));
       }
       if (bad.load()) { (void)hipStreamSynchronize(ctx->stream); ba->h_stage_used = 0; ctx->err = "svs_ba_window_update: negative point / pose id in an observation"; return SVS_ERR_INVALID; }
       if (obs_checked) { max_point_id = std::max(max_point_id, L - 1); max_pose_id = std::max(max_pose_id, P - 1); }
@@ -388,24 +375,14 @@ static int window_update_impl(svs_ba *ba, int P, const int32_t *h_pose_ids, cons
   auto t_s = std::chrono::steady_clock::now();
   // ---- the store grows by the new observations (unpacked into its tail below) --------------------------------------------------------
   const size_t w_n_old = ba->w_n;
-  {
-    size_t cap_b = ba->w_cap * sizeof(svs_ba_edge);
-    int rc = grow((void **)&ba->w_store, &cap_b, (ba->w_n + (size_t)n_new) * sizeof(svs_ba_edge), true, ba->w_n * sizeof(svs_ba_edge));
-    if (rc) return rc;
-    ba->w_cap = cap_b / sizeof(svs_ba_edge);
-    ba->w_n += (size_t)n_new;
-  }
+  SVS_HIP(ctx, win_grow(ba->w_store, (ba->w_n + (size_t)n_new) * sizeof(svs_ba_edge), ba->w_n * sizeof(svs_ba_edge)));
+  ba->w_n += (size_t)n_new;
   const size_t N = ba->w_n;
   SVS_REQUIRE(ctx, N < (size_t)INT_MAX - 1);
   // ---- id tables ---------------------------------------------------------------------------------------------------------------
-  {
-    size_t cb = ba->w_pose_tab_n * sizeof(int);
-    int rc = grow((void **)&ba->w_pose_tab, &cb, ((size_t)max_pose_id + 1) * sizeof(int), false, 0); if (rc) return rc;
-    ba->w_pose_tab_n = cb / sizeof(int);
-    cb = ba->w_point_tab_n * sizeof(int);
-    rc = grow((void **)&ba->w_point_tab, &cb, ((size_t)max_point_id + 2) * sizeof(int), false, 0); if (rc) return rc;
-    ba->w_point_tab_n = cb / sizeof(int);
-  }
+  SVS_HIP(ctx, win_grow(ba->w_pose_tab, ((size_t)max_pose_id + 1) * sizeof(int)));
+  SVS_HIP(ctx, win_grow(ba->w_point_tab, ((size_t)max_point_id + 2) * sizeof(int)));
+  const size_t pose_tab_n = ba->w_pose_tab.bytes() / sizeof(int), point_tab_n = ba->w_point_tab.bytes() / sizeof(int);
   // ---- work arrays (one allocation): anchor_idx | [count | masks | pattern | counters: zeroed together] | landmark lengths ([pattern .. lengths]: read back
   //      together) | edge offsets | (tile, bucket) table | lm_start
   const size_t capE = N + 1;
@@ -415,38 +392,29 @@ static int window_update_impl(svs_ba *ba, int P, const int32_t *h_pose_ids, cons
   const size_t o_aidx = take(sizeof(int) * (size_t)std::max(L, 1)), o_count = take(sizeof(int) * (size_t)std::max(L, 1)), o_mask = take(32 * (size_t)std::max(L, 1)),
                o_pat = take((size_t)P * P), o_ctr = take(sizeof(WinCounters)), o_lml = take(4 * ((size_t)L + 2)),
                o_eoff = take(sizeof(int) * (size_t)std::max(L, 1)), o_tile = take(sizeof(int) * 2 * n_tiles * 2 * (size_t)P), o_lms = take(4 * ((size_t)L + 2));
-  { int rc = grow(&ba->w_work, &ba->w_work_bytes, off, false, 0); if (rc) return rc; }
-  char *W = static_cast<char *>(ba->w_work);
-  char *IN = static_cast<char *>(ba->w_in);
+  SVS_HIP(ctx, win_grow(ba->w_work, off));
+  char *W = static_cast<char *>(ba->w_work.get());
+  char *IN = static_cast<char *>(ba->w_in.get());
   int *d_aidx = (int *)(W + o_aidx), *d_count = (int *)(W + o_count);
   unsigned long long *d_mask = (unsigned long long *)(W + o_mask);
   int *d_eoff = (int *)(W + o_eoff), *d_tile = (int *)(W + o_tile), *d_lms = (int *)(W + o_lms), *d_lml = (int *)(W + o_lml);
   unsigned char *d_pat = (unsigned char *)(W + o_pat);
   WinCounters *d_ctr = (WinCounters *)(W + o_ctr);
   // device buffers of the optimizer proper (grow-only, as in svs_ba_set_problem)
-  auto ensure = [&](void **ptr, size_t *cap, size_t bytes) -> hipError_t {
-    if (bytes <= *cap && *ptr) return hipSuccess;
-    if (*ptr) (void)hipFree(*ptr);
-    *ptr = nullptr; *cap = 0;
-    const size_t want = bytes + bytes / 4 + 256;
-    hipError_t e = hipMalloc(ptr, want);
-    if (e == hipSuccess) *cap = want;
-    return e;
-  };
-  SVS_HIP(ctx, ensure((void **)&ba->d_edges, &ba->cap_edges, sizeof(svs_ba_edge) * capE));
+  SVS_HIP(ctx, ba_grow(ba->d_edges, sizeof(svs_ba_edge) * capE));
   for (int k = 0; k < 2; ++k) {
-    SVS_HIP(ctx, ensure((void **)&ba->d_poses[k], &ba->cap_poses[k], sizeof(double) * 12 * (size_t)P));
-    SVS_HIP(ctx, ensure((void **)&ba->d_psi[k], &ba->cap_psi[k], sizeof(double) * 3 * (size_t)std::max(L, 1)));
+    SVS_HIP(ctx, ba_grow(ba->d_poses[k], sizeof(double) * 12 * (size_t)P));
+    SVS_HIP(ctx, ba_grow(ba->d_psi[k], sizeof(double) * 3 * (size_t)std::max(L, 1)));
   }
-  SVS_HIP(ctx, ensure((void **)&ba->d_cons, &ba->cap_cons, sizeof(svs_ba_constraint) * (size_t)std::max(C, 1)));
-  SVS_HIP(ctx, ensure((void **)&ba->d_x, &ba->cap_x, sizeof(double) * 6 * (size_t)P));
+  SVS_HIP(ctx, ba_grow(ba->d_cons, sizeof(svs_ba_constraint) * (size_t)std::max(C, 1)));
+  SVS_HIP(ctx, ba_grow(ba->d_x, sizeof(double) * 6 * (size_t)P));
   // ---- enqueue: one upload, three clears, seven kernels, one read-back ----------------------------------------------------------------------
   const int TB = 256;
   int rc = SVS_OK;
   {   // one launch instead of three memsets: both id tables to -1; count, masks, pattern, counters to 0
-    const size_t nz = ((o_ctr - o_count) + sizeof(WinCounters) + 3) / 4, n_all = std::max({ba->w_pose_tab_n, ba->w_point_tab_n, nz});
+    const size_t nz = ((o_ctr - o_count) + sizeof(WinCounters) + 3) / 4, n_all = std::max({pose_tab_n, point_tab_n, nz});
     hipLaunchKernelGGL(win_clear_kernel, dim3((unsigned)std::min<size_t>((n_all + 4 * TB - 1) / (4 * TB), 2048)), dim3(TB), 0, ctx->stream, ba->w_pose_tab,
-                       ba->w_pose_tab_n, ba->w_point_tab, ba->w_point_tab_n, reinterpret_cast<int *>(W + o_count), nz);
+                       pose_tab_n, ba->w_point_tab, point_tab_n, reinterpret_cast<int *>(W + o_count), nz);
   }
   {
     WinIn A;
@@ -454,7 +422,7 @@ static int window_update_impl(svs_ba *ba, int P, const int32_t *h_pose_ids, cons
     A.obs = (const double *)(IN + i_obs); A.cons = (const double *)(IN + i_cons);
     A.P = P; A.L = L; A.obs_words = (size_t)n_new * (sizeof(svs_ba_edge) / 8); A.cons_words = (size_t)C * (sizeof(svs_ba_constraint) / 8);
     A.poses0 = ba->d_poses[0]; A.poses1 = ba->d_poses[1]; A.psi0 = ba->d_psi[0]; A.psi1 = ba->d_psi[1];
-    A.store_tail = reinterpret_cast<double *>(ba->w_store + w_n_old); A.d_cons = reinterpret_cast<double *>(ba->d_cons); A.d_x = ba->d_x;
+    A.store_tail = reinterpret_cast<double *>(ba->w_store + w_n_old); A.d_cons = reinterpret_cast<double *>(ba->d_cons.get()); A.d_x = ba->d_x;
     A.pose_tab = ba->w_pose_tab; A.point_tab = ba->w_point_tab;
     const size_t n_max = std::max<size_t>({12 * (size_t)P, 3 * (size_t)L, A.obs_words, A.cons_words, (size_t)1});
     hipLaunchKernelGGL(win_unpack_kernel, dim3((unsigned)((n_max + TB - 1) / TB)), dim3(TB), 0, ctx->stream, A);
@@ -465,7 +433,7 @@ static int window_update_impl(svs_ba *ba, int P, const int32_t *h_pose_ids, cons
   stage("tables");
   if (N && L) {
     const unsigned gN = (unsigned)((N + TB - 1) / TB);
-    hipLaunchKernelGGL(win_mark_kernel, dim3(gN), dim3(TB), 0, ctx->stream, ba->w_store, N, ba->w_pose_tab, ba->w_pose_tab_n, ba->w_point_tab, ba->w_point_tab_n, d_aidx,
+    hipLaunchKernelGGL(win_mark_kernel, dim3(gN), dim3(TB), 0, ctx->stream, ba->w_store, N, ba->w_pose_tab, pose_tab_n, ba->w_point_tab, point_tab_n, d_aidx,
                        d_count, d_mask, d_ctr);
     stage("mark");
     hipLaunchKernelGGL(win_tile_hist_kernel, dim3((unsigned)n_tiles), dim3(256), 0, ctx->stream, d_count, d_aidx, L, P, d_tile);
@@ -473,7 +441,7 @@ static int window_update_impl(svs_ba *ba, int P, const int32_t *h_pose_ids, cons
     stage("landmark order");
     hipLaunchKernelGGL(win_tile_rank_kernel, dim3((unsigned)n_tiles), dim3(WIN_TILE), 0, ctx->stream, d_count, d_aidx, d_mask, L, P, d_tile, d_ctr, d_eoff, d_lms, d_lml, d_pat);
     stage("rank");
-    hipLaunchKernelGGL(win_place_kernel, dim3(gN), dim3(TB), 0, ctx->stream, ba->w_store, N, ba->w_pose_tab, ba->w_pose_tab_n, ba->w_point_tab, ba->w_point_tab_n, d_aidx,
+    hipLaunchKernelGGL(win_place_kernel, dim3(gN), dim3(TB), 0, ctx->stream, ba->w_store, N, ba->w_pose_tab, pose_tab_n, ba->w_point_tab, point_tab_n, d_aidx,
                        d_eoff, d_mask, ba->d_edges);
     SVS_LAUNCH_CHECK(ctx);
     stage("place");
@@ -481,12 +449,7 @@ static int window_update_impl(svs_ba *ba, int P, const int32_t *h_pose_ids, cons
   }
   // ---- one read-back: pattern | counters | landmark lengths (contiguous in the work arrays) ------------------------------------------------
   const size_t back_bytes = (o_lml - o_pat) + 4 * ((size_t)L + 2);
-  if (back_bytes > ba->w_hback_bytes) {
-    if (ba->w_hback) (void)hipHostFree(ba->w_hback);
-    ba->w_hback = nullptr; ba->w_hback_bytes = 0;
-    SVS_HIP(ctx, hipHostMalloc((void **)&ba->w_hback, back_bytes + back_bytes / 2, hipHostMallocDefault));
-    ba->w_hback_bytes = back_bytes + back_bytes / 2;
-  }
+  if (back_bytes > ba->w_hback.bytes()) SVS_HIP(ctx, ba->w_hback.alloc_bytes(back_bytes + back_bytes / 2));
   unsigned char *h_pat = ba->w_hback;
   WinCounters *h_ctr = reinterpret_cast<WinCounters *>(ba->w_hback + (o_ctr - o_pat));
   int *h_lml = reinterpret_cast<int *>(ba->w_hback + (o_lml - o_pat));
@@ -526,14 +489,14 @@ static int window_update_impl(svs_ba *ba, int P, const int32_t *h_pose_ids, cons
   ba->profile_ready = false; ba->env_R = 0; ba->use_lds_solve = ba->use_fused_solve = false;
   const size_t nblk = (size_t)P * (P + 1) / 2;
   ba->red_count = nblk * 36 + 12 * (size_t)P + SC_SLOTS;
-  SVS_HIP(ctx, ensure((void **)&ba->d_chunk_start, &ba->cap_cs, sizeof(int) * (size_t)std::max(ba->n_chunks + ba->n_wide, 1)));
-  SVS_HIP(ctx, ensure((void **)&ba->d_chunk_len, &ba->cap_cl, sizeof(int) * (size_t)std::max(ba->n_chunks + ba->n_wide, 1)));
-  SVS_HIP(ctx, ensure((void **)&ba->d_red, &ba->cap_red, sizeof(double) * ba->red_count));
-  SVS_HIP(ctx, ensure((void **)&ba->d_scal, &ba->cap_scal, sizeof(double) * SC_N));
-  SVS_HIP(ctx, ensure((void **)&ba->d_linv, &ba->cap_linv, sizeof(double) * 36 * (size_t)P));
-  SVS_HIP(ctx, ensure((void **)&ba->d_rowmax, &ba->cap_rowmax, sizeof(int) * (size_t)P));
-  SVS_HIP(ctx, ensure((void **)&ba->d_colmin, &ba->cap_colmin, sizeof(int) * (size_t)P));
-  SVS_HIP(ctx, ensure((void **)&ba->d_pattern, &ba->cap_pattern, sizeof(double) * (size_t)P * P));
+  SVS_HIP(ctx, ba_grow(ba->d_chunk_start, sizeof(int) * (size_t)std::max(ba->n_chunks + ba->n_wide, 1)));
+  SVS_HIP(ctx, ba_grow(ba->d_chunk_len, sizeof(int) * (size_t)std::max(ba->n_chunks + ba->n_wide, 1)));
+  SVS_HIP(ctx, ba_grow(ba->d_red, sizeof(double) * ba->red_count));
+  SVS_HIP(ctx, ba_grow(ba->d_scal, sizeof(double) * SC_N));
+  SVS_HIP(ctx, ba_grow(ba->d_linv, sizeof(double) * 36 * (size_t)P));
+  SVS_HIP(ctx, ba_grow(ba->d_rowmax, sizeof(int) * (size_t)P));
+  SVS_HIP(ctx, ba_grow(ba->d_colmin, sizeof(int) * (size_t)P));
+  SVS_HIP(ctx, ba_grow(ba->d_pattern, sizeof(double) * (size_t)P * P));
   if (!cs.empty()) {
     if ((rc = stage_upload(ba, ba->d_chunk_start, cs.data(), sizeof(int) * cs.size()))) return rc;
     if ((rc = stage_upload(ba, ba->d_chunk_len, cl.data(), sizeof(int) * cl.size()))) return rc;

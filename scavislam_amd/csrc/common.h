@@ -4,24 +4,24 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
+#include <memory>
 #include <string>
 
 #include "../../include/scavislam_hip.h"
+#include "owned.h"
 
 struct svs_ctx {
   int device = 0;
   int n_cu = 256;                 // compute units of the device (MI355X: 256)
-  hipStream_t stream = nullptr;
-  bool own_stream = false;
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
+  hipStream_t stream = nullptr;   // the stream in use: the caller's, or own_stream (the front end points it at its side stream for a stretch)
+  owned::Stream own_stream;       // empty when the caller brought the stream
+  owned::Event ev0, ev1;
   std::string err;
   // device scratch owned by the context (block partials, cross-workgroup hand-off words): grown on demand, freed with the ctx
-  void *scratch = nullptr;
-  size_t scratch_bytes = 0;
+  DevBuf<void> scratch;
   // the matcher's per-call tables (relative poses per (stream, keyframe), predictions per point): its own buffer, because the trackers'
   // scratch above carries hand-off words across the launches of one call chain
-  void *match_scratch = nullptr;
-  size_t match_scratch_bytes = 0;
+  DevBuf<void> match_scratch;
   // switches read ONCE at svs_ctx_create (debug / experiment only; never per call)
   int trk_nwg = 0;            // SVS_TRK_NWG: workgroups per stream of the latency-mode quarter-grid tracker (0 = automatic)
   int trk_balance = 1;        // big batches (dense.hip, BAL): 1 = grid order by the last frame's LM work, 2 = also 2..4 workgroups for the longest streams (experimental), 0 = stream order
@@ -46,10 +46,10 @@ struct svs_ctx {
   // set by the one-call front end around svs_match (few keyframes): the tracked pose / the active keyframe's pose per stream, from which the matcher's prediction kernel forms
   // T_cur_from_w / T_w_from_actkey and the per-keyframe relative poses itself (match.hip) -- two small launches less between tracker and matcher
   const double *match_src_T = nullptr, *match_src_Ta = nullptr;
-  void *seq_buf = nullptr; size_t seq_buf_bytes = 0;      // the per-pass term buffers of both modes
-  void *seq_stats = nullptr;                              // device: [0] exact float sums formed, [1] of those by the fallback chain (svs_ctx_get_stat)
-  hipEvent_t spin_ev = nullptr;      // "a device-filling kernel of mine has finished" (svs_spin_enter / svs_spin_leave)
-  hipEvent_t lane_ev = nullptr;      // the same behind my latest priority-lane launch
+  DevBuf<void> seq_buf;                                   // the per-pass term buffers of both modes
+  DevBuf<unsigned> seq_stats;                             // device: [0] exact float sums formed, [1] of those by the fallback chain (svs_ctx_get_stat)
+  owned::Event spin_ev;              // "a device-filling kernel of mine has finished" (svs_spin_enter / svs_spin_leave)
+  owned::Event lane_ev;              // the same behind my latest priority-lane launch
   bool spin_lane = false;            // the launch between the last svs_spin_enter and its svs_spin_leave took the priority lane
   int spin_demand = 0;               // compute units that launch may hold (one per workgroup)
   long long spin_n_lane = 0, spin_n_gated = 0;      // svs_ctx_get_stat "spin_lane_launches" / "spin_gated_launches"
@@ -78,8 +78,9 @@ struct SvsSpinScope {
   SvsSpinScope &operator=(const SvsSpinScope &) = delete;
 };
 // returns ctx-owned device scratch of at least `bytes` (contents undefined); may synchronise the stream when it has to grow
-int svs_ctx_scratch(svs_ctx *ctx, size_t bytes, void **out);
-int svs_ctx_match_scratch(svs_ctx *ctx, size_t bytes, void **out);
+int svs_ctx_grow(svs_ctx *ctx, DevBuf<void> svs_ctx::*which, size_t bytes, void **out);
+inline int svs_ctx_scratch(svs_ctx *ctx, size_t bytes, void **out) { return svs_ctx_grow(ctx, &svs_ctx::scratch, bytes, out); }
+inline int svs_ctx_match_scratch(svs_ctx *ctx, size_t bytes, void **out) { return svs_ctx_grow(ctx, &svs_ctx::match_scratch, bytes, out); }
 // svs_dense_track_cpu_sem with the state of the balanced launch of big batches (dense.hip: per-stream LM work of the last frame -> workgroups per stream);
 // d_bal_state: svs_dense_track_balance_bytes(batch) bytes of device memory, initialised once by svs_dense_track_balance_init; may be NULL
 size_t svs_dense_track_balance_bytes(int batch);

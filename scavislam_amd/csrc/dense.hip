@@ -1528,19 +1528,18 @@ int svs_dense_track_cpu_sem_work(svs_ctx *ctx, const svs_dense_track_args *a, do
     t_b = (size_t)(a->cam_vec[0].w / 4) * (a->cam_vec[0].h / 4);
     if (lazy) t_b = ((t_b + 3) & ~(size_t)3) + 64;      // 16-byte aligned buffers, padded by more than the longest run a lane reads in one go (SEQ_RUN_MAX)
     const size_t want = (size_t)batch * t_b * sizeof(float) * (lazy ? 2 : 1) + 256;
-    if (ctx->seq_buf_bytes < want) {
-      if (ctx->seq_buf) { SVS_HIP(ctx, hipStreamSynchronize(ctx->stream)); (void)hipFree(ctx->seq_buf); ctx->seq_buf = nullptr; ctx->seq_buf_bytes = 0; }
-      SVS_HIP(ctx, hipMalloc(&ctx->seq_buf, want));
-      ctx->seq_buf_bytes = want;
+    if (ctx->seq_buf.bytes() < want) {
+      if (ctx->seq_buf) SVS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+      SVS_HIP(ctx, ctx->seq_buf.reserve(want, want));
     }
-    if (seq_all) t_buf = static_cast<float *>(ctx->seq_buf); else terms = static_cast<float *>(ctx->seq_buf);
+    if (seq_all) t_buf = static_cast<float *>(ctx->seq_buf.get()); else terms = static_cast<float *>(ctx->seq_buf.get());
     if (!ctx->seq_stats) {
-      SVS_HIP(ctx, hipMalloc(&ctx->seq_stats, 256));
+      SVS_HIP(ctx, ctx->seq_stats.alloc_bytes(256));
       SVS_HIP(ctx, hipMemsetAsync(ctx->seq_stats, 0, 256, ctx->stream));
     }
   }
   TrackMulti G{};
-  G.terms = terms; G.terms_b = t_b; G.seq_stats = static_cast<unsigned *>(ctx->seq_stats); G.terms_only = ctx->trk_lazy_chi2 == 2;
+  G.terms = terms; G.terms_b = t_b; G.seq_stats = ctx->seq_stats; G.terms_only = ctx->trk_lazy_chi2 == 2;
   if (t_buf) {
     G.part = reinterpret_cast<double *>(t_buf); G.fail_off = (int)t_b;
     TRK_LAUNCH(u8src, dense_track_cpu_sem_kernel, (false, 2, true), dim3(batch), A, d_T_io, d_passes_out, G);

@@ -375,9 +375,15 @@ __global__ __launch_bounds__(NT) void fast_compact_bitmap_kernel(FastParams P) {
 
 struct svs_fast {
   svs_ctx *ctx;
-  FastParams P;
+  FastParams P;               // what the kernels take: raw views of the buffers below
   int batch;
   TileDesc *d_tiles; int n_tiles;
+  DevBuf<uint32_t> bm[SVS_NUM_PYR_LEVELS], cand;
+  DevBuf<int16_t> xy[SVS_NUM_PYR_LEVELS];
+  DevBuf<unsigned> hist;
+  DevBuf<int> thr, emit, count, offset, level_total, cand_n, cell_tile0, cell_ntile;
+  DevBuf<TileDesc> tiles;
+  ~svs_fast() { (void)hipStreamSynchronize(ctx->stream); }      // (runs before the buffers are freed, also when create gives up behind its clears and uploads)
   size_t cmp_lds = 0;         // dynamic LDS of the compaction: bitmap + row offsets of the largest cell
 };
 
@@ -397,7 +403,7 @@ extern "C" int svs_fast_create(svs_ctx *ctx, int n_levels, const int32_t *w, con
     }
     SVS_REQUIRE(ctx, (size_t)nc * 256 * 4 <= 64 * 1024);          // the adaptation kernel's suffix-summed histograms of one stream in LDS
   }
-  svs_fast *f = new svs_fast();
+  std::unique_ptr<svs_fast> f(new svs_fast());
   f->ctx = ctx; f->batch = batch;
   FastParams &P = f->P;
   P = FastParams{};
@@ -407,8 +413,6 @@ extern "C" int svs_fast_create(svs_ctx *ctx, int n_levels, const int32_t *w, con
   int cell_base = 0, t_lo = 255;
   for (int l = 0; l < n_levels; ++l) {
     const svs_fastgrid &g = grids[l];
-    SVS_REQUIRE(ctx, g.gx >= 1 && g.gy >= 1 && g.gx * g.gy <= SVS_MAX_CELLS && g.cell_w * g.gx <= w[l] && g.cell_h * g.gy <= h[l]);
-    SVS_REQUIRE(ctx, g.cell_w <= 4096 && g.cell_h <= 4096);      // 12-bit cell-local coordinates in the candidate records
     LevelDev &L = P.lv[l];
     L.w = w[l]; L.h = h[l]; L.gx = g.gx; L.gy = g.gy; L.cell_w = g.cell_w; L.cell_h = g.cell_h;
     L.min_inner = g.min_inner; L.min_outer = g.min_outer; L.max_inner = g.max_inner; L.max_outer = g.max_outer;
@@ -420,10 +424,10 @@ extern "C" int svs_fast_create(svs_ctx *ctx, int n_levels, const int32_t *w, con
     L.bm_stride = ((std::max(w[l], g.gx * g.cell_w) + gap * (g.gx - 1) + 7) / 8 + 8 + 15) / 16 * 16;
     SVS_REQUIRE(ctx, L.bm_stride >= 4 * L.bm_wpr * g.gx);
     L.bm_bstride = (size_t)L.bm_stride * h[l] + 16;
-    SVS_HIP(ctx, hipMalloc(&L.bm, L.bm_bstride * batch));
+    SVS_HIP(ctx, f->bm[l].alloc_bytes(L.bm_bstride * batch, &L.bm));
     SVS_HIP(ctx, hipMemsetAsync(L.bm, 0, L.bm_bstride * batch, ctx->stream));
     f->cmp_lds = std::max(f->cmp_lds, ((size_t)g.cell_h * L.bm_wpr + g.cell_h) * 4);
-    SVS_HIP(ctx, hipMalloc(&L.xy, sizeof(int16_t) * 2 * (size_t)cap * batch));
+    SVS_HIP(ctx, f->xy[l].alloc(2 * (size_t)cap * batch, &L.xy));
     for (int c = 0; c < g.gx * g.gy; ++c) {
       t_lo = std::min(t_lo, std::min(g.fast_min, g.thr[c]));
       cell_tile0.push_back((int)tiles.size());
@@ -435,20 +439,18 @@ extern "C" int svs_fast_create(svs_ctx *ctx, int n_levels, const int32_t *w, con
   }
   P.ncell_total = cell_base;
   P.t_lo = std::max(t_lo, 0);
-  SVS_REQUIRE(ctx, (size_t)P.ncell_total * 256 * 4 <= 64 * 1024);
-  SVS_REQUIRE(ctx, f->cmp_lds <= (size_t)BM_LDS_MAX);      // a cell's bitmap lives in LDS during the compaction: cells up to ~1.1 M pixels (e.g. 1184 x 1024)
   if (f->cmp_lds > 64 * 1024) {
     SVS_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(&fast_compact_bitmap_kernel<256>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)f->cmp_lds));
     SVS_HIP(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(&fast_compact_bitmap_kernel<1024>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)f->cmp_lds));
   }
   size_t nc = (size_t)P.ncell_total * batch;
-  SVS_HIP(ctx, hipMalloc(&P.hist, nc * 256 * sizeof(unsigned)));
+  SVS_HIP(ctx, f->hist.alloc(nc * 256, &P.hist));
   SVS_HIP(ctx, hipMemsetAsync(P.hist, 0, nc * 256 * sizeof(unsigned), ctx->stream));
-  SVS_HIP(ctx, hipMalloc(&P.thr, nc * sizeof(int)));
-  SVS_HIP(ctx, hipMalloc(&P.emit, nc * sizeof(int)));
-  SVS_HIP(ctx, hipMalloc(&P.count, nc * sizeof(int)));
-  SVS_HIP(ctx, hipMalloc(&P.offset, nc * sizeof(int)));
-  SVS_HIP(ctx, hipMalloc(&P.level_total, (size_t)batch * n_levels * sizeof(int)));
+  SVS_HIP(ctx, f->thr.alloc(nc, &P.thr));
+  SVS_HIP(ctx, f->emit.alloc(nc, &P.emit));
+  SVS_HIP(ctx, f->count.alloc(nc, &P.count));
+  SVS_HIP(ctx, f->offset.alloc(nc, &P.offset));
+  SVS_HIP(ctx, f->level_total.alloc((size_t)batch * n_levels, &P.level_total));
   SVS_HIP(ctx, hipMemsetAsync(P.emit, 0, nc * sizeof(int), ctx->stream));
   SVS_HIP(ctx, hipMemsetAsync(P.count, 0, nc * sizeof(int), ctx->stream));
   SVS_HIP(ctx, hipMemsetAsync(P.offset, 0, nc * sizeof(int), ctx->stream));
@@ -460,26 +462,21 @@ extern "C" int svs_fast_create(svs_ctx *ctx, int n_levels, const int32_t *w, con
   SVS_HIP(ctx, hipMemcpyAsync(P.thr, thr0.data(), nc * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
   f->n_tiles = (int)tiles.size();
   P.n_tiles = f->n_tiles;
-  SVS_HIP(ctx, hipMalloc(&P.cand, sizeof(uint32_t) * (size_t)batch * tiles.size() * CAND_CAP));
-  SVS_HIP(ctx, hipMalloc(&P.cand_n, sizeof(int) * (size_t)batch * tiles.size()));
-  SVS_HIP(ctx, hipMalloc(&P.cell_tile0, sizeof(int) * cell_tile0.size()));
-  SVS_HIP(ctx, hipMalloc(&P.cell_ntile, sizeof(int) * cell_ntile.size()));
+  SVS_HIP(ctx, f->cand.alloc((size_t)batch * tiles.size() * CAND_CAP, &P.cand));
+  SVS_HIP(ctx, f->cand_n.alloc((size_t)batch * tiles.size(), &P.cand_n));
+  SVS_HIP(ctx, f->cell_tile0.alloc(cell_tile0.size(), &P.cell_tile0));
+  SVS_HIP(ctx, f->cell_ntile.alloc(cell_ntile.size(), &P.cell_ntile));
   SVS_HIP(ctx, hipMemcpyAsync(P.cell_tile0, cell_tile0.data(), sizeof(int) * cell_tile0.size(), hipMemcpyHostToDevice, ctx->stream));
   SVS_HIP(ctx, hipMemcpyAsync(P.cell_ntile, cell_ntile.data(), sizeof(int) * cell_ntile.size(), hipMemcpyHostToDevice, ctx->stream));
-  SVS_HIP(ctx, hipMalloc(&f->d_tiles, sizeof(TileDesc) * tiles.size()));
+  SVS_HIP(ctx, f->tiles.alloc(tiles.size(), &f->d_tiles));
   SVS_HIP(ctx, hipMemcpyAsync(f->d_tiles, tiles.data(), sizeof(TileDesc) * tiles.size(), hipMemcpyHostToDevice, ctx->stream));
   SVS_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  *out = f;
+  *out = f.release();
   return SVS_OK;
 }
 
 extern "C" int svs_fast_destroy(svs_fast *f) {
   if (!f) return SVS_OK;
-  (void)hipStreamSynchronize(f->ctx->stream);
-  for (int l = 0; l < f->P.n_levels; ++l) { hipFree(f->P.lv[l].bm); hipFree(f->P.lv[l].xy); }
-  hipFree(f->P.hist); hipFree(f->P.thr); hipFree(f->P.emit); hipFree(f->P.count); hipFree(f->P.offset);
-  hipFree(f->P.level_total); hipFree(f->d_tiles);
-  hipFree(f->P.cand); hipFree(f->P.cand_n); hipFree(f->P.cell_tile0); hipFree(f->P.cell_ntile);
   delete f;
   return SVS_OK;
 }

@@ -94,6 +94,8 @@ __global__ __launch_bounds__(256) void copy_rows_kernel(const uint8_t *__restric
   d[x] = s[x];
 }
 inline int round_up(int a, int b) { return (a + b - 1) / b * b; }
+struct Views3 { float *p[3]; operator float *const *() const { return p; } };      // the three levels of an owner array as the pointer array the stage calls take
+inline Views3 views(const DevBuf<float> (&b)[3]) { return {{b[0], b[1], b[2]}}; }
 }  // namespace
 
 struct svs_frontend {
@@ -108,26 +110,29 @@ struct svs_frontend {
   bool have_prev = false;
   // device: three pyramid slots per stream (previous / current / next: the next frame may be uploaded while the current one is
   // processed) with their right images / disparities, reference clouds
-  uint8_t *d_pyr[3][3] = {};
+  DevBuf<uint8_t> d_pyr[3][3];
   int i_prev = 2, i_cur = 0, i_next = 1;
-  uint8_t *d_right[3] = {};            // right image / disparity of the frame in pyramid slot k
-  float *d_disp[3] = {};
+  DevBuf<uint8_t> d_right[3];          // right image / disparity of the frame in pyramid slot k
+  DevBuf<float> d_disp[3];
   const float *last_disp = nullptr; int last_dstride = 0; size_t last_dbstride = 0;      // disparity the frame processed last was given / produced
   const uint8_t *ext_left = nullptr; int ext_lstride = 0; size_t ext_lbstride = 0;       // a caller's device frame waiting to be taken in by the first pyramid step
-  float *d_cloud[3] = {};               // quarter grid (CPU build) or full resolution (CUDA build), float4 per sample
+  DevBuf<float> d_cloud[3];             // quarter grid (CPU build) or full resolution (CUDA build), float4 per sample
   size_t cloud_elems[3]{};              // floats per stream and level
   // CUDA build (prm.cuda_build): f32 pyramids of the current / previous frame, derivative images of the current one
-  float *d_f32[2][3] = {}, *d_dx[3] = {}, *d_dy[3] = {};
+  DevBuf<float> d_f32[2][3], d_dx[3], d_dy[3];
   int i_f32 = 0;
-  uint8_t *d_kf_pyr = nullptr;          // [B][max_keyframes] x 3 levels, packed
+  DevBuf<uint8_t> d_kf_pyr;             // [B][max_keyframes] x 3 levels, packed
   size_t kf_level_off[3] = {}, kf_bytes = 0;
-  svs_keyframe *d_kfs = nullptr;        // [B][max_keyframes]
+  DevBuf<svs_keyframe> d_kfs;           // [B][max_keyframes]
   std::vector<svs_keyframe> h_kfs;
-  svs_candidate_point *d_pts = nullptr; // [B][max_points]
-  svs_candidate_point *h_cand_stage = nullptr;      // pinned, [B][max_points]: svs_frontend_set_candidates_all's staging block (allocated on first use)
+  DevBuf<svs_candidate_point> d_pts;    // [B][max_points]
+  PinnedBuf<svs_candidate_point> h_cand_stage;      // pinned, [B][max_points]: svs_frontend_set_candidates_all's staging block (allocated on first use)
+  // the frame's results: views, backed by d_out_block (one stream: d_small | d_res | d_gated carved from ONE allocation in h_out's layout -- the results go home
+  // in one copy) or by the three blocks beside it (several streams)
   svs_match_result *d_res = nullptr;
   svs_gated_point *d_gated = nullptr;
-  int32_t *d_group_end = nullptr, *d_n_groups = nullptr, *d_n_new = nullptr;      // [B][MAX_GROUPS], [B], [B]: records of the new-feature lists
+  DevBuf<uint8_t> d_out_block; DevBuf<svs_match_result> res_block; DevBuf<svs_gated_point> gated_block; DevBuf<double> small_block;
+  DevBuf<int32_t> d_group_end, d_n_groups, d_n_new;      // [B][MAX_GROUPS], [B], [B]: records of the new-feature lists
   // small device block: T [B][12] | T_actkey_from_w [B][12] | T_cur_from_w [B][12] | T_w_from_actkey [B][12] | pose stats [B] | point stats [B] | passes [B]
   double *d_small = nullptr;
   size_t small_bytes = 0;
@@ -136,32 +141,39 @@ struct svs_frontend {
   int32_t *d_passes = nullptr;
   svs_fast *fast = nullptr;
   // cross-frame pipeline (ctx option "fe_pipeline"): the pyramid of frame N+1 is built on the side stream while frame N's pose refinement / gate / cloud run
-  hipEvent_t ev_early[2] = {}, ev_late[2] = {};      // by frame parity: pyramid done (side stream) / the whole frame done (context's stream)
-  hipEvent_t ev_trk[2] = {};                         // ... / the point of the context's stream right in front of the pose refinement's launch
+  owned::Event ev_early[2], ev_late[2];              // by frame parity: pyramid done (side stream) / the whole frame done (context's stream)
+  owned::Event ev_trk[2];                            // ... / the point of the context's stream right in front of the pose refinement's launch
   unsigned pipe_run = 0;                             // frames issued through the pipelined path since the last frame that was not
   svs_stereo *stereo = nullptr;
   // pinned host staging: two input sets (images of stream 0, poses of all streams), one output set
-  uint8_t *h_in[2] = {}; size_t h_in_bytes = 0; int i_stage = 0;
-  uint8_t *h_out = nullptr; size_t h_out_bytes = 0;
-  uint8_t *d_out_block = nullptr;      // one stream: d_small | d_res | d_gated carved from ONE allocation in h_out's layout -- the frame's results go home in one copy
-  hipStream_t copy_stream = nullptr;
-  hipEvent_t ev_upload[2] = {}, ev_done[2] = {};
+  PinnedBuf<uint8_t> h_in[2]; size_t h_in_bytes = 0; int i_stage = 0;
+  PinnedBuf<uint8_t> h_out; size_t h_out_bytes = 0;
+  owned::Stream copy_stream;
+  owned::Event ev_upload[2], ev_done[2];
   // FAST (and block matching) need the new pyramid only, the dense tracker runs ~18 dependent sweeps per stream with a long tail (streams finish at
   // different times): the detector stages are enqueued on a second stream and meet the chain again in front of the matcher
-  hipStream_t side_stream = nullptr;
-  hipEvent_t ev_fork = nullptr, ev_join = nullptr;
+  owned::Stream side_stream;
+  owned::Event ev_fork, ev_join;
   bool prefetched = false, submitted = false, want_matches = false, want_gated = false;
   int n_submitted = 0;
   // accept / reject record of the dense tracker's LM loop, per stream (svs_frontend_dense_records)
-  svs_dense_lm_record *d_rec = nullptr; int32_t *d_nrec = nullptr;
-  void *d_trk_work = nullptr;           // state of the tracker's balanced launch (dense.hip: LM work of every stream's last frame -> workgroups per stream); big batches only
+  DevBuf<svs_dense_lm_record> d_rec; DevBuf<int32_t> d_nrec;
+  DevBuf<void> d_trk_work;              // state of the tracker's balanced launch (dense.hip: LM work of every stream's last frame -> workgroups per stream); big batches only
   // optional stage timing (svs_frontend_set_timing): events between the stages of the last call
   bool timing = false;
-  hipEvent_t ev_stage[SVS_FRONTEND_STAGES + 1] = {};
+  owned::Event ev_stage[SVS_FRONTEND_STAGES + 1];
   // new-point seeding (svs_frontend_seed_keyframes): records the last step's gate wrote per stream; -1 while they do not describe the candidate list (no step
   // since the last first frame, or the list was replaced behind the step), staging blocks grown on demand
   int n_gated = -1;
-  uint8_t *h_seed = nullptr, *d_seed = nullptr; size_t h_seed_bytes = 0, d_seed_bytes = 0;
+  PinnedBuf<uint8_t> h_seed; DevBuf<uint8_t> d_seed;
+  // drains the streams and takes the detector / block matcher along before the members above go (also when create gives up half way)
+  ~svs_frontend() {
+    (void)hipStreamSynchronize(ctx->stream);
+    if (copy_stream) (void)hipStreamSynchronize(copy_stream);
+    if (side_stream) (void)hipStreamSynchronize(side_stream);
+    if (fast) svs_fast_destroy(fast);
+    if (stereo) svs_stereo_destroy(stereo);
+  }
 };
 constexpr int REC_CAP = 64;
 
@@ -179,38 +191,6 @@ static void fastgrid_for_level(int w, int h, int level, svs_fastgrid *g) {      
 
 extern "C" int svs_frontend_destroy(svs_frontend *fe) {
   if (!fe) return SVS_OK;
-  (void)hipStreamSynchronize(fe->ctx->stream);
-  if (fe->copy_stream) (void)hipStreamSynchronize(fe->copy_stream);
-  if (fe->side_stream) (void)hipStreamSynchronize(fe->side_stream);
-  if (fe->fast) svs_fast_destroy(fe->fast);
-  for (hipEvent_t e : fe->ev_early) if (e) (void)hipEventDestroy(e);
-  for (hipEvent_t e : fe->ev_late) if (e) (void)hipEventDestroy(e);
-  for (hipEvent_t e : fe->ev_trk) if (e) (void)hipEventDestroy(e);
-  if (fe->stereo) svs_stereo_destroy(fe->stereo);
-  for (int k = 0; k < 3; ++k) for (int l = 0; l < 3; ++l) if (fe->d_pyr[k][l]) (void)hipFree(fe->d_pyr[k][l]);
-  for (int k = 0; k < 2; ++k) for (int l = 0; l < 3; ++l) if (fe->d_f32[k][l]) (void)hipFree(fe->d_f32[k][l]);
-  for (int l = 0; l < 3; ++l) { if (fe->d_cloud[l]) (void)hipFree(fe->d_cloud[l]); if (fe->d_dx[l]) (void)hipFree(fe->d_dx[l]); if (fe->d_dy[l]) (void)hipFree(fe->d_dy[l]); }
-  if (fe->d_out_block) { (void)hipFree(fe->d_out_block); fe->d_res = nullptr; fe->d_gated = nullptr; fe->d_small = nullptr; }
-  void *ptrs[] = {fe->d_right[0], fe->d_right[1], fe->d_right[2], fe->d_disp[0], fe->d_disp[1], fe->d_disp[2], fe->d_n_new, fe->d_kf_pyr, fe->d_kfs, fe->d_pts, fe->d_res, fe->d_gated, fe->d_small,
-                  fe->d_group_end, fe->d_n_groups};
-  for (void *p : ptrs) if (p) (void)hipFree(p);
-  for (int k = 0; k < 2; ++k) {
-    if (fe->h_in[k]) (void)hipHostFree(fe->h_in[k]);
-    if (fe->ev_upload[k]) (void)hipEventDestroy(fe->ev_upload[k]);
-    if (fe->ev_done[k]) (void)hipEventDestroy(fe->ev_done[k]);
-  }
-  if (fe->h_out) (void)hipHostFree(fe->h_out);
-  if (fe->h_cand_stage) (void)hipHostFree(fe->h_cand_stage);
-  if (fe->h_seed) (void)hipHostFree(fe->h_seed);
-  if (fe->d_seed) (void)hipFree(fe->d_seed);
-  if (fe->d_rec) (void)hipFree(fe->d_rec);
-  if (fe->d_nrec) (void)hipFree(fe->d_nrec);
-  if (fe->d_trk_work) (void)hipFree(fe->d_trk_work);
-  for (hipEvent_t e : fe->ev_stage) if (e) (void)hipEventDestroy(e);
-  if (fe->copy_stream) (void)hipStreamDestroy(fe->copy_stream);
-  if (fe->side_stream) (void)hipStreamDestroy(fe->side_stream);
-  if (fe->ev_fork) (void)hipEventDestroy(fe->ev_fork);
-  if (fe->ev_join) (void)hipEventDestroy(fe->ev_join);
   delete fe;
   return SVS_OK;
 }
@@ -221,7 +201,7 @@ extern "C" int svs_frontend_create_batch(svs_ctx *ctx, const svs_cam *cam, const
   SVS_REQUIRE(ctx, cam->w % 16 == 0 && cam->h % 16 == 0);              // quarter grid on three levels (dense_tracking.cpp:45-46)
   SVS_REQUIRE(ctx, prm->n_levels >= 0 && prm->n_levels <= 3 && prm->num_max_points >= 0 && prm->min_matches >= 0);
   SVS_DEVICE(ctx);
-  svs_frontend *fe = new svs_frontend();
+  std::unique_ptr<svs_frontend> fe(new svs_frontend());
   fe->ctx = ctx; fe->prm = *prm; fe->max_points = max_points; fe->max_keyframes = max_keyframes; fe->B = n_streams;
   if (fe->prm.n_levels == 0) fe->prm.n_levels = 3;
   if (fe->prm.num_max_points == 0) fe->prm.num_max_points = 300;      // ui.num_max_points (stereo_frontend.cpp:1000)
@@ -229,8 +209,6 @@ extern "C" int svs_frontend_create_batch(svs_ctx *ctx, const svs_cam *cam, const
   const size_t B = (size_t)n_streams;
   fe->n_points.assign(B, 0); fe->n_new_records.assign(B, 0);
   fe->kept.assign(B * max_keyframes, 0);
-  int rc = SVS_OK;
-  auto fail = [&](int code) { svs_frontend_destroy(fe); return code; };
   size_t off = 0;
   for (int l = 0; l < 3; ++l) {
     const double s = (double)(1 << l);
@@ -242,83 +220,79 @@ extern "C" int svs_frontend_create_batch(svs_ctx *ctx, const svs_cam *cam, const
   }
   fe->kf_bytes = off;
   for (int k = 0; k < 3; ++k)
-    for (int l = 0; l < 3; ++l) if (hipMalloc(&fe->d_pyr[k][l], fe->lvl_elems[l] * B) != hipSuccess) return fail(SVS_ERR_HIP);
+    for (int l = 0; l < 3; ++l) SVS_HIP(ctx, fe->d_pyr[k][l].alloc(fe->lvl_elems[l] * B));
   const size_t px0 = fe->lvl_elems[0];
   for (int k = 0; k < 3; ++k) {
-    if (prm->use_block_matching && hipMalloc(&fe->d_right[k], px0 * B) != hipSuccess) return fail(SVS_ERR_HIP);
-    if (hipMalloc(&fe->d_disp[k], px0 * B * sizeof(float)) != hipSuccess) return fail(SVS_ERR_HIP);
+    if (prm->use_block_matching) SVS_HIP(ctx, fe->d_right[k].alloc(px0 * B));
+    SVS_HIP(ctx, fe->d_disp[k].alloc(px0 * B));
   }
   for (int l = 0; l < 3; ++l) {
     fe->cloud_elems[l] = prm->cuda_build ? 4 * (size_t)fe->w[l] * fe->h[l] : 4 * (size_t)(fe->w[l] / 4) * (fe->h[l] / 4);
-    if (hipMalloc(&fe->d_cloud[l], sizeof(float) * fe->cloud_elems[l] * B) != hipSuccess) return fail(SVS_ERR_HIP);
-    if (prm->cuda_build) {
-      const size_t bytes = sizeof(float) * fe->lvl_elems[l] * B;
-      if (hipMalloc(&fe->d_f32[0][l], bytes) != hipSuccess || hipMalloc(&fe->d_f32[1][l], bytes) != hipSuccess || hipMalloc(&fe->d_dx[l], bytes) != hipSuccess ||
-          hipMalloc(&fe->d_dy[l], bytes) != hipSuccess)
-        return fail(SVS_ERR_HIP);
-    }
+    SVS_HIP(ctx, fe->d_cloud[l].alloc(fe->cloud_elems[l] * B));
+    if (prm->cuda_build)
+      for (DevBuf<float> *b : {&fe->d_f32[0][l], &fe->d_f32[1][l], &fe->d_dx[l], &fe->d_dy[l]}) SVS_HIP(ctx, b->alloc(fe->lvl_elems[l] * B));
   }
   // per-stream scalars (poses in and out, statistics): a multiple of 256 bytes, so that the record arrays may follow it in one allocation
   fe->small_bytes = ((sizeof(double) * 48 + sizeof(svs_pose_opt_stats) + sizeof(svs_point_stats) + 8) * B + 255) & ~(size_t)255;
   if (B == 1) {      // latency mode: d_small | d_res | d_gated in the layout of the pinned result buffer -- ONE device-to-host copy per frame instead of three (12 us apart each)
-    const size_t bytes = fe->small_bytes + (sizeof(svs_match_result) + sizeof(svs_gated_point)) * (size_t)max_points;
-    if (hipMalloc(&fe->d_out_block, bytes) != hipSuccess) return fail(SVS_ERR_HIP);
-    fe->d_small = reinterpret_cast<double *>(fe->d_out_block);
+    SVS_HIP(ctx, fe->d_out_block.alloc(fe->small_bytes + (sizeof(svs_match_result) + sizeof(svs_gated_point)) * (size_t)max_points));
+    fe->d_small = reinterpret_cast<double *>(fe->d_out_block.get());
     fe->d_res = reinterpret_cast<svs_match_result *>(fe->d_out_block + fe->small_bytes);
     fe->d_gated = reinterpret_cast<svs_gated_point *>(fe->d_out_block + fe->small_bytes + sizeof(svs_match_result) * (size_t)max_points);
-  } else if (hipMalloc(&fe->d_res, sizeof(svs_match_result) * max_points * B) != hipSuccess || hipMalloc(&fe->d_gated, sizeof(svs_gated_point) * max_points * B) != hipSuccess ||
-             hipMalloc(&fe->d_small, fe->small_bytes) != hipSuccess)
-    return fail(SVS_ERR_HIP);
-  if (hipMalloc(&fe->d_kf_pyr, fe->kf_bytes * max_keyframes * B) != hipSuccess || hipMalloc(&fe->d_kfs, sizeof(svs_keyframe) * max_keyframes * B) != hipSuccess ||
-      hipMalloc(&fe->d_pts, sizeof(svs_candidate_point) * max_points * B) != hipSuccess || hipMalloc(&fe->d_group_end, sizeof(int32_t) * MAX_GROUPS * B) != hipSuccess ||
-      hipMalloc(&fe->d_n_groups, sizeof(int32_t) * B) != hipSuccess || hipMalloc(&fe->d_n_new, sizeof(int32_t) * B) != hipSuccess)
-    return fail(SVS_ERR_HIP);
+  } else {
+    SVS_HIP(ctx, fe->res_block.alloc(max_points * B, &fe->d_res));
+    SVS_HIP(ctx, fe->gated_block.alloc(max_points * B, &fe->d_gated));
+    SVS_HIP(ctx, fe->small_block.alloc_bytes(fe->small_bytes, &fe->d_small));
+  }
+  SVS_HIP(ctx, fe->d_kf_pyr.alloc(fe->kf_bytes * max_keyframes * B));
+  SVS_HIP(ctx, fe->d_kfs.alloc(max_keyframes * B));
+  SVS_HIP(ctx, fe->d_pts.alloc(max_points * B));
+  SVS_HIP(ctx, fe->d_group_end.alloc(MAX_GROUPS * B));
+  SVS_HIP(ctx, fe->d_n_groups.alloc(B));
+  SVS_HIP(ctx, fe->d_n_new.alloc(B));
   // unused keyframe slots hold null pyramids, unused candidate records kf_index = -1 (-> SVS_MATCH_NO_ANCHOR): nothing a kernel could follow
-  if (hipMemsetAsync(fe->d_kfs, 0, sizeof(svs_keyframe) * max_keyframes * B, ctx->stream) != hipSuccess ||
-      hipMemsetAsync(fe->d_pts, 0xff, sizeof(svs_candidate_point) * max_points * B, ctx->stream) != hipSuccess ||
-      hipMemsetAsync(fe->d_n_groups, 0, sizeof(int32_t) * B, ctx->stream) != hipSuccess || hipMemsetAsync(fe->d_n_new, 0, sizeof(int32_t) * B, ctx->stream) != hipSuccess)
-    return fail(SVS_ERR_HIP);
-  if (hipMemsetAsync(fe->d_small, 0, fe->small_bytes, ctx->stream) != hipSuccess) return fail(SVS_ERR_HIP);
+  SVS_HIP(ctx, hipMemsetAsync(fe->d_kfs, 0, sizeof(svs_keyframe) * max_keyframes * B, ctx->stream));
+  SVS_HIP(ctx, hipMemsetAsync(fe->d_pts, 0xff, sizeof(svs_candidate_point) * max_points * B, ctx->stream));
+  SVS_HIP(ctx, hipMemsetAsync(fe->d_n_groups, 0, sizeof(int32_t) * B, ctx->stream));
+  SVS_HIP(ctx, hipMemsetAsync(fe->d_n_new, 0, sizeof(int32_t) * B, ctx->stream));
+  SVS_HIP(ctx, hipMemsetAsync(fe->d_small, 0, fe->small_bytes, ctx->stream));
   fe->d_pstats = reinterpret_cast<svs_pose_opt_stats *>(fe->d_small + 48 * B);
   fe->d_ptstats = reinterpret_cast<svs_point_stats *>(fe->d_pstats + B);
   fe->d_passes = reinterpret_cast<int32_t *>(fe->d_ptstats + B);
   fe->h_kfs.assign(max_keyframes * B, svs_keyframe{});
   svs_fastgrid grids[3];
   for (int l = 0; l < 3; ++l) fastgrid_for_level(fe->w[l], fe->h[l], l, &grids[l]);
-  rc = svs_fast_create(ctx, fe->prm.n_levels, fe->w, fe->h, grids, n_streams, 8192, &fe->fast);
-  if (rc) return fail(rc);
+  if (int rc = svs_fast_create(ctx, fe->prm.n_levels, fe->w, fe->h, grids, n_streams, 8192, &fe->fast)) return rc;
   if (ctx->fe_pipeline && n_streams > 1 && n_streams <= 2 * ctx->n_cu && !prm->use_block_matching && !prm->cuda_build) {
     for (int k = 0; k < 2; ++k)
-      if (hipEventCreateWithFlags(&fe->ev_early[k], hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&fe->ev_late[k], hipEventDisableTiming) != hipSuccess ||
-          hipEventCreateWithFlags(&fe->ev_trk[k], hipEventDisableTiming) != hipSuccess)
-        return fail(SVS_ERR_HIP);
+      for (owned::Event *e : {&fe->ev_early[k], &fe->ev_late[k], &fe->ev_trk[k]}) SVS_HIP(ctx, e->create(hipEventDisableTiming));
   }
-  if (prm->use_block_matching) { rc = svs_stereo_create(ctx, fe->w[0], fe->h[0], n_streams, &prm->stereo, &fe->stereo); if (rc) return fail(rc); }
+  if (prm->use_block_matching) if (int rc = svs_stereo_create(ctx, fe->w[0], fe->h[0], n_streams, &prm->stereo, &fe->stereo)) return rc;
   fe->h_in_bytes = 2 * (size_t)fe->w[0] * fe->h[0] + sizeof(float) * (size_t)fe->w[0] * fe->h[0] + sizeof(double) * 24 * B;
   fe->h_out_bytes = fe->small_bytes + (sizeof(svs_match_result) + sizeof(svs_gated_point)) * (size_t)max_points;
   for (int k = 0; k < 2; ++k) {
-    if (hipHostMalloc((void **)&fe->h_in[k], fe->h_in_bytes, hipHostMallocDefault) != hipSuccess) return fail(SVS_ERR_HIP);
-    if (hipEventCreateWithFlags(&fe->ev_upload[k], hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&fe->ev_done[k], hipEventDisableTiming) != hipSuccess)
-      return fail(SVS_ERR_HIP);
+    SVS_HIP(ctx, fe->h_in[k].alloc(fe->h_in_bytes));
+    SVS_HIP(ctx, fe->ev_upload[k].create(hipEventDisableTiming));
+    SVS_HIP(ctx, fe->ev_done[k].create(hipEventDisableTiming));
   }
-  if (hipHostMalloc((void **)&fe->h_out, fe->h_out_bytes, hipHostMallocDefault) != hipSuccess) return fail(SVS_ERR_HIP);
-  if (hipStreamCreateWithFlags(&fe->copy_stream, hipStreamNonBlocking) != hipSuccess) return fail(SVS_ERR_HIP);
+  SVS_HIP(ctx, fe->h_out.alloc(fe->h_out_bytes));
+  SVS_HIP(ctx, fe->copy_stream.create(hipStreamNonBlocking));
   {
     int least = 0, greatest = 0;      // the chain's own stream keeps the first claim on the CUs
     if (hipDeviceGetStreamPriorityRange(&least, &greatest) != hipSuccess) least = 0;
-    if (hipStreamCreateWithPriority(&fe->side_stream, hipStreamNonBlocking, least) != hipSuccess) return fail(SVS_ERR_HIP);
-    if (hipEventCreateWithFlags(&fe->ev_fork, hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&fe->ev_join, hipEventDisableTiming) != hipSuccess)
-      return fail(SVS_ERR_HIP);
+    SVS_HIP(ctx, fe->side_stream.create(hipStreamNonBlocking, least));
+    SVS_HIP(ctx, fe->ev_fork.create(hipEventDisableTiming));
+    SVS_HIP(ctx, fe->ev_join.create(hipEventDisableTiming));
   }
-  if (hipMalloc(&fe->d_rec, sizeof(svs_dense_lm_record) * REC_CAP * B) != hipSuccess || hipMalloc(&fe->d_nrec, sizeof(int32_t) * B) != hipSuccess ||
-      hipMemsetAsync(fe->d_nrec, 0, sizeof(int32_t) * B, ctx->stream) != hipSuccess)
-    return fail(SVS_ERR_HIP);
+  SVS_HIP(ctx, fe->d_rec.alloc(REC_CAP * B));
+  SVS_HIP(ctx, fe->d_nrec.alloc(B));
+  SVS_HIP(ctx, hipMemsetAsync(fe->d_nrec, 0, sizeof(int32_t) * B, ctx->stream));
   if (B >= 2 * ctx->n_cu && B <= 4096) {
-    if (hipMalloc(&fe->d_trk_work, svs_dense_track_balance_bytes(B)) != hipSuccess) return fail(SVS_ERR_HIP);
-    if ((rc = svs_dense_track_balance_init(ctx, fe->d_trk_work, B))) return fail(rc);
+    SVS_HIP(ctx, fe->d_trk_work.alloc_bytes(svs_dense_track_balance_bytes(B)));
+    if (int rc = svs_dense_track_balance_init(ctx, fe->d_trk_work, B)) return rc;
   }
-  if (hipStreamSynchronize(ctx->stream) != hipSuccess) return fail(SVS_ERR_HIP);
-  *out = fe;
+  SVS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  *out = fe.release();
   return SVS_OK;
 }
 
@@ -427,7 +401,7 @@ extern "C" int svs_frontend_set_candidates_all(svs_frontend *fe, const svs_candi
   }
   // the device list is [n_streams][max_points]: lay the records out like that in a pinned block the front end keeps (unused tails = 0xff, "no candidate") and send
   // the first m records of every stream as one strided copy, m = the longest list now or before (what lies behind a stream's list on the device is 0xff: svs_frontend_create, the per-stream setters)
-  if (!fe->h_cand_stage) SVS_HIP(ctx, hipHostMalloc(reinterpret_cast<void **>(&fe->h_cand_stage), sizeof(svs_candidate_point) * (size_t)fe->B * fe->max_points, hipHostMallocDefault));
+  if (!fe->h_cand_stage) SVS_HIP(ctx, fe->h_cand_stage.alloc((size_t)fe->B * fe->max_points));
   int m = 0;
   for (int b = 0; b < B; ++b) m = std::max(m, std::max(h_n[b], fe->n_points[b]));
   std::vector<int32_t> ge((size_t)B * MAX_GROUPS, 0), ng((size_t)B, n_groups), nn((size_t)B);
@@ -579,7 +553,7 @@ int frontend_chain(svs_frontend *fe, bool first, DispView dv, bool ext_frames = 
   }
   const int f32c = fe->i_f32, f32p = 1 - fe->i_f32;
   if (fe->prm.cuda_build) {
-    if ((rc = svs_preprocess_gpu_sem(ctx, fe->d_pyr[cur][0], fe->w[0], fe->h[0], fe->stride[0], fe->lvl_elems[0], fe->d_f32[f32c], fe->d_dx, fe->d_dy, fe->stride,
+    if ((rc = svs_preprocess_gpu_sem(ctx, fe->d_pyr[cur][0], fe->w[0], fe->h[0], fe->stride[0], fe->lvl_elems[0], views(fe->d_f32[f32c]), views(fe->d_dx), views(fe->d_dy), fe->stride,
                                      fe->lvl_elems, 3, B)))
       return rc;
   }
@@ -700,7 +674,7 @@ int frontend_chain(svs_frontend *fe, bool first, DispView dv, bool ext_frames = 
   STAGE_MARK(7);
   if (!fused_tail && !fe->prm.cuda_build) {                                                   // "dense point cloud" (reference for the next frame): three levels, one launch
     size_t cb[3] = {fe->cloud_elems[0], fe->cloud_elems[1], fe->cloud_elems[2]};
-    if ((rc = svs_pointcloud_cpu_sem_levels(ctx, dv.p, dv.stride, dv.bstride, fe->cams, d_T, fe->d_cloud, cb, B))) return rc;
+    if ((rc = svs_pointcloud_cpu_sem_levels(ctx, dv.p, dv.stride, dv.bstride, fe->cams, d_T, views(fe->d_cloud), cb, B))) return rc;
   }
   for (int l = 0; l < 3 && !fused_tail && fe->prm.cuda_build; ++l) {
     if (fe->prm.cuda_build)
@@ -982,7 +956,7 @@ extern "C" int svs_frontend_set_timing(svs_frontend *fe, int on) {
   SVS_REQUIRE(ctx, fe);
   SVS_DEVICE(ctx);
   if (on && !fe->ev_stage[0])
-    for (hipEvent_t &e : fe->ev_stage) SVS_HIP(ctx, hipEventCreate(&e));
+    for (owned::Event &e : fe->ev_stage) SVS_HIP(ctx, e.create());
   fe->timing = on != 0;
   return SVS_OK;
 }
@@ -1047,20 +1021,10 @@ extern "C" int svs_frontend_seed_keyframes(svs_frontend *fe, int n, const svs_se
   // small results go home in one copy through the pinned block; big ones as the counts, then one strided copy of the longest list's width into the caller's array
   const bool one_copy = out_bytes <= ((size_t)1 << 20);
   const size_t h_bytes = std::max(in_bytes, one_copy ? out_bytes : off_rec - off_cnt);
-  if (fe->h_seed_bytes < h_bytes || fe->d_seed_bytes < d_bytes) SVS_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  if (fe->h_seed_bytes < h_bytes) {
-    if (fe->h_seed) (void)hipHostFree(fe->h_seed);
-    fe->h_seed = nullptr; fe->h_seed_bytes = 0;
-    SVS_HIP(ctx, hipHostMalloc(reinterpret_cast<void **>(&fe->h_seed), h_bytes, hipHostMallocDefault));
-    fe->h_seed_bytes = h_bytes;
-  }
-  if (fe->d_seed_bytes < d_bytes) {
-    if (fe->d_seed) (void)hipFree(fe->d_seed);
-    fe->d_seed = nullptr; fe->d_seed_bytes = 0;
-    SVS_HIP(ctx, hipMalloc(reinterpret_cast<void **>(&fe->d_seed), d_bytes));
-    fe->d_seed_bytes = d_bytes;
-  }
-  svs_seed_problem *hp = reinterpret_cast<svs_seed_problem *>(fe->h_seed);
+  if (fe->h_seed.bytes() < h_bytes || fe->d_seed.bytes() < d_bytes) SVS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  if (fe->h_seed.bytes() < h_bytes) SVS_HIP(ctx, fe->h_seed.alloc_bytes(h_bytes));
+  if (fe->d_seed.bytes() < d_bytes) SVS_HIP(ctx, fe->d_seed.alloc_bytes(d_bytes));
+  svs_seed_problem *hp = reinterpret_cast<svs_seed_problem *>(fe->h_seed.get());
   int32_t *hs = reinterpret_cast<int32_t *>(fe->h_seed + off_slot);
   for (int r = 0; r < n; ++r) {
     const svs_seed_request &q = req[r];
@@ -1088,7 +1052,7 @@ extern "C" int svs_frontend_seed_keyframes(svs_frontend *fe, int n, const svs_se
   }
   a.d_disp = fe->last_disp; a.disp_stride = fe->last_dstride; a.disp_bstride = fe->last_dbstride;
   a.cam = fe->cams[0];
-  a.d_prob = reinterpret_cast<const svs_seed_problem *>(fe->d_seed);
+  a.d_prob = reinterpret_cast<const svs_seed_problem *>(fe->d_seed.get());
   a.batch = n;
   SeedFrontendSrc fs{};
   fs.slot_of = reinterpret_cast<const int32_t *>(fe->d_seed + off_slot);

@@ -57,8 +57,8 @@ int svs_spin_enter(svs_ctx *c, int n_workgroups) {
 int svs_spin_leave(svs_ctx *c) {
   SpinGate &g = gate_of(c);
   hipError_t e = hipSuccess;
-  hipEvent_t &ev = c->spin_lane ? c->lane_ev : c->spin_ev;
-  if (!ev) e = hipEventCreateWithFlags(&ev, hipEventDisableTiming);
+  owned::Event &ev = c->spin_lane ? c->lane_ev : c->spin_ev;
+  if (!ev) e = ev.create(hipEventDisableTiming);
   if (e == hipSuccess) e = hipEventRecord(ev, c->stream);
   if (e == hipSuccess) {
     if (c->spin_lane) {
@@ -83,62 +83,39 @@ extern "C" int svs_ctx_create(int device, void *hip_stream, svs_ctx **out) {
   if (!out) return SVS_ERR_INVALID;
   int n = 0;
   if (hipGetDeviceCount(&n) != hipSuccess || n <= 0 || device < 0 || device >= n) return SVS_ERR_NO_DEVICE;
-  svs_ctx *c = new svs_ctx();
+  std::unique_ptr<svs_ctx> c(new svs_ctx());
   c->device = device;
-  if (hipSetDevice(device) != hipSuccess) { delete c; return SVS_ERR_NO_DEVICE; }
+  if (hipSetDevice(device) != hipSuccess) return SVS_ERR_NO_DEVICE;
   { int cu = 0; if (hipDeviceGetAttribute(&cu, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess && cu > 0) c->n_cu = cu; }
-  if (hip_stream) { c->stream = (hipStream_t)hip_stream; c->own_stream = false; }
-  else {
-    if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) { delete c; return SVS_ERR_HIP; }
-    c->own_stream = true;
-  }
-  if (hipEventCreate(&c->ev0) != hipSuccess || hipEventCreate(&c->ev1) != hipSuccess) { delete c; return SVS_ERR_HIP; }
+  if (hip_stream) c->stream = (hipStream_t)hip_stream;
+  else if (c->own_stream.create(hipStreamNonBlocking) != hipSuccess) return SVS_ERR_HIP;
+  else c->stream = c->own_stream;
+  if (c->ev0.create() != hipSuccess || c->ev1.create() != hipSuccess) return SVS_ERR_HIP;
   auto env_int = [](const char *name, int lo, int hi) { const char *e = getenv(name); if (!e) return 0; const int v = atoi(e); return v < lo ? lo : (v > hi ? hi : v); };
   c->trk_nwg = env_int("SVS_TRK_NWG", 1, 64);
   if (getenv("SVS_TRK_BALANCE")) c->trk_balance = atoi(getenv("SVS_TRK_BALANCE"));
   c->trk_regs = getenv("SVS_TRK_ONE_PER_CU") ? 1 : (getenv("SVS_TRK_TWO_PER_CU") ? 2 : 0);
   c->full_nwg = env_int("SVS_FULL_NWG", 1, 1024);
-  *out = c;
+  *out = c.release();
   return SVS_OK;
 }
 extern "C" int svs_ctx_destroy(svs_ctx *c) {
   if (!c) return SVS_OK;
   (void)hipStreamSynchronize(c->stream);
   spin_forget(c);                                                   // (the stream is drained: nobody needs to wait for this context any more)
-  if (c->spin_ev) (void)hipEventDestroy(c->spin_ev);
-  if (c->lane_ev) (void)hipEventDestroy(c->lane_ev);
-  if (c->ev0) (void)hipEventDestroy(c->ev0);
-  if (c->ev1) (void)hipEventDestroy(c->ev1);
-  if (c->scratch) (void)hipFree(c->scratch);
-  if (c->match_scratch) (void)hipFree(c->match_scratch);
-  if (c->seq_buf) (void)hipFree(c->seq_buf);
-  if (c->seq_stats) (void)hipFree(c->seq_stats);
-  if (c->own_stream) (void)hipStreamDestroy(c->stream);
   delete c;
   return SVS_OK;
 }
-int svs_ctx_scratch(svs_ctx *c, size_t bytes, void **out) {
+// the context's two grow-only scratch blocks (common.h: svs_ctx_scratch, svs_ctx_match_scratch)
+int svs_ctx_grow(svs_ctx *c, DevBuf<void> svs_ctx::*which, size_t bytes, void **out) {
   SVS_REQUIRE(c, c && out);
-  if (c->scratch_bytes < bytes) {
+  DevBuf<void> &buf = c->*which;
+  if (buf.bytes() < bytes) {
     SVS_DEVICE(c);
-    if (c->scratch) { SVS_HIP(c, hipStreamSynchronize(c->stream)); (void)hipFree(c->scratch); c->scratch = nullptr; c->scratch_bytes = 0; }
-    const size_t want = bytes + bytes / 2 + 4096;
-    SVS_HIP(c, hipMalloc(&c->scratch, want));
-    c->scratch_bytes = want;
+    if (buf) SVS_HIP(c, hipStreamSynchronize(c->stream));
+    SVS_HIP(c, buf.reserve(bytes, bytes + bytes / 2 + 4096));
   }
-  *out = c->scratch;
-  return SVS_OK;
-}
-int svs_ctx_match_scratch(svs_ctx *c, size_t bytes, void **out) {
-  SVS_REQUIRE(c, c && out);
-  if (c->match_scratch_bytes < bytes) {
-    SVS_DEVICE(c);
-    if (c->match_scratch) { SVS_HIP(c, hipStreamSynchronize(c->stream)); (void)hipFree(c->match_scratch); c->match_scratch = nullptr; c->match_scratch_bytes = 0; }
-    const size_t want = bytes + bytes / 2 + 4096;
-    SVS_HIP(c, hipMalloc(&c->match_scratch, want));
-    c->match_scratch_bytes = want;
-  }
-  *out = c->match_scratch;
+  *out = buf;
   return SVS_OK;
 }
 extern "C" int svs_ctx_set_option(svs_ctx *c, const char *name, int value) {
@@ -170,6 +147,10 @@ extern "C" int svs_ctx_get_stat(svs_ctx *c, const char *name, long long *out) {
   // the spin gate's book-keeping of this context (host-side counters): launches that took the priority lane / that went through the gate
   if (n == "spin_lane_launches") { *out = c->spin_n_lane; return SVS_OK; }
   if (n == "spin_gated_launches") { *out = c->spin_n_gated; return SVS_OK; }
+  // what the owners of the whole process hold right now (owned.h)
+  if (n == "live_device_bytes") { *out = owned::g_live_device_bytes; return SVS_OK; }
+  if (n == "live_pinned_bytes") { *out = owned::g_live_pinned_bytes; return SVS_OK; }
+  if (n == "live_sync_objects") { *out = owned::g_live_sync_objects; return SVS_OK; }
   SVS_REQUIRE(c, n == "trk_exact_sums" || n == "trk_exact_fallbacks");
   unsigned v[2] = {0, 0};
   if (c->seq_stats) {
@@ -192,10 +173,10 @@ extern "C" const char *svs_last_error(svs_ctx *c) { return c ? c->err.c_str() : 
 extern "C" int svs_malloc(svs_ctx *c, size_t bytes, void **p) {
   SVS_REQUIRE(c, c && p);
   SVS_HIP(c, hipSetDevice(c->device));
-  SVS_HIP(c, hipMalloc(p, bytes ? bytes : 1));
+  SVS_HIP(c, owned::caller_malloc(p, bytes ? bytes : 1));
   return SVS_OK;
 }
-extern "C" int svs_free(svs_ctx *c, void *p) { SVS_REQUIRE(c, c); if (p) SVS_HIP(c, hipFree(p)); return SVS_OK; }
+extern "C" int svs_free(svs_ctx *c, void *p) { SVS_REQUIRE(c, c); if (p) SVS_HIP(c, owned::caller_free(p)); return SVS_OK; }
 extern "C" int svs_memcpy_h2d(svs_ctx *c, void *d, const void *h, size_t n) {
   SVS_REQUIRE(c, c);
   SVS_DEVICE(c);

@@ -37,14 +37,15 @@ struct svs_loop {
   svs_ctx *ctx = nullptr;
   loop_cam cam{};
   int K = 0, max_desc = 0, max_places = 0, max_hyp = 0, max_checks = 0;
-  float *d_desc = nullptr, *d_norm = nullptr;      // [max_places][max_desc][K], [max_places][max_desc] squared norms
-  double *d_uvu = nullptr, *d_xyz = nullptr;       // [max_places][max_desc][3]
-  int *n_place = nullptr;                          // host: descriptors per slot, 0 = empty
-  uint8_t *h_stage = nullptr;                      // pinned: one place on its way up
-  hipEvent_t ev_stage = nullptr; bool stage_busy = false;
+  DevBuf<float> d_desc, d_norm;                    // [max_places][max_desc][K], [max_places][max_desc] squared norms
+  DevBuf<double> d_uvu, d_xyz;                     // [max_places][max_desc][3]
+  std::unique_ptr<int[]> n_place;                  // host: descriptors per slot, 0 = empty
+  PinnedBuf<uint8_t> h_stage;                      // pinned: one place on its way up
+  owned::Event ev_stage; bool stage_busy = false;
   size_t in_stride = 0; loop_out_layout lay{};
-  uint8_t *h_in = nullptr, *d_in = nullptr, *h_out = nullptr, *d_out = nullptr;      // pinned / device: the checks, the results
-  int timing = 0; hipEvent_t ev[3] = {nullptr, nullptr, nullptr}; float stage_ms[2] = {0.f, 0.f};
+  PinnedBuf<uint8_t> h_in, h_out; DevBuf<uint8_t> d_in, d_out;      // pinned / device: the checks, the results
+  int timing = 0; owned::Event ev[3]; float stage_ms[2] = {0.f, 0.f};
+  ~svs_loop() { if (ctx) { (void)hipSetDevice(ctx->device); (void)hipStreamSynchronize(ctx->stream); } }      // (before the members go, also when create gives up)
 };
 
 #define LOOP_CAPACITY(ctx, cond)                                                                          \
@@ -409,19 +410,6 @@ __global__ __launch_bounds__(LR_THREADS) void loop_ransac_kernel(const double *_
 // ---- host --------------------------------------------------------------------------------------------------------------------------------------------
 extern "C" int svs_loop_destroy(svs_loop *l) {
   if (!l) return SVS_OK;
-  if (l->ctx) { (void)hipSetDevice(l->ctx->device); (void)hipStreamSynchronize(l->ctx->stream); }
-  if (l->d_desc) (void)hipFree(l->d_desc);
-  if (l->d_norm) (void)hipFree(l->d_norm);
-  if (l->d_uvu) (void)hipFree(l->d_uvu);
-  if (l->d_xyz) (void)hipFree(l->d_xyz);
-  if (l->d_in) (void)hipFree(l->d_in);
-  if (l->d_out) (void)hipFree(l->d_out);
-  if (l->h_stage) (void)hipHostFree(l->h_stage);
-  if (l->h_in) (void)hipHostFree(l->h_in);
-  if (l->h_out) (void)hipHostFree(l->h_out);
-  if (l->ev_stage) (void)hipEventDestroy(l->ev_stage);
-  for (int i = 0; i < 3; ++i) if (l->ev[i]) (void)hipEventDestroy(l->ev[i]);
-  delete[] l->n_place;
   delete l;
   return SVS_OK;
 }
@@ -429,17 +417,17 @@ extern "C" int svs_loop_destroy(svs_loop *l) {
 static int loop_alloc(svs_loop *l) {
   svs_ctx *ctx = l->ctx;
   const size_t rows = (size_t)l->max_places * l->max_desc;
-  SVS_HIP(ctx, hipMalloc((void **)&l->d_desc, rows * l->K * sizeof(float)));
-  SVS_HIP(ctx, hipMalloc((void **)&l->d_norm, rows * sizeof(float)));
-  SVS_HIP(ctx, hipMalloc((void **)&l->d_uvu, rows * 3 * sizeof(double)));
-  SVS_HIP(ctx, hipMalloc((void **)&l->d_xyz, rows * 3 * sizeof(double)));
-  SVS_HIP(ctx, hipHostMalloc((void **)&l->h_stage, (size_t)l->max_desc * (l->K * sizeof(float) + 6 * sizeof(double)), hipHostMallocDefault));
-  SVS_HIP(ctx, hipEventCreateWithFlags(&l->ev_stage, hipEventDisableTiming));
-  SVS_HIP(ctx, hipMalloc((void **)&l->d_in, l->in_stride * l->max_checks));
-  SVS_HIP(ctx, hipMalloc((void **)&l->d_out, l->lay.stride * l->max_checks));
-  SVS_HIP(ctx, hipHostMalloc((void **)&l->h_in, l->in_stride * l->max_checks, hipHostMallocDefault));
-  SVS_HIP(ctx, hipHostMalloc((void **)&l->h_out, l->lay.stride * l->max_checks, hipHostMallocDefault));
-  for (int i = 0; i < 3; ++i) SVS_HIP(ctx, hipEventCreate(&l->ev[i]));
+  SVS_HIP(ctx, l->d_desc.alloc(rows * l->K));
+  SVS_HIP(ctx, l->d_norm.alloc(rows));
+  SVS_HIP(ctx, l->d_uvu.alloc(rows * 3));
+  SVS_HIP(ctx, l->d_xyz.alloc(rows * 3));
+  SVS_HIP(ctx, l->h_stage.alloc((size_t)l->max_desc * (l->K * sizeof(float) + 6 * sizeof(double))));
+  SVS_HIP(ctx, l->ev_stage.create(hipEventDisableTiming));
+  SVS_HIP(ctx, l->d_in.alloc(l->in_stride * l->max_checks));
+  SVS_HIP(ctx, l->d_out.alloc(l->lay.stride * l->max_checks));
+  SVS_HIP(ctx, l->h_in.alloc(l->in_stride * l->max_checks));
+  SVS_HIP(ctx, l->h_out.alloc(l->lay.stride * l->max_checks));
+  for (int i = 0; i < 3; ++i) SVS_HIP(ctx, l->ev[i].create());
   return SVS_OK;
 }
 
@@ -448,11 +436,11 @@ extern "C" int svs_loop_create(svs_ctx *ctx, const svs_cam *cam, int desc_dim, i
                        max_hyp <= LOOP_MAX_HYP && max_checks >= 1);
   SVS_REQUIRE(ctx, cam->f > 0.0 && cam->b > 0.0);
   SVS_DEVICE(ctx);
-  svs_loop *l = new svs_loop();
+  std::unique_ptr<svs_loop> l(new svs_loop());
   l->ctx = ctx;
   l->cam = loop_cam{cam->f, cam->cx, cam->cy, cam->b};
   l->K = desc_dim; l->max_desc = max_desc; l->max_places = max_places; l->max_hyp = max_hyp; l->max_checks = max_checks;
-  l->n_place = new int[max_places]();
+  l->n_place.reset(new int[max_places]());
   l->in_stride = loop_align16(sizeof(loop_check_dev) + (size_t)max_hyp * 3 * sizeof(int32_t));
   l->lay.tidx = (int)loop_align16(sizeof(svs_loop_result));
   l->lay.dist = l->lay.tidx + 4 * max_desc;
@@ -460,8 +448,8 @@ extern "C" int svs_loop_create(svs_ctx *ctx, const svs_cam *cam, int desc_dim, i
   l->lay.hinl = l->lay.smp + 12 * max_hyp;
   l->lay.inl = l->lay.hinl + 4 * max_hyp;
   l->lay.stride = loop_align16((size_t)l->lay.inl + max_desc);
-  if (int rc = loop_alloc(l)) { (void)svs_loop_destroy(l); return rc; }
-  *out = l;
+  if (int rc = loop_alloc(l.get())) return rc;
+  *out = l.release();
   return SVS_OK;
 }
 

@@ -59,7 +59,8 @@ constexpr int RECT_TILE_W = 64, RECT_TILE_H = 16;      // output pixels per 256-
 struct svs_rectify {
   svs_ctx *ctx = nullptr;
   int w = 0, h = 0, max_batch = 0;
-  uint32_t *d_map[2] = {nullptr, nullptr};      // left, right: [h][w] packed words; nullptr = no remap for that side
+  DevBuf<uint32_t> d_map[2];      // left, right: [h][w] packed words; nullptr = no remap for that side
+  ~svs_rectify() { if (ctx) (void)hipStreamSynchronize(ctx->stream); }      // (runs before the maps are freed, also when create gives up)
 };
 
 static int rect_pack_upload(svs_rectify *r, int side, const int16_t *xy, const uint16_t *frac) {
@@ -71,15 +72,13 @@ static int rect_pack_upload(svs_rectify *r, int side, const int16_t *xy, const u
     const int x0 = xy[2 * o], y0 = xy[2 * o + 1];
     pk[o] = (x0 < -1 || x0 > r->w - 1 || y0 < -1 || y0 > r->h - 1) ? RECT_ALL_OUT : ((uint32_t)(y0 + 1) << 21) | ((uint32_t)(x0 + 1) << 10) | frac[o];
   }
-  SVS_HIP(ctx, hipMalloc((void **)&r->d_map[side], n * sizeof(uint32_t)));
+  SVS_HIP(ctx, r->d_map[side].alloc(n));
   SVS_HIP(ctx, hipMemcpy(r->d_map[side], pk.data(), n * sizeof(uint32_t), hipMemcpyHostToDevice));
   return SVS_OK;
 }
 
 extern "C" int svs_rectify_destroy(svs_rectify *r) {
   if (!r) return SVS_OK;
-  if (r->ctx) (void)hipStreamSynchronize(r->ctx->stream);
-  for (int s = 0; s < 2; ++s) if (r->d_map[s]) (void)hipFree(r->d_map[s]);
   delete r;
   return SVS_OK;
 }
@@ -89,13 +88,11 @@ extern "C" int svs_rectify_create(svs_ctx *ctx, int w, int h, int max_batch, con
   SVS_REQUIRE(ctx, ctx && out && w >= 4 && h >= 1 && w % 4 == 0 && w <= RECT_MAX_DIM && h <= RECT_MAX_DIM && max_batch >= 1);
   SVS_REQUIRE(ctx, (h_left_xy != nullptr) == (h_left_frac != nullptr) && (h_right_xy != nullptr) == (h_right_frac != nullptr));
   SVS_DEVICE(ctx);
-  svs_rectify *r = new svs_rectify();
+  std::unique_ptr<svs_rectify> r(new svs_rectify());
   r->ctx = ctx; r->w = w; r->h = h; r->max_batch = max_batch;
-  int rc = SVS_OK;
-  if (h_left_xy) rc = rect_pack_upload(r, 0, h_left_xy, h_left_frac);
-  if (rc == SVS_OK && h_right_xy) rc = rect_pack_upload(r, 1, h_right_xy, h_right_frac);
-  if (rc != SVS_OK) { (void)svs_rectify_destroy(r); return rc; }
-  *out = r;
+  if (h_left_xy) if (int rc = rect_pack_upload(r.get(), 0, h_left_xy, h_left_frac)) return rc;
+  if (h_right_xy) if (int rc = rect_pack_upload(r.get(), 1, h_right_xy, h_right_frac)) return rc;
+  *out = r.release();
   return SVS_OK;
 }
 

@@ -1063,16 +1063,17 @@ struct svs_stereo {
   svs_ctx *ctx = nullptr;
   int w = 0, h = 0, max_batch = 0, pitch = 0;
   svs_stereo_params prm{};
-  uint8_t *d_lp = nullptr, *d_rp = nullptr;
-  int16_t *d_disp16 = nullptr;
-  uint16_t *d_cost = nullptr;
-  int32_t *d_label = nullptr, *d_count = nullptr;
+  DevBuf<uint8_t> d_lp, d_rp;
+  DevBuf<int16_t> d_disp16;
+  DevBuf<uint16_t> d_cost;
+  DevBuf<int32_t> d_label, d_count;
   int strip_rows = 0, n_strips = 0;                     // strip speckle filter (0: whole-frame path)
-  int32_t *d_brow = nullptr, *d_npend = nullptr;
-  int2 *d_pend = nullptr;
+  DevBuf<int32_t> d_brow, d_npend;
+  DevBuf<int2> d_pend;
   int debug = 0;                                      // SVS_STEREO_DEBUG=1 at create
   int force_frame_ccl = 0;                            // SVS_STEREO_FRAME_CCL=1 at create: the whole-frame union-find path (tests compare the two)
   int force_prefilter4 = 0;                           // SVS_STEREO_PREFILTER4=1 at create: the generic 4-pixel prefilter kernel on aligned input too (tests compare the two)
+  ~svs_stereo() { (void)hipStreamSynchronize(ctx->stream); }      // (runs before the buffers are freed)
 };
 
 extern "C" int svs_stereo_create(svs_ctx *ctx, int w, int h, int max_batch, const svs_stereo_params *prm, svs_stereo **out) {
@@ -1083,18 +1084,18 @@ extern "C" int svs_stereo_create(svs_ctx *ctx, int w, int h, int max_batch, cons
     ctx->err = "svs_stereo: only SADWindowSize 7, minDisparity 0, numberOfDisparities 32, preFilterCap 1..63, w >= 38 are supported";
     return SVS_ERR_UNSUPPORTED;
   }
-  svs_stereo *s = new svs_stereo();
+  std::unique_ptr<svs_stereo> s(new svs_stereo());
   s->ctx = ctx; s->w = w; s->h = h; s->max_batch = max_batch; s->pitch = (w + PADL + PADR + 3) & ~3; s->prm = *prm;
   { const char *e = getenv("SVS_STEREO_FRAME_CCL"); s->force_frame_ccl = e && atoi(e) != 0; }
   { const char *e = getenv("SVS_STEREO_PREFILTER4"); s->force_prefilter4 = e && atoi(e) != 0; }      // A/B: the generic 4-pixel kernel on aligned input too
   { const char *e = getenv("SVS_STEREO_DEBUG"); s->debug = e && atoi(e) != 0; }
   const size_t n = (size_t)w * h * max_batch, np = (size_t)s->pitch * h * max_batch + 64;
-  SVS_HIP(ctx, hipMalloc(&s->d_lp, np));
-  SVS_HIP(ctx, hipMalloc(&s->d_rp, np));
-  SVS_HIP(ctx, hipMalloc(&s->d_disp16, n * sizeof(int16_t)));
-  SVS_HIP(ctx, hipMalloc(&s->d_cost, n * sizeof(uint16_t)));
-  SVS_HIP(ctx, hipMalloc(&s->d_label, n * sizeof(int32_t)));
-  SVS_HIP(ctx, hipMalloc(&s->d_count, n * sizeof(int32_t)));
+  SVS_HIP(ctx, s->d_lp.alloc(np));
+  SVS_HIP(ctx, s->d_rp.alloc(np));
+  SVS_HIP(ctx, s->d_disp16.alloc(n));
+  SVS_HIP(ctx, s->d_cost.alloc(n));
+  SVS_HIP(ctx, s->d_label.alloc(n));
+  SVS_HIP(ctx, s->d_count.alloc(n));
   // strip speckle filter where a strip of >= 16 rows (labels 4 B + disparities 2 B per pixel) fits LDS, and the saturating run counts of
   // SPK_THREADS concurrent adds stay below the mark bit
   {
@@ -1104,24 +1105,19 @@ extern "C" int svs_stereo_create(svs_ctx *ctx, int w, int h, int max_batch, cons
     const int rows = std::min(h, (strip_kb * 1024) / spk_row_bytes(w));
     if (rows >= 16 && w <= 64 * SPK_MAX_SEG && (size_t)rows * w < (1u << 24) && (long long)(SPK_THREADS + 1) * std::max(prm->speckle_window, w) < SPK_TOUCH) {
       s->strip_rows = rows; s->n_strips = div_up(h, rows);
-      SVS_HIP(ctx, hipMalloc(&s->d_brow, sizeof(int32_t) * 2 * (size_t)s->n_strips * w * max_batch));
-      SVS_HIP(ctx, hipMalloc(&s->d_pend, sizeof(int2) * n));
-      SVS_HIP(ctx, hipMalloc(&s->d_npend, sizeof(int32_t) * ((size_t)max_batch * s->n_strips + 32)));
+      SVS_HIP(ctx, s->d_brow.alloc(2 * (size_t)s->n_strips * w * max_batch));
+      SVS_HIP(ctx, s->d_pend.alloc(n));
+      SVS_HIP(ctx, s->d_npend.alloc((size_t)max_batch * s->n_strips + 32));
       SVS_HIP(ctx, hipMemset(s->d_npend, 0, sizeof(int32_t) * ((size_t)max_batch * s->n_strips + 32)));
       SVS_HIP(ctx, hipFuncSetAttribute((const void *)stereo_speckle_strip_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, rows * spk_row_bytes(w)));
     }
   }
-  *out = s;
+  *out = s.release();
   return SVS_OK;
 }
 
 extern "C" int svs_stereo_destroy(svs_stereo *s) {
   if (!s) return SVS_OK;
-  (void)hipStreamSynchronize(s->ctx->stream);
-  if (s->d_lp) (void)hipFree(s->d_lp); if (s->d_rp) (void)hipFree(s->d_rp);
-  if (s->d_disp16) (void)hipFree(s->d_disp16); if (s->d_cost) (void)hipFree(s->d_cost);
-  if (s->d_label) (void)hipFree(s->d_label); if (s->d_count) (void)hipFree(s->d_count);
-  if (s->d_brow) (void)hipFree(s->d_brow); if (s->d_pend) (void)hipFree(s->d_pend); if (s->d_npend) (void)hipFree(s->d_npend);
   delete s;
   return SVS_OK;
 }
