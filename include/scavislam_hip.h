@@ -180,7 +180,15 @@ typedef struct {
   int32_t disp12_max_diff;    /* :634  (1; < 0 = no left-right check) */
 } svs_stereo_params;
 typedef struct svs_stereo svs_stereo;
-/* scratch for `max_batch` independent w x h frames (prefiltered images, 16-bit disparity, cost, labels) */
+/* scratch for `max_batch` independent w x h frames (prefiltered images, 16-bit disparity, cost, labels).  38 <= w <= 20164, h >= 2, else SVS_ERR_UNSUPPORTED:
+   the left-right check and the whole-frame speckle filter hold one row in LDS, 8 w + 8 ceil(w / 64) bytes of the 160 KB a workgroup of the MI355X can have
+   (requests above 64 KB are announced with hipFuncAttributeMaxDynamicSharedMemorySize at create).
+   svs_ctx_get_stat of the context tells which kernels svs_stereo_compute chose, one step per call (host-side): "stereo_prefilter16_calls" (rows of 16 n pixels on
+   4-byte aligned pointers and strides) / "stereo_prefilter4_calls" (everything else, or SVS_STEREO_PREFILTER4=1 at create), "stereo_strip_filter_calls" (speckle
+   filter on strips of rows in LDS; "stereo_strip_filter_strips" adds up the strips per frame of those calls) / "stereo_frame_filter_calls" (the whole-frame union-find: rows too wide for 16 of them in LDS, h < 16, speckle_window >= 16368,
+   or SVS_STEREO_FRAME_CCL=1 at create; SVS_STEREO_STRIP_KB=8..151 at create sets the LDS of a strip), "stereo_validate_wide_calls" (left-right check with one row
+   per workgroup, w > 2048).  "stereo_speckle_error_mask" (blocking) is the OR of the bits the bounded walks of the strip filter leave when one gives up (never
+   expected; 0 = none since the context was created): 1 / 2 a find inside a strip, 4 a union inside a strip, 8 / 16 a find / a union across strips. */
 int svs_stereo_create(svs_ctx *ctx, int w, int h, int max_batch, const svs_stereo_params *prm, svs_stereo **out);
 int svs_stereo_destroy(svs_stereo *s);
 /* d_disp[b][y*dstride + x] = disparity in pixels, (min_disparity - 1) where filtered (all device pointers;

@@ -91,6 +91,7 @@ extern "C" int svs_ctx_create(int device, void *hip_stream, svs_ctx **out) {
   else if (c->own_stream.create(hipStreamNonBlocking) != hipSuccess) return SVS_ERR_HIP;
   else c->stream = c->own_stream;
   if (c->ev0.create() != hipSuccess || c->ev1.create() != hipSuccess) return SVS_ERR_HIP;
+  if (c->stereo_err.alloc(32) != hipSuccess || hipMemset(c->stereo_err, 0, 32 * sizeof(int)) != hipSuccess) return SVS_ERR_HIP;
   auto env_int = [](const char *name, int lo, int hi) { const char *e = getenv(name); if (!e) return 0; const int v = atoi(e); return v < lo ? lo : (v > hi ? hi : v); };
   c->trk_nwg = env_int("SVS_TRK_NWG", 1, 64);
   if (getenv("SVS_TRK_BALANCE")) c->trk_balance = atoi(getenv("SVS_TRK_BALANCE"));
@@ -151,6 +152,21 @@ extern "C" int svs_ctx_get_stat(svs_ctx *c, const char *name, long long *out) {
   if (n == "live_device_bytes") { *out = owned::g_live_device_bytes; return SVS_OK; }
   if (n == "live_pinned_bytes") { *out = owned::g_live_pinned_bytes; return SVS_OK; }
   if (n == "live_sync_objects") { *out = owned::g_live_sync_objects; return SVS_OK; }
+  // which kernels svs_stereo_compute chose (host-side counters, one step per call)
+  if (n == "stereo_prefilter16_calls") { *out = c->stereo_n_prefilter16; return SVS_OK; }
+  if (n == "stereo_prefilter4_calls") { *out = c->stereo_n_prefilter4; return SVS_OK; }
+  if (n == "stereo_strip_filter_calls") { *out = c->stereo_n_strip_filter; return SVS_OK; }
+  if (n == "stereo_strip_filter_strips") { *out = c->stereo_n_strips; return SVS_OK; }
+  if (n == "stereo_frame_filter_calls") { *out = c->stereo_n_frame_filter; return SVS_OK; }
+  if (n == "stereo_validate_wide_calls") { *out = c->stereo_n_validate_wide; return SVS_OK; }
+  if (n == "stereo_speckle_error_mask") {      // the give-up bits of the strip speckle filter's bounded walks, on the device (blocking)
+    int m = 0;
+    SVS_DEVICE(c);
+    SVS_HIP(c, hipMemcpyAsync(&m, c->stereo_err, sizeof m, hipMemcpyDeviceToHost, c->stream));
+    SVS_HIP(c, hipStreamSynchronize(c->stream));
+    *out = m;
+    return SVS_OK;
+  }
   SVS_REQUIRE(c, n == "trk_exact_sums" || n == "trk_exact_fallbacks");
   unsigned v[2] = {0, 0};
   if (c->seq_stats) {

@@ -18,6 +18,7 @@
 #include <algorithm>
 #include <cstdlib>
 #include <cstdio>
+#include <mutex>
 #include <vector>
 
 namespace {
@@ -41,7 +42,7 @@ struct StereoDev {
   int2 *pend;            // [batch][h*w]: (pixel, node) of the pixels of undecided components, a list per strip (at the strip's first pixel)
   int32_t *npend;        // [batch][n_strips]
   int timing;            // SVS_STEREO_DEBUG: phase stamps of one workgroup behind the error word
-  int *err;              // [1] set when a bounded walk of the strip path gave up (never expected)
+  int *err;              // the context's word (svs_ctx::stereo_err): bits set when a bounded walk of the strip path gave up (never expected)
   int swz;               // workgroups in XCD-contiguous order (common.h: xcd_contiguous)
 };
 
@@ -1011,7 +1012,7 @@ __global__ __launch_bounds__(SPK_THREADS) void stereo_speckle_strip_kernel(Stere
     int dq[4];
     spk_unpack4(*reinterpret_cast<const uint2 *>(dsp + i0), dq);
     float *o = out + (size_t)b * d_bstride + (size_t)(y0 + row) * dstride + x0;
-    if (vec && (dstride & 3) == 0 && (d_bstride & 3) == 0) *reinterpret_cast<float4 *>(o) = make_float4((float)dq[0] * sc, (float)dq[1] * sc, (float)dq[2] * sc, (float)dq[3] * sc);
+    if (vec && (dstride & 3) == 0 && (d_bstride & 3) == 0 && ((uintptr_t)out & 15) == 0) *reinterpret_cast<float4 *>(o) = make_float4((float)dq[0] * sc, (float)dq[1] * sc, (float)dq[2] * sc, (float)dq[3] * sc);
     else {
 #pragma unroll
       for (int k = 0; k < 4; ++k) if (x0 + k < w) o[k] = (float)dq[k] * sc;
@@ -1057,6 +1058,29 @@ __global__ __launch_bounds__(256) void stereo_speckle_resolve_kernel(StereoDev S
   }
 }
 
+// Dynamic LDS the two kernels ask for whose request grows with the row (every other kernel's LDS is fixed, and the strip speckle filter is only chosen where 16
+// rows fit).  A workgroup of the MI355X can hold 160 KB; a launch that asks for more fails, so svs_stereo_create refuses rows that svs_stereo_compute could
+// not launch.  Requests above the 64 KB a kernel gets by default are announced with hipFuncAttributeMaxDynamicSharedMemorySize at create, as for the strip kernel.
+constexpr size_t LDS_WORKGROUP_BYTES = 160 * 1024, LDS_DEFAULT_BYTES = 64 * 1024;
+constexpr int validate_rows(int w) { return w <= 2048 ? 4 : 1; }                                                      // image rows per workgroup
+constexpr size_t validate_lds_bytes(int w) { return sizeof(int) * 2 * validate_rows(w) * (size_t)w; }                 // (disparity | cost, key) per pixel
+constexpr size_t ccl_runs_lds_bytes(int w) { return sizeof(int) * (2 * (size_t)w + 2 * (size_t)((w + 63) / 64)); }    // (start, length) per pixel, two carries per segment
+constexpr bool row_fits_lds(int w) { return validate_lds_bytes(w) <= LDS_WORKGROUP_BYTES && ccl_runs_lds_bytes(w) <= LDS_WORKGROUP_BYTES; }
+// the widest row every path can hold: 8 w + 8 ceil(w / 64) <= 163840 (stereo_ccl_runs_kernel; stereo_validate_kernel asks for 8 w there).  Both requests grow with w
+// above 2048, and up to 2048 neither exceeds 64 KB.
+constexpr int STEREO_MAX_W = 20164;
+// hipFuncAttributeMaxDynamicSharedMemorySize belongs to the KERNEL, not to a handle: it is only ever raised, to the largest request any handle of the process has
+// made so far (a later, narrower handle must not take away what an earlier one needs at launch).  Set again at every create: the value also has to reach a device
+// that sees the kernel for the first time.
+struct LdsRequest { std::mutex m; size_t high = 0; };
+hipError_t raise_dynamic_lds(const void *kernel, LdsRequest &r, size_t bytes) {
+  std::lock_guard<std::mutex> lk(r.m);
+  r.high = std::max(r.high, bytes);
+  return hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)r.high);
+}
+LdsRequest g_lds_strip, g_lds_validate, g_lds_ccl_runs;
+static_assert(row_fits_lds(STEREO_MAX_W) && !row_fits_lds(STEREO_MAX_W + 1) && row_fits_lds(2048) && row_fits_lds(2049), "STEREO_MAX_W is not the LDS bound");
+
 }  // namespace
 
 struct svs_stereo {
@@ -1071,8 +1095,8 @@ struct svs_stereo {
   DevBuf<int32_t> d_brow, d_npend;
   DevBuf<int2> d_pend;
   int debug = 0;                                      // SVS_STEREO_DEBUG=1 at create
-  int force_frame_ccl = 0;                            // SVS_STEREO_FRAME_CCL=1 at create: the whole-frame union-find path (tests compare the two)
-  int force_prefilter4 = 0;                           // SVS_STEREO_PREFILTER4=1 at create: the generic 4-pixel prefilter kernel on aligned input too (tests compare the two)
+  int force_frame_ccl = 0;                            // SVS_STEREO_FRAME_CCL=1 at create: the whole-frame union-find path (tests/test_gpu_stereo_paths.py compares the two)
+  int force_prefilter4 = 0;                           // SVS_STEREO_PREFILTER4=1 at create: the generic 4-pixel prefilter kernel on aligned input too (the same file compares the two)
   ~svs_stereo() { (void)hipStreamSynchronize(ctx->stream); }      // (runs before the buffers are freed)
 };
 
@@ -1080,8 +1104,12 @@ extern "C" int svs_stereo_create(svs_ctx *ctx, int w, int h, int max_batch, cons
   SVS_REQUIRE(ctx, ctx && prm && out && w > 0 && h > 0 && max_batch > 0);
   SVS_DEVICE(ctx);
   if (prm->sad_window != 7 || prm->min_disparity != 0 || prm->num_disparities != NDISP || prm->prefilter_cap < 1 || prm->prefilter_cap > 63 ||
-      w < NDISP + 2 * WSZ2 || w > 65535 || h < 2 || prm->speckle_window > 65535) {
+      w < NDISP + 2 * WSZ2 || h < 2 || prm->speckle_window > 65535) {
     ctx->err = "svs_stereo: only SADWindowSize 7, minDisparity 0, numberOfDisparities 32, preFilterCap 1..63, w >= 38 are supported";
+    return SVS_ERR_UNSUPPORTED;
+  }
+  if (w > STEREO_MAX_W) {
+    ctx->err = "svs_stereo: w <= " + std::to_string(STEREO_MAX_W) + " is supported (the left-right check and the whole-frame speckle filter hold a row in the 160 KB of LDS)";
     return SVS_ERR_UNSUPPORTED;
   }
   std::unique_ptr<svs_stereo> s(new svs_stereo());
@@ -1107,11 +1135,15 @@ extern "C" int svs_stereo_create(svs_ctx *ctx, int w, int h, int max_batch, cons
       s->strip_rows = rows; s->n_strips = div_up(h, rows);
       SVS_HIP(ctx, s->d_brow.alloc(2 * (size_t)s->n_strips * w * max_batch));
       SVS_HIP(ctx, s->d_pend.alloc(n));
-      SVS_HIP(ctx, s->d_npend.alloc((size_t)max_batch * s->n_strips + 32));
-      SVS_HIP(ctx, hipMemset(s->d_npend, 0, sizeof(int32_t) * ((size_t)max_batch * s->n_strips + 32)));
-      SVS_HIP(ctx, hipFuncSetAttribute((const void *)stereo_speckle_strip_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, rows * spk_row_bytes(w)));
+      SVS_HIP(ctx, s->d_npend.alloc((size_t)max_batch * s->n_strips));
+      SVS_HIP(ctx, hipMemset(s->d_npend, 0, sizeof(int32_t) * (size_t)max_batch * s->n_strips));
+      SVS_HIP(ctx, raise_dynamic_lds((const void *)stereo_speckle_strip_kernel, g_lds_strip, (size_t)rows * spk_row_bytes(w)));
     }
   }
+  if (validate_lds_bytes(w) > LDS_DEFAULT_BYTES)
+    SVS_HIP(ctx, raise_dynamic_lds((const void *)stereo_validate_kernel, g_lds_validate, validate_lds_bytes(w)));
+  if (ccl_runs_lds_bytes(w) > LDS_DEFAULT_BYTES)
+    SVS_HIP(ctx, raise_dynamic_lds((const void *)stereo_ccl_runs_kernel, g_lds_ccl_runs, ccl_runs_lds_bytes(w)));
   *out = s.release();
   return SVS_OK;
 }
@@ -1136,6 +1168,7 @@ extern "C" int svs_stereo_compute(svs_stereo *s, const uint8_t *d_left, int lstr
   const int w = s->w, h = s->h, width1 = w - NDISP + 1, n = w * h;
   const bool aligned16 = w % 16 == 0 && s->pitch % 16 == 0 && lstride % 4 == 0 && rstride % 4 == 0 && l_bstride % 4 == 0 && r_bstride % 4 == 0 &&
                          ((uintptr_t)d_left | (uintptr_t)d_right) % 4 == 0 && !s->force_prefilter4;
+  ++(aligned16 ? ctx->stereo_n_prefilter16 : ctx->stereo_n_prefilter4);
   if (aligned16)
     hipLaunchKernelGGL(stereo_prefilter16_kernel, dim3(div_up((s->pitch / 16) * div_up(h, 4), 256), 1, 2 * n_batch), dim3(256), 0, ctx->stream, S, d_left, lstride,
                        l_bstride, d_right, rstride, r_bstride);
@@ -1151,13 +1184,15 @@ extern "C" int svs_stereo_compute(svs_stereo *s, const uint8_t *d_left, int lstr
     SVS_LAUNCH_CHECK(ctx);
   }
   if (s->prm.disp12_max_diff >= 0) {
-    { const int R = w <= 2048 ? 4 : 1; hipLaunchKernelGGL(stereo_validate_kernel, dim3(div_up(h, R), n_batch), dim3(64 * R), sizeof(int) * 2 * R * (size_t)w, ctx->stream, S); }
+    { const int R = validate_rows(w); hipLaunchKernelGGL(stereo_validate_kernel, dim3(div_up(h, R), n_batch), dim3(64 * R), validate_lds_bytes(w), ctx->stream, S); }
+    if (validate_rows(w) == 1) ++ctx->stereo_n_validate_wide;
     SVS_LAUNCH_CHECK(ctx);
   }
   const bool ccl = s->prm.speckle_range >= 0 && s->prm.speckle_window > 0;
   const dim3 gp(div_up(n, 256), n_batch);
   if (ccl && s->strip_rows > 0 && !s->force_frame_ccl) {
-    S.strip_rows = s->strip_rows; S.n_strips = s->n_strips; S.brow = s->d_brow; S.pend = s->d_pend; S.npend = s->d_npend; S.err = s->d_npend + (((size_t)s->max_batch * s->n_strips + 1) & ~(size_t)1); S.timing = s->debug;
+    S.strip_rows = s->strip_rows; S.n_strips = s->n_strips; S.brow = s->d_brow; S.pend = s->d_pend; S.npend = s->d_npend; S.err = ctx->stereo_err; S.timing = s->debug;
+    ++ctx->stereo_n_strip_filter; ctx->stereo_n_strips += s->n_strips;
     hipLaunchKernelGGL(stereo_speckle_strip_kernel, dim3(s->n_strips, n_batch), dim3(SPK_THREADS), (size_t)s->strip_rows * spk_row_bytes(w), ctx->stream, S, d_disp, dstride, d_bstride);
     SVS_LAUNCH_CHECK(ctx);
     if (s->n_strips > 1) {
@@ -1183,7 +1218,8 @@ extern "C" int svs_stereo_compute(svs_stereo *s, const uint8_t *d_left, int lstr
     return SVS_OK;
   }
   if (ccl) {
-    hipLaunchKernelGGL(stereo_ccl_runs_kernel, dim3(h, n_batch), dim3(256), sizeof(int) * (2 * (size_t)w + 2 * (size_t)((w + 63) / 64)), ctx->stream, S);
+    ++ctx->stereo_n_frame_filter;
+    hipLaunchKernelGGL(stereo_ccl_runs_kernel, dim3(h, n_batch), dim3(256), ccl_runs_lds_bytes(w), ctx->stream, S);
     SVS_LAUNCH_CHECK(ctx);
     if (w % 4 == 0) hipLaunchKernelGGL(stereo_ccl_merge4_kernel, dim3(div_up(n, 1024), n_batch), dim3(256), 0, ctx->stream, S);
     else hipLaunchKernelGGL(stereo_ccl_merge_kernel, gp, dim3(256), 0, ctx->stream, S);

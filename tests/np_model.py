@@ -290,11 +290,18 @@ def stereo_filter_speckles(disp16, max_size=100, max_diff=32, new_val=-16):
     return out
 
 
-def stereo_bm(left, right):
-    lp, rp = stereo_prefilter(left), stereo_prefilter(right)
-    d16, cost = stereo_bm_core(lp, rp)
-    d16 = stereo_validate(d16, cost)
-    d16 = stereo_filter_speckles(d16)
+def stereo_bm(left, right, prm=None):
+    """prm: an svs_stereo_params (ctypes_types.StereoParams; SADWindowSize, minDisparity as the reference sets them), None = the reference's values.
+    The stages are chained as cv::StereoBM chains them: no left-right check for disp12MaxDiff < 0, no speckle filter for speckleWindowSize <= 0 or speckleRange < 0."""
+    cap, ndisp, texthr, uniq, window, rng, maxdiff = (31, 32, 10, 15, 100, 32, 1) if prm is None else (
+        prm.prefilter_cap, prm.num_disparities, prm.texture_threshold, prm.uniqueness_ratio, prm.speckle_window, prm.speckle_range, prm.disp12_max_diff)
+    assert prm is None or (prm.sad_window == 7 and prm.min_disparity == 0)
+    lp, rp = stereo_prefilter(left, cap), stereo_prefilter(right, cap)
+    d16, cost = stereo_bm_core(lp, rp, ndisp, 7, cap, texthr, uniq)
+    if maxdiff >= 0:
+        d16 = stereo_validate(d16, cost, ndisp, maxdiff)
+    if rng >= 0 and window > 0:
+        d16 = stereo_filter_speckles(d16, window, rng)
     return d16.astype(np.float32) / 16.0
 
 
