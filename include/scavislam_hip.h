@@ -680,6 +680,96 @@ int svs_loop_check_batch(svs_loop *l, int n_checks, const svs_loop_check *checks
 int svs_loop_set_timing(svs_loop *l, int on);
 int svs_loop_stage_times(svs_loop *l, float *ms);
 
+/* ---- back end: re-registration of a keyframe against the map.  Backend::localRegisterFrame (backend.cpp:190-199, 549-611) and Backend::globalLoopClosure
+   (:201-219, 830-1001) share one shape -- project map points into a root keyframe (pointsVisibleInRoot :472-546 / the loop at :853-893), matchAndAlign
+   (:725-784), gate and count (keyframesToRegister :615-722 / :904-961) -- and run here for a batch of requests as ONE chain of launches on the context's
+   stream: one staged upload, one download, no host round trip in between.  The graph bookkeeping around the call (framesInNeighborhood, the hash-set
+   deduplication of the point walk, registerKeyframes / addLoopClosure, new_edges_) stays with the caller; the MONO / Sim3 branches are not covered.
+   The cull and the counting are restated in tests/register_model.py (backend.cpp is not among the reference-compiled pins); the
+   matcher, the refinement and the gate inequality are the entry points above.
+   Chain, per request:
+     1. cull (:506-526 / :861-878).  Source point i is kept iff its kf_index names an entry of the request's keyframe table, anchor_level is 0 .. 2, that
+        entry has SVS_REG_KF_IN_WINDOW, and with T_root_from_anchor = T_root_from_world * inverse(T_anchor_from_w) (one 3x4 product per keyframe: rows
+        (a0 b0 + a1 b1) + a2 b2, translation added last; inverse = transpose and -(R^T t) summed left to right; no contraction), p = T_root_from_anchor * xyz_anchor
+        (row sums left to right), u = f (p0 / p2) + cx, v = f (p1 / p2) + cy with the camera of anchor_level: 0 <= (int)u < w and 0 <= (int)v < h, the casts
+        truncating toward zero (so u = -0.5 is kept).  There is NO depth test: a point behind the camera that projects into the frame is kept, and the matcher
+        answers it with SVS_MATCH_DEPTH.  The reference's cast is undefined for a non-finite projection; here a point whose |u| or |v| is not below 2^31 (NaN
+        included) is dropped.  Survivors keep the source order.  in_vertex_table (:537-543, :887-892) is set for root_kf and for the anchor of every survivor.
+        SVS_REG_LOCAL with fewer than covis_thr survivors: status 1 (:577).
+     2. FastGrid::detect at the request's stored thresholds (recomputeFastCorners :452-469), GuidedMatcher::match at search_radius[0] from the identity,
+        calcFastMotionOnly(PoseOptimizerParams(true, kernel_param, num_iter[0])), match at search_radius[1], calcFastMotionOnly(.., num_iter[1]) (:735-779).
+        Fewer than covis_thr observations after the first match: status 2 (:751), after the second: status 3 (:780).  Both refinements take min_obs = covis_thr:
+        where the reference returns false the pose stays as it was (the reference still refines behind :775 and discards the result).
+     3. gate (:644-646 / :928-930): |du|, |dv| < reproj_thr * 2^anchor_level and |du_right| < 3 reproj_thr at the refined pose -- the inequality of
+        svs_process_matched_points.  SVS_REG_LOCAL: every accepted observation counts for each keyframe of its point's observer row that is in the vertex table
+        and is no direct neighbour (:650-696): strength, and the halves u > w / 2 | else, v > h / 2 | else of the level-0 image; a keyframe qualifies with
+        strength >= covis_thr and every half >= covis_thr / 2 (integer division, :707-711); none qualifies: status 4 (:598).  SVS_REG_LOOP: the same counters for
+        the frame as a whole in entry 0 of the request's svs_reg_kf_stats row (:934-961).
+   A request that left at an exit costs nothing but its share of the launches: its candidate records are answered with SVS_MATCH_NO_ANCHOR from then on, its
+   accepted flags and counters are 0.  A request's outputs are a function of that request alone, bit for bit, whatever else is in the batch and on every repetition. */
+enum { SVS_REG_LOCAL = 0, SVS_REG_LOOP = 1 };
+enum { SVS_REG_OK = 0, SVS_REG_FEW_CANDIDATES = 1, SVS_REG_FEW_MATCHES_PASS1 = 2, SVS_REG_FEW_MATCHES_PASS2 = 3, SVS_REG_NOT_COVISIBLE = 4 };
+enum { SVS_REG_KF_IN_WINDOW = 1,        /* the keyframe is in graph_.double_window() (:506, :861) */
+       SVS_REG_KF_DIRECT_NEIGHBOR = 2 };/* it is the root or one of directNeighborsOf(root) (:433-449); SVS_REG_LOCAL only */
+typedef struct {
+  int32_t covis_thr;                   /* graph_.covis_thr() (15) */
+  int32_t search_radius[2];            /* 10, 4 (:746, :771); each <= 31 */
+  int32_t thr_mean, thr_std;           /* 22, 10 */
+  int32_t num_iter[2];                 /* 25, 15 (:758, :777) */
+  int32_t pad_;
+  double reproj_thr;                   /* REPROJ_THR 2.0 (:625, :904) */
+  double kernel_param;                 /* 2 */
+} svs_reg_params;
+void svs_reg_params_default(svs_reg_params *p);
+typedef struct {
+  int32_t mode;                        /* SVS_REG_LOCAL / SVS_REG_LOOP */
+  int32_t n_kf, n_src;
+  int32_t root_kf;                     /* the root keyframe's entry of h_kfs: its pyramid is the cur_frame of match (device pointers, as svs_match takes them) */
+  const float *d_root_disp;            /* DEVICE: the root frame's f32 disparity, level 0 */
+  int32_t root_disp_stride, pad_;
+  int32_t fast_thr[SVS_NUM_PYR_LEVELS][SVS_MAX_CELLS];      /* root_frame.cell_grid2d[level]: the stored per-cell thresholds, cells row-major; each >= 10 */
+  double T_root_from_world[12];        /* v_root.T_me_from_world / T_loop_from_world (:845) */
+  const svs_keyframe *h_kfs;           /* HOST [n_kf]: the vertex-table candidates with their poses, pyramids on the device */
+  const uint8_t *h_kf_flags;           /* HOST [n_kf]: SVS_REG_KF_* bits */
+  const svs_candidate_point *h_src;    /* HOST [n_src]: the points in the caller's iteration order, deduplicated; kf_index = entry of h_kfs of the anchor */
+  const int32_t *h_obs_begin;          /* HOST [n_src + 1], SVS_REG_LOCAL: row i of the observer table is h_obs_kf[h_obs_begin[i] .. h_obs_begin[i + 1]) */
+  const int32_t *h_obs_kf;             /* HOST: entries of h_kfs whose feature_table holds the point, each at most once per row; an entry outside the table is ignored */
+} svs_reg_request;
+typedef struct {
+  int32_t status;                      /* SVS_REG_* */
+  int32_t n_candidates, n_obs_pass1, n_obs_pass2, n_accepted;
+  int32_t n_qualified;                 /* keyframes that qualify (SVS_REG_LOOP: 0 or 1) */
+  double T_newroot_from_oldroot[12];   /* meaningful with status 0 and 4 */
+  double T_pass1[12];                  /* the pose behind the first refinement */
+  svs_pose_opt_stats stats_pass1, stats_pass2;
+} svs_reg_result;
+typedef struct {
+  int32_t strength;                    /* point_list.size() (:706) */
+  int32_t n_u_hi, n_u_lo, n_v_hi, n_v_lo;      /* u > w / 2, else, v > h / 2, else (:688-695, :936-943) */
+  int32_t qualifies;
+  int32_t in_vertex_table;
+  int32_t pad_;
+} svs_reg_kf_stats;
+typedef struct svs_reg svs_reg;
+/* cam: the level-0 StereoCamera.  At most max_requests requests per call, max_points source points, max_keyframes (<= 1024) table entries and max_observers
+   observer-table entries per request.  The handle owns its svs_fast (one slot per request, the grids of stereo_frontend.cpp:73-88), its scratch and a pinned
+   staging block */
+int svs_reg_create(svs_ctx *ctx, const svs_cam *cam, int max_requests, int max_points, int max_keyframes, int max_observers, svs_reg **out);
+int svs_reg_destroy(svs_reg *reg);
+/* BLOCKING.  Outputs (each optional, HOST): h_res [n_requests]; per candidate, rows of max_points: h_cand_src (index of the candidate in h_src; -1 behind
+   n_candidates), h_matches (the record of the second match; behind n_candidates SVS_MATCH_NO_ANCHOR), h_status_pass1 (the status of the first match),
+   h_accepted (the gate), h_matches_pass1 (the whole record of the first match: tests); per keyframe-table entry, rows of max_keyframes: h_kf_stats (zero behind
+   n_kf).  n_requests == 0: SVS_OK, nothing runs.  n_requests > max_requests or a request beyond the capacities of the handle: SVS_ERR_CAPACITY; a malformed
+   request (NULL table, root_kf outside it, a threshold below 10, a decreasing observer row): SVS_ERR_INVALID -- both before anything is launched */
+int svs_reg_register_batch(svs_reg *reg, int n_requests, const svs_reg_request *req, const svs_reg_params *prm, svs_reg_result *h_res, int32_t *h_cand_src,
+                           svs_match_result *h_matches, int32_t *h_status_pass1, int32_t *h_accepted, svs_reg_kf_stats *h_kf_stats,
+                           svs_match_result *h_matches_pass1);
+/* profiling: events between the stages of every svs_reg_register_batch; ms[SVS_REG_STAGES] of the last call: cull (+ the copy of the root frames where they do
+   not lie at one stride), FAST, match 1, refinement 1, match 2, refinement 2, gate */
+#define SVS_REG_STAGES 7
+int svs_reg_set_timing(svs_reg *reg, int on);
+int svs_reg_stage_times(svs_reg *reg, float *ms);
+
 /* ---- multi-GPU: the library-owned collective of the landmark-sharded back-end.  The reference has no
    distributed code; one process per GPU each creates a context and a communicator (RCCL, bound at run time) --------------*/
 typedef struct { char bytes[128]; } svs_unique_id;      /* = ncclUniqueId */

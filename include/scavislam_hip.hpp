@@ -12,6 +12,7 @@
 //   StereoFrontend  <- StereoFrontend::processFrame / processFirstFrame, scavislam/stereo_frontend.h:88-95 (one call per frame)
 //   SlamGraphBA     <- SlamGraph::optimize, scavislam/slam_graph.hpp:457-462
 //   FrameRectifier  <- FrameGrabber<StereoCamera>::intializeRectifier / rectifyFrame / depthToDisp, scavislam/frame_grabber.cpp:245-256, frame_grabber-impl.cpp:93-152
+//   BackendRegistration <- Backend::localRegisterFrame / globalLoopClosure, scavislam/backend.cpp:549-611, 830-1001 (one call per registration)
 //   Communicator    <- (no reference counterpart) landmark-sharded optimize over RCCL, SURVEY.md 8e
 //
 // One svs_ctx per calling thread (front-end on main, re-registration matcher/FAST + optimize on
@@ -698,6 +699,122 @@ class PlaceRecognizerGeom {
   uint64_t seed_;
   std::vector<int> keyframe_id_;
   svs_loop_result last_;
+  bool ok_;
+};
+
+// Backend::localRegisterFrame (backend.cpp:549-611) and Backend::globalLoopClosure (:830-1001) from the pose-graph walk onwards: the caller flattens the
+// reference's containers -- the candidate keyframes (larger_neighborhood + the anchors' vertices) into a table, the deduplicated point walk of pointsVisibleInRoot
+// (:480-498) / v_query.feature_table (:853) into a list whose kf_index names the anchor's table entry, the feature_table membership into observer rows -- and gets
+// back what registerKeyframes / addLoopClosure take.  One blocking call each; the cull, FastGrid::detect, both matches and refinements, the gate and the counting
+// run on the device in between.
+struct RegistrationFrame {               // the root keyframe (root_frame / loop_frame) as the call needs it
+  int table_entry;                       // its entry of the keyframe table: that entry's device pyramid is the frame matched into
+  const float *d_disp; int disp_stride;  // its disparity, DEVICE
+  std::vector<int32_t> cell_grid2d[SVS_NUM_PYR_LEVELS];      // root_frame.cell_grid2d: the stored FAST thresholds per level
+  double T_from_world[12];               // v_root.T_me_from_world / T_loop_from_world (:845)
+};
+struct RegistrationKeyframe {            // one candidate keyframe: keyframe_map_ entry + vertex pose + its sets
+  int frame_id;
+  svs_keyframe kf;
+  bool in_double_window;                 // IS_IN_SET(frame_id, graph_.double_window())
+  bool direct_neighbor;                  // IS_IN_SET(frame_id, directNeighborsOf(root)) (:433-449)
+};
+struct TrackPoint { int global_id; double uvu[3]; int anchor_level; };      // StereoGraph::MyTrackPoint: point id + ImageFeature<3>(uvu, anchor_level)
+class BackendRegistration {
+ public:
+  BackendRegistration(const Context &c, const svs_cam &stereo_cam, int max_points = 4096, int max_keyframes = 256, int max_observers = 65536, int covis_thr = 15)
+      : ctx_(c), reg_(nullptr), max_points_(max_points), max_keyframes_(max_keyframes) {
+    std::memset(&last_, 0, sizeof last_);
+    svs_reg_params_default(&prm_);
+    prm_.covis_thr = covis_thr;
+    ok_ = c.check(svs_reg_create(c.get(), &stereo_cam, 1, max_points, max_keyframes, max_observers, &reg_));
+  }
+  ~BackendRegistration() { if (reg_) svs_reg_destroy(reg_); }
+  BackendRegistration(const BackendRegistration &) = delete;
+  BackendRegistration &operator=(const BackendRegistration &) = delete;
+  bool ok() const { return ok_; }
+  svs_reg *get() const { return reg_; }
+  // bool Backend::localRegisterFrame(int rootframe_id): true when a neighbour qualifies.  points[i].kf_index = entry of `keyframes` of the anchor; row i of the
+  // observer table = obs_kf[obs_begin[i] .. obs_begin[i + 1]): the entries whose feature_table holds points[i].  neighborid_to_strength: (frame_id, strength) of
+  // the qualifying keyframes in table order; trackpoint_list: per qualifying keyframe, in that order, the accepted observations it shares, in point order
+  bool localRegisterFrame(const RegistrationFrame &root, const std::vector<RegistrationKeyframe> &keyframes, const std::vector<svs_candidate_point> &points,
+                          const std::vector<int32_t> &obs_begin, const std::vector<int32_t> &obs_kf, double T_newroot_from_oldroot[12],
+                          std::vector<std::pair<int, int> > *neighborid_to_strength, std::vector<TrackPoint> *trackpoint_list) {
+    if (neighborid_to_strength) neighborid_to_strength->clear();
+    if (trackpoint_list) trackpoint_list->clear();
+    if (obs_begin.size() != points.size() + 1) return false;
+    if (!run(SVS_REG_LOCAL, root, keyframes, points, &obs_begin, &obs_kf)) return false;
+    if (T_newroot_from_oldroot) std::memcpy(T_newroot_from_oldroot, last_.T_newroot_from_oldroot, sizeof last_.T_newroot_from_oldroot);
+    if (last_.status != SVS_REG_OK) return false;
+    for (size_t k = 0; k < keyframes.size(); ++k) {
+      if (!kf_stats_[k].qualifies) continue;
+      if (neighborid_to_strength) neighborid_to_strength->push_back(std::make_pair(keyframes[k].frame_id, (int)kf_stats_[k].strength));
+      for (int i = 0; trackpoint_list && i < last_.n_candidates; ++i) {
+        if (!accepted_[i]) continue;
+        const int s = cand_src_[i];
+        bool shared = false;
+        for (int32_t e = obs_begin[s]; e < obs_begin[s + 1] && !shared; ++e) shared = obs_kf[e] == (int32_t)k;
+        if (shared) trackpoint_list->push_back(track_point(points[s], matches_[i]));
+      }
+    }
+    return true;
+  }
+  // bool Backend::globalLoopClosure(const DetectedLoop&): loop_frame = the loop keyframe with T_from_world = T_query_from_loop^-1 * T_query_from_world (:845),
+  // points = v_query.feature_table in the caller's order.  trackpoint_list: the accepted observations, in point order (:945-950)
+  bool globalLoopClosure(const RegistrationFrame &loop_frame, const std::vector<RegistrationKeyframe> &keyframes, const std::vector<svs_candidate_point> &points,
+                         double T_newloop_from_oldloop[12], std::vector<TrackPoint> *trackpoint_list) {
+    if (trackpoint_list) trackpoint_list->clear();
+    if (!run(SVS_REG_LOOP, loop_frame, keyframes, points, nullptr, nullptr)) return false;
+    if (T_newloop_from_oldloop) std::memcpy(T_newloop_from_oldloop, last_.T_newroot_from_oldroot, sizeof last_.T_newroot_from_oldroot);
+    if (last_.status != SVS_REG_OK) return false;
+    for (int i = 0; trackpoint_list && i < last_.n_candidates; ++i)
+      if (accepted_[i]) trackpoint_list->push_back(track_point(points[cand_src_[i]], matches_[i]));
+    return true;
+  }
+  const svs_reg_result &lastResult() const { return last_; }                       // status says which exit was taken
+  const std::vector<svs_reg_kf_stats> &lastKeyframeStats() const { return kf_stats_; }
+  const std::vector<svs_match_result> &lastMatches() const { return matches_; }
+  const std::vector<int32_t> &lastAccepted() const { return accepted_; }
+  const std::vector<int32_t> &lastCandidates() const { return cand_src_; }
+
+ private:
+  static TrackPoint track_point(const svs_candidate_point &p, const svs_match_result &m) {
+    TrackPoint t;
+    t.global_id = p.point_id; t.anchor_level = p.anchor_level;
+    t.uvu[0] = m.obs[0]; t.uvu[1] = m.obs[1]; t.uvu[2] = m.obs[2];
+    return t;
+  }
+  bool run(int mode, const RegistrationFrame &root, const std::vector<RegistrationKeyframe> &keyframes, const std::vector<svs_candidate_point> &points,
+           const std::vector<int32_t> *obs_begin, const std::vector<int32_t> *obs_kf) {
+    if (!ok_ || keyframes.empty()) return false;
+    std::vector<svs_keyframe> kfs(keyframes.size());
+    std::vector<uint8_t> flags(keyframes.size());
+    for (size_t k = 0; k < keyframes.size(); ++k) {
+      kfs[k] = keyframes[k].kf;
+      flags[k] = (uint8_t)((keyframes[k].in_double_window ? SVS_REG_KF_IN_WINDOW : 0) | (keyframes[k].direct_neighbor ? SVS_REG_KF_DIRECT_NEIGHBOR : 0));
+    }
+    svs_reg_request q;
+    std::memset(&q, 0, sizeof q);
+    q.mode = mode; q.n_kf = (int32_t)kfs.size(); q.n_src = (int32_t)points.size(); q.root_kf = root.table_entry;
+    q.d_root_disp = root.d_disp; q.root_disp_stride = root.disp_stride;
+    for (int l = 0; l < SVS_NUM_PYR_LEVELS; ++l)
+      for (int c = 0; c < SVS_MAX_CELLS; ++c) q.fast_thr[l][c] = c < (int)root.cell_grid2d[l].size() ? root.cell_grid2d[l][c] : 25;
+    std::memcpy(q.T_root_from_world, root.T_from_world, sizeof q.T_root_from_world);
+    q.h_kfs = kfs.data(); q.h_kf_flags = flags.data(); q.h_src = points.empty() ? nullptr : points.data();
+    q.h_obs_begin = obs_begin ? obs_begin->data() : nullptr;
+    q.h_obs_kf = obs_kf && !obs_kf->empty() ? obs_kf->data() : nullptr;
+    cand_src_.assign((size_t)max_points_, -1); matches_.assign((size_t)max_points_, svs_match_result()); accepted_.assign((size_t)max_points_, 0);
+    kf_stats_.assign((size_t)max_keyframes_, svs_reg_kf_stats());
+    return ctx_.check(svs_reg_register_batch(reg_, 1, &q, &prm_, &last_, cand_src_.data(), matches_.data(), nullptr, accepted_.data(), kf_stats_.data(), nullptr));
+  }
+  const Context &ctx_;
+  svs_reg *reg_;
+  int max_points_, max_keyframes_;
+  svs_reg_params prm_;
+  svs_reg_result last_;
+  std::vector<int32_t> cand_src_, accepted_;
+  std::vector<svs_match_result> matches_;
+  std::vector<svs_reg_kf_stats> kf_stats_;
   bool ok_;
 };
 

@@ -561,6 +561,14 @@ FastView svs_fast_view_internal(const svs_fast *f) {
   return v;
 }
 
+// internal accessor for register.hip
+FastThrView svs_fast_thr_view_internal(svs_fast *f) {
+  FastThrView v{};
+  v.thr = f->P.thr; v.ncell_total = f->P.ncell_total; v.t_lo = f->P.t_lo; v.n_levels = f->P.n_levels; v.batch = f->batch;
+  for (int l = 0; l < f->P.n_levels; ++l) { v.cell_base[l] = f->P.lv[l].cell_base; v.ncell[l] = f->P.lv[l].gx * f->P.lv[l].gy; }
+  return v;
+}
+
 // internal accessor for seed.hip
 FastListView svs_fast_list_view_internal(const svs_fast *f) {
   FastListView v{};

@@ -4,6 +4,7 @@
 // ONE launch per frame batch (motion_only_fused_kernel<true>: gate and clouds as the tail of a stream's refinement workgroup).
 // The fused tail and the stand-alone kernels share their device functions (gate_stream, cloud_TQ, cloud_sample): identical bits.
 #include "common.h"
+#include "gate.h"
 #include "lm6.h"
 #include <algorithm>
 
@@ -125,25 +126,7 @@ __device__ __forceinline__ double mo_kernel(double delta, double b) {      // ps
   const double a = fabs(delta);
   return a < b ? delta * delta : 2 * b * a - b * b;
 }
-// f = obs - map_uvu(T xyz) (stereo_camera.cpp:37-44); J = SE3XYZ_STEREO::frameJac (transformations.h:424-447) if wanted
-template <bool JAC>
-__device__ __forceinline__ void mo_residual(const double *T, const svs_match_result &o, const svs_cam &cam, double *f, double *J) {
-  const double *q = o.xyz_actkey;
-  const double x = T[0] * q[0] + T[1] * q[1] + T[2] * q[2] + T[3];
-  const double y = T[4] * q[0] + T[5] * q[1] + T[6] * q[2] + T[7];
-  const double z = T[8] * q[0] + T[9] * q[1] + T[10] * q[2] + T[11];
-  const double fl = cam.f;
-  f[0] = o.obs[0] - (x / z * fl + cam.cx);
-  f[1] = o.obs[1] - (y / z * fl + cam.cy);
-  f[2] = o.obs[2] - ((x - cam.b) / z * fl + cam.cx);
-  if (JAC) {
-    const double ibz = 1. / z, ibz2 = 1. / (z * z);
-    const double A = -fl * ibz, B = -fl * ibz, C = fl * x * ibz2, D = fl * y * ibz2, E = fl * (x - cam.b) * ibz2;
-    J[0] = A; J[1] = 0; J[2] = C; J[3] = y * C; J[4] = z * A - x * C; J[5] = -y * A;
-    J[6] = 0; J[7] = B; J[8] = D; J[9] = -z * B + y * D; J[10] = -x * D; J[11] = x * B;
-    J[12] = A; J[13] = 0; J[14] = E; J[15] = y * E; J[16] = z * A - x * E; J[17] = -y * A;
-  }
-}
+// (mo_residual: gate.h)
 __device__ __forceinline__ double mo_weighted_sq(double *f, int robust, double b) {
   if (robust) {
     const double nrm = fmax(1e-10, sqrt(f[0] * f[0] + f[1] * f[1] + f[2] * f[2]));
@@ -440,7 +423,7 @@ __device__ __forceinline__ void gate_stream(const svs_match_result *__restrict__
       mo_residual<false>(T, res[i], cam, d, nullptr);          // uvu - se3xyz_stereo_.map(T_cur_from_actkey_, point)
       const int level = pts[i].anchor_level;
       const int factor = 1 << level;                             // zeroFromPyr_i(1, anchor_level)
-      if (fabs(d[0]) < mre * factor && fabs(d[1]) < mre * factor && fabs(d[2]) < 3. * mre) {
+      if (SVS_GATE_PASSES(d, factor, mre)) {
         const double *uvu = res[i].obs, *q = res[i].xyz_actkey;
         const int i2 = uvu[0] < half_w ? 0 : 1, j2 = uvu[1] < half_h ? 0 : 1;
         const int i3 = uvu[0] < third_w ? 0 : (uvu[0] < tt_w ? 1 : 2), j3 = uvu[1] < third_h ? 0 : (uvu[1] < tt_h ? 1 : 2);

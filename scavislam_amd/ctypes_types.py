@@ -170,3 +170,39 @@ class SeedRequest(C.Structure):
     """svs_seed_request: one new keyframe of one stream for svs_frontend_seed_keyframes"""
     _fields_ = [("stream", C.c_int32), ("mode", C.c_int32), ("kf_index", C.c_int32), ("first_point_id", C.c_int32),
                 ("T_newkey_from_cur", C.c_double * 12), ("seed", C.c_uint64), ("h_order", C.c_void_p * 3), ("n_order", C.c_int32 * 3), ("pad_", C.c_int32)]
+
+
+# ---- back end: re-registration of a keyframe (svs_reg_*; Backend::localRegisterFrame / globalLoopClosure, backend.cpp:549-611, 830-1001)
+REG_LOCAL, REG_LOOP = 0, 1
+REG_OK, REG_FEW_CANDIDATES, REG_FEW_MATCHES_PASS1, REG_FEW_MATCHES_PASS2, REG_NOT_COVISIBLE = range(5)
+REG_KF_IN_WINDOW, REG_KF_DIRECT_NEIGHBOR = 1, 2
+REG_STAGES = 7
+
+
+class RegParams(C.Structure):
+    """svs_reg_params: covis_thr, the two search radii / iteration counts of matchAndAlign (backend.cpp:735-779), REPROJ_THR (:625)."""
+    _fields_ = [("covis_thr", C.c_int32), ("search_radius", C.c_int32 * 2), ("thr_mean", C.c_int32), ("thr_std", C.c_int32), ("num_iter", C.c_int32 * 2),
+                ("pad_", C.c_int32), ("reproj_thr", C.c_double), ("kernel_param", C.c_double)]
+
+    @classmethod
+    def reference(cls, covis_thr=15):
+        return cls(covis_thr, (C.c_int32 * 2)(10, 4), 22, 10, (C.c_int32 * 2)(25, 15), 0, 2.0, 2.0)
+
+
+class RegRequest(C.Structure):
+    """svs_reg_request: one root keyframe with its keyframe table, source points and (local mode) observer table"""
+    _fields_ = [("mode", C.c_int32), ("n_kf", C.c_int32), ("n_src", C.c_int32), ("root_kf", C.c_int32),
+                ("d_root_disp", C.c_void_p), ("root_disp_stride", C.c_int32), ("pad_", C.c_int32),
+                ("fast_thr", (C.c_int32 * SVS_MAX_CELLS) * 3), ("T_root_from_world", C.c_double * 12),
+                ("h_kfs", C.c_void_p), ("h_kf_flags", C.c_void_p), ("h_src", C.c_void_p), ("h_obs_begin", C.c_void_p), ("h_obs_kf", C.c_void_p)]
+
+
+class RegResult(C.Structure):
+    _fields_ = [("status", C.c_int32), ("n_candidates", C.c_int32), ("n_obs_pass1", C.c_int32), ("n_obs_pass2", C.c_int32), ("n_accepted", C.c_int32),
+                ("n_qualified", C.c_int32), ("T_newroot_from_oldroot", C.c_double * 12), ("T_pass1", C.c_double * 12),
+                ("stats_pass1", PoseOptStats), ("stats_pass2", PoseOptStats)]
+
+
+REG_KF_STATS_DTYPE = np.dtype([("strength", "<i4"), ("n_u_hi", "<i4"), ("n_u_lo", "<i4"), ("n_v_hi", "<i4"), ("n_v_lo", "<i4"), ("qualifies", "<i4"),
+                               ("in_vertex_table", "<i4"), ("pad_", "<i4")])
+assert REG_KF_STATS_DTYPE.itemsize == 32
