@@ -129,8 +129,9 @@ int svs_ctx_sync(svs_ctx *ctx);
    front end enqueues FAST / block matching on a side stream beside the dense tracker; 0: everything on the context's stream),
    "xcd_swizzle" (default 1: tile kernels whose neighbours share image lines -- FAST score, pyramid, block matching, the four-points-per-wave matcher -- take their
    blocks in XCD-contiguous order; 0: the dispatcher's round robin),
-   "trk_flat" (default 1: batches of more than one stream per CU run the flat tracker kernel -- the sweep inlined, the LM state in LDS; 0: the
-   round-5 kernel, same bits), "trk_split" (default 10: in such batches a stream still iterating after that many trials on the finest level is
+   "trk_balance" (default 1: batches of two or more streams per CU launch the tracker's workgroups in the order of the LM work their streams needed in the
+   last frame; 0: stream order; larger values count as 1; initial value from SVS_TRK_BALANCE), "trk_split" (default 10: in batches of more than one stream
+   per CU, which run the flat tracker kernel, a stream still iterating after that many trials on the finest level is
    finished by a second launch with eight workgroups per stream -- same accept decisions, poses equal to 1e-12, a stream's bits independent of the rest of its batch; 0: one launch).
    A context and every handle made from it are used by ONE thread at a time. */
 int svs_ctx_set_option(svs_ctx *ctx, const char *name, int value);

@@ -24,7 +24,7 @@ struct svs_ctx {
   DevBuf<void> match_scratch;
   // switches read ONCE at svs_ctx_create (debug / experiment only; never per call)
   int trk_nwg = 0;            // SVS_TRK_NWG: workgroups per stream of the latency-mode quarter-grid tracker (0 = automatic)
-  int trk_balance = 1;        // big batches (dense.hip, BAL): 1 = grid order by the last frame's LM work, 2 = also 2..4 workgroups for the longest streams (experimental), 0 = stream order
+  int trk_balance = 1;        // "trk_balance" / SVS_TRK_BALANCE, big batches (dense.hip, BAL): 1 = grid order by the last frame's LM work, 0 = stream order
   int trk_regs = 0;           // SVS_TRK_ONE_PER_CU (1) / SVS_TRK_TWO_PER_CU (2): register budget of that tracker (0 = automatic)
   int full_nwg = 0;           // SVS_FULL_NWG: workgroups per stream of the full-resolution tracker (0 = automatic)
   int match_legacy = 0;       // "match_legacy": 0 = four points per wave (match_kernel3), 1 = the round-1/2 kernel (one wave per point, ballots), 2 = one wave per point with the lean scan
@@ -37,8 +37,7 @@ struct svs_ctx {
   int trk_seq_chi2 = 0;       // "trk_seq_chi2": the quarter-grid tracker decides accept / reject on the reference's own sequential f32 chi2 sums (dense.hip; slow: parity runs)
   int trk_lazy_chi2 = 1;      // "trk_lazy_chi2" (default): the same decisions at full speed -- the f64 sums decide wherever their difference is outside the rigorous error bound of the
                               // reference's float sums, and inside it the float sums are formed bit for bit without the sequential chain (seqsum.h).  0: f64 sums alone (rounds 1-4)
-  int trk_flat = 1;           // "trk_flat": big batches run the flat state-machine tracker kernel (dense.hip, round 6: the sweep inlined, LM state in LDS); 0: the round-5 kernel (sweep as a call) -- same bits
-  int trk_split = 10;         // "trk_split" (with trk_flat): K -- a stream of a big batch that is still iterating after K trials on the finest level parks and is finished by a
+  int trk_split = 10;         // "trk_split": K -- a stream of a big batch that is still iterating after K trials on the finest level parks and is finished by a
                               // second launch with several workgroups per stream (dense.hip: the continuation launch); 0: off.  Measured on the bench batch (512
                               // streams): tracker stage 1.40 ms unsplit, 1.30 at K = 8..9, 1.33 at K = 10; the whole step 2.66-2.69 unsplit, 2.75 at K = 8 (the side
                               // stream's FAST no longer finds the tail to run in), 2.63 at K = 10

@@ -15,6 +15,7 @@
 #include "lm6.h"
 #include "seqsum.h"
 #include <algorithm>
+#include <climits>
 
 namespace {
 
@@ -50,9 +51,9 @@ struct LevelArgs {
   int c8stride;
 };
 
-// The same with the address space of every pointer spelled out (global memory).  The tracker's sweep is a real call (track_pass_call): its operands come out of
-// LDS, and a pointer that has been through memory is a flat pointer to the compiler -- every access a flat_load that also probes the LDS aperture and counts on
-// both wait counters.
+// The same with the address space of every pointer spelled out (global memory).  The flat tracker kernel's sweep takes its operands out of LDS
+// (track_pass_from_lds), and a pointer that has been through memory is a flat pointer to the compiler -- every access a flat_load that also probes the LDS
+// aperture and counts on both wait counters.
 #define SVS_AS1 __attribute__((address_space(1)))
 typedef float svs_f4 __attribute__((ext_vector_type(4)));
 struct LevelArgsG {
@@ -318,7 +319,6 @@ struct TrackArgs {
 
 // tuning constants, as measured (profiles/r3_notes.md, r5_notes.md)
 constexpr int TRK_THREADS = 512;      // lanes per workgroup
-constexpr int TRK_MINW_BIG = 4;       // waves per SIMD the big-batch instantiations are built for (4: 128 VGPRs, two 512-lane workgroups per CU)
 constexpr int TRK_UNROLL = 1;         // samples per lane and trip of the sweep (2: the 128-register build spills 126 registers)
 constexpr bool TRK_T_SCALAR = true;   // the pose of a sweep in scalar registers instead of 24 vector registers
 
@@ -390,12 +390,11 @@ __device__ __forceinline__ void track_pass(const LA &L_in, const double *T_in, d
   block_reduce<TRK_THREADS / 64>(a, s_part, s_out);
 }
 
-// ---- the sweep as a CALL ---------------------------------------------------------------------------------------------------------------------------------
-// The tracker kernel is built for 128 vector registers (two 512-lane workgroups per CU) and the sweep alone fills them: 28 f64 accumulators, the sample in
-// flight, the prefetched next one.  Inlined into the LM loop it shared its register allocation with everything that loop keeps alive -- per-stream pointers, the
-// records, the accept test -- and paid with spills inside the loop over the samples and reloads in every pass.  As a function of its own the sweep gets the whole
-// budget: the caller leaves its operands in LDS (uniform: read back into scalar registers), keeps its own state across the call, and nothing of the LM loop is
-// live inside.  Results in g_s_out as before.
+// ---- the sweep with its operands in LDS --------------------------------------------------------------------------------------------------------------------
+// The big-batch kernel (dense_track_batch_kernel) is built for 128 vector registers (two 512-lane workgroups per CU) and the sweep alone fills them: 28 f64
+// accumulators, the sample in flight, the prefetched next one.  Whatever else is alive across the sweep shares that allocation and spills inside the loop over
+// the samples.  So one lane leaves the sweep's operands in LDS (g_pa), and the sweep reads them back into scalar registers (they are uniform): nothing of the
+// LM loop is live inside.  Results in g_s_out.
 struct PassArgs { LevelArgs L; double T[12]; float *t_buf; int wg, nwg; };
 __shared__ PassArgs g_pa;
 __shared__ double g_s_part[TRK_THREADS / 64][NSUM + 1];
@@ -421,8 +420,6 @@ __device__ __forceinline__ void track_pass_from_lds() {      // a sweep with its
   const int nwg = uni_i32(g_pa.nwg), first = uni_i32(g_pa.wg) * TRK_THREADS + (int)threadIdx.x;
   track_pass<true, U8SRC, TM, LevelArgsG>(L, g_pa.T, g_s_part, g_s_out, g_iplut, first, nwg, uni_ptr(g_pa.t_buf));
 }
-template <bool U8SRC, int TM>
-__device__ __noinline__ void track_pass_call() { track_pass_from_lds<U8SRC, TM>(); }
 
 // "trk_seq_chi2": the reference's `float chi2`, summed the way the reference sums it -- one f32 accumulator, samples in row-major order (dense_tracking.cpp:229-262,
 // 341-367).  Near convergence chi2 - new_chi2 is below the rounding noise of these 19 200-term sums, so the accept test of the last LM steps of a level is decided by
@@ -701,14 +698,14 @@ struct TrackMulti {
   double *part;                                   // [batch][2][nwg][32] partial sums of the shared sweeps, by sweep parity (latency mode: [batch][2][nwg][64] flagged words)
   unsigned *bar; int fail_off;                    // [batch] arrival counters + [batch] failure flags at bar + fail_off (zeroed before the launch)
   double *bcast;                                  // [batch][16]: the pose after the coarsest level + a ready word (zeroed before the launch)
-  const int *map; const unsigned char *nwg_of;    // BAL only: workgroup -> (stream << 4 | part), workgroups per stream
+  const int *map;                                 // the ordered launch of a big batch: workgroup -> (stream << 4)
   float *terms; size_t terms_b;                   // the float terms of the accepted and of the trial pass, [batch][2][terms_b] (null: accept test on the f64 sums alone)
   unsigned *seq_stats;                            // [0] exact sums formed, [1] fallbacks to the chain
   int terms_only;                                 // kernel A/B: the stores of the terms without the sums
   int *work16;                                    // (optional, flat kernel): [batch] the stream's passes counted as 16 / 4 / 1 per sweep of level 0 / 1 / 2
 };
 
-// ---- the LM step, written once: both tracker kernels below (the round-5 kernel with its sweep as a call, the flat kernel of big batches) inline these ----------------
+// ---- the LM step, written once: both tracker kernels below (the nested-loop kernel, the flat kernel of big batches) inline these ---------------------------------
 // the operands of a stream's sweeps of one level: the level's cloud and images at the stream's batch offsets
 template <bool U8SRC>
 __device__ __forceinline__ LevelArgs stream_level(const TrackArgs &A, int level, int slot) {
@@ -803,21 +800,11 @@ __device__ __forceinline__ TrkVerdict track_accept(const TrackMulti &G, int slot
   return V;
 }
 
-// MINW = minimum waves per SIMD the register allocation must allow: 2 (<= 256 VGPRs; the kernel takes 147: one 8-wave
-// workgroup per CU) when there is at most one stream per CU, 4 (<= 128 VGPRs, a few spills, two workgroups per CU) for
-// bigger batches, where the second resident workgroup hides the first one's dependent chains: 0.55 -> 0.45 ms per 256 streams.
-// BAL ("trk_balance", big batches): MULTI with a per-stream number of workgroups.  All streams of a big batch are resident at once (two workgroups per
-// CU) and the launch lasts as long as the stream with the most LM passes (bench batch: 5.6 .. 17.8 level-0 sweeps per stream, mean 8.8).  The streams that needed
-// the most sweeps in the LAST frame get 2 .. 4 workgroups each (trk_assign_kernel), placed first in the grid so that they are resident together; the
-// single-workgroup streams follow in order of decreasing work, the shortest ones start in the slots the first finishers leave.
-template <bool U8SRC, bool MULTI, int MINW, bool SEQ = false, bool BAL = false>      // SEQ: "trk_seq_chi2" (its own instantiation: the hot ones keep their register budget)
-__global__ __launch_bounds__(TRK_THREADS, MINW) void dense_track_cpu_sem_kernel(TrackArgs A, double *__restrict__ T_io, int *__restrict__ passes_out, TrackMulti G) {
-  static_assert(!BAL || !SEQ, "BAL: grid order (and, with MULTI, workgroups per stream) from the assignment tables");
-  int bal_entry = 0;
-  if constexpr (BAL) {
-    bal_entry = G.map[blockIdx.x];
-    if (bal_entry < 0 || (!MULTI && (bal_entry & 15) != 0)) return;      // idle workgroup / a sibling of a table made for the split variant: the order-only variant runs part 0 alone
-  }
+// ---- the nested-loop kernel: latency mode (MULTI), at most one stream per CU, "trk_seq_chi2" (SEQ) -----------------------------------------------------------
+// Built for two waves per SIMD (<= 256 VGPRs; the kernel takes 147: one 8-wave workgroup per CU): room for the sweep inline in the level / iteration loops
+// beside everything those loops keep alive.  Batches of more than one stream per CU run dense_track_batch_kernel below, which is held to this one bit for bit.
+template <bool U8SRC, bool MULTI, bool SEQ = false>      // SEQ: "trk_seq_chi2" (its own instantiation: the hot ones keep their register budget)
+__global__ __launch_bounds__(TRK_THREADS, 2) void dense_track_cpu_sem_kernel(TrackArgs A, double *__restrict__ T_io, int *__restrict__ passes_out, TrackMulti G) {
   double (&s_out)[NSUM + 1] = g_s_out;
   float (&s_iplut)[256] = g_iplut;
   __shared__ double s_T[12], s_Tn[12], s_x[6], s_H[27], s_Tj[3][12];
@@ -825,50 +812,45 @@ __global__ __launch_bounds__(TRK_THREADS, MINW) void dense_track_cpu_sem_kernel(
   if (threadIdx.x == 0) { s_failed = false; if (!SEQ) g_seq_sh.fell_back = 0; }
   constexpr int TM = SEQ ? 1 : (MULTI ? 2 : 1);      // the terms of a pass: plain stores, or past the caches when sibling workgroups read them
   unsigned n_exact = 0, n_decisions = 0, n_old_sums = 0;      // exact float sums formed by this workgroup; near-ties of this stream so far / those of them that needed the accepted pass's sum as well (shared_near_sums)
-  const int slot = BAL ? (bal_entry >> 4) : (MULTI ? blockIdx.y : blockIdx.x), wg = BAL ? (bal_entry & 15) : (MULTI ? blockIdx.x : 0);
-  const int nwg = !MULTI ? 1 : (BAL ? (int)G.nwg_of[slot] : (int)gridDim.x);
+  const int slot = MULTI ? blockIdx.y : blockIdx.x, wg = MULTI ? blockIdx.x : 0;
+  const int nwg = MULTI ? (int)gridDim.x : 1;
   const int first = wg * TRK_THREADS + threadIdx.x;
   int sweep = 0;
   auto all_workgroups = [&]() {      // s_out[0..NSUM] <- sum over the workgroups of this stream
     if (!MULTI) return;
-    if (BAL && nwg == 1) return;
-    if constexpr (!BAL) {
-      // Round 6: every 8-byte word carries its own flag (4 bytes of data + the sweep number: what NCCL calls the LL protocol).  A workgroup publishes its 29 sums as 58
-      // such words and reads the others' the moment they carry this sweep's number: ONE store-to-load hop between workgroups -- no drain of the store queue, no arrival
-      // counter (a device-scope read-modify-write), no second wait.  Rounds 2-5: stores, s_waitcnt vmcnt(0), barrier, counter += 1, poll the counter, barrier, loads --
-      // 4-5 us of a 10 us pass in latency mode.  Two parities of buffers: a word is overwritten two sweeps later, which its writer can only reach after every sibling has
-      // consumed this sweep (it needs their next sweep's words to get there).  The buffers are zeroed before the launch (sweep numbers start at 1).
-      const unsigned ep = (unsigned)(++sweep);
-      unsigned long long *buf = reinterpret_cast<unsigned long long *>(G.part) + ((size_t)slot * 2 + (ep & 1u)) * (size_t)nwg * 64;
-      bool timed_out = false;
-      if (threadIdx.x < 2 * (NSUM + 1)) {
-        const int k = threadIdx.x;
-        const double mine = s_out[k >> 1];
-        const unsigned my_half = (k & 1) ? (unsigned)__double2hiint(mine) : (unsigned)__double2loint(mine);
-        __hip_atomic_store(buf + (size_t)wg * 64 + k, ((unsigned long long)ep << 32) | my_half, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        double acc = 0;
-        long budget = 1l << 24;
-        for (int w = 0; w < nwg; ++w) {                      // workgroup order: the same sum in every workgroup
-          unsigned h = my_half;
-          if (w != wg) {
-            unsigned long long v = __hip_atomic_load(buf + (size_t)w * 64 + k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            while ((unsigned)(v >> 32) != ep && budget > 0) { __builtin_amdgcn_s_sleep(1); --budget; v = __hip_atomic_load(buf + (size_t)w * 64 + k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-            if ((unsigned)(v >> 32) != ep) timed_out = true;
-            h = (unsigned)v;
-          }
-          const unsigned other = (unsigned)__shfl_xor((int)h, 1, 64);      // even lane: the low half is mine, the high half my neighbour's
-          acc += __hiloint2double((int)((k & 1) ? h : other), (int)((k & 1) ? other : h));
+    // Round 6: every 8-byte word carries its own flag (4 bytes of data + the sweep number: what NCCL calls the LL protocol).  A workgroup publishes its 29 sums as 58
+    // such words and reads the others' the moment they carry this sweep's number: ONE store-to-load hop between workgroups -- no drain of the store queue, no arrival
+    // counter (a device-scope read-modify-write), no second wait.  Rounds 2-5: stores, s_waitcnt vmcnt(0), barrier, counter += 1, poll the counter, barrier, loads --
+    // 4-5 us of a 10 us pass in latency mode.  Two parities of buffers: a word is overwritten two sweeps later, which its writer can only reach after every sibling has
+    // consumed this sweep (it needs their next sweep's words to get there).  The buffers are zeroed before the launch (sweep numbers start at 1).
+    const unsigned ep = (unsigned)(++sweep);
+    unsigned long long *buf = reinterpret_cast<unsigned long long *>(G.part) + ((size_t)slot * 2 + (ep & 1u)) * (size_t)nwg * 64;
+    bool timed_out = false;
+    if (threadIdx.x < 2 * (NSUM + 1)) {
+      const int k = threadIdx.x;
+      const double mine = s_out[k >> 1];
+      const unsigned my_half = (k & 1) ? (unsigned)__double2hiint(mine) : (unsigned)__double2loint(mine);
+      __hip_atomic_store(buf + (size_t)wg * 64 + k, ((unsigned long long)ep << 32) | my_half, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      double acc = 0;
+      long budget = 1l << 24;
+      for (int w = 0; w < nwg; ++w) {                      // workgroup order: the same sum in every workgroup
+        unsigned h = my_half;
+        if (w != wg) {
+          unsigned long long v = __hip_atomic_load(buf + (size_t)w * 64 + k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+          while ((unsigned)(v >> 32) != ep && budget > 0) { __builtin_amdgcn_s_sleep(1); --budget; v = __hip_atomic_load(buf + (size_t)w * 64 + k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+          if ((unsigned)(v >> 32) != ep) timed_out = true;
+          h = (unsigned)v;
         }
-        if (!(k & 1)) s_out[k >> 1] = acc;                     // (this wave published from s_out before any lane of it writes here)
+        const unsigned other = (unsigned)__shfl_xor((int)h, 1, 64);      // even lane: the low half is mine, the high half my neighbour's
+        acc += __hiloint2double((int)((k & 1) ? h : other), (int)((k & 1) ? other : h));
       }
-      // a sibling never published (not resident: the device is shared with other work): raise the stream's failure flag -- the pose is left as it came in, passes_out reports -1
-      if (__syncthreads_or(timed_out ? 1 : 0)) {
-        if (threadIdx.x == 0) { __hip_atomic_store(G.bar + G.fail_off + slot, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); s_failed = true; }
-        __syncthreads();
-      }
-      return;
+      if (!(k & 1)) s_out[k >> 1] = acc;                     // (this wave published from s_out before any lane of it writes here)
     }
-    sum_workgroups(G, slot, G.part + ((size_t)slot * 2 + (sweep & 1)) * 4 * 32, wg, nwg, sweep, s_failed);      // (BAL: up to four workgroups per stream)
+    // a sibling never published (not resident: the device is shared with other work): raise the stream's failure flag -- the pose is left as it came in, passes_out reports -1
+    if (__syncthreads_or(timed_out ? 1 : 0)) {
+      if (threadIdx.x == 0) { __hip_atomic_store(G.bar + G.fail_off + slot, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); s_failed = true; }
+      __syncthreads();
+    }
   };
   if (threadIdx.x < 12) s_T[threadIdx.x] = T_io[(size_t)slot * 12 + threadIdx.x];
   for (int i = threadIdx.x; i < 256; i += TRK_THREADS) s_iplut[i] = (float)((1. / 255.) * i);
@@ -884,7 +866,7 @@ __global__ __launch_bounds__(TRK_THREADS, MINW) void dense_track_cpu_sem_kernel(
   for (int level = 2; level >= 0; --level) {
     // MULTI: the coarsest level (1/16 of the samples: less than one per lane and workgroup) is run by workgroup 0 ALONE -- a sweep of it is
     // shorter than the cross-workgroup exchange that sharing it would cost -- and the others pick the pose up when it is done
-    const bool solo = MULTI && level == 2 && !(BAL && nwg == 1);
+    const bool solo = MULTI && level == 2;
     if (solo && wg != 0) {
       if (threadIdx.x == 0) {
         long spin = 0;
@@ -901,20 +883,9 @@ __global__ __launch_bounds__(TRK_THREADS, MINW) void dense_track_cpu_sem_kernel(
     const int lnwg = solo ? 1 : nwg;
     const LevelArgs L = stream_level<U8SRC>(A, level, slot);
     const int n_lvl = (L.cam.w / 4) * (L.cam.h / 4);
-    // the operands of this level's sweeps (track_pass_call): the level, which workgroups share it; pose and term buffer follow before each sweep
-    __syncthreads();
-    if (MINW != 2 && threadIdx.x == 0) { g_pa.L = L; g_pa.wg = solo ? 0 : wg; g_pa.nwg = lnwg; }
+    __syncthreads();      // (between the levels: everybody is through with the last trial's sums and state)
     auto sweep_at = [&](const double *s_pose, float *t_buf) {      // s_pose: 12 doubles in LDS
-      if constexpr (MINW == 2) {
-        // one workgroup per CU (latency mode, small batches): 256 registers to live in -- the sweep inline, as it always was; its passes are a few
-        // microseconds long and a call (operands through LDS, callee-saved registers to scratch and back) would cost as much again
-        track_pass<true, U8SRC, TM>(L, s_pose, g_s_part, g_s_out, g_iplut, solo ? (int)threadIdx.x : first, lnwg, t_buf);
-      } else {
-        if (threadIdx.x < 12) g_pa.T[threadIdx.x] = s_pose[threadIdx.x];
-        if (threadIdx.x == 12) g_pa.t_buf = t_buf;
-        __syncthreads();
-        track_pass_call<U8SRC, TM>();
-      }
+      track_pass<true, U8SRC, TM>(L, s_pose, g_s_part, g_s_out, g_iplut, solo ? (int)threadIdx.x : first, lnwg, t_buf);
     };
     // SEQ: one term buffer, every sum by the chain ("trk_seq_chi2"; never MULTI: G.part carries the buffer and fail_off its stream stride).
     // Default: two buffers -- the terms of the accepted pass (tb[cur]) and of the trial -- for the sums the accept test cannot decide in f64 (seqsum.h)
@@ -996,14 +967,13 @@ __global__ __launch_bounds__(TRK_THREADS, MINW) void dense_track_cpu_sem_kernel(
   }
 }
 
-// ---- big batches, round 6: the LM loop as a flat state machine around ONE inlined sweep ------------------------------------------------------------------------
-// dense_track_cpu_sem_kernel<., false, 4> calls its sweep (track_pass_call): the sweep fills the 128-register budget by itself, so as a callee it saves and restores every
-// callee-saved register it touches -- 29 dwords per lane and call, 59 KB per workgroup each way, 18 calls per frame: 0.55 GB written (and read back) per 512-stream batch for
-// nothing (round 5's rocprof: WRITE_SIZE 996 MB against 0.34 GB of terms).  Inlining it into the level / iteration loops was worse: everything those loops keep alive (sums,
-// flags, buffers: uniform values the compiler cannot prove uniform) shared the sweep's allocation and spilled inside the loop over the samples.
-// Here the LM state of the stream lives in LDS (TrkState: one lane writes it, everybody reads what it needs), the kernel is ONE loop { sweep; step }, and nothing of the step
-// is alive while the sweep runs: no call on the hot path, no callee-saved traffic, no spills in the sweep.  Same sweep, same sums, same solve, same decisions as the kernel
-// above: bit-identical results (tests/test_gpu_frontend.py::test_flat_tracker_kernel_is_bit_identical).
+// ---- big batches: the LM loop as a flat state machine around ONE inlined sweep ---------------------------------------------------------------------------------
+// Two 512-lane workgroups per CU (the second one hides the first one's dependent chains: 0.55 -> 0.45 ms per 256 streams) leave 128 vector registers, and the sweep
+// fills them by itself.  Inlined into level / iteration loops like the kernel above's, everything those loops keep alive (sums, flags, buffers: uniform values the
+// compiler cannot prove uniform) shares the sweep's allocation and spills inside the loop over the samples; as a callee the sweep saves and restores every callee-saved
+// register it touches, 29 dwords per lane and call.  So the LM state of the stream lives in LDS (TrkState: one lane writes it, everybody reads what it needs), the kernel
+// is ONE loop { sweep; step }, and nothing of the step is alive while the sweep runs: no call on the hot path, no callee-saved traffic, no spills in the sweep.  Same
+// sweep, same sums, same solve, same decisions as the kernel above: bit-identical results (tests/test_gpu_frontend_batch.py::test_tracker_grid_order_does_not_change_results).
 struct TrkState {
   double S_old; float chi2, seq_old;
   int work16;                                                        // passes so far, weighted 16 / 4 / 1 by level (what trk_assign_kernel orders the next frame's grid by)
@@ -1169,13 +1139,14 @@ __device__ __forceinline__ void track_batch_stream(const TrackArgs &A, double *_
     if (g_seq_sh.fell_back) atomicAdd(G.seq_stats + 1, 1u);
   }
 }
+// (four waves per SIMD: 128 VGPRs, two 512-lane workgroups per CU)
 template <bool U8SRC, bool BAL, int CONT>      // CONT 0: first launch (BAL: grid order from the table); 1: the continuation (grid = CONT_MAX_NWG x groups: launch_batch_tracker)
-__global__ __launch_bounds__(TRK_THREADS, TRK_MINW_BIG) void dense_track_batch_kernel(TrackArgs A, double *__restrict__ T_io, int *__restrict__ passes_out, TrackMulti G, TrackCont C) {
+__global__ __launch_bounds__(TRK_THREADS, 4) void dense_track_batch_kernel(TrackArgs A, double *__restrict__ T_io, int *__restrict__ passes_out, TrackMulti G, TrackCont C) {
   if constexpr (CONT == 0) {
     int slot = blockIdx.x;
     if constexpr (BAL) {
       const int e = G.map[blockIdx.x];
-      if (e < 0 || (e & 15) != 0) return;      // idle workgroup / a sibling entry of a table made for the split variant
+      if (e < 0) return;      // (the table is device memory this kernel does not own)
       slot = e >> 4;
     }
     track_batch_stream<U8SRC, false>(A, T_io, passes_out, G, C, slot, 0, 1);
@@ -1278,109 +1249,31 @@ extern "C" int svs_dense_pass_cpu_sem(svs_ctx *ctx, const float *d_cloud, size_t
 }
 
 namespace {
-// "trk_balance": workgroups per stream from the work of the last frame, and the grid order (one workgroup, B <= 4096 streams).
-//   nwg_b = min(4, ceil(w_b / M)), M = 1.2 x the mean work, raised in steps of 8 % until the extra workgroups fit x_max and the multi-workgroup streams fit
-//   the resident slots (a function of the multiset of works only: streams with equal history get equal treatment, e.g. replicas of one stream);
-//   grid: the multi-workgroup streams in index order, then the others by decreasing work (ties: index), then -1 (idle workgroups).
+// "trk_balance": the grid order of the next frame's ordered launch (one workgroup, B <= 4096 streams): the streams by decreasing LM work of this frame, ties by
+// index.  All streams of a big batch are resident at once (two workgroups per CU) and the launch lasts as long as its longest stream; the shortest streams start
+// last, in the slots the first finishers leave.  work16 [B]: each stream's work in 1/16 level-0 sweeps, left by the flat tracker kernel (all zero: stream order).
+// map [B]: position in the grid -> (stream << 4), the encoding motion.hip's tail and svs_dense_track_balance_order read
 constexpr int BAL_MAX_STREAMS = 4096;
 constexpr int ASSIGN_THREADS = 1024;
-__global__ __launch_bounds__(ASSIGN_THREADS) void trk_assign_kernel(const svs_dense_lm_record *__restrict__ rec, int rec_cap, const int32_t *__restrict__ n_rec, int B, int slots, int x_max, int grid, float ratio, int *__restrict__ map,
-                                                          unsigned char *__restrict__ nwg_of, const int *__restrict__ work16) {      // work16 (optional): the streams' work in 1/16 sweeps, left by the flat tracker kernel
-  __shared__ __attribute__((aligned(16))) float s_w[BAL_MAX_STREAMS];
-  __shared__ unsigned char s_n[BAL_MAX_STREAMS];
-  __shared__ float s_red[ASSIGN_THREADS / 64];
-  __shared__ int s_cnt[2];
+__global__ __launch_bounds__(ASSIGN_THREADS) void trk_assign_kernel(const int *__restrict__ work16, int B, int *__restrict__ map) {
+  // the position of a stream = its rank by (work descending, index ascending) = the number of keys greater than its own; keys = work << 12 | (4095 - index),
+  // packed in LDS and compared four per read (the padding is below every key, so a position stays below B whatever the words hold)
+  __shared__ __attribute__((aligned(16))) int s_key[BAL_MAX_STREAMS];
   const int tid = threadIdx.x;
-  // serial work of every stream's last frame in level-0 sweeps: a sweep of level l counts 4^-l (one LM record per sweep).  All records of the batch are read
-  // with the whole workgroup, eight 16-byte loads in flight per lane (a lane walking its own stream's 64 records one load at a time took 80 us), and summed
-  // per stream with integer LDS atomics (units of 1/16 sweep: the sum does not depend on the order)
-  int *s_wi = reinterpret_cast<int *>(s_w);
-  for (int b = tid; b < B; b += ASSIGN_THREADS) s_wi[b] = 0;
-  __syncthreads();
-  if (work16) {      // round 6: the tracker counted while it ran (one word per stream instead of 64 records per stream: 524 KB through one workgroup was half of this kernel)
-    for (int b = tid; b < B; b += ASSIGN_THREADS) s_wi[b] = work16[b];
-  } else if (rec) {
-    const int total = B * rec_cap;
-    for (int base = tid; base < total; base += 8 * ASSIGN_THREADS) {
-      int4 r[8];
-#pragma unroll
-      for (int u = 0; u < 8; ++u) { const int idx = base + u * ASSIGN_THREADS; r[u] = idx < total ? *reinterpret_cast<const int4 *>(rec + idx) : make_int4(3, 0, 0, 0); }
-#pragma unroll
-      for (int u = 0; u < 8; ++u) {
-        const int idx = base + u * ASSIGN_THREADS;
-        if (idx < total) {
-          const int b = idx / rec_cap, i = idx - b * rec_cap, l = r[u].x;
-          if (i < min(n_rec[b], rec_cap) && l >= 0 && l <= 2) atomicAdd(&s_wi[b], l == 0 ? 16 : (l == 1 ? 4 : 1));
-        }
-      }
-    }
-  }
-  __syncthreads();
-  float sum = 0.f;
-  for (int b = tid; b < B; b += ASSIGN_THREADS) { const float w = (float)s_wi[b] * 0.0625f; s_w[b] = w; sum += w; }
-  for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o, 64);
-  if ((tid & 63) == 0) s_red[tid >> 6] = sum;
-  __syncthreads();
-  float mean = 0.f;
-  for (int k = 0; k < ASSIGN_THREADS / 64; ++k) mean += s_red[k];
-  mean /= (float)B;
-  float M = ratio * mean;
-  if (x_max == 0) {      // order only ("trk_balance" = 1): every stream one workgroup -- nothing to fit (the loop below needed ~7 rounds of two barriers to find that out)
-    for (int b = tid; b < B; b += ASSIGN_THREADS) s_n[b] = 1;
-    if (tid < 2) s_cnt[tid] = 0;
-    __syncthreads();
-  } else
-  for (int round = 0; round < 24; ++round) {
-    if (tid < 2) s_cnt[tid] = 0;
-    __syncthreads();
-    int extra = 0, multi = 0;
-    for (int b = tid; b < B; b += ASSIGN_THREADS) {
-      int n = 1;
-      if (mean > 0.f) { n = (int)ceilf(s_w[b] / M); n = n < 1 ? 1 : (n > 4 ? 4 : n); }
-      s_n[b] = (unsigned char)n;
-      extra += n - 1; multi += n > 1 ? n : 0;
-    }
-    for (int o = 32; o > 0; o >>= 1) { extra += __shfl_xor(extra, o, 64); multi += __shfl_xor(multi, o, 64); }
-    if ((tid & 63) == 0 && extra) { atomicAdd(&s_cnt[0], extra); atomicAdd(&s_cnt[1], multi); }
-    __syncthreads();
-    const bool fits = s_cnt[0] <= x_max && s_cnt[1] <= slots;
-    __syncthreads();
-    if (fits) break;
-    M *= 1.08f;
-    if (round == 23) { for (int b = tid; b < B; b += ASSIGN_THREADS) s_n[b] = 1; __syncthreads(); if (tid < 2) s_cnt[tid] = 0; __syncthreads(); }
-  }
-  // positions.  Single-workgroup streams: rank by (work descending, index ascending) = the number of keys greater than the own one, keys = work in 1/16 sweeps
-  // << 12 | (4095 - index) packed in LDS and compared four per read (multi-workgroup streams carry key -1: they sit in front of all singles)
-  const int n_multi_wgs = s_cnt[1];
-  __syncthreads();
-  int *s_key = reinterpret_cast<int *>(s_w);                 // the works are not needed as floats any more
   const int Bp = (B + 3) & ~3;
-  for (int b = tid; b < Bp; b += ASSIGN_THREADS) {
-    const int key = b < B && s_n[b] == 1 ? ((int)(s_w[b] * 16.f) << 12) | (4095 - b) : -1;      // (read and written by the same lane)
-    s_key[b] = key;
-  }
-  for (int g = tid; g < grid; g += ASSIGN_THREADS) map[g] = -1;
+  for (int b = tid; b < Bp; b += ASSIGN_THREADS) s_key[b] = b < B ? (work16[b] << 12) | (4095 - b) : INT_MIN;
   __syncthreads();
   for (int b = tid; b < B; b += ASSIGN_THREADS) {
-    const int n = s_n[b];
+    const int mine = s_key[b];
     int pos = 0;
-    if (n > 1) { for (int k = 0; k < b; ++k) pos += s_n[k] > 1 ? s_n[k] : 0; }
-    else {
-      const int mine = s_key[b];
-      pos = n_multi_wgs;
-      for (int k = 0; k < Bp; k += 4) {
-        const int4 q = *reinterpret_cast<const int4 *>(s_key + k);
-        pos += (q.x > mine) + (q.y > mine) + (q.z > mine) + (q.w > mine);
-      }
+    for (int k = 0; k < Bp; k += 4) {
+      const int4 q = *reinterpret_cast<const int4 *>(s_key + k);
+      pos += (q.x > mine) + (q.y > mine) + (q.z > mine) + (q.w > mine);
     }
-    for (int k = 0; k < n; ++k) map[pos + k] = (b << 4) | k;
-    nwg_of[b] = (unsigned char)n;
+    map[pos] = b << 4;
   }
 }
 
-// the balanced launch of a big batch.  State (owned by the caller, frontend.hip; persistent from frame to frame): grid map [batch + batch/2] i32 | workgroups
-// per stream [batch] u8 | arrival counters, failure flags, hand-over words (zero before every launch).  The assignment for the NEXT frame is made right behind
-// this frame's tracker (from the LM records it leaves), so that nothing small sits between the fork of the side stream and the tracker's launch.
 // scratch of the continuation launch (dense_track_batch_kernel<., ., 1>): partial sums of the shared sweeps, arrival counters + failure flags, decision words, the
 // parked states and their list.  Returns G / C filled in; enqueues the memset of the words that must start at zero.
 static int cont_setup(svs_ctx *ctx, int batch, TrackMulti &G, TrackCont &C) {
@@ -1408,12 +1301,12 @@ static int cont_setup(svs_ctx *ctx, int batch, TrackMulti &G, TrackCont &C) {
     if (u8src) hipLaunchKernelGGL((K<true, TRK_ARGS TAIL>), grid, dim3(TRK_THREADS), 0, ctx->stream, __VA_ARGS__);         \
     else hipLaunchKernelGGL((K<false, TRK_ARGS TAIL>), grid, dim3(TRK_THREADS), 0, ctx->stream, __VA_ARGS__);              \
   } while (0)
-// the first launch of a big batch (grid: one workgroup per stream / the balanced table) and, with "trk_split", its continuation
+// the first launch of a big batch (one workgroup per stream; BAL: in the order of G.map) and, with "trk_split", its continuation
 template <bool BAL>
-static int launch_batch_tracker(svs_ctx *ctx, const TrackArgs &A, bool u8src, double *d_T_io, int32_t *d_passes_out, int batch, int grid, TrackMulti G) {
+static int launch_batch_tracker(svs_ctx *ctx, const TrackArgs &A, bool u8src, double *d_T_io, int32_t *d_passes_out, int batch, TrackMulti G) {
   TrackCont C{nullptr, nullptr, nullptr, -1, 0};
   if (ctx->trk_split > 0) { const int rc = cont_setup(ctx, batch, G, C); if (rc) return rc; }
-  TRK_LAUNCH(u8src, dense_track_batch_kernel, (BAL, 0), dim3(grid), A, d_T_io, d_passes_out, G, C);
+  TRK_LAUNCH(u8src, dense_track_batch_kernel, (BAL, 0), dim3(batch), A, d_T_io, d_passes_out, G, C);
   SVS_LAUNCH_CHECK(ctx);
   if (C.K < 0) return SVS_OK;
   // the parked streams, CONT_MAX_NWG workgroups each: they wait for each other inside the launch -- through the spin gate like every launch of that kind (common.h).
@@ -1425,71 +1318,38 @@ static int launch_batch_tracker(svs_ctx *ctx, const TrackArgs &A, bool u8src, do
   SVS_LAUNCH_CHECK(ctx);
   return gate.leave();
 }
-struct BalState { int *map; unsigned char *nwg_of; double *flags; size_t n_flags; int grid, x_max; int *work16; };      // work16 [batch]: each stream's LM work of the last frame in 1/16 level-0 sweeps (written by the flat tracker kernel)
+// the ordered launch of a big batch.  State (owned by the caller, frontend.hip; persistent from frame to frame): the grid order [batch] i32 | each stream's LM work
+// of the last frame [batch] i32 (written by the flat tracker kernel), each padded to 256 bytes.  The order for the NEXT frame is made right behind this frame's
+// tracker, so that nothing small sits between the fork of the side stream and the tracker's launch.
+struct BalState { int *map, *work16; };
+size_t bal_row_bytes(int batch) { return (sizeof(int) * (size_t)batch + 255) & ~(size_t)255; }
 BalState bal_state(void *state, int batch) {
-  BalState S;
-  S.x_max = batch / 2; S.grid = batch + S.x_max;
   char *p = static_cast<char *>(state);
-  auto take = [&](size_t bytes) { char *q = p; p += (bytes + 255) & ~(size_t)255; return q; };
-  S.map = reinterpret_cast<int *>(take(sizeof(int) * (size_t)S.grid));
-  S.nwg_of = reinterpret_cast<unsigned char *>(take((size_t)batch));
-  S.n_flags = (size_t)batch + (size_t)batch * 16;
-  S.flags = reinterpret_cast<double *>(take(sizeof(double) * S.n_flags));
-  S.work16 = reinterpret_cast<int *>(take(sizeof(int) * (size_t)batch));
-  return S;
+  return BalState{reinterpret_cast<int *>(p), reinterpret_cast<int *>(p + bal_row_bytes(batch))};
 }
-int bal_assign(svs_ctx *ctx, const BalState &S, int batch, const svs_dense_lm_record *rec, int rec_cap, const int32_t *n_rec, bool have_work = false) {
-  const int x_max = ctx->trk_balance == 2 ? S.x_max : 0;
-  const float ratio = 1.2f;
-  hipLaunchKernelGGL(trk_assign_kernel, dim3(1), dim3(ASSIGN_THREADS), 0, ctx->stream, rec, rec_cap, n_rec, batch, 2 * ctx->n_cu, x_max, S.grid, ratio, S.map, S.nwg_of,
-                     have_work ? S.work16 : nullptr);
+int bal_assign(svs_ctx *ctx, const BalState &S, int batch) {
+  hipLaunchKernelGGL(trk_assign_kernel, dim3(1), dim3(ASSIGN_THREADS), 0, ctx->stream, S.work16, batch, S.map);
   SVS_LAUNCH_CHECK(ctx);
   return SVS_OK;
 }
-int svs_dense_track_cpu_sem_balanced(svs_ctx *ctx, const TrackArgs &A, bool u8src, double *d_T_io, int32_t *d_passes_out, int batch, void *state, const TrackMulti &G0) {
+int svs_dense_track_cpu_sem_balanced(svs_ctx *ctx, const TrackArgs &A, bool u8src, double *d_T_io, int32_t *d_passes_out, int batch, void *state, TrackMulti G) {
   const BalState S = bal_state(state, batch);
-  double *scratch = nullptr;
-  int rc = ensure_scratch(ctx, &scratch, (size_t)batch * 2 * 4 * 32);
-  if (rc) return rc;
-  TrackMulti G = G0;      // (the term buffers of the accept test)
-  G.part = scratch;
-  G.bar = reinterpret_cast<unsigned *>(S.flags);
-  G.fail_off = batch;
-  G.bcast = S.flags + (size_t)batch;
-  G.map = S.map; G.nwg_of = S.nwg_of;
-  if (ctx->trk_balance == 2) {      // order + split (experimental): sibling workgroups wait for each other -- one such launch on the device at a time (common.h)
-    SVS_HIP(ctx, hipMemsetAsync(S.flags, 0, sizeof(double) * S.n_flags, ctx->stream));      // arrival counters, failure flags, hand-over words
-    SvsSpinScope gate(ctx);
-    if (gate.rc) return gate.rc;
-    TRK_LAUNCH(u8src, dense_track_cpu_sem_kernel, (true, TRK_MINW_BIG, false, true), dim3(S.grid), A, d_T_io, d_passes_out, G);
-    SVS_LAUNCH_CHECK(ctx);
-    if (int grc = gate.leave()) return grc;
-  } else if (ctx->trk_flat) {       // order only: one workgroup per stream, nothing waits for anything -- the flat kernel (round 6), bit-identical to the one below
-    G.work16 = S.work16;
-    if (int lrc = launch_batch_tracker<true>(ctx, A, u8src, d_T_io, d_passes_out, batch, S.grid, G)) return lrc;
-    return bal_assign(ctx, S, batch, A.rec, A.rec_cap, A.n_rec, true);
-  } else {
-    TRK_LAUNCH(u8src, dense_track_cpu_sem_kernel, (false, TRK_MINW_BIG, false, true), dim3(S.grid), A, d_T_io, d_passes_out, G);
-  }
-  SVS_LAUNCH_CHECK(ctx);
-  return bal_assign(ctx, S, batch, A.rec, A.rec_cap, A.n_rec);
+  G.map = S.map; G.work16 = S.work16;
+  if (int rc = launch_batch_tracker<true>(ctx, A, u8src, d_T_io, d_passes_out, batch, G)) return rc;
+  return bal_assign(ctx, S, batch);
 }
 }  // namespace
-// the grid order the balanced launch will use for the next tracker launch, as (stream << 4) entries -- a permutation of the streams while "trk_balance" is 1
+// the grid order the ordered launch will use for the next tracker launch, as (stream << 4) entries: a permutation of the streams
 const int *svs_dense_track_balance_order(svs_ctx *ctx, void *state, int batch) {
-  return state && ctx->trk_balance == 1 ? bal_state(state, batch).map : nullptr;
+  return state && ctx->trk_balance ? bal_state(state, batch).map : nullptr;
 }
-size_t svs_dense_track_balance_bytes(int batch) {
-  const uintptr_t base = 1 << 16;                                  // (layout arithmetic only: nothing is dereferenced)
-  const BalState S = bal_state(reinterpret_cast<void *>(base), batch);
-  return (size_t)(reinterpret_cast<uintptr_t>(S.work16) - base) + sizeof(int) * (size_t)batch + 256;
-}
-// zero history: every stream one workgroup, streams in index order
+size_t svs_dense_track_balance_bytes(int batch) { return 2 * bal_row_bytes(batch); }
+// zero history: streams in index order
 int svs_dense_track_balance_init(svs_ctx *ctx, void *state, int batch) {
   SVS_REQUIRE(ctx, ctx && state && batch >= 1 && batch <= BAL_MAX_STREAMS);
   SVS_DEVICE(ctx);
   SVS_HIP(ctx, hipMemsetAsync(state, 0, svs_dense_track_balance_bytes(batch), ctx->stream));
-  return bal_assign(ctx, bal_state(state, batch), batch, nullptr, 0, nullptr);
+  return bal_assign(ctx, bal_state(state, batch), batch);
 }
 extern "C" int svs_dense_track_cpu_sem(svs_ctx *ctx, const svs_dense_track_args *a, double *d_T_io, int32_t *d_passes_out,
                                        int batch) {
@@ -1540,35 +1400,43 @@ int svs_dense_track_cpu_sem_work(svs_ctx *ctx, const svs_dense_track_args *a, do
   }
   TrackMulti G{};
   G.terms = terms; G.terms_b = t_b; G.seq_stats = ctx->seq_stats; G.terms_only = ctx->trk_lazy_chi2 == 2;
-  if (t_buf) {
-    G.part = reinterpret_cast<double *>(t_buf); G.fail_off = (int)t_b;
-    TRK_LAUNCH(u8src, dense_track_cpu_sem_kernel, (false, 2, true), dim3(batch), A, d_T_io, d_passes_out, G);
-  } else if (nwg >= 2) {
-    double *scratch = nullptr;
-    const size_t n_part = (size_t)batch * 2 * nwg * 64;      // per stream, parity and workgroup: 58 (+ 6) flagged 8-byte words (all_workgroups)
-    // (the cleared size rounded up to 64 bytes: a clear whose size is no multiple of 16 bytes is TWO fill kernels in the runtime -- an aligned bulk and a tail --
-    //  and in latency mode every launch in front of the tracker is on the frame's critical path)
-    const size_t n_clear = (n_part + (size_t)batch + (size_t)batch * 16 + 7) & ~(size_t)7;
-    int rc = ensure_scratch(ctx, &scratch, n_clear);      // + one counter word and one failure flag (4 + 4 bytes) per stream + the hand-over words
-    if (rc) return rc;
-    G.part = scratch;
-    G.bar = reinterpret_cast<unsigned *>(scratch + n_part);
-    G.fail_off = batch;
-    G.bcast = scratch + n_part + (size_t)batch;
-    SVS_HIP(ctx, hipMemsetAsync(scratch, 0, sizeof(double) * n_clear, ctx->stream));      // flagged words, failure flags, hand-over words: one clear
-    SvsSpinScope gate(ctx, nwg * batch);      // the workgroups of a stream wait for each other: one such launch on the device at a time (common.h); one stream: priority lane
-    if (gate.rc) return gate.rc;
-    TRK_LAUNCH(u8src, dense_track_cpu_sem_kernel, (true, 2), dim3(nwg, batch), A, d_T_io, d_passes_out, G);
-    SVS_LAUNCH_CHECK(ctx);
-    if (int grc = gate.leave()) return grc;
-  } else if (d_bal_state && ctx->trk_balance && batch >= 2 * ctx->n_cu && batch <= BAL_MAX_STREAMS && A.rec && A.n_rec) {
-    return svs_dense_track_cpu_sem_balanced(ctx, A, u8src, d_T_io, d_passes_out, batch, d_bal_state, G);
-  } else if (((batch > ctx->n_cu && ctx->trk_regs != 1) || ctx->trk_regs == 2) && ctx->trk_flat) {
-    if (int lrc = launch_batch_tracker<false>(ctx, A, u8src, d_T_io, d_passes_out, batch, batch, G)) return lrc;
-  } else if ((batch > ctx->n_cu && ctx->trk_regs != 1) || ctx->trk_regs == 2) {      // trk_regs: tests / experiments, latched at svs_ctx_create
-    TRK_LAUNCH(u8src, dense_track_cpu_sem_kernel, (false, TRK_MINW_BIG), dim3(batch), A, d_T_io, d_passes_out, G);
-  } else {
-    TRK_LAUNCH(u8src, dense_track_cpu_sem_kernel, (false, 2), dim3(batch), A, d_T_io, d_passes_out, G);
+  // the form of the launch.  SeqChain: "trk_seq_chi2"; Latency: nwg workgroups share each stream's sweeps; BigOrdered / Big: the flat kernel, two workgroups
+  // per CU, in the order of the last frame's LM work where the front end keeps that state and records ("trk_regs" = 2 asks for the flat kernel at any batch
+  // size, 1 for the nested-loop kernel: tests / experiments); OnePerCu: the nested-loop kernel, one workgroup per stream
+  enum class Form { SeqChain, Latency, BigOrdered, Big, OnePerCu };
+  const bool ordered = d_bal_state && ctx->trk_balance && batch >= 2 * ctx->n_cu && batch <= BAL_MAX_STREAMS && A.rec && A.n_rec;
+  const bool big = (batch > ctx->n_cu && ctx->trk_regs != 1) || ctx->trk_regs == 2;
+  const Form form = t_buf ? Form::SeqChain : nwg >= 2 ? Form::Latency : ordered ? Form::BigOrdered : big ? Form::Big : Form::OnePerCu;
+  switch (form) {
+    case Form::SeqChain:
+      G.part = reinterpret_cast<double *>(t_buf); G.fail_off = (int)t_b;
+      TRK_LAUNCH(u8src, dense_track_cpu_sem_kernel, (false, true), dim3(batch), A, d_T_io, d_passes_out, G);
+      break;
+    case Form::Latency: {
+      double *scratch = nullptr;
+      const size_t n_part = (size_t)batch * 2 * nwg * 64;      // per stream, parity and workgroup: 58 (+ 6) flagged 8-byte words (all_workgroups)
+      // (the cleared size rounded up to 64 bytes: a clear whose size is no multiple of 16 bytes is TWO fill kernels in the runtime -- an aligned bulk and a tail --
+      //  and in latency mode every launch in front of the tracker is on the frame's critical path)
+      const size_t n_clear = (n_part + (size_t)batch + (size_t)batch * 16 + 7) & ~(size_t)7;
+      int rc = ensure_scratch(ctx, &scratch, n_clear);      // + one counter word and one failure flag (4 + 4 bytes) per stream + the hand-over words
+      if (rc) return rc;
+      G.part = scratch;
+      G.bar = reinterpret_cast<unsigned *>(scratch + n_part);
+      G.fail_off = batch;
+      G.bcast = scratch + n_part + (size_t)batch;
+      SVS_HIP(ctx, hipMemsetAsync(scratch, 0, sizeof(double) * n_clear, ctx->stream));      // flagged words, failure flags, hand-over words: one clear
+      SvsSpinScope gate(ctx, nwg * batch);      // the workgroups of a stream wait for each other: one such launch on the device at a time (common.h); one stream: priority lane
+      if (gate.rc) return gate.rc;
+      TRK_LAUNCH(u8src, dense_track_cpu_sem_kernel, (true), dim3(nwg, batch), A, d_T_io, d_passes_out, G);
+      SVS_LAUNCH_CHECK(ctx);
+      if (int grc = gate.leave()) return grc;
+      break;
+    }
+    case Form::BigOrdered: return svs_dense_track_cpu_sem_balanced(ctx, A, u8src, d_T_io, d_passes_out, batch, d_bal_state, G);
+    case Form::Big: return launch_batch_tracker<false>(ctx, A, u8src, d_T_io, d_passes_out, batch, G);
+    case Form::OnePerCu:
+      TRK_LAUNCH(u8src, dense_track_cpu_sem_kernel, (false), dim3(batch), A, d_T_io, d_passes_out, G);
+      break;
   }
   SVS_LAUNCH_CHECK(ctx);
   return SVS_OK;

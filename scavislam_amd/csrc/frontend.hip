@@ -158,7 +158,7 @@ struct svs_frontend {
   int n_submitted = 0;
   // accept / reject record of the dense tracker's LM loop, per stream (svs_frontend_dense_records)
   DevBuf<svs_dense_lm_record> d_rec; DevBuf<int32_t> d_nrec;
-  DevBuf<void> d_trk_work;              // state of the tracker's balanced launch (dense.hip: LM work of every stream's last frame -> workgroups per stream); big batches only
+  DevBuf<void> d_trk_work;              // state of the tracker's balanced launch (dense.hip: LM work of every stream's last frame -> grid order); big batches only
   // optional stage timing (svs_frontend_set_timing): events between the stages of the last call
   bool timing = false;
   owned::Event ev_stage[SVS_FRONTEND_STAGES + 1];

@@ -791,7 +791,7 @@ def test_dense_tracking_multi_workgroup_variant(gpu_ctx, scene_frames, monkeypat
         dt.ref_dense_points = dtp.ref_dense_points
         T, passes = dt.denseTrackingCpu(prev.pyr, I.reshape(12), from_u8=True)
         out[nwg] = (T.copy(), passes.copy(), dt.d_T_jac.cpu().numpy().copy())
-    # the 128-register build of the one-workgroup kernel (used when there are more streams than CUs): same arithmetic
+    # the flat kernel of big batches (used when there are more streams than CUs; "trk_regs" = 2 asks for it at any batch size): same arithmetic, same bits
     ctx.set_option("trk_nwg", 1)
     ctx.set_option("trk_regs", 2)
     dt = DenseTracker(ctx, cur)

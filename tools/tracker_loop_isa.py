@@ -2,7 +2,7 @@
 """What the compiler made of the dense tracker's sample loop (scavislam_amd/csrc/dense.hip, track_pass).
 
 Compiles dense.hip for gfx950 with the flags of csrc/Makefile plus `--cuda-device-only -S` into a temporary directory, finds the loop over the
-samples in every function that inlines track_pass (the tracker kernels and track_pass_call) and prints, per loop: instructions per trip by class,
+samples in every function that inlines track_pass (the tracker kernels) and prints, per loop: instructions per trip by class,
 the function's VGPRs / scratch / occupancy, the order in which the trip issues its memory operations and waits for them, and a verdict:
 
     do all tap loads of a sample (the four rows of its 4 x 4 neighbourhood in the u8 image) go out before the first wait that covers one of them?
@@ -69,7 +69,7 @@ def checkout_rev(rev, tmp):
 
 def pretty_name(mangled):
     """dense_track_batch_kernel<true, false, 1> from the mangled name (the tracker's template arguments are bools and ints)."""
-    m = re.search(r"\d+(dense_track_batch_kernel|dense_track_cpu_sem_kernel|track_pass_call)I((?:Lb[01]E|Li\d+E)+)E", mangled)
+    m = re.search(r"\d+(dense_track_batch_kernel|dense_track_cpu_sem_kernel)I((?:Lb[01]E|Li\d+E)+)E", mangled)
     if not m:
         return None
     args = ["true" if a == "b1" else "false" if a == "b0" else a[1:] for a in re.findall(r"L(b[01]|i\d+)E", m.group(2))]
@@ -257,8 +257,6 @@ def analyse(asm_text):
             if a["f64_fma"] >= 27 and not any(x.startswith("s_swappc") for x in ins):      # the 27 accumulations of H and b and no call: a loop over samples
                 a["header"] = head
                 loops.append(a)
-        if not loops:
-            continue      # (a kernel that calls its sweep: the loop is track_pass_call's)
         out.append(dict(name=name, mangled=mangled, vgpr=info.get("NumVgprs"), sgpr=info.get("NumSgprs"), scratch=info.get("ScratchSize"), occupancy=info.get("Occupancy"),
                         hot=name in HOT, loops=loops, verdict=all(l["verdict"] is not False for l in loops)))
     out.sort(key=lambda r: (not r["hot"], r["name"]))
