@@ -681,6 +681,57 @@ int svs_loop_check_batch(svs_loop *l, int n_checks, const svs_loop_check *checks
 int svs_loop_set_timing(svs_loop *l, int on);
 int svs_loop_stage_times(svs_loop *l, float *ms);
 
+/* ---- loop closure, the front half of PlaceRecognizer::addLocation (placerecognizer.cpp:248-318): visual words, the inverted index, TF-IDF place scores and
+   the candidate test.  SURF stays with the caller; a place's descriptors are loaded with svs_loop_set_place beforehand.
+   svs_loop_set_vocabulary: h_words [n_words][desc_dim] f32, the counterpart of words_ (data/surfwords10000.png: 9 983 x 64); squared norms are formed as for a
+   place (f64 sum of the exact f32 squares, rounded once).  Allocates the index for the handle's max_places slots and resets it to EMPTY (a second call drops
+   every location; the places themselves stay loaded).  BLOCKING.  n_words < 1: SVS_ERR_INVALID; n_words > SVS_LOOP_MAX_WORDS: SVS_ERR_CAPACITY.  The index is
+   dense: n_words x max_places int32 counts */
+#define SVS_LOOP_MAX_WORDS 1048576
+int svs_loop_set_vocabulary(svs_loop *l, int n_words, const float *h_words);
+typedef struct {
+  int32_t slot;                        /* the place to add: loaded, not yet a location */
+  int32_t do_loop_detection;           /* pr_data.do_loop_detection: 0 adds the location without scoring */
+  const int32_t *h_exclude;            /* pr_data.exclude_set as slots, [n_exclude] (NULL with 0); the location's own slot is always excluded */
+  int32_t n_exclude;
+  float radius;                        /* 0.1f (placerecognizer.cpp:264): cvflann's L2 is the SQUARED distance, so this is a squared radius */
+  float min_score;                     /* 2.0f (:316) */
+} svs_loop_location;
+typedef struct {
+  int32_t number_of_words;             /* Place::number_of_words: descriptors that got a word */
+  int32_t n_scored;                    /* location_stats.size(): slots that received a term */
+  int32_t best_slot;                   /* max_score_idx as a slot; -1: none */
+  float best_score;                    /* max_score; 0 with best_slot -1 */
+  int32_t candidate;                   /* best_score > min_score: the pair (slot, best_slot) is worth a geometric check */
+} svs_loop_location_result;
+/* addLocation from :248 to :318 for n places IN ORDER: location k sees locations 0 .. k-1 of the same call in the index.  BLOCKING; one staged upload, one
+   download and SIX launches whatever n and the descriptor counts are (reset of the call's work arrays, distances, word assignment + insertion, df / idf
+   pre-pass, scores, commit of df).
+   Word of descriptor r: argmin_j over the vocabulary of d2 = (|q|^2 + |w_j|^2) - 2 q.w_j in f32, clamped at 0, the lowest j wins an exact tie -- the matching of
+   svs_loop_check_batch, evaluated pair by pair in the same way whatever the grid.  The word is assigned iff d2 < radius (f32 compare), otherwise it is -1
+   (max_number_of_words = 1, :248).  The reference asks a hierarchical k-means tree with 32 checks, an approximate search that returns SOME word inside the radius
+   and depends on OpenCV's k-means++ draws; the exact search is what it approximates.
+   Index state: n_loc locations; nw[slot] = number_of_words of a location; cnt[w][slot] = occurrences of word w in it; df[w] = slots with cnt[w][slot] > 0.
+   Adding a location, for r = 0 .. n-1 in descriptor order; a descriptor without a word is skipped, every other one adds 1 to number_of_words and
+     1. if do_loop_detection and df[w] > 0 (calcLoopStatistics, :130-172): idf = (float)n_loc / (float)df[w]; for every slot o with cnt[w][o] > 0 that is neither
+        this slot nor excluded: score[o] = score[o] + ((float)cnt[w][o] / (float)nw[o]) * idf -- quotient, product and sum each rounded to f32 on their own, no FMA,
+        in descriptor order (the order is part of the result: a pairwise or f64 sum differs in most cases);
+     2. if cnt[w][slot] == 0 then df[w] += 1; cnt[w][slot] += 1 (:287-296).
+   So a word that repeats inside one keyframe meets a df that already counts that keyframe, and n_loc does not count the keyframe being added (:299 comes after
+   the loop).  Afterwards nw[slot] = number_of_words and n_loc += 1, with or without do_loop_detection.
+   Results: n_scored slots received a term; best_slot = the slot with the greatest score above 0, the LOWEST slot on a tie (the reference takes the first in
+   hash-map order, which is not a function of its input); candidate = best_score > min_score.
+   Outputs (each optional, HOST): h_results [n]; h_word (-1: none) and h_word_d2 (the squared distance to the nearest word, assigned or not) [n][max_desc] --
+   behind a place's descriptor count the rows hold -1 and 0; h_scores [n][max_places], 0 for a slot without a term.
+   A location's outputs are a function of the index state before it and of that location alone: bit-identical in a batch or alone, and on every repetition.
+   Refused before anything is launched, the index unchanged: no vocabulary, a bad or empty slot, a slot that is already a location, an exclude slot outside
+   [0, max_places), two locations of the call naming one slot: SVS_ERR_INVALID; n > max_checks: SVS_ERR_CAPACITY.
+   svs_loop_set_place on a slot that is a location keeps its behaviour (the descriptors are replaced); the index keeps the counts it took */
+int svs_loop_add_locations(svs_loop *l, int n, const svs_loop_location *locs, svs_loop_location_result *h_results, int32_t *h_word, float *h_word_d2,
+                           float *h_scores);
+/* profiling (svs_loop_set_timing): ms[2] = words stage (reset + distances), scoring stage (the other four launches) of the last svs_loop_add_locations */
+int svs_loop_index_stage_times(svs_loop *l, float *ms);
+
 /* ---- back end: re-registration of a keyframe against the map.  Backend::localRegisterFrame (backend.cpp:190-199, 549-611) and Backend::globalLoopClosure
    (:201-219, 830-1001) share one shape -- project map points into a root keyframe (pointsVisibleInRoot :472-546 / the loop at :853-893), matchAndAlign
    (:725-784), gate and count (keyframesToRegister :615-722 / :904-961) -- and run here for a batch of requests as ONE chain of launches on the context's

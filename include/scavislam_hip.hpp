@@ -653,15 +653,17 @@ class FrameRectifier {
   svs_rectify *rect_;
 };
 
-// PlaceRecognizer's geometric check (placerecognizer.cpp:175-202) on device-resident places: addPlace() is where addLocation hands a Place over
-// (location_map_.insert, :299), geometricCheck() is the BFMatcher + RanSaC<SE3Model>::compute(100, ...) pair and the inliers > 30 test.  Detection, SURF and the
-// bag of words stay with the caller.
+// PlaceRecognizer (placerecognizer.cpp:175-322) on device-resident places: addPlace() is where addLocation hands a Place over (location_map_.insert, :299),
+// setVocabulary() takes words_, addLocation() is addLocation from :248 onwards (visual words, inverted index, TF-IDF scores, the > 2 test, then the geometric
+// check of the candidate), geometricCheck() is the BFMatcher + RanSaC<SE3Model>::compute(100, ...) pair and the inliers > 30 test.  Detection and SURF stay with
+// the caller.
 struct DetectedLoop { int query_keyframe_id, loop_keyframe_id; double T_query_from_loop[12]; };      // T: [R | t] row-major
 class PlaceRecognizerGeom {
  public:
   PlaceRecognizerGeom(const Context &c, const svs_cam &stereo_cam, int desc_dim = 64, int max_desc = 2048, int max_places = 64, int num_ransac = 100)
       : ctx_(c), loop_(nullptr), num_ransac_(num_ransac), pixel_thr_(2.5), seed_(0), keyframe_id_(max_places > 0 ? max_places : 0, -1) {
     std::memset(&last_, 0, sizeof last_);
+    std::memset(&last_loc_, 0, sizeof last_loc_);
     ok_ = c.check(svs_loop_create(c.get(), &stereo_cam, desc_dim, max_desc, max_places, num_ransac, 1, &loop_));
   }
   ~PlaceRecognizerGeom() { if (loop_) svs_loop_destroy(loop_); }
@@ -690,6 +692,23 @@ class PlaceRecognizerGeom {
     return last_.n_inliers > 30;
   }
   const svs_loop_result &lastResult() const { return last_; }
+  // words_ [n_words][desc_dim] (the rows of surfwords10000.png); the index starts empty
+  bool setVocabulary(int n_words, const float *words) { return ok_ && ctx_.check(svs_loop_set_vocabulary(loop_, n_words, words)); }
+  // addLocation from :248 onwards for the place loaded into `slot` with addPlace: words, scores against every earlier location outside exclude_slots, insertion;
+  // when the best score passes 2, geometricCheck(slot, best).  true when a loop was detected; *loop as for geometricCheck.  error() tells a refused call
+  // from "no loop"
+  bool addLocation(int slot, int keyframe_id, bool do_loop_detection, const int *exclude_slots, int n_exclude, DetectedLoop *loop) {
+    svs_loop_location lc;
+    std::vector<int32_t> ex(exclude_slots, exclude_slots + (n_exclude > 0 ? n_exclude : 0));
+    lc.slot = slot; lc.do_loop_detection = do_loop_detection ? 1 : 0; lc.h_exclude = ex.empty() ? nullptr : ex.data(); lc.n_exclude = (int32_t)ex.size();
+    lc.radius = 0.1f; lc.min_score = 2.0f;
+    error_ = !ok_ || !ctx_.check(svs_loop_add_locations(loop_, 1, &lc, &last_loc_, nullptr, nullptr, nullptr));
+    if (error_) return false;
+    keyframe_id_[slot] = keyframe_id;
+    return last_loc_.candidate && geometricCheck(slot, last_loc_.best_slot, loop);
+  }
+  const svs_loop_location_result &lastLocation() const { return last_loc_; }
+  bool error() const { return error_; }
 
  private:
   const Context &ctx_;
@@ -699,7 +718,8 @@ class PlaceRecognizerGeom {
   uint64_t seed_;
   std::vector<int> keyframe_id_;
   svs_loop_result last_;
-  bool ok_;
+  svs_loop_location_result last_loc_;
+  bool ok_, error_ = false;
 };
 
 // Backend::localRegisterFrame (backend.cpp:549-611) and Backend::globalLoopClosure (:830-1001) from the pose-graph walk onwards: the caller flattens the

@@ -8,7 +8,7 @@ import ctypes as C
 import os
 import weakref
 
-from .ctypes_types import BaParams, BaStats, Cam, FastGrid, LoopCheck, LoopResult, PoseOptParams, PoseOptStats, RegParams, RegRequest, RegResult, SeedArgs, SeedParams, SeedRequest, StereoParams
+from .ctypes_types import BaParams, BaStats, Cam, FastGrid, LoopCheck, LoopLocation, LoopLocationResult, LoopResult, PoseOptParams, PoseOptStats, RegParams, RegRequest, RegResult, SeedArgs, SeedParams, SeedRequest, StereoParams
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SVS_LIB_PATH") or os.path.join(_HERE, "libscavislam_hip.so")   # override = kernel A/B experiments only
@@ -191,6 +191,9 @@ _SIGS = {
     "svs_loop_check_batch": [C.c_void_p, C.c_int, C.POINTER(LoopCheck), C.POINTER(LoopResult), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
     "svs_loop_set_timing": [C.c_void_p, C.c_int],
     "svs_loop_stage_times": [C.c_void_p, C.c_void_p],
+    "svs_loop_set_vocabulary": [C.c_void_p, C.c_int, C.c_void_p],
+    "svs_loop_add_locations": [C.c_void_p, C.c_int, C.POINTER(LoopLocation), C.POINTER(LoopLocationResult), C.c_void_p, C.c_void_p, C.c_void_p],
+    "svs_loop_index_stage_times": [C.c_void_p, C.c_void_p],
     "svs_reg_create": [C.c_void_p, C.POINTER(Cam), C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)],
     "svs_reg_destroy": [C.c_void_p],
     "svs_reg_register_batch": [C.c_void_p, C.c_int, C.POINTER(RegRequest), C.POINTER(RegParams), C.POINTER(RegResult), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,

@@ -6,6 +6,8 @@
 // for a batch of (query place, train place) pairs in TWO launches: loop_match_kernel (f32-input MFMA distances + per-query argmin) and
 // loop_ransac_kernel (draw, fit, score, select, final pass: one workgroup per check).  A check's outputs are a function of that check alone.
 // Not pinned by the reference's binaries: the yardstick is the NumPy restatement tests/loop_model.py.
+// Further down, the front half of PlaceRecognizer::addLocation (placerecognizer.cpp:248-318) -- a visual word per descriptor, the inverted index, TF-IDF place
+// scores, the candidate test -- for a batch of places in SIX launches (svs_loop_add_locations; yardstick tests/place_model.py).
 #include "common.h"
 #include <math.h>
 #include <string.h>
@@ -32,6 +34,11 @@ struct loop_check_dev {
 // byte offsets inside a check's output block
 struct loop_out_layout { int tidx, dist, smp, hinl, inl; size_t stride; };
 struct loop_cam { double f, cx, cy, b; };
+// one location as the index kernels read it, followed by its [max_places] bytes "slot o may receive a term" (a location before this one, not excluded, not itself)
+struct loop_loc_dev { int32_t slot, n, do_detect, n_loc; float radius, pad_[3]; };
+// what the kernels leave at the head of a location's output block
+struct loop_loc_out { unsigned long long best_key; int32_t n_scored, number_of_words; };
+struct loop_index_layout { int word, d2, score; size_t stride; };
 
 struct svs_loop {
   svs_ctx *ctx = nullptr;
@@ -45,6 +52,17 @@ struct svs_loop {
   size_t in_stride = 0; loop_out_layout lay{};
   PinnedBuf<uint8_t> h_in, h_out; DevBuf<uint8_t> d_in, d_out;      // pinned / device: the checks, the results
   int timing = 0; owned::Event ev[3]; float stage_ms[2] = {0.f, 0.f};
+  // the place index (svs_loop_set_vocabulary / svs_loop_add_locations): a dense inverted index, word-major with the places contiguous
+  int n_words = 0, n_loc = 0;
+  std::unique_ptr<uint8_t[]> is_loc;               // host: the slot is a location
+  DevBuf<float> d_words, d_wnorm;                  // [n_words][K], [n_words]
+  DevBuf<int32_t> d_cnt, d_df, d_nw;               // [n_words][max_places], [n_words], [max_places]
+  DevBuf<unsigned long long> d_wkey;               // [max_checks][max_desc]: the running minimum of (bits(d2) << 32) | word
+  DevBuf<int32_t> d_first, d_nwk;                  // [max_checks][n_words]: first descriptor of the location with the word; [max_checks]: its number_of_words
+  DevBuf<float> d_idf;                             // [max_checks][max_desc]: idf as descriptor r meets it; < 0: no scoring step
+  size_t ix_in_stride = 0; loop_index_layout ixl{};
+  PinnedBuf<uint8_t> h_ix_in, h_ix_out; DevBuf<uint8_t> d_ix_in, d_ix_out;
+  float index_ms[2] = {0.f, 0.f};
   ~svs_loop() { if (ctx) { (void)hipSetDevice(ctx->device); (void)hipStreamSynchronize(ctx->stream); } }      // (before the members go, also when create gives up)
 };
 
@@ -540,5 +558,345 @@ extern "C" int svs_loop_check_batch(svs_loop *l, int n_checks, const svs_loop_ch
     if (h_samples_out) { memcpy(h_samples_out + (size_t)c * mh * 3, o + l->lay.smp, 12 * (size_t)H); std::fill(h_samples_out + ((size_t)c * mh + H) * 3, h_samples_out + (size_t)(c + 1) * mh * 3, -1); }
     if (h_hyp_inliers) { memcpy(h_hyp_inliers + (size_t)c * mh, o + l->lay.hinl, 4 * (size_t)H); std::fill(h_hyp_inliers + (size_t)c * mh + H, h_hyp_inliers + (size_t)(c + 1) * mh, 0); }
   }
+  return SVS_OK;
+}
+
+// ---- the place index: visual words, inverted index, TF-IDF scores (placerecognizer.cpp:248-318) -----------------------------------------------------------------
+// Words.  grid = (query blocks of 32, vocabulary chunks of LW_CHUNK rows, locations), 4 waves: the tile walk, the MFMA feeding and the per-pair arithmetic of
+// loop_match_kernel, so a pair's d2 does not depend on the chunk or the batch it falls in; the chunks meet in a 64-bit atomic minimum on the same key, whose
+// minimum is order-independent.  One keyframe of 500 descriptors against 9 983 words is 16 x 39 workgroups.  A lane issues the eight 16-byte loads of its
+// share of a tile together and stores them to LDS when they have arrived.  A form that fetched the NEXT tile into registers under the MFMAs of the present one
+// kept 32 registers more alive (two waves per SIMD instead of three) and measured 5 to 9 % slower at both sizes (profiles/place_index.md): the workgroups of
+// the other chunks are what hides the load.
+constexpr int LW_CHUNK = 2 * LM_TROWS;
+template <int K>
+__global__ __launch_bounds__(256) void loop_words_kernel(const float *__restrict__ desc, const float *__restrict__ norm, size_t place_rows, const float *__restrict__ W,
+                                                        const float *__restrict__ Wn, int n_words, const uint8_t *__restrict__ in, size_t in_stride,
+                                                        unsigned long long *__restrict__ wkey, int max_desc) {
+  constexpr int NKC = K / LM_KC, PER = LM_TROWS * (LM_KC / 4) / 256;
+  __shared__ float4 s_tile[LM_TROWS * LM_LD4];
+  __shared__ float s_tnorm[LM_TROWS];
+  __shared__ unsigned long long s_best[4][LM_QROWS];
+  const loop_loc_dev *lc = reinterpret_cast<const loop_loc_dev *>(in + (size_t)blockIdx.z * in_stride);
+  const int nq = lc->n, q0 = (int)blockIdx.x * LM_QROWS;
+  if (q0 >= nq) return;                                                    // (the grid is sized for the longest place of the call)
+  const int c0 = (int)blockIdx.y * LW_CHUNK, c1 = min(n_words, c0 + LW_CHUNK);      // this workgroup's words; c0 < n_words by the grid
+  const float *Q = desc + (size_t)lc->slot * place_rows * K, *Qn = norm + (size_t)lc->slot * place_rows;
+  const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6, r = lane & 31, hh = lane >> 5;
+  const bool qok = q0 + r < nq;
+  float4 qf[K / 8];
+#pragma unroll
+  for (int s = 0; s < K / 8; ++s)
+    qf[s] = qok ? *reinterpret_cast<const float4 *>(Q + (size_t)(q0 + r) * K + 8 * s + 4 * hh) : make_float4(0.f, 0.f, 0.f, 0.f);
+  const float qn = qok ? Qn[q0 + r] : 0.f;
+  unsigned long long best = ~0ull;
+  f32x16 acc;
+  for (int t0 = c0; t0 < c1; t0 += LM_TROWS) {
+    const bool mine = t0 + wave * 32 < c1;                                 // wave-uniform
+#pragma unroll
+    for (int e = 0; e < 16; ++e) acc[e] = 0.f;
+#pragma unroll
+    for (int kc = 0; kc < NKC; ++kc) {                                     // (unrolled: the query fragment is indexed by constants and stays in registers)
+      __syncthreads();                                                     // the previous tile has been read
+      float4 ld[PER];                                                      // all eight loads of the lane in flight, then the stores
+#pragma unroll
+      for (int u = 0; u < PER; ++u) {
+        const int i = tid + 256 * u, row = i >> 4, c4 = i & 15;
+        ld[u] = t0 + row < c1 ? *reinterpret_cast<const float4 *>(W + (size_t)(t0 + row) * K + kc * LM_KC + 4 * c4) : make_float4(0.f, 0.f, 0.f, 0.f);
+      }
+      const float ldn = kc == 0 && tid < LM_TROWS && t0 + tid < c1 ? Wn[t0 + tid] : 0.f;
+#pragma unroll
+      for (int u = 0; u < PER; ++u) {
+        const int i = tid + 256 * u;
+        s_tile[(i >> 4) * LM_LD4 + (i & 15)] = ld[u];
+      }
+      if (kc == 0 && tid < LM_TROWS) s_tnorm[tid] = ldn;
+      __syncthreads();
+      if (mine) {
+#pragma unroll
+        for (int ss = 0; ss < LM_KC / 8; ++ss) {
+          const float4 a = s_tile[(wave * 32 + r) * LM_LD4 + 2 * ss + hh], b = qf[kc * (LM_KC / 8) + ss];
+          acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.x, b.x, acc, 0, 0, 0);
+          acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.y, b.y, acc, 0, 0, 0);
+          acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.z, b.z, acc, 0, 0, 0);
+          acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.w, b.w, acc, 0, 0, 0);
+        }
+      }
+    }
+    if (mine) {
+#pragma unroll
+      for (int e = 0; e < 16; ++e) {
+        const int i = (e & 3) + 8 * (e >> 2) + 4 * hh, j = t0 + wave * 32 + i;
+        float d2 = (qn + s_tnorm[wave * 32 + i]) - 2.f * acc[e];
+        d2 = d2 < 0.f ? 0.f : d2;
+        const unsigned long long key = ((unsigned long long)__float_as_uint(d2) << 32) | (unsigned)j;
+        if (j < c1 && key < best) best = key;
+      }
+    }
+  }
+  {
+    const unsigned long long o = __shfl_xor(best, 32, 64);
+    best = o < best ? o : best;
+  }
+  if (lane < 32) s_best[wave][lane] = best;
+  __syncthreads();
+  if (tid < LM_QROWS && q0 + tid < nq) {
+    unsigned long long b = s_best[0][tid];
+#pragma unroll
+    for (int w = 1; w < 4; ++w) b = s_best[w][tid] < b ? s_best[w][tid] : b;
+    atomicMin(wkey + (size_t)blockIdx.z * max_desc + q0 + tid, b);
+  }
+}
+
+// the call's work arrays: keys to "nothing yet", first occurrences to "none", the counters to 0.  grid-stride over locations x max(max_desc, n_words)
+__global__ __launch_bounds__(256) void loop_index_reset_kernel(int n, int max_desc, int n_words, unsigned long long *__restrict__ wkey, int32_t *__restrict__ first,
+                                                              int32_t *__restrict__ nwk, uint8_t *__restrict__ out, size_t out_stride) {
+  const size_t m = (size_t)max(max_desc, n_words), total = m * n;
+  for (size_t i = (size_t)blockIdx.x * 256u + threadIdx.x; i < total; i += (size_t)gridDim.x * 256u) {
+    const size_t k = i / m, j = i - k * m;
+    if (j < (size_t)max_desc) wkey[k * max_desc + j] = ~0ull;
+    if (j < (size_t)n_words) first[k * n_words + j] = INT32_MAX;
+    if (j == 0) {
+      nwk[k] = 0;
+      loop_loc_out *h = reinterpret_cast<loop_loc_out *>(out + k * out_stride);
+      h->best_key = 0ull; h->n_scored = 0; h->number_of_words = 0;
+    }
+  }
+}
+
+// grid = (descriptor blocks, locations).  The word of every descriptor, and everything about the insertion that does not depend on the order: the place's
+// column of cnt (integer atomics), the first descriptor that carries each word, the number of words
+__global__ __launch_bounds__(256) void loop_assign_kernel(const uint8_t *__restrict__ in, size_t in_stride, const unsigned long long *__restrict__ wkey, int max_desc,
+                                                         int n_words, int max_places, int32_t *__restrict__ cnt, int32_t *__restrict__ first, int32_t *__restrict__ nwk,
+                                                         uint8_t *__restrict__ out, loop_index_layout lay) {
+  const int k = (int)blockIdx.y, r = (int)(blockIdx.x * 256u + threadIdx.x);
+  const loop_loc_dev *lc = reinterpret_cast<const loop_loc_dev *>(in + (size_t)k * in_stride);
+  const bool act = r < lc->n;
+  int w = -1;
+  if (act) {
+    const unsigned long long key = wkey[(size_t)k * max_desc + r];
+    const float d2 = __uint_as_float((unsigned)(key >> 32));
+    const unsigned j = (unsigned)(key & 0xffffffffull);
+    w = d2 < lc->radius && j < (unsigned)n_words ? (int)j : -1;
+    uint8_t *o = out + (size_t)k * lay.stride;
+    reinterpret_cast<int32_t *>(o + lay.word)[r] = w;
+    reinterpret_cast<float *>(o + lay.d2)[r] = d2;
+    if (w >= 0) {
+      atomicMin(first + (size_t)k * n_words + w, r);
+      atomicAdd(cnt + (size_t)w * max_places + lc->slot, 1);
+    }
+  }
+  const int c = __popcll(__ballot(w >= 0));
+  if ((threadIdx.x & 63) == 0 && c) atomicAdd(nwk + k, c);
+}
+
+// grid = (descriptor blocks, locations).  df as descriptor r of location k meets it = df before the call + the earlier locations of the call that hold the word
+// + this location itself once an earlier descriptor of it has inserted the word; idf = (float)n_loc / (float)df, -1 where there is no scoring step
+__global__ __launch_bounds__(256) void loop_idf_kernel(const uint8_t *__restrict__ in, size_t in_stride, int max_desc, int n_words, const int32_t *__restrict__ df,
+                                                      const int32_t *__restrict__ first, const int32_t *__restrict__ nwk, int32_t *__restrict__ nw,
+                                                      float *__restrict__ idf, uint8_t *__restrict__ out, loop_index_layout lay) {
+  const int k = (int)blockIdx.y, r = (int)(blockIdx.x * 256u + threadIdx.x);
+  const loop_loc_dev *lc = reinterpret_cast<const loop_loc_dev *>(in + (size_t)k * in_stride);
+  if (r >= lc->n) return;
+  uint8_t *o = out + (size_t)k * lay.stride;
+  const int w = reinterpret_cast<const int32_t *>(o + lay.word)[r];
+  float v = -1.f;
+  if (w >= 0 && lc->do_detect) {
+    int d = df[w] + (first[(size_t)k * n_words + w] < r ? 1 : 0);
+    for (int e = 0; e < k; ++e) d += first[(size_t)e * n_words + w] != INT32_MAX ? 1 : 0;
+    if (d > 0) v = (float)lc->n_loc / (float)d;
+  }
+  idf[(size_t)k * max_desc + r] = v;
+  if (r == 0) {
+    nw[lc->slot] = nwk[k];
+    reinterpret_cast<loop_loc_out *>(o)->number_of_words = nwk[k];
+  }
+}
+
+// grid = (place blocks, locations): one thread per (location, place).  The thread of place o reads column o of cnt and nothing of another thread's; cnt holds
+// the call's locations already, and the host's byte "o is a location before this one, not excluded, not itself" decides whether the column counts.  Word and
+// idf are wave-uniform.  The LS_BLOCK loads of a block of descriptors are issued together; only the adds are a chain -- in descriptor order, every operation
+// rounded on its own (no contraction in this file)
+constexpr int LS_BLOCK = 32;
+__global__ __launch_bounds__(256) void loop_score_kernel(const uint8_t *__restrict__ in, size_t in_stride, int max_desc, int max_places, const int32_t *__restrict__ cnt,
+                                                        const int32_t *__restrict__ nw, const float *__restrict__ idf, uint8_t *__restrict__ out, loop_index_layout lay) {
+  const int k = (int)blockIdx.y, o = (int)(blockIdx.x * 256u + threadIdx.x);
+  const loop_loc_dev *lc = reinterpret_cast<const loop_loc_dev *>(in + (size_t)k * in_stride);
+  const uint8_t *vis = reinterpret_cast<const uint8_t *>(lc + 1);
+  uint8_t *ob = out + (size_t)k * lay.stride;
+  const int32_t *word = reinterpret_cast<const int32_t *>(ob + lay.word);
+  const float *f = idf + (size_t)k * max_desc;
+  const int n = lc->n;
+  float s = 0.f;
+  bool got = false;
+  if (o < max_places && lc->do_detect && vis[o]) {
+    const float nwo = (float)nw[o];
+    for (int r0 = 0; r0 < n; r0 += LS_BLOCK) {
+      int c[LS_BLOCK]; float v[LS_BLOCK];
+#pragma unroll
+      for (int u = 0; u < LS_BLOCK; ++u) {
+        const int r = r0 + u, w = r < n ? word[r] : -1;
+        v[u] = r < n ? f[r] : -1.f;
+        c[u] = w >= 0 && v[u] >= 0.f ? cnt[(size_t)w * max_places + o] : 0;
+      }
+#pragma unroll
+      for (int u = 0; u < LS_BLOCK; ++u)
+        if (c[u] > 0) {
+          const float tf = (float)c[u] / nwo, val = tf * v[u];
+          s = s + val;
+          got = true;
+        }
+    }
+  }
+  if (o < max_places) reinterpret_cast<float *>(ob + lay.score)[o] = s;
+  // the greatest score above 0, the lowest slot on a tie: positive floats order like their bits
+  unsigned long long key = got && s > 0.f ? ((unsigned long long)__float_as_uint(s) << 32) | (0xffffffffu - (unsigned)o) : 0ull;
+#pragma unroll
+  for (int m = 32; m > 0; m >>= 1) {
+    const unsigned long long x = __shfl_xor(key, m, 64);
+    key = x > key ? x : key;
+  }
+  const int ngot = __popcll(__ballot(got));
+  if ((threadIdx.x & 63) == 0) {
+    loop_loc_out *h = reinterpret_cast<loop_loc_out *>(ob);
+    if (ngot) atomicAdd(&h->n_scored, ngot);
+    if (key) atomicMax(&h->best_key, key);
+  }
+}
+
+// grid = (descriptor blocks, locations): df takes the call's locations (the first descriptor with a word speaks for its location)
+__global__ __launch_bounds__(256) void loop_commit_kernel(const uint8_t *__restrict__ in, size_t in_stride, int n_words, const int32_t *__restrict__ first,
+                                                         int32_t *__restrict__ df, const uint8_t *__restrict__ out, loop_index_layout lay) {
+  const int k = (int)blockIdx.y, r = (int)(blockIdx.x * 256u + threadIdx.x);
+  const loop_loc_dev *lc = reinterpret_cast<const loop_loc_dev *>(in + (size_t)k * in_stride);
+  if (r >= lc->n) return;
+  const int w = reinterpret_cast<const int32_t *>(out + (size_t)k * lay.stride + lay.word)[r];
+  if (w >= 0 && first[(size_t)k * n_words + w] == r) atomicAdd(df + w, 1);
+}
+
+extern "C" int svs_loop_set_vocabulary(svs_loop *l, int n_words, const float *h_words) {
+  svs_ctx *ctx = l ? l->ctx : nullptr;
+  SVS_REQUIRE(ctx, l && n_words >= 1 && h_words);
+  LOOP_CAPACITY(ctx, n_words <= SVS_LOOP_MAX_WORDS);
+  SVS_DEVICE(ctx);
+  SVS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  l->n_words = 0; l->n_loc = 0;                                            // (no vocabulary while this call can still give up)
+  const size_t P = (size_t)l->max_places, C = (size_t)l->max_checks, nwd = (size_t)n_words;
+  SVS_HIP(ctx, l->d_words.alloc(nwd * l->K));
+  SVS_HIP(ctx, l->d_wnorm.alloc(nwd));
+  SVS_HIP(ctx, l->d_cnt.alloc(nwd * P));
+  SVS_HIP(ctx, l->d_df.alloc(nwd));
+  SVS_HIP(ctx, l->d_nw.alloc(P));
+  SVS_HIP(ctx, l->d_wkey.alloc(C * l->max_desc));
+  SVS_HIP(ctx, l->d_first.alloc(C * nwd));
+  SVS_HIP(ctx, l->d_nwk.alloc(C));
+  SVS_HIP(ctx, l->d_idf.alloc(C * l->max_desc));
+  l->ix_in_stride = loop_align16(sizeof(loop_loc_dev) + P);
+  l->ixl.word = (int)loop_align16(sizeof(loop_loc_out));
+  l->ixl.d2 = l->ixl.word + 4 * l->max_desc;
+  l->ixl.score = l->ixl.d2 + 4 * l->max_desc;
+  l->ixl.stride = loop_align16((size_t)l->ixl.score + 4 * P);
+  SVS_HIP(ctx, l->d_ix_in.alloc(l->ix_in_stride * C));
+  SVS_HIP(ctx, l->h_ix_in.alloc(l->ix_in_stride * C));
+  SVS_HIP(ctx, l->d_ix_out.alloc(l->ixl.stride * C));
+  SVS_HIP(ctx, l->h_ix_out.alloc(l->ixl.stride * C));
+  l->is_loc.reset(new uint8_t[P]());
+  SVS_HIP(ctx, hipMemcpyAsync(l->d_words, h_words, nwd * l->K * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+  hipLaunchKernelGGL(loop_place_kernel, dim3(div_up(n_words, 256)), dim3(256), 0, ctx->stream, l->d_words, l->K, n_words, l->d_wnorm, (const double *)nullptr,
+                     (double *)nullptr, 0, l->cam);
+  SVS_LAUNCH_CHECK(ctx);
+  SVS_HIP(ctx, hipMemsetAsync(l->d_cnt, 0, nwd * P * sizeof(int32_t), ctx->stream));
+  SVS_HIP(ctx, hipMemsetAsync(l->d_df, 0, nwd * sizeof(int32_t), ctx->stream));
+  SVS_HIP(ctx, hipMemsetAsync(l->d_nw, 0, P * sizeof(int32_t), ctx->stream));
+  SVS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  l->n_words = n_words;
+  return SVS_OK;
+}
+
+extern "C" int svs_loop_index_stage_times(svs_loop *l, float *ms) {
+  if (!l || !ms) return SVS_ERR_INVALID;
+  ms[0] = l->index_ms[0]; ms[1] = l->index_ms[1];
+  return SVS_OK;
+}
+
+extern "C" int svs_loop_add_locations(svs_loop *l, int n, const svs_loop_location *locs, svs_loop_location_result *h_results, int32_t *h_word, float *h_word_d2,
+                                      float *h_scores) {
+  svs_ctx *ctx = l ? l->ctx : nullptr;
+  SVS_REQUIRE(ctx, l && n >= 0 && (n == 0 || locs));
+  SVS_REQUIRE(ctx, l->n_words > 0);                                        // no vocabulary
+  LOOP_CAPACITY(ctx, n <= l->max_checks);
+  const int P = l->max_places, md = l->max_desc;
+  int max_n = 0;
+  for (int k = 0; k < n; ++k) {
+    const svs_loop_location &c = locs[k];
+    SVS_REQUIRE(ctx, c.slot >= 0 && c.slot < P && l->n_place[c.slot] > 0 && !l->is_loc[c.slot]);
+    SVS_REQUIRE(ctx, c.n_exclude >= 0 && (c.n_exclude == 0 || c.h_exclude));
+    for (int e = 0; e < c.n_exclude; ++e) SVS_REQUIRE(ctx, c.h_exclude[e] >= 0 && c.h_exclude[e] < P);
+    for (int e = 0; e < k; ++e) SVS_REQUIRE(ctx, locs[e].slot != c.slot);
+    max_n = std::max(max_n, l->n_place[c.slot]);
+  }
+  if (n == 0) return SVS_OK;
+  SVS_DEVICE(ctx);
+  for (int k = 0; k < n; ++k) {
+    const svs_loop_location &c = locs[k];
+    loop_loc_dev *d = reinterpret_cast<loop_loc_dev *>(l->h_ix_in + (size_t)k * l->ix_in_stride);
+    *d = loop_loc_dev{c.slot, l->n_place[c.slot], c.do_loop_detection ? 1 : 0, l->n_loc + k, c.radius, {0.f, 0.f, 0.f}};
+    uint8_t *vis = reinterpret_cast<uint8_t *>(d + 1);
+    memcpy(vis, l->is_loc.get(), (size_t)P);
+    for (int e = 0; e < k; ++e) vis[locs[e].slot] = 1;
+    for (int e = 0; e < c.n_exclude; ++e) vis[c.h_exclude[e]] = 0;
+    vis[c.slot] = 0;
+  }
+  SVS_HIP(ctx, hipMemcpyAsync(l->d_ix_in, l->h_ix_in, l->ix_in_stride * n, hipMemcpyHostToDevice, ctx->stream));
+  if (l->timing) SVS_HIP(ctx, hipEventRecord(l->ev[0], ctx->stream));
+  const size_t reset_items = (size_t)std::max(md, l->n_words) * n;
+  hipLaunchKernelGGL(loop_index_reset_kernel, dim3((unsigned)std::min<size_t>((reset_items + 255) / 256, 4096)), dim3(256), 0, ctx->stream, n, md, l->n_words,
+                     l->d_wkey, l->d_first, l->d_nwk, l->d_ix_out, l->ixl.stride);
+  SVS_LAUNCH_CHECK(ctx);
+  const dim3 wgrid(div_up(max_n, LM_QROWS), div_up(l->n_words, LW_CHUNK), n);
+  if (l->K == 64) hipLaunchKernelGGL(loop_words_kernel<64>, wgrid, dim3(256), 0, ctx->stream, l->d_desc, l->d_norm, (size_t)md, l->d_words, l->d_wnorm, l->n_words,
+                                     l->d_ix_in, l->ix_in_stride, l->d_wkey, md);
+  else hipLaunchKernelGGL(loop_words_kernel<128>, wgrid, dim3(256), 0, ctx->stream, l->d_desc, l->d_norm, (size_t)md, l->d_words, l->d_wnorm, l->n_words, l->d_ix_in,
+                          l->ix_in_stride, l->d_wkey, md);
+  SVS_LAUNCH_CHECK(ctx);
+  if (l->timing) SVS_HIP(ctx, hipEventRecord(l->ev[1], ctx->stream));
+  const dim3 rgrid(div_up(max_n, 256), n);
+  hipLaunchKernelGGL(loop_assign_kernel, rgrid, dim3(256), 0, ctx->stream, l->d_ix_in, l->ix_in_stride, l->d_wkey, md, l->n_words, P, l->d_cnt, l->d_first, l->d_nwk,
+                     l->d_ix_out, l->ixl);
+  SVS_LAUNCH_CHECK(ctx);
+  hipLaunchKernelGGL(loop_idf_kernel, rgrid, dim3(256), 0, ctx->stream, l->d_ix_in, l->ix_in_stride, md, l->n_words, l->d_df, l->d_first, l->d_nwk, l->d_nw, l->d_idf,
+                     l->d_ix_out, l->ixl);
+  SVS_LAUNCH_CHECK(ctx);
+  hipLaunchKernelGGL(loop_score_kernel, dim3(div_up(P, 256), n), dim3(256), 0, ctx->stream, l->d_ix_in, l->ix_in_stride, md, P, l->d_cnt, l->d_nw, l->d_idf, l->d_ix_out,
+                     l->ixl);
+  SVS_LAUNCH_CHECK(ctx);
+  hipLaunchKernelGGL(loop_commit_kernel, rgrid, dim3(256), 0, ctx->stream, l->d_ix_in, l->ix_in_stride, l->n_words, l->d_first, l->d_df, l->d_ix_out, l->ixl);
+  SVS_LAUNCH_CHECK(ctx);
+  if (l->timing) SVS_HIP(ctx, hipEventRecord(l->ev[2], ctx->stream));
+  SVS_HIP(ctx, hipMemcpyAsync(l->h_ix_out, l->d_ix_out, l->ixl.stride * n, hipMemcpyDeviceToHost, ctx->stream));
+  SVS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  if (l->timing) {
+    SVS_HIP(ctx, hipEventElapsedTime(&l->index_ms[0], l->ev[0], l->ev[1]));
+    SVS_HIP(ctx, hipEventElapsedTime(&l->index_ms[1], l->ev[1], l->ev[2]));
+  }
+  for (int k = 0; k < n; ++k) {
+    const uint8_t *o = l->h_ix_out + (size_t)k * l->ixl.stride;
+    const loop_loc_out *h = reinterpret_cast<const loop_loc_out *>(o);
+    const int nd = l->n_place[locs[k].slot];
+    if (h_results) {
+      svs_loop_location_result &res = h_results[k];
+      res.number_of_words = h->number_of_words;
+      res.n_scored = h->n_scored;
+      res.best_slot = h->best_key ? (int32_t)(0xffffffffu - (uint32_t)(h->best_key & 0xffffffffull)) : -1;
+      const uint32_t bits = (uint32_t)(h->best_key >> 32);
+      memcpy(&res.best_score, &bits, 4);
+      res.candidate = res.best_score > locs[k].min_score ? 1 : 0;
+    }
+    if (h_word) { memcpy(h_word + (size_t)k * md, o + l->ixl.word, 4 * (size_t)nd); std::fill(h_word + (size_t)k * md + nd, h_word + (size_t)(k + 1) * md, -1); }
+    if (h_word_d2) { memcpy(h_word_d2 + (size_t)k * md, o + l->ixl.d2, 4 * (size_t)nd); std::fill(h_word_d2 + (size_t)k * md + nd, h_word_d2 + (size_t)(k + 1) * md, 0.f); }
+    if (h_scores) memcpy(h_scores + (size_t)k * P, o + l->ixl.score, 4 * (size_t)P);
+    l->is_loc[locs[k].slot] = 1;
+  }
+  l->n_loc += n;
   return SVS_OK;
 }

@@ -133,6 +133,16 @@ class LoopResult(C.Structure):
                 ("T_query_from_train", C.c_double * 12)]
 
 
+class LoopLocation(C.Structure):
+    """svs_loop_location: one place on its way into the index (PlaceRecognizer::addLocation, placerecognizer.cpp:248-318)."""
+    _fields_ = [("slot", C.c_int32), ("do_loop_detection", C.c_int32), ("h_exclude", C.c_void_p), ("n_exclude", C.c_int32), ("radius", C.c_float),
+                ("min_score", C.c_float)]
+
+
+class LoopLocationResult(C.Structure):
+    _fields_ = [("number_of_words", C.c_int32), ("n_scored", C.c_int32), ("best_slot", C.c_int32), ("best_score", C.c_float), ("candidate", C.c_int32)]
+
+
 class SeedParams(C.Structure):
     """svs_seed_params: params_.newpoint_clearance, ui.num_max_points, ui.min_num_points, USE_N_LEVELS_FOR_MATCHING (stereo_frontend.cpp:319-331, :735-749)."""
     _fields_ = [("clearance", C.c_int32), ("num_max_points", C.c_int32), ("min_num_points", C.c_int32), ("n_levels", C.c_int32)]

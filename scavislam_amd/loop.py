@@ -3,14 +3,17 @@
   GeometricChecker.check(query, train)  <- PlaceRecognizer::geometricCheck   placerecognizer.cpp:175-202
   GeometricChecker.set_place(...)       <- location_map_.insert(...)         placerecognizer.cpp:299
 
-Detection, description (SURF) and the bag-of-words index stay with the caller; this class takes a Place the way geometricCheck consumes it
+  GeometricChecker.set_vocabulary(w)    <- words_ / flann_index_             placerecognizer.cpp:55-75
+  GeometricChecker.add_locations(...)   <- addLocation from :248 to :318     visual words, inverted index, TF-IDF scores, the candidate test
+
+Detection and description (SURF) stay with the caller; this class takes a Place the way geometricCheck consumes it
 (descriptors, uvu_0_vec, optionally xyz_vec) and keeps it on the device.  There is no CPU path: every call goes to svs_loop_* of the HIP library.
 """
 import ctypes as C
 
 import numpy as np
 
-from .ctypes_types import Cam, LoopCheck, LoopResult
+from .ctypes_types import Cam, LoopCheck, LoopLocation, LoopLocationResult, LoopResult
 
 
 class LoopCheckOutput:
@@ -26,6 +29,24 @@ class LoopCheckOutput:
         return self.n_inliers > min_inliers
 
 
+class LocationOutput:
+    """One added location: the fields of svs_loop_location_result, its words / squared distances cut to its descriptor count, its score row."""
+
+    def __init__(self, slot, res, word, word_d2, scores):
+        self.slot = slot
+        self.number_of_words, self.n_scored, self.best_slot, self.best_score, self.candidate = (res.number_of_words, res.n_scored, res.best_slot,
+                                                                                                np.float32(res.best_score), bool(res.candidate))
+        self.word, self.word_d2, self.scores = word, word_d2, scores
+
+
+class LocationBatch(list):
+    """The LocationOutputs of one add_locations call, in call order."""
+
+    def candidates(self):
+        """(query_slot, best_slot) of the locations whose best score passed min_score: what check_batch takes"""
+        return [(o.slot, o.best_slot) for o in self if o.candidate]
+
+
 class GeometricChecker:
     def __init__(self, ctx, cam, desc_dim=64, max_desc=2048, max_places=64, max_hyp=100, max_checks=32):
         self.ctx, self.h = ctx, None
@@ -36,6 +57,8 @@ class GeometricChecker:
         self.h = h
         ctx.children.add(self)
         self.raw = None      # the full-length rows of the last check_batch (tests: byte comparisons)
+        self.raw_index = None      # the same of the last add_locations
+        self.n_place = {}      # descriptors per loaded slot
 
     def set_place(self, slot, descriptors, uvu, xyz=None):
         d = np.ascontiguousarray(descriptors, np.float32)
@@ -45,6 +68,7 @@ class GeometricChecker:
         if n and (d.shape[1] != self.desc_dim or u.shape != (n, 3) or (x is not None and x.shape != (n, 3))):
             raise ValueError("descriptors [n][desc_dim], uvu [n][3], xyz [n][3] expected")
         self.ctx.check(self.ctx.lib.svs_loop_set_place(self.h, int(slot), int(n), d.ctypes.data, u.ctypes.data, None if x is None else x.ctypes.data))
+        self.n_place[int(slot)] = int(n)
 
     def check_batch(self, checks, n_hyp=100, pixel_thr=2.5, seed=0):
         """checks: (query_slot, train_slot) pairs or dicts with query, train and optionally n_hyp, pixel_thr, seed, samples ([n_hyp][3] match indices)"""
@@ -80,6 +104,45 @@ class GeometricChecker:
 
     def check(self, query, train, **kw):
         return self.check_batch([dict(query=query, train=train, **kw)])[0]
+
+    def set_vocabulary(self, words):
+        """words [n_words][desc_dim] f32 (the rows of surfwords10000.png); resets the index to empty"""
+        w = np.ascontiguousarray(words, np.float32)
+        if w.ndim != 2 or w.shape[1] != self.desc_dim:
+            raise ValueError("words [n_words][desc_dim] expected")
+        self.ctx.check(self.ctx.lib.svs_loop_set_vocabulary(self.h, int(w.shape[0]), w.ctypes.data))
+        self.n_words = int(w.shape[0])
+
+    def add_locations(self, locations, do_loop_detection=True, radius=0.1, min_score=2.0):
+        """locations: slots or dicts with slot and optionally exclude (slots), do_loop_detection, radius, min_score; the places were loaded with set_place.
+        Returns a LocationBatch; .candidates() goes straight to check_batch"""
+        n = len(locations)
+        arr = (LoopLocation * max(n, 1))()
+        keep, slots = [], []
+        for i, c in enumerate(locations):
+            c = c if isinstance(c, dict) else dict(slot=c)
+            ex = np.ascontiguousarray(c.get("exclude", ()), np.int32).reshape(-1)
+            keep.append(ex)
+            slots.append(int(c["slot"]))
+            arr[i] = LoopLocation(slots[-1], int(bool(c.get("do_loop_detection", do_loop_detection))), ex.ctypes.data if len(ex) else None, len(ex),
+                                  float(c.get("radius", radius)), float(c.get("min_score", min_score)))
+        res = (LoopLocationResult * max(n, 1))()
+        word = np.empty((n, self.max_desc), np.int32)
+        d2 = np.empty((n, self.max_desc), np.float32)
+        scores = np.empty((n, self.max_places), np.float32)
+        self.ctx.check(self.ctx.lib.svs_loop_add_locations(self.h, n, arr, res, word.ctypes.data, d2.ctypes.data, scores.ctypes.data))
+        self.raw_index = dict(results=bytes(res)[:n * C.sizeof(LoopLocationResult)], word=word, word_d2=d2, scores=scores)
+        out = LocationBatch()
+        for i in range(n):
+            m = self.n_place[slots[i]]
+            out.append(LocationOutput(slots[i], res[i], word[i, :m], d2[i, :m], scores[i]))
+        return out
+
+    def index_stage_times_ms(self):
+        """(words stage, scoring stage) of the last add_locations, from events; zeros unless set_timing(True)"""
+        ms = (C.c_float * 2)()
+        self.ctx.check(self.ctx.lib.svs_loop_index_stage_times(self.h, ms))
+        return float(ms[0]), float(ms[1])
 
     def set_timing(self, on=True):
         self.ctx.check(self.ctx.lib.svs_loop_set_timing(self.h, int(on)))
