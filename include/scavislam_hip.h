@@ -732,6 +732,56 @@ int svs_loop_add_locations(svs_loop *l, int n, const svs_loop_location *locs, sv
 /* profiling (svs_loop_set_timing): ms[2] = words stage (reset + distances), scoring stage (the other four launches) of the last svs_loop_add_locations */
 int svs_loop_index_stage_times(svs_loop *l, float *ms);
 
+/* ---- loop closure: training the visual vocabulary (what svs_loop_set_vocabulary takes).  The reference makes its words with a program of its own
+   (create_dictionary.cpp:144-177: cvflann::hierarchicalClustering with KMeansIndexParams(32, 11, FLANN_CENTERS_KMEANSPP), a cut through a 32-ary k-means tree
+   that yields 1 + 31 m words).  Here: FLAT Lloyd iterations with k-means++ seeding, which is what that cut approximates, and which yields the asked number of
+   words.  Needs a context and no svs_loop handle.  Semantics restated in tests/vocab_model.py (not pinned by the reference's binaries).
+   svs_vocab_train is BLOCKING.  h_desc [n][desc_dim] f32 on the host; every output is optional (NULL) and on the host.
+   Refused before anything is uploaded or launched: desc_dim not 64 or 128, n < 1, n_words < 1, n_words > n, iterations < 0, a component of h_desc (or h_init)
+   that is not finite or has |x| >= 4 (the pipeline's descriptors are unit vectors; the bound keeps every integer sum below 2^63): SVS_ERR_INVALID;
+   n > 2^21 (SVS_VOCAB_MAX_POINTS), n_words > SVS_LOOP_MAX_WORDS: SVS_ERR_CAPACITY.
+   1. Seeding (h_init NULL): k-means++ on the device.  splitmix64 and mulhi32 as for svs_loop_check_batch; mulhi64(a, b) = the high 64 bits of the 128-bit product.
+        i_0 = mulhi32(splitmix64(seed) >> 32, n).  Every point has a weight w_i, +inf at first.  After centre c-1 (point i_{c-1}, row y) is chosen, for every
+        point with row x:  s = 0.0; for k = 0 .. K-1: d = (double)x[k] - (double)y[k]; s = s + d * d   (f64, component order, no FMA);  w_i = min(w_i, s);
+        the chosen point's own weight is 0.  W_i = (uint64)(w_i * 2^28), truncated; T = sum W_i (exact: any order gives the same value).  T == 0 ends the
+        seeding with n_seeded = c words.  Otherwise r = mulhi64(splitmix64(seed ^ (1 << 62 | c)), T), and i_c is the smallest i whose inclusive prefix sum of
+        W exceeds r.  Word c is row i_c of h_desc.  h_seed_index [n_words] gets the indices, -1 behind n_seeded.  TWO launches per step (weights + block sums;
+        total, draw and search by one workgroup), queued without a host synchronisation in between: the chosen index stays on the device.
+      With h_init the start centres are its rows, n_seeded = 0 and h_seed_index is all -1.
+      The clustering goes on with k = n_seeded (h_init: n_words) words.
+   2. Assignment.  The word of a point is argmin_j of d2 = (|x|^2 + |c_j|^2) - 2 x.c_j in f32, clamped at 0, the lowest j wins an exact tie: the arithmetic of
+      svs_loop_add_locations pair for pair (the same tile walk and MFMA order; squared norms as svs_loop_set_vocabulary forms them).
+   3. Update.  q = (int64)rint((double)x[k] * 2^38); per word and component sum_q = sum of q over the word's members in int64 (exact, so independent of the
+      order); c[k] = (float)(((double)sum_q / (double)count) * 2^-38).  A word without members keeps its centre.
+   4. One iteration = assignment, then update.  h_changed[t] = points whose word differs from iteration t-1 (n for t = 0).  The loop ends after the first
+      iteration with changed == 0 (converged = 1) or after `iterations` of them; iterations_run counts them, and h_changed holds -1 behind it.
+   5. Output.  With drop_empty, the words without a member in the LAST iteration's assignment are left out and the order of the others is kept; n_empty counts
+      such words whether they are dropped or not (iterations == 0: there is no such assignment, n_empty = 0 and nothing is dropped).  n_words_out rows are
+      written to h_words [n_words][desc_dim] (rows behind n_words_out are 0).  ONE MORE assignment is then made against the words as returned: it gives
+      h_assign [n], h_assign_d2 [n] (the clamped f32 d2), h_count [n_words] (members per returned word, 0 behind n_words_out) and
+      inertia_q28 = sum over the points of (uint64)((double)d2 * 2^28).  So h_assign / h_assign_d2 are what svs_loop_add_locations with radius = +inf gives for
+      the same points against h_words.
+   6. The outputs are a function of the inputs alone: bit-identical on every repetition, on every context, whatever the launch shapes.
+   Flat, not hierarchical; weights are resolved to 2^-28. */
+#define SVS_VOCAB_MAX_POINTS 2097152
+typedef struct {
+  int32_t n_words;                     /* asked; 1 .. SVS_LOOP_MAX_WORDS, <= n */
+  int32_t iterations;                  /* Lloyd iterations at most; 11 (create_dictionary.cpp:150); 0: seeding + final assignment only */
+  uint64_t seed;
+  const float *h_init;                 /* [n_words][desc_dim] start centres, or NULL: k-means++ on the device */
+  int32_t drop_empty;                  /* 1: words without a member in the last iteration's assignment are left out, order kept */
+} svs_vocab_params;
+typedef struct {
+  int32_t n_words_out, n_seeded, iterations_run, converged, n_empty;
+  uint64_t inertia_q28;
+} svs_vocab_result;
+/* n_words 10000, iterations 11, seed 0, h_init NULL, drop_empty 1 */
+void svs_vocab_params_default(svs_vocab_params *p);
+int svs_vocab_train(svs_ctx *ctx, int desc_dim, int n, const float *h_desc, const svs_vocab_params *prm, float *h_words, svs_vocab_result *h_res,
+                    int32_t *h_seed_index, int32_t *h_assign, float *h_assign_d2, int32_t *h_count, int32_t *h_changed);
+/* profiling: ms[3] = seeding, the assignment launches of all iterations, the update launches of all iterations of the context's last svs_vocab_train (events) */
+int svs_vocab_stage_times(svs_ctx *ctx, float *ms);
+
 /* ---- back end: re-registration of a keyframe against the map.  Backend::localRegisterFrame (backend.cpp:190-199, 549-611) and Backend::globalLoopClosure
    (:201-219, 830-1001) share one shape -- project map points into a root keyframe (pointsVisibleInRoot :472-546 / the loop at :853-893), matchAndAlign
    (:725-784), gate and count (keyframesToRegister :615-722 / :904-961) -- and run here for a batch of requests as ONE chain of launches on the context's

@@ -722,6 +722,39 @@ class PlaceRecognizerGeom {
   bool ok_, error_ = false;
 };
 
+// calculateWordsAndSaveThem of the reference's dictionary program (create_dictionary.cpp:144-177) without the file: descriptors in, words_ out -- what
+// PlaceRecognizerGeom::setVocabulary takes.  Flat Lloyd iterations with k-means++ seeding on the device (svs_vocab_train) where the reference cuts a 32-ary
+// k-means tree; the asked number of words comes back unless words end up without members (or the points run out of distinct rows).
+class VocabularyTrainer {
+ public:
+  explicit VocabularyTrainer(const Context &c, int desc_dim = 64) : ctx_(c), desc_dim_(desc_dim) {
+    svs_vocab_params_default(&prm_);
+    std::memset(&last_, 0, sizeof last_);
+  }
+  void setIterations(int iterations) { prm_.iterations = iterations; }      // 11 (create_dictionary.cpp:150)
+  void setSeed(uint64_t seed) { prm_.seed = seed; }
+  void setDropEmpty(bool drop) { prm_.drop_empty = drop ? 1 : 0; }
+  // descriptors [n][desc_dim]; *words becomes [lastResult().n_words_out][desc_dim].  false: refused (Context::check has the reason)
+  bool createDictionary(int n, const float *descriptors, int target_num_words, std::vector<float> *words, std::vector<int32_t> *assignment = nullptr) {
+    if (!words || target_num_words < 1) return false;
+    prm_.n_words = target_num_words;
+    words->assign((size_t)target_num_words * desc_dim_, 0.f);
+    if (assignment) assignment->assign((size_t)(n > 0 ? n : 0), -1);
+    if (!ctx_.check(svs_vocab_train(ctx_.get(), desc_dim_, n, descriptors, &prm_, words->data(), &last_, nullptr, assignment ? assignment->data() : nullptr, nullptr,
+                                    nullptr, nullptr)))
+      return false;
+    words->resize((size_t)last_.n_words_out * desc_dim_);
+    return true;
+  }
+  const svs_vocab_result &lastResult() const { return last_; }
+
+ private:
+  const Context &ctx_;
+  int desc_dim_;
+  svs_vocab_params prm_;
+  svs_vocab_result last_;
+};
+
 // Backend::localRegisterFrame (backend.cpp:549-611) and Backend::globalLoopClosure (:830-1001) from the pose-graph walk onwards: the caller flattens the
 // reference's containers -- the candidate keyframes (larger_neighborhood + the anchors' vertices) into a table, the deduplicated point walk of pointsVisibleInRoot
 // (:480-498) / v_query.feature_table (:853) into a list whose kf_index names the anchor's table entry, the feature_table membership into observer rows -- and gets

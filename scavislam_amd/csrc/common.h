@@ -59,6 +59,7 @@ struct svs_ctx {
                               // "stereo_speckle_error_mask"), [8..21] the phase stamps of SVS_STEREO_DEBUG.  Shared by every svs_stereo of the context
   int xcd_swizzle = 1;        // "xcd_swizzle": tile kernels whose neighbouring tiles share image lines (FAST score, block matching, ...) hand every XCD a CONTIGUOUS range of
                               // the linear workgroup index (xcd_contiguous below) so the shared lines are fetched into one L2, not into 2-3; 0: the dispatcher's round robin (A/B)
+  float vocab_ms[3] = {0.f, 0.f, 0.f};      // svs_vocab_stage_times: seeding, assignment, update of the last svs_vocab_train (vocab.hip)
   int mo_legacy = 0;          // "mo_legacy": the record-walking motion-only kernel of rounds 1-2 instead of the fused one (A/B experiments)
 };
 // Kernels whose workgroups wait for each other INSIDE one launch (the latency-mode trackers, the multi-workgroup Cholesky) size their grids to a device they have

@@ -9,20 +9,16 @@
 // Further down, the front half of PlaceRecognizer::addLocation (placerecognizer.cpp:248-318) -- a visual word per descriptor, the inverted index, TF-IDF place
 // scores, the candidate test -- for a batch of places in SIX launches (svs_loop_add_locations; yardstick tests/place_model.py).
 #include "common.h"
+#include "loop_words.h"
 #include <math.h>
 #include <string.h>
 #include <algorithm>
 
 constexpr int LOOP_MAX_HYP = 256;
 constexpr int LOOP_MAX_DRAWS = 64;      // draws per hypothesis before it is given up (the reference loops forever)
-constexpr int LM_QROWS = 32;            // query rows per workgroup: the N side of one 32x32 MFMA tile, one query per lane
-constexpr int LM_TROWS = 128;           // train rows per LDS tile: 32 per wave
-constexpr int LM_KC = 64;               // descriptor columns per LDS tile (K = 128: two tiles per train block, one accumulator)
-constexpr int LM_LD4 = LM_KC / 4 + 1;   // tile row stride in float4 (one 16-byte slot of padding: fragment reads of 32 rows spread over the banks)
+// (the tile shape LM_QROWS x LM_TROWS x LM_KC of the distance walks: loop_words.h)
 constexpr int LR_THREADS = 512;
 constexpr double LOOP_JTOL = 8.881784197001252e-16;      // 2^-50: columns count as orthogonal when |p.q| <= this * |p| |q|
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 // one check as the kernels read it, followed by its [max_hyp][3] caller triples
 struct loop_check_dev {
@@ -90,13 +86,7 @@ __global__ __launch_bounds__(256) void loop_place_kernel(const float *__restrict
                                                         double *__restrict__ xyz, int make_xyz, loop_cam cam) {
   const int i = (int)(blockIdx.x * 256u + threadIdx.x);
   if (i >= n) return;
-  const float4 *row = reinterpret_cast<const float4 *>(desc + (size_t)i * K);
-  double s = 0.0;
-  for (int k = 0; k < K / 4; ++k) {
-    const float4 v = row[k];
-    s += (double)v.x * (double)v.x; s += (double)v.y * (double)v.y; s += (double)v.z * (double)v.z; s += (double)v.w * (double)v.w;
-  }
-  norm[i] = (float)s;
+  norm[i] = loop_sqnorm(desc + (size_t)i * K, K);
   if (make_xyz) {
     double x, y, z;
     loop_unmap_uvu(cam, uvu[3 * i], uvu[3 * i + 1], uvu[3 * i + 2], x, y, z);
@@ -186,12 +176,7 @@ __global__ __launch_bounds__(256) void loop_match_kernel(const float *__restrict
 }
 
 // ---- the RANSAC stage ---------------------------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ uint64_t loop_splitmix64(uint64_t z) {
-  z += 0x9E3779B97F4A7C15ull;
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  return z ^ (z >> 31);
-}
+// (loop_splitmix64: loop_words.h)
 // draw number d of hypothesis h (the header's text)
 __device__ __forceinline__ int loop_draw(uint64_t seed, int h, int d, int n) {
   const uint64_t z = loop_splitmix64(seed ^ (((uint64_t)(uint32_t)h << 32) | (uint32_t)d));
@@ -568,84 +553,19 @@ extern "C" int svs_loop_check_batch(svs_loop *l, int n_checks, const svs_loop_ch
 // share of a tile together and stores them to LDS when they have arrived.  A form that fetched the NEXT tile into registers under the MFMAs of the present one
 // kept 32 registers more alive (two waves per SIMD instead of three) and measured 5 to 9 % slower at both sizes (profiles/place_index.md): the workgroups of
 // the other chunks are what hides the load.
-constexpr int LW_CHUNK = 2 * LM_TROWS;
+// The walk itself is loop_words_walk (loop_words.h), shared with the vocabulary trainer (vocab.hip).
 template <int K>
 __global__ __launch_bounds__(256) void loop_words_kernel(const float *__restrict__ desc, const float *__restrict__ norm, size_t place_rows, const float *__restrict__ W,
                                                         const float *__restrict__ Wn, int n_words, const uint8_t *__restrict__ in, size_t in_stride,
                                                         unsigned long long *__restrict__ wkey, int max_desc) {
-  constexpr int NKC = K / LM_KC, PER = LM_TROWS * (LM_KC / 4) / 256;
-  __shared__ float4 s_tile[LM_TROWS * LM_LD4];
-  __shared__ float s_tnorm[LM_TROWS];
-  __shared__ unsigned long long s_best[4][LM_QROWS];
   const loop_loc_dev *lc = reinterpret_cast<const loop_loc_dev *>(in + (size_t)blockIdx.z * in_stride);
   const int nq = lc->n, q0 = (int)blockIdx.x * LM_QROWS;
   if (q0 >= nq) return;                                                    // (the grid is sized for the longest place of the call)
   const int c0 = (int)blockIdx.y * LW_CHUNK, c1 = min(n_words, c0 + LW_CHUNK);      // this workgroup's words; c0 < n_words by the grid
   const float *Q = desc + (size_t)lc->slot * place_rows * K, *Qn = norm + (size_t)lc->slot * place_rows;
-  const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6, r = lane & 31, hh = lane >> 5;
-  const bool qok = q0 + r < nq;
-  float4 qf[K / 8];
-#pragma unroll
-  for (int s = 0; s < K / 8; ++s)
-    qf[s] = qok ? *reinterpret_cast<const float4 *>(Q + (size_t)(q0 + r) * K + 8 * s + 4 * hh) : make_float4(0.f, 0.f, 0.f, 0.f);
-  const float qn = qok ? Qn[q0 + r] : 0.f;
-  unsigned long long best = ~0ull;
-  f32x16 acc;
-  for (int t0 = c0; t0 < c1; t0 += LM_TROWS) {
-    const bool mine = t0 + wave * 32 < c1;                                 // wave-uniform
-#pragma unroll
-    for (int e = 0; e < 16; ++e) acc[e] = 0.f;
-#pragma unroll
-    for (int kc = 0; kc < NKC; ++kc) {                                     // (unrolled: the query fragment is indexed by constants and stays in registers)
-      __syncthreads();                                                     // the previous tile has been read
-      float4 ld[PER];                                                      // all eight loads of the lane in flight, then the stores
-#pragma unroll
-      for (int u = 0; u < PER; ++u) {
-        const int i = tid + 256 * u, row = i >> 4, c4 = i & 15;
-        ld[u] = t0 + row < c1 ? *reinterpret_cast<const float4 *>(W + (size_t)(t0 + row) * K + kc * LM_KC + 4 * c4) : make_float4(0.f, 0.f, 0.f, 0.f);
-      }
-      const float ldn = kc == 0 && tid < LM_TROWS && t0 + tid < c1 ? Wn[t0 + tid] : 0.f;
-#pragma unroll
-      for (int u = 0; u < PER; ++u) {
-        const int i = tid + 256 * u;
-        s_tile[(i >> 4) * LM_LD4 + (i & 15)] = ld[u];
-      }
-      if (kc == 0 && tid < LM_TROWS) s_tnorm[tid] = ldn;
-      __syncthreads();
-      if (mine) {
-#pragma unroll
-        for (int ss = 0; ss < LM_KC / 8; ++ss) {
-          const float4 a = s_tile[(wave * 32 + r) * LM_LD4 + 2 * ss + hh], b = qf[kc * (LM_KC / 8) + ss];
-          acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.x, b.x, acc, 0, 0, 0);
-          acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.y, b.y, acc, 0, 0, 0);
-          acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.z, b.z, acc, 0, 0, 0);
-          acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.w, b.w, acc, 0, 0, 0);
-        }
-      }
-    }
-    if (mine) {
-#pragma unroll
-      for (int e = 0; e < 16; ++e) {
-        const int i = (e & 3) + 8 * (e >> 2) + 4 * hh, j = t0 + wave * 32 + i;
-        float d2 = (qn + s_tnorm[wave * 32 + i]) - 2.f * acc[e];
-        d2 = d2 < 0.f ? 0.f : d2;
-        const unsigned long long key = ((unsigned long long)__float_as_uint(d2) << 32) | (unsigned)j;
-        if (j < c1 && key < best) best = key;
-      }
-    }
-  }
-  {
-    const unsigned long long o = __shfl_xor(best, 32, 64);
-    best = o < best ? o : best;
-  }
-  if (lane < 32) s_best[wave][lane] = best;
-  __syncthreads();
-  if (tid < LM_QROWS && q0 + tid < nq) {
-    unsigned long long b = s_best[0][tid];
-#pragma unroll
-    for (int w = 1; w < 4; ++w) b = s_best[w][tid] < b ? s_best[w][tid] : b;
-    atomicMin(wkey + (size_t)blockIdx.z * max_desc + q0 + tid, b);
-  }
+  const unsigned long long b = loop_words_walk<K>(Q, Qn, nq, q0, W, Wn, c0, c1);
+  const int tid = (int)threadIdx.x;
+  if (tid < LM_QROWS && q0 + tid < nq) atomicMin(wkey + (size_t)blockIdx.z * max_desc + q0 + tid, b);
 }
 
 // the call's work arrays: keys to "nothing yet", first occurrences to "none", the counters to 0.  grid-stride over locations x max(max_desc, n_words)

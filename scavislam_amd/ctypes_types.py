@@ -143,6 +143,16 @@ class LoopLocationResult(C.Structure):
     _fields_ = [("number_of_words", C.c_int32), ("n_scored", C.c_int32), ("best_slot", C.c_int32), ("best_score", C.c_float), ("candidate", C.c_int32)]
 
 
+class VocabParams(C.Structure):
+    """svs_vocab_params: what svs_vocab_train clusters into (create_dictionary.cpp:144-177: 11 iterations, k-means++ centres)."""
+    _fields_ = [("n_words", C.c_int32), ("iterations", C.c_int32), ("seed", C.c_uint64), ("h_init", C.c_void_p), ("drop_empty", C.c_int32)]
+
+
+class VocabResult(C.Structure):
+    _fields_ = [("n_words_out", C.c_int32), ("n_seeded", C.c_int32), ("iterations_run", C.c_int32), ("converged", C.c_int32), ("n_empty", C.c_int32),
+                ("inertia_q28", C.c_uint64)]
+
+
 class SeedParams(C.Structure):
     """svs_seed_params: params_.newpoint_clearance, ui.num_max_points, ui.min_num_points, USE_N_LEVELS_FOR_MATCHING (stereo_frontend.cpp:319-331, :735-749)."""
     _fields_ = [("clearance", C.c_int32), ("num_max_points", C.c_int32), ("min_num_points", C.c_int32), ("n_levels", C.c_int32)]

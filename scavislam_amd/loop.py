@@ -5,6 +5,7 @@
 
   GeometricChecker.set_vocabulary(w)    <- words_ / flann_index_             placerecognizer.cpp:55-75
   GeometricChecker.add_locations(...)   <- addLocation from :248 to :318     visual words, inverted index, TF-IDF scores, the candidate test
+  train_vocabulary(ctx, descriptors, n) <- calculateWordsAndSaveThem         create_dictionary.cpp:144-177 (flat Lloyd + k-means++ instead of the tree cut)
 
 Detection and description (SURF) stay with the caller; this class takes a Place the way geometricCheck consumes it
 (descriptors, uvu_0_vec, optionally xyz_vec) and keeps it on the device.  There is no CPU path: every call goes to svs_loop_* of the HIP library.
@@ -13,7 +14,7 @@ import ctypes as C
 
 import numpy as np
 
-from .ctypes_types import Cam, LoopCheck, LoopLocation, LoopLocationResult, LoopResult
+from .ctypes_types import Cam, LoopCheck, LoopLocation, LoopLocationResult, LoopResult, VocabParams, VocabResult
 
 
 class LoopCheckOutput:
@@ -45,6 +46,59 @@ class LocationBatch(list):
     def candidates(self):
         """(query_slot, best_slot) of the locations whose best score passed min_score: what check_batch takes"""
         return [(o.slot, o.best_slot) for o in self if o.candidate]
+
+
+class VocabularyOutput:
+    """What svs_vocab_train returns: words [n_words_out][desc_dim] (set_vocabulary takes them as they are), seed_index [n_words] (-1 behind n_seeded),
+    assign / assign_d2 [n] against the words as returned, count [n_words_out], changed [iterations_run], result (the svs_vocab_result fields).
+    raw: the full-length arrays as the library wrote them (tests: byte comparisons)"""
+
+    def __init__(self, res, words, seed_index, assign, assign_d2, count, changed):
+        self.result = res
+        self.n_words_out, self.n_seeded, self.iterations_run, self.converged, self.n_empty, self.inertia_q28 = (
+            res.n_words_out, res.n_seeded, res.iterations_run, bool(res.converged), res.n_empty, int(res.inertia_q28))
+        self.raw = dict(words=words, seed_index=seed_index, assign=assign, assign_d2=assign_d2, count=count, changed=changed)
+        self.words, self.seed_index, self.assign, self.assign_d2 = words[:res.n_words_out], seed_index, assign, assign_d2
+        self.count, self.changed = count[:res.n_words_out], changed[:res.iterations_run]
+
+    def raw_bytes(self):
+        r = self.result
+        head = np.array([r.n_words_out, r.n_seeded, r.iterations_run, r.converged, r.n_empty, r.inertia_q28 & 0xffffffff, r.inertia_q28 >> 32], np.int64)
+        return [head.tobytes()] + [self.raw[k].tobytes() for k in ("words", "seed_index", "assign", "assign_d2", "count", "changed")]
+
+
+def train_vocabulary(ctx, descriptors, n_words, iterations=11, seed=0, init=None, drop_empty=True):
+    """k-means++ seeding and Lloyd iterations on the device (svs_vocab_train; the header has the semantics).  descriptors [n][64 or 128] f32 with |x| < 4,
+    init: [n_words][desc_dim] start centres instead of the seeding.  Blocking; returns a VocabularyOutput"""
+    d = np.ascontiguousarray(descriptors, np.float32)
+    if d.ndim != 2:
+        raise ValueError("descriptors [n][desc_dim] expected")
+    n, K = d.shape
+    nw = int(n_words)
+    ini = None
+    if init is not None:
+        ini = np.ascontiguousarray(init, np.float32)
+        if ini.shape != (nw, K):
+            raise ValueError("init [n_words][desc_dim] expected")
+    prm = VocabParams(nw, int(iterations), int(seed) & (2 ** 64 - 1), None if ini is None else ini.ctypes.data, int(bool(drop_empty)))
+    res = VocabResult()
+    m = max(nw, 0)
+    words = np.zeros((m, K), np.float32)
+    seed_index = np.full(m, -1, np.int32)
+    assign = np.full(n, -1, np.int32)
+    d2 = np.zeros(n, np.float32)
+    count = np.zeros(m, np.int32)
+    changed = np.full(max(int(iterations), 0), -1, np.int32)
+    ctx.call("svs_vocab_train", int(K), int(n), d.ctypes.data, C.byref(prm), words.ctypes.data, C.byref(res), seed_index.ctypes.data, assign.ctypes.data,
+             d2.ctypes.data, count.ctypes.data, changed.ctypes.data)
+    return VocabularyOutput(res, words, seed_index, assign, d2, count, changed)
+
+
+def vocabulary_stage_times_ms(ctx):
+    """(seeding, assignment, update) of the context's last train_vocabulary, from events: the launches of all iterations summed"""
+    ms = (C.c_float * 3)()
+    ctx.call("svs_vocab_stage_times", ms)
+    return float(ms[0]), float(ms[1]), float(ms[2])
 
 
 class GeometricChecker:
