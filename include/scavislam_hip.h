@@ -628,7 +628,7 @@ int svs_depth_to_disp(svs_ctx *ctx, const svs_cam *cam, const uint16_t *d_depth1
 
 /* ---- loop closure: the geometric check of PlaceRecognizer (placerecognizer.cpp:175-202) = cv::BFMatcher(NORM_L2).match + RanSaC<SE3Model>::compute
    (ransac.cpp:28-137, ransac_models.cpp:27-81,138-181, stereo_camera.cpp:36-52) for a batch of (query place, train place) pairs.  Descriptors come from any
-   extractor (SURF, the bag of words and Sim3Model / MONO stay with the caller).  Semantics restated in tests/loop_model.py (not pinned).
+   extractor (the reference's SURF is svs_surf_extract below, its bag of words svs_loop_add_locations; Sim3Model / MONO stay with the caller).  Semantics restated in tests/loop_model.py (not pinned).
    The handle holds a device-resident store of places, the counterpart of location_map_. -------------------------------------------------------------------*/
 typedef struct svs_loop svs_loop;
 /* desc_dim 64 or 128 floats per descriptor; at most max_desc descriptors per place (<= 2^21), max_places slots, max_hyp (<= 256) hypotheses per check,
@@ -682,7 +682,8 @@ int svs_loop_set_timing(svs_loop *l, int on);
 int svs_loop_stage_times(svs_loop *l, float *ms);
 
 /* ---- loop closure, the front half of PlaceRecognizer::addLocation (placerecognizer.cpp:248-318): visual words, the inverted index, TF-IDF place scores and
-   the candidate test.  SURF stays with the caller; a place's descriptors are loaded with svs_loop_set_place beforehand.
+   the candidate test.  A place's descriptors are loaded beforehand: with svs_loop_set_place from the host, or with svs_loop_set_place_from_surf from the device
+   arrays of svs_surf_extract (detection and description, placerecognizer.cpp:212-246).
    svs_loop_set_vocabulary: h_words [n_words][desc_dim] f32, the counterpart of words_ (data/surfwords10000.png: 9 983 x 64); squared norms are formed as for a
    place (f64 sum of the exact f32 squares, rounded once).  Allocates the index for the handle's max_places slots and resets it to EMPTY (a second call drops
    every location; the places themselves stay loaded).  BLOCKING.  n_words < 1: SVS_ERR_INVALID; n_words > SVS_LOOP_MAX_WORDS: SVS_ERR_CAPACITY.  The index is
@@ -781,6 +782,91 @@ int svs_vocab_train(svs_ctx *ctx, int desc_dim, int n, const float *h_desc, cons
                     int32_t *h_seed_index, int32_t *h_assign, float *h_assign_d2, int32_t *h_count, int32_t *h_changed);
 /* profiling: ms[3] = seeding, the assignment launches of all iterations, the update launches of all iterations of the context's last svs_vocab_train (events) */
 int svs_vocab_stage_times(svs_ctx *ctx, float *ms);
+
+/* ---- loop closure, the start of PlaceRecognizer::addLocation (placerecognizer.cpp:212-246): cv::SurfFeatureDetector(600, 2).detect on the keyframe's level-0
+   image, the disparity filter, cv::SurfDescriptorExtractor(2, 4, 2, false).compute -- for a batch of keyframes, device images in, device places and host records
+   out, no host round trip between the stages.  SURF is Bay, Ess, Tuytelaars, Van Gool, "Speeded-Up Robust Features", CVIU 2008; the arithmetic below restates
+   OpenCV 2.4's surf.cpp from its definitions.  OpenCV is not part of the reference tree, so none of this is pinned by the reference's binaries (DESIGN.md
+   section 4): the yardstick is the NumPy restatement tests/surf_model.py.  OpenCV ships SURF in its `nonfree` module; the feature therefore has a translation
+   unit (surf.hip), a handle and a build switch of its own (make SURF=0: every svs_surf_* call and svs_loop_set_place_from_surf return SVS_ERR_UNSUPPORTED,
+   svs_surf_params_default still fills the struct) and nothing else in the library depends on it.
+   Everything is compiled without contraction.  cvRound = round half to even (rint) of the value widened to f64; "f32" means every operation rounds to f32.
+   1. Integral image S: int32 [h + 1][w + 1], exact.  box(x1, y1, x2, y2) at origin (oy, ox) = S[oy+y1][ox+x1] + S[oy+y2][ox+x2] - S[oy+y2][ox+x1] - S[oy+y1][ox+x2].
+   2. Responses.  Octave o < n_octaves, layer l < n_octave_layers + 2: size = (9 + 6 l) << o, step = 1 << o.  Patterns {x1, y1, x2, y2, weight} on a 9-grid:
+      Dx {0,2,3,7,+1} {3,2,6,7,-2} {6,2,9,7,+1}; Dy {2,0,7,3,+1} {2,3,7,6,-2} {2,6,7,9,+1}; Dxy {1,1,4,4,+1} {5,1,8,4,-1} {1,5,4,8,-1} {5,5,8,8,+1}.  Scaled with
+      ratio = (float)size / 9: every corner is cvRound(ratio * corner) (f32 product), weight = w / ((float)(x2 - x1) * (y2 - y1)) (f32).  A pattern's value is a
+      DOUBLE accumulator over its boxes in the order written of (float)(int box sum) * weight (f32 product), cast to float.  det = dx * dy - (0.81f * dxy) * dxy,
+      trace = dx + dy (f32).  Samples (i, j), i < 1 + (h - size) / step, j < 1 + (w - size) / step, have their origin at (i step, j step) and are stored at
+      (i + margin, j + margin), margin = (size / 2) / step, of a layer of (h / step) x (w / step) that is zero elsewhere.
+   3. Maxima, middle layers 1 .. n_octave_layers only.  border = (size of layer + 1 / 2) / step + 1; positions border <= i < rows - border (j alike) with
+      val > hessian_threshold and val strictly greater than all 26 neighbours (N9[q][3 r + s] = layer - 1 + q at (i + r - 1, j + s - 1)).
+      centre = step (i - (size / 2) / step) + (size - 1) * 0.5f for y (from i) and x (from j); laplacian = sign of trace.
+   4. Refinement (f32).  b = (-(N9[1][5] - N9[1][3]) / 2, -(N9[1][7] - N9[1][1]) / 2, -(N9[2][4] - N9[0][4]) / 2);  A symmetric with
+      A00 = N9[1][3] - 2 N9[1][4] + N9[1][5], A11 = N9[1][1] - 2 N9[1][4] + N9[1][7], A22 = N9[0][4] - 2 N9[1][4] + N9[2][4],
+      A01 = (N9[1][8] - N9[1][6] - N9[1][2] + N9[1][0]) / 4, A02 = (N9[2][5] - N9[2][3] - N9[0][5] + N9[0][3]) / 4, A12 = (N9[2][7] - N9[2][1] - N9[0][7] + N9[0][1]) / 4,
+      each evaluated left to right.  A x = b by LU with partial pivoting: for r = 0, 1, 2: the pivot row is the FIRST row q >= r of the largest |A[q][r]|; a pivot
+      below 10 FLT_EPSILON in magnitude: no solution, the maximum is dropped; swap rows r and the pivot row (A from column r on, and b); d = -1 / A[r][r]; for
+      q > r: alpha = A[q][r] * d, A[q][s] += alpha * A[r][s] for s > r, b[q] += alpha * b[r]; A[r][r] = -d.  Back substitution for r = 2, 1, 0: s = b[r],
+      s -= A[r][q] * b[q] for q = r + 1 .. 2 in that order, x[r] = s * A[r][r].  Keep iff x != 0 and every |x_k| <= 1; then pt.x += x0 * step, pt.y += x1 * step,
+      size = cvRound(size + x2 * (size - size of layer - 1)).
+   5. Order: response descending, size descending, then y, x, octave, layer, i * cols + j ascending -- cv::KeypointGreater made total, so the order is a function
+      of the image.  The first max_keypoints of that order are kept (overflow flag: there were more).
+   6. Disparity filter (require_disparity; placerecognizer.cpp:222-238): rx = round((double)x), ry = round((double)y) (C round: half away from zero); a position
+      outside the image drops the keypoint; d = (double)disp[ry][rx]; uvu = (x, y, x - d) in f64; keep iff d > 0 (a NaN drops) and uvu[0] - uvu[2] > 0 (a d
+      below half an ulp of x would give a place that svs_loop_set_place refuses).  require_disparity 0 and no
+      d_disp: every keypoint is kept and uvu = (x, y, x).
+   7. Orientation.  s = size * 1.2f / 9.0f, haar = 2 cvRound(2 s); haar > h + 1 or > w + 1 removes the keypoint.  The 113 offsets (i, j), i outer, j inner, both
+      -6 .. 6 with i^2 + j^2 <= 36, x offset i, y offset j, weight g[i + 6] * g[j + 6] (f32 product) with g = the 13-tap f32 Gaussian of sigma 2.5: cf_i =
+      (float)exp(-0.5 / sigma^2 * x^2), x = i - (n - 1) / 2, sum the f32 taps in f64, g_i = (float)(cf_i * (1 / sum)).  Sample at x = cvRound((cx + i * s) -
+      (float)(haar - 1) / 2) (y alike, f32); skipped unless 0 <= x < w + 1 - haar and 0 <= y < h + 1 - haar; no sample left removes the keypoint.  Patterns on a
+      4-grid, scaled as in 2. with ratio (float)haar / 4: x {0,0,2,4,-1} {2,0,4,4,+1}, y {0,0,4,2,+1} {0,2,4,4,-1}; X = vx * weight, Y = vy * weight.  A sample's
+      angle = deg(Y, X) := (float)(atan2((double)Y, (double)X) * 57.29577951308232, + 360 if negative).  72 windows q at 5 q degrees take, IN SAMPLE ORDER, the
+      samples with d = |cvRound(angle) - 5 q|, d < 30 or d > 330, into f32 sums; the first window with the strictly greatest sumx^2 + sumy^2 (f32) wins;
+      dir = deg(sumy, sumx); angle = 360 - dir, 0 where |angle - 360| < FLT_EPSILON.
+      DEPARTURE: OpenCV's phase / fastAtan2 is a polynomial good to about 0.3 degrees; here both angles are f64 atan2.
+   8. Descriptor (64 floats).  win = (int)(21 * s).  rad = dir * (float)(pi / 180); sin_dir = (float)sin((double)rad), cos_dir alike (DEPARTURE: f64 functions on
+      the f32 argument, not sinf / cosf).  off = -(float)(win - 1) / 2; start_x = cx + off * cos_dir + off * sin_dir; start_y = cy - off * sin_dir + off * cos_dir;
+      row i starts after i times (start_x += sin_dir, start_y += cos_dir); along a row pixel_x += cos_dir, pixel_y -= sin_dir (running f32 sums).  WIN[i][j] =
+      image at (cvRound(pixel_y), cvRound(pixel_x)), both clamped to the image.  WIN is reduced to 21 x 21 by INTER_AREA's table: scale = win / 21 (f64); for
+      destination d: f1 = d scale, f2 = f1 + scale, cell = min(scale, win - f1), s1 = ceil(f1), s2 = min(floor(f2), win - 1), s1 = min(s1, s2); taps in this
+      order: (s1 - 1, (s1 - f1) / cell) if s1 - f1 > 1e-3; (s, 1 / cell) for s1 <= s < s2; (s2, min(f2 - s2, 1, cell) / cell) if f2 - s2 > 1e-3; weights f64,
+      stored f32.  Horizontal pass first (f32 sum of (float)pixel * weight in tap order), then vertical (f32 sum of weight * value), cvRound, clamp to 0 .. 255.
+      DEPARTURE: this table is used for every win, also multiples of 21 (OpenCV takes an integer fast path there).  For i, j < 20:
+      vx = (float)(P[i][j+1] - P[i][j] + P[i+1][j+1] - P[i+1][j]) * DW[i][j], vy = (float)(P[i+1][j] - P[i][j] + P[i+1][j+1] - P[i][j+1]) * DW[i][j], DW = outer
+      product (f32) of the 20-tap sigma 3.3 Gaussian.  4 x 4 cells of 5 x 5, cell (ci, cj) at index 4 (4 ci + cj): (sum vx, sum vy, sum |vx|, sum |vy|) in f32 in
+      raster order.  mag = f64 sum over the 64 values in index order of the f32 squares; every value is multiplied by (float)(1 / (sqrt(mag) + DBL_EPSILON)).
+   Keypoints removed in 6. - 8. leave every output array together, the order is preserved.  DEPARTURES from the reference: it reads the disparity image out of
+   bounds for a keypoint that rounds outside (here: dropped), and asserts that the extractor removes nothing (here: uvu stays aligned with the descriptors).
+   An image's outputs are a function of that image alone: identical bits alone or in a batch, at any stride, on every repetition (no float atomics; maxima are
+   appended in arrival order to a list that is then RANKED by the total order of 5., and the list grows until it holds every maximum). */
+typedef struct svs_surf svs_surf;
+typedef struct {
+  float hessian_threshold;                                  /* 600 */
+  int32_t n_octaves, n_octave_layers;                       /* 2, 2 */
+  int32_t require_disparity;                                /* 1: svs_surf_extract needs d_disp */
+} svs_surf_params;
+typedef struct { float x, y, size, angle, response; int32_t octave, laplacian, pad_; } svs_surf_keypoint;      /* 32 bytes */
+#define SVS_SURF_STAGES 6      /* integral, responses, maxima + refinement, order, orientation + descriptor, filter / compaction */
+void svs_surf_params_default(svs_surf_params *p);
+/* w x h images, at most max_batch per call and max_keypoints per image.  cam: the level-0 StereoCamera (its w, h, where set, must be w, h).
+   w h 255 >= 2^31: SVS_ERR_CAPACITY (the integral image is int32).  An image smaller than the largest filter ((9 + 6 (n_octave_layers + 1)) << (n_octaves - 1)),
+   n_octaves outside 1 .. 4, n_octave_layers outside 1 .. 4, or a largest descriptor window whose work arrays exceed 64 KiB of LDS: SVS_ERR_UNSUPPORTED */
+int svs_surf_create(svs_ctx *ctx, const svs_cam *cam, int w, int h, int max_batch, int max_keypoints, const svs_surf_params *prm, svs_surf **out);
+int svs_surf_destroy(svs_surf *s);
+/* BLOCKING.  d_img: u8 level-0 images (stride in bytes, bstride bytes between images), d_disp: f32 level-0 disparity (dstride, d_bstride in floats; NULL only
+   with require_disparity 0) -- e.g. what svs_frontend_input_view and the stereo stage leave on the device.  Host outputs, each optional:
+   h_count [n_batch]; h_overflow [n_batch]; h_kp [n_batch][max_keypoints]; h_uvu [n_batch][max_keypoints][3] f64; h_desc [n_batch][max_keypoints][64] f32 -- the
+   first h_count[b] rows of image b are written, the others are left alone.  The same arrays stay on the device in the handle until the next call.
+   n_batch < 1: SVS_ERR_INVALID; n_batch > max_batch: SVS_ERR_CAPACITY */
+int svs_surf_extract(svs_surf *s, const uint8_t *d_img, int stride, size_t bstride, const float *d_disp, int dstride, size_t d_bstride, int n_batch,
+                     int32_t *h_count, int32_t *h_overflow, svs_surf_keypoint *h_kp, double *h_uvu, float *h_desc);
+/* loads slot `slot` of the loop handle from image `image_index` of the last svs_surf_extract, device to device; squared norms and xyz are formed exactly as
+   svs_loop_set_place forms them, so the slot is bit-identical to svs_loop_set_place on the downloaded arrays.  The handle's count 0, a bad slot / image, or a last extract without disparity (uvu[0] - uvu[2] = 0,
+   which svs_loop_set_place refuses): SVS_ERR_INVALID; count > the loop handle's max_desc: SVS_ERR_CAPACITY; desc_dim of the loop handle not 64: SVS_ERR_INVALID */
+int svs_loop_set_place_from_surf(svs_loop *l, int slot, svs_surf *s, int image_index);
+/* profiling: bracket the stages with events; ms[SVS_SURF_STAGES] of the last svs_surf_extract */
+int svs_surf_set_timing(svs_surf *s, int on);
+int svs_surf_stage_times(svs_surf *s, float *ms);
 
 /* ---- back end: re-registration of a keyframe against the map.  Backend::localRegisterFrame (backend.cpp:190-199, 549-611) and Backend::globalLoopClosure
    (:201-219, 830-1001) share one shape -- project map points into a root keyframe (pointsVisibleInRoot :472-546 / the loop at :853-893), matchAndAlign

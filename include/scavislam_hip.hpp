@@ -653,10 +653,68 @@ class FrameRectifier {
   svs_rectify *rect_;
 };
 
+// placerecognizer.cpp:212-246 for a batch of keyframes: SurfFeatureDetector(600, 2).detect on the level-0 image, the disparity filter,
+// SurfDescriptorExtractor(2, 4, 2, false).compute (svs_surf_extract; the header has the arithmetic and its departures from OpenCV).  The places stay on the
+// device; the host copies are what Place::descriptors / uvu_0_vec hold.  A build without SURF (make SURF=0) reports !ok().
+class SurfPlaces {
+ public:
+  SurfPlaces(const Context &c, const svs_cam &stereo_cam, int w, int h, int max_batch = 1, int max_keypoints = 2048, double surf_thr = 600)
+      : ctx_(c), surf_(nullptr), w_(w), h_(h), max_batch_(max_batch), max_kp_(max_keypoints), n_(0), ok_(false) {
+    svs_surf_params prm;
+    svs_surf_params_default(&prm);
+    prm.hessian_threshold = (float)surf_thr;
+    ok_ = c.check(svs_surf_create(c.get(), &stereo_cam, w, h, max_batch, max_keypoints, &prm, &surf_));
+  }
+  ~SurfPlaces() { if (surf_) svs_surf_destroy(surf_); }
+  SurfPlaces(const SurfPlaces &) = delete;
+  SurfPlaces &operator=(const SurfPlaces &) = delete;
+  bool ok() const { return ok_; }
+  svs_surf *get() const { return surf_; }
+  // device images (stride / bstride in bytes) and device disparity (dstride / d_bstride in floats) of n_batch keyframes.  Blocking
+  bool addLocations(const uint8_t *d_img, int stride, size_t bstride, const float *d_disp, int dstride, size_t d_bstride, int n_batch) {
+    n_ = 0;
+    if (!ok_ || n_batch < 1 || n_batch > max_batch_) return false;
+    count_.assign(n_batch, 0); overflow_.assign(n_batch, 0);
+    kp_.resize((size_t)n_batch * max_kp_); uvu_.resize((size_t)n_batch * max_kp_ * 3); desc_.resize((size_t)n_batch * max_kp_ * 64);
+    if (!ctx_.check(svs_surf_extract(surf_, d_img, stride, bstride, d_disp, dstride, d_bstride, n_batch, count_.data(), overflow_.data(), kp_.data(), uvu_.data(),
+                                     desc_.data())))
+      return false;
+    n_ = n_batch;
+    return true;
+  }
+  // one keyframe from host memory (keyframe.pyr.at(0), keyframe.disp), uploaded first: tools and tests; a tracker's images are on the device already
+  bool addLocation(const uint8_t *image, const float *disp) {
+    void *d_img = nullptr, *d_disp = nullptr;
+    const size_t n = (size_t)w_ * h_;
+    bool ok = ok_ && ctx_.check(svs_malloc(ctx_.get(), n, &d_img)) && ctx_.check(svs_malloc(ctx_.get(), n * sizeof(float), &d_disp)) &&
+              ctx_.check(svs_memcpy_h2d(ctx_.get(), d_img, image, n)) && ctx_.check(svs_memcpy_h2d(ctx_.get(), d_disp, disp, n * sizeof(float))) &&
+              ctx_.check(svs_ctx_sync(ctx_.get())) &&
+              addLocations(static_cast<const uint8_t *>(d_img), w_, n, static_cast<const float *>(d_disp), w_, n, 1);
+    if (d_img) svs_free(ctx_.get(), d_img);
+    if (d_disp) svs_free(ctx_.get(), d_disp);
+    return ok;
+  }
+  int size(int image = 0) const { return image >= 0 && image < n_ ? count_[image] : 0; }
+  bool overflow(int image = 0) const { return image >= 0 && image < n_ && overflow_[image] != 0; }
+  const svs_surf_keypoint *keypoints(int image = 0) const { return kp_.data() + (size_t)image * max_kp_; }
+  const double *uvu_0_vec(int image = 0) const { return uvu_.data() + (size_t)image * max_kp_ * 3; }
+  const float *descriptors(int image = 0) const { return desc_.data() + (size_t)image * max_kp_ * 64; }
+
+ private:
+  const Context &ctx_;
+  svs_surf *surf_;
+  int w_, h_, max_batch_, max_kp_, n_;
+  bool ok_;
+  std::vector<int32_t> count_, overflow_;
+  std::vector<svs_surf_keypoint> kp_;
+  std::vector<double> uvu_;
+  std::vector<float> desc_;
+};
+
 // PlaceRecognizer (placerecognizer.cpp:175-322) on device-resident places: addPlace() is where addLocation hands a Place over (location_map_.insert, :299),
 // setVocabulary() takes words_, addLocation() is addLocation from :248 onwards (visual words, inverted index, TF-IDF scores, the > 2 test, then the geometric
-// check of the candidate), geometricCheck() is the BFMatcher + RanSaC<SE3Model>::compute(100, ...) pair and the inliers > 30 test.  Detection and SURF stay with
-// the caller.
+// check of the candidate), geometricCheck() is the BFMatcher + RanSaC<SE3Model>::compute(100, ...) pair and the inliers > 30 test.  Detection and description
+// (surf.detect, the disparity filter, surf_ext.compute, :212-246) are SurfPlaces above; addPlaceFromSurf() hands its places over on the device.
 struct DetectedLoop { int query_keyframe_id, loop_keyframe_id; double T_query_from_loop[12]; };      // T: [R | t] row-major
 class PlaceRecognizerGeom {
  public:
@@ -674,6 +732,12 @@ class PlaceRecognizerGeom {
   // Place::descriptors [n][desc_dim], uvu_0_vec [n][3], xyz_vec [n][3] (NULL: cam.unmap_uvu on the device)
   bool addPlace(int slot, int keyframe_id, int n, const float *descriptors, const double *uvu_0_vec, const double *xyz_vec = nullptr) {
     if (!ok_ || !ctx_.check(svs_loop_set_place(loop_, slot, n, descriptors, uvu_0_vec, xyz_vec))) return false;
+    keyframe_id_[slot] = keyframe_id;
+    return true;
+  }
+  // the place of image `image` of surf's last addLocation(s), device to device (svs_loop_set_place_from_surf): bit-identical to addPlace on its host copies
+  bool addPlaceFromSurf(int slot, int keyframe_id, const SurfPlaces &surf, int image = 0) {
+    if (!ok_ || !ctx_.check(svs_loop_set_place_from_surf(loop_, slot, surf.get(), image))) return false;
     keyframe_id_[slot] = keyframe_id;
     return true;
   }

@@ -8,7 +8,7 @@ import ctypes as C
 import os
 import weakref
 
-from .ctypes_types import BaParams, BaStats, Cam, FastGrid, LoopCheck, LoopLocation, LoopLocationResult, LoopResult, PoseOptParams, PoseOptStats, RegParams, RegRequest, RegResult, SeedArgs, SeedParams, SeedRequest, StereoParams, VocabParams, VocabResult
+from .ctypes_types import BaParams, BaStats, Cam, FastGrid, LoopCheck, LoopLocation, LoopLocationResult, LoopResult, PoseOptParams, PoseOptStats, RegParams, RegRequest, RegResult, SeedArgs, SeedParams, SeedRequest, StereoParams, SurfParams, VocabParams, VocabResult
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SVS_LIB_PATH") or os.path.join(_HERE, "libscavislam_hip.so")   # override = kernel A/B experiments only
@@ -197,6 +197,13 @@ _SIGS = {
     "svs_vocab_train": [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.POINTER(VocabParams), C.c_void_p, C.POINTER(VocabResult), C.c_void_p, C.c_void_p, C.c_void_p,
                         C.c_void_p, C.c_void_p],
     "svs_vocab_stage_times": [C.c_void_p, C.c_void_p],
+    "svs_surf_create": [C.c_void_p, C.POINTER(Cam), C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(SurfParams), C.POINTER(C.c_void_p)],
+    "svs_surf_destroy": [C.c_void_p],
+    "svs_surf_extract": [C.c_void_p, C.c_void_p, C.c_int, C.c_size_t, C.c_void_p, C.c_int, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                         C.c_void_p],
+    "svs_loop_set_place_from_surf": [C.c_void_p, C.c_int, C.c_void_p, C.c_int],
+    "svs_surf_set_timing": [C.c_void_p, C.c_int],
+    "svs_surf_stage_times": [C.c_void_p, C.c_void_p],
     "svs_reg_create": [C.c_void_p, C.POINTER(Cam), C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)],
     "svs_reg_destroy": [C.c_void_p],
     "svs_reg_register_batch": [C.c_void_p, C.c_int, C.POINTER(RegRequest), C.POINTER(RegParams), C.POINTER(RegResult), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
@@ -235,7 +242,7 @@ _SIGS = {
                             C.POINTER(C.c_int32)],
     "svs_ba_graph_stats": [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)],
 }
-EXPORTS = sorted(list(_SIGS) + ["svs_ctx_stream", "svs_last_error", "svs_api_version", "svs_pose_opt_params_default", "svs_seed_params_default", "svs_reg_params_default", "svs_vocab_params_default"])
+EXPORTS = sorted(list(_SIGS) + ["svs_ctx_stream", "svs_last_error", "svs_api_version", "svs_pose_opt_params_default", "svs_seed_params_default", "svs_reg_params_default", "svs_vocab_params_default", "svs_surf_params_default"])
 API_VERSION = 9      # SVS_API_VERSION of include/scavislam_hip.h this binding was written against
 
 
@@ -268,6 +275,8 @@ def load():
         lib.svs_reg_params_default.restype = None
         lib.svs_vocab_params_default.argtypes = [C.c_void_p]
         lib.svs_vocab_params_default.restype = None
+        lib.svs_surf_params_default.argtypes = [C.c_void_p]
+        lib.svs_surf_params_default.restype = None
         if lib.svs_api_version() != API_VERSION:
             raise SvsError(f"{LIB_PATH} was built with SVS_API_VERSION {lib.svs_api_version()}, this binding expects {API_VERSION}: rebuild (__graft_entry__.build())")
         _LIB = lib

@@ -140,6 +140,11 @@ int svs_process_matched_points_dev(svs_ctx *ctx, const svs_match_result *d_resul
 int svs_pointcloud_cpu_sem_levels(svs_ctx *ctx, const float *d_disp, int disp_stride, size_t disp_bstride, const svs_cam *cams, const double *d_T, float *const *d_cloud,
                                   const size_t *cloud_bstride, int batch);
 
+// internal: svs_loop_set_place from device arrays (loop.hip; used by svs_loop_set_place_from_surf in surf.hip), and the context a loop handle lives on
+struct svs_loop;
+int svs_loop_set_place_dev(svs_loop *l, int slot, int n, const float *d_desc, const double *d_uvu);
+svs_ctx *svs_loop_ctx(svs_loop *l);
+
 __host__ __device__ static inline int div_up(int a, int b) { return (a + b - 1) / b; }
 
 // Workgroup b of a launch is observed on XCD b % 8 (nothing promises it: speed only, never correctness).  Kernels whose neighbouring tiles share cache lines take their tile from

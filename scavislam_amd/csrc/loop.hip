@@ -481,6 +481,25 @@ extern "C" int svs_loop_set_place(svs_loop *l, int slot, int n, const float *h_d
   return SVS_OK;
 }
 
+// internal (common.h): svs_loop_set_place with the descriptors and uvu already on the device (svs_loop_set_place_from_surf, surf.hip).  Nothing is checked on
+// the host here: whoever made the arrays guarantees uvu[0] - uvu[2] > 0 for every row (svs_surf_extract's disparity filter keeps no other keypoint).  The
+// copies are device to device on the context's stream, norms and xyz by the same kernel
+int svs_loop_set_place_dev(svs_loop *l, int slot, int n, const float *d_desc, const double *d_uvu) {
+  svs_ctx *ctx = l ? l->ctx : nullptr;
+  SVS_REQUIRE(ctx, l && slot >= 0 && slot < l->max_places && n >= 1 && d_desc && d_uvu && l->K == 64);
+  LOOP_CAPACITY(ctx, n <= l->max_desc);
+  SVS_DEVICE(ctx);
+  const size_t nd = (size_t)n * l->K * sizeof(float), nu = (size_t)n * 3 * sizeof(double), row0 = (size_t)slot * l->max_desc;
+  SVS_HIP(ctx, hipMemcpyAsync(l->d_desc + row0 * l->K, d_desc, nd, hipMemcpyDeviceToDevice, ctx->stream));
+  SVS_HIP(ctx, hipMemcpyAsync(l->d_uvu + row0 * 3, d_uvu, nu, hipMemcpyDeviceToDevice, ctx->stream));
+  hipLaunchKernelGGL(loop_place_kernel, dim3(div_up(n, 256)), dim3(256), 0, ctx->stream, l->d_desc + row0 * l->K, l->K, n, l->d_norm + row0, l->d_uvu + row0 * 3,
+                     l->d_xyz + row0 * 3, 1, l->cam);
+  SVS_LAUNCH_CHECK(ctx);
+  l->n_place[slot] = n;
+  return SVS_OK;
+}
+svs_ctx *svs_loop_ctx(svs_loop *l) { return l ? l->ctx : nullptr; }
+
 extern "C" int svs_loop_set_timing(svs_loop *l, int on) {
   if (!l) return SVS_ERR_INVALID;
   l->timing = on ? 1 : 0;

@@ -153,6 +153,22 @@ class VocabResult(C.Structure):
                 ("inertia_q28", C.c_uint64)]
 
 
+class SurfParams(C.Structure):
+    """svs_surf_params: SurfFeatureDetector(600, 2) / SurfDescriptorExtractor(2, 4, 2, false) of placerecognizer.cpp:216, :240."""
+    _fields_ = [("hessian_threshold", C.c_float), ("n_octaves", C.c_int32), ("n_octave_layers", C.c_int32), ("require_disparity", C.c_int32)]
+
+    @classmethod
+    def reference(cls, hessian_threshold=600.0, n_octaves=2, n_octave_layers=2, require_disparity=True):
+        return cls(hessian_threshold, n_octaves, n_octave_layers, int(bool(require_disparity)))
+
+
+# svs_surf_keypoint
+SURF_KEYPOINT_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("size", "<f4"), ("angle", "<f4"), ("response", "<f4"), ("octave", "<i4"), ("laplacian", "<i4"),
+                                ("pad_", "<i4")])
+assert SURF_KEYPOINT_DTYPE.itemsize == 32
+SURF_STAGES = 6
+
+
 class SeedParams(C.Structure):
     """svs_seed_params: params_.newpoint_clearance, ui.num_max_points, ui.min_num_points, USE_N_LEVELS_FOR_MATCHING (stereo_frontend.cpp:319-331, :735-749)."""
     _fields_ = [("clearance", C.c_int32), ("num_max_points", C.c_int32), ("min_num_points", C.c_int32), ("n_levels", C.c_int32)]

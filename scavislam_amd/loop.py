@@ -7,14 +7,18 @@
   GeometricChecker.add_locations(...)   <- addLocation from :248 to :318     visual words, inverted index, TF-IDF scores, the candidate test
   train_vocabulary(ctx, descriptors, n) <- calculateWordsAndSaveThem         create_dictionary.cpp:144-177 (flat Lloyd + k-means++ instead of the tree cut)
 
-Detection and description (SURF) stay with the caller; this class takes a Place the way geometricCheck consumes it
-(descriptors, uvu_0_vec, optionally xyz_vec) and keeps it on the device.  There is no CPU path: every call goes to svs_loop_* of the HIP library.
+  SurfExtractor.extract(images, disp)   <- surf.detect / the disparity filter / surf_ext.compute   placerecognizer.cpp:212-246
+  GeometricChecker.set_place_from_surf  <- the same insert, device to device
+
+GeometricChecker takes a Place the way geometricCheck consumes it (descriptors, uvu_0_vec, optionally xyz_vec) and keeps it on the device; SurfExtractor makes
+one from a keyframe's level-0 image and disparity that are already there.  There is no CPU path: every call goes to svs_loop_* of the HIP library.
 """
 import ctypes as C
+import time
 
 import numpy as np
 
-from .ctypes_types import Cam, LoopCheck, LoopLocation, LoopLocationResult, LoopResult, VocabParams, VocabResult
+from .ctypes_types import SURF_KEYPOINT_DTYPE, SURF_STAGES, Cam, LoopCheck, LoopLocation, LoopLocationResult, LoopResult, SurfParams, VocabParams, VocabResult
 
 
 class LoopCheckOutput:
@@ -124,6 +128,11 @@ class GeometricChecker:
         self.ctx.check(self.ctx.lib.svs_loop_set_place(self.h, int(slot), int(n), d.ctypes.data, u.ctypes.data, None if x is None else x.ctypes.data))
         self.n_place[int(slot)] = int(n)
 
+    def set_place_from_surf(self, slot, surf, image_index):
+        """the place of image `image_index` of surf's last extract(), device to device (svs_loop_set_place_from_surf)"""
+        self.ctx.check(self.ctx.lib.svs_loop_set_place_from_surf(self.h, int(slot), surf.h, int(image_index)))
+        self.n_place[int(slot)] = int(surf.last_count[int(image_index)])
+
     def check_batch(self, checks, n_hyp=100, pixel_thr=2.5, seed=0):
         """checks: (query_slot, train_slot) pairs or dicts with query, train and optionally n_hyp, pixel_thr, seed, samples ([n_hyp][3] match indices)"""
         n = len(checks)
@@ -210,6 +219,86 @@ class GeometricChecker:
     def close(self):
         if self.h:
             self.ctx.lib.svs_loop_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class SurfPlace:
+    """One image's outputs of SurfExtractor.extract, cut to its count: keypoints (SURF_KEYPOINT_DTYPE), uvu [n][3] f64, descriptors [n][64] f32, overflow"""
+
+    def __init__(self, keypoints, uvu, descriptors, overflow):
+        self.keypoints, self.uvu, self.descriptors, self.overflow = keypoints, uvu, descriptors, bool(overflow)
+
+    def __len__(self):
+        return len(self.keypoints)
+
+
+class SurfExtractor:
+    """svs_surf_*: SURF detection, the disparity filter and description of a batch of keyframes on the device (the header has the semantics)."""
+
+    def __init__(self, ctx, cam, w, h, max_batch=1, max_keypoints=2048, params=None):
+        self.ctx, self.h = ctx, None
+        self.cam = cam if isinstance(cam, Cam) else Cam(cam["f"], cam["cx"], cam["cy"], cam["b"], int(w), int(h))
+        self.w, self.hgt, self.max_batch, self.max_keypoints = int(w), int(h), int(max_batch), int(max_keypoints)
+        self.params = params or SurfParams.reference()
+        h_ = C.c_void_p()
+        ctx.call("svs_surf_create", C.byref(self.cam), self.w, self.hgt, self.max_batch, self.max_keypoints, C.byref(self.params), C.byref(h_))
+        self.h = h_
+        ctx.children.add(self)
+        self.last_count = np.zeros(0, np.int32)
+        self.raw = None      # the full-length arrays of the last extract (tests: byte comparisons)
+
+    def extract_device(self, d_img, stride, bstride, d_disp, dstride, d_bstride, n_batch):
+        """device pointers (ints): u8 images (strides in bytes), f32 disparity (strides in floats; 0 / None without).  Blocking; returns [SurfPlace]"""
+        n, m = int(n_batch), self.max_keypoints
+        count, over = np.zeros(max(n, 1), np.int32), np.zeros(max(n, 1), np.int32)
+        kp = np.zeros((max(n, 1), m), SURF_KEYPOINT_DTYPE)
+        uvu = np.zeros((max(n, 1), m, 3), np.float64)
+        desc = np.zeros((max(n, 1), m, 64), np.float32)
+        t0 = time.perf_counter()
+        rc = self.ctx.lib.svs_surf_extract(self.h, d_img, int(stride), int(bstride), d_disp or None, int(dstride), int(d_bstride), n, count.ctypes.data,
+                                           over.ctypes.data, kp.ctypes.data, uvu.ctypes.data, desc.ctypes.data)
+        self.last_call_ms = (time.perf_counter() - t0) * 1e3      # wall time of the blocking library call alone
+        self.ctx.check(rc)
+        self.last_count = count[:n].copy()
+        self.raw = dict(count=count, overflow=over, keypoints=kp, uvu=uvu, descriptors=desc)
+        return [SurfPlace(kp[b, :count[b]], uvu[b, :count[b]], desc[b, :count[b]], over[b]) for b in range(n)]
+
+    def extract(self, images, disp=None, stride=None):
+        """images [n][h][w] u8 and disp [n][h][w] f32 on the host (convenience: uploaded through torch, `stride` pads the device rows)"""
+        import torch
+        img = np.ascontiguousarray(images, np.uint8)
+        n, h, w = img.shape
+        st = int(stride or w)
+        pad = np.zeros((n, h, st), np.uint8)
+        pad[:, :, :w] = img
+        d_img = torch.as_tensor(pad).cuda()
+        d_disp = None
+        if disp is not None:
+            dp = np.full((n, h, st), np.nan, np.float32)
+            dp[:, :, :w] = np.ascontiguousarray(disp, np.float32)
+            d_disp = torch.as_tensor(dp).cuda()
+        torch.cuda.synchronize()
+        out = self.extract_device(d_img.data_ptr(), st, h * st, d_disp.data_ptr() if d_disp is not None else None, st, h * st, n)
+        return out
+
+    def set_timing(self, on=True):
+        self.ctx.check(self.ctx.lib.svs_surf_set_timing(self.h, int(on)))
+
+    def stage_times_ms(self):
+        """(integral, responses, maxima, order, orientation + descriptor, compaction) of the last extract, from events; zeros unless set_timing(True)"""
+        ms = (C.c_float * SURF_STAGES)()
+        self.ctx.check(self.ctx.lib.svs_surf_stage_times(self.h, ms))
+        return tuple(float(v) for v in ms)
+
+    def close(self):
+        if self.h:
+            self.ctx.lib.svs_surf_destroy(self.h)
             self.h = None
 
     def __del__(self):
