@@ -18,6 +18,7 @@
 //    36*P(P+1)/2 + 12P + 1 doubles) and two scalars per LM trial; the 6P x 6P Cholesky is
 //    replicated (deterministic, no broadcast).
 #include "common.h"
+#include "pose.h"
 #include <climits>
 #include <algorithm>
 #include <cmath>

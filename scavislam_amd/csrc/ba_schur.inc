@@ -241,20 +241,6 @@ __device__ void d_so3_log(const double *R, double *w, double &theta) {
   w[0] = two_atan * q[1]; w[1] = two_atan * q[2]; w[2] = two_atan * q[3];
   theta = two_atan * n;
 }
-__device__ void d_pose_mul(const double *A, const double *Bm, double *Cm) {
-  double t[12];
-  for (int i = 0; i < 3; ++i) {
-    for (int j = 0; j < 4; ++j) t[4 * i + j] = A[4 * i] * Bm[j] + A[4 * i + 1] * Bm[4 + j] + A[4 * i + 2] * Bm[8 + j];
-    t[4 * i + 3] += A[4 * i + 3];
-  }
-  for (int i = 0; i < 12; ++i) Cm[i] = t[i];
-}
-__device__ void d_pose_inv(const double *A, double *Bm) {
-  double t[12];
-  for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) t[4 * i + j] = A[4 * j + i];
-  for (int i = 0; i < 3; ++i) t[4 * i + 3] = -(t[4 * i] * A[3] + t[4 * i + 1] * A[7] + t[4 * i + 2] * A[11]);
-  for (int i = 0; i < 12; ++i) Bm[i] = t[i];
-}
 __device__ void d_se3_log(const double *T, double *x) {
   double R[9], W[9], W2[9], Vi[9], th;
   for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) R[3 * i + j] = T[4 * i + j];
@@ -269,7 +255,6 @@ __device__ void d_se3_log(const double *T, double *x) {
 }
 // One wavefront per constraint; lane (i,j) = element of the 6x6 products, operands staged in LDS.
 // (A one-thread-per-constraint version spent 60 us in scratch-spilled serial 6x6x6 products.)
-__device__ __forceinline__ void wave_lds_sync() { __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_s_waitcnt(0xc07f); __builtin_amdgcn_wave_barrier(); }
 
 // one wave per constraint (lanes 0..63 of the calling workgroup); s_m: 8 x 36 doubles of LDS
 // 0 Adj(T21) 1 dl(e) 2 t1 3 J1 4 dl(-e) 5 J2 6 O*J1 7 O*J2
@@ -279,9 +264,9 @@ __device__ __forceinline__ void ba_constraint_body(const BaDev &B, int c, double
   const svs_ba_constraint &cc = B.cons[c];
   const double *poses = MODE == 0 ? B.poses : B.poses_trial;
   double T2i[12], t[12], err[6];
-  d_pose_inv(poses + 12 * cc.pose2, T2i);
-  d_pose_mul(cc.T_21, poses + 12 * cc.pose1, t);
-  d_pose_mul(t, T2i, t);
+  pose_inv(poses + 12 * cc.pose2, T2i);
+  pose_mul(cc.T_21, poses + 12 * cc.pose1, t);
+  pose_mul(t, T2i, t);
   d_se3_log(t, err);                                    // redundant per lane: ~300 flop
   double oe[6], e2 = 0;
 #pragma unroll
@@ -495,7 +480,7 @@ __global__ __launch_bounds__(NW * 64, (NW <= 4 && WC == 1) ? 2 : 1) void ba_land
   // one global atomic per WORKGROUP for the scalar sums: same-address f64 atomics serialise in L2 (~20 ns each), and one
   // per wave cost more than the rest of the back-substitution kernel
   if (MODE == 0) {
-    const double c = wave_sum_f64(lin.rho0);
+    const double c = wave_sum(lin.rho0);
     if (lane == 0 && c != 0.0) lds_add_f64(&s_scal[0], c);      // window init barrier above ordered the zeroing
   }
   // observer role: this lane owns pose ed.pose of its landmark.  A self edge (observer == anchor: R = I, y = x_a up to
@@ -616,8 +601,8 @@ __global__ __launch_bounds__(NW * 64, (NW <= 4 && WC == 1) ? 2 : 1) void ba_land
       for (int i = 0; i < 12; ++i) { Tno[i] = B.poses_trial[12 * (size_t)ed.pose + i]; Tna[i] = B.poses_trial[12 * (size_t)anchor + i]; }
       chi = edge_chi2(npsi, Tno, Tna, ed, B.cam, B.delta, B.robust);
     }
-    sc = wave_sum_f64(sc);
-    chi = wave_sum_f64(chi);
+    sc = wave_sum(sc);
+    chi = wave_sum(chi);
     __syncthreads();                                   // s_scal zeroed
     if (lane == 0) { lds_add_f64(&s_scal[0], chi); lds_add_f64(&s_scal[1], sc); }
     __syncthreads();
@@ -856,7 +841,7 @@ __device__ __forceinline__ void wide_block_sum(double (&v)[N], double *s_red /* 
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 #pragma unroll
   for (int i = 0; i < N; ++i) {
-    const double w = wave_sum_f64(v[i]);
+    const double w = wave_sum(v[i]);
     if (lane == 0) s_red[wave * N + i] = w;
   }
   __syncthreads();

@@ -193,7 +193,7 @@ __global__ __launch_bounds__(SOLVE_THREADS) void ba_solve_kernel(BaDev B, double
   // outputs: x, scale_p = sum x (lambda x + b_p), trial poses
   double sc = 0;
   for (int i = tid; i < n; i += SOLVE_THREADS) { const double xv = s_b[i]; x_out[i] = xv; sc += xv * (B.lambda * xv + B.bp[i]); }
-  sc = wave_sum_f64(sc);
+  sc = wave_sum(sc);
   if ((tid & 63) == 0 && sc != 0.0) atomic_add_f64(&B.scal[2], sc);
   for (int p = tid; p < P; p += SOLVE_THREADS) {
     double Tn[12];
@@ -285,9 +285,6 @@ __global__ __launch_bounds__(64) void ba_unpermute_kernel(BaDev B, const int *__
 // the solve's failure path (the LM trial is then rejected like a non-positive pivot).
 __device__ __forceinline__ void g_st(double *p, double v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 __device__ __forceinline__ double g_ld(const double *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ double bcast_f64(double v, int l) {      // value of lane l (wave-uniform l)
-  return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), l), __builtin_amdgcn_readlane(__double2loint(v), l));
-}
 __global__ __launch_bounds__(SOLVE_THREADS) void ba_solve_grid_kernel(BaDev B, double *__restrict__ x_out, double *__restrict__ linv_ws,
                                                                       const int *__restrict__ rowmax, unsigned *__restrict__ bar, unsigned epoch0) {
   extern __shared__ double smem[];
@@ -362,8 +359,8 @@ __global__ __launch_bounds__(SOLVE_THREADS) void ba_solve_grid_kernel(BaDev B, d
       for (int j = 0; j < 6; ++j) {
         double sv = Acol[j];                              // A[j][c], meaningful for c >= j
 #pragma unroll
-        for (int q = 0; q < j; ++q) sv -= bcast_f64(Ucol[q], j) * Ucol[q];      // U[q][j] U[q][c]
-        double d = bcast_f64(sv, j);
+        for (int q = 0; q < j; ++q) sv -= lane_bcast(Ucol[q], j) * Ucol[q];      // U[q][j] U[q][c]
+        double d = lane_bcast(sv, j);
         if (!(d > 0) || !isfinite(d)) { fail = 1; d = 1; }
         d = sqrt(d);
         rdv[j] = 1.0 / d;
@@ -374,7 +371,7 @@ __global__ __launch_bounds__(SOLVE_THREADS) void ba_solve_grid_kernel(BaDev B, d
       for (int r = 0; r < 6; ++r) {
         double sv = (r == c) ? 1.0 : 0.0;
 #pragma unroll
-        for (int q = 0; q < r; ++q) sv -= bcast_f64(Ucol[q], r) * Lic[q];      // U[q][r] Li[q][c] (Li[q][c] = 0 for q < c)
+        for (int q = 0; q < r; ++q) sv -= lane_bcast(Ucol[q], r) * Lic[q];      // U[q][r] Li[q][c] (Li[q][c] = 0 for q < c)
         Lic[r] = r >= c ? sv * rdv[r] : 0.0;
       }
       if (c < 6) {
@@ -547,7 +544,7 @@ __global__ __launch_bounds__(SOLVE_THREADS) void ba_solve_grid_kernel(BaDev B, d
   }
   double sc = 0;
   for (int i = tid; i < n; i += SOLVE_THREADS) { const double xv = s_b[i]; x_out[i] = xv; sc += xv * (B.lambda * xv + B.bp[i]); }
-  sc = wave_sum_f64(sc);
+  sc = wave_sum(sc);
   if ((tid & 63) == 0 && sc != 0.0) atomic_add_f64(&B.scal[2], sc);
   for (int p = tid; p < P; p += SOLVE_THREADS) {
     double Tn[12];
@@ -584,7 +581,8 @@ __device__ __forceinline__ void wave_lds_fence() { asm volatile("s_waitcnt lgkmc
 constexpr int PIPE_THREADS = 384;
 constexpr int PIPE_LD = 16;     // loader registers per lane and buffer: R*36 <= 64*PIPE_LD  => R <= 28
 
-// reciprocal by hardware estimate + 2 Newton steps
+// reciprocal by hardware estimate + 2 Newton steps.  The value of dense.hip's rcp_rn with the factors of the two correction products the other way round: the
+// compiler keeps that order in the v_fmac_f64 operands of the solve kernels, which were measured with this one (profiles/shared_helpers.md)
 __device__ __forceinline__ double rcp_nr(double d) {
   double x = __builtin_amdgcn_rcp(d);
   double e = __builtin_fma(-d, x, 1.0);
@@ -595,9 +593,6 @@ __device__ __forceinline__ double rcp_nr(double d) {
 // (Round 5 tried ONE Newton step on the pivot chain of the fused solve -- two FMAs of 8 issue cycles less per pivot, 70.5 -> 68.6 us -- on the assumption that
 // v_rcp_f64 delivers single-precision accuracy.  It does not: the landmark update of the recorded-graph test moved from ~1e-10 to 1.07e-6 of its size, which puts the
 // estimate near 2^-13.  Two steps stay.)
-__device__ __forceinline__ double readlane_f64(double v, int l) {
-  return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), l), __builtin_amdgcn_readlane(__double2loint(v), l));
-}
 
 // H + lambda I = U^T D U (U unit upper, D diagonal), organised in 6x6 block rows inside the envelope.
 //   row k:  U_kk (unit upper), Y_kj = D_k^-1 U_kk^-T A~_kj  (j > k);   Z_kj = D_k Y_kj
@@ -833,7 +828,7 @@ __global__ __launch_bounds__(PIPE_THREADS) void ba_solve_lds_kernel(BaDev B, dou
         // unit-upper back substitution across lanes 0..5 (ucol: row `lane` of U_kk, prefetched above)
 #pragma unroll
         for (int r = 5; r >= 1; --r) {
-          const double xr = readlane_f64(x, r);
+          const double xr = lane_bcast(x, r);
           if (lane < r) x = __builtin_fma(-ucol[r], xr, x);
         }
         if (lane < 6) s_b[6 * k + lane] = x;
@@ -847,7 +842,7 @@ __global__ __launch_bounds__(PIPE_THREADS) void ba_solve_lds_kernel(BaDev B, dou
   const long long t_back = wall_clock64();
   double sc = 0;
   for (int i = tid; i < n; i += PIPE_THREADS) { const double xv = s_b[i]; x_out[i] = xv; sc += xv * (B.lambda * xv + B.bp[i]); }
-  sc = wave_sum_f64(sc);
+  sc = wave_sum(sc);
   if ((tid & 63) == 0 && sc != 0.0) atomic_add_f64(&B.scal[2], sc);
   for (int p = tid; p < P; p += PIPE_THREADS) {
     double Tn[12];
@@ -1045,11 +1040,11 @@ __global__ __launch_bounds__(FUSE_THREADS) void ba_solve_fused_kernel(BaDev B, d
     double rd[6];
 #pragma unroll
     for (int q = 0; q < 6; ++q) {
-      const double rj = rcp_nr(readlane_f64(a[q], pl + q));
+      const double rj = rcp_nr(lane_bcast(a[q], pl + q));
       rd[q] = rj;
 #pragma unroll
       for (int r = q + 1; r < 6; ++r) {
-        const double u = readlane_f64(a[q], pl + r) * rj;            // U_pp[q][r]
+        const double u = lane_bcast(a[q], pl + r) * rj;            // U_pp[q][r]
         a[r] = __builtin_fma(-u, a[q], a[r]);
       }
     }
@@ -1255,10 +1250,10 @@ __global__ __launch_bounds__(FUSE_THREADS) void ba_solve_fused_kernel(BaDev B, d
             double xs[6];
 #pragma unroll
             for (int rr = 5; rr >= 1; --rr) {
-              xs[rr] = readlane_f64(acc, pl + rr);
+              xs[rr] = lane_bcast(acc, pl + rr);
               acc = __builtin_fma(piv ? -ucol[rr] : 0.0, xs[rr], acc);
             }
-            xs[0] = readlane_f64(acc, pl);
+            xs[0] = lane_bcast(acc, pl);
             if (piv) {
               s_b[6 * k + r] = acc;                                   // x_k
               if (publish && k >= m0) xpub[6 * (k - m0) + r] = acc;
@@ -1325,10 +1320,10 @@ __global__ __launch_bounds__(FUSE_THREADS) void ba_solve_fused_kernel(BaDev B, d
             for (int rr = 1; rr < 6; ++rr) cm[rr] = piv ? ucol[rr] : 0.0;
 #pragma unroll
             for (int rr = 5; rr >= 1; --rr) {
-              xs[rr] = readlane_f64(acc, pl + rr);
+              xs[rr] = lane_bcast(acc, pl + rr);
               acc = __builtin_fma(-cm[rr], xs[rr], acc);
             }
-            xs[0] = readlane_f64(acc, pl);
+            xs[0] = lane_bcast(acc, pl);
             if (piv) {
               s_b[6 * k + r] = acc;                                   // x_k
               if (publish && k >= m0) xpub[6 * (k - m0) + r] = acc;
@@ -1370,7 +1365,7 @@ __global__ __launch_bounds__(FUSE_THREADS) void ba_solve_fused_kernel(BaDev B, d
     x_out[g] = xv;
     sc += xv * (B.lambda * xv + B.bp[g]);
   }
-  sc = wave_sum_f64(sc);
+  sc = wave_sum(sc);
   if ((tid & 63) == 0 && sc != 0.0) atomic_add_f64(&B.scal[2], sc);
   for (int p = tid; p < Pe; p += FUSE_THREADS) {
     double Tn[12];

@@ -175,14 +175,14 @@ __global__ __launch_bounds__(TS_THREADS) void ba_solve_tiles_kernel(BaDev B, dou
         double s0 = acol[j], s1 = 0.0, s2 = 0.0, s3 = 0.0;      // A[j][c] - sum_q U[q][j] U[q][c] (meaningful for c >= j), four chains
 #pragma unroll
         for (int q = 0; q < j; ++q) {
-          const double m = -bcast_f64(Ucol[q], j);
+          const double m = -lane_bcast(Ucol[q], j);
           if ((q & 3) == 0) s0 = __builtin_fma(m, Ucol[q], s0);
           else if ((q & 3) == 1) s1 = __builtin_fma(m, Ucol[q], s1);
           else if ((q & 3) == 2) s2 = __builtin_fma(m, Ucol[q], s2);
           else s3 = __builtin_fma(m, Ucol[q], s3);
         }
         const double sv = (s0 + s1) + (s2 + s3);
-        double d = bcast_f64(sv, j);
+        double d = lane_bcast(sv, j);
         if (!(d > 0) || !(d < 1.7976931348623157e308)) { fail = 1; d = 1; }
         // 1 / sqrt(d) from the hardware estimate and two Newton steps (sqrt and a division in IEEE form are ~50 dependent instructions each, 24 times on this chain)
         double y = __builtin_amdgcn_rsq(d);
@@ -339,7 +339,7 @@ __global__ __launch_bounds__(TS_THREADS) void ba_solve_tiles_kernel(BaDev B, dou
         double xs = 0.0;
 #pragma unroll
         for (int j = TS_N - 1; j >= 0; --j) {
-          const double xj = bcast_f64(rhs * rdr, j);
+          const double xj = lane_bcast(rhs * rdr, j);
           if (rr == j) xs = xj;
           rhs = __builtin_fma(-s_piv[rr * TS_N + j], xj, rhs);      // (rows below j get zeros of the upper factor: harmless)
         }
@@ -353,7 +353,7 @@ __global__ __launch_bounds__(TS_THREADS) void ba_solve_tiles_kernel(BaDev B, dou
   }
   double sc = 0;
   for (int i = tid; i < n; i += TS_THREADS) { const double xv = s_sol[i]; x_out[i] = xv; sc += xv * (B.lambda * xv + B.bp[i]); }
-  sc = wave_sum_f64(sc);
+  sc = wave_sum(sc);
   if (lane == 0 && sc != 0.0) atomic_add_f64(&B.scal[2], sc);
   for (int p = tid; p < P; p += TS_THREADS) {
     double Tn[12];

@@ -1,4 +1,4 @@
-// common.h -- context, error plumbing and wave64 helpers shared by the gfx950 kernels.
+// common.h -- context and error plumbing shared by the gfx950 kernels; brings in the leaf device helpers (devutil.h).
 // Target: MI355X (gfx950, CDNA4, wave64) only.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -9,6 +9,7 @@
 
 #include "../../include/scavislam_hip.h"
 #include "owned.h"
+#include "devutil.h"
 
 struct svs_ctx {
   int device = 0;
@@ -58,7 +59,7 @@ struct svs_ctx {
   DevBuf<int> stereo_err;     // device, [32], zeroed at svs_ctx_create: [0] the give-up bits the strip speckle filter's bounded walks OR in (svs_ctx_get_stat
                               // "stereo_speckle_error_mask"), [8..21] the phase stamps of SVS_STEREO_DEBUG.  Shared by every svs_stereo of the context
   int xcd_swizzle = 1;        // "xcd_swizzle": tile kernels whose neighbouring tiles share image lines (FAST score, block matching, ...) hand every XCD a CONTIGUOUS range of
-                              // the linear workgroup index (xcd_contiguous below) so the shared lines are fetched into one L2, not into 2-3; 0: the dispatcher's round robin (A/B)
+                              // the linear workgroup index (devutil.h: xcd_contiguous) so the shared lines are fetched into one L2, not into 2-3; 0: the dispatcher's round robin (A/B)
   float vocab_ms[3] = {0.f, 0.f, 0.f};      // svs_vocab_stage_times: seeding, assignment, update of the last svs_vocab_train (vocab.hip)
   int mo_legacy = 0;          // "mo_legacy": the record-walking motion-only kernel of rounds 1-2 instead of the fused one (A/B experiments)
 };
@@ -144,31 +145,3 @@ int svs_pointcloud_cpu_sem_levels(svs_ctx *ctx, const float *d_disp, int disp_st
 struct svs_loop;
 int svs_loop_set_place_dev(svs_loop *l, int slot, int n, const float *d_desc, const double *d_uvu);
 svs_ctx *svs_loop_ctx(svs_loop *l);
-
-__host__ __device__ static inline int div_up(int a, int b) { return (a + b - 1) / b; }
-
-// Workgroup b of a launch is observed on XCD b % 8 (nothing promises it: speed only, never correctness).  Kernels whose neighbouring tiles share cache lines take their tile from
-// this bijective remap of the linear workgroup index instead: XCD x works through the contiguous range [x * n / 8, (x + 1) * n / 8) in dispatch order, so the lines two neighbours
-// share arrive in ONE L2 (any n, also n % 8 != 0).
-__device__ __forceinline__ unsigned xcd_contiguous(unsigned id, unsigned n) {
-  const unsigned q = n >> 3, r = n & 7u, x = id & 7u, k = id >> 3;
-  return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + k;
-}
-
-// ---- wave64 reductions (DPP/bpermute via __shfl; no LDS, no volatile warp idioms) -----------
-__device__ __forceinline__ int wave_sum_i32(int v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-__device__ __forceinline__ float wave_sum_f32(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-__device__ __forceinline__ int lane_id() { return threadIdx.x & 63; }

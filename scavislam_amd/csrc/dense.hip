@@ -13,6 +13,7 @@
 //    LDS broadcasts, so a frame costs one launch instead of ~90 launch+sync+D2H round trips.
 #include "common.h"
 #include "lm6.h"
+#include "pose.h"
 #include "seqsum.h"
 #include <algorithm>
 #include <climits>
@@ -65,7 +66,7 @@ struct LevelArgsG {
 };
 __device__ __forceinline__ float4 load_f4(const float *p) { return *reinterpret_cast<const float4 *>(p); }
 __device__ __forceinline__ float4 load_f4(const SVS_AS1 float *p) { const svs_f4 v = *(const SVS_AS1 svs_f4 *)p; return make_float4(v.x, v.y, v.z, v.w); }
-__device__ __forceinline__ uint32_t load_u32_unaligned(const uint8_t *p) { uint32_t w; __builtin_memcpy(&w, p, 4); return w; }
+__device__ __forceinline__ uint32_t load_u32_unaligned(const uint8_t *p) { return ld_unaligned<uint32_t>(p); }      // (the pair exists for taps_u8_issue, which takes either pointer)
 __device__ __forceinline__ uint32_t load_u32_unaligned(const SVS_AS1 uint8_t *p) {
   typedef uint32_t u32_unaligned __attribute__((aligned(1)));
   return *(const SVS_AS1 u32_unaligned *)p;
@@ -182,9 +183,8 @@ __device__ __forceinline__ void sample_cpu_sem(const LA &L, const double *T, con
   const float4 c4 = in.c4;
   bool ok = in_range && (c4.w > 0);
   const double xp0 = c4.x, xp1 = c4.y, xp2 = c4.z;
-  const double x = T[0] * xp0 + T[1] * xp1 + T[2] * xp2 + T[3];
-  const double y = T[4] * xp0 + T[5] * xp1 + T[6] * xp2 + T[7];
-  const double z = T[8] * xp0 + T[9] * xp1 + T[10] * xp2 + T[11];
+  double x, y, z;
+  pose_act(T, xp0, xp1, xp2, x, y, z);
   const double rz = rcp_rn(z);
   float uvx = (float)(L.cam.f * div_rn(x, z, rz) + L.cam.cx);
   float uvy = (float)(L.cam.f * div_rn(y, z, rz) + L.cam.cy);
@@ -1181,9 +1181,8 @@ __global__ __launch_bounds__(256) void residual_image_cpu_sem_kernel(LevelArgs L
   float4 o = make_float4(0.f, 1.f, 0.f, 1.f);
   if (c4.w > 0) {
     const double xp0 = c4.x, xp1 = c4.y, xp2 = c4.z;
-    const double x = T[0] * xp0 + T[1] * xp1 + T[2] * xp2 + T[3];
-    const double y = T[4] * xp0 + T[5] * xp1 + T[6] * xp2 + T[7];
-    const double z = T[8] * xp0 + T[9] * xp1 + T[10] * xp2 + T[11];
+    double x, y, z;
+    pose_act(T, xp0, xp1, xp2, x, y, z);
     const float uvx = (float)(L.cam.f * (x / z) + L.cam.cx);
     const float uvy = (float)(L.cam.f * (y / z) + L.cam.cy);
     bool ok = fabsf(uvx) < 1e9f && fabsf(uvy) < 1e9f;

@@ -596,11 +596,6 @@ __global__ __launch_bounds__(256) void convert_f32_kernel(const uint8_t *__restr
   if (x >= w || y >= h) return;
   dst[b * d_b + (size_t)y * ds + x] = (float)src[b * s_b + (size_t)y * ss + x] * (float)(1. / 255.);
 }
-__device__ __forceinline__ int refl101(int i, int n) {
-  if (n == 1) return 0;
-  while (i < 0 || i >= n) i = i < 0 ? -i : 2 * n - 2 - i;
-  return i;
-}
 // cv::gpu::pyrDown on f32 (ASSUMED OpenCV 2.4.2 gpu semantics, see oracle/vision.c): columns first, then rows, taps in
 // ascending order, REFLECT_101.  One lane per output pixel: 25 taps from L1/L2 (the source row set of neighbouring lanes
 // overlaps 5/2-fold); the level images are 1.2 MB + 0.3 MB per frame, this is not where the time goes.
@@ -612,7 +607,7 @@ __global__ __launch_bounds__(256) void pyr_down_f32_kernel(const float *__restri
   const float *s = src + b * s_b;
   int xs[5], ys[5];
 #pragma unroll
-  for (int t = 0; t < 5; ++t) { xs[t] = refl101(2 * x - 2 + t, w); ys[t] = refl101(2 * y - 2 + t, h); }
+  for (int t = 0; t < 5; ++t) { xs[t] = reflect101(2 * x - 2 + t, w); ys[t] = reflect101(2 * y - 2 + t, h); }
   float col[5];
 #pragma unroll
   for (int t = 0; t < 5; ++t) {

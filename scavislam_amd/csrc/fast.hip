@@ -52,7 +52,7 @@ struct FastParams {
   uint32_t *cand; int *cand_n;      // cand_n [batch][n_tiles]
   int *cell_tile0, *cell_ntile;     // [ncell_total]: tiles of a cell are contiguous in the tile list
   int n_tiles;
-  int swz;                          // tiles in XCD-contiguous order (common.h: xcd_contiguous)
+  int swz;                          // tiles in XCD-contiguous order (devutil.h: xcd_contiguous)
 };
 constexpr int CAND_CAP = 2048;      // per 64x32 tile = its pixels
 constexpr int BM_LDS_MAX = 144 * 1024;      // LDS bytes of the largest cell's bitmap + row offsets the compaction may use (checked at svs_fast_create)

@@ -18,6 +18,7 @@
 // told to keep (Frame::clone, keyframes.h:72-83), the candidate points (ap_map) and the FAST threshold state -- per stream.
 #include "common.h"
 #include "fast_view.h"
+#include "pose.h"
 #include "seed.h"
 #include <string.h>
 #include <algorithm>
@@ -27,22 +28,15 @@ namespace {
 constexpr int MAX_GROUPS = 64;
 
 // T_cur_from_w = T_cur_from_actkey * T_actkey_from_w and T_w_from_actkey = T_actkey_from_w^-1 (matcher.cpp:326-330), formed on the
-// device from the tracked pose so that the matcher needs no host round trip.  Operation order of the oracle / the host mirror:
-// (a0 b0 + a1 b1) + a2 b2, then + t; this file is built without contraction.  One workgroup per stream.
+// device from the tracked pose so that the matcher needs no host round trip.  One workgroup per stream.
 __global__ void frontend_pose_kernel(const double *__restrict__ T_cur_from_actkey, const double *__restrict__ T_actkey_from_w,
                                      double *__restrict__ T_cur_from_w, double *__restrict__ T_w_from_actkey) {
   if (threadIdx.x != 0) return;
   const size_t s = (size_t)blockIdx.x * 12;
   const double *A = T_cur_from_actkey + s, *Bm = T_actkey_from_w + s;
   double *Tcw = T_cur_from_w + s, *Twa = T_w_from_actkey + s;
-  for (int i = 0; i < 3; ++i) {
-    for (int j = 0; j < 4; ++j) Tcw[4 * i + j] = A[4 * i] * Bm[j] + A[4 * i + 1] * Bm[4 + j] + A[4 * i + 2] * Bm[8 + j];
-    Tcw[4 * i + 3] += A[4 * i + 3];
-  }
-  double o[12];
-  for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) o[4 * i + j] = Bm[4 * j + i];
-  for (int i = 0; i < 3; ++i) o[4 * i + 3] = -(o[4 * i] * Bm[3] + o[4 * i + 1] * Bm[7] + o[4 * i + 2] * Bm[11]);
-  for (int i = 0; i < 12; ++i) Twa[i] = o[i];
+  pose_inv(Bm, Twa);
+  pose_mul(A, Bm, Tcw);
 }
 
 // matchAndTrack's neighbour cut (stereo_frontend.cpp:1000-1024): the new-point list of neighbour j is matched only while

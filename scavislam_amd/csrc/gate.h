@@ -2,15 +2,15 @@
 // (keyframesToRegister / globalLoopClosure): one definition, identical bits.
 #pragma once
 #include "common.h"
+#include "pose.h"
 
 namespace {
 // f = obs - map_uvu(T xyz) (stereo_camera.cpp:37-44); J = SE3XYZ_STEREO::frameJac (transformations.h:424-447) if wanted
 template <bool JAC>
 __device__ __forceinline__ void mo_residual(const double *T, const svs_match_result &o, const svs_cam &cam, double *f, double *J) {
   const double *q = o.xyz_actkey;
-  const double x = T[0] * q[0] + T[1] * q[1] + T[2] * q[2] + T[3];
-  const double y = T[4] * q[0] + T[5] * q[1] + T[6] * q[2] + T[7];
-  const double z = T[8] * q[0] + T[9] * q[1] + T[10] * q[2] + T[11];
+  double x, y, z;
+  pose_act(T, q[0], q[1], q[2], x, y, z);
   const double fl = cam.f;
   f[0] = o.obs[0] - (x / z * fl + cam.cx);
   f[1] = o.obs[1] - (y / z * fl + cam.cy);

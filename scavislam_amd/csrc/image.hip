@@ -218,16 +218,9 @@ extern "C" int svs_timer_stop_ms(svs_ctx *c, float *ms) {
 }
 
 // ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ int reflect101(int i, int n) {
-  if (n == 1) return 0;
-  while (i < 0 || i >= n) { i = i < 0 ? -i : 2 * n - 2 - i; }
-  return i;
-}
-
 // One pyrDown step, no LDS: a lane produces a 4 x 2 patch of output pixels from a 7-row x 11-byte source footprint
 // held in registers (three unaligned dword loads per row), horizontal [1 4 6 4 1] per row with V_DOT4_U32_U8, the two
 // vertical combinations on packed u16 pairs; `(s+128)>>8`; one dword store per output row.
-__device__ __forceinline__ uint32_t ld_u32u(const uint8_t *p) { uint32_t v; __builtin_memcpy(&v, p, 4); return v; }
 // COPY: the lane also stores the 8 x 4 source pixels that only it covers (columns 2 ox .. 2 ox + 7, rows 2 oy .. 2 oy + 3: exactly the byte-aligned dwords
 // d01 / d12 of its four middle rows) into `cpy` -- the front end takes a caller's device frame into its own level-0 buffer while it builds level 1,
 // instead of with a copy kernel of its own (one read of the frame instead of two).
@@ -281,7 +274,7 @@ __global__ __launch_bounds__(256) void pyr_down_u8_kernel(const uint8_t *__restr
       y = y < 0 ? -y : y;
       y = y >= h ? 2 * h - 2 - y : y;
       const uint8_t *p = src + (size_t)y * ss;
-      D0[r] = ld_u32u(p + (left ? 0 : sx0)); D1[r] = ld_u32u(p + sx0 + 4); D2[r] = ld_u32u(p + off2);
+      D0[r] = ld_unaligned<uint32_t>(p + (left ? 0 : sx0)); D1[r] = ld_unaligned<uint32_t>(p + sx0 + 4); D2[r] = ld_unaligned<uint32_t>(p + off2);
     }
   } else {
 #pragma unroll 1
@@ -289,9 +282,9 @@ __global__ __launch_bounds__(256) void pyr_down_u8_kernel(const uint8_t *__restr
       const uint8_t *p = src + (size_t)reflect101(sy0 + r, h) * ss;
       uint32_t d0, d1, d2;
       if (fast) {
-        d0 = __builtin_amdgcn_perm(0u, ld_u32u(p + (left ? 0 : sx0)), sel0);
-        d1 = ld_u32u(p + sx0 + 4);
-        d2 = __builtin_amdgcn_perm(0u, ld_u32u(p + off2), sel2);
+        d0 = __builtin_amdgcn_perm(0u, ld_unaligned<uint32_t>(p + (left ? 0 : sx0)), sel0);
+        d1 = ld_unaligned<uint32_t>(p + sx0 + 4);
+        d2 = __builtin_amdgcn_perm(0u, ld_unaligned<uint32_t>(p + off2), sel2);
       } else {
         uint32_t bt[12];
 #pragma unroll

@@ -1,7 +1,8 @@
 // lm6.h -- the 6x6 step of the front end's Levenberg-Marquardt loops (f64): solve and SE3 update exp(x) * T, each in two spellings.
 //  * d_solve6 / d_se3_exp_mul: one lane, out of line -- the record-walking refinement kernel (motion.hip) and the full-resolution tracker (dense_full.hip), whose
 //    LM step runs on one lane while the workgroup waits;
-//  * wave_solve6 / mo2_exp_mul: seven lanes of a wave, everything in registers -- the quarter-grid tracker (dense.hip) and the fused refinement kernel (motion.hip).
+//  * wave_solve6 / mo2_exp_mul: seven lanes of a wave, everything in registers (broadcasts: lane_bcast, devutil.h) -- the quarter-grid tracker (dense.hip) and the
+//    fused refinement kernel (motion.hip).
 // Included by translation units built with contraction off.  ba.hip has its own SE3 exponential (ba_solve.inc: power series, built with contraction on) and does not
 // include this header.
 #pragma once
@@ -71,10 +72,6 @@ __device__ void d_se3_exp_mul(const double *x, const double *T, double *Tn) {   
   }
 }
 
-__device__ __forceinline__ double mo2_bcast(double v, int src_lane) {      // src_lane is a compile-time constant after unrolling
-  const int lo = __builtin_amdgcn_readlane(__double2loint(v), src_lane), hi = __builtin_amdgcn_readlane(__double2hiint(v), src_lane);
-  return __hiloint2double(hi, lo);
-}
 // A x = b for a symmetric positive definite 6x6 system on seven lanes of a wave: lane c < 6 holds column c of A in col[0..6), lane 6 holds b.
 // Gauss-Jordan, the multipliers of a step broadcast from the pivot column's lane; no pivoting (the reference's ldlt() pivots, which an SPD matrix
 // does not need).  Every lane returns x in x[0..6).
@@ -84,18 +81,18 @@ __device__ __forceinline__ void wave_solve6(const double (&col)[6], double (&x)[
   for (int r = 0; r < 6; ++r) a[r] = col[r];
 #pragma unroll
   for (int k = 0; k < 6; ++k) {
-    const double ip = 1.0 / mo2_bcast(a[k], k);
+    const double ip = 1.0 / lane_bcast(a[k], k);
     const double ak = a[k] * ip;               // row k of this lane's column, scaled
 #pragma unroll
     for (int r = 0; r < 6; ++r) {
       if (r == k) continue;
-      const double m = mo2_bcast(a[r], k);     // element (r, k) of the pivot column
+      const double m = lane_bcast(a[r], k);     // element (r, k) of the pivot column
       a[r] -= m * ak;
     }
     a[k] = ak;
   }
 #pragma unroll
-  for (int r = 0; r < 6; ++r) x[r] = mo2_bcast(a[r], 6);
+  for (int r = 0; r < 6; ++r) x[r] = lane_bcast(a[r], 6);
 }
 // exp(x) * T with everything in registers (d_se3_exp_mul above is an out-of-line call on arrays in scratch memory)
 __device__ __forceinline__ void mo2_exp_mul(const double (&x)[6], const double (&T)[12], double (&Tn)[12]) {

@@ -176,10 +176,9 @@ __global__ __launch_bounds__(256) void loop_match_kernel(const float *__restrict
 }
 
 // ---- the RANSAC stage ---------------------------------------------------------------------------------------------------------------------------------
-// (loop_splitmix64: loop_words.h)
 // draw number d of hypothesis h (the header's text)
 __device__ __forceinline__ int loop_draw(uint64_t seed, int h, int d, int n) {
-  const uint64_t z = loop_splitmix64(seed ^ (((uint64_t)(uint32_t)h << 32) | (uint32_t)d));
+  const uint64_t z = splitmix64(seed ^ (((uint64_t)(uint32_t)h << 32) | (uint32_t)d));
   return (int)(((z >> 32) * (uint64_t)(uint32_t)n) >> 32);
 }
 

@@ -11,14 +11,6 @@ constexpr int LW_CHUNK = 2 * LM_TROWS;  // vocabulary rows per workgroup of the 
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
-// the mixer of every counter-based draw of the loop-closure code (the header's splitmix64)
-__host__ __device__ __forceinline__ uint64_t loop_splitmix64(uint64_t z) {
-  z += 0x9E3779B97F4A7C15ull;
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  return z ^ (z >> 31);
-}
-
 // squared norm of a row of K floats: f64 sum of the exact f32 squares in component order, rounded once
 __device__ __forceinline__ float loop_sqnorm(const float *__restrict__ rowp, int K) {
   const float4 *row = reinterpret_cast<const float4 *>(rowp);

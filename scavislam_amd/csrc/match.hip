@@ -20,45 +20,18 @@
 #include "common.h"
 
 #include "fast_view.h"
+#include "pose.h"
 #include <algorithm>
 
 namespace {
 
-__device__ __forceinline__ void d_pose_act(const double *T, const double *x, double *y) {
-  double a = T[0] * x[0] + T[1] * x[1] + T[2] * x[2] + T[3];
-  double b = T[4] * x[0] + T[5] * x[1] + T[6] * x[2] + T[7];
-  double c = T[8] * x[0] + T[9] * x[1] + T[10] * x[2] + T[11];
-  y[0] = a; y[1] = b; y[2] = c;
-}
-__device__ __forceinline__ void d_pose_mul(const double *A, const double *B, double *C) {
-  double t[12];
-#pragma unroll
-  for (int i = 0; i < 3; ++i) {
-#pragma unroll
-    for (int j = 0; j < 4; ++j) t[4 * i + j] = A[4 * i] * B[j] + A[4 * i + 1] * B[4 + j] + A[4 * i + 2] * B[8 + j];
-    t[4 * i + 3] += A[4 * i + 3];
-  }
-#pragma unroll
-  for (int i = 0; i < 12; ++i) C[i] = t[i];
-}
-__device__ __forceinline__ void d_pose_inv(const double *A, double *B) {
-  double t[12];
-#pragma unroll
-  for (int i = 0; i < 3; ++i)
-#pragma unroll
-    for (int j = 0; j < 3; ++j) t[4 * i + j] = A[4 * j + i];
-#pragma unroll
-  for (int i = 0; i < 3; ++i) t[4 * i + 3] = -(t[4 * i] * A[3] + t[4 * i + 1] * A[7] + t[4 * i + 2] * A[11]);
-#pragma unroll
-  for (int i = 0; i < 12; ++i) B[i] = t[i];
-}
 __device__ __forceinline__ bool d_in_frame(const svs_cam &c, int u, int v, int border) {
   return u >= border && v >= border && u < c.w - border && v < c.h - border;
 }
 __device__ __forceinline__ void d_warp_f(const double *T, double depth, const svs_cam &cam, double ku, double kv, double *o) {
   double p[3] = {depth * ((ku - cam.cx) / cam.f), depth * ((kv - cam.cy) / cam.f), depth * 1.0};
   double q[3];
-  d_pose_act(T, p, q);
+  pose_act(T, p, q);
   o[0] = cam.f * (q[0] / q[2]) + cam.cx;
   o[1] = cam.f * (q[1] / q[2]) + cam.cy;
 }
@@ -137,7 +110,7 @@ struct MatchParams {
   // optional (the one-call front end, few keyframes): the tracked pose and the active keyframe's pose per stream -- match_predict_kernel<true> then forms the two poses of
   // matcher.cpp:326-330 and the per-keyframe relative poses itself (what frontend_pose_kernel + match_pose_kernel did in two launches of their own between tracker and matcher)
   const double *src_T, *src_Ta;
-  int swz;                // match_kernel3 takes its blocks in XCD-contiguous order (common.h: xcd_contiguous)
+  int swz;                // match_kernel3 takes its blocks in XCD-contiguous order (devutil.h: xcd_contiguous)
 };
 
 // The two relative poses a candidate needs depend only on (camera stream, anchor keyframe), not on
@@ -162,12 +135,12 @@ __global__ void match_pose_kernel(MatchParams M, double *__restrict__ out) {
   if (kf >= A.n_kf) return;
   double kfT[12], Tcw[12], Twk[12], t0[12], t1[12];
   for (int i = 0; i < 12; ++i) { kfT[i] = A.d_kfs[(size_t)slot * A.kf_bstride + kf].T_anchor_from_w[i]; Tcw[i] = A.d_T_cur_from_w[(size_t)slot * 12 + i]; Twk[i] = A.d_T_w_from_actkey[(size_t)slot * 12 + i]; }
-  d_pose_inv(kfT, t0);
-  d_pose_mul(Tcw, t0, t1);
+  pose_inv(kfT, t0);
+  pose_mul(Tcw, t0, t1);
   double *o = out + ((size_t)slot * A.n_kf + kf) * 24;
   for (int i = 0; i < 12; ++i) o[i] = t1[i];
-  d_pose_mul(kfT, Twk, t0);
-  d_pose_inv(t0, t1);
+  pose_mul(kfT, Twk, t0);
+  pose_inv(t0, t1);
   for (int i = 0; i < 12; ++i) o[12 + i] = t1[i];
 }
 
@@ -199,14 +172,14 @@ __global__ __launch_bounds__(64) void match_predict_kernel(MatchParams M) {
       double Tc[12], Ta[12], Tcw[12], Twk[12], kfT[12], t0[12], t1[12];
 #pragma unroll
       for (int i = 0; i < 12; ++i) { Tc[i] = M.src_T[(size_t)slot * 12 + i]; Ta[i] = M.src_Ta[(size_t)slot * 12 + i]; kfT[i] = A.d_kfs[(size_t)slot * A.kf_bstride + kf].T_anchor_from_w[i]; }
-      d_pose_mul(Tc, Ta, Tcw);
-      d_pose_inv(Ta, Twk);
-      d_pose_inv(kfT, t0);
-      d_pose_mul(Tcw, t0, t1);
+      pose_mul(Tc, Ta, Tcw);
+      pose_inv(Ta, Twk);
+      pose_inv(kfT, t0);
+      pose_mul(Tcw, t0, t1);
 #pragma unroll
       for (int i = 0; i < 12; ++i) s_kfT[kf][i] = t1[i];
-      d_pose_mul(kfT, Twk, t0);
-      d_pose_inv(t0, t1);
+      pose_mul(kfT, Twk, t0);
+      pose_inv(t0, t1);
 #pragma unroll
       for (int i = 0; i < 12; ++i) s_kfT[kf][12 + i] = t1[i];
     }
@@ -227,7 +200,7 @@ __global__ __launch_bounds__(64) void match_predict_kernel(MatchParams M) {
     double T_cur_from_anchor[12], xyz_cur[3];
 #pragma unroll
     for (int i = 0; i < 12; ++i) T_cur_from_anchor[i] = kfT[i];
-    d_pose_act(T_cur_from_anchor, ap.xyz_anchor, xyz_cur);
+    pose_act(T_cur_from_anchor, ap.xyz_anchor, xyz_cur);
     const double uv0 = cam.f * (xyz_cur[0] / xyz_cur[2]) + cam.cx;
     const double uv1 = cam.f * (xyz_cur[1] / xyz_cur[2]) + cam.cy;
     const double depth_cur = 1. / xyz_cur[2], depth_anchor = 1. / ap.xyz_anchor[2];
@@ -247,7 +220,7 @@ __global__ __launch_bounds__(64) void match_predict_kernel(MatchParams M) {
       double T_actkey_from_anchor[12];
 #pragma unroll
       for (int i = 0; i < 12; ++i) T_actkey_from_anchor[i] = kfT[12 + i];
-      d_pose_act(T_actkey_from_anchor, ap.xyz_anchor, pr.xyz_actkey);
+      pose_act(T_actkey_from_anchor, ap.xyz_anchor, pr.xyz_actkey);
       const int lvl = ap.anchor_level, R = A.search_radius;
       const svs_keyframe &kf = A.d_kfs[(size_t)slot * A.kf_bstride + ap.kf_index];
       pr.kimg = kf.pyr[lvl]; pr.kstride = kf.stride[lvl];
@@ -274,8 +247,6 @@ __global__ __launch_bounds__(64) void match_predict_kernel(MatchParams M) {
 // ---- the corner bitmap of fast.hip (fast.hip, LevelDev): pixel (x, y) of cell column ci is bit x + gap * ci of row y; rows end in >= 8 zero bytes ----
 typedef uint32_t U4 __attribute__((ext_vector_type(4)));
 typedef uint32_t U2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ U4 ld_u4u(const uint8_t *p) { U4 v; __builtin_memcpy(&v, p, 16); return v; }      // 16 bytes from any address: one global_load_dwordx4
-__device__ __forceinline__ U2 ld_u2u(const uint8_t *p) { U2 v; __builtin_memcpy(&v, p, 8); return v; }
 // one pixel (any x inside the image), the cell column found by compares: the general matcher, whose windows may be wider than a cell
 __device__ __forceinline__ bool corner_bit(const uint8_t *row, int x, int cw, int gx, int gap) {
   int ci = 0;
@@ -355,7 +326,7 @@ __global__ __launch_bounds__(256) void match_kernel(MatchParams M, svs_match_res
         }
         keyv = val;
       }
-      const int sumA = wave_sum_i32(keyv), sumAA = wave_sum_i32(keyv * keyv);
+      const int sumA = wave_sum(keyv), sumAA = wave_sum(keyv * keyv);
       if (sumA * sumA - sumAA < A.thr_std * A.thr_std * 64) status = SVS_MATCH_TEXTURE;
       else {
         // ---- window scan + ZNSSD of every candidate corner ----------------------------------
@@ -533,7 +504,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
         int ci = 0;
         for (int q = 1; q < gx; ++q) ci += xl >= q * cw;
         const int pb = xl + gap * ci;
-        const U2 w = ld_u2u(bm + (size_t)cy * bm_stride + (pb >> 3));
+        const U2 w = ld_unaligned<U2>(bm + (size_t)cy * bm_stride + (pb >> 3));
         lo = window_bits(w, pb, cx0, ci + 1 < gx ? (ci + 1) * cw : 0x7fffffff, gap) & span_mask(cx0, min(8, side - g8), xlo, xhi);
       }
     };
@@ -564,7 +535,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
       }
       keyv = val;
     }
-    const int sumA = wave_sum_i32(keyv), sumAA = wave_sum_i32(keyv * keyv);
+    const int sumA = wave_sum(keyv), sumAA = wave_sum(keyv * keyv);
     if (sumA * sumA - sumAA < A.thr_std * A.thr_std * 64) status = SVS_MATCH_TEXTURE;
     else {
       const uint8_t *cimg = A.d_cur_pyr[lvl] + (size_t)slot * A.cur_bstride[lvl];
@@ -743,8 +714,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
     const uint8_t *bm = Lp->bm + (size_t)slot * Lp->bm_bstride + (pp->pb_lo >> 3);
     const int bm_stride = Lp->bm_stride, yhi = Lp->yhi;
     const bool col_ok = go && x0 < Lw;
-    if (col_ok && sub < side && cy >= 6 && cy < yhi) w0 = ld_u2u(bm + (size_t)cy * bm_stride);
-    if (col_ok && side > 16 && cyx >= 6 && cyx < yhi) w1 = ld_u2u(bm + (size_t)cyx * bm_stride);
+    if (col_ok && sub < side && cy >= 6 && cy < yhi) w0 = ld_unaligned<U2>(bm + (size_t)cy * bm_stride);
+    if (col_ok && side > 16 && cyx >= 6 && cyx < yhi) w1 = ld_unaligned<U2>(bm + (size_t)cyx * bm_stride);
   }
   // ---- (2) warpAffinve, requests: the centre 8x8 of the 10x10 patch (KEY_PATCH, matcher.cpp:376-381), lane = (row, half): four pixels = one packed
   // dword.  The common case -- a warp close to a translation -- has the lane's four samples on one source row pair within 8 columns: two 8-byte
@@ -778,7 +749,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
                         (unsigned)(xis[3] - xis[0]) <= 6u && xis[0] + 8 <= Lw;
     if (oneRow) {
       const uint8_t *q = kimg + (size_t)ymin * kstride + xis[0];
-      const U2 ra = ld_u2u(q), rb = ld_u2u(q + kstride), rc = ld_u2u(q + (ymin + 2 < Lh ? 2 : 1) * (ptrdiff_t)kstride);      // (row y+2 is only used by pixels on row y+1, whose y+2 is inside)
+      const U2 ra = ld_unaligned<U2>(q), rb = ld_unaligned<U2>(q + kstride), rc = ld_unaligned<U2>(q + (ymin + 2 < Lh ? 2 : 1) * (ptrdiff_t)kstride);      // (row y+2 is only used by pixels on row y+1, whose y+2 is inside)
       px0 = ra.x; px1 = ra.y; px2 = rb.x; px3 = rb.y; px4 = rc.x; px5 = rc.y;
       flags |= 16u | (uint32_t)(yis[0] - ymin) << 5 | (uint32_t)(yis[1] - ymin) << 6 | (uint32_t)(yis[2] - ymin) << 7 | (uint32_t)(yis[3] - ymin) << 8;
       offs = (uint32_t)(xis[1] - xis[0]) << 8 | (uint32_t)(xis[2] - xis[0]) << 16 | (uint32_t)(xis[3] - xis[0]) << 24;
@@ -827,7 +798,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
 #pragma unroll
     for (int r = 0; r < 8; ++r)
       if (r >= r_lo && r < r_hi) {
-        v[r] = act ? ld_u2u(q) : U2{0u, 0u};
+        v[r] = act ? ld_unaligned<U2>(q) : U2{0u, 0u};
         q += cstride;
         asm volatile("" : "+v"(q));
       }

@@ -6,6 +6,7 @@
 #include "common.h"
 #include "gate.h"
 #include "lm6.h"
+#include "pose.h"
 #include <algorithm>
 
 namespace {
@@ -283,9 +284,8 @@ __device__ __forceinline__ void mo2_terms(const double (&T)[12], const MoObs &ob
                                           double &max_diag) {
   static_assert(JAC || !FIRST, "the first sweep needs the Jacobian");
   const double *q = ob.q;
-  const double X = T[0] * q[0] + T[1] * q[1] + T[2] * q[2] + T[3];
-  const double Y = T[4] * q[0] + T[5] * q[1] + T[6] * q[2] + T[7];
-  const double Z = T[8] * q[0] + T[9] * q[1] + T[10] * q[2] + T[11];
+  double X, Y, Z;
+  pose_act(T, q[0], q[1], q[2], X, Y, Z);
   const double fl = cam.f, iz = 1.0 / Z, fiz = fl * iz, Xb = X - cam.b;
   double f0 = ob.o[0] - (X * fiz + cam.cx), f1 = ob.o[1] - (Y * fiz + cam.cy), f2 = ob.o[2] - (Xb * fiz + cam.cx);
   // frameJac (transformations.h:424-447): rows (A 0 C yC zA-xC -yA), (0 A D -zA+yD -xD xA), (A 0 E yE zA-xE -yA) with A = -f/z, C = f x/z^2, ...
@@ -543,7 +543,7 @@ __global__ __launch_bounds__(MO2_THREADS) void motion_only_fused_kernel(const sv
 #pragma unroll
         for (int r = 0; r < 6; ++r) a[r] = col[r] + (r == lane ? mu : 0.0);
 #pragma unroll
-        for (int r = 0; r < 6; ++r) bmax = fmax(bmax, fabs(mo2_bcast(col[r], 6)));
+        for (int r = 0; r < 6; ++r) bmax = fmax(bmax, fabs(lane_bcast(col[r], 6)));
         wave_solve6(a, delta);
         double Tc[12], Tx[12];
 #pragma unroll

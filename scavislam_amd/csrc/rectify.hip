@@ -96,8 +96,6 @@ extern "C" int svs_rectify_create(svs_ctx *ctx, int w, int h, int max_batch, con
   return SVS_OK;
 }
 
-__device__ __forceinline__ uint32_t rect_ld_u32u(const uint8_t *p) { uint32_t v; __builtin_memcpy(&v, p, 4); return v; }
-__device__ __forceinline__ uint32_t rect_ld_u16u(const uint8_t *p) { uint16_t v; __builtin_memcpy(&v, p, 2); return v; }
 // CV_BGR2GRAY, 14-bit fixed point
 __device__ __forceinline__ uint32_t rect_gray(uint32_t b, uint32_t g, uint32_t r) { return (1868u * b + 9617u * g + 4899u * r + 8192u) >> 14; }
 
@@ -112,10 +110,10 @@ __device__ __forceinline__ uint32_t rect_pixel(const uint8_t *__restrict__ src, 
   if (INSIDE) {
     const uint8_t *q = src + (size_t)y0 * ss + CH * x0;
     if (CH == 1) {
-      const uint32_t t0 = rect_ld_u16u(q), t1 = rect_ld_u16u(q + ss);
+      const uint32_t t0 = ld_unaligned<uint16_t>(q), t1 = ld_unaligned<uint16_t>(q + ss);
       p00 = t0 & 255u; p01 = t0 >> 8; p10 = t1 & 255u; p11 = t1 >> 8;
     } else {
-      const uint32_t a0 = rect_ld_u32u(q), b0 = rect_ld_u16u(q + 4), a1 = rect_ld_u32u(q + ss), b1 = rect_ld_u16u(q + ss + 4);
+      const uint32_t a0 = ld_unaligned<uint32_t>(q), b0 = ld_unaligned<uint16_t>(q + 4), a1 = ld_unaligned<uint32_t>(q + ss), b1 = ld_unaligned<uint16_t>(q + ss + 4);
       p00 = rect_gray(a0 & 255u, (a0 >> 8) & 255u, (a0 >> 16) & 255u); p01 = rect_gray(a0 >> 24, b0 & 255u, b0 >> 8);
       p10 = rect_gray(a1 & 255u, (a1 >> 8) & 255u, (a1 >> 16) & 255u); p11 = rect_gray(a1 >> 24, b1 & 255u, b1 >> 8);
     }
@@ -186,9 +184,9 @@ __global__ __launch_bounds__(256) void rectify_convert_kernel(const uint8_t *__r
   const int y = item / ncol, x = 4 * (item - y * ncol);
   const uint8_t *q = src + (size_t)blockIdx.y * sb + (size_t)y * ss + CH * x;
   uint32_t o;
-  if (CH == 1) o = rect_ld_u32u(q);
+  if (CH == 1) o = ld_unaligned<uint32_t>(q);
   else {
-    const uint32_t a = rect_ld_u32u(q), b = rect_ld_u32u(q + 4), c = rect_ld_u32u(q + 8);      // B0 G0 R0 B1 | G1 R1 B2 G2 | R2 B3 G3 R3
+    const uint32_t a = ld_unaligned<uint32_t>(q), b = ld_unaligned<uint32_t>(q + 4), c = ld_unaligned<uint32_t>(q + 8);      // B0 G0 R0 B1 | G1 R1 B2 G2 | R2 B3 G3 R3
     o = rect_gray(a & 255u, (a >> 8) & 255u, (a >> 16) & 255u) | rect_gray(a >> 24, b & 255u, (b >> 8) & 255u) << 8 |
         rect_gray((b >> 16) & 255u, b >> 24, c & 255u) << 16 | rect_gray((c >> 8) & 255u, (c >> 16) & 255u, c >> 24) << 24;
   }

@@ -17,6 +17,7 @@
 #include "common.h"
 #include "fast_view.h"
 #include "gate.h"
+#include "pose.h"
 #include <string.h>
 #include <algorithm>
 
@@ -57,30 +58,6 @@ struct RegK {
   svs_reg_result *res; const svs_match_result *m1, *m2; int32_t *status1, *accepted, *cand_src; svs_reg_kf_stats *kfst;
 };
 
-// the pose arithmetic of match.hip (d_pose_mul / d_pose_inv / d_pose_act), the same expressions: rows (a0 b0 + a1 b1) + a2 b2, translation added last
-__device__ __forceinline__ void reg_pose_mul(const double *A, const double *B, double *C) {
-  double t[12];
-#pragma unroll
-  for (int i = 0; i < 3; ++i) {
-#pragma unroll
-    for (int j = 0; j < 4; ++j) t[4 * i + j] = A[4 * i] * B[j] + A[4 * i + 1] * B[4 + j] + A[4 * i + 2] * B[8 + j];
-    t[4 * i + 3] += A[4 * i + 3];
-  }
-#pragma unroll
-  for (int i = 0; i < 12; ++i) C[i] = t[i];
-}
-__device__ __forceinline__ void reg_pose_inv(const double *A, double *B) {
-  double t[12];
-#pragma unroll
-  for (int i = 0; i < 3; ++i)
-#pragma unroll
-    for (int j = 0; j < 3; ++j) t[4 * i + j] = A[4 * j + i];
-#pragma unroll
-  for (int i = 0; i < 3; ++i) t[4 * i + 3] = -(t[4 * i] * A[3] + t[4 * i + 1] * A[7] + t[4 * i + 2] * A[11]);
-#pragma unroll
-  for (int i = 0; i < 12; ++i) B[i] = t[i];
-}
-
 // grid = requests
 __global__ __launch_bounds__(RC_THREADS) void reg_cull_kernel(RegK K) {
   __shared__ int s_wcnt[RC_THREADS / 64];
@@ -97,8 +74,8 @@ __global__ __launch_bounds__(RC_THREADS) void reg_cull_kernel(RegK K) {
       double Ta[12], Tr[12], t0[12], t1[12];
 #pragma unroll
       for (int i = 0; i < 12; ++i) { Ta[i] = kfs[kf].T_anchor_from_w[i]; Tr[i] = H.T_root[i]; }
-      reg_pose_inv(Ta, t0);
-      reg_pose_mul(Tr, t0, t1);
+      pose_inv(Ta, t0);
+      pose_mul(Tr, t0, t1);
 #pragma unroll
       for (int i = 0; i < 12; ++i) Trel[(size_t)kf * 12 + i] = t1[i];
     }
@@ -107,10 +84,10 @@ __global__ __launch_bounds__(RC_THREADS) void reg_cull_kernel(RegK K) {
     double I[12], Tr[12], t0[12];
 #pragma unroll
     for (int i = 0; i < 12; ++i) { I[i] = i % 5 == 0 ? 1.0 : 0.0; Tr[i] = H.T_root[i]; }
-    reg_pose_mul(I, Tr, t0);
+    pose_mul(I, Tr, t0);
 #pragma unroll
     for (int i = 0; i < 12; ++i) { K.T[(size_t)r * 12 + i] = I[i]; K.Tcw[(size_t)r * 12 + i] = t0[i]; }
-    reg_pose_inv(Tr, t0);
+    pose_inv(Tr, t0);
 #pragma unroll
     for (int i = 0; i < 12; ++i) K.Twa[(size_t)r * 12 + i] = t0[i];
   }
@@ -131,9 +108,8 @@ __global__ __launch_bounds__(RC_THREADS) void reg_cull_kernel(RegK K) {
       const int lvl = src[i].anchor_level;
       if ((unsigned)kf < (unsigned)n_kf && (unsigned)lvl < (unsigned)SVS_NUM_PYR_LEVELS && (flags[kf] & SVS_REG_KF_IN_WINDOW)) {
         const double *T = Trel + (size_t)kf * 12, *x = src[i].xyz_anchor;
-        const double p0 = T[0] * x[0] + T[1] * x[1] + T[2] * x[2] + T[3];
-        const double p1 = T[4] * x[0] + T[5] * x[1] + T[6] * x[2] + T[7];
-        const double p2 = T[8] * x[0] + T[9] * x[1] + T[10] * x[2] + T[11];
+        double p0, p1, p2;
+        pose_act(T, x[0], x[1], x[2], p0, p1, p2);
         const svs_cam &cam = K.cams[lvl];
         const double u = cam.f * (p0 / p2) + cam.cx, v = cam.f * (p1 / p2) + cam.cy;      // cam_pyr.map(project2d(xyz_root)) (:522)
         if (fabs(u) < 2147483648.0 && fabs(v) < 2147483648.0) {                           // (NaN compares false)
@@ -217,7 +193,7 @@ __global__ __launch_bounds__(64) void reg_pose_kernel(RegK K) {
     double T[12], Tr[12], t0[12];
 #pragma unroll
     for (int i = 0; i < 12; ++i) { T[i] = K.T[(size_t)r * 12 + i]; Tr[i] = K.hdr[r].T_root[i]; }
-    reg_pose_mul(T, Tr, t0);
+    pose_mul(T, Tr, t0);
 #pragma unroll
     for (int i = 0; i < 12; ++i) { K.T1[(size_t)r * 12 + i] = T[i]; K.Tcw[(size_t)r * 12 + i] = t0[i]; }
     K.dead[r] = dead ? 1 : 0;

@@ -33,15 +33,9 @@ struct SeedK {
   svs_candidate_point *out; int cap; int32_t *n_new;
 };
 
-__device__ __forceinline__ uint64_t seed_splitmix64(uint64_t z) {
-  z += 0x9E3779B97F4A7C15ull;
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  return z ^ (z >> 31);
-}
-__device__ __forceinline__ uint64_t seed_key_a(uint64_t seed, int l, int i) { return seed_splitmix64(seed ^ ((1ull << 62) | ((uint64_t)l << 32) | (uint32_t)i)); }
+__device__ __forceinline__ uint64_t seed_key_a(uint64_t seed, int l, int i) { return splitmix64(seed ^ ((1ull << 62) | ((uint64_t)l << 32) | (uint32_t)i)); }
 __device__ __forceinline__ uint64_t seed_key_b(uint64_t seed, int l, int j, int c) {
-  return seed_splitmix64(seed ^ ((2ull << 62) | ((uint64_t)l << 48) | ((uint64_t)(uint32_t)j << 16) | (uint32_t)c));
+  return splitmix64(seed ^ ((2ull << 62) | ((uint64_t)l << 48) | ((uint64_t)(uint32_t)j << 16) | (uint32_t)c));
 }
 __device__ __forceinline__ int seed_list_len(const SeedK &K, int l, size_t slot) {
   return min(max(K.a.d_n[l][slot * K.a.n_bstride[l]], 0), K.a.xy_cap[l]);
@@ -218,6 +212,7 @@ __global__ __launch_bounds__(SEED_THREADS) void seed_greedy_kernel(SeedK K) {
     const double u0 = p0 * fac, u1 = p1 * fac, u2 = p2 * fac;      // zeroFromPyr_3d
     const double sd = (u0 - u2) / cam.b, z = cam.f / sd;           // unmap_uvu, stereo_camera.cpp:46-52
     const double x = ((u0 - cam.cx) / cam.f) * z, y = ((u1 - cam.cy) / cam.f) * z;
+    // pose_act's rows (pose.h), spelled out here: through the helper the compiler schedules the tail of this kernel differently (profiles/shared_helpers.md)
     const double X = ((T[0] * x + T[1] * y) + T[2] * z) + T[3], Y = ((T[4] * x + T[5] * y) + T[6] * z) + T[7], Z = ((T[8] * x + T[9] * y) + T[10] * z) + T[11];
     const int pos = total - 1 - k;                                 // push_front
     if (pos < K.cap) {

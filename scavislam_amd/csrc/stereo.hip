@@ -43,17 +43,11 @@ struct StereoDev {
   int32_t *npend;        // [batch][n_strips]
   int timing;            // SVS_STEREO_DEBUG: phase stamps of one workgroup behind the error word
   int *err;              // the context's word (svs_ctx::stereo_err): bits set when a bounded walk of the strip path gave up (never expected)
-  int swz;               // workgroups in XCD-contiguous order (common.h: xcd_contiguous)
+  int swz;               // workgroups in XCD-contiguous order (devutil.h: xcd_contiguous)
 };
 
-__device__ __forceinline__ void wave_sync_lds() { __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_s_waitcnt(0xc07f); __builtin_amdgcn_wave_barrier(); }
 __device__ __forceinline__ int xsobel_tab(int v, int cap) { return v < -cap ? 0 : v > cap ? 2 * cap : v + cap; }
 
-__device__ __forceinline__ uint32_t load_u32_unaligned(const uint8_t *p) {
-  uint32_t v;
-  __builtin_memcpy(&v, p, 4);
-  return v;
-}
 __device__ __forceinline__ int byte_of(uint32_t lo, uint32_t hi, int i) { return (int)((i < 4 ? lo >> (8 * i) : hi >> (8 * (i - 4))) & 0xffu); }
 
 // dword at byte position q of a row of w bytes, read from the clamped position and shifted into place: bytes that fall
@@ -61,7 +55,7 @@ __device__ __forceinline__ int byte_of(uint32_t lo, uint32_t hi, int i) { return
 // a per-byte border path makes every wave that holds an edge lane walk it, with a wait behind each load.
 __device__ __forceinline__ uint32_t load_u32_clamped(const uint8_t *row, int q, int w) {
   const int qs = min(max(q, 0), w - 4), d = q - qs;
-  const uint32_t raw = load_u32_unaligned(row + qs);
+  const uint32_t raw = ld_unaligned<uint32_t>(row + qs);
   return d == 0 ? raw : (d >= 4 || d <= -4) ? 0u : d > 0 ? raw >> (8 * d) : raw << (-8 * d);
 }
 // 4 padded columns x 4 rows per thread (the six input rows of a 4-row group are read once: 12 dword loads per 16 pixels instead of 24; the
@@ -189,10 +183,10 @@ union Pk { uint64_t q; us2 h[2]; uint32_t u[2]; };
 struct RowWin { uint32_t l0, l1, r[11]; };
 __device__ __forceinline__ RowWin load_rowwin(const uint8_t *lrow, const uint8_t *rrow) {
   RowWin wv;
-  wv.l0 = load_u32_unaligned(lrow);
-  wv.l1 = load_u32_unaligned(lrow + 4);
+  wv.l0 = ld_unaligned<uint32_t>(lrow);
+  wv.l1 = ld_unaligned<uint32_t>(lrow + 4);
 #pragma unroll
-  for (int k = 0; k < 11; ++k) wv.r[k] = load_u32_unaligned(rrow + 4 * k);
+  for (int k = 0; k < 11; ++k) wv.r[k] = ld_unaligned<uint32_t>(rrow + 4 * k);
   return wv;
 }
 // horizontal 7-tap SADs of one row for the 32 disparity indices (4 per V_QSAD/V_MQSAD pair) + texture term
@@ -433,7 +427,7 @@ __global__ __launch_bounds__(256) void stereo_validate_kernel(StereoDev S) {
   } else {
     for (int x = lane; x < w; x += 64) { s_d[x] = (int)(((unsigned)(uint16_t)dp[x]) | ((unsigned)cp[x] << 16)); s_key[x] = 0xffffffffu; }
   }
-  wave_sync_lds();
+  wave_lds_sync();
   const int minX1 = NDISP;
   for (int x = minX1 + lane; x < w; x += 64) {
     const int e = s_d[x], d = (int16_t)(e & 0xffff);
@@ -441,7 +435,7 @@ __global__ __launch_bounds__(256) void stereo_validate_kernel(StereoDev S) {
     const int x2 = x - ((d + SCALE / 2) >> DISP_SHIFT);
     if (x2 >= 0 && x2 < w) atomicMin(&s_key[x2], ((unsigned)e & 0xffff0000u) | (unsigned)x);
   }
-  wave_sync_lds();
+  wave_lds_sync();
   for (int x = minX1 + lane; x < w; x += 64) {
     const int d = (int16_t)(s_d[x] & 0xffff);
     if (d == INVALID) continue;
@@ -734,10 +728,6 @@ __device__ __forceinline__ unsigned spk_writelane(unsigned acc, unsigned val, in
 #undef SPK_WL
   return acc;
 }
-__device__ __forceinline__ unsigned long long spk_readlane64(unsigned long long v, int l) {      // value of lane l (l wave-uniform)
-  const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)v, l), hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(v >> 32), l);
-  return ((unsigned long long)hi << 32) | lo;
-}
 __global__ __launch_bounds__(SPK_THREADS) void stereo_speckle_strip_kernel(StereoDev S, float *__restrict__ out, int dstride, size_t d_bstride) {
   extern __shared__ int s_mem[];
   __shared__ unsigned long long s_bb[SPK_THREADS / 64][SPK_MAX_SEG];
@@ -901,7 +891,7 @@ __global__ __launch_bounds__(SPK_THREADS) void stereo_speckle_strip_kernel(Stere
       if (use_msk) {
         const unsigned long long mv = row_masks(row);
 #pragma unroll
-        for (int k = 0; k < SPK_NS; ++k) enqueue(spk_readlane64(mv, 0 * SPK_NS + k), 0ull, k * 64, row, flush);
+        for (int k = 0; k < SPK_NS; ++k) enqueue(lane_bcast(mv, 0 * SPK_NS + k), 0ull, k * 64, row, flush);
       } else {
         const int16_t *da = dsp + row * wp, *db = da + wp;
         for (int seg = 0; seg < nseg; ++seg) {
@@ -937,7 +927,7 @@ __global__ __launch_bounds__(SPK_THREADS) void stereo_speckle_strip_kernel(Stere
       if (use_msk) {
         const unsigned long long mv = row_masks(row);
 #pragma unroll
-        for (int k = 0; k < SPK_NS; ++k) enqueue(spk_readlane64(mv, 1 * SPK_NS + k), spk_readlane64(mv, 3 * SPK_NS + k), k * 64, row, flush);
+        for (int k = 0; k < SPK_NS; ++k) enqueue(lane_bcast(mv, 1 * SPK_NS + k), lane_bcast(mv, 3 * SPK_NS + k), k * 64, row, flush);
       } else {
         const int16_t *d = dsp + row * wp;
         const int *l = lab + row * wp;
@@ -988,7 +978,7 @@ __global__ __launch_bounds__(SPK_THREADS) void stereo_speckle_strip_kernel(Stere
       if (use_msk) {
         const unsigned long long mv = row_masks(row);
 #pragma unroll
-        for (int k = 0; k < SPK_NS; ++k) enqueue(spk_readlane64(mv, 2 * SPK_NS + k), spk_readlane64(mv, 3 * SPK_NS + k), k * 64, row, flush);
+        for (int k = 0; k < SPK_NS; ++k) enqueue(lane_bcast(mv, 2 * SPK_NS + k), lane_bcast(mv, 3 * SPK_NS + k), k * 64, row, flush);
       } else {
         const int16_t *d = dsp + row * wp;
         const int *l = lab + row * wp;

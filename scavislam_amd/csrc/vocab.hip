@@ -21,12 +21,6 @@ constexpr int VS_PICK = 1024;                                        // threads 
 constexpr int VS_PER = SVS_VOCAB_MAX_POINTS / VS_BLOCK / VS_PICK;    // block sums per thread of the pick workgroup at the largest n (8)
 constexpr double VS_W_SCALE = 0x1p28, VS_Q_SCALE = 0x1p38, VS_Q_INV = 0x1p-38;
 
-__device__ __forceinline__ u64 vocab_wave_sum_u64(u64 v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
 // ---- seeding ------------------------------------------------------------------------------------------------------------------------------------------------
 // grid-stride over max(n, n_words): weights to +inf, centre 0 = i0, the others "none"; state[0] = n_seeded, -1 while the seeding has not ended early
 __global__ __launch_bounds__(256) void vocab_seed_init_kernel(int n, int n_words, int i0, double *__restrict__ w, int32_t *__restrict__ seed_idx, int32_t *__restrict__ state) {
@@ -63,7 +57,7 @@ __global__ __launch_bounds__(VS_BLOCK) void vocab_seed_weight_kernel(const float
     Wi = (u64)(wi * VS_W_SCALE);                                           // < 2^41: |x| < 4
     W[i] = Wi;
   }
-  Wi = vocab_wave_sum_u64(Wi);
+  Wi = wave_sum(Wi);
   if ((threadIdx.x & 63) == 0) s_sum[threadIdx.x >> 6] = Wi;
   __syncthreads();
   if (threadIdx.x == 0) bsum[blockIdx.x] = (s_sum[0] + s_sum[1]) + (s_sum[2] + s_sum[3]);
@@ -104,7 +98,7 @@ __global__ __launch_bounds__(VS_PICK) void vocab_seed_pick_kernel(int n, int nb,
     if (tid == 0) state[0] = c;
     return;
   }
-  const u64 r = __umul64hi(loop_splitmix64(seed ^ ((1ull << 62) | (u64)(uint32_t)c)), T);      // < T
+  const u64 r = __umul64hi(splitmix64(seed ^ ((1ull << 62) | (u64)(uint32_t)c)), T);      // < T
   if (tid == 0) s_blk = -1;
   __syncthreads();
   if (incl - loc <= r && r < incl) {                                       // exactly one thread: the prefix sums are monotone and r < T
@@ -195,7 +189,7 @@ __global__ __launch_bounds__(256) void vocab_final_kernel(int n, int k_words, co
       q = (u64)((double)d2 * VS_W_SCALE);
     } else { assign[i] = -1; d2out[i] = 0.f; }                             // (never)
   }
-  q = vocab_wave_sum_u64(q);
+  q = wave_sum(q);
   if ((threadIdx.x & 63) == 0 && q) atomicAdd(inertia, q);
 }
 
@@ -288,7 +282,7 @@ extern "C" int svs_vocab_train(svs_ctx *ctx, int desc_dim, int n, const float *h
     SVS_HIP(ctx, wk.d_w.alloc(n));
     SVS_HIP(ctx, wk.d_W.alloc(n));
     SVS_HIP(ctx, wk.d_bsum.alloc(nb));
-    const int i0 = (int)(((loop_splitmix64(prm->seed) >> 32) * (uint64_t)(uint32_t)n) >> 32);
+    const int i0 = (int)(((splitmix64(prm->seed) >> 32) * (uint64_t)(uint32_t)n) >> 32);
     SVS_HIP(ctx, hipEventRecord(wk.ev[0], st));
     hipLaunchKernelGGL(vocab_seed_init_kernel, dim3(std::min(div_up(std::max(n, nw), 256), 4096)), dim3(256), 0, st, n, nw, i0, wk.d_w, wk.d_seed, wk.d_state);
     SVS_LAUNCH_CHECK(ctx);

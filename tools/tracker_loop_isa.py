@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """What the compiler made of the dense tracker's sample loop (scavislam_amd/csrc/dense.hip, track_pass).
 
-Compiles dense.hip for gfx950 with the flags of csrc/Makefile plus `--cuda-device-only -S` into a temporary directory, finds the loop over the
+Has csrc/Makefile write the gfx950 assembly of dense.hip (build/dense.s: the unit's own flags, device only), finds the loop over the
 samples in every function that inlines track_pass (the tracker kernels) and prints, per loop: instructions per trip by class,
 the function's VGPRs / scratch / occupancy, the order in which the trip issues its memory operations and waits for them, and a verdict:
 
@@ -36,27 +36,13 @@ def find_hipcc():
     return cand if cand and os.path.exists(cand) and os.access(cand, os.X_OK) else None
 
 
-def makefile_flags(csrc_dir):
-    """FLAGS of csrc/Makefile with its variables substituted (what build/%.o is compiled with)."""
-    var = {}
-    for line in open(os.path.join(csrc_dir, "Makefile")):
-        m = re.match(r"^(\w+)\s*\??=\s*(.*)$", line.rstrip("\n"))
-        if m:
-            var[m.group(1)] = m.group(2).strip()
-    flags = var["FLAGS"]
-    for _ in range(4):
-        flags = re.sub(r"\$\((\w+)\)", lambda m: var.get(m.group(1), ""), flags)
-    return flags.split()
-
-
-def compile_asm(src_root, tmp, hipcc):
+def compile_asm(src_root, hipcc):
+    """build/dense.s by the Makefile's own rule: the Makefile alone knows the flags (a revision from before that rule cannot be analysed)."""
     csrc = os.path.join(src_root, CSRC)
-    out = os.path.join(tmp, "dense.s")
-    cmd = [hipcc] + makefile_flags(csrc) + ["--cuda-device-only", "-S", os.path.join(csrc, "dense.hip"), "-o", out]
-    r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, universal_newlines=True)
+    r = subprocess.run(["make", "-C", csrc, "HIPCC=" + hipcc, "build/dense.s"], stdout=subprocess.PIPE, stderr=subprocess.PIPE, universal_newlines=True)
     if r.returncode != 0:
-        raise RuntimeError("hipcc failed:\n" + r.stderr[-4000:])
-    return open(out).read()
+        raise RuntimeError("make build/dense.s failed:\n" + r.stderr[-4000:])
+    return open(os.path.join(csrc, "build", "dense.s")).read()
 
 
 def checkout_rev(rev, tmp):
@@ -299,7 +285,7 @@ def run(rev=None, asm=None, src_root=None):
         raise RuntimeError("no hipcc")
     with tempfile.TemporaryDirectory(prefix="tracker_isa_") as tmp:
         root = checkout_rev(rev, tmp) if rev else (src_root or ROOT)
-        return analyse(compile_asm(root, tmp, hipcc))
+        return analyse(compile_asm(root, hipcc))
 
 
 def main():
