@@ -173,7 +173,7 @@ typedef struct {
   int32_t prefilter_cap;      /* stereo_frontend.cpp:626  (31)  */
   int32_t sad_window;         /* :627  (7; only 7 supported)    */
   int32_t min_disparity;      /* :628  (0; only 0 supported)    */
-  int32_t num_disparities;    /* :636  (num_disp16*16 = 32; only 32 supported) */
+  int32_t num_disparities;    /* :636  (16 * ui.num_disp16 = 32; 16, 32, 48, ..., 160 supported: num_disp16 1..10 of :536 / :623) */
   int32_t texture_threshold;  /* :630  (10) */
   int32_t uniqueness_ratio;   /* :631  (15) */
   int32_t speckle_window;     /* :632  (100; 0 = no speckle filter) */
@@ -181,14 +181,17 @@ typedef struct {
   int32_t disp12_max_diff;    /* :634  (1; < 0 = no left-right check) */
 } svs_stereo_params;
 typedef struct svs_stereo svs_stereo;
-/* scratch for `max_batch` independent w x h frames (prefiltered images, 16-bit disparity, cost, labels).  38 <= w <= 20164, h >= 2, else SVS_ERR_UNSUPPORTED:
-   the left-right check and the whole-frame speckle filter hold one row in LDS, 8 w + 8 ceil(w / 64) bytes of the 160 KB a workgroup of the MI355X can have
+/* scratch for `max_batch` independent w x h frames (prefiltered images, 16-bit disparity, cost, labels).  num_disparities + 6 <= w <= 20164 (38 at the 32
+   disparities of the reference: three edge columns and four searched ones), h >= 2, num_disparities a multiple of 16 in 16..160, else SVS_ERR_UNSUPPORTED with
+   nothing allocated: the left-right check and the whole-frame speckle filter hold one row in LDS, 8 w + 8 ceil(w / 64) bytes of the 160 KB a workgroup of the MI355X can have
    (requests above 64 KB are announced with hipFuncAttributeMaxDynamicSharedMemorySize at create).
    svs_ctx_get_stat of the context tells which kernels svs_stereo_compute chose, one step per call (host-side): "stereo_prefilter16_calls" (rows of 16 n pixels on
    4-byte aligned pointers and strides) / "stereo_prefilter4_calls" (everything else, or SVS_STEREO_PREFILTER4=1 at create), "stereo_strip_filter_calls" (speckle
    filter on strips of rows in LDS; "stereo_strip_filter_strips" adds up the strips per frame of those calls) / "stereo_frame_filter_calls" (the whole-frame union-find: rows too wide for 16 of them in LDS, h < 16, speckle_window >= 16368,
    or SVS_STEREO_FRAME_CCL=1 at create; SVS_STEREO_STRIP_KB=8..151 at create sets the LDS of a strip), "stereo_validate_wide_calls" (left-right check with one row
-   per workgroup, w > 2048).  "stereo_speckle_error_mask" (blocking) is the OR of the bits the bounded walks of the strip filter leave when one gives up (never
+   per workgroup, w > 2048), "stereo_wide_search_calls" (the search kernels for any disparity count, which keep a pixel's window sums in LDS: every
+   num_disparities but 32, and 32 too under SVS_STEREO_WIDE=1 at create; 32 otherwise runs the register-ring kernels, with the same result bit for bit).
+   "stereo_speckle_error_mask" (blocking) is the OR of the bits the bounded walks of the strip filter leave when one gives up (never
    expected; 0 = none since the context was created): 1 / 2 a find inside a strip, 4 a union inside a strip, 8 / 16 a find / a union across strips. */
 int svs_stereo_create(svs_ctx *ctx, int w, int h, int max_batch, const svs_stereo_params *prm, svs_stereo **out);
 int svs_stereo_destroy(svs_stereo *s);

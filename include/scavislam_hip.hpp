@@ -297,6 +297,7 @@ class BA_SE3_XYZ_STEREO {
 
 // StereoFrontend::calcDisparityCpu (stereo_frontend.cpp:620-653): cv::StereoBM on the level-0 left image and the
 // right image; the float disparity lands in the frame's disparity image (FrameDev::disp, -1 where filtered).
+// num_disp16 = ui.num_disp16 (stereo_frontend.cpp:536 / :623), 1..10: 16 * num_disp16 disparities are searched, in frames at least that + 6 pixels wide.
 class StereoBM {
  public:
   StereoBM(const Context &c, int w, int h, int num_disp16 = 2) : ctx_(c), s_(0), w_(w), h_(h), right_(c, (size_t)((w + 63) / 64 * 64) * h) {
@@ -492,14 +493,15 @@ class StereoFrontend {
   StereoFrontend(const StereoFrontend &) = delete;
   StereoFrontend &operator=(const StereoFrontend &) = delete;
   // cuda_build: the reference compiled with SCAVISLAM_CUDA_SUPPORT (full-resolution denseTrackingGpu, matcher search radius 4, stereo_frontend.cpp:1043-1047);
-  // n_levels: use_n_levels_in_frontent (stereo_frontend.cpp:68; the code default is 2, the shipped configurations set 3)
-  static svs_frontend_params referenceParams(bool block_matching, bool cuda_build = false, int n_levels = 3) {
+  // n_levels: use_n_levels_in_frontent (stereo_frontend.cpp:68; the code default is 2, the shipped configurations set 3); num_disp16: ui.num_disp16 (:536 / :623),
+  // 1..10, for use_block_matching
+  static svs_frontend_params referenceParams(bool block_matching, bool cuda_build = false, int n_levels = 3, int num_disp16 = 2) {
     svs_frontend_params p;
     std::memset(&p, 0, sizeof p);
     p.fast_trials = 6; p.search_radius = cuda_build ? 4 : 8; p.thr_mean = 22; p.thr_std = 10; p.max_reproj_error = 2.f; p.use_block_matching = block_matching ? 1 : 0;
     p.n_levels = n_levels; p.num_max_points = 300; p.min_matches = 20; p.cuda_build = cuda_build ? 1 : 0;
     p.pose_opt.robust_kernel = 1; p.pose_opt.num_iter = 15; p.pose_opt.kernel_param = 2.0; p.pose_opt.initial_mu = -1.0; p.pose_opt.tau = 1e-5;
-    const svs_stereo_params sp = {31, 7, 0, 32, 10, 15, 100, 32, 1};
+    const svs_stereo_params sp = {31, 7, 0, 16 * num_disp16, 10, 15, 100, 32, 1};
     p.stereo = sp;
     return p;
   }

@@ -46,12 +46,13 @@ class FrontendParams(C.Structure):
                 ("n_levels", C.c_int32), ("num_max_points", C.c_int32), ("min_matches", C.c_int32), ("cuda_build", C.c_int32)]
 
     @classmethod
-    def reference(cls, use_block_matching=False, cuda_build=False, n_levels=3, search_radius=None, thr_mean=22, thr_std=10, num_max_points=300):
+    def reference(cls, use_block_matching=False, cuda_build=False, n_levels=3, search_radius=None, thr_mean=22, thr_std=10, num_max_points=300, num_disp16=2):
         """the values StereoFrontend uses (stereo_frontend.cpp:232, :989-1004, :845-846, :1061, :620-653); cuda_build = its SCAVISLAM_CUDA_SUPPORT
-        build (full-resolution tracker, matcher search radius 4, :1043-1047).  n_levels: use_n_levels_in_frontent (code default 2, shipped cfgs 3)"""
+        build (full-resolution tracker, matcher search radius 4, :1043-1047).  n_levels: use_n_levels_in_frontent (code default 2, shipped cfgs 3);
+        num_disp16: ui.num_disp16 (:536 / :623), 1..10 -- block matching over 16 * num_disp16 disparities"""
         if search_radius is None:
             search_radius = 4 if cuda_build else 8
-        return cls(6, search_radius, thr_mean, thr_std, 2.0, int(use_block_matching), PoseOptParams.reference(), StereoParams.reference(),
+        return cls(6, search_radius, thr_mean, thr_std, 2.0, int(use_block_matching), PoseOptParams.reference(), StereoParams.reference(num_disp16),
                    n_levels, num_max_points, 20, int(cuda_build))
 
 
@@ -313,7 +314,7 @@ class Context:
     def get_stat(self, name):
         """counters of the context (svs_ctx_get_stat): "trk_exact_sums", "trk_exact_fallbacks" (blocking), "spin_lane_launches", "spin_gated_launches";
         which kernels svs_stereo_compute chose, one step per call: "stereo_prefilter16_calls", "stereo_prefilter4_calls", "stereo_strip_filter_calls" ("stereo_strip_filter_strips": their strips per frame, summed),
-        "stereo_frame_filter_calls", "stereo_validate_wide_calls"; "stereo_speckle_error_mask" (blocking): give-up bits of the strip speckle filter, 0 = none;
+        "stereo_frame_filter_calls", "stereo_validate_wide_calls", "stereo_wide_search_calls" (the search for any disparity count: every count but 32); "stereo_speckle_error_mask" (blocking): give-up bits of the strip speckle filter, 0 = none;
         of the whole process: "live_device_bytes", "live_pinned_bytes", "live_sync_objects" (what contexts and handles hold right now)"""
         v = C.c_longlong(0)
         self.call("svs_ctx_get_stat", name.encode(), C.byref(v))

@@ -54,7 +54,7 @@ struct svs_ctx {
   int spin_demand = 0;               // compute units that launch may hold (one per workgroup)
   long long spin_n_lane = 0, spin_n_gated = 0;      // svs_ctx_get_stat "spin_lane_launches" / "spin_gated_launches"
   // block matching (stereo.hip): the kernels svs_stereo_compute chose, counted per call on the host (svs_ctx_get_stat "stereo_prefilter16_calls", "stereo_prefilter4_calls",
-  // "stereo_strip_filter_calls", "stereo_frame_filter_calls", "stereo_validate_wide_calls"; "stereo_strip_filter_strips": strips per frame, summed over the strip calls)
+  // "stereo_strip_filter_calls", "stereo_frame_filter_calls", "stereo_validate_wide_calls", "stereo_wide_search_calls"; "stereo_strip_filter_strips": strips per frame, summed over the strip calls)
   long long stereo_n_prefilter16 = 0, stereo_n_prefilter4 = 0, stereo_n_strip_filter = 0, stereo_n_frame_filter = 0, stereo_n_validate_wide = 0, stereo_n_strips = 0;
   DevBuf<int> stereo_err;     // device, [32], zeroed at svs_ctx_create: [0] the give-up bits the strip speckle filter's bounded walks OR in (svs_ctx_get_stat
                               // "stereo_speckle_error_mask"), [8..21] the phase stamps of SVS_STEREO_DEBUG.  Shared by every svs_stereo of the context
@@ -62,6 +62,7 @@ struct svs_ctx {
                               // the linear workgroup index (devutil.h: xcd_contiguous) so the shared lines are fetched into one L2, not into 2-3; 0: the dispatcher's round robin (A/B)
   float vocab_ms[3] = {0.f, 0.f, 0.f};      // svs_vocab_stage_times: seeding, assignment, update of the last svs_vocab_train (vocab.hip)
   int mo_legacy = 0;          // "mo_legacy": the record-walking motion-only kernel of rounds 1-2 instead of the fused one (A/B experiments)
+  long long stereo_n_wide_search = 0;      // "stereo_wide_search_calls": calls of svs_stereo_compute whose search ran the any-count kernels (stereo.hip)
 };
 // Kernels whose workgroups wait for each other INSIDE one launch (the latency-mode trackers, the multi-workgroup Cholesky) size their grids to a device they have
 // to themselves: every workgroup must become resident while its siblings spin.  Next to ordinary kernels of other contexts that always happens -- those finish in

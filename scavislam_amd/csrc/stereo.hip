@@ -1,5 +1,5 @@
 // stereo.hip -- block-matching disparity for gfx950: StereoFrontend::calcDisparityCpu (stereo_frontend.cpp:620-653)
-// = cv::StereoBM (OpenCV 2.4.2, external) with XSOBEL prefilter, 7x7 SAD over 32 disparities, texture and
+// = cv::StereoBM (OpenCV 2.4.2, external) with XSOBEL prefilter, 7x7 SAD over 16 n disparities (n = ui.num_disp16 = 1..10; the reference's 32 by default), texture and
 // uniqueness tests, sub-pixel interpolation, left-right check (validateDisparity) and speckle filter.
 // Semantics as restated in oracle/stereo.c; results are bit-identical to it (integer pipeline).
 //
@@ -11,6 +11,8 @@
 //                            the last 7 rows in an LDS ring and slides the vertical sum with packed-u16 adds;
 //                            argmin / uniqueness / parabola per pixel
 //   stereo_bm_edge_kernel    the 3 leftmost output columns, whose right-image window clamps before the shift
+//   stereo_bm_wide_kernel    the same search for every other disparity count (and 32 under SVS_STEREO_WIDE=1): the window sums of a lane's column in LDS,
+//   stereo_bm_wide_edge_kernel   a runtime loop over groups of 16 disparities
 //   stereo_validate_kernel   validateDisparity, one workgroup per row (one LDS atomicMin of (cost, x) per source pixel)
 //   stereo_ccl_*             speckle filter = connected components (horizontal runs, then union-find with atomicMin
 //                            across rows) + saturating size count; the size test is fused with the 1/16 float conversion
@@ -44,6 +46,7 @@ struct StereoDev {
   int timing;            // SVS_STEREO_DEBUG: phase stamps of one workgroup behind the error word
   int *err;              // the context's word (svs_ctx::stereo_err): bits set when a bounded walk of the strip path gave up (never expected)
   int swz;               // workgroups in XCD-contiguous order (devutil.h: xcd_contiguous)
+  int ndisp;             // numberOfDisparities of the handle: 16, 32, ..., 160
 };
 
 __device__ __forceinline__ int xsobel_tab(int v, int cap) { return v < -cap ? 0 : v > cap ? 2 * cap : v + cap; }
@@ -399,6 +402,213 @@ __global__ __launch_bounds__(EDGE_THREADS) void stereo_bm_edge_kernel(StereoDev 
   }
 }
 
+// ---- the search for any numberOfDisparities N = 16, 32, ..., 160 (the kernels above are the N = 32 case) ----------
+// Seven rows of N row SADs per lane do not fit the register file (7 x N/2 VGPRs), so the ring goes: a lane keeps the N WINDOW sums of its column in LDS and
+// slides them down the strip by adding the entering row's SADs and subtracting the leaving row's, both formed again from the images (two V_QSAD / V_MQSAD passes
+// per output row instead of one).  The sums lie lane-major, two disparities per dword: dword k of lane l at [k * 64 + l], so that the 64 lanes of a wave touch 64
+// consecutive dwords whichever k they share -- N x 128 bytes per wave, 20 KB at N = 160.  Disparities are worked through in groups of 16 by a runtime loop (one
+// kernel for every N): a group needs six dwords of the right row, of which it inherits two from the group before and loads four as one 16-byte load, issued a
+// group ahead.  The first minimum is found while the sums are updated, on 32-bit keys sum << 8 | d (13 bits of sum at cap 63, 8 bits of index); the uniqueness
+// scan is a second pass over the sums in LDS.
+constexpr int WIDE_TILE = 64, WIDE_STRIP = 48;      // output columns (= lanes) and output rows per wave
+constexpr int WIDE_MAX_NDISP = 160;
+typedef unsigned short __attribute__((may_alias)) lds_u16;      // halfword view of the dword sums
+
+__device__ __forceinline__ uint64_t u64_of(uint32_t lo, uint32_t hi) { return (uint64_t)lo | ((uint64_t)hi << 32); }
+// the part of an image row one lane's window needs, walked group by group: 7 left bytes (8th masked), the right row's two inherited dwords and the group's four
+struct WideRow {
+  uint32_t l0, l1, c0, c1;
+  uint4 nx;
+  const uint8_t *r;
+  __device__ __forceinline__ void open(const uint8_t *lrow, const uint8_t *rrow) {
+    l0 = ld_unaligned<uint32_t>(lrow); l1 = ld_unaligned<uint32_t>(lrow + 4) & 0x00ffffffu;      // byte 7 = 0 = masked out by MQSAD
+    c0 = ld_unaligned<uint32_t>(rrow); c1 = ld_unaligned<uint32_t>(rrow + 4);
+    nx = ld_unaligned<uint4>(rrow + 8);
+    r = rrow + 24;
+  }
+  __device__ __forceinline__ int texture(uint32_t ft4) const { return (int)__builtin_amdgcn_sad_u8(l1 | (ft4 & 0xff000000u), ft4, __builtin_amdgcn_sad_u8(l0, ft4, 0u)); }
+  // horizontal 7-tap SADs of disparity indices 16 g .. 16 g + 15; more: another group follows (its four dwords are requested here)
+  __device__ __forceinline__ void group(int g, bool more, Pk (&hh)[4]) {
+    const uint32_t a[6] = {c0, c1, nx.x, nx.y, nx.z, nx.w};
+    c0 = nx.z; c1 = nx.w;
+    if (more) nx = ld_unaligned<uint4>(r + 16 * g);      // (uniform)
+#pragma unroll
+    for (int u = 0; u < 4; ++u)
+      hh[u].q = __builtin_amdgcn_mqsad_pk_u16_u8(u64_of(a[u + 1], a[u + 2]), l1, __builtin_amdgcn_qsad_pk_u16_u8(u64_of(a[u], a[u + 1]), l0, 0ull));
+  }
+};
+// one step of a lane's window sums (sums: the lane's column, stride 64 dwords): + row A, - row B (SUB); SEL: best = the first minimum's key.  No half of a dword
+// carries or borrows: a sum stays within [0, 49 * 126].
+template <bool SUB, bool SEL>
+__device__ __forceinline__ void wide_step(uint32_t *sums, int ngroups, uint32_t ft4, const uint8_t *la, const uint8_t *ra, const uint8_t *lb, const uint8_t *rb,
+                                          int &tsum, uint32_t &best) {
+  WideRow A, B;
+  A.open(la, ra);
+  tsum += A.texture(ft4);
+  if (SUB) { B.open(lb, rb); tsum -= B.texture(ft4); }
+  best = 0xffffffffu;
+  for (int g = 0; g < ngroups; ++g) {
+    Pk ha[4], hb[4];
+    A.group(g, g + 1 < ngroups, ha);
+    if (SUB) B.group(g, g + 1 < ngroups, hb);
+    uint32_t *sg = sums + g * 8 * 64;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+      uint32_t v = sg[k * 64] + ha[k >> 1].u[k & 1];
+      if (SUB) v -= hb[k >> 1].u[k & 1];
+      sg[k * 64] = v;
+      if (SEL) {
+        const uint32_t d = (uint32_t)(16 * g + 2 * k);
+        best = min(best, ((v & 0xffffu) << 8) | d);
+        best = min(best, ((v >> 16) << 8) | (d + 1));
+      }
+    }
+  }
+}
+// the rest of findStereoCorrespondenceBM's inner loop for one pixel, from its N sums in LDS and the first minimum's key
+__device__ __forceinline__ void wide_select(uint32_t *sums, uint32_t best, int tsum, const StereoDev &S, int16_t &disp, uint16_t &cost) {
+  disp = (int16_t)FILTERED16; cost = 0;
+  if (tsum < S.texthr) return;
+  const int N = S.ndisp, minsad = (int)(best >> 8), mind = (int)(best & 255u);
+  lds_u16 *s16 = reinterpret_cast<lds_u16 *>(sums);
+  auto slot = [](int d) { return (d >> 1) * 128 + (d & 1); };      // halfword of disparity index d in the lane's column
+  // sad[mind + 1], sad[mind - 1] with the mirrored ends sad[-1] = sad[1], sad[N] = sad[N-2]
+  const int p = s16[slot(mind == N - 1 ? N - 2 : mind + 1)], n = s16[slot(mind == 0 ? 1 : mind - 1)];
+  if (S.uniq > 0) {
+    // the scan of the original stops at a d outside [mind-1, mind+1] with sad[d] <= thresh: mask those three, take the minimum, put them back (the sums slide on)
+    const int thresh = minsad + (minsad * S.uniq / 100);
+    s16[slot(mind)] = 0xffff;
+    if (mind > 0) s16[slot(mind - 1)] = 0xffff;
+    if (mind < N - 1) s16[slot(mind + 1)] = 0xffff;
+    us2 m = {0xffff, 0xffff};
+#pragma unroll 8
+    for (int k = 0; k < (N >> 1); ++k) { Pk t; t.u[0] = sums[k * 64]; m = __builtin_elementwise_min(m, t.h[0]); }
+    s16[slot(mind)] = (unsigned short)minsad;
+    if (mind > 0) s16[slot(mind - 1)] = (unsigned short)n;
+    if (mind < N - 1) s16[slot(mind + 1)] = (unsigned short)p;
+    if ((int)min(m.x, m.y) <= thresh) return;      // (at least 13 real sums are in the minimum, so a thresh >= 0xffff changes nothing)
+  }
+  const int dd = p + n - 2 * minsad + abs(p - n);      // < 2^15, |p - n| * 256 < 2^24
+  disp = (int16_t)(((N - mind - 1) * 256 + (dd != 0 ? div_trunc_small((p - n) * 256, dd) : 0) + 15) >> 4);
+  cost = (uint16_t)minsad;
+}
+// grid: (ceil((width1-3)/WIDE_TILE), ceil(h/WIDE_STRIP), batch), block 64, dynamic LDS = N * 128 bytes.  Output columns x in [3, width1), X = x + N - 1.
+// With T(y) the window sums of output row y (window rows clamped one by one), T(y) = T(y-1) + row(clamp(y+3)) - row(clamp(y-4)) holds for every y, T(y0-1)
+// included: a strip starts from the seven rows of T(y0-1) and then takes one step per output row.
+// Reads of a row: right bytes x-3 .. x+N+4 and left bytes x+N-4 .. x+N+3 with x <= w-N, all inside the padded row (PADL 16, PADR 48).
+__global__ __launch_bounds__(64) void stereo_bm_wide_kernel(StereoDev S) {
+  extern __shared__ uint32_t w_sums[];      // [N/2][64]
+  unsigned wg = (blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
+  if (S.swz) wg = xcd_contiguous(wg, gridDim.x * gridDim.y * gridDim.z);
+  const int bx = wg % gridDim.x, by = (wg / gridDim.x) % gridDim.y;
+  const int lane = threadIdx.x, b = wg / (gridDim.x * gridDim.y);
+  const int w = S.w, h = S.h, N = S.ndisp, ngroups = N >> 4, width1 = w - N + 1;
+  const int x = min(3 + bx * WIDE_TILE + lane, width1 - 1);      // lanes past the end redo the last column (no store)
+  const bool store = 3 + bx * WIDE_TILE + lane < width1;
+  const int y0 = by * WIDE_STRIP, y1 = min(y0 + WIDE_STRIP, h);
+  const uint8_t *lp = S.lp + (size_t)b * h * S.pitch + PADL + (N - 1) - WSZ2 + x;
+  const uint8_t *rp = S.rp + (size_t)b * h * S.pitch + PADL - WSZ2 + x;
+  const uint32_t ft4 = 0x01010101u * (uint32_t)(S.cap + 1);
+  auto row = [&](int r) { return (uint32_t)min(max(r, 0), h - 1) * (uint32_t)S.pitch; };
+  uint32_t *sums = w_sums + lane;
+  for (int k = 0; k < (N >> 1); ++k) sums[k * 64] = 0u;
+  int tsum = 0;
+  uint32_t best;
+  for (int j = 0; j < 2 * WSZ2 + 1; ++j) {      // T(y0 - 1)
+    const uint32_t o = row(y0 - 1 - WSZ2 + j);
+    wide_step<false, false>(sums, ngroups, ft4, lp + o, rp + o, nullptr, nullptr, tsum, best);
+  }
+  for (int y = y0; y < y1; ++y) {
+    const uint32_t oa = row(y + WSZ2), ob = row(y - WSZ2 - 1);
+    wide_step<true, true>(sums, ngroups, ft4, lp + oa, rp + oa, lp + ob, rp + ob, tsum, best);
+    int16_t d16; uint16_t c16;
+    wide_select(sums, best, tsum, S, d16, c16);
+    if (store) {
+      const size_t o = ((size_t)b * h + y) * w + x + (N - 1);
+      S.disp16[o] = d16; S.cost[o] = c16;
+    }
+  }
+}
+
+// columns X < N - 1 (never searched) and x in [0,3), as stereo_bm_edge_kernel: a WAVE per pixel, lane = disparity index within a chunk of 64 (up to three chunks).
+// Staged per image row: right bytes 0 .. N+7 (N/4 + 2 dwords) and left bytes N-4 .. N+7 (3 dwords).  x <= 2 and d <= N-1: the right index is at most N+4 < w,
+// so neither image clamps on the right.  grid: (ceil(h/EDGE_ROWS), batch), block 256, dynamic LDS = wide_edge_lds_bytes(N)
+constexpr int WIDE_EDGE_CHUNKS = (WIDE_MAX_NDISP + 63) / 64;
+constexpr size_t wide_edge_lds_bytes(int ndisp) { return sizeof(uint32_t) * (size_t)(EDGE_ROWS + 2 * WSZ2) * (size_t)(ndisp / 4 + 5); }
+__global__ __launch_bounds__(EDGE_THREADS) void stereo_bm_wide_edge_kernel(StereoDev S) {
+  extern __shared__ uint32_t w_rec[];      // [EDGE_ROWS + 6][nr + 3]
+  const int b = blockIdx.y, w = S.w, h = S.h, N = S.ndisp, tid = threadIdx.x, lane = tid & 63;
+  const int nr = N / 4 + 2, rec_n = nr + 3;
+  const int width1 = w - N + 1, ncol = min(3, width1);
+  const int ybase = blockIdx.x * EDGE_ROWS, nrow = min(EDGE_ROWS, h - ybase);
+  const uint8_t *lp = S.lp + (size_t)b * h * S.pitch + PADL, *rp = S.rp + (size_t)b * h * S.pitch + PADL;      // (PADL, the pitch and N are multiples of 4)
+  for (int i = tid; i < (nrow + 2 * WSZ2) * rec_n; i += EDGE_THREADS) {
+    const int r = i / rec_n, c = i - r * rec_n, yy = min(max(ybase - WSZ2 + r, 0), h - 1);
+    w_rec[i] = *reinterpret_cast<const uint32_t *>((c < nr ? rp + 4 * c : lp + (N - 4) + 4 * (c - nr)) + (size_t)yy * S.pitch);
+  }
+  {   // the never-searched left border, FILTERED
+    const int n = (N - 1) * nrow;
+    for (int i = tid; i < n; i += EDGE_THREADS) {
+      const size_t o = ((size_t)b * h + ybase + i / (N - 1)) * w + i % (N - 1);
+      S.disp16[o] = (int16_t)FILTERED16; S.cost[o] = 0;
+    }
+  }
+  __syncthreads();
+  const uint32_t ft4 = 0x01010101u * (uint32_t)(S.cap + 1);
+  for (int pix = tid >> 6; pix < ncol * nrow; pix += EDGE_THREADS / 64) {
+    const int yl = pix / ncol, x = pix - yl * ncol, y = ybase + yl;
+    // the window taps as in stereo_bm_edge_kernel: a byte shuffle of the right bytes d .. d+7
+    const uint32_t selA = x == 0 ? 0x00000000u : x == 1 ? 0x01000000u : 0x02010000u;      // taps dx = -3..0
+    const uint32_t selB = x == 0 ? 0x0c030201u : x == 1 ? 0x0c040302u : 0x0c050403u;      // taps dx = 1..3, then a zero byte
+    int sadc[WIDE_EDGE_CHUNKS];
+    uint32_t key = 0xffffffffu, tsum_u = 0;
+#pragma unroll
+    for (int c = 0; c < WIDE_EDGE_CHUNKS; ++c) {
+      sadc[c] = 0x7fffffff;
+      if (64 * c < N) {      // (uniform)
+        const int d = 64 * c + lane, dr = min(d, N - 1), q = dr >> 2, sh = dr & 3;      // lanes past N - 1 redo it and stay out of the selection
+        uint32_t sad_u = 0;
+#pragma unroll
+        for (int k = 0; k <= 2 * WSZ2; ++k) {
+          const uint32_t *rec = w_rec + (yl + k) * rec_n;
+          const uint32_t w0 = rec[q], w1 = rec[q + 1], w2 = rec[q + 2], a0 = rec[nr], a1 = rec[nr + 1], a2 = rec[nr + 2];
+          const uint32_t r0 = __builtin_amdgcn_alignbyte(w1, w0, sh), r1 = __builtin_amdgcn_alignbyte(w2, w1, sh);
+          const uint32_t l0 = __builtin_amdgcn_alignbyte(a1, a0, x), l1 = __builtin_amdgcn_alignbyte(a2, a1, x) & 0x00ffffffu;
+          const uint32_t ra = __builtin_amdgcn_perm(r1, r0, selA), rb = __builtin_amdgcn_perm(r1, r0, selB);
+          sad_u = __builtin_amdgcn_sad_u8(l1, rb, __builtin_amdgcn_sad_u8(l0, ra, sad_u));
+          if (c == 0) tsum_u = __builtin_amdgcn_sad_u8(l1 | (ft4 & 0xff000000u), ft4, __builtin_amdgcn_sad_u8(l0, ft4, tsum_u));
+        }
+        if (d < N) { sadc[c] = (int)sad_u; key = min(key, (sad_u << 8) | (uint32_t)d); }
+      }
+    }
+    // selection across the wave (same rules as wide_select)
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) key = min(key, (uint32_t)__shfl_xor((int)key, o, 64));
+    const int minsad = (int)(key >> 8), mind = (int)(key & 255u), tsum = (int)tsum_u;
+    const int ip = mind == N - 1 ? N - 2 : mind + 1, in = mind == 0 ? 1 : mind - 1;
+    const int thresh = minsad + (minsad * S.uniq / 100);
+    int p = 0, n = 0;
+    bool rival = false;
+#pragma unroll
+    for (int c = 0; c < WIDE_EDGE_CHUNKS; ++c) {
+      const int vp = __shfl(sadc[c], ip & 63, 64), vn = __shfl(sadc[c], in & 63, 64), d = 64 * c + lane;
+      if ((ip >> 6) == c) p = vp;
+      if ((in >> 6) == c) n = vn;
+      rival = rival || __ballot(sadc[c] <= thresh && d < N && (d < mind - 1 || d > mind + 1)) != 0ull;
+    }
+    if (lane == 0) {
+      int16_t d16 = (int16_t)FILTERED16; uint16_t c16 = 0;
+      if (tsum >= S.texthr && !(S.uniq > 0 && rival)) {
+        const int dd = p + n - 2 * minsad + abs(p - n);
+        d16 = (int16_t)(((N - mind - 1) * 256 + (dd != 0 ? (p - n) * 256 / dd : 0) + 15) >> 4);
+        c16 = (uint16_t)minsad;
+      }
+      const size_t o = ((size_t)b * h + y) * w + x + (N - 1);
+      S.disp16[o] = d16; S.cost[o] = c16;
+    }
+  }
+}
+
 // validateDisparity (with D2): one WAVE per image row, four rows per workgroup (a row is 640 pixels: a 256-lane workgroup per row spent
 // its time in dispatch and two workgroup barriers; a wave orders its own LDS traffic without them).  The reference's sequential first
 // pass ("a strictly smaller cost wins", ascending x => first x on ties) is a minimum over (cost, x): every valid source pixel does one
@@ -428,7 +638,7 @@ __global__ __launch_bounds__(256) void stereo_validate_kernel(StereoDev S) {
     for (int x = lane; x < w; x += 64) { s_d[x] = (int)(((unsigned)(uint16_t)dp[x]) | ((unsigned)cp[x] << 16)); s_key[x] = 0xffffffffu; }
   }
   wave_lds_sync();
-  const int minX1 = NDISP;
+  const int minX1 = S.ndisp;
   for (int x = minX1 + lane; x < w; x += 64) {
     const int e = s_d[x], d = (int16_t)(e & 0xffff);
     if (d == INVALID) continue;
@@ -1087,15 +1297,19 @@ struct svs_stereo {
   int debug = 0;                                      // SVS_STEREO_DEBUG=1 at create
   int force_frame_ccl = 0;                            // SVS_STEREO_FRAME_CCL=1 at create: the whole-frame union-find path (tests/test_gpu_stereo_paths.py compares the two)
   int force_prefilter4 = 0;                           // SVS_STEREO_PREFILTER4=1 at create: the generic 4-pixel prefilter kernel on aligned input too (the same file compares the two)
+  int force_wide = 0;                                 // SVS_STEREO_WIDE=1 at create: 32 disparities through the any-count search (tests/test_gpu_stereo_ndisp.py compares the two)
   ~svs_stereo() { (void)hipStreamSynchronize(ctx->stream); }      // (runs before the buffers are freed)
 };
 
 extern "C" int svs_stereo_create(svs_ctx *ctx, int w, int h, int max_batch, const svs_stereo_params *prm, svs_stereo **out) {
   SVS_REQUIRE(ctx, ctx && prm && out && w > 0 && h > 0 && max_batch > 0);
   SVS_DEVICE(ctx);
-  if (prm->sad_window != 7 || prm->min_disparity != 0 || prm->num_disparities != NDISP || prm->prefilter_cap < 1 || prm->prefilter_cap > 63 ||
-      w < NDISP + 2 * WSZ2 || h < 2 || prm->speckle_window > 65535) {
-    ctx->err = "svs_stereo: only SADWindowSize 7, minDisparity 0, numberOfDisparities 32, preFilterCap 1..63, w >= 38 are supported";
+  const int ndisp = prm->num_disparities;
+  const bool ndisp_ok = ndisp >= 16 && ndisp <= WIDE_MAX_NDISP && ndisp % 16 == 0;
+  if (prm->sad_window != 7 || prm->min_disparity != 0 || !ndisp_ok || prm->prefilter_cap < 1 || prm->prefilter_cap > 63 ||
+      w < ndisp + 2 * WSZ2 || h < 2 || prm->speckle_window > 65535) {
+    ctx->err = "svs_stereo: only SADWindowSize 7, minDisparity 0, numberOfDisparities 16, 32, ..., 160, preFilterCap 1..63, w >= numberOfDisparities + 6" +
+               (ndisp_ok ? " (= " + std::to_string(ndisp + 2 * WSZ2) + " at " + std::to_string(ndisp) + " disparities)" : std::string()) + " are supported";
     return SVS_ERR_UNSUPPORTED;
   }
   if (w > STEREO_MAX_W) {
@@ -1106,6 +1320,7 @@ extern "C" int svs_stereo_create(svs_ctx *ctx, int w, int h, int max_batch, cons
   s->ctx = ctx; s->w = w; s->h = h; s->max_batch = max_batch; s->pitch = (w + PADL + PADR + 3) & ~3; s->prm = *prm;
   { const char *e = getenv("SVS_STEREO_FRAME_CCL"); s->force_frame_ccl = e && atoi(e) != 0; }
   { const char *e = getenv("SVS_STEREO_PREFILTER4"); s->force_prefilter4 = e && atoi(e) != 0; }      // A/B: the generic 4-pixel kernel on aligned input too
+  { const char *e = getenv("SVS_STEREO_WIDE"); s->force_wide = e && atoi(e) != 0; }                  // A/B: 32 disparities through the any-count search too
   { const char *e = getenv("SVS_STEREO_DEBUG"); s->debug = e && atoi(e) != 0; }
   const size_t n = (size_t)w * h * max_batch, np = (size_t)s->pitch * h * max_batch + 64;
   SVS_HIP(ctx, s->d_lp.alloc(np));
@@ -1154,8 +1369,8 @@ extern "C" int svs_stereo_compute(svs_stereo *s, const uint8_t *d_left, int lstr
   S.cap = s->prm.prefilter_cap; S.texthr = s->prm.texture_threshold; S.uniq = s->prm.uniqueness_ratio;
   S.speckle_window = s->prm.speckle_window; S.speckle_range = s->prm.speckle_range; S.disp12 = s->prm.disp12_max_diff;
   S.lp = s->d_lp; S.rp = s->d_rp; S.disp16 = s->d_disp16; S.cost = s->d_cost; S.label = s->d_label; S.count = s->d_count;
-  S.swz = ctx->xcd_swizzle;
-  const int w = s->w, h = s->h, width1 = w - NDISP + 1, n = w * h;
+  S.swz = ctx->xcd_swizzle; S.ndisp = s->prm.num_disparities;
+  const int w = s->w, h = s->h, width1 = w - S.ndisp + 1, n = w * h;
   const bool aligned16 = w % 16 == 0 && s->pitch % 16 == 0 && lstride % 4 == 0 && rstride % 4 == 0 && l_bstride % 4 == 0 && r_bstride % 4 == 0 &&
                          ((uintptr_t)d_left | (uintptr_t)d_right) % 4 == 0 && !s->force_prefilter4;
   ++(aligned16 ? ctx->stereo_n_prefilter16 : ctx->stereo_n_prefilter4);
@@ -1166,12 +1381,20 @@ extern "C" int svs_stereo_compute(svs_stereo *s, const uint8_t *d_left, int lstr
     hipLaunchKernelGGL(stereo_prefilter_kernel, dim3(div_up(s->pitch, 256), div_up(h, 16), 2 * n_batch), dim3(64, 4), 0, ctx->stream, S, d_left, lstride,
                        l_bstride, d_right, rstride, r_bstride);
   SVS_LAUNCH_CHECK(ctx);
-  hipLaunchKernelGGL(stereo_bm_edge_kernel, dim3(div_up(h, EDGE_ROWS), n_batch), dim3(EDGE_THREADS), 0, ctx->stream, S);
-  SVS_LAUNCH_CHECK(ctx);
-  if (width1 > 3) {
-    if (S.cap <= 41) hipLaunchKernelGGL(stereo_bm_kernel<true>, dim3(div_up(width1 - 3, 64), div_up(h, BM_STRIP), n_batch), dim3(64), 0, ctx->stream, S);
-    else hipLaunchKernelGGL(stereo_bm_kernel<false>, dim3(div_up(width1 - 3, 64), div_up(h, BM_STRIP), n_batch), dim3(64), 0, ctx->stream, S);
+  if (S.ndisp != NDISP || s->force_wide) {      // the any-count search; 32 disparities keep the register-ring kernels below
+    ++ctx->stereo_n_wide_search;
+    hipLaunchKernelGGL(stereo_bm_wide_edge_kernel, dim3(div_up(h, EDGE_ROWS), n_batch), dim3(EDGE_THREADS), wide_edge_lds_bytes(S.ndisp), ctx->stream, S);
     SVS_LAUNCH_CHECK(ctx);
+    hipLaunchKernelGGL(stereo_bm_wide_kernel, dim3(div_up(width1 - 3, WIDE_TILE), div_up(h, WIDE_STRIP), n_batch), dim3(64), (size_t)S.ndisp * 128, ctx->stream, S);
+    SVS_LAUNCH_CHECK(ctx);
+  } else {
+    hipLaunchKernelGGL(stereo_bm_edge_kernel, dim3(div_up(h, EDGE_ROWS), n_batch), dim3(EDGE_THREADS), 0, ctx->stream, S);
+    SVS_LAUNCH_CHECK(ctx);
+    if (width1 > 3) {
+      if (S.cap <= 41) hipLaunchKernelGGL(stereo_bm_kernel<true>, dim3(div_up(width1 - 3, 64), div_up(h, BM_STRIP), n_batch), dim3(64), 0, ctx->stream, S);
+      else hipLaunchKernelGGL(stereo_bm_kernel<false>, dim3(div_up(width1 - 3, 64), div_up(h, BM_STRIP), n_batch), dim3(64), 0, ctx->stream, S);
+      SVS_LAUNCH_CHECK(ctx);
+    }
   }
   if (s->prm.disp12_max_diff >= 0) {
     { const int R = validate_rows(w); hipLaunchKernelGGL(stereo_validate_kernel, dim3(div_up(h, R), n_batch), dim3(64 * R), validate_lds_bytes(w), ctx->stream, S); }

@@ -830,11 +830,12 @@ class StereoFrontend:
 
 class StereoMatcher:
     """StereoFrontend::calcDisparityCpu (stereo_frontend.cpp:620-653): cv::StereoBM on the level-0 left image
-    and the right image, float disparity written into the frame's `disp` (-1 where filtered)."""
+    and the right image, float disparity written into the frame's `disp` (-1 where filtered).  num_disp16 = ui.num_disp16
+    (:536 / :623), 1..10: 16 * num_disp16 disparities are searched (`params`, where given, decides alone)."""
 
-    def __init__(self, ctx, frame, params=None):
+    def __init__(self, ctx, frame, params=None, num_disp16=2):
         self.ctx, self.frame = ctx, frame
-        self.params = params or StereoParams.reference()
+        self.params = params or StereoParams.reference(num_disp16)
         self.h = C.c_void_p()
         ctx.call("svs_stereo_create", frame.w[0], frame.h[0], frame.batch, C.byref(self.params), C.byref(self.h))
         ctx.children.add(self)
