@@ -961,6 +961,68 @@ int svs_reg_register_batch(svs_reg *reg, int n_requests, const svs_reg_request *
 int svs_reg_set_timing(svs_reg *reg, int on);
 int svs_reg_stage_times(svs_reg *reg, float *ms);
 
+/* ---- back end: the map kept on the device for re-registration.  svs_reg_register_batch is stateless: every request carries its keyframe table, its source points
+   and its observer rows, which the caller has walked out of the graph (pointsVisibleInRoot, backend.cpp:472-546).  An svs_map keeps what those arrays are made
+   from -- keyframes, points, and the (point, keyframe) pairs of every feature_table -- in device memory under the graph's own ids, is updated incrementally, and
+   svs_reg_register_map_batch names a request by ids and does the walk on the device.
+   Ids are dense 32-bit integers below the capacities (frame ids and point ids come from one counter in the reference, stereo_frontend.cpp:826-831), the
+   convention of svs_ba_window_update.  max_keyframes <= 16384 (SVS_ERR_UNSUPPORTED above: the keyframe sets of a request are LDS bitmaps).
+   Every update is one staged upload and at most two launches, ASYNCHRONOUS on the context's stream, and is refused as a whole -- the map unchanged, nothing
+   uploaded -- on: an id outside the capacity or more entries than fit (SVS_ERR_CAPACITY), an id already present, an unknown id, an id twice in one call (SVS_ERR_INVALID).
+   The host keeps the id sets and the set of pairs (as the window store of svs_ba_window_update does); removal is not offered (the reference's back end never removes). */
+typedef struct svs_map svs_map;
+int svs_map_create(svs_ctx *ctx, int max_keyframes, int max_points, int max_observations, svs_map **out);
+int svs_map_destroy(svs_map *map);
+/* h_keyframes [n]: T_me_from_world and the pyramid (device pointers; the images stay where the front end keeps them); h_disp_ptr / h_disp_stride [n]: the
+   level-0 f32 disparity (device pointer, stride in elements); h_fast_thr [n][SVS_NUM_PYR_LEVELS][SVS_MAX_CELLS]: cell_grid2d, the stored thresholds, each of the
+   SVS_MAX_CELLS entries per level in 10 .. 255 (unused cells: 25), else SVS_ERR_INVALID as svs_reg_register_batch refuses a threshold below 10.  The new
+   keyframes are outside the window until svs_map_set_window names them */
+int svs_map_add_keyframes(svs_map *map, int n, const int32_t *h_ids, const svs_keyframe *h_keyframes, const float *const *h_disp_ptr, const int32_t *h_disp_stride,
+                          const int32_t *h_fast_thr);
+/* h_points[i].kf_index holds the ID of the anchor keyframe, which must be in the map; point_id and pad_ are ignored (the record is stored with point_id = its id) */
+int svs_map_add_points(svs_map *map, int n, const int32_t *h_ids, const svs_candidate_point *h_points);
+/* point h_point_ids[i] is in the feature_table of keyframe h_kf_ids[i].  A pair already present (or twice in the call) is ignored: feature_table is a map */
+int svs_map_add_observations(svs_map *map, int n, const int32_t *h_point_ids, const int32_t *h_kf_ids);
+/* what restoreDataFromG2o changes (slam_graph.cpp:1035-1058): h_poses [n][12] T_me_from_world; h_xyz_anchor [n][3] */
+int svs_map_set_poses(svs_map *map, int n, const int32_t *h_kf_ids, const double *h_poses);
+int svs_map_set_points(svs_map *map, int n, const int32_t *h_point_ids, const double *h_xyz_anchor);
+/* graph_.double_window(): exactly these keyframes have SVS_REG_KF_IN_WINDOW afterwards */
+int svs_map_set_window(svs_map *map, int n, const int32_t *h_kf_ids);
+/* host-side counts (each optional); n_observations counts distinct pairs */
+int svs_map_info(svs_map *map, int32_t *n_keyframes, int32_t *n_points, int32_t *n_observations);
+
+/* A request by ids.  The device builds the svs_reg_request of the stateless call from the map:
+     1. source points.  SVS_REG_LOCAL: every point with at least one observation in a keyframe of h_walk_kf that is not the root and not in h_direct_kf
+        (:481-497; the root is a direct neighbour, :433-449).  SVS_REG_LOOP: every point observed by h_walk_kf[0], the query keyframe (:853-858).  Each point
+        once, in ASCENDING POINT ID (the reference's order is that of a hash set and no function of its input).
+     2. keyframe table.  Entry 0 is the root; behind it, in ascending id, the anchor keyframes of the source points and the keyframes of h_walk_kf, each once.
+        Flags: SVS_REG_KF_IN_WINDOW from the map, SVS_REG_KF_DIRECT_NEIGHBOR for the root and the ids of h_direct_kf.  The root's pyramid, disparity and
+        stored thresholds come from the map; T_root_from_world from the request (the loop closure's is not the stored pose, :845).
+     3. observer rows (SVS_REG_LOCAL): for each source point the table entries of the keyframes that observe it, ascending; observers outside the table are left out.
+   From there the chain of svs_reg_register_batch runs unchanged: the outputs are byte for byte those of svs_reg_register_batch on that request.  h_kf_stats and
+   h_cand_src refer to the built table and list. */
+enum { SVS_REG_OVER_CAPACITY = 5 };    /* svs_reg_result.status of svs_reg_register_map_batch only */
+typedef struct {
+  int32_t mode;                        /* SVS_REG_LOCAL / SVS_REG_LOOP */
+  int32_t root_kf;                     /* id */
+  int32_t n_walk, n_direct;            /* each <= the registrar's max_keyframes; SVS_REG_LOOP: n_walk >= 1 */
+  double T_root_from_world[12];
+  const int32_t *h_walk_kf;            /* HOST [n_walk]: framesInNeighborhood(root) / the query keyframe */
+  const int32_t *h_direct_kf;          /* HOST [n_direct]: directNeighborsOf(root); the root need not be listed */
+} svs_reg_map_request;
+/* BLOCKING: one staged upload of ids, one download, no host synchronisation in between (the first call behind an svs_map_add_observations also rebuilds the
+   map's two CSR views on the stream; the first call with more requests than any before allocates the walk's bitmaps).  map and reg belong to one context.
+   Outputs as svs_reg_register_batch, and (each optional, HOST): h_cand_point_id [n_requests][max_points]: the built source list's point id of every candidate
+   (-1 behind n_candidates); h_kf_ids [n_requests][max_keyframes]: the ids of the built table (-1 behind it); h_n_kf [n_requests]: its length.
+   A built table above the registrar's max_keyframes, a source list above max_points or observer rows above max_observers are only known on the device: that
+   request is answered with status SVS_REG_OVER_CAPACITY, every other byte of its outputs zero (h_n_kf 0), the call returns SVS_OK and the other requests of the
+   batch are unaffected.  An unknown id in a request, a root whose pyramid or disparity is narrower than the registrar's camera: SVS_ERR_INVALID before anything is
+   launched.  A request's outputs are a function of the map's content and of that request alone: not of the order or grouping of the updates that built the map,
+   of the rest of the batch, or of repetition. */
+int svs_reg_register_map_batch(svs_reg *reg, svs_map *map, int n_requests, const svs_reg_map_request *req, const svs_reg_params *prm, svs_reg_result *h_res,
+                               int32_t *h_cand_src, svs_match_result *h_matches, int32_t *h_status_pass1, int32_t *h_accepted, svs_reg_kf_stats *h_kf_stats,
+                               svs_match_result *h_matches_pass1, int32_t *h_cand_point_id, int32_t *h_kf_ids, int32_t *h_n_kf);
+
 /* ---- multi-GPU: the library-owned collective of the landmark-sharded back-end.  The reference has no
    distributed code; one process per GPU each creates a context and a communicator (RCCL, bound at run time) --------------*/
 typedef struct { char bytes[128]; } svs_unique_id;      /* = ncclUniqueId */

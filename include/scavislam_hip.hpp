@@ -839,6 +839,65 @@ struct RegistrationKeyframe {            // one candidate keyframe: keyframe_map
   bool direct_neighbor;                  // IS_IN_SET(frame_id, directNeighborsOf(root)) (:433-449)
 };
 struct TrackPoint { int global_id; double uvu[3]; int anchor_level; };      // StereoGraph::MyTrackPoint: point id + ImageFeature<3>(uvu, anchor_level)
+
+// The back end's map kept on the device for re-registration (svs_map_*): the vertex_table's poses and frames, the point_table, and every feature_table as
+// (point, keyframe) pairs, under the graph's own ids.  The back-end thread feeds it as the graph grows -- addKeyframes / addPoints / addObservations from
+// addKeyframeToGraph, setPoses / setPoints from the restoreDataFromG2o walk, setWindow from graph_.double_window() -- and BackendRegistration::registerFrames
+// names a registration by ids.  Every update is one staged upload, asynchronous on the context's stream; false = refused as a whole (Context::lastError).
+class BackendMap {
+ public:
+  BackendMap(const Context &c, int max_keyframes = 4096, int max_points = 1 << 20, int max_observations = 1 << 22) : ctx_(c), map_(nullptr) {
+    ok_ = c.check(svs_map_create(c.get(), max_keyframes, max_points, max_observations, &map_));
+    if (ok_) level_.assign((size_t)max_points, 0);
+  }
+  ~BackendMap() { if (map_) svs_map_destroy(map_); }
+  BackendMap(const BackendMap &) = delete;
+  BackendMap &operator=(const BackendMap &) = delete;
+  bool ok() const { return ok_; }
+  svs_map *get() const { return map_; }
+  // keyframes[i].kf: T_me_from_world and the device pyramid; frames[i]: d_disp / disp_stride / cell_grid2d are read (table_entry and T_from_world are not)
+  bool addKeyframes(const std::vector<RegistrationKeyframe> &keyframes, const std::vector<RegistrationFrame> &frames) {
+    const size_t n = keyframes.size();
+    if (!ok_ || frames.size() != n) return false;
+    std::vector<int32_t> ids(n), stride(n), thr(n * SVS_NUM_PYR_LEVELS * SVS_MAX_CELLS, 25);
+    std::vector<svs_keyframe> kfs(n);
+    std::vector<const float *> disp(n);
+    for (size_t i = 0; i < n; ++i) {
+      ids[i] = keyframes[i].frame_id; kfs[i] = keyframes[i].kf; disp[i] = frames[i].d_disp; stride[i] = frames[i].disp_stride;
+      for (int l = 0; l < SVS_NUM_PYR_LEVELS; ++l)
+        for (size_t c = 0; c < frames[i].cell_grid2d[l].size() && c < SVS_MAX_CELLS; ++c) thr[(i * SVS_NUM_PYR_LEVELS + l) * SVS_MAX_CELLS + c] = frames[i].cell_grid2d[l][c];
+    }
+    if (!ctx_.check(svs_map_add_keyframes(map_, (int)n, ids.data(), kfs.data(), disp.data(), stride.data(), thr.data()))) return false;
+    return true;      // (in_double_window is not read: the window is set as a whole, setWindow)
+  }
+  // points[i].point_id: the id; points[i].kf_index: the ID of the anchor keyframe (p.anchorframe_id)
+  bool addPoints(const std::vector<svs_candidate_point> &points) {
+    if (!ok_) return false;
+    std::vector<int32_t> ids(points.size());
+    for (size_t i = 0; i < points.size(); ++i) ids[i] = points[i].point_id;
+    if (!ctx_.check(svs_map_add_points(map_, (int)points.size(), ids.data(), points.data()))) return false;
+    for (size_t i = 0; i < points.size(); ++i) level_[(size_t)ids[i]] = (int8_t)points[i].anchor_level;
+    return true;
+  }
+  // v.feature_table of keyframe kf_ids[i] holds point point_ids[i]
+  bool addObservations(const std::vector<int32_t> &point_ids, const std::vector<int32_t> &kf_ids) {
+    return ok_ && point_ids.size() == kf_ids.size() && ctx_.check(svs_map_add_observations(map_, (int)point_ids.size(), point_ids.data(), kf_ids.data()));
+  }
+  bool setPoses(const std::vector<int32_t> &kf_ids, const std::vector<double> &poses12) {
+    return ok_ && poses12.size() == 12 * kf_ids.size() && ctx_.check(svs_map_set_poses(map_, (int)kf_ids.size(), kf_ids.data(), poses12.data()));
+  }
+  bool setPoints(const std::vector<int32_t> &point_ids, const std::vector<double> &xyz_anchor3) {
+    return ok_ && xyz_anchor3.size() == 3 * point_ids.size() && ctx_.check(svs_map_set_points(map_, (int)point_ids.size(), point_ids.data(), xyz_anchor3.data()));
+  }
+  bool setWindow(const std::vector<int32_t> &kf_ids) { return ok_ && ctx_.check(svs_map_set_window(map_, (int)kf_ids.size(), kf_ids.data())); }
+  int anchorLevel(int point_id) const { return point_id >= 0 && (size_t)point_id < level_.size() ? level_[(size_t)point_id] : 0; }
+
+ private:
+  const Context &ctx_;
+  svs_map *map_;
+  std::vector<int8_t> level_;      // anchor_level by point id: MyTrackPoint carries it
+  bool ok_;
+};
 class BackendRegistration {
  public:
   BackendRegistration(const Context &c, const svs_cam &stereo_cam, int max_points = 4096, int max_keyframes = 256, int max_observers = 65536, int covis_thr = 15)
@@ -890,6 +949,43 @@ class BackendRegistration {
       if (accepted_[i]) trackpoint_list->push_back(track_point(points[cand_src_[i]], matches_[i]));
     return true;
   }
+  // localRegisterFrame (mode SVS_REG_LOCAL: walk = framesInNeighborhood(root), direct = directNeighborsOf(root)) / globalLoopClosure (SVS_REG_LOOP: root = the
+  // loop keyframe, T_root_from_world = T_loop_from_world (:845), walk = {the query keyframe}) against a device-resident map: the point walk, the keyframe table and the
+  // observer rows are built on the device.  neighborid_to_strength: (frame_id, strength) of the qualifying keyframes in ascending id (loop mode: the loop keyframe
+  // with the frame-wide strength); trackpoint_list: the accepted observations once, in ascending point id -- the caller's feature tables say which of the
+  // qualifying keyframes shares which.  false with lastResult().status == SVS_REG_OVER_CAPACITY: the built request exceeds this object's capacities
+  bool registerFrames(const BackendMap &map, int mode, int root_id, const double T_root_from_world[12], const std::vector<int32_t> &walk, const std::vector<int32_t> &direct,
+                      double T_newroot_from_oldroot[12], std::vector<std::pair<int, int> > *neighborid_to_strength, std::vector<TrackPoint> *trackpoint_list) {
+    if (neighborid_to_strength) neighborid_to_strength->clear();
+    if (trackpoint_list) trackpoint_list->clear();
+    if (!ok_ || !map.ok()) return false;
+    svs_reg_map_request q;
+    std::memset(&q, 0, sizeof q);
+    q.mode = mode; q.root_kf = root_id; q.n_walk = (int32_t)walk.size(); q.n_direct = (int32_t)direct.size();
+    std::memcpy(q.T_root_from_world, T_root_from_world, sizeof q.T_root_from_world);
+    q.h_walk_kf = walk.empty() ? nullptr : walk.data(); q.h_direct_kf = direct.empty() ? nullptr : direct.data();
+    cand_src_.assign((size_t)max_points_, -1); matches_.assign((size_t)max_points_, svs_match_result()); accepted_.assign((size_t)max_points_, 0);
+    kf_stats_.assign((size_t)max_keyframes_, svs_reg_kf_stats());
+    point_ids_.assign((size_t)max_points_, -1); kf_ids_.assign((size_t)max_keyframes_, -1);
+    int32_t n_kf = 0;
+    if (!ctx_.check(svs_reg_register_map_batch(reg_, map.get(), 1, &q, &prm_, &last_, cand_src_.data(), matches_.data(), nullptr, accepted_.data(), kf_stats_.data(),
+                                                nullptr, point_ids_.data(), kf_ids_.data(), &n_kf)))
+      return false;
+    if (T_newroot_from_oldroot) std::memcpy(T_newroot_from_oldroot, last_.T_newroot_from_oldroot, sizeof last_.T_newroot_from_oldroot);
+    if (last_.status != SVS_REG_OK) return false;
+    for (int k = 0; neighborid_to_strength && k < n_kf; ++k)
+      if (kf_stats_[(size_t)k].qualifies) neighborid_to_strength->push_back(std::make_pair((int)kf_ids_[(size_t)k], (int)kf_stats_[(size_t)k].strength));
+    for (int i = 0; trackpoint_list && i < last_.n_candidates; ++i) {
+      if (!accepted_[(size_t)i]) continue;
+      svs_candidate_point p;
+      std::memset(&p, 0, sizeof p);
+      p.point_id = point_ids_[(size_t)i]; p.anchor_level = map.anchorLevel(p.point_id);
+      trackpoint_list->push_back(track_point(p, matches_[(size_t)i]));
+    }
+    return true;
+  }
+  const std::vector<int32_t> &lastPointIds() const { return point_ids_; }          // registerFrames: per candidate
+  const std::vector<int32_t> &lastKeyframeIds() const { return kf_ids_; }          // registerFrames: per table entry
   const svs_reg_result &lastResult() const { return last_; }                       // status says which exit was taken
   const std::vector<svs_reg_kf_stats> &lastKeyframeStats() const { return kf_stats_; }
   const std::vector<svs_match_result> &lastMatches() const { return matches_; }
@@ -931,7 +1027,7 @@ class BackendRegistration {
   int max_points_, max_keyframes_;
   svs_reg_params prm_;
   svs_reg_result last_;
-  std::vector<int32_t> cand_src_, accepted_;
+  std::vector<int32_t> cand_src_, accepted_, point_ids_, kf_ids_;
   std::vector<svs_match_result> matches_;
   std::vector<svs_reg_kf_stats> kf_stats_;
   bool ok_;

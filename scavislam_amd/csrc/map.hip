@@ -1,0 +1,636 @@
+// map.hip -- the back end's map kept on the device for keyframe re-registration (svs_map_*), and the walk that builds the requests of the registration chain
+// (register.hip) from it: pointsVisibleInRoot's point walk (backend.cpp:480-497) / the query keyframe's feature_table (:853-858) as set operations.
+//   storage         keyframes, points and thresholds by id; the observations as an append log of (point, keyframe) pairs plus two CSR views -- by keyframe
+//                   (a feature_table) and by point (an observer row, sorted by keyframe id) -- rebuilt by a counting sort when the log has grown
+//   map_scatter_*   the updates: one staged upload, one lane per record (16-byte loads of the 64-byte point records)
+//   map_count / map_scan / map_fill / map_sort_rows      the CSR rebuild
+//   map_build_kernel    one workgroup per request: the walk and direct sets and the built table are LDS bitmaps over keyframe ids, the point set a bitmap in
+//                   global memory (one row per request); marking walks the feature_tables of the walk set, compaction turns bitmap words into ascending ids by
+//                   popcounts and a wave64 / workgroup prefix, so no atomic decides an order: the built request is a function of the map's content alone
+// Integer and copy work throughout; the host keeps the id sets and the set of pairs, so every refusal happens before anything is uploaded.
+#include "reg_map.h"
+#include <string.h>
+#include <algorithm>
+#include <unordered_set>
+#include <vector>
+
+namespace {
+constexpr int MB_THREADS = 512;
+constexpr int MAP_MAX_KF = 16384;
+constexpr int MAP_KF_WORDS = MAP_MAX_KF / 32;      // = MB_THREADS: one bitmap word per lane
+constexpr int THR_N = SVS_NUM_PYR_LEVELS * SVS_MAX_CELLS;
+static_assert(MAP_KF_WORDS == MB_THREADS, "the rank pass gives every lane one word");
+static_assert(sizeof(svs_candidate_point) == 64 && sizeof(svs_keyframe) == 136, "record copies below");
+
+// the map's tables as the kernels read them
+struct MapK {
+  svs_keyframe *kf; const float **kf_disp; int32_t *kf_dstride; int32_t *kf_thr; uint8_t *kf_flags;
+  svs_candidate_point *pt;
+  const int2 *log; int n_log;
+  int32_t *kf_begin, *kf_rows, *pt_begin, *pt_rows, *kf_cur, *pt_cur;
+  int kf_hi, pt_hi;                    // every id in use is below these
+  uint32_t *mark; size_t mark_b;       // [requests][mark_b] words: the point set of a request
+};
+
+// ---- updates: lane i scatters staged record i -------------------------------------------------------------------------------------------------------
+struct kf_up { int32_t id, disp_stride; const float *disp; svs_keyframe kf; int32_t thr[THR_N]; };
+static_assert(sizeof(kf_up) % 8 == 0, "staged as an array");
+
+__global__ __launch_bounds__(256) void map_scatter_kf_kernel(MapK M, const kf_up *up, int n) {
+  // 64 lanes per record: the thresholds are the bulk
+  const int i = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  if (i >= n) return;
+  const kf_up &u = up[i];
+  const int id = u.id;
+  for (int k = lane; k < THR_N; k += 64) M.kf_thr[(size_t)id * THR_N + k] = u.thr[k];
+  if (lane < 17) reinterpret_cast<long long *>(M.kf + id)[lane] = reinterpret_cast<const long long *>(&u.kf)[lane];
+  if (lane == 17) { M.kf_disp[id] = u.disp; M.kf_dstride[id] = u.disp_stride; M.kf_flags[id] = 0; }
+}
+
+__global__ __launch_bounds__(256) void map_scatter_pt_kernel(MapK M, const int32_t *ids, const svs_candidate_point *up, int n) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const int id = ids[i];
+  const int4 *s4 = reinterpret_cast<const int4 *>(up + i);
+  int4 *d4 = reinterpret_cast<int4 *>(M.pt + id);
+  int4 q = s4[3];
+  q.z = id; q.w = 0;                   // anchor_level, kf_index (the anchor's id), point_id, pad_
+  d4[0] = s4[0]; d4[1] = s4[1]; d4[2] = s4[2]; d4[3] = q;
+}
+
+__global__ __launch_bounds__(256) void map_scatter_pose_kernel(MapK M, const int32_t *ids, const double *poses, int n) {
+  const int t = blockIdx.x * 256 + threadIdx.x, i = t / 12, k = t % 12;
+  if (i < n) M.kf[ids[i]].T_anchor_from_w[k] = poses[(size_t)i * 12 + k];
+}
+
+__global__ __launch_bounds__(256) void map_scatter_xyz_kernel(MapK M, const int32_t *ids, const double *xyz, int n) {
+  const int t = blockIdx.x * 256 + threadIdx.x, i = t / 3, k = t % 3;
+  if (i < n) M.pt[ids[i]].xyz_anchor[k] = xyz[(size_t)i * 3 + k];
+}
+
+// set == 0: every flag byte below kf_hi loses the bit; set == 1: the listed keyframes get it (two launches, stream order)
+__global__ __launch_bounds__(256) void map_window_kernel(MapK M, const int32_t *ids, int n, int set) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (set) { if (i < n) M.kf_flags[ids[i]] = SVS_REG_KF_IN_WINDOW; }
+  else if (i < M.kf_hi) M.kf_flags[i] = 0;
+}
+
+// ---- the CSR rebuild -----------------------------------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ int wave_incl_scan(int v) {
+  const int lane = lane_id();
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) { const int t = __shfl_up(v, o, 64); if (lane >= o) v += t; }
+  return v;
+}
+// exclusive prefix of v over the MB_THREADS lanes of the workgroup, `total` = the sum; every lane calls it (two barriers inside)
+__device__ __forceinline__ int block_excl_scan(int v, int *s_w, int &total) {
+  const int lane = lane_id(), wave = threadIdx.x >> 6;
+  const int inc = wave_incl_scan(v);
+  if (lane == 63) s_w[wave] = inc;
+  __syncthreads();
+  int off = 0, tot = 0;
+#pragma unroll
+  for (int w = 0; w < MB_THREADS / 64; ++w) { const int k = s_w[w]; off += w < wave ? k : 0; tot += k; }
+  __syncthreads();
+  total = tot;
+  return off + inc - v;
+}
+
+// ctr[key] += 1 for every active lane, with ONE atomic per distinct key of the wave: the log is appended a feature_table at a time, so the 64 lanes of a wave
+// mostly hold one keyframe, and 64 atomics on one address serialise in the L2.  Returns the lane's slot (the counter's old value + its rank among the wave's
+// lanes with that key), -1 for an inactive lane.  Every lane of the wave calls it (ballots and shuffles inside)
+__device__ __forceinline__ int wave_add_by_key(int32_t *ctr, int key, bool active) {
+  const int lane = lane_id();
+  int slot = -1;
+  unsigned long long todo = __ballot(active);
+  while (todo) {                                         // wave-uniform
+    const int leader = __ffsll((long long)todo) - 1;     // an active lane
+    const int k0 = __shfl(key, leader, 64);
+    const bool mine = active && key == k0;
+    const unsigned long long mask = __ballot(mine);      // holds the leader's bit: the loop ends
+    int base = 0;
+    if (lane == leader) base = atomicAdd(&ctr[k0], __popcll(mask));
+    base = __shfl(base, leader, 64);
+    if (mine) { slot = base + __popcll(mask & ((1ull << lane) - 1ull)); active = false; }
+    todo &= ~mask;
+  }
+  return slot;
+}
+
+__global__ __launch_bounds__(256) void map_count_kernel(MapK M) {
+  const int e = blockIdx.x * 256 + threadIdx.x;
+  const bool active = e < M.n_log;
+  const int2 o = active ? M.log[e] : make_int2(0, 0);      // (point, keyframe): ids the host has checked
+  if (active) atomicAdd(&M.pt_begin[o.x], 1);              // a point is in a wave once, but for pairs of different feature_tables
+  (void)wave_add_by_key(M.kf_begin, o.y, active);
+}
+
+// workgroup 0: keyframes, workgroup 1: points.  counts [n] -> begin [n + 1] in place, and a copy as the fill cursors.  Eight entries per lane and step (two
+// 16-byte loads where all eight exist), so the single workgroup's chain of barriers is n / 4096 steps long
+constexpr int SCAN_ITEMS = 8;
+__global__ __launch_bounds__(MB_THREADS) void map_scan_kernel(MapK M) {
+  __shared__ int s_w[MB_THREADS / 64];
+  int32_t *a = blockIdx.x == 0 ? M.kf_begin : M.pt_begin, *cur = blockIdx.x == 0 ? M.kf_cur : M.pt_cur;
+  const int n = blockIdx.x == 0 ? M.kf_hi : M.pt_hi;
+  int run = 0;
+  for (int base = 0; base <= n; base += MB_THREADS * SCAN_ITEMS) {      // block-uniform; entry n becomes the total
+    const int i0 = base + threadIdx.x * SCAN_ITEMS;                     // a multiple of 8: 16-byte aligned in a hipMalloc block
+    int v[SCAN_ITEMS];
+    if (i0 + SCAN_ITEMS <= n) {
+      const int4 lo = reinterpret_cast<const int4 *>(a + i0)[0], hi = reinterpret_cast<const int4 *>(a + i0)[1];
+      v[0] = lo.x; v[1] = lo.y; v[2] = lo.z; v[3] = lo.w; v[4] = hi.x; v[5] = hi.y; v[6] = hi.z; v[7] = hi.w;
+    } else {
+#pragma unroll
+      for (int k = 0; k < SCAN_ITEMS; ++k) v[k] = i0 + k < n ? a[i0 + k] : 0;
+    }
+    int sum = 0;
+#pragma unroll
+    for (int k = 0; k < SCAN_ITEMS; ++k) { const int c = v[k]; v[k] = sum; sum += c; }
+    int tot;
+    const int off = run + block_excl_scan(sum, s_w, tot);
+    if (i0 + SCAN_ITEMS <= n + 1) {
+      const int4 lo = make_int4(off + v[0], off + v[1], off + v[2], off + v[3]), hi = make_int4(off + v[4], off + v[5], off + v[6], off + v[7]);
+      reinterpret_cast<int4 *>(a + i0)[0] = lo; reinterpret_cast<int4 *>(a + i0)[1] = hi;
+      reinterpret_cast<int4 *>(cur + i0)[0] = lo; reinterpret_cast<int4 *>(cur + i0)[1] = hi;
+    } else {
+#pragma unroll
+      for (int k = 0; k < SCAN_ITEMS; ++k)
+        if (i0 + k <= n) { a[i0 + k] = off + v[k]; cur[i0 + k] = off + v[k]; }
+    }
+    run += tot;
+  }
+}
+
+// the position inside a row is whatever the atomics give: rows by keyframe are read as sets, rows by point are sorted by the next kernel
+__global__ __launch_bounds__(256) void map_fill_kernel(MapK M) {
+  const int e = blockIdx.x * 256 + threadIdx.x;
+  const bool active = e < M.n_log;
+  const int2 o = active ? M.log[e] : make_int2(0, 0);
+  if (active) M.pt_rows[atomicAdd(&M.pt_cur[o.x], 1)] = o.y;      // < begin of the next row <= n_log
+  const int slot = wave_add_by_key(M.kf_cur, o.y, active);
+  if (active) M.kf_rows[slot] = o.x;
+}
+
+// one lane per point: its observer row ascending (rows are a handful of keyframes long: insertion sort; pairs are distinct)
+__global__ __launch_bounds__(256) void map_sort_rows_kernel(MapK M) {
+  const int p = blockIdx.x * 256 + threadIdx.x;
+  if (p >= M.pt_hi) return;
+  const int b = M.pt_begin[p], e = M.pt_begin[p + 1];
+  for (int i = b + 1; i < e; ++i) {
+    const int v = M.pt_rows[i];
+    int j = i - 1;
+    while (j >= b && M.pt_rows[j] > v) { M.pt_rows[j + 1] = M.pt_rows[j]; --j; }
+    M.pt_rows[j + 1] = v;
+  }
+}
+
+// ---- the walk: one workgroup per request ---------------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ bool bit_of(const uint32_t *s, int i) { return (s[i >> 5] >> (i & 31)) & 1u; }
+
+__global__ __launch_bounds__(MB_THREADS) void map_build_kernel(MapK M, MapBuildDst D) {
+  __shared__ uint32_t s_walk[MAP_KF_WORDS], s_dir[MAP_KF_WORDS], s_tab[MAP_KF_WORDS];
+  __shared__ int s_rank[MAP_KF_WORDS];
+  __shared__ int s_w[MB_THREADS / 64];
+  const int r = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const map_req &Q = D.req[r];
+  const int root = Q.root, mode = Q.mode;
+  const int32_t *walk = D.ids + Q.walk_off, *direct = D.ids + Q.direct_off;
+  uint32_t *mark = M.mark + (size_t)r * M.mark_b;
+  const int n_words = (M.pt_hi + 31) >> 5;                      // <= mark_b
+  // a. empty sets
+  s_walk[tid] = 0; s_dir[tid] = 0; s_tab[tid] = 0;
+  for (int i = tid; i < n_words; i += MB_THREADS) mark[i] = 0;
+  __syncthreads();
+  // b. the keyframe sets (ids the host has checked: in the map, so below kf_hi <= MAP_MAX_KF)
+  for (int i = tid; i < Q.n_direct; i += MB_THREADS) { const int id = direct[i]; atomicOr(&s_dir[id >> 5], 1u << (id & 31)); }
+  for (int i = tid; i < Q.n_walk; i += MB_THREADS) { const int id = walk[i]; atomicOr(&s_walk[id >> 5], 1u << (id & 31)); }
+  if (tid == 0) atomicOr(&s_dir[root >> 5], 1u << (root & 31));      // directNeighborsOf inserts the frame itself (:437)
+  __syncthreads();
+  // c. mark the points: a wave per feature_table
+  const int n_marking = mode == SVS_REG_LOOP ? 1 : Q.n_walk;
+  for (int i = wave; i < n_marking; i += MB_THREADS / 64) {
+    const int kf = walk[i];
+    if (mode == SVS_REG_LOCAL && bit_of(s_dir, kf)) continue;      // (:485)
+    const int e1 = M.kf_begin[kf + 1];
+    for (int e = M.kf_begin[kf] + lane; e < e1; e += 64) {
+      const int p = M.kf_rows[e];
+      if ((unsigned)p < (unsigned)M.pt_hi) atomicOr(&mark[p >> 5], 1u << (p & 31));
+    }
+  }
+  __syncthreads();
+  // d. the source list: the set bits in ascending order
+  int n_src = 0;
+  for (int base = 0; base < n_words; base += MB_THREADS) {      // block-uniform trip count
+    const int w = base + tid;
+    uint32_t bits = w < n_words ? __hip_atomic_load(&mark[w], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0u;
+    int tot;
+    int pos = n_src + block_excl_scan(__popc(bits), s_w, tot);
+    while (bits) {
+      const int b = __ffs((int)bits) - 1;
+      bits &= bits - 1;
+      if (pos < D.SB) D.point_id[(size_t)r * D.NP + pos] = (w << 5) + b;      // SB <= NP
+      ++pos;
+    }
+    n_src += tot;
+  }
+  const int n_src_c = min(n_src, D.SB);
+  __syncthreads();
+  // e. the records (four 16-byte loads each); their anchors join the table
+  svs_candidate_point *src = D.src + (size_t)r * D.SB;
+  for (int i = tid; i < n_src_c; i += MB_THREADS) {
+    const int p = D.point_id[(size_t)r * D.NP + i];
+    const int4 *s4 = reinterpret_cast<const int4 *>(M.pt + p);
+    int4 *d4 = reinterpret_cast<int4 *>(src + i);
+    const int4 q = s4[3];
+    d4[0] = s4[0]; d4[1] = s4[1]; d4[2] = s4[2]; d4[3] = q;      // kf_index: still the anchor's id (translated in g)
+    if ((unsigned)q.y < (unsigned)MAP_MAX_KF) atomicOr(&s_tab[q.y >> 5], 1u << (q.y & 31));
+  }
+  __syncthreads();
+  // f. the table: entry 0 the root, behind it anchors and walk keyframes in ascending id; the rank of a word's first bit by a prefix over the popcounts
+  int n_kf;
+  {
+    uint32_t bits = s_tab[tid] | s_walk[tid];
+    if (tid == (root >> 5)) bits &= ~(1u << (root & 31));
+    s_tab[tid] = bits;                                            // a lane's own word
+    int tot;
+    const int rank = block_excl_scan(__popc(bits), s_w, tot);
+    s_rank[tid] = rank;
+    n_kf = 1 + tot;
+    svs_keyframe *kfs = D.kfs + (size_t)r * D.KB;
+    uint8_t *flags = D.flags + (size_t)r * D.KB;
+    int32_t *kf_id = D.kf_id + (size_t)r * D.KB;
+    int e = 1 + rank;
+    while (bits) {
+      const int id = (tid << 5) + __ffs((int)bits) - 1;
+      bits &= bits - 1;
+      if (e < D.KB) {
+        for (int k = 0; k < 17; ++k) reinterpret_cast<long long *>(kfs + e)[k] = reinterpret_cast<const long long *>(M.kf + id)[k];
+        flags[e] = (uint8_t)((M.kf_flags[id] & SVS_REG_KF_IN_WINDOW) | (bit_of(s_dir, id) ? SVS_REG_KF_DIRECT_NEIGHBOR : 0));
+        kf_id[e] = id;
+      }
+      ++e;
+    }
+    if (tid == 0) {                                               // KB >= 1
+      for (int k = 0; k < 17; ++k) reinterpret_cast<long long *>(kfs)[k] = reinterpret_cast<const long long *>(M.kf + root)[k];
+      flags[0] = (uint8_t)((M.kf_flags[root] & SVS_REG_KF_IN_WINDOW) | SVS_REG_KF_DIRECT_NEIGHBOR);
+      kf_id[0] = root;
+    }
+    // behind the table: what the stateless call's staging holds there
+    for (int k = min(n_kf, D.KB) + tid; k < D.KB; k += MB_THREADS) {
+      for (int q = 0; q < 17; ++q) reinterpret_cast<long long *>(kfs + k)[q] = 0;
+      flags[k] = 0;
+    }
+  }
+  __syncthreads();
+  // g. anchors as table entries; the observer rows
+  int32_t *ob = D.obs_begin + (size_t)r * (D.SB + 1), *ok = D.obs_kf + (size_t)r * D.OB;
+  int n_obs = 0;
+  for (int base = 0; base < n_src_c; base += MB_THREADS) {      // block-uniform
+    const int i = base + tid;
+    int c = 0, p = -1, row_b = 0, row_e = 0;
+    bool has_root = false;
+    if (i < n_src_c) {
+      const int a = src[i].kf_index;                              // written by this lane in e
+      src[i].kf_index = a == root ? 0 : 1 + s_rank[a >> 5] + __popc(s_tab[a >> 5] & ((1u << (a & 31)) - 1u));
+      if (mode == SVS_REG_LOCAL) {
+        p = D.point_id[(size_t)r * D.NP + i];
+        row_b = M.pt_begin[p]; row_e = M.pt_begin[p + 1];
+        for (int e = row_b; e < row_e; e += 4) {                   // four loads in flight: a row is read at the latency of a quarter of its entries
+          int kf[4];
+#pragma unroll
+          for (int k = 0; k < 4; ++k) kf[k] = e + k < row_e ? M.pt_rows[e + k] : -1;
+#pragma unroll
+          for (int k = 0; k < 4; ++k) {
+            if (kf[k] == root) has_root = true;
+            else if ((unsigned)kf[k] < (unsigned)MAP_MAX_KF && bit_of(s_tab, kf[k])) ++c;
+          }
+        }
+        c += has_root ? 1 : 0;
+      }
+    }
+    int tot;
+    int pos = n_obs + block_excl_scan(c, s_w, tot);
+    if (i < n_src_c && mode == SVS_REG_LOCAL) {
+      ob[i] = pos;
+      if (has_root) { if (pos < D.OB) ok[pos] = 0; ++pos; }
+      for (int e = row_b; e < row_e; e += 4) {                     // ascending ids = ascending entries
+        int kf[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) kf[k] = e + k < row_e ? M.pt_rows[e + k] : -1;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+          if (kf[k] != root && (unsigned)kf[k] < (unsigned)MAP_MAX_KF && bit_of(s_tab, kf[k])) {
+            if (pos < D.OB) ok[pos] = 1 + s_rank[kf[k] >> 5] + __popc(s_tab[kf[k] >> 5] & ((1u << (kf[k] & 31)) - 1u));
+            ++pos;
+          }
+        }
+      }
+    }
+    n_obs += tot;
+  }
+  const bool over = n_src > D.SB || n_kf > D.KB || n_obs > D.OB;
+  if (tid == 0 && mode == SVS_REG_LOCAL) ob[n_src_c] = min(n_obs, D.OB);
+  // h. the request record.  Over capacity: a request without points, which the chain answers at its first exit
+  reg_hdr &H = D.hdr[r];
+  for (int k = tid; k < THR_N; k += MB_THREADS) (&H.thr[0][0])[k] = M.kf_thr[(size_t)root * THR_N + k];
+  if (tid < 12) H.T_root[tid] = Q.T_root[tid];
+  if (tid == 0) {
+    H.mode = mode; H.n_kf = over ? 1 : n_kf; H.n_src = over ? 0 : n_src; H.root_kf = 0;
+    H.disp = M.kf_disp[root]; H.disp_stride = M.kf_dstride[root]; H.pad_ = 0;
+    D.meta[r] = make_int4(n_kf, n_src, n_obs, over ? 1 : 0);
+  }
+}
+
+#define MAP_CAPACITY(ctx, cond)                                                                           \
+  do {                                                                                                    \
+    if (!(cond)) {                                                                                        \
+      char buf_[512];                                                                                     \
+      snprintf(buf_, sizeof buf_, "%s:%d capacity exceeded: %s", __FILE__, __LINE__, #cond);              \
+      (ctx)->err = buf_;                                                                                  \
+      return SVS_ERR_CAPACITY;                                                                            \
+    }                                                                                                     \
+  } while (0)
+}  // namespace
+
+struct svs_map {
+  svs_ctx *ctx = nullptr;
+  int max_kf = 0, max_pt = 0, max_obs = 0;
+  // the host's share: the id sets, the frames (where FAST and the matcher read a root), the set of pairs
+  std::vector<uint8_t> kf_in, pt_in;
+  std::vector<MapRootView> kf_view;
+  std::unordered_set<uint64_t> pairs;
+  std::vector<uint32_t> stamp; uint32_t stamp_now = 0;      // "twice in one call", by keyframe or point id
+  int n_kf = 0, n_pt = 0, n_obs = 0, kf_hi = 0, pt_hi = 0;
+  int csr_n = 0;                                            // the log length the CSR views were built from
+  // the device's
+  DevBuf<svs_keyframe> d_kf; DevBuf<const float *> d_kf_disp; DevBuf<int32_t> d_kf_dstride, d_kf_thr; DevBuf<uint8_t> d_kf_flags;
+  DevBuf<svs_candidate_point> d_pt;
+  DevBuf<int2> d_log;
+  DevBuf<int32_t> d_kf_begin, d_kf_rows, d_pt_begin, d_pt_rows, d_kf_cur, d_pt_cur;
+  DevBuf<uint32_t> d_mark; size_t mark_b = 0; int mark_rows = 0;
+  // staging of the updates: one pinned block and its device twin, reused once the upload out of the pinned block has happened
+  PinnedBuf<uint8_t> h_up; DevBuf<uint8_t> d_up; owned::Event up_ev; bool up_pending = false;
+  ~svs_map() {      // (before the members go, also when create gives up)
+    if (ctx) { (void)hipSetDevice(ctx->device); (void)hipStreamSynchronize(ctx->stream); }
+  }
+  MapK view() const {
+    MapK M{};
+    M.kf = d_kf; M.kf_disp = d_kf_disp; M.kf_dstride = d_kf_dstride; M.kf_thr = d_kf_thr; M.kf_flags = d_kf_flags;
+    M.pt = d_pt; M.log = d_log; M.n_log = n_obs;
+    M.kf_begin = d_kf_begin; M.kf_rows = d_kf_rows; M.pt_begin = d_pt_begin; M.pt_rows = d_pt_rows; M.kf_cur = d_kf_cur; M.pt_cur = d_pt_cur;
+    M.kf_hi = kf_hi; M.pt_hi = pt_hi;
+    M.mark = d_mark; M.mark_b = mark_b;
+    return M;
+  }
+  uint32_t next_stamp() {
+    if (++stamp_now == 0) { std::fill(stamp.begin(), stamp.end(), 0u); stamp_now = 1; }
+    return stamp_now;
+  }
+};
+
+svs_ctx *svs_map_ctx(svs_map *map) { return map ? map->ctx : nullptr; }
+bool svs_map_has_keyframe(const svs_map *map, int32_t id) { return map && id >= 0 && id < map->max_kf && map->kf_in[id]; }
+void svs_map_root_view(const svs_map *map, int32_t id, MapRootView *out) { *out = map->kf_view[id]; }
+
+extern "C" int svs_map_create(svs_ctx *ctx, int max_keyframes, int max_points, int max_observations, svs_map **out) {
+  SVS_REQUIRE(ctx, ctx && out && max_keyframes >= 1 && max_points >= 1 && max_observations >= 1);
+  if (max_keyframes > MAP_MAX_KF) { ctx->err = "svs_map_create: at most 16384 keyframes"; return SVS_ERR_UNSUPPORTED; }
+  SVS_REQUIRE(ctx, max_points < (1 << 30) && max_observations < (1 << 30));
+  SVS_DEVICE(ctx);
+  std::unique_ptr<svs_map> m(new svs_map());
+  m->ctx = ctx; m->max_kf = max_keyframes; m->max_pt = max_points; m->max_obs = max_observations;
+  m->kf_in.assign(max_keyframes, 0); m->pt_in.assign(max_points, 0);
+  m->kf_view.resize(max_keyframes);
+  m->stamp.assign(std::max(max_keyframes, max_points), 0u);
+  const size_t K = (size_t)max_keyframes, P = (size_t)max_points, O = (size_t)max_observations;
+  SVS_HIP(ctx, m->d_kf.alloc(K));
+  SVS_HIP(ctx, m->d_kf_disp.alloc(K));
+  SVS_HIP(ctx, m->d_kf_dstride.alloc(K));
+  SVS_HIP(ctx, m->d_kf_thr.alloc(K * THR_N));
+  SVS_HIP(ctx, m->d_kf_flags.alloc(K));
+  SVS_HIP(ctx, m->d_pt.alloc(P));
+  SVS_HIP(ctx, m->d_log.alloc(O));
+  SVS_HIP(ctx, m->d_kf_begin.alloc(K + 1));
+  SVS_HIP(ctx, m->d_kf_cur.alloc(K + 1));
+  SVS_HIP(ctx, m->d_pt_begin.alloc(P + 1));
+  SVS_HIP(ctx, m->d_pt_cur.alloc(P + 1));
+  SVS_HIP(ctx, m->d_kf_rows.alloc(O));
+  SVS_HIP(ctx, m->d_pt_rows.alloc(O));
+  SVS_HIP(ctx, m->up_ev.create(hipEventDisableTiming));
+  m->mark_b = (P + 31) / 32;
+  // empty CSR views: a request on a map without observations reads them
+  SVS_HIP(ctx, hipMemsetAsync(m->d_kf_begin, 0, (K + 1) * sizeof(int32_t), ctx->stream));
+  SVS_HIP(ctx, hipMemsetAsync(m->d_pt_begin, 0, (P + 1) * sizeof(int32_t), ctx->stream));
+  SVS_HIP(ctx, hipMemsetAsync(m->d_kf_flags, 0, K, ctx->stream));
+  *out = m.release();
+  return SVS_OK;
+}
+
+extern "C" int svs_map_destroy(svs_map *map) {
+  if (!map) return SVS_OK;
+  delete map;
+  return SVS_OK;
+}
+
+extern "C" int svs_map_info(svs_map *map, int32_t *n_keyframes, int32_t *n_points, int32_t *n_observations) {
+  if (!map) return SVS_ERR_INVALID;
+  if (n_keyframes) *n_keyframes = map->n_kf;
+  if (n_points) *n_points = map->n_pt;
+  if (n_observations) *n_observations = map->n_obs;
+  return SVS_OK;
+}
+
+// the pinned block, free to be written: the upload out of it that is still in flight has happened, and it holds `bytes`
+static int map_stage(svs_map *m, size_t bytes, uint8_t **out) {
+  svs_ctx *ctx = m->ctx;
+  if (m->up_pending) { SVS_HIP(ctx, hipEventSynchronize(m->up_ev)); m->up_pending = false; }
+  if (m->h_up.bytes() < bytes) {
+    // the device twin may still be read by the scatter of the last update
+    SVS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    const size_t want = std::max(bytes * 2, (size_t)1 << 16);
+    SVS_HIP(ctx, m->h_up.alloc(want));
+    SVS_HIP(ctx, m->d_up.alloc(want));
+  }
+  *out = m->h_up;
+  return SVS_OK;
+}
+static int map_upload(svs_map *m, void *d_dst, size_t bytes) {
+  svs_ctx *ctx = m->ctx;
+  SVS_HIP(ctx, hipMemcpyAsync(d_dst, m->h_up, bytes, hipMemcpyHostToDevice, ctx->stream));
+  SVS_HIP(ctx, hipEventRecord(m->up_ev, ctx->stream));
+  m->up_pending = true;
+  return SVS_OK;
+}
+static size_t up_align(size_t v) { return (v + 15) & ~(size_t)15; }
+
+// n ids, each below `cap`, each `present` in `in`, none twice
+static int map_check_ids(svs_map *m, int n, const int32_t *ids, const std::vector<uint8_t> &in, int cap, bool present) {
+  svs_ctx *ctx = m->ctx;
+  const uint32_t st = m->next_stamp();
+  for (int i = 0; i < n; ++i) {
+    const int32_t id = ids[i];
+    if (present) SVS_REQUIRE(ctx, id >= 0 && id < cap && in[id]);
+    else { SVS_REQUIRE(ctx, id >= 0); MAP_CAPACITY(ctx, id < cap); SVS_REQUIRE(ctx, !in[id]); }
+    SVS_REQUIRE(ctx, m->stamp[id] != st);
+    m->stamp[id] = st;
+  }
+  return SVS_OK;
+}
+
+extern "C" int svs_map_add_keyframes(svs_map *m, int n, const int32_t *h_ids, const svs_keyframe *h_keyframes, const float *const *h_disp_ptr,
+                                     const int32_t *h_disp_stride, const int32_t *h_fast_thr) {
+  svs_ctx *ctx = m ? m->ctx : nullptr;
+  SVS_REQUIRE(ctx, m && n >= 0 && (n == 0 || (h_ids && h_keyframes && h_disp_ptr && h_disp_stride && h_fast_thr)));
+  if (n == 0) return SVS_OK;
+  if (int rc = map_check_ids(m, n, h_ids, m->kf_in, m->max_kf, false)) return rc;
+  for (int i = 0; i < n; ++i) {
+    SVS_REQUIRE(ctx, h_disp_ptr[i] && h_disp_stride[i] > 0);
+    for (int l = 0; l < SVS_NUM_PYR_LEVELS; ++l) SVS_REQUIRE(ctx, h_keyframes[i].pyr[l] && h_keyframes[i].stride[l] > 0);
+    for (int k = 0; k < THR_N; ++k) SVS_REQUIRE(ctx, h_fast_thr[(size_t)i * THR_N + k] >= 10 && h_fast_thr[(size_t)i * THR_N + k] <= 255);
+  }
+  SVS_DEVICE(ctx);
+  uint8_t *hs;
+  if (int rc = map_stage(m, (size_t)n * sizeof(kf_up), &hs)) return rc;
+  kf_up *up = reinterpret_cast<kf_up *>(hs);
+  for (int i = 0; i < n; ++i) {
+    up[i].id = h_ids[i]; up[i].disp_stride = h_disp_stride[i]; up[i].disp = h_disp_ptr[i]; up[i].kf = h_keyframes[i]; up[i].kf.pad_ = 0;
+    memcpy(up[i].thr, h_fast_thr + (size_t)i * THR_N, sizeof up[i].thr);
+  }
+  if (int rc = map_upload(m, m->d_up, (size_t)n * sizeof(kf_up))) return rc;
+  hipLaunchKernelGGL(map_scatter_kf_kernel, dim3(div_up(n, 4)), dim3(256), 0, ctx->stream, m->view(), reinterpret_cast<const kf_up *>(m->d_up.get()), n);
+  SVS_LAUNCH_CHECK(ctx);
+  for (int i = 0; i < n; ++i) {
+    const int id = h_ids[i];
+    m->kf_in[id] = 1;
+    MapRootView &v = m->kf_view[id];
+    for (int l = 0; l < SVS_NUM_PYR_LEVELS; ++l) { v.pyr[l] = h_keyframes[i].pyr[l]; v.stride[l] = h_keyframes[i].stride[l]; }
+    v.disp = h_disp_ptr[i]; v.disp_stride = h_disp_stride[i];
+    m->kf_hi = std::max(m->kf_hi, id + 1);
+  }
+  m->n_kf += n;
+  return SVS_OK;
+}
+
+extern "C" int svs_map_add_points(svs_map *m, int n, const int32_t *h_ids, const svs_candidate_point *h_points) {
+  svs_ctx *ctx = m ? m->ctx : nullptr;
+  SVS_REQUIRE(ctx, m && n >= 0 && (n == 0 || (h_ids && h_points)));
+  if (n == 0) return SVS_OK;
+  if (int rc = map_check_ids(m, n, h_ids, m->pt_in, m->max_pt, false)) return rc;
+  for (int i = 0; i < n; ++i) SVS_REQUIRE(ctx, svs_map_has_keyframe(m, h_points[i].kf_index));
+  SVS_DEVICE(ctx);
+  const size_t o_pts = up_align((size_t)n * sizeof(int32_t)), bytes = o_pts + (size_t)n * sizeof(svs_candidate_point);
+  uint8_t *hs;
+  if (int rc = map_stage(m, bytes, &hs)) return rc;
+  memcpy(hs, h_ids, (size_t)n * sizeof(int32_t));
+  memcpy(hs + o_pts, h_points, (size_t)n * sizeof(svs_candidate_point));
+  if (int rc = map_upload(m, m->d_up, bytes)) return rc;
+  hipLaunchKernelGGL(map_scatter_pt_kernel, dim3(div_up(n, 256)), dim3(256), 0, ctx->stream, m->view(), reinterpret_cast<const int32_t *>(m->d_up.get()),
+                     reinterpret_cast<const svs_candidate_point *>(m->d_up.get() + o_pts), n);
+  SVS_LAUNCH_CHECK(ctx);
+  for (int i = 0; i < n; ++i) { m->pt_in[h_ids[i]] = 1; m->pt_hi = std::max(m->pt_hi, h_ids[i] + 1); }
+  m->n_pt += n;
+  return SVS_OK;
+}
+
+extern "C" int svs_map_add_observations(svs_map *m, int n, const int32_t *h_point_ids, const int32_t *h_kf_ids) {
+  svs_ctx *ctx = m ? m->ctx : nullptr;
+  SVS_REQUIRE(ctx, m && n >= 0 && (n == 0 || (h_point_ids && h_kf_ids)));
+  if (n == 0) return SVS_OK;
+  for (int i = 0; i < n; ++i) SVS_REQUIRE(ctx, h_point_ids[i] >= 0 && h_point_ids[i] < m->max_pt && m->pt_in[h_point_ids[i]] && svs_map_has_keyframe(m, h_kf_ids[i]));
+  // the pairs that are new, each once, in the caller's order
+  std::vector<int2> fresh;
+  std::unordered_set<uint64_t> seen;
+  for (int i = 0; i < n; ++i) {
+    const uint64_t key = ((uint64_t)(uint32_t)h_point_ids[i] << 32) | (uint32_t)h_kf_ids[i];
+    if (m->pairs.count(key) || !seen.insert(key).second) continue;
+    fresh.push_back(make_int2(h_point_ids[i], h_kf_ids[i]));
+  }
+  MAP_CAPACITY(ctx, (size_t)m->n_obs + fresh.size() <= (size_t)m->max_obs);
+  if (fresh.empty()) return SVS_OK;
+  SVS_DEVICE(ctx);
+  uint8_t *hs;
+  if (int rc = map_stage(m, fresh.size() * sizeof(int2), &hs)) return rc;
+  memcpy(hs, fresh.data(), fresh.size() * sizeof(int2));
+  if (int rc = map_upload(m, m->d_log.get() + m->n_obs, fresh.size() * sizeof(int2))) return rc;      // straight to the log's tail
+  for (const int2 &o : fresh) m->pairs.insert(((uint64_t)(uint32_t)o.x << 32) | (uint32_t)o.y);
+  m->n_obs += (int)fresh.size();
+  return SVS_OK;
+}
+
+// ids [n] and n rows of `row` doubles, scattered by `kernel`
+template <class Kernel>
+static int map_set_rows(svs_map *m, int n, const int32_t *ids, const double *rows, int row, Kernel kernel) {
+  svs_ctx *ctx = m->ctx;
+  SVS_DEVICE(ctx);
+  const size_t o_rows = up_align((size_t)n * sizeof(int32_t)), bytes = o_rows + (size_t)n * row * sizeof(double);
+  uint8_t *hs;
+  if (int rc = map_stage(m, bytes, &hs)) return rc;
+  memcpy(hs, ids, (size_t)n * sizeof(int32_t));
+  memcpy(hs + o_rows, rows, (size_t)n * row * sizeof(double));
+  if (int rc = map_upload(m, m->d_up, bytes)) return rc;
+  hipLaunchKernelGGL(kernel, dim3(div_up(n * row, 256)), dim3(256), 0, ctx->stream, m->view(), reinterpret_cast<const int32_t *>(m->d_up.get()),
+                     reinterpret_cast<const double *>(m->d_up.get() + o_rows), n);
+  SVS_LAUNCH_CHECK(ctx);
+  return SVS_OK;
+}
+
+extern "C" int svs_map_set_poses(svs_map *m, int n, const int32_t *h_kf_ids, const double *h_poses) {
+  svs_ctx *ctx = m ? m->ctx : nullptr;
+  SVS_REQUIRE(ctx, m && n >= 0 && (n == 0 || (h_kf_ids && h_poses)));
+  if (n == 0) return SVS_OK;
+  if (int rc = map_check_ids(m, n, h_kf_ids, m->kf_in, m->max_kf, true)) return rc;
+  return map_set_rows(m, n, h_kf_ids, h_poses, 12, map_scatter_pose_kernel);
+}
+
+extern "C" int svs_map_set_points(svs_map *m, int n, const int32_t *h_point_ids, const double *h_xyz_anchor) {
+  svs_ctx *ctx = m ? m->ctx : nullptr;
+  SVS_REQUIRE(ctx, m && n >= 0 && (n == 0 || (h_point_ids && h_xyz_anchor)));
+  if (n == 0) return SVS_OK;
+  if (int rc = map_check_ids(m, n, h_point_ids, m->pt_in, m->max_pt, true)) return rc;
+  return map_set_rows(m, n, h_point_ids, h_xyz_anchor, 3, map_scatter_xyz_kernel);
+}
+
+extern "C" int svs_map_set_window(svs_map *m, int n, const int32_t *h_kf_ids) {
+  svs_ctx *ctx = m ? m->ctx : nullptr;
+  SVS_REQUIRE(ctx, m && n >= 0 && (n == 0 || h_kf_ids));
+  if (int rc = map_check_ids(m, n, h_kf_ids, m->kf_in, m->max_kf, true)) return rc;
+  SVS_DEVICE(ctx);
+  if (n) {
+    uint8_t *hs;
+    if (int rc = map_stage(m, (size_t)n * sizeof(int32_t), &hs)) return rc;
+    memcpy(hs, h_kf_ids, (size_t)n * sizeof(int32_t));
+    if (int rc = map_upload(m, m->d_up, (size_t)n * sizeof(int32_t))) return rc;
+  }
+  if (m->kf_hi) {
+    hipLaunchKernelGGL(map_window_kernel, dim3(div_up(m->kf_hi, 256)), dim3(256), 0, ctx->stream, m->view(), (const int32_t *)nullptr, 0, 0);
+    SVS_LAUNCH_CHECK(ctx);
+  }
+  if (n) {
+    hipLaunchKernelGGL(map_window_kernel, dim3(div_up(n, 256)), dim3(256), 0, ctx->stream, m->view(), reinterpret_cast<const int32_t *>(m->d_up.get()), n, 1);
+    SVS_LAUNCH_CHECK(ctx);
+  }
+  return SVS_OK;
+}
+
+int svs_map_build_requests(svs_map *m, int n_requests, const MapBuildDst &dst) {
+  svs_ctx *ctx = m->ctx;
+  if (m->mark_rows < n_requests) {      // grow-only; a new block needs the stream drained of the walks that read the old one
+    SVS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    SVS_HIP(ctx, m->d_mark.alloc((size_t)n_requests * m->mark_b));
+    m->mark_rows = n_requests;
+  }
+  if (m->csr_n != m->n_obs) {
+    const MapK M = m->view();
+    SVS_HIP(ctx, hipMemsetAsync(m->d_kf_begin, 0, ((size_t)m->kf_hi + 1) * sizeof(int32_t), ctx->stream));
+    SVS_HIP(ctx, hipMemsetAsync(m->d_pt_begin, 0, ((size_t)m->pt_hi + 1) * sizeof(int32_t), ctx->stream));
+    hipLaunchKernelGGL(map_count_kernel, dim3(div_up(m->n_obs, 256)), dim3(256), 0, ctx->stream, M);
+    hipLaunchKernelGGL(map_scan_kernel, dim3(2), dim3(MB_THREADS), 0, ctx->stream, M);
+    hipLaunchKernelGGL(map_fill_kernel, dim3(div_up(m->n_obs, 256)), dim3(256), 0, ctx->stream, M);
+    hipLaunchKernelGGL(map_sort_rows_kernel, dim3(div_up(m->pt_hi, 256)), dim3(256), 0, ctx->stream, M);
+    SVS_LAUNCH_CHECK(ctx);
+    m->csr_n = m->n_obs;
+  }
+  hipLaunchKernelGGL(map_build_kernel, dim3(n_requests), dim3(MB_THREADS), 0, ctx->stream, m->view(), dst);
+  SVS_LAUNCH_CHECK(ctx);
+  return SVS_OK;
+}

@@ -1,0 +1,39 @@
+// reg_map.h -- what register.hip and map.hip share: the request record the registration chain reads, and the interface through which the device-resident
+// map (map.hip) builds such records, with their tables, in the registrar's own staging block.
+#pragma once
+#include "common.h"
+
+// one request as the chain's kernels read it (register.hip); the stateless call stages it from the host, the map builds it on the device
+struct reg_hdr {
+  int32_t mode, n_kf, n_src, root_kf;
+  const float *disp; int32_t disp_stride, pad_;
+  double T_root[12];
+  int32_t thr[SVS_NUM_PYR_LEVELS][SVS_MAX_CELLS];
+};
+
+// a request by ids as it is staged: the id lists of all requests lie in one array, walk_off / direct_off index it
+struct map_req {
+  int32_t mode, root, n_walk, n_direct, walk_off, direct_off, pad_[2];
+  double T_root[12];
+};
+
+// where the map's build kernel writes (all DEVICE): the regions of the registrar's staging block, rows of KB / SB / SB + 1 / OB entries per request, and of
+// its output block
+struct MapBuildDst {
+  const map_req *req; const int32_t *ids;
+  reg_hdr *hdr; svs_keyframe *kfs; uint8_t *flags; svs_candidate_point *src; int32_t *obs_begin; int32_t *obs_kf;
+  int KB, SB, OB;
+  int32_t *point_id; int NP;      // [R][NP]: the built source list
+  int32_t *kf_id;                 // [R][KB]: the built table
+  int4 *meta;                     // [R]: n_kf, n_src, observer entries (each as the walk found it, not clamped), over capacity
+};
+
+// the root of a request as the host needs it to lay out FAST and the matcher
+struct MapRootView { const uint8_t *pyr[SVS_NUM_PYR_LEVELS]; int32_t stride[SVS_NUM_PYR_LEVELS]; const float *disp; int32_t disp_stride; };
+
+svs_ctx *svs_map_ctx(svs_map *map);
+// host side: is the id a keyframe of the map; its frame
+bool svs_map_has_keyframe(const svs_map *map, int32_t id);
+void svs_map_root_view(const svs_map *map, int32_t id, MapRootView *out);
+// rebuilds the CSR views when the log has grown, then one workgroup per request builds what MapBuildDst names; asynchronous on the context's stream
+int svs_map_build_requests(svs_map *map, int n_requests, const MapBuildDst &dst);

@@ -14,10 +14,13 @@
 // A request that left at an exit has its candidate records turned into kf_index = -1, which the matcher answers with SVS_MATCH_NO_ANCHOR: the later stages
 // run over it and find nothing.  Requests of a batch are padded to the longest source list with such records.
 // Not pinned by the reference's binaries (backend.cpp is not among them): the yardstick of the cull and the counting is tests/register_model.py.
+// svs_reg_register_map_batch (at the end) runs the same chain (reg_chain) behind requests that the device-resident map (map.hip, reg_map.h) builds from ids in this
+// handle's staging block; the stateless call stages them from the host.
 #include "common.h"
 #include "fast_view.h"
 #include "gate.h"
 #include "pose.h"
+#include "reg_map.h"
 #include <string.h>
 #include <algorithm>
 
@@ -26,14 +29,7 @@ constexpr int RC_THREADS = 512;
 constexpr int RG_THREADS = 256;
 constexpr int REG_MAX_KF = 1024;
 
-// one request as the kernels read it
-struct reg_hdr {
-  int32_t mode, n_kf, n_src, root_kf;
-  const float *disp; int32_t disp_stride, pad_;
-  double T_root[12];
-  int32_t thr[SVS_NUM_PYR_LEVELS][SVS_MAX_CELLS];
-};
-
+// (one request as the kernels read it: reg_hdr of reg_map.h)
 struct RegK {
   // the staged requests: table r at + r * (its stride) elements
   const reg_hdr *hdr;
@@ -291,11 +287,13 @@ size_t reg_align(size_t v) { return (v + 255) & ~(size_t)255; }
     }                                                                                                     \
   } while (0)
 
-// where the tables of a call lie in the staging block / the output block, for the call's longest keyframe table (KB), source list (SB) and observer table (OB)
+// where the tables of a call lie in the staging block / the output block, for the call's longest keyframe table (KB), source list (SB) and observer table (OB).
+// by_map: a call by ids (svs_reg_register_map_batch) -- the tables are built on the device, the staged bytes are the id requests behind them, and the output
+// block also carries the built lists
 struct RegLayout {
-  size_t hdr, kfs, flags, src, ob, ok, in_bytes;
-  size_t res, m2, st1, acc, csrc, kfst, m1, out_bytes, out_bytes_m1;
-  void set(size_t R, size_t KB, size_t SB, size_t OB, size_t NP) {
+  size_t hdr, kfs, flags, src, ob, ok, in_bytes, mreq, mids;
+  size_t res, m2, st1, acc, csrc, kfst, pid, kfid, meta, m1, out_bytes, out_bytes_m1;
+  void set(size_t R, size_t KB, size_t SB, size_t OB, size_t NP, bool by_map = false) {
     size_t o = 0;
     hdr = o; o = reg_align(o + R * sizeof(reg_hdr));
     kfs = o; o = reg_align(o + R * KB * sizeof(svs_keyframe));
@@ -303,6 +301,11 @@ struct RegLayout {
     src = o; o = reg_align(o + R * SB * sizeof(svs_candidate_point));
     ob = o; o = reg_align(o + R * (SB + 1) * sizeof(int32_t));
     ok = o; o = reg_align(o + R * OB * sizeof(int32_t));
+    mreq = mids = o;
+    if (by_map) {
+      mreq = o; o = reg_align(o + R * sizeof(map_req));
+      mids = o; o = reg_align(o + R * 2 * KB * sizeof(int32_t));
+    }
     in_bytes = o;
     o = 0;
     res = o; o = reg_align(o + R * sizeof(svs_reg_result));
@@ -311,6 +314,12 @@ struct RegLayout {
     acc = o; o = reg_align(o + R * NP * sizeof(int32_t));
     csrc = o; o = reg_align(o + R * NP * sizeof(int32_t));
     kfst = o; o = reg_align(o + R * KB * sizeof(svs_reg_kf_stats));
+    pid = kfid = meta = o;
+    if (by_map) {
+      pid = o; o = reg_align(o + R * NP * sizeof(int32_t));
+      kfid = o; o = reg_align(o + R * KB * sizeof(int32_t));
+      meta = o; o = reg_align(o + R * sizeof(int4));
+    }
     out_bytes = o;
     m1 = o; o = reg_align(o + R * NP * sizeof(svs_match_result));
     out_bytes_m1 = o;
@@ -368,7 +377,7 @@ static int reg_alloc(svs_reg *g) {
   svs_ctx *ctx = g->ctx;
   const size_t R = (size_t)g->max_req;
   RegLayout L;
-  L.set(R, (size_t)g->max_kf, (size_t)g->max_pts, (size_t)g->max_obs, (size_t)std::max(g->max_pts, 1));
+  L.set(R, (size_t)g->max_kf, (size_t)g->max_pts, (size_t)g->max_obs, (size_t)std::max(g->max_pts, 1), true);
   SVS_HIP(ctx, g->h_in.alloc(L.in_bytes));
   SVS_HIP(ctx, g->d_in.alloc(L.in_bytes));
   SVS_HIP(ctx, g->h_out.alloc(L.out_bytes_m1));
@@ -420,6 +429,98 @@ extern "C" int svs_reg_set_timing(svs_reg *reg, int on) {
 extern "C" int svs_reg_stage_times(svs_reg *reg, float *ms) {
   if (!reg || !ms) return SVS_ERR_INVALID;
   for (int i = 0; i < SVS_REG_STAGES; ++i) ms[i] = reg->stage_ms[i];
+  return SVS_OK;
+}
+
+// the chain of launches behind the staged (or device-built) requests, the download and the wait.  r0 / r1: the root frames of requests 0 and 1 (direct: all
+// roots lie at the stride between them and are read in place)
+static int reg_chain(svs_reg *g, const svs_reg_params &P, int R, int KB, int SB, int OB, int NP, const RegLayout &L, bool direct, const MapRootView &r0,
+                     const MapRootView &r1, bool want_m1) {
+  svs_ctx *ctx = g->ctx;
+  // ---- the chain
+  const size_t MR = (size_t)g->max_req;
+  RegK K{};
+  uint8_t *di = g->d_in, *dout = g->d_out;
+  K.hdr = reinterpret_cast<const reg_hdr *>(di + L.hdr);
+  K.kfs = reinterpret_cast<const svs_keyframe *>(di + L.kfs); K.kf_b = (size_t)KB;
+  K.flags = di + L.flags;
+  K.src = reinterpret_cast<const svs_candidate_point *>(di + L.src); K.src_b = (size_t)SB;
+  K.obs_begin = reinterpret_cast<const int32_t *>(di + L.ob); K.ob_b = (size_t)SB + 1;
+  K.obs_kf = reinterpret_cast<const int32_t *>(di + L.ok); K.ok_b = (size_t)OB;
+  K.cand = g->d_cand; K.cand_b = (size_t)std::max(g->max_pts, 1); K.n_pad = NP;
+  K.in_vt = g->d_in_vt; K.Trel = g->d_Trel;
+  K.T = g->d_T; K.Tcw = g->d_T + MR * 12; K.Twa = g->d_T + 2 * MR * 12; K.T1 = g->d_T + 3 * MR * 12;
+  K.n_cand = g->d_cnt; K.dead = g->d_cnt + MR;
+  K.st1 = g->d_st; K.st2 = g->d_st + MR;
+  K.fv = svs_fast_thr_view_internal(g->fast);
+  for (int l = 0; l < SVS_NUM_PYR_LEVELS; ++l) K.cams[l] = g->cams[l];
+  K.covis = P.covis_thr; K.reproj = (float)P.reproj_thr;
+  K.res = reinterpret_cast<svs_reg_result *>(dout + L.res);
+  svs_match_result *d_m1 = reinterpret_cast<svs_match_result *>(dout + L.m1), *d_m2 = reinterpret_cast<svs_match_result *>(dout + L.m2);
+  K.m1 = d_m1; K.m2 = d_m2;
+  K.status1 = reinterpret_cast<int32_t *>(dout + L.st1); K.accepted = reinterpret_cast<int32_t *>(dout + L.acc); K.cand_src = reinterpret_cast<int32_t *>(dout + L.csrc);
+  K.kfst = reinterpret_cast<svs_reg_kf_stats *>(dout + L.kfst);
+  int ev = 0;
+  if (g->timing) SVS_HIP(ctx, hipEventRecord(g->ev[ev++], ctx->stream));
+  hipLaunchKernelGGL(reg_cull_kernel, dim3(R), dim3(RC_THREADS), 0, ctx->stream, K);
+  SVS_LAUNCH_CHECK(ctx);
+  svs_match_args A;
+  memset(&A, 0, sizeof A);
+  const uint8_t *img[SVS_NUM_PYR_LEVELS]; int32_t istride[SVS_NUM_PYR_LEVELS]; size_t ibstride[SVS_NUM_PYR_LEVELS];
+  if (direct) {
+    for (int l = 0; l < SVS_NUM_PYR_LEVELS; ++l) {
+      img[l] = r0.pyr[l]; istride[l] = r0.stride[l];
+      ibstride[l] = R > 1 ? (size_t)(r1.pyr[l] - r0.pyr[l]) : 0;
+    }
+    A.d_disp = r0.disp; A.disp_stride = r0.disp_stride; A.disp_bstride = R > 1 ? (size_t)(r1.disp - r0.disp) : 0;
+  } else {
+    RegGather G{};
+    for (int l = 0; l < SVS_NUM_PYR_LEVELS; ++l) {
+      G.pyr[l] = g->d_pyr[l]; G.stride[l] = g->stride[l]; G.bstride[l] = (size_t)g->stride[l] * g->cams[l].h;
+      img[l] = G.pyr[l]; istride[l] = G.stride[l]; ibstride[l] = G.bstride[l];
+    }
+    G.disp = g->d_disp; G.dstride = g->stride[0]; G.d_bstride = (size_t)g->stride[0] * g->cams[0].h;
+    A.d_disp = G.disp; A.disp_stride = G.dstride; A.disp_bstride = G.d_bstride;
+    hipLaunchKernelGGL(reg_gather_kernel, dim3(std::min(g->cams[0].h, 120), SVS_NUM_PYR_LEVELS + 1, R), dim3(256), 0, ctx->stream, K, G);
+    SVS_LAUNCH_CHECK(ctx);
+  }
+  if (g->timing) SVS_HIP(ctx, hipEventRecord(g->ev[ev++], ctx->stream));
+  if (int rc = svs_fast_detect(g->fast, img, istride, ibstride, R, 0)) return rc;
+  if (g->timing) SVS_HIP(ctx, hipEventRecord(g->ev[ev++], ctx->stream));
+  A.d_kfs = K.kfs; A.n_kf = KB; A.kf_bstride = (size_t)KB;
+  A.d_pts = K.cand; A.n_pts = NP; A.pts_bstride = K.cand_b; A.out_bstride = (size_t)NP;
+  A.d_T_cur_from_w = K.Tcw; A.d_T_w_from_actkey = K.Twa;
+  for (int l = 0; l < SVS_NUM_PYR_LEVELS; ++l) { A.d_cur_pyr[l] = img[l]; A.cur_stride[l] = istride[l]; A.cur_bstride[l] = ibstride[l]; A.cam_vec[l] = g->cams[l]; }
+  A.thr_mean = P.thr_mean; A.thr_std = P.thr_std; A.n_batch = R;
+  svs_pose_opt_params po;
+  svs_pose_opt_params_default(&po);
+  po.robust_kernel = 1; po.kernel_param = P.kernel_param; po.min_obs = P.covis_thr;
+  // the front end's fused prediction reads its poses from the context: not here
+  const double *keep_T = ctx->match_src_T, *keep_Ta = ctx->match_src_Ta;
+  ctx->match_src_T = ctx->match_src_Ta = nullptr;
+  int rc = SVS_OK;
+  for (int pass = 0; pass < 2 && rc == SVS_OK; ++pass) {
+    A.search_radius = P.search_radius[pass];
+    rc = svs_match(ctx, &A, g->fast, pass == 0 ? d_m1 : d_m2);
+    if (rc == SVS_OK && g->timing && hipEventRecord(g->ev[ev++], ctx->stream) != hipSuccess) rc = SVS_ERR_HIP;
+    po.num_iter = P.num_iter[pass];
+    if (rc == SVS_OK) rc = svs_motion_only(ctx, pass == 0 ? d_m1 : d_m2, NP, (size_t)NP, &g->cams[0], &po, K.T, pass == 0 ? K.st1 : K.st2, R);
+    if (rc == SVS_OK && pass == 0) {
+      hipLaunchKernelGGL(reg_pose_kernel, dim3(R), dim3(64), 0, ctx->stream, K);
+      if (hipGetLastError() != hipSuccess) rc = SVS_ERR_HIP;
+    }
+    if (rc == SVS_OK && g->timing && hipEventRecord(g->ev[ev++], ctx->stream) != hipSuccess) rc = SVS_ERR_HIP;
+  }
+  ctx->match_src_T = keep_T; ctx->match_src_Ta = keep_Ta;
+  if (rc) { if (rc == SVS_ERR_HIP && ctx->err.empty()) ctx->err = "svs_reg_register_batch: a launch of the chain failed"; return rc; }
+  hipLaunchKernelGGL(reg_gate_kernel, dim3(R), dim3(RG_THREADS), (size_t)5 * KB * sizeof(int), ctx->stream, K);
+  SVS_LAUNCH_CHECK(ctx);
+  if (g->timing) SVS_HIP(ctx, hipEventRecord(g->ev[ev++], ctx->stream));
+  const size_t down = want_m1 ? L.out_bytes_m1 : L.out_bytes;
+  SVS_HIP(ctx, hipMemcpyAsync(g->h_out, g->d_out, down, hipMemcpyDeviceToHost, ctx->stream));
+  SVS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  if (g->timing)
+    for (int i = 0; i < SVS_REG_STAGES; ++i) SVS_HIP(ctx, hipEventElapsedTime(&g->stage_ms[i], g->ev[i], g->ev[i + 1]));
   return SVS_OK;
 }
 
@@ -489,90 +590,13 @@ extern "C" int svs_reg_register_batch(svs_reg *g, int n_requests, const svs_reg_
     }
   }
   SVS_HIP(ctx, hipMemcpyAsync(g->d_in, g->h_in, L.in_bytes, hipMemcpyHostToDevice, ctx->stream));
-  // ---- the chain
-  const size_t MR = (size_t)g->max_req;
-  RegK K{};
-  uint8_t *di = g->d_in, *dout = g->d_out;
-  K.hdr = reinterpret_cast<const reg_hdr *>(di + L.hdr);
-  K.kfs = reinterpret_cast<const svs_keyframe *>(di + L.kfs); K.kf_b = (size_t)KB;
-  K.flags = di + L.flags;
-  K.src = reinterpret_cast<const svs_candidate_point *>(di + L.src); K.src_b = (size_t)SB;
-  K.obs_begin = reinterpret_cast<const int32_t *>(di + L.ob); K.ob_b = (size_t)SB + 1;
-  K.obs_kf = reinterpret_cast<const int32_t *>(di + L.ok); K.ok_b = (size_t)OB;
-  K.cand = g->d_cand; K.cand_b = (size_t)std::max(g->max_pts, 1); K.n_pad = NP;
-  K.in_vt = g->d_in_vt; K.Trel = g->d_Trel;
-  K.T = g->d_T; K.Tcw = g->d_T + MR * 12; K.Twa = g->d_T + 2 * MR * 12; K.T1 = g->d_T + 3 * MR * 12;
-  K.n_cand = g->d_cnt; K.dead = g->d_cnt + MR;
-  K.st1 = g->d_st; K.st2 = g->d_st + MR;
-  K.fv = svs_fast_thr_view_internal(g->fast);
-  for (int l = 0; l < SVS_NUM_PYR_LEVELS; ++l) K.cams[l] = g->cams[l];
-  K.covis = P.covis_thr; K.reproj = (float)P.reproj_thr;
-  K.res = reinterpret_cast<svs_reg_result *>(dout + L.res);
-  svs_match_result *d_m1 = reinterpret_cast<svs_match_result *>(dout + L.m1), *d_m2 = reinterpret_cast<svs_match_result *>(dout + L.m2);
-  K.m1 = d_m1; K.m2 = d_m2;
-  K.status1 = reinterpret_cast<int32_t *>(dout + L.st1); K.accepted = reinterpret_cast<int32_t *>(dout + L.acc); K.cand_src = reinterpret_cast<int32_t *>(dout + L.csrc);
-  K.kfst = reinterpret_cast<svs_reg_kf_stats *>(dout + L.kfst);
-  int ev = 0;
-  if (g->timing) SVS_HIP(ctx, hipEventRecord(g->ev[ev++], ctx->stream));
-  hipLaunchKernelGGL(reg_cull_kernel, dim3(R), dim3(RC_THREADS), 0, ctx->stream, K);
-  SVS_LAUNCH_CHECK(ctx);
-  svs_match_args A;
-  memset(&A, 0, sizeof A);
-  const uint8_t *img[SVS_NUM_PYR_LEVELS]; int32_t istride[SVS_NUM_PYR_LEVELS]; size_t ibstride[SVS_NUM_PYR_LEVELS];
-  if (direct) {
-    for (int l = 0; l < SVS_NUM_PYR_LEVELS; ++l) {
-      img[l] = root0.pyr[l]; istride[l] = root0.stride[l];
-      ibstride[l] = R > 1 ? (size_t)(req[1].h_kfs[req[1].root_kf].pyr[l] - root0.pyr[l]) : 0;
-    }
-    A.d_disp = req[0].d_root_disp; A.disp_stride = req[0].root_disp_stride; A.disp_bstride = R > 1 ? (size_t)(req[1].d_root_disp - req[0].d_root_disp) : 0;
-  } else {
-    RegGather G{};
-    for (int l = 0; l < SVS_NUM_PYR_LEVELS; ++l) {
-      G.pyr[l] = g->d_pyr[l]; G.stride[l] = g->stride[l]; G.bstride[l] = (size_t)g->stride[l] * g->cams[l].h;
-      img[l] = G.pyr[l]; istride[l] = G.stride[l]; ibstride[l] = G.bstride[l];
-    }
-    G.disp = g->d_disp; G.dstride = g->stride[0]; G.d_bstride = (size_t)g->stride[0] * g->cams[0].h;
-    A.d_disp = G.disp; A.disp_stride = G.dstride; A.disp_bstride = G.d_bstride;
-    hipLaunchKernelGGL(reg_gather_kernel, dim3(std::min(g->cams[0].h, 120), SVS_NUM_PYR_LEVELS + 1, R), dim3(256), 0, ctx->stream, K, G);
-    SVS_LAUNCH_CHECK(ctx);
+  MapRootView rv[2];
+  for (int k = 0; k < 2; ++k) {
+    const svs_reg_request &q = req[std::min(k, R - 1)];
+    for (int l = 0; l < SVS_NUM_PYR_LEVELS; ++l) { rv[k].pyr[l] = q.h_kfs[q.root_kf].pyr[l]; rv[k].stride[l] = q.h_kfs[q.root_kf].stride[l]; }
+    rv[k].disp = q.d_root_disp; rv[k].disp_stride = q.root_disp_stride;
   }
-  if (g->timing) SVS_HIP(ctx, hipEventRecord(g->ev[ev++], ctx->stream));
-  if (int rc = svs_fast_detect(g->fast, img, istride, ibstride, R, 0)) return rc;
-  if (g->timing) SVS_HIP(ctx, hipEventRecord(g->ev[ev++], ctx->stream));
-  A.d_kfs = K.kfs; A.n_kf = KB; A.kf_bstride = (size_t)KB;
-  A.d_pts = K.cand; A.n_pts = NP; A.pts_bstride = K.cand_b; A.out_bstride = (size_t)NP;
-  A.d_T_cur_from_w = K.Tcw; A.d_T_w_from_actkey = K.Twa;
-  for (int l = 0; l < SVS_NUM_PYR_LEVELS; ++l) { A.d_cur_pyr[l] = img[l]; A.cur_stride[l] = istride[l]; A.cur_bstride[l] = ibstride[l]; A.cam_vec[l] = g->cams[l]; }
-  A.thr_mean = P.thr_mean; A.thr_std = P.thr_std; A.n_batch = R;
-  svs_pose_opt_params po;
-  svs_pose_opt_params_default(&po);
-  po.robust_kernel = 1; po.kernel_param = P.kernel_param; po.min_obs = P.covis_thr;
-  // the front end's fused prediction reads its poses from the context: not here
-  const double *keep_T = ctx->match_src_T, *keep_Ta = ctx->match_src_Ta;
-  ctx->match_src_T = ctx->match_src_Ta = nullptr;
-  int rc = SVS_OK;
-  for (int pass = 0; pass < 2 && rc == SVS_OK; ++pass) {
-    A.search_radius = P.search_radius[pass];
-    rc = svs_match(ctx, &A, g->fast, pass == 0 ? d_m1 : d_m2);
-    if (rc == SVS_OK && g->timing && hipEventRecord(g->ev[ev++], ctx->stream) != hipSuccess) rc = SVS_ERR_HIP;
-    po.num_iter = P.num_iter[pass];
-    if (rc == SVS_OK) rc = svs_motion_only(ctx, pass == 0 ? d_m1 : d_m2, NP, (size_t)NP, &g->cams[0], &po, K.T, pass == 0 ? K.st1 : K.st2, R);
-    if (rc == SVS_OK && pass == 0) {
-      hipLaunchKernelGGL(reg_pose_kernel, dim3(R), dim3(64), 0, ctx->stream, K);
-      if (hipGetLastError() != hipSuccess) rc = SVS_ERR_HIP;
-    }
-    if (rc == SVS_OK && g->timing && hipEventRecord(g->ev[ev++], ctx->stream) != hipSuccess) rc = SVS_ERR_HIP;
-  }
-  ctx->match_src_T = keep_T; ctx->match_src_Ta = keep_Ta;
-  if (rc) { if (rc == SVS_ERR_HIP && ctx->err.empty()) ctx->err = "svs_reg_register_batch: a launch of the chain failed"; return rc; }
-  hipLaunchKernelGGL(reg_gate_kernel, dim3(R), dim3(RG_THREADS), (size_t)5 * KB * sizeof(int), ctx->stream, K);
-  SVS_LAUNCH_CHECK(ctx);
-  if (g->timing) SVS_HIP(ctx, hipEventRecord(g->ev[ev++], ctx->stream));
-  const size_t down = h_matches_pass1 ? L.out_bytes_m1 : L.out_bytes;
-  SVS_HIP(ctx, hipMemcpyAsync(g->h_out, g->d_out, down, hipMemcpyDeviceToHost, ctx->stream));
-  SVS_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  if (g->timing)
-    for (int i = 0; i < SVS_REG_STAGES; ++i) SVS_HIP(ctx, hipEventElapsedTime(&g->stage_ms[i], g->ev[i], g->ev[i + 1]));
+  if (int rc = reg_chain(g, P, R, KB, SB, OB, NP, L, direct, rv[0], rv[1], h_matches_pass1 != nullptr)) return rc;
   // ---- hand the rows out: max_points / max_keyframes long, defaults behind a request's own entries
   const uint8_t *ho = g->h_out;
   const size_t MP = (size_t)g->max_pts, MK = (size_t)g->max_kf;
@@ -593,6 +617,119 @@ extern "C" int svs_reg_register_batch(svs_reg *g, int n_requests, const svs_reg_
       memcpy(h_kf_stats + r * MK, ho + L.kfst + (size_t)r * KB * sizeof(svs_reg_kf_stats), nk * sizeof(svs_reg_kf_stats));
       memset(h_kf_stats + r * MK + nk, 0, (MK - nk) * sizeof(svs_reg_kf_stats));
     }
+  }
+  return SVS_OK;
+}
+
+// ---- requests by ids against a device-resident map (map.hip): the staged bytes are the id lists, the map's walk builds the tables where the stateless call stages
+// them -- at the handle's capacities, since the sizes are only known on the device; a request's outputs do not depend on the padding -- and the chain above runs
+extern "C" int svs_reg_register_map_batch(svs_reg *g, svs_map *map, int n_requests, const svs_reg_map_request *req, const svs_reg_params *prm, svs_reg_result *h_res,
+                                          int32_t *h_cand_src, svs_match_result *h_matches, int32_t *h_status_pass1, int32_t *h_accepted,
+                                          svs_reg_kf_stats *h_kf_stats, svs_match_result *h_matches_pass1, int32_t *h_cand_point_id, int32_t *h_kf_ids,
+                                          int32_t *h_n_kf) {
+  svs_ctx *ctx = g ? g->ctx : nullptr;
+  SVS_REQUIRE(ctx, g && map && svs_map_ctx(map) == ctx && n_requests >= 0 && (n_requests == 0 || req));
+  svs_reg_params P;
+  if (prm) P = *prm; else svs_reg_params_default(&P);
+  SVS_REQUIRE(ctx, P.covis_thr >= 0 && P.search_radius[0] >= 0 && P.search_radius[0] <= 31 && P.search_radius[1] >= 0 && P.search_radius[1] <= 31 && P.num_iter[0] >= 0 &&
+                       P.num_iter[1] >= 0 && P.reproj_thr >= 0.0);
+  REG_CAPACITY(ctx, n_requests <= g->max_req);
+  const int R = n_requests, KB = g->max_kf, SB = g->max_pts, OB = g->max_obs, NP = std::max(SB, 1);
+  MapRootView rv[2], v;
+  bool direct = true;
+  for (int r = 0; r < R; ++r) {
+    const svs_reg_map_request &q = req[r];
+    SVS_REQUIRE(ctx, (q.mode == SVS_REG_LOCAL || q.mode == SVS_REG_LOOP) && q.n_walk >= (q.mode == SVS_REG_LOOP ? 1 : 0) && q.n_direct >= 0 &&
+                         (q.n_walk == 0 || q.h_walk_kf) && (q.n_direct == 0 || q.h_direct_kf));
+    REG_CAPACITY(ctx, q.n_walk <= KB);
+    REG_CAPACITY(ctx, q.n_direct <= KB);
+    SVS_REQUIRE(ctx, svs_map_has_keyframe(map, q.root_kf));
+    for (int i = 0; i < q.n_walk; ++i) SVS_REQUIRE(ctx, svs_map_has_keyframe(map, q.h_walk_kf[i]));
+    for (int i = 0; i < q.n_direct; ++i) SVS_REQUIRE(ctx, svs_map_has_keyframe(map, q.h_direct_kf[i]));
+    svs_map_root_view(map, q.root_kf, &v);
+    SVS_REQUIRE(ctx, v.disp_stride >= g->cams[0].w);
+    for (int l = 0; l < SVS_NUM_PYR_LEVELS; ++l) SVS_REQUIRE(ctx, v.stride[l] >= g->cams[l].w);
+    if (r < 2) rv[r] = v;
+    if (r == 0) rv[1] = v;
+    if (r > 0) {      // the roots lie at one stride from the first: FAST and the matcher read them in place
+      for (int l = 0; l < SVS_NUM_PYR_LEVELS; ++l)
+        direct = direct && v.stride[l] == rv[0].stride[l] && rv[1].pyr[l] >= rv[0].pyr[l] && v.pyr[l] == rv[0].pyr[l] + (size_t)r * (size_t)(rv[1].pyr[l] - rv[0].pyr[l]);
+      direct = direct && v.disp_stride == rv[0].disp_stride && rv[1].disp >= rv[0].disp && v.disp == rv[0].disp + (size_t)r * (size_t)(rv[1].disp - rv[0].disp);
+    }
+  }
+  if (R == 0) return SVS_OK;
+  SVS_DEVICE(ctx);
+  RegLayout L;
+  L.set((size_t)R, (size_t)KB, (size_t)SB, (size_t)OB, (size_t)NP, true);
+  // ---- stage the ids
+  uint8_t *hi = g->h_in;
+  map_req *mq = reinterpret_cast<map_req *>(hi + L.mreq);
+  int32_t *ids = reinterpret_cast<int32_t *>(hi + L.mids);
+  int n_ids = 0;
+  for (int r = 0; r < R; ++r) {
+    const svs_reg_map_request &q = req[r];
+    memset(&mq[r], 0, sizeof mq[r]);
+    mq[r].mode = q.mode; mq[r].root = q.root_kf; mq[r].n_walk = q.n_walk; mq[r].n_direct = q.n_direct;
+    mq[r].walk_off = n_ids;
+    if (q.n_walk) memcpy(ids + n_ids, q.h_walk_kf, (size_t)q.n_walk * sizeof(int32_t));
+    n_ids += q.n_walk;
+    mq[r].direct_off = n_ids;
+    if (q.n_direct) memcpy(ids + n_ids, q.h_direct_kf, (size_t)q.n_direct * sizeof(int32_t));
+    n_ids += q.n_direct;
+    memcpy(mq[r].T_root, q.T_root_from_world, sizeof mq[r].T_root);
+  }
+  const size_t up_bytes = L.mids + (size_t)n_ids * sizeof(int32_t) - L.mreq;
+  uint8_t *di = g->d_in, *dout = g->d_out;
+  SVS_HIP(ctx, hipMemcpyAsync(di + L.mreq, hi + L.mreq, up_bytes, hipMemcpyHostToDevice, ctx->stream));
+  // ---- the walk builds the requests
+  MapBuildDst D{};
+  D.req = reinterpret_cast<const map_req *>(di + L.mreq); D.ids = reinterpret_cast<const int32_t *>(di + L.mids);
+  D.hdr = reinterpret_cast<reg_hdr *>(di + L.hdr); D.kfs = reinterpret_cast<svs_keyframe *>(di + L.kfs); D.flags = di + L.flags;
+  D.src = reinterpret_cast<svs_candidate_point *>(di + L.src); D.obs_begin = reinterpret_cast<int32_t *>(di + L.ob); D.obs_kf = reinterpret_cast<int32_t *>(di + L.ok);
+  D.KB = KB; D.SB = SB; D.OB = OB; D.NP = NP;
+  D.point_id = reinterpret_cast<int32_t *>(dout + L.pid); D.kf_id = reinterpret_cast<int32_t *>(dout + L.kfid); D.meta = reinterpret_cast<int4 *>(dout + L.meta);
+  if (int rc = svs_map_build_requests(map, R, D)) return rc;
+  if (int rc = reg_chain(g, P, R, KB, SB, OB, NP, L, direct, rv[0], rv[1], h_matches_pass1 != nullptr)) return rc;
+  // ---- hand the rows out
+  const uint8_t *ho = g->h_out;
+  const size_t MP = (size_t)g->max_pts, MK = (size_t)g->max_kf;
+  svs_match_result none;
+  memset(&none, 0, sizeof none);
+  none.status = SVS_MATCH_NO_ANCHOR;
+  for (int r = 0; r < R; ++r) {
+    const svs_reg_result *rs = reinterpret_cast<const svs_reg_result *>(ho + L.res) + r;
+    const int4 meta = reinterpret_cast<const int4 *>(ho + L.meta)[r];
+    if (meta.w) {      // over capacity: the status and zeros
+      if (h_res) { memset(&h_res[r], 0, sizeof h_res[r]); h_res[r].status = SVS_REG_OVER_CAPACITY; }
+      if (h_matches) memset(h_matches + r * MP, 0, MP * sizeof(svs_match_result));
+      if (h_matches_pass1) memset(h_matches_pass1 + r * MP, 0, MP * sizeof(svs_match_result));
+      if (h_status_pass1) memset(h_status_pass1 + r * MP, 0, MP * 4);
+      if (h_accepted) memset(h_accepted + r * MP, 0, MP * 4);
+      if (h_cand_src) memset(h_cand_src + r * MP, 0, MP * 4);
+      if (h_cand_point_id) memset(h_cand_point_id + r * MP, 0, MP * 4);
+      if (h_kf_stats) memset(h_kf_stats + r * MK, 0, MK * sizeof(svs_reg_kf_stats));
+      if (h_kf_ids) memset(h_kf_ids + r * MK, 0, MK * 4);
+      if (h_n_kf) h_n_kf[r] = 0;
+      continue;
+    }
+    const size_t n = (size_t)std::min(std::max(rs->n_candidates, 0), SB), nk = (size_t)std::min(std::max(meta.x, 1), KB);
+    if (h_res) h_res[r] = *rs;
+    if (h_matches) { memcpy(h_matches + r * MP, ho + L.m2 + (size_t)r * NP * sizeof(svs_match_result), n * sizeof(svs_match_result)); std::fill(h_matches + r * MP + n, h_matches + (r + 1) * MP, none); }
+    if (h_matches_pass1) { memcpy(h_matches_pass1 + r * MP, ho + L.m1 + (size_t)r * NP * sizeof(svs_match_result), n * sizeof(svs_match_result)); std::fill(h_matches_pass1 + r * MP + n, h_matches_pass1 + (r + 1) * MP, none); }
+    if (h_status_pass1) { memcpy(h_status_pass1 + r * MP, ho + L.st1 + (size_t)r * NP * 4, n * 4); std::fill(h_status_pass1 + r * MP + n, h_status_pass1 + (r + 1) * MP, (int32_t)SVS_MATCH_NO_ANCHOR); }
+    if (h_accepted) { memcpy(h_accepted + r * MP, ho + L.acc + (size_t)r * NP * 4, n * 4); std::fill(h_accepted + r * MP + n, h_accepted + (r + 1) * MP, 0); }
+    if (h_cand_src) { memcpy(h_cand_src + r * MP, ho + L.csrc + (size_t)r * NP * 4, n * 4); std::fill(h_cand_src + r * MP + n, h_cand_src + (r + 1) * MP, -1); }
+    if (h_cand_point_id) {      // the candidates' ids: the built list read through the cull's indices
+      const int32_t *csrc = reinterpret_cast<const int32_t *>(ho + L.csrc) + (size_t)r * NP, *pid = reinterpret_cast<const int32_t *>(ho + L.pid) + (size_t)r * NP;
+      for (size_t i = 0; i < n; ++i) h_cand_point_id[r * MP + i] = (unsigned)csrc[i] < (unsigned)SB ? pid[csrc[i]] : -1;
+      std::fill(h_cand_point_id + r * MP + n, h_cand_point_id + (r + 1) * MP, -1);
+    }
+    if (h_kf_stats) {
+      memcpy(h_kf_stats + r * MK, ho + L.kfst + (size_t)r * KB * sizeof(svs_reg_kf_stats), nk * sizeof(svs_reg_kf_stats));
+      memset(h_kf_stats + r * MK + nk, 0, (MK - nk) * sizeof(svs_reg_kf_stats));
+    }
+    if (h_kf_ids) { memcpy(h_kf_ids + r * MK, ho + L.kfid + (size_t)r * KB * 4, nk * 4); std::fill(h_kf_ids + r * MK + nk, h_kf_ids + (r + 1) * MK, -1); }
+    if (h_n_kf) h_n_kf[r] = (int32_t)nk;
   }
   return SVS_OK;
 }

@@ -242,3 +242,14 @@ class RegResult(C.Structure):
 REG_KF_STATS_DTYPE = np.dtype([("strength", "<i4"), ("n_u_hi", "<i4"), ("n_u_lo", "<i4"), ("n_v_hi", "<i4"), ("n_v_lo", "<i4"), ("qualifies", "<i4"),
                                ("in_vertex_table", "<i4"), ("pad_", "<i4")])
 assert REG_KF_STATS_DTYPE.itemsize == 32
+
+
+# ---- back end: the device-resident map and requests by ids (svs_map_*, svs_reg_register_map_batch)
+REG_OVER_CAPACITY = 5
+MAP_MAX_KEYFRAMES = 16384
+
+
+class RegMapRequest(C.Structure):
+    """svs_reg_map_request: a root keyframe by id, with the ids of framesInNeighborhood(root) and directNeighborsOf(root)"""
+    _fields_ = [("mode", C.c_int32), ("root_kf", C.c_int32), ("n_walk", C.c_int32), ("n_direct", C.c_int32), ("T_root_from_world", C.c_double * 12),
+                ("h_walk_kf", C.c_void_p), ("h_direct_kf", C.c_void_p)]

@@ -7,13 +7,16 @@
 A request is one root keyframe with the candidate map points the caller's graph walk found (framesInNeighborhood, the hash-set deduplication, registerKeyframes /
 addLoopClosure stay with the caller).  A batch of requests is ONE library call: one staged upload, one chain of launches, one download.  There is no CPU path:
 every call goes to svs_reg_* of the HIP library.
+
+  ResidentMap                                  the map on the device (svs_map_*): keyframes, points and feature_table pairs under the graph's ids, updated incrementally
+  KeyframeRegistrar.register_map_batch(map, requests)   the same registration with a request named by ids: the point walk of pointsVisibleInRoot runs on the device
 """
 import ctypes as C
 
 import numpy as np
 
-from .ctypes_types import (CANDIDATE_DTYPE, KEYFRAME_DTYPE, MATCH_RESULT_DTYPE, REG_KF_STATS_DTYPE, REG_LOCAL, REG_LOOP, REG_OK, REG_STAGES, SVS_MAX_CELLS, Cam,
-                           RegParams, RegRequest, RegResult)
+from .ctypes_types import (CANDIDATE_DTYPE, KEYFRAME_DTYPE, MATCH_RESULT_DTYPE, REG_KF_STATS_DTYPE, REG_LOCAL, REG_LOOP, REG_OK, REG_OVER_CAPACITY, REG_STAGES,
+                           SVS_MAX_CELLS, Cam, RegMapRequest, RegParams, RegRequest, RegResult)
 
 
 def keyframe_table(entries):
@@ -121,6 +124,48 @@ class KeyframeRegistrar:
             out.append(RegistrationOutput(res[i], csrc[i, :k], m2[i, :k], st1[i, :k], acc[i, :k], kfst[i, :nk], m1[i, :k] if want_pass1 else None))
         return out
 
+    def register_map_batch(self, resident_map, requests, params=None, want_pass1=False):
+        """requests: dicts with mode, root_kf (id), T_root_from_world, walk_kf (ids: framesInNeighborhood(root) / [the query keyframe]) and direct_kf (ids:
+        directNeighborsOf(root)).  The outputs are those of register_batch on the request the map's walk builds; each carries point_ids (per candidate) and
+        kf_ids (per table entry).  A request whose built tables exceed this registrar's capacities comes back with status REG_OVER_CAPACITY and empty rows"""
+        n = len(requests)
+        keep = []
+        arr = (RegMapRequest * max(n, 1))()
+        for i, q in enumerate(requests):
+            walk = np.ascontiguousarray(q["walk_kf"], np.int32).reshape(-1)
+            direct = np.ascontiguousarray(q.get("direct_kf", ()), np.int32).reshape(-1)
+            keep += [walk, direct]
+            r = arr[i]
+            r.mode, r.root_kf, r.n_walk, r.n_direct = int(q["mode"]), int(q["root_kf"]), len(walk), len(direct)
+            T = np.asarray(q["T_root_from_world"], np.float64).reshape(12)
+            for k in range(12):
+                r.T_root_from_world[k] = float(T[k])
+            r.h_walk_kf, r.h_direct_kf = walk.ctypes.data if len(walk) else None, direct.ctypes.data if len(direct) else None
+        prm = params or self.params
+        res = (RegResult * max(n, 1))()
+        MP, MK = self.max_points, self.max_keyframes
+        csrc = np.empty((n, MP), np.int32)
+        m2 = np.empty((n, MP), MATCH_RESULT_DTYPE)
+        st1 = np.empty((n, MP), np.int32)
+        acc = np.empty((n, MP), np.int32)
+        kfst = np.empty((n, MK), REG_KF_STATS_DTYPE)
+        m1 = np.empty((n, MP), MATCH_RESULT_DTYPE) if want_pass1 else None
+        pid = np.empty((n, MP), np.int32)
+        kfid = np.empty((n, MK), np.int32)
+        nkf = np.empty(n, np.int32)
+        self.ctx.check(self.ctx.lib.svs_reg_register_map_batch(self.h, resident_map.h, n, arr, C.byref(prm), res, csrc.ctypes.data, m2.ctypes.data, st1.ctypes.data,
+                                                               acc.ctypes.data, kfst.ctypes.data, m1.ctypes.data if want_pass1 else None, pid.ctypes.data,
+                                                               kfid.ctypes.data, nkf.ctypes.data))
+        self.raw = dict(results=bytes(res)[:n * C.sizeof(RegResult)], cand_src=csrc, matches=m2, status_pass1=st1, accepted=acc, kf_stats=kfst, matches_pass1=m1,
+                        point_ids=pid, kf_ids=kfid, n_kf=nkf)
+        out = []
+        for i in range(n):
+            k, nk = res[i].n_candidates, int(nkf[i])
+            o = RegistrationOutput(res[i], csrc[i, :k], m2[i, :k], st1[i, :k], acc[i, :k], kfst[i, :nk], m1[i, :k] if want_pass1 else None)
+            o.point_ids, o.kf_ids = pid[i, :k], kfid[i, :nk]
+            out.append(o)
+        return out
+
     def local_register(self, requests, **kw):
         return self.register_batch(requests, [REG_LOCAL] * len(requests), **kw)
 
@@ -139,6 +184,88 @@ class KeyframeRegistrar:
     def close(self):
         if self.h:
             self.ctx.lib.svs_reg_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class ResidentMap:
+    """svs_map: the back end's map in device memory, under the graph's own ids (dense, below the capacities).  Every update is one staged upload, asynchronous
+    on the context's stream, and is refused as a whole (SvsError, the map unchanged) on an unknown, repeated or out-of-range id."""
+
+    def __init__(self, ctx, max_keyframes=1024, max_points=1 << 16, max_observations=1 << 19):
+        self.ctx, self.h = ctx, None
+        h = C.c_void_p()
+        ctx.call("svs_map_create", int(max_keyframes), int(max_points), int(max_observations), C.byref(h))
+        self.h = h
+        ctx.children.add(self)
+
+    def _call(self, name, *args):
+        self.ctx.check(getattr(self.ctx.lib, name)(self.h, *args))
+
+    def add_keyframes(self, ids, kfs, disp, fast_thr):
+        """kfs: KEYFRAME_DTYPE (see keyframe_table: T_me_from_world, pyramid device pointers and strides); disp: (device pointer, stride) of the level-0 f32
+        disparity per keyframe; fast_thr: per keyframe, per level, the stored thresholds (cells beyond a level's grid are filled with 25)"""
+        ids = np.ascontiguousarray(ids, np.int32).reshape(-1)
+        kfs = np.ascontiguousarray(kfs, KEYFRAME_DTYPE).reshape(-1)
+        n = len(ids)
+        if not (len(kfs) == len(disp) == len(fast_thr) == n):
+            raise ValueError("one keyframe record, disparity and threshold set per id expected")
+        ptr = np.array([int(d[0]) for d in disp], np.uint64)
+        stride = np.array([int(d[1]) for d in disp], np.int32)
+        thr = np.full((n, 3, SVS_MAX_CELLS), 25, np.int32)
+        for i, per_level in enumerate(fast_thr):
+            for l in range(3):
+                t = np.asarray(per_level[l], np.int32).reshape(-1)
+                if len(t) > SVS_MAX_CELLS:
+                    raise ValueError("at most SVS_MAX_CELLS thresholds per level")
+                thr[i, l, :len(t)] = t
+        self._call("svs_map_add_keyframes", n, ids.ctypes.data, kfs.ctypes.data, ptr.ctypes.data, stride.ctypes.data, thr.ctypes.data)
+
+    def add_points(self, ids, points):
+        """points: CANDIDATE_DTYPE with kf_index = the ID of the anchor keyframe"""
+        ids = np.ascontiguousarray(ids, np.int32).reshape(-1)
+        pts = np.ascontiguousarray(points, CANDIDATE_DTYPE).reshape(-1)
+        if len(pts) != len(ids):
+            raise ValueError("one point record per id expected")
+        self._call("svs_map_add_points", len(ids), ids.ctypes.data, pts.ctypes.data)
+
+    def add_observations(self, point_ids, kf_ids):
+        """point point_ids[i] is in the feature_table of keyframe kf_ids[i]; pairs already present are ignored"""
+        p = np.ascontiguousarray(point_ids, np.int32).reshape(-1)
+        k = np.ascontiguousarray(kf_ids, np.int32).reshape(-1)
+        if len(p) != len(k):
+            raise ValueError("pairs expected")
+        self._call("svs_map_add_observations", len(p), p.ctypes.data, k.ctypes.data)
+
+    def set_poses(self, kf_ids, poses):
+        k = np.ascontiguousarray(kf_ids, np.int32).reshape(-1)
+        T = np.ascontiguousarray(poses, np.float64).reshape(len(k), 12)
+        self._call("svs_map_set_poses", len(k), k.ctypes.data, T.ctypes.data)
+
+    def set_points(self, point_ids, xyz_anchor):
+        p = np.ascontiguousarray(point_ids, np.int32).reshape(-1)
+        x = np.ascontiguousarray(xyz_anchor, np.float64).reshape(len(p), 3)
+        self._call("svs_map_set_points", len(p), p.ctypes.data, x.ctypes.data)
+
+    def set_window(self, kf_ids):
+        """graph_.double_window(): exactly these keyframes are in the window afterwards"""
+        k = np.ascontiguousarray(kf_ids, np.int32).reshape(-1)
+        self._call("svs_map_set_window", len(k), k.ctypes.data)
+
+    def info(self):
+        """(keyframes, points, distinct observations)"""
+        a, b, c = C.c_int32(), C.c_int32(), C.c_int32()
+        self._call("svs_map_info", C.byref(a), C.byref(b), C.byref(c))
+        return a.value, b.value, c.value
+
+    def close(self):
+        if self.h:
+            self.ctx.lib.svs_map_destroy(self.h)
             self.h = None
 
     def __del__(self):
