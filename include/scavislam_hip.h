@@ -1023,6 +1023,55 @@ int svs_reg_register_map_batch(svs_reg *reg, svs_map *map, int n_requests, const
                                int32_t *h_cand_src, svs_match_result *h_matches, int32_t *h_status_pass1, int32_t *h_accepted, svs_reg_kf_stats *h_kf_stats,
                                svs_match_result *h_matches_pass1, int32_t *h_cand_point_id, int32_t *h_kf_ids, int32_t *h_n_kf);
 
+/* ---- front end: a stream's neighbourhood list built from the map.  Backend::computeNeighborhood (backend.cpp:244-386) from the vertex list onwards: the caller
+   names the keyframes addPoseToNeighborhood(root) + findNeighborsOfRoot(root, 10) chose (the ordering by strength and the double_window test stay with it, as
+   framesInNeighborhood does for registration), the device does addPointsToNeighbors (:311-345) and addAnchorPosesToNeighbors (:371-386) on the map and writes
+   neighborhood_->point_list into the stream's candidate list where svs_frontend_set_candidates_grouped would have uploaded it, behind the new-point groups
+   ("the head"), which still come from the host.  The reference's orders are those of hash containers and no function of its input; a canonical one is chosen:
+     1. points.  Every point with at least one observation in a keyframe of h_vertex_kf, each once, in ASCENDING POINT ID.  The record is the map's: xyz_anchor,
+        anchor_obs_pyr, anchor_level, point_id = its id.
+     2. vertex set.  The ids of h_vertex_kf in the given order; behind them, in ascending id, the anchors of rule 1's points that are not among them.  Each with
+        T_me_from_world AS THE MAP STORES IT: for a keyframe outside the window the reference calls computeAbsolutePose (:363) -- the caller keeps the map's pose
+        of such a keyframe current through svs_map_set_poses.
+     3. slots.  kf_index of a record of rule 1 is the slot s with h_slot_kf[s] == the anchor's id, -1 when no slot holds it (the matcher answers -1 with
+        SVS_MATCH_NO_ANCHOR, matcher.cpp:336-339).  An entry of h_slot_kf that is < 0, or an id that is no keyframe of the map, holds no anchor.
+     4. the stream's list becomes: the n_head head records in n_head_groups groups (as svs_frontend_set_candidates_grouped takes groups 0 .. G-2), then rule 1's
+        records as the last group; the group ends, the group count n_head_groups + 1 and the new-record count n_head follow, and the records between the new
+        length and the stream's previous one become "no candidate" (0xff) as the other setters leave them.
+     5. pose refresh (refresh_poses != 0).  Every slot whose h_slot_kf entry is a keyframe of the map takes the map's pose as its T_anchor_from_w; pyramid
+        pointers and strides are not touched.  (The poses of neighborhood_->vertex_map are what the matcher reads, matcher.cpp:328-347.)
+     6. all or nothing per request.  If n_head + the points of rule 1 exceed the front end's max_points, or the vertex set exceeds vertex_cap, the stream's list,
+        group ends, counts and slot poses stay exactly as they were and the result has over_capacity = 1: n_points / n_map_points are the counts the walk found;
+        n_vertex / n_no_slot are those of the points it read -- 0 when the points did not fit.  The call returns SVS_OK, the other requests are unaffected.
+     7. a request's outputs are a function of the map's content and of that request alone: not of the order or grouping of the updates that built the map, of
+        the rest of the batch, or of repetition. */
+typedef struct {
+  int32_t stream, n_vertex, n_head, n_head_groups;      /* n_vertex >= 1, n_head_groups >= 1 (an absent list is an empty group) */
+  const int32_t *h_vertex_kf;          /* HOST [n_vertex]: ids, root first */
+  const int32_t *h_slot_kf;            /* HOST [the front end's max_keyframes]: the keyframe id kept in each slot of the stream, -1 for none */
+  const int32_t *h_head_group_end;     /* HOST [n_head_groups]: one past the last record of each head group; the last = n_head */
+  const svs_candidate_point *h_head;   /* HOST [n_head]: kf_index = a kept slot, or < 0 */
+} svs_nbh_request;
+typedef struct {
+  int32_t n_points;                    /* records of the stream's list: n_head + n_map_points */
+  int32_t n_map_points;                /* rule 1 */
+  int32_t n_vertex;                    /* rule 2 */
+  int32_t n_no_slot;                   /* records of rule 1 with kf_index = -1 */
+  int32_t over_capacity;               /* rule 6 */
+  int32_t pad_[3];
+} svs_nbh_result;
+/* BLOCKING: one staged upload (ids, slot tables, head records), at most the map's CSR rebuild plus one launch (one workgroup per request), one download (the
+   results, the refreshed slot poses -- the front end's host mirror follows them -- and the rows asked for).  fe and map belong to one context.
+   Outputs, each optional, HOST: h_res [n_requests]; h_point_id [n_requests][max_points]: the point id of every record of the built list, -1 behind it;
+   h_vertex_id [n_requests][vertex_cap] (-1 behind the set) and h_vertex_T [n_requests][vertex_cap][12] (zeros behind it): rule 2; rows of a request over capacity:
+   -1 / zeros.  h_records [n_streams][max_points]: the front end's whole candidate table as it lies on the device behind the call (a second copy; for tests).
+   Refused before anything is uploaded or launched, all state unchanged -- SVS_ERR_INVALID: between svs_frontend_submit_frame and _wait_frame; fe and map on
+   different contexts; n_requests above the number of streams; a stream named twice; an id of a vertex list that is no keyframe of the map, or twice in the list;
+   a slot-table entry >= 0 for a slot that was never kept, or one id in two slots; a head svs_frontend_set_candidates_grouped would refuse (group ends, n_head above
+   max_points, kf_index of an unkept slot); SVS_ERR_CAPACITY: more than 64 groups; SVS_ERR_UNSUPPORTED: max_keyframes above 32767. */
+int svs_frontend_set_candidates_from_map(svs_frontend *fe, svs_map *map, int n_requests, const svs_nbh_request *req, int refresh_poses, int vertex_cap,
+                                         svs_nbh_result *h_res, int32_t *h_point_id, int32_t *h_vertex_id, double *h_vertex_T, svs_candidate_point *h_records);
+
 /* ---- multi-GPU: the library-owned collective of the landmark-sharded back-end.  The reference has no
    distributed code; one process per GPU each creates a context and a communicator (RCCL, bound at run time) --------------*/
 typedef struct { char bytes[128]; } svs_unique_id;      /* = ncclUniqueId */

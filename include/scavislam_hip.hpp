@@ -484,9 +484,12 @@ class DenseTrackerGpu {
 
 // StereoFrontend::processFrame(bool*) / processFirstFrame() (stereo_frontend.h:88-95): the data-parallel part of a frame in ONE blocking call with
 // host buffers in and out; the caller keeps the reference's bookkeeping (keyframe switch / drop, list building) and uses the returned records.
+class BackendMap;
+struct FrontendVertex { int frame_id; double T_me_from_w[12]; };      // an entry of neighborhood_->vertex_map: the id and the pose (the edge strengths stay with the caller)
 class StereoFrontend {
  public:
-  StereoFrontend(const Context &c, const svs_cam &cam, const svs_frontend_params &prm, int max_points, int max_keyframes) : ctx_(c), fe_(nullptr) {
+  StereoFrontend(const Context &c, const svs_cam &cam, const svs_frontend_params &prm, int max_points, int max_keyframes)
+      : ctx_(c), fe_(nullptr), max_points_(max_points), max_keyframes_(max_keyframes) {
     ok_ = c.check(svs_frontend_create(c.get(), &cam, &prm, max_points, max_keyframes, &fe_));
   }
   ~StereoFrontend() { if (fe_) svs_frontend_destroy(fe_); }
@@ -545,6 +548,14 @@ class StereoFrontend {
     return res->tracking_ok != 0;
   }
   bool recomputeDensePointCloud(const double T_cur_from_actkey[12]) { return ctx_.check(svs_frontend_recompute_cloud(fe_, T_cur_from_actkey)); }
+  // Backend::computeNeighborhood (backend.cpp:244-386) from the vertex list onwards, on the device-resident map: neighborhood_->point_list is written into the
+  // candidate list behind the new-point groups (setCandidateLists' groups 0 .. G-2: newpoints / newpoint_group_end), neighborhood_->vertex_map comes back as ids
+  // and poses, and with refresh_poses every slot of slot_keyframe_ids that names a keyframe of the map takes the map's pose.  vertex_ids: the root first, then
+  // what findNeighborsOfRoot chose; slot_keyframe_ids [max_keyframes]: the frame id kept in each slot, -1 for none; point_ids: per record of the built list.
+  // false: refused, or over capacity (res->over_capacity; the list is then the one of before).  Defined behind BackendMap
+  inline bool setCandidatesFromMap(BackendMap &map, const std::vector<int32_t> &vertex_ids, const std::vector<int32_t> &slot_keyframe_ids,
+                                   const std::vector<svs_candidate_point> &newpoints, const std::vector<int32_t> &newpoint_group_end, bool refresh_poses,
+                                   svs_nbh_result *res, std::vector<int32_t> *point_ids, std::vector<FrontendVertex> *vertex_map, int vertex_cap = 64);
   // computeFastCorners' outputs of the frame processed last (stereo_frontend.cpp:656-679): the corner list of a level in the order FastGrid inserts it into the
   // quadtree (cells row-major, corners of a cell row-major), corners per cell, and the persistent thresholds as they stand now (the CellGrid2d snapshot a Frame keeps)
   bool fastCorners(int level, std::vector<Corner> *corners, std::vector<int32_t> *cell_counts, std::vector<int32_t> *thresholds) {
@@ -597,6 +608,7 @@ class StereoFrontend {
   svs_frontend *fe_;
   bool ok_;
   int n_ = 0;
+  int max_points_, max_keyframes_;
 };
 
 // The per-pixel input conversions of FrameGrabber<StereoCamera> (frame_grabber.cpp:125-186, frame_grabber-impl.cpp:93-152) on device frames of n streams:
@@ -898,6 +910,30 @@ class BackendMap {
   std::vector<int8_t> level_;      // anchor_level by point id: MyTrackPoint carries it
   bool ok_;
 };
+inline bool StereoFrontend::setCandidatesFromMap(BackendMap &map, const std::vector<int32_t> &vertex_ids, const std::vector<int32_t> &slot_keyframe_ids,
+                                                 const std::vector<svs_candidate_point> &newpoints, const std::vector<int32_t> &newpoint_group_end, bool refresh_poses,
+                                                 svs_nbh_result *res, std::vector<int32_t> *point_ids, std::vector<FrontendVertex> *vertex_map, int vertex_cap) {
+  if (!ok_ || !map.ok() || (int)slot_keyframe_ids.size() != max_keyframes_ || vertex_cap < 1) return false;
+  const std::vector<int32_t> one_group(1, (int32_t)newpoints.size());
+  const std::vector<int32_t> &ge = newpoint_group_end.empty() ? one_group : newpoint_group_end;
+  svs_nbh_request q;
+  std::memset(&q, 0, sizeof q);
+  q.stream = 0; q.n_vertex = (int32_t)vertex_ids.size(); q.n_head = (int32_t)newpoints.size(); q.n_head_groups = (int32_t)ge.size();
+  q.h_vertex_kf = vertex_ids.data(); q.h_slot_kf = slot_keyframe_ids.data(); q.h_head_group_end = ge.data(); q.h_head = newpoints.empty() ? nullptr : newpoints.data();
+  svs_nbh_result r;
+  std::vector<int32_t> pid((size_t)max_points_), vid((size_t)vertex_cap);
+  std::vector<double> vT((size_t)vertex_cap * 12);
+  if (!ctx_.check(svs_frontend_set_candidates_from_map(fe_, map.get(), 1, &q, refresh_poses ? 1 : 0, vertex_cap, &r, pid.data(), vid.data(), vT.data(), nullptr))) return false;
+  if (res) *res = r;
+  if (r.over_capacity) return false;
+  n_ = r.n_points;
+  if (point_ids) point_ids->assign(pid.begin(), pid.begin() + r.n_points);
+  if (vertex_map) {
+    vertex_map->resize((size_t)r.n_vertex);
+    for (int i = 0; i < r.n_vertex; ++i) { (*vertex_map)[(size_t)i].frame_id = vid[(size_t)i]; std::memcpy((*vertex_map)[(size_t)i].T_me_from_w, &vT[(size_t)i * 12], 12 * sizeof(double)); }
+  }
+  return true;
+}
 class BackendRegistration {
  public:
   BackendRegistration(const Context &c, const svs_cam &stereo_cam, int max_points = 4096, int max_keyframes = 256, int max_observers = 65536, int covis_thr = 15)

@@ -18,6 +18,7 @@
 // told to keep (Frame::clone, keyframes.h:72-83), the candidate points (ap_map) and the FAST threshold state -- per stream.
 #include "common.h"
 #include "fast_view.h"
+#include "nbh_map.h"
 #include "pose.h"
 #include "seed.h"
 #include <string.h>
@@ -26,6 +27,7 @@
 
 namespace {
 constexpr int MAX_GROUPS = 64;
+static_assert(MAX_GROUPS == NBH_MAX_GROUPS, "the map's walk writes rows of d_group_end");
 
 // T_cur_from_w = T_cur_from_actkey * T_actkey_from_w and T_w_from_actkey = T_actkey_from_w^-1 (matcher.cpp:326-330), formed on the
 // device from the tracked pose so that the matcher needs no host round trip.  One workgroup per stream.
@@ -160,6 +162,8 @@ struct svs_frontend {
   // since the last first frame, or the list was replaced behind the step), staging blocks grown on demand
   int n_gated = -1;
   PinnedBuf<uint8_t> h_seed; DevBuf<uint8_t> d_seed;
+  // svs_frontend_set_candidates_from_map: the staged requests and, behind them, what comes back; grown on demand
+  PinnedBuf<uint8_t> h_nbh; DevBuf<uint8_t> d_nbh;
   // drains the streams and takes the detector / block matcher along before the members above go (also when create gives up half way)
   ~svs_frontend() {
     (void)hipStreamSynchronize(ctx->stream);
@@ -420,6 +424,124 @@ extern "C" int svs_frontend_set_candidates_all(svs_frontend *fe, const svs_candi
   fe->n_launch = *std::max_element(fe->n_points.begin(), fe->n_points.end());
   fe->n_gated = -1;      // the last step's gate records no longer belong to the list on the device
   fe->max_groups_used = std::max(fe->max_groups_used, n_groups);
+  return SVS_OK;
+}
+
+/* a stream's neighbourhood list from the device-resident map (map.hip through nbh_map.h; the contract is in the header): everything is checked on the host first,
+   then one staged upload, the map's walk writing d_pts / d_group_end / d_n_groups / d_n_new / d_kfs in place, one download from which the host state follows */
+extern "C" int svs_frontend_set_candidates_from_map(svs_frontend *fe, svs_map *map, int n_requests, const svs_nbh_request *req, int refresh_poses, int vertex_cap,
+                                                    svs_nbh_result *h_res, int32_t *h_point_id, int32_t *h_vertex_id, double *h_vertex_T,
+                                                    svs_candidate_point *h_records) {
+  svs_ctx *ctx = fe ? fe->ctx : nullptr;
+  SVS_REQUIRE(ctx, fe && map && svs_map_ctx(map) == ctx && !fe->submitted && n_requests >= 0 && n_requests <= fe->B && (n_requests == 0 || req) && vertex_cap >= 1);
+  if (fe->max_keyframes > 32767) { ctx->err = "svs_frontend_set_candidates_from_map: at most 32767 keyframe slots"; return SVS_ERR_UNSUPPORTED; }
+  const int R = n_requests, B = fe->B, K = fe->max_keyframes, MP = fe->max_points, VB = vertex_cap;
+  size_t n_ids = 0, n_head = 0;
+  {
+    std::vector<uint8_t> named((size_t)B, 0);
+    std::vector<int32_t> sorted;
+    for (int r = 0; r < R; ++r) {
+      const svs_nbh_request &q = req[r];
+      SVS_REQUIRE(ctx, q.stream >= 0 && q.stream < B && !named[q.stream]);
+      named[q.stream] = 1;
+      SVS_REQUIRE(ctx, q.n_vertex >= 1 && q.h_vertex_kf && q.h_slot_kf && q.n_head >= 0 && q.n_head <= MP && (q.n_head == 0 || q.h_head) && q.n_head_groups >= 1 &&
+                           q.h_head_group_end);
+      if (q.n_head_groups + 1 > MAX_GROUPS) { ctx->err = "svs_frontend_set_candidates_from_map: more than 64 groups"; return SVS_ERR_CAPACITY; }
+      for (int i = 0; i < q.n_vertex; ++i) SVS_REQUIRE(ctx, svs_map_has_keyframe(map, q.h_vertex_kf[i]));
+      sorted.assign(q.h_vertex_kf, q.h_vertex_kf + q.n_vertex);
+      std::sort(sorted.begin(), sorted.end());
+      SVS_REQUIRE(ctx, std::adjacent_find(sorted.begin(), sorted.end()) == sorted.end());
+      const uint8_t *kept = fe->kept.data() + (size_t)q.stream * K;
+      sorted.clear();
+      for (int s = 0; s < K; ++s)
+        if (q.h_slot_kf[s] >= 0) { SVS_REQUIRE(ctx, kept[s]); sorted.push_back(q.h_slot_kf[s]); }
+      std::sort(sorted.begin(), sorted.end());
+      SVS_REQUIRE(ctx, std::adjacent_find(sorted.begin(), sorted.end()) == sorted.end());
+      SVS_REQUIRE(ctx, q.h_head_group_end[q.n_head_groups - 1] == q.n_head);
+      for (int g = 0; g < q.n_head_groups; ++g) SVS_REQUIRE(ctx, q.h_head_group_end[g] >= (g ? q.h_head_group_end[g - 1] : 0));
+      for (int i = 0; i < q.n_head; ++i) SVS_REQUIRE(ctx, q.h_head[i].kf_index < 0 || (q.h_head[i].kf_index < K && kept[q.h_head[i].kf_index]));
+      n_ids += (size_t)q.n_vertex + (size_t)K;
+      n_head += (size_t)q.n_head;
+    }
+  }
+  if (R == 0) return SVS_OK;
+  SVS_DEVICE(ctx);
+  auto al = [](size_t v) { return (v + 15) & ~(size_t)15; };
+  const size_t o_ids = al((size_t)R * sizeof(nbh_req)), o_head = o_ids + al(n_ids * sizeof(int32_t)), in_bytes = o_head + n_head * sizeof(svs_candidate_point);
+  const size_t o_res = al(in_bytes), o_slot = o_res + (size_t)R * sizeof(svs_nbh_result), o_vid = o_slot + (size_t)R * K * 12 * sizeof(double),
+               o_vT = o_vid + al((size_t)R * VB * sizeof(int32_t)), o_pid = o_vT + (size_t)R * VB * 12 * sizeof(double), bytes = o_pid + (size_t)R * MP * sizeof(int32_t);
+  if (fe->h_nbh.bytes() < bytes) {      // (no call is in flight: this one is blocking)
+    SVS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    SVS_HIP(ctx, fe->h_nbh.alloc(bytes * 2));
+    SVS_HIP(ctx, fe->d_nbh.alloc(bytes * 2));
+  }
+  uint8_t *hs = fe->h_nbh, *ds = fe->d_nbh;
+  nbh_req *hq = reinterpret_cast<nbh_req *>(hs);
+  int32_t *ids = reinterpret_cast<int32_t *>(hs + o_ids);
+  svs_candidate_point *head = reinterpret_cast<svs_candidate_point *>(hs + o_head);
+  size_t at_id = 0, at_head = 0;
+  for (int r = 0; r < R; ++r) {
+    const svs_nbh_request &q = req[r];
+    nbh_req &s = hq[r];
+    memset(&s, 0, sizeof s);
+    s.stream = q.stream; s.n_vertex = q.n_vertex; s.n_head = q.n_head; s.n_groups = q.n_head_groups + 1; s.prev_len = fe->n_points[q.stream];
+    s.vertex_off = (int32_t)at_id;
+    memcpy(ids + at_id, q.h_vertex_kf, (size_t)q.n_vertex * sizeof(int32_t));
+    at_id += (size_t)q.n_vertex;
+    s.slot_off = (int32_t)at_id;
+    for (int k = 0; k < K; ++k) ids[at_id + k] = svs_map_has_keyframe(map, q.h_slot_kf[k]) ? q.h_slot_kf[k] : -1;
+    at_id += (size_t)K;
+    s.head_off = (int32_t)at_head;
+    if (q.n_head) memcpy(head + at_head, q.h_head, (size_t)q.n_head * sizeof(svs_candidate_point));
+    at_head += (size_t)q.n_head;
+    for (int g = 0; g < q.n_head_groups; ++g) s.group_end[g] = q.h_head_group_end[g];
+  }
+  SVS_HIP(ctx, hipMemcpyAsync(ds, hs, in_bytes, hipMemcpyHostToDevice, ctx->stream));
+  MapNbhDst D{};
+  D.req = reinterpret_cast<const nbh_req *>(ds); D.ids = reinterpret_cast<const int32_t *>(ds + o_ids); D.head = reinterpret_cast<const svs_candidate_point *>(ds + o_head);
+  D.pts = fe->d_pts; D.max_points = MP; D.group_end = fe->d_group_end; D.n_groups = fe->d_n_groups; D.n_new = fe->d_n_new; D.kfs = fe->d_kfs; D.max_keyframes = K;
+  D.refresh = refresh_poses ? 1 : 0;
+  D.res = reinterpret_cast<svs_nbh_result *>(ds + o_res); D.slot_T = reinterpret_cast<double *>(ds + o_slot);
+  D.vertex_id = reinterpret_cast<int32_t *>(ds + o_vid); D.vertex_T = reinterpret_cast<double *>(ds + o_vT); D.VB = VB;
+  D.point_id = reinterpret_cast<int32_t *>(ds + o_pid);
+  if (int rc = svs_map_build_neighborhoods(map, R, D)) return rc;
+  const size_t down_end = h_point_id ? bytes : (h_vertex_id || h_vertex_T) ? o_pid : o_vid;
+  SVS_HIP(ctx, hipMemcpyAsync(hs + o_res, ds + o_res, down_end - o_res, hipMemcpyDeviceToHost, ctx->stream));
+  if (h_records) SVS_HIP(ctx, hipMemcpyAsync(h_records, fe->d_pts, sizeof(svs_candidate_point) * (size_t)MP * B, hipMemcpyDeviceToHost, ctx->stream));
+  SVS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  // ---- the host state follows the download
+  const svs_nbh_result *res = reinterpret_cast<const svs_nbh_result *>(hs + o_res);
+  bool any = false;
+  for (int r = 0; r < R; ++r) {
+    const svs_nbh_request &q = req[r];
+    const bool over = res[r].over_capacity != 0;
+    if (h_res) h_res[r] = res[r];
+    if (h_point_id) {
+      if (over) std::fill(h_point_id + (size_t)r * MP, h_point_id + (size_t)(r + 1) * MP, -1);
+      else memcpy(h_point_id + (size_t)r * MP, hs + o_pid + (size_t)r * MP * sizeof(int32_t), (size_t)MP * sizeof(int32_t));
+    }
+    if (h_vertex_id) {
+      if (over) std::fill(h_vertex_id + (size_t)r * VB, h_vertex_id + (size_t)(r + 1) * VB, -1);
+      else memcpy(h_vertex_id + (size_t)r * VB, hs + o_vid + (size_t)r * VB * sizeof(int32_t), (size_t)VB * sizeof(int32_t));
+    }
+    if (h_vertex_T) {
+      if (over) memset(h_vertex_T + (size_t)r * VB * 12, 0, (size_t)VB * 12 * sizeof(double));
+      else memcpy(h_vertex_T + (size_t)r * VB * 12, hs + o_vT + (size_t)r * VB * 12 * sizeof(double), (size_t)VB * 12 * sizeof(double));
+    }
+    if (over) continue;
+    any = true;
+    fe->n_points[q.stream] = res[r].n_points; fe->n_new_records[q.stream] = q.n_head;
+    fe->max_groups_used = std::max(fe->max_groups_used, q.n_head_groups + 1);
+    if (refresh_poses) {
+      const double *sT = reinterpret_cast<const double *>(hs + o_slot) + (size_t)r * K * 12;
+      for (int k = 0; k < K; ++k)
+        if (svs_map_has_keyframe(map, q.h_slot_kf[k])) memcpy(fe->h_kfs[(size_t)q.stream * K + k].T_anchor_from_w, sT + (size_t)k * 12, 12 * sizeof(double));
+    }
+  }
+  if (any) {
+    fe->n_launch = *std::max_element(fe->n_points.begin(), fe->n_points.end());
+    fe->n_gated = -1;      // the last step's gate records no longer belong to the list on the device
+  }
   return SVS_OK;
 }
 

@@ -7,8 +7,11 @@
 //   map_build_kernel    one workgroup per request: the walk and direct sets and the built table are LDS bitmaps over keyframe ids, the point set a bitmap in
 //                   global memory (one row per request); marking walks the feature_tables of the walk set, compaction turns bitmap words into ascending ids by
 //                   popcounts and a wave64 / workgroup prefix, so no atomic decides an order: the built request is a function of the map's content alone
+//   map_nbh_kernel      one workgroup per request of a front-end stream (nbh_map.h): addPointsToNeighbors / addAnchorPosesToNeighbors (backend.cpp:311-386) with the
+//                   same sets, written straight into the stream's candidate list, group ends and keyframe slots
 // Integer and copy work throughout; the host keeps the id sets and the set of pairs, so every refusal happens before anything is uploaded.
 #include "reg_map.h"
+#include "nbh_map.h"
 #include <string.h>
 #include <algorithm>
 #include <unordered_set>
@@ -341,7 +344,152 @@ __global__ __launch_bounds__(MB_THREADS) void map_build_kernel(MapK M, MapBuildD
   }
 }
 
-#define MAP_CAPACITY(ctx, cond)                                                                           \
+// mark[word] |= bit for every active lane, with ONE atomic per distinct word of the wave: the points a keyframe seeded have consecutive ids, so the 64 lanes of
+// a wave that reads a feature_table mostly share a few words, and atomics on one address serialise in the L2 (as wave_add_by_key found for the counters).
+// Every lane of the wave calls it (ballots and shuffles inside)
+__device__ __forceinline__ void wave_or_by_word(uint32_t *mark, int word, uint32_t bit, bool active) {
+  const int lane = lane_id();
+  unsigned long long todo = __ballot(active);
+  while (todo) {                                         // wave-uniform
+    const int leader = __ffsll((long long)todo) - 1;     // an active lane
+    const int w0 = __shfl(word, leader, 64);
+    const bool mine = active && word == w0;
+    uint32_t v = mine ? bit : 0u;
+#pragma unroll
+    for (int o = 32; o; o >>= 1) v |= (uint32_t)__shfl_xor((int)v, o, 64);
+    if (lane == leader) atomicOr(&mark[w0], v);
+    todo &= ~__ballot(mine);                             // holds the leader's bit: the loop ends
+  }
+}
+
+// ---- the neighbourhood of a front-end stream (Backend::computeNeighborhood from the vertex list onwards, backend.cpp:311-386): one workgroup per request.
+// The same sets as above -- the given vertices and the anchors as LDS bitmaps over keyframe ids, the points as the request's row of M.mark, ascending ids by
+// popcounts and prefixes -- and a table id -> slot of the stream in LDS.  Everything that decides whether the request fits (the point count, the vertex count) is
+// known before the first write into the front end's tables: a request over capacity returns with those untouched.
+__global__ __launch_bounds__(MB_THREADS) void map_nbh_kernel(MapK M, MapNbhDst D) {
+  __shared__ uint32_t s_vert[MAP_KF_WORDS], s_anch[MAP_KF_WORDS];
+  __shared__ int16_t s_slot[MAP_MAX_KF];                           // -1: no slot of the stream holds the keyframe
+  __shared__ int s_w[MB_THREADS / 64];
+  const int r = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const nbh_req &Q = D.req[r];
+  const int b = Q.stream, n_vertex = Q.n_vertex, n_head = Q.n_head, G = Q.n_groups, MP = D.max_points, K = D.max_keyframes;
+  const int32_t *vertex = D.ids + Q.vertex_off, *slot_kf = D.ids + Q.slot_off;
+  uint32_t *mark = M.mark + (size_t)r * M.mark_b;
+  int32_t *point_id = D.point_id + (size_t)r * MP;
+  const int n_words = (M.pt_hi + 31) >> 5;                      // <= mark_b
+  // a. empty sets
+  s_vert[tid] = 0; s_anch[tid] = 0;
+  for (int i = tid; i < MAP_MAX_KF; i += MB_THREADS) s_slot[i] = -1;
+  for (int i = tid; i < n_words; i += MB_THREADS) mark[i] = 0;
+  __syncthreads();
+  // b. the given vertices (ids the host has checked: in the map, so below kf_hi <= MAP_MAX_KF); the slots (an id in at most one slot)
+  for (int i = tid; i < n_vertex; i += MB_THREADS) { const int id = vertex[i]; atomicOr(&s_vert[id >> 5], 1u << (id & 31)); }
+  for (int s = tid; s < K; s += MB_THREADS) { const int id = slot_kf[s]; if ((unsigned)id < (unsigned)MAP_MAX_KF) s_slot[id] = (int16_t)s; }
+  __syncthreads();
+  // c. mark the points: a wave per feature_table (:316-331)
+  for (int i = wave; i < n_vertex; i += MB_THREADS / 64) {
+    const int kf = vertex[i];
+    const int e1 = M.kf_begin[kf + 1];
+    for (int e0 = M.kf_begin[kf]; e0 < e1; e0 += 64) {          // wave-uniform
+      const int p = e0 + lane < e1 ? M.kf_rows[e0 + lane] : -1;
+      wave_or_by_word(mark, p >> 5, 1u << (p & 31), (unsigned)p < (unsigned)M.pt_hi);
+    }
+  }
+  __syncthreads();
+  // d. the set bits in ascending order, behind the head's ids; what does not fit is only counted
+  int n_map = 0;
+  for (int base = 0; base < n_words; base += MB_THREADS) {      // block-uniform trip count
+    const int w = base + tid;
+    uint32_t bits = w < n_words ? __hip_atomic_load(&mark[w], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0u;
+    int tot;
+    int pos = n_head + n_map + block_excl_scan(__popc(bits), s_w, tot);
+    while (bits) {
+      const int bit = __ffs((int)bits) - 1;
+      bits &= bits - 1;
+      if (pos < MP) point_id[pos] = (w << 5) + bit;
+      ++pos;
+    }
+    n_map += tot;
+  }
+  const int total = n_head + n_map;
+  const bool over_points = total > MP;
+  __syncthreads();
+  // e. their anchors (:374-384), and how many of them the stream holds no slot for
+  int c = 0;
+  if (!over_points)
+    for (int i = tid; i < n_map; i += MB_THREADS) {
+      const int a = M.pt[point_id[n_head + i]].kf_index;
+      if ((unsigned)a < (unsigned)MAP_MAX_KF) atomicOr(&s_anch[a >> 5], 1u << (a & 31));
+      if ((unsigned)a >= (unsigned)MAP_MAX_KF || s_slot[a] < 0) ++c;
+    }
+  int n_no_slot;
+  (void)block_excl_scan(c, s_w, n_no_slot);                      // (its barriers also complete s_anch)
+  // f. the vertex set: the given ids, behind them the anchors that are not among them, ascending
+  uint32_t extra = s_anch[tid] & ~s_vert[tid];
+  int n_extra;
+  const int rank = block_excl_scan(__popc(extra), s_w, n_extra);
+  const int n_vert = over_points ? 0 : n_vertex + n_extra;
+  if (over_points || n_vert > D.VB) {                            // block-uniform: nothing of the stream has been touched
+    if (tid == 0) {
+      svs_nbh_result R{};
+      R.n_points = total; R.n_map_points = n_map; R.n_vertex = n_vert; R.n_no_slot = n_no_slot; R.over_capacity = 1;
+      D.res[r] = R;
+    }
+    return;
+  }
+  // g. the stream's list: the head as it was staged, the map's records (four 16-byte loads each) with the anchor's slot, 0xff up to the previous length
+  svs_candidate_point *pts = D.pts + (size_t)b * MP;
+  int4 *d4 = reinterpret_cast<int4 *>(pts);
+  const svs_candidate_point *head = D.head + Q.head_off;
+  const int4 *h4 = reinterpret_cast<const int4 *>(head);
+  for (int i = tid; i < n_head * 4; i += MB_THREADS) d4[i] = h4[i];
+  for (int i = tid; i < n_map; i += MB_THREADS) {
+    const int4 *s4 = reinterpret_cast<const int4 *>(M.pt + point_id[n_head + i]);
+    int4 q = s4[3];                                              // anchor_level, the anchor's id, point_id, pad_
+    q.y = (unsigned)q.y < (unsigned)MAP_MAX_KF ? (int)s_slot[q.y] : -1;
+    int4 *o4 = d4 + (size_t)(n_head + i) * 4;
+    o4[0] = s4[0]; o4[1] = s4[1]; o4[2] = s4[2]; o4[3] = q;
+  }
+  for (int i = total * 4 + tid; i < Q.prev_len * 4; i += MB_THREADS) d4[i] = make_int4(-1, -1, -1, -1);
+  for (int i = tid; i < n_head; i += MB_THREADS) point_id[i] = head[i].point_id;
+  for (int i = total + tid; i < MP; i += MB_THREADS) point_id[i] = -1;
+  if (tid < NBH_MAX_GROUPS) D.group_end[(size_t)b * NBH_MAX_GROUPS + tid] = tid < G - 1 ? Q.group_end[tid] : tid == G - 1 ? total : 0;
+  if (tid == 0) { D.n_groups[b] = G; D.n_new[b] = n_head; }
+  // h. the vertex set with the poses the map stores
+  int32_t *vid = D.vertex_id + (size_t)r * D.VB;
+  double *vT = D.vertex_T + (size_t)r * D.VB * 12;
+  for (int i = tid; i < n_vertex * 12; i += MB_THREADS) {
+    const int v = i / 12, k = i % 12, id = vertex[v];
+    vT[i] = M.kf[id].T_anchor_from_w[k];
+    if (k == 0) vid[v] = id;
+  }
+  for (int e = n_vertex + rank; extra; ++e) {                    // e < n_vert <= VB
+    const int id = (tid << 5) + __ffs((int)extra) - 1;
+    extra &= extra - 1;
+    vid[e] = id;
+    for (int k = 0; k < 12; ++k) vT[(size_t)e * 12 + k] = M.kf[id].T_anchor_from_w[k];
+  }
+  for (int i = n_vert * 12 + tid; i < D.VB * 12; i += MB_THREADS) {
+    vT[i] = 0.0;
+    if (i % 12 == 0) vid[i / 12] = -1;
+  }
+  // i. the slots that hold a keyframe of the map take its pose (the pyramid pointers and strides stay)
+  svs_keyframe *kfs = D.kfs + (size_t)b * K;
+  double *sT = D.slot_T + (size_t)r * K * 12;
+  for (int i = tid; i < K * 12; i += MB_THREADS) {
+    const int s = i / 12, k = i % 12, id = slot_kf[s];
+    double v = 0.0;
+    if (D.refresh && (unsigned)id < (unsigned)MAP_MAX_KF) { v = M.kf[id].T_anchor_from_w[k]; kfs[s].T_anchor_from_w[k] = v; }
+    sT[i] = v;
+  }
+  if (tid == 0) {
+    svs_nbh_result R{};
+    R.n_points = total; R.n_map_points = n_map; R.n_vertex = n_vert; R.n_no_slot = n_no_slot; R.over_capacity = 0;
+    D.res[r] = R;
+  }
+}
+
+#define MAP_CAPACITY(ctx, cond)                                                                        \
   do {                                                                                                    \
     if (!(cond)) {                                                                                        \
       char buf_[512];                                                                                     \
@@ -612,7 +760,8 @@ extern "C" int svs_map_set_window(svs_map *m, int n, const int32_t *h_kf_ids) {
   return SVS_OK;
 }
 
-int svs_map_build_requests(svs_map *m, int n_requests, const MapBuildDst &dst) {
+// what every walk needs before its launch: a row of the point bitmap per request, and CSR views of the whole log
+static int map_prepare_walk(svs_map *m, int n_requests) {
   svs_ctx *ctx = m->ctx;
   if (m->mark_rows < n_requests) {      // grow-only; a new block needs the stream drained of the walks that read the old one
     SVS_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -630,7 +779,21 @@ int svs_map_build_requests(svs_map *m, int n_requests, const MapBuildDst &dst) {
     SVS_LAUNCH_CHECK(ctx);
     m->csr_n = m->n_obs;
   }
+  return SVS_OK;
+}
+
+int svs_map_build_requests(svs_map *m, int n_requests, const MapBuildDst &dst) {
+  svs_ctx *ctx = m->ctx;
+  if (int rc = map_prepare_walk(m, n_requests)) return rc;
   hipLaunchKernelGGL(map_build_kernel, dim3(n_requests), dim3(MB_THREADS), 0, ctx->stream, m->view(), dst);
+  SVS_LAUNCH_CHECK(ctx);
+  return SVS_OK;
+}
+
+int svs_map_build_neighborhoods(svs_map *m, int n_requests, const MapNbhDst &dst) {
+  svs_ctx *ctx = m->ctx;
+  if (int rc = map_prepare_walk(m, n_requests)) return rc;
+  hipLaunchKernelGGL(map_nbh_kernel, dim3(n_requests), dim3(MB_THREADS), 0, ctx->stream, m->view(), dst);
   SVS_LAUNCH_CHECK(ctx);
   return SVS_OK;
 }

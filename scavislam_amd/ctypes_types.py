@@ -253,3 +253,19 @@ class RegMapRequest(C.Structure):
     """svs_reg_map_request: a root keyframe by id, with the ids of framesInNeighborhood(root) and directNeighborsOf(root)"""
     _fields_ = [("mode", C.c_int32), ("root_kf", C.c_int32), ("n_walk", C.c_int32), ("n_direct", C.c_int32), ("T_root_from_world", C.c_double * 12),
                 ("h_walk_kf", C.c_void_p), ("h_direct_kf", C.c_void_p)]
+
+
+# ---- front end: a stream's neighbourhood list from the map (svs_frontend_set_candidates_from_map)
+class NbhRequest(C.Structure):
+    """svs_nbh_request: the stream, the vertex list (ids, root first), the stream's slot table (id per slot, -1 for none) and the new-point groups from the host"""
+    _fields_ = [("stream", C.c_int32), ("n_vertex", C.c_int32), ("n_head", C.c_int32), ("n_head_groups", C.c_int32), ("h_vertex_kf", C.c_void_p),
+                ("h_slot_kf", C.c_void_p), ("h_head_group_end", C.c_void_p), ("h_head", C.c_void_p)]
+
+
+class NbhResult(C.Structure):
+    """svs_nbh_result"""
+    _fields_ = [("n_points", C.c_int32), ("n_map_points", C.c_int32), ("n_vertex", C.c_int32), ("n_no_slot", C.c_int32), ("over_capacity", C.c_int32),
+                ("pad_", C.c_int32 * 3)]
+
+
+assert C.sizeof(NbhRequest) == 48 and C.sizeof(NbhResult) == 32

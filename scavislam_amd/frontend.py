@@ -596,6 +596,7 @@ class StereoFrontend:
 
     def __init__(self, ctx, cam, max_points=4096, max_keyframes=8, params=None, n_streams=1):
         self.ctx, self.cam, self.n_streams = ctx, cam, n_streams
+        self.max_points, self.max_keyframes = int(max_points), int(max_keyframes)
         self.params = params or capi.FrontendParams.reference()
         camc = Cam(cam["f"], cam["cx"], cam["cy"], cam["b"], cam["w"], cam["h"])
         self.h = C.c_void_p()
@@ -653,6 +654,49 @@ class StereoFrontend:
         ge = np.ascontiguousarray(group_end, np.int32)
         self.ctx.check(self.ctx.lib.svs_frontend_set_candidates_grouped(self.h, stream, pts.ctypes.data, len(pts), ge.ctypes.data, len(ge)))
         self.n_points[stream] = len(pts)
+
+    def setCandidatesFromMap(self, resident_map, requests, refresh_poses=True, vertex_cap=64, want_records=False):
+        """Backend::computeNeighborhood from the vertex list onwards (backend.cpp:311-386) on the device-resident map, written into the streams' lists in place.
+        requests: dicts with stream, vertex_kf (ids, root first), slot_kf (the keyframe id kept in each slot of the stream, -1 for none) and optionally head
+        (CANDIDATE_DTYPE: the new-point groups) with head_group_end (default: one group).  Returns one dict per request: the svs_nbh_result counts, point_ids
+        (per record of the built list), vertex_ids / vertex_T (the vertex set and its poses as the map stores them); want_records adds `table`, the whole
+        candidate table [n_streams][max_points] as it lies on the device.  A request over capacity leaves its stream untouched (over_capacity = 1)"""
+        from .ctypes_types import NbhRequest, NbhResult
+        n = len(requests)
+        arr = (NbhRequest * max(n, 1))()
+        keep = []
+        for r, q in zip(arr, requests):
+            vertex = np.ascontiguousarray(q["vertex_kf"], np.int32).reshape(-1)
+            slot = np.ascontiguousarray(q["slot_kf"], np.int32).reshape(-1)
+            head = np.ascontiguousarray(q.get("head", np.zeros(0, CANDIDATE_DTYPE)), CANDIDATE_DTYPE).reshape(-1)
+            ge = np.ascontiguousarray(q.get("head_group_end", [len(head)]), np.int32).reshape(-1)
+            if len(slot) != self.max_keyframes:
+                raise ValueError("slot_kf needs one entry per keyframe slot of the front end")
+            keep += [vertex, slot, head, ge]
+            r.stream, r.n_vertex, r.n_head, r.n_head_groups = int(q.get("stream", 0)), len(vertex), len(head), len(ge)
+            r.h_vertex_kf, r.h_slot_kf, r.h_head_group_end, r.h_head = vertex.ctypes.data, slot.ctypes.data, ge.ctypes.data, head.ctypes.data if len(head) else None
+        res = (NbhResult * max(n, 1))()
+        mp = self.max_points
+        pid = np.empty((max(n, 1), mp), np.int32)
+        vid = np.empty((max(n, 1), vertex_cap), np.int32)
+        vT = np.empty((max(n, 1), vertex_cap, 12), np.float64)
+        table = np.empty((self.n_streams, mp), CANDIDATE_DTYPE) if want_records else None
+        self.ctx.check(self.ctx.lib.svs_frontend_set_candidates_from_map(self.h, resident_map.h, n, arr, int(bool(refresh_poses)), int(vertex_cap), res, pid.ctypes.data,
+                                                                         vid.ctypes.data, vT.ctypes.data, table.ctypes.data if want_records else None))
+        out = []
+        for i in range(n):
+            o = {f: int(getattr(res[i], f)) for f in ("n_points", "n_map_points", "n_vertex", "n_no_slot", "over_capacity")}
+            ok = not o["over_capacity"]
+            if ok:
+                self.n_points[arr[i].stream] = o["n_points"]
+            o["point_ids"] = pid[i, :o["n_points"] if ok else 0].copy()
+            o["vertex_ids"] = vid[i, :o["n_vertex"] if ok else 0].copy()
+            o["vertex_T"] = vT[i, :o["n_vertex"] if ok else 0].copy()
+            o["raw"] = (bytes(res[i]), pid[i].tobytes(), vid[i].tobytes(), vT[i].tobytes())      # the full-length rows (tests: byte comparisons)
+            if want_records:
+                o["table"] = table
+            out.append(o)
+        return out
 
     def stagingView(self):
         """numpy views (left u8 [h, w], right u8 [h, w], disp f32 [h, w]) of the pinned buffers the next frame is staged in: a frame written into
