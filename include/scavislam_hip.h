@@ -191,8 +191,9 @@ typedef struct svs_stereo svs_stereo;
    or SVS_STEREO_FRAME_CCL=1 at create; SVS_STEREO_STRIP_KB=8..151 at create sets the LDS of a strip), "stereo_validate_wide_calls" (left-right check with one row
    per workgroup, w > 2048), "stereo_wide_search_calls" (the search kernels for any disparity count, which keep a pixel's window sums in LDS: every
    num_disparities but 32, and 32 too under SVS_STEREO_WIDE=1 at create; 32 otherwise runs the register-ring kernels, with the same result bit for bit).
-   "stereo_speckle_error_mask" (blocking) is the OR of the bits the bounded walks of the strip filter leave when one gives up (never
-   expected; 0 = none since the context was created): 1 / 2 a find inside a strip, 4 a union inside a strip, 8 / 16 a find / a union across strips. */
+   "stereo_speckle_error_mask" (blocking) is the OR of the bits the bounded walks of the speckle filter leave when one gives up (never
+   expected; 0 = none since the context was created): 1 / 2 a find inside a strip, 4 a union inside a strip, 8 / 16 a find / a union on frame labels (across
+   strips, and every walk of the whole-frame filter). */
 int svs_stereo_create(svs_ctx *ctx, int w, int h, int max_batch, const svs_stereo_params *prm, svs_stereo **out);
 int svs_stereo_destroy(svs_stereo *s);
 /* d_disp[b][y*dstride + x] = disparity in pixels, (min_disparity - 1) where filtered (all device pointers;

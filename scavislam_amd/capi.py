@@ -327,7 +327,7 @@ class Context:
     def get_stat(self, name):
         """counters of the context (svs_ctx_get_stat): "trk_exact_sums", "trk_exact_fallbacks" (blocking), "spin_lane_launches", "spin_gated_launches";
         which kernels svs_stereo_compute chose, one step per call: "stereo_prefilter16_calls", "stereo_prefilter4_calls", "stereo_strip_filter_calls" ("stereo_strip_filter_strips": their strips per frame, summed),
-        "stereo_frame_filter_calls", "stereo_validate_wide_calls", "stereo_wide_search_calls" (the search for any disparity count: every count but 32); "stereo_speckle_error_mask" (blocking): give-up bits of the strip speckle filter, 0 = none;
+        "stereo_frame_filter_calls", "stereo_validate_wide_calls", "stereo_wide_search_calls" (the search for any disparity count: every count but 32); "stereo_speckle_error_mask" (blocking): give-up bits of the speckle filter, 0 = none;
         of the whole process: "live_device_bytes", "live_pinned_bytes", "live_sync_objects" (what contexts and handles hold right now)"""
         v = C.c_longlong(0)
         self.call("svs_ctx_get_stat", name.encode(), C.byref(v))

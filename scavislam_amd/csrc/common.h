@@ -56,7 +56,7 @@ struct svs_ctx {
   // block matching (stereo.hip): the kernels svs_stereo_compute chose, counted per call on the host (svs_ctx_get_stat "stereo_prefilter16_calls", "stereo_prefilter4_calls",
   // "stereo_strip_filter_calls", "stereo_frame_filter_calls", "stereo_validate_wide_calls", "stereo_wide_search_calls"; "stereo_strip_filter_strips": strips per frame, summed over the strip calls)
   long long stereo_n_prefilter16 = 0, stereo_n_prefilter4 = 0, stereo_n_strip_filter = 0, stereo_n_frame_filter = 0, stereo_n_validate_wide = 0, stereo_n_strips = 0;
-  DevBuf<int> stereo_err;     // device, [32], zeroed at svs_ctx_create: [0] the give-up bits the strip speckle filter's bounded walks OR in (svs_ctx_get_stat
+  DevBuf<int> stereo_err;     // device, [32], zeroed at svs_ctx_create: [0] the give-up bits the speckle filter's bounded walks OR in (svs_ctx_get_stat
                               // "stereo_speckle_error_mask"), [8..21] the phase stamps of SVS_STEREO_DEBUG.  Shared by every svs_stereo of the context
   int xcd_swizzle = 1;        // "xcd_swizzle": tile kernels whose neighbouring tiles share image lines (FAST score, block matching, ...) hand every XCD a CONTIGUOUS range of
                               // the linear workgroup index (devutil.h: xcd_contiguous) so the shared lines are fetched into one L2, not into 2-3; 0: the dispatcher's round robin (A/B)

@@ -159,7 +159,7 @@ extern "C" int svs_ctx_get_stat(svs_ctx *c, const char *name, long long *out) {
   if (n == "stereo_frame_filter_calls") { *out = c->stereo_n_frame_filter; return SVS_OK; }
   if (n == "stereo_validate_wide_calls") { *out = c->stereo_n_validate_wide; return SVS_OK; }
   if (n == "stereo_wide_search_calls") { *out = c->stereo_n_wide_search; return SVS_OK; }
-  if (n == "stereo_speckle_error_mask") {      // the give-up bits of the strip speckle filter's bounded walks, on the device (blocking)
+  if (n == "stereo_speckle_error_mask") {      // the give-up bits of the speckle filter's bounded walks, on the device (blocking)
     int m = 0;
     SVS_DEVICE(c);
     SVS_HIP(c, hipMemcpyAsync(&m, c->stereo_err, sizeof m, hipMemcpyDeviceToHost, c->stream));

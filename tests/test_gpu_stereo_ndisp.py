@@ -1,4 +1,4 @@
-"""Block matching over 16, 32, ..., 160 disparities (ui.num_disp16 = 1..10): stereo_bm_wide_kernel / stereo_bm_wide_edge_kernel of csrc/stereo.hip against the
+"""Block matching over 16, 32, ..., 160 disparities (ui.num_disp16 = 1..10): stereo_bm_wide_kernel / stereo_bm_edge_kernel<64> of csrc/stereo_search.inc against the
 oracle restatement of cv::StereoBM, bit for bit (np.array_equal everywhere: an integer pipeline).  tests/test_gpu_stereo_paths.py walks the dispatch at 32
 disparities; here the disparity count varies.  Input: the banded noise pair of tests/stereo_ndisp_cases.py, whose winners cover the whole search range
 (tests/test_stereo_ndisp_cpu.py pins the oracle to the NumPy model on it), and noise against its own roll.
@@ -23,7 +23,7 @@ import test_gpu_stereo_paths as P
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
-TILE, STRIP = 64, 48      # csrc/stereo.hip: WIDE_TILE, WIDE_STRIP
+TILE, STRIP = 64, 48      # csrc/stereo.hip: WIDE_TILE, WIDE_STRIP (the constants the host shares with csrc/stereo_search.inc)
 WIDE = "stereo_wide_search_calls"
 RAW = dict(disp12_max_diff=-1, speckle_window=0)      # the raw plane of the search
 LR = dict(speckle_window=0)                           # ... after the left-right check (cost plane)

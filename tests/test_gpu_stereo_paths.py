@@ -1,11 +1,12 @@
 """Every path svs_stereo_compute can take, and every parameter of the block matcher, against the oracle restatement of cv::StereoBM (bit-exact: an integer
-pipeline).  tests/test_gpu_stereo.py runs the reference parameters on frames up to 640 pixels wide with pyramid strides; here the dispatch of csrc/stereo.hip is
+pipeline).  tests/test_gpu_stereo.py runs the reference parameters on frames up to 640 pixels wide with pyramid strides; here the dispatch of csrc/stereo.hip
+(svs_stereo_compute; the kernels are in csrc/stereo_prefilter.inc, stereo_search.inc and stereo_speckle.inc) is
 walked on purpose: the whole-frame speckle filter (rows too wide for strips, short frames, huge windows, and forced beside the strip filter), many small strips,
 the one-row left-right check of rows wider than 2048 pixels, both prefilter kernels, unaligned pointers and three different strides, the tile edges of the
 block-matching kernels, handles reused on changing frames, and the widest row create accepts.
 
-Which path ran is ASSERTED through the context's counters (svs_ctx_get_stat "stereo_*"), and after every call the error mask of the strip filter's bounded
-walks must be 0.  Before a comparison the test checks on the ORACLE's output alone that the case has work for the stage it is about (pixels kept and removed by the
+Which path ran is ASSERTED through the context's counters (svs_ctx_get_stat "stereo_*"), and after every call the error mask of the speckle filter's bounded
+walks must be 0: the strip filter's and, since its union-find is bounded too, the whole-frame filter's.  Before a comparison the test checks on the ORACLE's output alone that the case has work for the stage it is about (pixels kept and removed by the
 speckle filter, pixels removed by the left-right check, small components across strip boundaries): the counts measured when the test was written stand in the
 docstrings.  Inputs: tests/stereo_cases.py (a rendered pair of Scene(7) with uniform integer noise on both images; noise against its own roll)."""
 import ctypes as C
@@ -29,7 +30,7 @@ def _round_up(a, b):
 
 
 def spk_row_bytes(w):
-    """LDS bytes of one strip row (csrc/stereo.hip: spk_row_bytes)"""
+    """LDS bytes of one strip row (csrc/stereo.hip: spk_row_bytes, SPK_NS)"""
     return _round_up(w, 4) * 6 + (320 if (w + 63) // 64 <= 10 else 0)
 
 
@@ -108,7 +109,7 @@ def _run(gpu_ctx, pairs, prm, max_batch=None, **layout):
     with Handle(ctx, w, h, max_batch or len(pairs), prm) as hd:
         got = _compute(gpu_ctx, hd, pairs, **layout)
     after = _stats(ctx)
-    assert _error_mask(ctx) == 0, "a bounded walk of the strip speckle filter gave up"
+    assert _error_mask(ctx) == 0, "a bounded walk of the speckle filter (strip or whole-frame) gave up"
     return got, {k: after[k] - before[k] for k in COUNTERS}
 
 
@@ -157,6 +158,7 @@ def test_frame_filter_natural_fallbacks(gpu_ctx, w, h, amp, window):
     _speckle_work(l, r, prm)
     got, d = _run(gpu_ctx, [(l, r)], prm)
     assert d["stereo_frame_filter_calls"] == 1 and d["stereo_strip_filter_calls"] == 0
+    assert _error_mask(gpu_ctx[0]) == 0, "a bounded union-find walk of the whole-frame filter gave up"
     _assert_equal(got, [(l, r)], prm)
 
 
@@ -193,6 +195,7 @@ def test_frame_filter_forced_against_strip_filter(gpu_ctx, monkeypatch, w, h, am
     monkeypatch.setenv("SVS_STEREO_FRAME_CCL", "1")
     got2, d2 = _run(gpu_ctx, [(l, r)], prm)
     assert d2["stereo_frame_filter_calls"] == 1 and d2["stereo_strip_filter_calls"] == 0
+    assert _error_mask(gpu_ctx[0]) == 0, "a bounded union-find walk of the whole-frame filter gave up"      # (_run has asserted it already: said again where it matters)
     _assert_equal(got2, [(l, r)], prm, "whole-frame filter,")
 
 

@@ -47,7 +47,7 @@ def main(fetch_txt, write_txt, bench_log, df_fetch_txt=None, df_write_txt=None, 
     B = bench["config"]["batch_streams_per_gpu"]
     for key, sub, src in (("fast_score_kernel", "fast_score_kernel", "fast.hip"), ("match_kernel3", "match_kernel3", "match.hip"),
                           ("dense_track_cpu_sem_kernel", "dense_track_cpu_sem_kernel", "dense.hip"), ("motion_only_fused_kernel", "motion_only_fused_kernel", "motion.hip"),
-                          ("stereo_bm_kernel", "stereo_bm_kernel", "stereo.hip"), ("stereo_speckle_strip_kernel", "stereo_speckle_strip_kernel", "stereo.hip"),
+                          ("stereo_bm_kernel", "stereo_bm_kernel", "stereo_search.inc"), ("stereo_speckle_strip_kernel", "stereo_speckle_strip_kernel", "stereo_speckle.inc"),
                           ("pyr_down_u8_kernel", "pyr_down_u8_kernel", "image.hip")):
         k = pick(sub)
         if sub == "dense_track_cpu_sem_kernel":      # the instantiation the bench batch runs by default: grid order by last frame's work (5th argument true), one workgroup per stream
