@@ -581,7 +581,7 @@ __device__ __forceinline__ void wave_lds_fence() { asm volatile("s_waitcnt lgkmc
 constexpr int PIPE_THREADS = 384;
 constexpr int PIPE_LD = 16;     // loader registers per lane and buffer: R*36 <= 64*PIPE_LD  => R <= 28
 
-// reciprocal by hardware estimate + 2 Newton steps.  The value of dense.hip's rcp_rn with the factors of the two correction products the other way round: the
+// reciprocal by hardware estimate + 2 Newton steps.  The value of devutil.h's rcp_rn with the factors of the two correction products the other way round: the
 // compiler keeps that order in the v_fmac_f64 operands of the solve kernels, which were measured with this one (profiles/shared_helpers.md)
 __device__ __forceinline__ double rcp_nr(double d) {
   double x = __builtin_amdgcn_rcp(d);

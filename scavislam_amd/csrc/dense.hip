@@ -157,23 +157,7 @@ __device__ __forceinline__ SampleIn sample_load(const LA &L, int u, int v, int c
   s.prev = L.prev[__umul24((in_range ? v : 0) * 4, L.pstride) + (unsigned)((in_range ? u : 0) * 4)];
   return s;
 }
-// x / z and y / z share their denominator, and the Jacobian needs 1 / z again: one refined reciprocal serves all three.
-// r = RN(1 / b) after two Newton steps on v_rcp_f64 (what the compiler's own division expansion does per quotient), then
-// q = a r, e = a - q b (exact in an FMA), q + e r is the correctly rounded a / b by Markstein's theorem whenever r is the
-// correctly rounded reciprocal -- 3 f64 instructions per quotient instead of 11.  The pass is f64-issue bound
-// (~200 VALU instructions per sample, profiles/r1_notes.md), so this is ~10 % of its time.  Non-finite / zero b give
-// NaN or inf exactly where the IEEE quotient would be inf or NaN: those samples fail the |uv| < 1e9 gate either way.
-__device__ __forceinline__ double rcp_rn(double b) {
-  double r = __builtin_amdgcn_rcp(b);
-  double e = __builtin_fma(-b, r, 1.0);
-  r = __builtin_fma(e, r, r);
-  e = __builtin_fma(-b, r, 1.0);
-  return __builtin_fma(e, r, r);
-}
-__device__ __forceinline__ double div_rn(double a, double b, double r) {
-  const double q = a * r;
-  return __builtin_fma(__builtin_fma(-q, b, a), r, q);
-}
+// (rcp_rn / div_rn, one refined reciprocal for x / z, y / z and the Jacobian: devutil.h)
 
 // TM (term mode): what happens to the sample's float term res * res of the reference's `chi2 += res * res` -- 0: nothing; 1: stored at t_out (if not null);
 // 2: stored past the caches (sibling workgroups of the stream will read it: MULTI)

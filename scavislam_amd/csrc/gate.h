@@ -12,9 +12,14 @@ __device__ __forceinline__ void mo_residual(const double *T, const svs_match_res
   double x, y, z;
   pose_act(T, q[0], q[1], q[2], x, y, z);
   const double fl = cam.f;
-  f[0] = o.obs[0] - (x / z * fl + cam.cx);
-  f[1] = o.obs[1] - (y / z * fl + cam.cy);
-  f[2] = o.obs[2] - ((x - cam.b) / z * fl + cam.cx);
+  // the three quotients share z: one checked reciprocal (div_rn_guarded, devutil.h) -- the bits of x / z, y / z, (x - b) / z for every operand, which is what lets
+  // register.hip's gate and the loop-closure check keep this one definition
+  const double num[3] = {x, y, x - cam.b};
+  double p[3];
+  div_rn_guarded(num, z, p);
+  f[0] = o.obs[0] - (p[0] * fl + cam.cx);
+  f[1] = o.obs[1] - (p[1] * fl + cam.cy);
+  f[2] = o.obs[2] - (p[2] * fl + cam.cx);
   if (JAC) {
     const double ibz = 1. / z, ibz2 = 1. / (z * z);
     const double A = -fl * ibz, B = -fl * ibz, C = fl * x * ibz2, D = fl * y * ibz2, E = fl * (x - cam.b) * ibz2;

@@ -2,7 +2,7 @@
 // (PoseOptimizer::calcFastMotionOnly), the reprojection gate of StereoFrontend::processMatchedPoints and the dense point clouds of the
 // new pose (DenseTracker::computeDensePointCloudCpu, dense_tracking.cpp:393-423) -- each as a launch of its own, and all three fused in
 // ONE launch per frame batch (motion_only_fused_kernel<true>: gate and clouds as the tail of a stream's refinement workgroup).
-// The fused tail and the stand-alone kernels share their device functions (gate_stream, cloud_TQ, cloud_sample): identical bits.
+// The fused tail and the stand-alone kernels share their device functions (gate_stream, cloud_TQ, cloud_disp, cloud_point): identical bits.
 #include "common.h"
 #include "gate.h"
 #include "lm6.h"
@@ -34,21 +34,62 @@ __device__ __forceinline__ void cloud_TQ(const double (&T)[12], const svs_cam &c
       TQ[4 * r + c] = s;
     }
 }
-// quarter-grid sample i of one stream's level: disp = the stream's level-0 disparity image, cloud = the stream's cloud of this level
-__device__ __forceinline__ void cloud_sample(const float *__restrict__ disp, int ds, int cw, int level, const double (&TQ)[16], int i, float *__restrict__ cloud) {
-  const int u = i % cw, v = i / cw;
+// quarter-grid sample (u, v) of one stream's level: disp = the stream's level-0 disparity image.  The load and the arithmetic are two functions so that the fused
+// tail can request the disparities of later samples before it works on this one; every caller runs these two: identical bits.
+__device__ __forceinline__ float cloud_disp(const float *__restrict__ disp, int ds, int level, int u, int v) {
+  return disp[(size_t)((v * 4) << level) * ds + ((u * 4) << level)];
+}
+__device__ __forceinline__ float4 cloud_point(float disp_uv, int level, const double (&TQ)[16], int u, int v) {
   const double inv_factor = 1.0 / (double)(1 << level);
-  const float d = (float)(disp[(size_t)((v * 4) << level) * ds + ((u * 4) << level)] * inv_factor);
-  float4 o;
-  if (d <= 0) o = make_float4(0.f, 0.f, 0.f, -1.f);
-  else {
-    const double q[4] = {(double)(u * 4), (double)(v * 4), (double)d, 1.0};
-    double r[4];
+  const float d = (float)(disp_uv * inv_factor);
+  if (d <= 0) return make_float4(0.f, 0.f, 0.f, -1.f);
+  const double q[4] = {(double)(u * 4), (double)(v * 4), (double)d, 1.0};
+  double r[4];
 #pragma unroll
-    for (int k = 0; k < 4; ++k) r[k] = TQ[4 * k] * q[0] + TQ[4 * k + 1] * q[1] + TQ[4 * k + 2] * q[2] + TQ[4 * k + 3] * q[3];
-    o = make_float4((float)(r[0] / r[3]), (float)(r[1] / r[3]), (float)(r[2] / r[3]), 1.f);
+  for (int k = 0; k < 4; ++k) r[k] = TQ[4 * k] * q[0] + TQ[4 * k + 1] * q[1] + TQ[4 * k + 2] * q[2] + TQ[4 * k + 3] * q[3];
+  // r[0] / r[3], r[1] / r[3], r[2] / r[3]: one reciprocal and three exact quotients (devutil.h: the bits of the three divisions, 19 f64 instructions instead of 3 x 13)
+  const double num[3] = {r[0], r[1], r[2]};
+  double p[3];
+  div_rn_guarded(num, r[3], p);
+  return make_float4((float)p[0], (float)p[1], (float)p[2], 1.f);
+}
+// sample i = v cw + u of the level (the stand-alone kernels: one sample per lane, one division per lane)
+__device__ __forceinline__ void cloud_sample(const float *__restrict__ disp, int ds, int cw, int level, const double (&TQ)[16], int i, float *__restrict__ cloud) {
+  const int v = i / cw, u = i - v * cw;
+  reinterpret_cast<float4 *>(cloud)[i] = cloud_point(cloud_disp(disp, ds, level, u, v), level, TQ, u, v);
+}
+// One level of one stream's cloud by the NT lanes of its workgroup (the fused tail).  A lane's samples are NT apart: their grid position is carried from trip to trip
+// (one division per lane and level), and the disparities of the next PF samples are in flight while this one's point is formed -- the stream's disparity image
+// is in no cache, and with one load per trip and nothing beside it every trip waited a whole memory round trip.
+constexpr int CLOUD_PF = 4;      // as measured (profiles/refinement_tail.md: 2, 4 and 8 are within each other's spread; the tail is then bound by the device's memory traffic)
+template <int NT, int PF>
+__device__ __forceinline__ void cloud_level_sweep(const float *__restrict__ disp, int ds, const svs_cam &cam, int level, const double (&TQ)[16], float *__restrict__ cloud,
+                                                  int tid) {
+  const int cw = cam.w / 4, n_px = cw * (cam.h / 4);
+  const int sv = NT / cw, su = NT - sv * cw;                 // one trip further: (u + su, v + sv), one carry at most (su < cw)
+  int v = tid / cw, u = tid - v * cw;                        // the sample this trip works on
+  int pv = v, pu = u, pi = tid;                              // the sample whose disparity is requested next: PF trips ahead
+  float ahead[PF];
+#pragma unroll
+  for (int k = 0; k < PF; ++k) {
+    const bool in = pi < n_px;
+    ahead[k] = cloud_disp(disp, ds, level, in ? pu : 0, in ? pv : 0);
+    pu += su; pv += sv; pi += NT;
+    if (pu >= cw) { pu -= cw; ++pv; }
   }
-  reinterpret_cast<float4 *>(cloud)[i] = o;
+  for (int i = tid; i < n_px; i += PF * NT) {
+#pragma unroll
+    for (int k = 0; k < PF; ++k) {
+      const float d = ahead[k];
+      const bool in = pi < n_px;
+      ahead[k] = cloud_disp(disp, ds, level, in ? pu : 0, in ? pv : 0);      // (past the end: the image's first sample, never used)
+      pu += su; pv += sv; pi += NT;
+      if (pu >= cw) { pu -= cw; ++pv; }
+      if (i + k * NT < n_px) reinterpret_cast<float4 *>(cloud)[i + k * NT] = cloud_point(d, level, TQ, u, v);
+      u += su; v += sv;
+      if (u >= cw) { u -= cw; ++v; }
+    }
+  }
 }
 __global__ __launch_bounds__(256) void pointcloud_cpu_sem_kernel(const float *__restrict__ disp, int ds, size_t disp_b, svs_cam cam,
                                                                  int level, const double *__restrict__ Tarr,
@@ -415,16 +456,31 @@ __device__ __forceinline__ void gate_stream(const svs_match_result *__restrict__
   const int third_w = (int)(cam.w * third), third_h = (int)(cam.h * third);
   const int tt_w = (int)(cam.w * 2 * third), tt_h = (int)(cam.h * 2 * third);
   double len = 0;
+  // a lane's records are 256 apart; the next one (the matcher's record and the point's anchor level: two round trips to memory that depend on nothing here) is
+  // requested before this one's arithmetic
+  struct GateIn { svs_match_result r; int level; };
+  auto gate_load = [&](int i) {
+    GateIn in;
+    const int j = i < n ? i : 0;                                 // (past the end: record 0, marked as no match)
+    in.r = res[j];
+    in.level = pts[j].anchor_level;
+    if (i >= n) in.r.status = 1;
+    return in;
+  };
+  GateIn nxt{};
+  if (n > 0 && tid < 256) nxt = gate_load(tid);
   for (int i = tid; i < n && tid < 256; i += 256) {
     svs_gated_point g{};
-    if (res[i].status == 0) {
+    const GateIn cur = nxt;
+    nxt = gate_load(i + 256);
+    if (cur.r.status == 0) {
       atomicAdd(&s_cnt[17], 1);
       double d[3];
-      mo_residual<false>(T, res[i], cam, d, nullptr);          // uvu - se3xyz_stereo_.map(T_cur_from_actkey_, point)
-      const int level = pts[i].anchor_level;
+      mo_residual<false>(T, cur.r, cam, d, nullptr);           // uvu - se3xyz_stereo_.map(T_cur_from_actkey_, point)
+      const int level = cur.level;
       const int factor = 1 << level;                             // zeroFromPyr_i(1, anchor_level)
       if (SVS_GATE_PASSES(d, factor, mre)) {
-        const double *uvu = res[i].obs, *q = res[i].xyz_actkey;
+        const double *uvu = cur.r.obs, *q = cur.r.xyz_actkey;
         const int i2 = uvu[0] < half_w ? 0 : 1, j2 = uvu[1] < half_h ? 0 : 1;
         const int i3 = uvu[0] < third_w ? 0 : (uvu[0] < tt_w ? 1 : 2), j3 = uvu[1] < third_h ? 0 : (uvu[1] < tt_h ? 1 : 2);
         atomicAdd(&s_cnt[i2 * 2 + j2], 1);
@@ -435,8 +491,11 @@ __device__ __forceinline__ void gate_stream(const svs_match_result *__restrict__
         g.accepted = 1;
         g.is_new = i < n_new ? 1 : 0;
         g.uv_pyr[0] = uvu[0] * inv; g.uv_pyr[1] = uvu[1] * inv;
-        g.curkey_uv_pyr[0] = (q[0] / q[2] * cam.f + cam.cx) * inv;
-        g.curkey_uv_pyr[1] = (q[1] / q[2] * cam.f + cam.cy) * inv;
+        const double num[2] = {q[0], q[1]};
+        double p[2];
+        div_rn_guarded(num, q[2], p);                            // q[0] / q[2], q[1] / q[2]
+        g.curkey_uv_pyr[0] = (p[0] * cam.f + cam.cx) * inv;
+        g.curkey_uv_pyr[1] = (p[1] * cam.f + cam.cy) * inv;
         const double dx = g.uv_pyr[0] - g.curkey_uv_pyr[0], dy = g.uv_pyr[1] - g.curkey_uv_pyr[1];
         len += sqrt(dx * dx + dy * dy);
       }
@@ -607,10 +666,9 @@ __global__ __launch_bounds__(MO2_THREADS) void motion_only_fused_kernel(const sv
     for (int l = 0; l < 3; ++l) {
       double TQ[16];
       cloud_TQ(T, Q.cams[l], TQ);
-      const int cw = Q.cams[l].w / 4, n_px = cw * (Q.cams[l].h / 4);
       const float *disp = Q.disp + slot * Q.disp_b;
       float *cloud = Q.cloud[l] + slot * Q.cloud_b[l];
-      for (int i = tid; i < n_px; i += MO2_THREADS) cloud_sample(disp, Q.ds, cw, l, TQ, i, cloud);
+      cloud_level_sweep<MO2_THREADS, CLOUD_PF>(disp, Q.ds, Q.cams[l], l, TQ, cloud, tid);
     }
   }
 }
