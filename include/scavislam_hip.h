@@ -992,6 +992,36 @@ int svs_map_set_window(svs_map *map, int n, const int32_t *h_kf_ids);
 /* host-side counts (each optional); n_observations counts distinct pairs */
 int svs_map_info(svs_map *map, int32_t *n_keyframes, int32_t *n_points, int32_t *n_observations);
 
+/* ---- back end: the double window's BA problem built from the map (SlamGraph::prepareForOptimization / optimize, slam_graph.cpp:288-355).
+   svs_map_add_measured_observations is svs_map_add_observations (the same refusals, all or nothing, asynchronous, one staged upload, a pair already present or
+   twice in the call ignored) for a caller that also wants to optimise: per NEW pair one svs_ba_edge record joins a device array in log order, "the measured
+   store": obs = h_center[i] (feat.center), info = (s * s, s * s, 0.333 * 0.333) with s = 1 / 2^h_level[i] (slam_graph.cpp:1010-1015, formed on the host while
+   staging), point / pose = the ids, anchor unused.  A level outside 0 .. SVS_NUM_PYR_LEVELS - 1: SVS_ERR_INVALID.  svs_map_measured_info (each optional)
+   counts the pairs that came with a measurement and those that came through svs_map_add_observations without one. */
+int svs_map_add_measured_observations(svs_map *map, int n, const int32_t *h_point_ids, const int32_t *h_kf_ids, const double *h_center /* [n][3] */,
+                                      const int32_t *h_level /* [n] */);
+int svs_map_measured_info(svs_map *map, int32_t *n_measured, int32_t *n_unmeasured);
+/* computeActivePointsAndExtendOuterWindow (slam_graph.cpp:599-663) on the device.  The caller keeps computeInitialDoubleWin and the edge_table_: it passes W0 =
+   double_window_ before the extension (ids, types 0 INNER / 1 OUTER, in its order) and the edge_table_ entries with at least one end in an INNER keyframe of W0,
+   in either orientation.  The reference extends double_window_ only at the end (:662), so its result is a statement about sets:
+     1. point p is ACTIVE iff some INNER keyframe F of W0 has p in its feature_table and either anchor(p) is in W0 or (F, anchor(p)) is among the pairs.  A point
+        whose anchor enters the window only through another point, none of whose own INNER observers has a pair to that anchor, is not active;
+     2. extension = { anchor(p) : p active, anchor(p) not in W0 }, typed OUTER;
+     3. final window = W0 in the caller's order, then the extension in ASCENDING ID (the reference's order is that of an unordered_map);
+     4. active list in ASCENDING POINT ID.
+   n_edges_bound = the sum of the active points' observer-row lengths (an upper bound of the window's edges).  set_window_flags != 0 leaves exactly the final
+   window with SVS_REG_KF_IN_WINDOW, as svs_map_set_window on it would.  h_window_ids / h_window_type (optional, [window_cap]): the final window, -1 behind it.
+   BLOCKING: one staged upload (ids, types, pairs), at most the CSR rebuild plus two launches (one workgroup per INNER keyframe marks; ascending lists by
+   popcount prefixes, no atomic decides an order), one download.
+   SVS_ERR_INVALID before anything is uploaded: an unknown id, an id twice in W0, a type other than 0 / 1, no INNER keyframe, a pair naming an unknown keyframe,
+   or a map that holds a pair without a measurement.  SVS_ERR_CAPACITY: n0 > window_cap, or window_cap > 256 (the solve's limit).  A final window above
+   window_cap is only known on the device: SVS_OK with n_window = the count found and n_active = -1; nothing is prepared and the flags are untouched.
+   The prepared window stays valid until the next svs_map_add_points / _add_observations / _add_measured_observations that changes the map, or the next
+   svs_map_prepare_window; svs_map_set_poses / svs_map_set_points do NOT invalidate it (reinitializePoses, :665-725, runs between this step and optimize). */
+typedef struct { int32_t n_window, n_initial, n_active, n_edges_bound; } svs_map_window_result;
+int svs_map_prepare_window(svs_map *map, int n0, const int32_t *h_kf_ids, const int32_t *h_kf_type, int n_pairs, const int32_t *h_edge_pairs /* [n_pairs][2] */,
+                           int set_window_flags, int window_cap, svs_map_window_result *h_res, int32_t *h_window_ids, int32_t *h_window_type);
+
 /* A request by ids.  The device builds the svs_reg_request of the stateless call from the map:
      1. source points.  SVS_REG_LOCAL: every point with at least one observation in a keyframe of h_walk_kf that is not the root and not in h_direct_kf
         (:481-497; the root is a direct neighbour, :433-449).  SVS_REG_LOOP: every point observed by h_walk_kf[0], the query keyframe (:853-858).  Each point
@@ -1142,6 +1172,19 @@ int svs_ba_optimize(svs_ba *ba, svs_allreduce_fn allreduce, void *user, svs_ba_s
 int svs_ba_optimize_batch(svs_ba *const *bas, int n, svs_ba_stats *stats);
 /* restoreDataFromG2o (slam_graph.cpp:1035-1058): poses [P][12], psi [L][3] */
 int svs_ba_get_state(svs_ba *ba, double *h_poses, double *h_psi);
+/* copyDataToG2o device to device: the window svs_map_prepare_window left in `map` becomes this handle's problem.  Poses (T_me_from_world of the final window, in
+   its order) and psi = (x / z, y / z, 1 / z) of xyz_anchor (invert_depth, maths_utils.h:66-69; the active points in ascending id) are read from the map AT THIS
+   MOMENT; the edge list is assembled by the kernels of svs_ba_window_update from the map's measured store -- no observation record is copied or uploaded -- with
+   that call's filter (slam_graph.cpp:1001-1006): the observations of the active points in keyframes of the final window.  The observer set is the map's
+   feature_table pairs; the reference iterates vis_set, which addNewPointsToMap / addNewObsToOldPoints keep equal to them: a caller whose vis_set differs must
+   not use this call.  Only the constraints cross the link (h_cons: frame IDS of the final window, copyContraintsToG2o stays with the caller).  State comes back
+   through svs_ba_get_state in the order of the final window / the active list.  The handle's own observation store (svs_ba_window_update) is not touched.
+   SVS_ERR_INVALID: no valid prepared window, handles of two contexts, a handle with a communicator, a constraint outside the window -- each before the handle is
+   touched: its problem is then as it was. */
+int svs_ba_window_from_map(svs_ba *ba, svs_map *map, int C, const svs_ba_constraint *h_cons, const svs_cam *cam, const svs_ba_params *prm);
+/* restoreDataFromG2o on the device (slam_graph.cpp:1035-1058), one launch, ASYNCHRONOUS: window pose i to the map's keyframe of its id, xyz_anchor =
+   invert_depth(psi) to the map's point of its id.  Valid only while the handle's problem is the one svs_ba_window_from_map built from this map's prepared window */
+int svs_ba_store_to_map(svs_ba *ba, svs_map *map);
 /* landmark-sharded operation over a library-owned communicator: svs_ba_optimize(ba, NULL, NULL, stats) then all-reduces the
    packed reduced system and the two trial sums of every LM trial (32 doubles: each sum is kept in 16 partial slots) (and, once per problem, the co-visibility pattern) with
    ncclAllReduce on the ctx stream.  comm == NULL detaches.  A non-NULL `allreduce` argument of svs_ba_optimize takes precedence
@@ -1158,6 +1201,9 @@ int svs_ba_set_option(svs_ba *ba, const char *name, int value);
 int svs_ba_reset_state(svs_ba *ba, const double *h_poses, const double *h_psi);
 int svs_ba_reduced_system(svs_ba *ba, double lambda, double *h_Hred /* (6P)^2 full sym */,
                           double *h_bred /* 6P */, double *h_chi2);
+/* the assembled edge list in slot order (wide | anchor | point | pose), window INDICES in .point / .pose / .anchor, after any of the three ways to set a
+   problem; *n = its length, h_edges == NULL returns only that (blocking) */
+int svs_ba_window_edges(svs_ba *ba, int32_t *n, svs_ba_edge *h_edges);
 /* the layout the next Schur and back-substitution launches take: waves per workgroup (4..8; the one svs_ba_set_problem laid the wave chunks out
    for, option "nw", or the smallest that gets the grid down to one workgroup per CU) and whether the Schur pass accumulates in the big LDS
    pool (one workgroup per CU, 22-pose window; always at 5..8 waves) or the small one (two per CU, 16 poses: four waves with more workgroups than CUs) */

@@ -895,6 +895,27 @@ class BackendMap {
   bool addObservations(const std::vector<int32_t> &point_ids, const std::vector<int32_t> &kf_ids) {
     return ok_ && point_ids.size() == kf_ids.size() && ctx_.check(svs_map_add_observations(map_, (int)point_ids.size(), point_ids.data(), kf_ids.data()));
   }
+  // the same with the ImageFeature of each pair (feat.center [n][3], feat.level): what a caller hands over that also optimises through the map
+  // (SlamGraphBA::copyDataFromMap); a map fed this way only can form a window
+  bool addObservations(const std::vector<int32_t> &point_ids, const std::vector<int32_t> &kf_ids, const std::vector<double> &center3, const std::vector<int32_t> &level) {
+    return ok_ && point_ids.size() == kf_ids.size() && center3.size() == 3 * point_ids.size() && level.size() == point_ids.size() &&
+           ctx_.check(svs_map_add_measured_observations(map_, (int)point_ids.size(), point_ids.data(), kf_ids.data(), center3.data(), level.data()));
+  }
+  // computeActivePointsAndExtendOuterWindow (slam_graph.cpp:599-663) on the device, behind the caller's computeInitialDoubleWin: window / types (0 INNER, 1 OUTER)
+  // are double_window_ before the extension, edge_pairs (id, id, ...) the edge_table_ entries with an end in an INNER keyframe.  On return window and types hold
+  // the final window (W0, then the extension ascending and OUTER) and the map's window flags name exactly it; *n_active: the active points.  false: refused, or
+  // the final window exceeds 256 keyframes (window and types are left as they were)
+  bool prepareForOptimization(std::vector<int32_t> *window, std::vector<int32_t> *types, const std::vector<int32_t> &edge_pairs, int *n_active = nullptr) {
+    if (!ok_ || window->size() != types->size() || edge_pairs.size() % 2) return false;
+    svs_map_window_result r;
+    std::vector<int32_t> ids(256), ty(256);
+    if (!ctx_.check(svs_map_prepare_window(map_, (int)window->size(), window->data(), types->data(), (int)(edge_pairs.size() / 2), edge_pairs.data(), 1, 256, &r,
+                                           ids.data(), ty.data()))) return false;
+    if (r.n_active < 0) return false;
+    window->assign(ids.begin(), ids.begin() + r.n_window); types->assign(ty.begin(), ty.begin() + r.n_window);
+    if (n_active) *n_active = r.n_active;
+    return true;
+  }
   bool setPoses(const std::vector<int32_t> &kf_ids, const std::vector<double> &poses12) {
     return ok_ && poses12.size() == 12 * kf_ids.size() && ctx_.check(svs_map_set_poses(map_, (int)kf_ids.size(), kf_ids.data(), poses12.data()));
   }
@@ -1198,6 +1219,23 @@ class SlamGraphBA {
     return true;
   }
   bool windowReset() { return ctx_.check(svs_ba_window_reset(ba_)); }
+  // ---- the window BackendMap::prepareForOptimization left in the map, device to device (svs_ba_window_from_map / svs_ba_store_to_map) ----
+  // copyDataToG2o: poses and points are read from the map now, the edges come from its measured observations; only the constraints (both directions, frame
+  // ids of the final window, as optimizeWindow takes them) are uploaded.  Then optimize() below and restoreDataToMap
+  bool copyDataFromMap(BackendMap &map, const OptParams &opt, const svs_cam &cam, const std::vector<ConstraintById> &constraints) {
+    std::vector<svs_ba_constraint> ec(constraints.size());
+    for (size_t k = 0; k < constraints.size(); ++k) {
+      svs_ba_constraint &r = ec[k];
+      std::memcpy(r.T_21, constraints[k].T_2_from_1, sizeof r.T_21);
+      std::memcpy(r.info, constraints[k].Lambda_2_from_1, sizeof r.info);
+      r.pose1 = constraints[k].pose_id_1; r.pose2 = constraints[k].pose_id_2;
+    }
+    svs_ba_params prm = params(opt, false);
+    return ctx_.check(svs_ba_window_from_map(ba_, map.get(), (int)ec.size(), ec.data(), &cam, &prm));
+  }
+  bool optimize(svs_ba_stats *stats = nullptr) { return ctx_.check(svs_ba_optimize(ba_, nullptr, nullptr, stats)); }
+  // restoreDataFromG2o on the device: one launch, asynchronous
+  bool restoreDataToMap(BackendMap &map) { return ctx_.check(svs_ba_store_to_map(ba_, map.get())); }
   // landmark-sharded operation: this rank passes only ITS landmarks' edges to optimize() (pose terms on exactly one rank: add_pose_terms)
   bool attach(const Communicator *comm) { return ctx_.check(svs_ba_set_comm(ba_, comm ? comm->get() : nullptr)); }
   svs_ba *get() const { return ba_; }

@@ -179,6 +179,30 @@ class SlamGraphOptimizer:
             self.h, self.P, pose_ids.ctypes.data, poses.ctypes.data, self.L, point_ids.ctypes.data, psi.ctypes.data, anchor_pose_ids.ctypes.data,
             len(new_obs), new_obs.ctypes.data, len(cons), cons.ctypes.data, C.byref(camc), C.byref(self.prm)))
 
+    def windowFromMap(self, resident_map, cons, cam, prm=None):
+        """svs_ba_window_from_map: copyDataToG2o device to device.  The window resident_map.prepare_window left in the map becomes this optimizer's problem:
+        poses and psi are read from the map now, the edges are assembled from the map's measured observations, only cons (BA_CONSTRAINT_DTYPE with frame ids
+        of the final window) is uploaded.  restoreDataFromG2o then returns the final window's poses and the active points' psi in the map's order."""
+        cons = np.ascontiguousarray(cons if cons is not None else np.zeros(0, BA_CONSTRAINT_DTYPE), BA_CONSTRAINT_DTYPE)
+        prm = prm or BaParams.reference_defaults()
+        camc = cam if isinstance(cam, Cam) else Cam(cam["f"], cam["cx"], cam["cy"], cam["b"], cam["w"], cam["h"])
+        self.ctx.check(self.ctx.lib.svs_ba_window_from_map(self.h, resident_map.h, len(cons), cons.ctypes.data if len(cons) else None, C.byref(camc), C.byref(prm)))
+        self.prm = prm
+        self.P, self.L = resident_map.window_shape
+
+    def storeToMap(self, resident_map):
+        """svs_ba_store_to_map: restoreDataFromG2o on the device -- the window's poses and invert_depth(psi) go back into the map (one launch, asynchronous)"""
+        self.ctx.check(self.ctx.lib.svs_ba_store_to_map(self.h, resident_map.h))
+
+    def window_edges(self):
+        """svs_ba_window_edges: the assembled edge list in slot order (BA_EDGE_DTYPE, window indices in point / pose / anchor)"""
+        n = C.c_int32()
+        self.ctx.check(self.ctx.lib.svs_ba_window_edges(self.h, C.byref(n), None))
+        e = np.zeros(n.value, BA_EDGE_DTYPE)
+        if n.value:
+            self.ctx.check(self.ctx.lib.svs_ba_window_edges(self.h, C.byref(n), e.ctypes.data))
+        return e
+
     def windowReset(self):
         self.ctx.check(self.ctx.lib.svs_ba_window_reset(self.h))
 

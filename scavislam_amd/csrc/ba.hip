@@ -19,6 +19,7 @@
 //    replicated (deterministic, no broadcast).
 #include "common.h"
 #include "pose.h"
+#include "ba_map.h"
 #include <climits>
 #include <algorithm>
 #include <cmath>
@@ -146,7 +147,8 @@ struct svs_ba {
   svs_ctx *ctx = nullptr;
   BaOptions opt;
   svs_comm *comm = nullptr;             // library-owned collective of sharded runs (svs_ba_set_comm)
-  bool problem_valid = false;           // set by a COMPLETED svs_ba_set_problem / svs_ba_window_update; every other entry point requires it
+  bool problem_valid = false;           // set by a COMPLETED svs_ba_set_problem / svs_ba_window_update / svs_ba_window_from_map; every other entry point requires it
+  uint64_t from_map_serial = 0;         // the prepared window of a map this problem was built from (svs_ba_window_from_map; ba_map.h), 0: none
   // ---- persistent window (svs_ba_window_*): every observation handed over since the last reset stays on the device ----
   DevBuf<svs_ba_edge> w_store; size_t w_n = 0;                         // observation store, ids in .point / .pose, arrival order
   DevBuf<int> w_pose_tab, w_point_tab;                                  // id -> window index (-1: not in the window), as many entries as the block holds
@@ -363,6 +365,7 @@ extern "C" int svs_ba_set_problem(svs_ba *ba, int P, const double *h_poses, int 
   }
   // a call that fails half-way must not leave new sizes next to old buffers behind: the handle is unusable until a call completes
   ba->problem_valid = false;
+  ba->from_map_serial = 0;
   if (P > SOLVE_MAX_P) { ctx->err = "svs_ba: P > 256 poses not supported by the single-workgroup solve yet"; return SVS_ERR_UNSUPPORTED; }
   SVS_HIP(ctx, hipStreamSynchronize(ctx->stream));
   ba->h_stage_used = 0;

@@ -1,0 +1,26 @@
+// ba_map.h -- what ba.hip and map.hip share: the window svs_map_prepare_window leaves in the device-resident map (map.hip), as svs_ba_window_from_map /
+// svs_ba_store_to_map (ba_window.inc) read and write it.  Neither translation unit reaches into the other's handle.
+#pragma once
+#include "common.h"
+
+// the prepared window (device pointers but for h_window_ids): the pieces of the block win_unpack_kernel reads
+struct MapWindowView {
+  int P, L;                            // final window, active points
+  const int32_t *window_ids;           // [P]  W0 in the caller's order, then the extension ascending
+  const int32_t *h_window_ids;         // the same on the host (the constraints come by frame id)
+  const int32_t *active_ids;           // [L]  ascending
+  const int32_t *anchor_ids;           // [L]  keyframe ids
+  const double *poses, *psi;           // [P][12], [L][3]: filled by svs_map_window_view's launch
+  const svs_ba_edge *store; size_t n_store;      // the measured store: ids in .point / .pose, log order
+  int kf_hi, pt_hi;                    // every id of the store is below these
+  uint64_t serial;                     // of this prepare (no two prepares of a process share one)
+};
+
+svs_ctx *svs_map_ctx(svs_map *map);
+// SVS_ERR_INVALID without a valid prepared window (nothing enqueued); else one launch on the context's stream re-reads the window's poses and psi = (x / z,
+// y / z, 1 / z) from the map into the block
+int svs_map_window_view(svs_map *map, MapWindowView *out);
+// is `serial` the map's valid prepared window
+bool svs_map_window_is(const svs_map *map, uint64_t serial);
+// one launch, asynchronous: d_poses [P][12] to the keyframes of the prepared window, invert_depth(d_psi [L][3]) to its points
+int svs_map_window_store(svs_map *map, const double *d_poses, const double *d_psi);

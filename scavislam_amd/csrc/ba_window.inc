@@ -227,6 +227,16 @@ __global__ __launch_bounds__(WIN_TILE) void win_keep_move_kernel(const svs_ba_ed
 }
 }  // namespace
 
+// where a window's definition lies on the device, and the store its edges are filtered from
+struct WinSrc {
+  const int *pids, *lids, *aids; const double *poses, *psi, *obs, *cons;
+  int n_new; svs_ba_edge *store_tail;      // the new observations (staged at `obs`) and where they join the store; none: 0
+  const svs_ba_edge *store; size_t N;
+  int max_pose_id, max_point_id;           // the id -> index tables hold at least these ids (the store's records are range-checked against the tables)
+};
+static int window_assemble(svs_ba *ba, int P, int L, int C, const WinSrc &S, const svs_cam *cam, const svs_ba_params *prm,
+                           std::chrono::steady_clock::time_point t_0, std::chrono::steady_clock::time_point t_s);
+
 extern "C" int svs_ba_window_reset(svs_ba *ba) {
   if (!ba) return SVS_ERR_INVALID;
   ba->w_n = 0;
@@ -296,7 +306,7 @@ static int window_update_impl(svs_ba *ba, int P, const int32_t *h_pose_ids, cons
   SVS_REQUIRE(ctx, P >= 1 && L >= 0 && n_new >= 0 && C >= 0);
   SVS_REQUIRE(ctx, !ba->comm);                        // single-GPU path (a sharded window goes through svs_ba_set_problem)
   SVS_DEVICE(ctx);
-  ba->problem_valid = false;
+  ba->problem_valid = false; ba->from_map_serial = 0;
   if (P > SOLVE_MAX_P) { ctx->err = "svs_ba: P > 256 poses not supported by the single-workgroup solve yet"; return SVS_ERR_UNSUPPORTED; }
   auto t_0 = std::chrono::steady_clock::now();
   // ---- host: ranges of the ids, constraints by index -------------------------------------------------------------------------
@@ -377,8 +387,25 @@ static int window_update_impl(svs_ba *ba, int P, const int32_t *h_pose_ids, cons
   const size_t w_n_old = ba->w_n;
   SVS_HIP(ctx, win_grow(ba->w_store, (ba->w_n + (size_t)n_new) * sizeof(svs_ba_edge), ba->w_n * sizeof(svs_ba_edge)));
   ba->w_n += (size_t)n_new;
-  const size_t N = ba->w_n;
-  SVS_REQUIRE(ctx, N < (size_t)INT_MAX - 1);
+  SVS_REQUIRE(ctx, ba->w_n < (size_t)INT_MAX - 1);
+  char *IN = static_cast<char *>(ba->w_in.get());
+  WinSrc S;
+  S.pids = (const int *)(IN + i_pids); S.lids = (const int *)(IN + i_lids); S.aids = (const int *)(IN + i_aids);
+  S.poses = (const double *)(IN + i_poses); S.psi = (const double *)(IN + i_psi); S.obs = (const double *)(IN + i_obs); S.cons = (const double *)(IN + i_cons);
+  S.n_new = n_new; S.store_tail = ba->w_store + w_n_old; S.store = ba->w_store; S.N = ba->w_n;
+  S.max_pose_id = max_pose_id; S.max_point_id = max_point_id;
+  return window_assemble(ba, P, L, C, S, cam, prm, t_0, t_s);
+}
+
+// The second half of every way to bring a window by ids: id -> index tables, the edge list in slot order filtered out of `S.store`, the co-visibility pattern, the one
+// read-back, wave chunks and envelope.  ba->w_cons_idx holds the constraints by window index; the stream has been drained and the staging area reset by the caller.
+static int window_assemble(svs_ba *ba, int P, int L, int C, const WinSrc &S, const svs_cam *cam, const svs_ba_params *prm,
+                           std::chrono::steady_clock::time_point t_0, std::chrono::steady_clock::time_point t_s) {
+  svs_ctx *ctx = ba->ctx;
+  const std::vector<svs_ba_constraint> &cons_idx = ba->w_cons_idx;
+  const size_t N = S.N;
+  const int n_new = S.n_new, max_pose_id = S.max_pose_id, max_point_id = S.max_point_id;
+  auto win_grow = [](auto &b, size_t bytes, size_t keep_bytes = 0) { return b.reserve_keep(bytes, bytes + bytes / 2 + 4096, keep_bytes); };
   // ---- id tables ---------------------------------------------------------------------------------------------------------------
   SVS_HIP(ctx, win_grow(ba->w_pose_tab, ((size_t)max_pose_id + 1) * sizeof(int)));
   SVS_HIP(ctx, win_grow(ba->w_point_tab, ((size_t)max_point_id + 2) * sizeof(int)));
@@ -394,7 +421,6 @@ static int window_update_impl(svs_ba *ba, int P, const int32_t *h_pose_ids, cons
                o_eoff = take(sizeof(int) * (size_t)std::max(L, 1)), o_tile = take(sizeof(int) * 2 * n_tiles * 2 * (size_t)P), o_lms = take(4 * ((size_t)L + 2));
   SVS_HIP(ctx, win_grow(ba->w_work, off));
   char *W = static_cast<char *>(ba->w_work.get());
-  char *IN = static_cast<char *>(ba->w_in.get());
   int *d_aidx = (int *)(W + o_aidx), *d_count = (int *)(W + o_count);
   unsigned long long *d_mask = (unsigned long long *)(W + o_mask);
   int *d_eoff = (int *)(W + o_eoff), *d_tile = (int *)(W + o_tile), *d_lms = (int *)(W + o_lms), *d_lml = (int *)(W + o_lml);
@@ -418,22 +444,21 @@ static int window_update_impl(svs_ba *ba, int P, const int32_t *h_pose_ids, cons
   }
   {
     WinIn A;
-    A.pids = (const int *)(IN + i_pids); A.lids = (const int *)(IN + i_lids); A.poses = (const double *)(IN + i_poses); A.psi = (const double *)(IN + i_psi);
-    A.obs = (const double *)(IN + i_obs); A.cons = (const double *)(IN + i_cons);
+    A.pids = S.pids; A.lids = S.lids; A.poses = S.poses; A.psi = S.psi; A.obs = S.obs; A.cons = S.cons;
     A.P = P; A.L = L; A.obs_words = (size_t)n_new * (sizeof(svs_ba_edge) / 8); A.cons_words = (size_t)C * (sizeof(svs_ba_constraint) / 8);
     A.poses0 = ba->d_poses[0]; A.poses1 = ba->d_poses[1]; A.psi0 = ba->d_psi[0]; A.psi1 = ba->d_psi[1];
-    A.store_tail = reinterpret_cast<double *>(ba->w_store + w_n_old); A.d_cons = reinterpret_cast<double *>(ba->d_cons.get()); A.d_x = ba->d_x;
+    A.store_tail = reinterpret_cast<double *>(S.store_tail); A.d_cons = reinterpret_cast<double *>(ba->d_cons.get()); A.d_x = ba->d_x;
     A.pose_tab = ba->w_pose_tab; A.point_tab = ba->w_point_tab;
     const size_t n_max = std::max<size_t>({12 * (size_t)P, 3 * (size_t)L, A.obs_words, A.cons_words, (size_t)1});
     hipLaunchKernelGGL(win_unpack_kernel, dim3((unsigned)((n_max + TB - 1) / TB)), dim3(TB), 0, ctx->stream, A);
   }
-  if (L) hipLaunchKernelGGL(win_anchor_kernel, dim3(div_up(L, TB)), dim3(TB), 0, ctx->stream, (const int *)(IN + i_aids), L, ba->w_pose_tab, d_aidx);
+  if (L) hipLaunchKernelGGL(win_anchor_kernel, dim3(div_up(L, TB)), dim3(TB), 0, ctx->stream, S.aids, L, ba->w_pose_tab, d_aidx);
   SVS_LAUNCH_CHECK(ctx);
   auto stage = [&](const char *what) { if (ba->opt.debug >= 2) { const hipError_t e = hipStreamSynchronize(ctx->stream); fprintf(stderr, "[svs_ba] window stage %s: %s\n", what, hipGetErrorString(e)); } };
   stage("tables");
   if (N && L) {
     const unsigned gN = (unsigned)((N + TB - 1) / TB);
-    hipLaunchKernelGGL(win_mark_kernel, dim3(gN), dim3(TB), 0, ctx->stream, ba->w_store, N, ba->w_pose_tab, pose_tab_n, ba->w_point_tab, point_tab_n, d_aidx,
+    hipLaunchKernelGGL(win_mark_kernel, dim3(gN), dim3(TB), 0, ctx->stream, S.store, N, ba->w_pose_tab, pose_tab_n, ba->w_point_tab, point_tab_n, d_aidx,
                        d_count, d_mask, d_ctr);
     stage("mark");
     hipLaunchKernelGGL(win_tile_hist_kernel, dim3((unsigned)n_tiles), dim3(256), 0, ctx->stream, d_count, d_aidx, L, P, d_tile);
@@ -441,7 +466,7 @@ static int window_update_impl(svs_ba *ba, int P, const int32_t *h_pose_ids, cons
     stage("landmark order");
     hipLaunchKernelGGL(win_tile_rank_kernel, dim3((unsigned)n_tiles), dim3(WIN_TILE), 0, ctx->stream, d_count, d_aidx, d_mask, L, P, d_tile, d_ctr, d_eoff, d_lms, d_lml, d_pat);
     stage("rank");
-    hipLaunchKernelGGL(win_place_kernel, dim3(gN), dim3(TB), 0, ctx->stream, ba->w_store, N, ba->w_pose_tab, pose_tab_n, ba->w_point_tab, point_tab_n, d_aidx,
+    hipLaunchKernelGGL(win_place_kernel, dim3(gN), dim3(TB), 0, ctx->stream, S.store, N, ba->w_pose_tab, pose_tab_n, ba->w_point_tab, point_tab_n, d_aidx,
                        d_eoff, d_mask, ba->d_edges);
     SVS_LAUNCH_CHECK(ctx);
     stage("place");
@@ -510,3 +535,66 @@ static int window_update_impl(svs_ba *ba, int P, const int32_t *h_pose_ids, cons
   return SVS_OK;
 }
 
+
+// ---- the window svs_map_prepare_window left in the map (ba_map.h) ---------------------------------------------------------------------------------------
+// copyDataToG2o device to device: ids, anchors, poses and psi are read where the map's kernels wrote them, the store is the map's measured store, and only the
+// constraints are staged.  Everything that can be refused is refused before the handle is touched.
+extern "C" int svs_ba_window_from_map(svs_ba *ba, svs_map *map, int C, const svs_ba_constraint *h_cons, const svs_cam *cam, const svs_ba_params *prm) {
+  svs_ctx *ctx = ba ? ba->ctx : nullptr;
+  SVS_REQUIRE(ctx, ba && map && C >= 0 && (C == 0 || h_cons) && cam && prm);
+  SVS_REQUIRE(ctx, svs_map_ctx(map) == ctx);          // one context: one stream orders the map's kernels and the assembly
+  SVS_REQUIRE(ctx, !ba->comm);                        // single-GPU path, as svs_ba_window_update
+  SVS_DEVICE(ctx);
+  MapWindowView V;
+  if (int rc = svs_map_window_view(map, &V)) return rc;      // no valid prepared window: nothing enqueued
+  const int P = V.P, L = V.L;
+  SVS_REQUIRE(ctx, P >= 1 && P <= SOLVE_MAX_P && L >= 0 && L < (1 << 23) && V.n_store < (size_t)INT_MAX - 1);
+  auto t_0 = std::chrono::steady_clock::now();
+  std::vector<svs_ba_constraint> cons_idx((size_t)C);
+  for (int c = 0; c < C; ++c) {
+    cons_idx[c] = h_cons[c];
+    int i1 = -1, i2 = -1;
+    for (int i = 0; i < P; ++i) { if (V.h_window_ids[i] == h_cons[c].pose1) i1 = i; if (V.h_window_ids[i] == h_cons[c].pose2) i2 = i; }
+    SVS_REQUIRE(ctx, i1 >= 0 && i2 >= 0);                   // a constraint of this window names two keyframes of the final window
+    cons_idx[c].pose1 = i1; cons_idx[c].pose2 = i2;
+  }
+  ba->problem_valid = false; ba->from_map_serial = 0;
+  ba->w_cons_idx.swap(cons_idx);
+  SVS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  ba->h_stage_used = 0;
+  const size_t cons_bytes = sizeof(svs_ba_constraint) * (size_t)C;
+  { int rc = stage_reserve(ba, cons_bytes + sizeof(int) * (V.n_store / 8 + 8 * (size_t)P) + 16384); if (rc) return rc; }
+  SVS_HIP(ctx, ba->w_in.reserve_keep(cons_bytes + 256, cons_bytes + cons_bytes / 2 + 4096, 0));
+  if (C) {
+    std::memcpy(ba->h_stage.get(), ba->w_cons_idx.data(), cons_bytes);
+    ba->h_stage_used = (cons_bytes + 255) & ~(size_t)255;
+    SVS_HIP(ctx, hipMemcpyAsync(ba->w_in, ba->h_stage.get(), cons_bytes, hipMemcpyHostToDevice, ctx->stream));
+  }
+  WinSrc S;
+  S.pids = V.window_ids; S.lids = V.active_ids; S.aids = V.anchor_ids; S.poses = V.poses; S.psi = V.psi; S.obs = nullptr;
+  S.cons = static_cast<const double *>(ba->w_in.get());
+  S.n_new = 0; S.store_tail = nullptr; S.store = V.store; S.N = V.n_store;
+  S.max_pose_id = std::max(V.kf_hi - 1, 0); S.max_point_id = std::max(V.pt_hi - 1, 0);
+  const int rc = window_assemble(ba, P, L, C, S, cam, prm, t_0, std::chrono::steady_clock::now());
+  if (rc == SVS_OK) ba->from_map_serial = V.serial;
+  return rc;
+}
+
+extern "C" int svs_ba_store_to_map(svs_ba *ba, svs_map *map) {
+  svs_ctx *ctx = ba ? ba->ctx : nullptr;
+  SVS_REQUIRE(ctx, ba && map && svs_map_ctx(map) == ctx);
+  SVS_REQUIRE(ctx, ba->problem_valid && ba->from_map_serial != 0 && svs_map_window_is(map, ba->from_map_serial));
+  SVS_DEVICE(ctx);
+  return svs_map_window_store(map, ba->d_poses[ba->cur], ba->d_psi[ba->cur]);
+}
+
+extern "C" int svs_ba_window_edges(svs_ba *ba, int32_t *n, svs_ba_edge *h_edges) {
+  svs_ctx *ctx = ba ? ba->ctx : nullptr;
+  SVS_REQUIRE(ctx, ba && n && ba->problem_valid);
+  *n = ba->E;
+  if (!h_edges || ba->E == 0) return SVS_OK;
+  SVS_DEVICE(ctx);
+  SVS_HIP(ctx, hipMemcpyAsync(h_edges, ba->d_edges, sizeof(svs_ba_edge) * (size_t)ba->E, hipMemcpyDeviceToHost, ctx->stream));
+  SVS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return SVS_OK;
+}

@@ -9,9 +9,13 @@
 //                   popcounts and a wave64 / workgroup prefix, so no atomic decides an order: the built request is a function of the map's content alone
 //   map_nbh_kernel      one workgroup per request of a front-end stream (nbh_map.h): addPointsToNeighbors / addAnchorPosesToNeighbors (backend.cpp:311-386) with the
 //                   same sets, written straight into the stream's candidate list, group ends and keyframe slots
-// Integer and copy work throughout; the host keeps the id sets and the set of pairs, so every refusal happens before anything is uploaded.
+//   map_win_mark / map_win_list    the double window's BA problem (ba_map.h): computeActivePointsAndExtendOuterWindow (slam_graph.cpp:599-663) with one workgroup per
+//                   INNER keyframe -- W0 and its graph neighbours as LDS bitmaps, active points and the extension as bitmaps in global memory -- then ascending
+//                   lists, poses and psi = invert_depth(xyz_anchor) by popcount prefixes; map_win_gather / map_win_store move the state to and from the optimizer
+// Integer and copy work throughout (but for the three divisions of invert_depth); the host keeps the id sets and the set of pairs, so every refusal happens before anything is uploaded.
 #include "reg_map.h"
 #include "nbh_map.h"
+#include "ba_map.h"
 #include <string.h>
 #include <algorithm>
 #include <unordered_set>
@@ -489,7 +493,137 @@ __global__ __launch_bounds__(MB_THREADS) void map_nbh_kernel(MapK M, MapNbhDst D
   }
 }
 
-#define MAP_CAPACITY(ctx, cond)                                                                        \
+// ---- the double window's BA problem (ba_map.h): computeActivePointsAndExtendOuterWindow (slam_graph.cpp:599-663) as set operations ----------------------------
+// lane i moves staged record i of svs_map_add_measured_observations to the tail of the measured store (four 16-byte loads) and its (point, keyframe) to the log's
+__global__ __launch_bounds__(256) void map_append_meas_kernel(const svs_ba_edge *__restrict__ up, int n, int2 *__restrict__ log_tail, svs_ba_edge *__restrict__ store_tail) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const int4 *s4 = reinterpret_cast<const int4 *>(up + i);
+  int4 *d4 = reinterpret_cast<int4 *>(store_tail + i);
+  const int4 q = s4[3];                // point, pose, anchor, pad_
+  d4[0] = s4[0]; d4[1] = s4[1]; d4[2] = s4[2]; d4[3] = q;
+  log_tail[i] = make_int2(q.x, q.y);
+}
+
+constexpr int MAP_WIN_MAX = 256;       // the solve's limit (ba.hip: SOLVE_MAX_P)
+struct MapWinK {
+  const int32_t *ids, *types, *pairs, *inner; int n0, n_pairs, window_cap, set_flags;      // staged: W0, the pairs, the INNER keyframes of W0
+  uint32_t *active, *ext;              // bitmaps over point ids (the walk's row 0 of M.mark) / keyframe ids; zero before the first launch
+  svs_map_window_result *res;          // zero before the first launch
+  int32_t *wid, *wtype;                // [MAP_WIN_MAX] the final window
+  int32_t *lids, *aids; double *poses, *psi;      // active ids | anchor ids | poses | psi
+};
+
+// one workgroup per INNER keyframe F of W0 (:611-646): W0 and F's graph neighbours are LDS bitmaps, F's feature_table row marks the active points and the extension
+__global__ __launch_bounds__(MB_THREADS) void map_win_mark_kernel(MapK M, MapWinK A) {
+  __shared__ uint32_t s_w0[MAP_KF_WORDS], s_nb[MAP_KF_WORDS];
+  const int tid = threadIdx.x, F = A.inner[blockIdx.x];
+  s_w0[tid] = 0; s_nb[tid] = 0;
+  __syncthreads();
+  // (ids the host has checked: in the map, so below kf_hi <= MAP_MAX_KF)
+  for (int i = tid; i < A.n0; i += MB_THREADS) { const int id = A.ids[i]; atomicOr(&s_w0[id >> 5], 1u << (id & 31)); }
+  for (int i = tid; i < A.n_pairs; i += MB_THREADS) {          // orderd_find is symmetric
+    const int a = A.pairs[2 * i], b = A.pairs[2 * i + 1];
+    if (a == F) atomicOr(&s_nb[b >> 5], 1u << (b & 31));
+    if (b == F) atomicOr(&s_nb[a >> 5], 1u << (a & 31));
+  }
+  __syncthreads();
+  const int e1 = M.kf_begin[F + 1];
+  for (int e0 = M.kf_begin[F]; e0 < e1; e0 += MB_THREADS) {    // block-uniform
+    const int e = e0 + tid;
+    const int p = e < e1 ? M.kf_rows[e] : -1;
+    const bool have = (unsigned)p < (unsigned)M.pt_hi;
+    const int a = have ? M.pt[p].kf_index : -1;                // the anchor's id
+    const bool a_ok = (unsigned)a < (unsigned)MAP_MAX_KF;
+    const bool in_w0 = a_ok && bit_of(s_w0, a);
+    const bool act = a_ok && (in_w0 || bit_of(s_nb, a));       // (:627, :636)
+    wave_or_by_word(A.active, p >> 5, 1u << (p & 31), act);
+    wave_or_by_word(A.ext, a >> 5, 1u << (a & 31), act && !in_w0);
+  }
+}
+
+// both bitmaps to ascending ids by popcount prefixes; workgroup b owns the words [b * MB_THREADS, (b + 1) * MB_THREADS) of the active bitmap, workgroup 0 also
+// the window's rows, poses, flags and the result.  Every workgroup finds the final window's size itself: over window_cap nothing is written but the result
+__global__ __launch_bounds__(MB_THREADS) void map_win_list_kernel(MapK M, MapWinK A) {
+  __shared__ uint32_t s_w0[MAP_KF_WORDS];
+  __shared__ int s_w[MB_THREADS / 64];
+  const int tid = threadIdx.x;
+  const uint32_t ext = A.ext[tid];
+  int n_ext;
+  const int ext_rank = block_excl_scan(__popc(ext), s_w, n_ext);
+  const int n_window = A.n0 + n_ext;
+  if (n_window > A.window_cap) {                               // block-uniform
+    if (blockIdx.x == 0 && tid == 0) { svs_map_window_result R; R.n_window = n_window; R.n_initial = A.n0; R.n_active = -1; R.n_edges_bound = 0; *A.res = R; }
+    return;
+  }
+  const int n_words = (M.pt_hi + 31) >> 5, w_first = blockIdx.x * MB_THREADS;
+  int before = 0, all = 0;
+  for (int w = tid; w < n_words; w += MB_THREADS) { const int c = __popc(A.active[w]); all += c; if (w < w_first) before += c; }
+  int n_before, n_active;
+  (void)block_excl_scan(before, s_w, n_before);
+  (void)block_excl_scan(all, s_w, n_active);
+  const int w = w_first + tid;
+  uint32_t bits = w < n_words ? A.active[w] : 0u;
+  int tot, bound = 0;
+  int pos = n_before + block_excl_scan(__popc(bits), s_w, tot);
+  while (bits) {                                               // pos < n_active <= the points of the map
+    const int p = (w << 5) + __ffs((int)bits) - 1;
+    bits &= bits - 1;
+    const svs_candidate_point &q = M.pt[p];
+    const double x = q.xyz_anchor[0], y = q.xyz_anchor[1], z = q.xyz_anchor[2];
+    A.lids[pos] = p; A.aids[pos] = q.kf_index;
+    A.psi[3 * (size_t)pos] = x / z; A.psi[3 * (size_t)pos + 1] = y / z; A.psi[3 * (size_t)pos + 2] = 1.0 / z;      // invert_depth (maths_utils.h:66-69)
+    bound += M.pt_begin[p + 1] - M.pt_begin[p];
+    ++pos;
+  }
+  int bound_all;
+  (void)block_excl_scan(bound, s_w, bound_all);
+  if (tid == 0 && bound_all) atomicAdd(&A.res->n_edges_bound, bound_all);      // a sum of integers: no order in it
+  if (blockIdx.x != 0) return;
+  // the final window: W0 as given, the extension ascending and OUTER
+  for (int i = tid; i < A.n0; i += MB_THREADS) { A.wid[i] = A.ids[i]; A.wtype[i] = A.types[i]; }
+  {
+    uint32_t b = ext;
+    for (int e = A.n0 + ext_rank; b; ++e) { A.wid[e] = (tid << 5) + __ffs((int)b) - 1; A.wtype[e] = 1; b &= b - 1; }
+  }
+  for (int i = n_window + tid; i < MAP_WIN_MAX; i += MB_THREADS) { A.wid[i] = -1; A.wtype[i] = -1; }
+  __syncthreads();
+  for (int i = tid; i < n_window * 12; i += MB_THREADS) A.poses[i] = M.kf[A.wid[i / 12]].T_anchor_from_w[i % 12];
+  if (A.set_flags) {                                           // exactly the final window, as map_window_kernel's two launches leave it
+    s_w0[tid] = 0;
+    __syncthreads();
+    for (int i = tid; i < A.n0; i += MB_THREADS) { const int id = A.ids[i]; atomicOr(&s_w0[id >> 5], 1u << (id & 31)); }
+    __syncthreads();
+    s_w0[tid] |= ext;
+    __syncthreads();
+    for (int i = tid; i < M.kf_hi; i += MB_THREADS) M.kf_flags[i] = bit_of(s_w0, i) ? SVS_REG_KF_IN_WINDOW : 0;
+  }
+  if (tid == 0) { A.res->n_window = n_window; A.res->n_initial = A.n0; A.res->n_active = n_active; }
+}
+
+// what svs_ba_window_from_map reads at its moment: the window's poses and psi again
+__global__ __launch_bounds__(256) void map_win_gather_kernel(MapK M, MapWinK A, int P, int L) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i < 12 * P) A.poses[i] = M.kf[A.wid[i / 12]].T_anchor_from_w[i % 12];
+  if (i < L) {
+    const svs_candidate_point &q = M.pt[A.lids[i]];
+    const double x = q.xyz_anchor[0], y = q.xyz_anchor[1], z = q.xyz_anchor[2];
+    A.psi[3 * (size_t)i] = x / z; A.psi[3 * (size_t)i + 1] = y / z; A.psi[3 * (size_t)i + 2] = 1.0 / z;
+  }
+}
+
+// restoreDataFromG2o (:1035-1058): poses by the window's ids, xyz_anchor = invert_depth(psi) by the active ids
+__global__ __launch_bounds__(256) void map_win_store_kernel(MapK M, MapWinK A, int P, int L, const double *__restrict__ poses, const double *__restrict__ psi) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i < 12 * P) M.kf[A.wid[i / 12]].T_anchor_from_w[i % 12] = poses[i];
+  if (i < L) {
+    const double u = psi[3 * (size_t)i], v = psi[3 * (size_t)i + 1], q = psi[3 * (size_t)i + 2];
+    double *xyz = M.pt[A.lids[i]].xyz_anchor;
+    xyz[0] = u / q; xyz[1] = v / q; xyz[2] = 1.0 / q;
+  }
+}
+
+#define MAP_CAPACITY(ctx, cond)                                                                     \
   do {                                                                                                    \
     if (!(cond)) {                                                                                        \
       char buf_[512];                                                                                     \
@@ -518,6 +652,11 @@ struct svs_map {
   DevBuf<uint32_t> d_mark; size_t mark_b = 0; int mark_rows = 0;
   // staging of the updates: one pinned block and its device twin, reused once the upload out of the pinned block has happened
   PinnedBuf<uint8_t> h_up; DevBuf<uint8_t> d_up; owned::Event up_ev; bool up_pending = false;
+  // the measured store (one svs_ba_edge per pair that came with a measurement, log order; allocated with the first of them) and the prepared window
+  DevBuf<svs_ba_edge> d_meas; int n_meas = 0, n_unmeasured = 0;
+  DevBuf<uint8_t> d_win; PinnedBuf<uint8_t> h_win;           // head (result | window ids | types) | extension bitmap | active ids | anchor ids | poses | psi
+  bool win_valid = false; int win_P = 0, win_L = 0; uint64_t win_serial = 0;
+  std::vector<int32_t> win_ids;
   ~svs_map() {      // (before the members go, also when create gives up)
     if (ctx) { (void)hipSetDevice(ctx->device); (void)hipStreamSynchronize(ctx->stream); }
   }
@@ -677,6 +816,56 @@ extern "C" int svs_map_add_points(svs_map *m, int n, const int32_t *h_ids, const
   SVS_LAUNCH_CHECK(ctx);
   for (int i = 0; i < n; ++i) { m->pt_in[h_ids[i]] = 1; m->pt_hi = std::max(m->pt_hi, h_ids[i] + 1); }
   m->n_pt += n;
+  m->win_valid = false;                // (the prepared window's lists are sized by the points it saw)
+  return SVS_OK;
+}
+
+// h_center == nullptr: svs_map_add_observations; else the pairs come with their measurements (h_level checked by the caller)
+static int map_add_observations(svs_map *m, int n, const int32_t *h_point_ids, const int32_t *h_kf_ids, const double *h_center, const int32_t *h_level) {
+  svs_ctx *ctx = m->ctx;
+  for (int i = 0; i < n; ++i) SVS_REQUIRE(ctx, h_point_ids[i] >= 0 && h_point_ids[i] < m->max_pt && m->pt_in[h_point_ids[i]] && svs_map_has_keyframe(m, h_kf_ids[i]));
+  // the pairs that are new, each once, in the caller's order
+  std::vector<int2> fresh;
+  std::vector<int> from;
+  std::unordered_set<uint64_t> seen;
+  for (int i = 0; i < n; ++i) {
+    const uint64_t key = ((uint64_t)(uint32_t)h_point_ids[i] << 32) | (uint32_t)h_kf_ids[i];
+    if (m->pairs.count(key) || !seen.insert(key).second) continue;
+    fresh.push_back(make_int2(h_point_ids[i], h_kf_ids[i]));
+    if (h_center) from.push_back(i);
+  }
+  MAP_CAPACITY(ctx, (size_t)m->n_obs + fresh.size() <= (size_t)m->max_obs);
+  if (fresh.empty()) return SVS_OK;
+  SVS_DEVICE(ctx);
+  const int nf = (int)fresh.size();
+  uint8_t *hs;
+  if (!h_center) {
+    if (int rc = map_stage(m, fresh.size() * sizeof(int2), &hs)) return rc;
+    memcpy(hs, fresh.data(), fresh.size() * sizeof(int2));
+    if (int rc = map_upload(m, m->d_log.get() + m->n_obs, fresh.size() * sizeof(int2))) return rc;      // straight to the log's tail
+    m->n_unmeasured += nf;
+  } else {
+    if (!m->d_meas) SVS_HIP(ctx, m->d_meas.alloc((size_t)m->max_obs));
+    if (int rc = map_stage(m, fresh.size() * sizeof(svs_ba_edge), &hs)) return rc;
+    svs_ba_edge *up = reinterpret_cast<svs_ba_edge *>(hs);
+    for (int k = 0; k < nf; ++k) {
+      const int i = from[k];
+      const double s = 1.0 / (double)(1 << h_level[i]);                                                 // pyrFromZero_d(1., level) (slam_graph.cpp:1012)
+      svs_ba_edge e;
+      for (int c = 0; c < 3; ++c) e.obs[c] = h_center[(size_t)i * 3 + c];
+      e.info[0] = s * s; e.info[1] = s * s; e.info[2] = 0.333 * 0.333;
+      e.point = fresh[k].x; e.pose = fresh[k].y; e.anchor = 0; e.pad_ = 0;
+      up[k] = e;
+    }
+    if (int rc = map_upload(m, m->d_up, fresh.size() * sizeof(svs_ba_edge))) return rc;
+    hipLaunchKernelGGL(map_append_meas_kernel, dim3(div_up(nf, 256)), dim3(256), 0, ctx->stream, reinterpret_cast<const svs_ba_edge *>(m->d_up.get()), nf,
+                       m->d_log.get() + m->n_obs, m->d_meas.get() + m->n_meas);
+    SVS_LAUNCH_CHECK(ctx);
+    m->n_meas += nf;
+  }
+  for (const int2 &o : fresh) m->pairs.insert(((uint64_t)(uint32_t)o.x << 32) | (uint32_t)o.y);
+  m->n_obs += nf;
+  m->win_valid = false;                // the prepared window was one of the map without these pairs
   return SVS_OK;
 }
 
@@ -684,24 +873,22 @@ extern "C" int svs_map_add_observations(svs_map *m, int n, const int32_t *h_poin
   svs_ctx *ctx = m ? m->ctx : nullptr;
   SVS_REQUIRE(ctx, m && n >= 0 && (n == 0 || (h_point_ids && h_kf_ids)));
   if (n == 0) return SVS_OK;
-  for (int i = 0; i < n; ++i) SVS_REQUIRE(ctx, h_point_ids[i] >= 0 && h_point_ids[i] < m->max_pt && m->pt_in[h_point_ids[i]] && svs_map_has_keyframe(m, h_kf_ids[i]));
-  // the pairs that are new, each once, in the caller's order
-  std::vector<int2> fresh;
-  std::unordered_set<uint64_t> seen;
-  for (int i = 0; i < n; ++i) {
-    const uint64_t key = ((uint64_t)(uint32_t)h_point_ids[i] << 32) | (uint32_t)h_kf_ids[i];
-    if (m->pairs.count(key) || !seen.insert(key).second) continue;
-    fresh.push_back(make_int2(h_point_ids[i], h_kf_ids[i]));
-  }
-  MAP_CAPACITY(ctx, (size_t)m->n_obs + fresh.size() <= (size_t)m->max_obs);
-  if (fresh.empty()) return SVS_OK;
-  SVS_DEVICE(ctx);
-  uint8_t *hs;
-  if (int rc = map_stage(m, fresh.size() * sizeof(int2), &hs)) return rc;
-  memcpy(hs, fresh.data(), fresh.size() * sizeof(int2));
-  if (int rc = map_upload(m, m->d_log.get() + m->n_obs, fresh.size() * sizeof(int2))) return rc;      // straight to the log's tail
-  for (const int2 &o : fresh) m->pairs.insert(((uint64_t)(uint32_t)o.x << 32) | (uint32_t)o.y);
-  m->n_obs += (int)fresh.size();
+  return map_add_observations(m, n, h_point_ids, h_kf_ids, nullptr, nullptr);
+}
+
+extern "C" int svs_map_add_measured_observations(svs_map *m, int n, const int32_t *h_point_ids, const int32_t *h_kf_ids, const double *h_center,
+                                                 const int32_t *h_level) {
+  svs_ctx *ctx = m ? m->ctx : nullptr;
+  SVS_REQUIRE(ctx, m && n >= 0 && (n == 0 || (h_point_ids && h_kf_ids && h_center && h_level)));
+  if (n == 0) return SVS_OK;
+  for (int i = 0; i < n; ++i) SVS_REQUIRE(ctx, h_level[i] >= 0 && h_level[i] < SVS_NUM_PYR_LEVELS);
+  return map_add_observations(m, n, h_point_ids, h_kf_ids, h_center, h_level);
+}
+
+extern "C" int svs_map_measured_info(svs_map *map, int32_t *n_measured, int32_t *n_unmeasured) {
+  if (!map) return SVS_ERR_INVALID;
+  if (n_measured) *n_measured = map->n_meas;
+  if (n_unmeasured) *n_unmeasured = map->n_unmeasured;
   return SVS_OK;
 }
 
@@ -794,6 +981,109 @@ int svs_map_build_neighborhoods(svs_map *m, int n_requests, const MapNbhDst &dst
   svs_ctx *ctx = m->ctx;
   if (int rc = map_prepare_walk(m, n_requests)) return rc;
   hipLaunchKernelGGL(map_nbh_kernel, dim3(n_requests), dim3(MB_THREADS), 0, ctx->stream, m->view(), dst);
+  SVS_LAUNCH_CHECK(ctx);
+  return SVS_OK;
+}
+
+// ---- the prepared window ------------------------------------------------------------------------------------------------------------------------------
+namespace {
+constexpr size_t WIN_O_EXT = 0, WIN_O_RES = WIN_O_EXT + sizeof(uint32_t) * MAP_KF_WORDS, WIN_O_WID = WIN_O_RES + sizeof(svs_map_window_result),
+                 WIN_O_WTYPE = WIN_O_WID + sizeof(int32_t) * MAP_WIN_MAX, WIN_HEAD_END = WIN_O_WTYPE + sizeof(int32_t) * MAP_WIN_MAX;
+size_t win_align(size_t v) { return (v + 255) & ~(size_t)255; }
+// the block's pieces; the lists are as long as the map has room for points
+MapWinK map_win_pieces(const svs_map *m) {
+  MapWinK A{};
+  uint8_t *W = m->d_win.get();
+  const size_t o_lids = win_align(WIN_HEAD_END), o_aids = o_lids + win_align(sizeof(int32_t) * (size_t)m->max_pt), o_poses = o_aids + win_align(sizeof(int32_t) * (size_t)m->max_pt),
+               o_psi = o_poses + win_align(sizeof(double) * 12 * MAP_WIN_MAX);
+  A.ext = reinterpret_cast<uint32_t *>(W + WIN_O_EXT); A.res = reinterpret_cast<svs_map_window_result *>(W + WIN_O_RES);
+  A.wid = reinterpret_cast<int32_t *>(W + WIN_O_WID); A.wtype = reinterpret_cast<int32_t *>(W + WIN_O_WTYPE);
+  A.lids = reinterpret_cast<int32_t *>(W + o_lids); A.aids = reinterpret_cast<int32_t *>(W + o_aids);
+  A.poses = reinterpret_cast<double *>(W + o_poses); A.psi = reinterpret_cast<double *>(W + o_psi);
+  A.active = m->d_mark;
+  return A;
+}
+size_t map_win_bytes(const svs_map *m) {
+  return win_align(WIN_HEAD_END) + 2 * win_align(sizeof(int32_t) * (size_t)m->max_pt) + win_align(sizeof(double) * 12 * MAP_WIN_MAX) + win_align(sizeof(double) * 3 * (size_t)m->max_pt);
+}
+uint64_t next_win_serial() { static uint64_t s = 0; return __atomic_add_fetch(&s, 1, __ATOMIC_RELAXED); }
+}  // namespace
+
+extern "C" int svs_map_prepare_window(svs_map *m, int n0, const int32_t *h_kf_ids, const int32_t *h_kf_type, int n_pairs, const int32_t *h_edge_pairs,
+                                      int set_window_flags, int window_cap, svs_map_window_result *h_res, int32_t *h_window_ids, int32_t *h_window_type) {
+  svs_ctx *ctx = m ? m->ctx : nullptr;
+  SVS_REQUIRE(ctx, m && n0 >= 1 && h_kf_ids && h_kf_type && n_pairs >= 0 && (n_pairs == 0 || h_edge_pairs) && window_cap >= 1 && h_res);
+  MAP_CAPACITY(ctx, n0 <= window_cap && window_cap <= MAP_WIN_MAX);
+  if (int rc = map_check_ids(m, n0, h_kf_ids, m->kf_in, m->max_kf, true)) return rc;
+  int n_inner = 0;
+  for (int i = 0; i < n0; ++i) { SVS_REQUIRE(ctx, h_kf_type[i] == 0 || h_kf_type[i] == 1); n_inner += h_kf_type[i] == 0; }
+  SVS_REQUIRE(ctx, n_inner >= 1);
+  for (int i = 0; i < 2 * n_pairs; ++i) SVS_REQUIRE(ctx, svs_map_has_keyframe(m, h_edge_pairs[i]));
+  if (m->n_unmeasured > 0) { ctx->err = "svs_map_prepare_window: the map holds observations without a measurement (svs_map_add_observations)"; return SVS_ERR_INVALID; }
+  SVS_DEVICE(ctx);
+  if (!m->d_win) SVS_HIP(ctx, m->d_win.alloc(map_win_bytes(m)));
+  if (m->h_win.bytes() < WIN_HEAD_END - WIN_O_RES) SVS_HIP(ctx, m->h_win.alloc(WIN_HEAD_END - WIN_O_RES));
+  if (int rc = map_prepare_walk(m, 1)) return rc;
+  // one staged upload: W0's ids | types | the INNER ones | the pairs
+  const size_t o_types = up_align(sizeof(int32_t) * (size_t)n0), o_inner = o_types + up_align(sizeof(int32_t) * (size_t)n0),
+               o_pairs = o_inner + up_align(sizeof(int32_t) * (size_t)n_inner), bytes = o_pairs + sizeof(int32_t) * 2 * (size_t)n_pairs;
+  uint8_t *hs;
+  if (int rc = map_stage(m, bytes, &hs)) return rc;
+  memcpy(hs, h_kf_ids, sizeof(int32_t) * (size_t)n0);
+  memcpy(hs + o_types, h_kf_type, sizeof(int32_t) * (size_t)n0);
+  { int32_t *inner = reinterpret_cast<int32_t *>(hs + o_inner); for (int i = 0, k = 0; i < n0; ++i) if (h_kf_type[i] == 0) inner[k++] = h_kf_ids[i]; }
+  if (n_pairs) memcpy(hs + o_pairs, h_edge_pairs, sizeof(int32_t) * 2 * (size_t)n_pairs);
+  if (int rc = map_upload(m, m->d_up, bytes)) return rc;
+  m->win_valid = false;                // from here on the block holds the new window, or nothing
+  MapWinK A = map_win_pieces(m);
+  const uint8_t *U = m->d_up.get();
+  A.ids = reinterpret_cast<const int32_t *>(U); A.types = reinterpret_cast<const int32_t *>(U + o_types); A.inner = reinterpret_cast<const int32_t *>(U + o_inner);
+  A.pairs = reinterpret_cast<const int32_t *>(U + o_pairs);
+  A.n0 = n0; A.n_pairs = n_pairs; A.window_cap = window_cap; A.set_flags = set_window_flags != 0;
+  const MapK M = m->view();
+  const int n_words = (m->pt_hi + 31) >> 5;
+  SVS_HIP(ctx, hipMemsetAsync(m->d_win.get() + WIN_O_EXT, 0, WIN_O_WID - WIN_O_EXT, ctx->stream));      // the extension bitmap and the result
+  if (n_words) SVS_HIP(ctx, hipMemsetAsync(m->d_mark, 0, sizeof(uint32_t) * (size_t)n_words, ctx->stream));
+  hipLaunchKernelGGL(map_win_mark_kernel, dim3(n_inner), dim3(MB_THREADS), 0, ctx->stream, M, A);
+  hipLaunchKernelGGL(map_win_list_kernel, dim3(std::max(1, div_up(n_words, MB_THREADS))), dim3(MB_THREADS), 0, ctx->stream, M, A);
+  SVS_LAUNCH_CHECK(ctx);
+  SVS_HIP(ctx, hipMemcpyAsync(m->h_win, m->d_win.get() + WIN_O_RES, WIN_HEAD_END - WIN_O_RES, hipMemcpyDeviceToHost, ctx->stream));
+  SVS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  const svs_map_window_result R = *reinterpret_cast<const svs_map_window_result *>(m->h_win.get());
+  const int32_t *wid = reinterpret_cast<const int32_t *>(m->h_win.get() + (WIN_O_WID - WIN_O_RES)), *wtype = wid + MAP_WIN_MAX;
+  *h_res = R;
+  const bool over = R.n_active < 0;
+  for (int i = 0; i < window_cap; ++i) {
+    if (h_window_ids) h_window_ids[i] = !over && i < R.n_window ? wid[i] : -1;
+    if (h_window_type) h_window_type[i] = !over && i < R.n_window ? wtype[i] : -1;
+  }
+  if (over) return SVS_OK;
+  m->win_ids.assign(wid, wid + R.n_window);
+  m->win_P = R.n_window; m->win_L = R.n_active; m->win_serial = next_win_serial(); m->win_valid = true;
+  return SVS_OK;
+}
+
+bool svs_map_window_is(const svs_map *m, uint64_t serial) { return m && m->win_valid && m->win_serial == serial; }
+
+int svs_map_window_view(svs_map *m, MapWindowView *out) {
+  svs_ctx *ctx = m->ctx;
+  SVS_REQUIRE(ctx, m->win_valid);
+  const MapWinK A = map_win_pieces(m);
+  const int P = m->win_P, L = m->win_L;
+  hipLaunchKernelGGL(map_win_gather_kernel, dim3(div_up(std::max(12 * P, L), 256)), dim3(256), 0, ctx->stream, m->view(), A, P, L);
+  SVS_LAUNCH_CHECK(ctx);
+  MapWindowView V{};
+  V.P = P; V.L = L; V.window_ids = A.wid; V.h_window_ids = m->win_ids.data(); V.active_ids = A.lids; V.anchor_ids = A.aids; V.poses = A.poses; V.psi = A.psi;
+  V.store = m->d_meas; V.n_store = (size_t)m->n_meas; V.kf_hi = m->kf_hi; V.pt_hi = m->pt_hi; V.serial = m->win_serial;
+  *out = V;
+  return SVS_OK;
+}
+
+int svs_map_window_store(svs_map *m, const double *d_poses, const double *d_psi) {
+  svs_ctx *ctx = m->ctx;
+  SVS_REQUIRE(ctx, m->win_valid);
+  const int P = m->win_P, L = m->win_L;
+  hipLaunchKernelGGL(map_win_store_kernel, dim3(div_up(std::max(12 * P, L), 256)), dim3(256), 0, ctx->stream, m->view(), map_win_pieces(m), P, L, d_poses, d_psi);
   SVS_LAUNCH_CHECK(ctx);
   return SVS_OK;
 }

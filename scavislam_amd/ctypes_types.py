@@ -269,3 +269,13 @@ class NbhResult(C.Structure):
 
 
 assert C.sizeof(NbhRequest) == 48 and C.sizeof(NbhResult) == 32
+
+
+# ---- back end: the double window's BA problem from the map (svs_map_prepare_window)
+class MapWindowResult(C.Structure):
+    """svs_map_window_result: final window, W0, active points (-1: the final window exceeded window_cap), upper bound of the window's edges"""
+    _fields_ = [("n_window", C.c_int32), ("n_initial", C.c_int32), ("n_active", C.c_int32), ("n_edges_bound", C.c_int32)]
+
+
+assert C.sizeof(MapWindowResult) == 16
+MAP_WINDOW_MAX = 256      # the solve's limit on a window's keyframes

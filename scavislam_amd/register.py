@@ -15,8 +15,8 @@ import ctypes as C
 
 import numpy as np
 
-from .ctypes_types import (CANDIDATE_DTYPE, KEYFRAME_DTYPE, MATCH_RESULT_DTYPE, REG_KF_STATS_DTYPE, REG_LOCAL, REG_LOOP, REG_OK, REG_OVER_CAPACITY, REG_STAGES,
-                           SVS_MAX_CELLS, Cam, RegMapRequest, RegParams, RegRequest, RegResult)
+from .ctypes_types import (CANDIDATE_DTYPE, KEYFRAME_DTYPE, MAP_WINDOW_MAX, MATCH_RESULT_DTYPE, REG_KF_STATS_DTYPE, REG_LOCAL, REG_LOOP, REG_OK, REG_OVER_CAPACITY,
+                           REG_STAGES, SVS_MAX_CELLS, Cam, MapWindowResult, RegMapRequest, RegParams, RegRequest, RegResult)
 
 
 def keyframe_table(entries):
@@ -202,6 +202,7 @@ class ResidentMap:
         h = C.c_void_p()
         ctx.call("svs_map_create", int(max_keyframes), int(max_points), int(max_observations), C.byref(h))
         self.h = h
+        self.window_shape = None
         ctx.children.add(self)
 
     def _call(self, name, *args):
@@ -241,6 +242,41 @@ class ResidentMap:
         if len(p) != len(k):
             raise ValueError("pairs expected")
         self._call("svs_map_add_observations", len(p), p.ctypes.data, k.ctypes.data)
+
+    def add_measured_observations(self, point_ids, kf_ids, center, level):
+        """add_observations for a caller that also optimises: every new pair brings feat.center [3] and feat.level (0 .. 2); the map keeps one BA observation
+        record per new pair on the device (svs_map_add_measured_observations)"""
+        p = np.ascontiguousarray(point_ids, np.int32).reshape(-1)
+        k = np.ascontiguousarray(kf_ids, np.int32).reshape(-1)
+        c = np.ascontiguousarray(center, np.float64).reshape(-1, 3)
+        l = np.ascontiguousarray(level, np.int32).reshape(-1)
+        if not (len(p) == len(k) == len(c) == len(l)):
+            raise ValueError("one keyframe, centre and level per point expected")
+        self._call("svs_map_add_measured_observations", len(p), p.ctypes.data, k.ctypes.data, c.ctypes.data, l.ctypes.data)
+
+    def measured_info(self):
+        """(pairs with a measurement, pairs without one)"""
+        a, b = C.c_int32(), C.c_int32()
+        self._call("svs_map_measured_info", C.byref(a), C.byref(b))
+        return a.value, b.value
+
+    def prepare_window(self, kf_ids, kf_type, edge_pairs=(), set_window_flags=True, window_cap=MAP_WINDOW_MAX):
+        """computeActivePointsAndExtendOuterWindow on the device (svs_map_prepare_window): kf_ids / kf_type (0 INNER, 1 OUTER) are double_window_ before the
+        extension, edge_pairs [n, 2] the edge_table_ entries with an end in an INNER keyframe.  Returns (MapWindowResult, final window ids, types); the two
+        arrays are empty and n_active is -1 when the final window exceeds window_cap"""
+        k = np.ascontiguousarray(kf_ids, np.int32).reshape(-1)
+        t = np.ascontiguousarray(kf_type, np.int32).reshape(-1)
+        e = np.ascontiguousarray(edge_pairs, np.int32).reshape(-1, 2)
+        if len(k) != len(t):
+            raise ValueError("one type per keyframe expected")
+        cap = int(window_cap)
+        res = MapWindowResult()
+        wid, wtype = np.full(max(cap, 1), -1, np.int32), np.full(max(cap, 1), -1, np.int32)
+        self._call("svs_map_prepare_window", len(k), k.ctypes.data, t.ctypes.data, len(e), e.ctypes.data if len(e) else None, int(bool(set_window_flags)), cap,
+                   C.byref(res), wid.ctypes.data, wtype.ctypes.data)
+        n = res.n_window if res.n_active >= 0 else 0
+        self.window_shape = (res.n_window, res.n_active) if res.n_active >= 0 else None      # what SlamGraphOptimizer.windowFromMap sizes its state by
+        return res, wid[:n].copy(), wtype[:n].copy()
 
     def set_poses(self, kf_ids, poses):
         k = np.ascontiguousarray(kf_ids, np.int32).reshape(-1)
