@@ -1022,6 +1022,79 @@ typedef struct { int32_t n_window, n_initial, n_active, n_edges_bound; } svs_map
 int svs_map_prepare_window(svs_map *map, int n0, const int32_t *h_kf_ids, const int32_t *h_kf_type, int n_pairs, const int32_t *h_edge_pairs /* [n_pairs][2] */,
                            int set_window_flags, int window_cap, svs_map_window_result *h_res, int32_t *h_window_ids, int32_t *h_window_type);
 
+/* ---- the pose graph's edges (EdgeTable, slam_graph.hpp:197-363) and their constraints (computeConstraint, slam_graph.cpp:787-846) ----
+   One record per undirected edge, keyed (lo, hi) with lo < hi as the reference's Edge is.  The relative pose is stored ONCE, as T_lo_from_hi, and there is ONE
+   info: every call site of setConstraint passes the same Lambda for both directions (slam_graph.cpp:457-461, :246-250, :897-898), so Lambda_1_from_2 and
+   Lambda_2_from_1 of the reference's Edge are equal wherever they are set.  The host keeps the key set and the is_marginalized flags (every refusal happens
+   before anything is uploaded); T and info live on the device alone.  A new edge has T and info zero and is not marginalised.
+   Capacity: svs_map_reserve_edges (once, >= 1; a second call: SVS_ERR_INVALID).  Without it the table holds no edge and every edge call returns
+   SVS_ERR_CAPACITY. */
+typedef struct {
+  int32_t lo, hi;                      /* lo < hi */
+  int32_t strength, edge_type;         /* 0 LOCAL, 1 METRIC, 2 APPEARANCE */
+  int32_t is_marginalized, pad_;
+  double T_lo_from_hi[12];
+  double info[36];
+} svs_map_edge;
+int svs_map_reserve_edges(svs_map *map, int max_edges);
+/* insertEdge (:333-354) for n edges, either orientation: ASYNCHRONOUS, one staged upload and one launch.  SVS_ERR_INVALID (the reference asserts): an unknown
+   keyframe, id1 == id2, an edge already present, an edge twice in the call, a type outside 0 .. 2; SVS_ERR_CAPACITY: more edges than reserved */
+int svs_map_add_edges(svs_map *map, int n, const int32_t *h_pairs /* [n][2] */, const int32_t *h_strength, const int32_t *h_type);
+/* setConstraint (:295-331) with a caller's own values: pose1 / pose2 name the edge, T_21 = T_pose2_from_pose1, info for both directions.  Stored as
+   T_lo_from_hi: the device inverts T_21 where pose1 < pose2 (:327 for the other orientation); sets is_marginalized.  ASYNCHRONOUS, one upload, one launch.
+   SVS_ERR_INVALID: an edge that does not exist, an edge twice in the call */
+int svs_map_set_constraints(svs_map *map, int n, const svs_ba_constraint *h_cons);
+/* unMarginalize (:235-240): clears the flag only, T and info stay.  ASYNCHRONOUS.  SVS_ERR_INVALID: an edge that does not exist, an edge twice in the call */
+int svs_map_unmarginalize(svs_map *map, int n, const int32_t *h_pairs /* [n][2] */);
+/* BLOCKING read-back of the records of the named edges (either orientation).  SVS_ERR_INVALID: an edge that does not exist */
+int svs_map_get_edges(svs_map *map, int n, const int32_t *h_pairs /* [n][2] */, svs_map_edge *h_out);
+/* the host-side counts (each optional) */
+int svs_map_edge_info(svs_map *map, int32_t *n_edges, int32_t *n_marginalized);
+
+/* computeConstraint (slam_graph.cpp:787-846) for a batch of keyframe pairs, one workgroup per request, as a statement that does not depend on hash order:
+     common points   the points of kf1's feature_table that are also in kf2's, in ascending point id;
+     anchor pose     of a common point: a pose override of the request if the anchor is named there; else the map's pose if the anchor has SVS_REG_KF_IN_WINDOW
+                     (double_window_, :809-813); else its entry in the request's cached list (the caller's computeAbsolutePose results -- shortestPathToWindow
+                     is a graph search and stays with the caller); else the request ends with SVS_CONS_MISSING_ANCHOR and returns the missing anchor ids
+                     ascending, each once, up to missing_cap, with n_missing = their total count: the caller walks its graph for exactly those and calls again;
+     depth           d = || T1 inv(T_anchor) xyz_anchor || evaluated right to left on the vector: pose_act(T1, pose_act(pose_inv(T_anchor), xyz)), rows
+                     ((a0 b0 + a1 b1) + a2 b2) + t, no contraction, sqrt((x x + y y) + z z) in f64;
+     strength        the number of common points;
+     median          maths_utils.h:114-136 over the multiset of depths: odd count the middle element, even count 0.5 * (a + b) of the two middle ones
+                     (a radix select over the 64-bit patterns: positive doubles order as their bits; no cap on the count, no sort);
+     T_12            T_1_from_2 = pose_mul(T1, pose_inv(T2));     norm_dist = || t(T_12) || / median;
+     info            diag(s a, s a, s a, s b, s b, s b), dense, s = (double)strength, a = Po2((350 * 1.0) * norm_dist), b = Po2(100 * 1.0).
+   Pose overrides (n_override <= 2: id, T[12]) replace the map's pose of that keyframe for the whole request, also where it serves as an anchor, whether or not
+   it is in the window: registerKeyframes (:197-204) and addLoopClosure (:233-244) bring a vertex "temporarily" to another pose.
+   strength == 0 (the reference's median asserts): SVS_CONS_EMPTY, T_12 still returned, median, norm_dist and info zero, nothing stored.  strength < covis_thr
+   is only a warning in the reference (:833-836) and no error here: the caller decides.
+   store != 0 with SVS_CONS_OK: setConstraint(kf1, kf2, T_12, info, info) is applied to the edge by the same launch (the edge must exist).
+   h_missing [n][missing_cap] (optional when missing_cap == 0): -1 behind a request's ids.  h_depths [n][depth_cap] (optional, for tests): the depths in
+   ascending point id with SVS_CONS_OK, zero behind them and with every other status.
+   BLOCKING: one staged upload, at most the CSR rebuild plus one launch, one download; the host's is_marginalized mirror follows the statuses.
+   Refused as a whole before the upload -- SVS_ERR_INVALID: an unknown keyframe, kf1 == kf2, n_override outside 0 .. 2, an override or cached id outside the
+   map's capacity, a cached list that is not strictly ascending, a storing request without its edge, two storing requests for one edge (their order would decide
+   the result); SVS_ERR_CAPACITY: more than SVS_MAP_CONS_MAX_REQUESTS requests, a cached list longer than the map's keyframe capacity, h_depths with depth_cap
+   below the length of a kf1's feature_table. */
+enum { SVS_CONS_OK = 0, SVS_CONS_EMPTY = 1, SVS_CONS_MISSING_ANCHOR = 2 };
+enum { SVS_MAP_CONS_MAX_REQUESTS = 256 };
+typedef struct {
+  int32_t kf1, kf2, store, n_override;
+  int32_t override_id[2];
+  int32_t n_cached, pad_;
+  double override_T[2][12];
+  const int32_t *cached_ids;           /* [n_cached] strictly ascending */
+  const double *cached_T;              /* [n_cached][12] T_anchor_from_world */
+} svs_map_constraint_request;
+typedef struct {
+  int32_t status, strength, n_missing, pad_;
+  double median, norm_dist;
+  double T_12[12];
+  double info[36];
+} svs_map_constraint_result;
+int svs_map_compute_constraints(svs_map *map, int n_requests, const svs_map_constraint_request *req, int missing_cap, svs_map_constraint_result *h_res,
+                                int32_t *h_missing, int depth_cap, double *h_depths);
+
 /* A request by ids.  The device builds the svs_reg_request of the stateless call from the map:
      1. source points.  SVS_REG_LOCAL: every point with at least one observation in a keyframe of h_walk_kf that is not the root and not in h_direct_kf
         (:481-497; the root is a direct neighbour, :433-449).  SVS_REG_LOOP: every point observed by h_walk_kf[0], the query keyframe (:853-858).  Each point
@@ -1185,6 +1258,15 @@ int svs_ba_window_from_map(svs_ba *ba, svs_map *map, int C, const svs_ba_constra
 /* restoreDataFromG2o on the device (slam_graph.cpp:1035-1058), one launch, ASYNCHRONOUS: window pose i to the map's keyframe of its id, xyz_anchor =
    invert_depth(psi) to the map's point of its id.  Valid only while the handle's problem is the one svs_ba_window_from_map built from this map's prepared window */
 int svs_ba_store_to_map(svs_ba *ba, svs_map *map);
+/* svs_ba_window_from_map with copyContraintsToG2o (slam_graph.cpp:937-981) done from the map's edge table: for i over the final window in its order, for j over
+   it in its order, j != i, an edge between them and at least one of the two OUTER: one constraint pose1 = id_i, pose2 = id_j, T_21 = T_j_from_i -- every such
+   edge twice, once per direction, as the reference's double loop adds it (its order is that of an unordered_map; ours is the one just stated).  Only the list
+   of (window index i, window index j, edge slot, direction) is staged; one gather launch writes the svs_ba_constraint records on the device and applies
+   pose_inv for the direction against storage (slam_graph.hpp:281).  An edge of that list that is not marginalised: SVS_ERR_INVALID before the handle is
+   touched (the reference asserts, :972); the other refusals are svs_ba_window_from_map's */
+int svs_ba_window_from_map_edges(svs_ba *ba, svs_map *map, const svs_cam *cam, const svs_ba_params *prm);
+/* the handle's constraints with window INDICES in pose1 / pose2, after any way to set a problem; *n = their count, h_cons == NULL returns only that (blocking) */
+int svs_ba_window_constraints(svs_ba *ba, int32_t *n, svs_ba_constraint *h_cons);
 /* landmark-sharded operation over a library-owned communicator: svs_ba_optimize(ba, NULL, NULL, stats) then all-reduces the
    packed reduced system and the two trial sums of every LM trial (32 doubles: each sum is kept in 16 partial slots) (and, once per problem, the co-visibility pattern) with
    ncclAllReduce on the ctx stream.  comm == NULL detaches.  A non-NULL `allreduce` argument of svs_ba_optimize takes precedence

@@ -923,12 +923,76 @@ class BackendMap {
     return ok_ && xyz_anchor3.size() == 3 * point_ids.size() && ctx_.check(svs_map_set_points(map_, (int)point_ids.size(), point_ids.data(), xyz_anchor3.data()));
   }
   bool setWindow(const std::vector<int32_t> &kf_ids) { return ok_ && ctx_.check(svs_map_set_window(map_, (int)kf_ids.size(), kf_ids.data())); }
+  // ---- the pose graph's edges (EdgeTable) and their constraints (computeConstraint, slam_graph.cpp:787-846) on the device ----
+  bool reserveEdges(int max_edges) { return ok_ && ctx_.check(svs_map_reserve_edges(map_, max_edges)); }
+  // insertEdge: pairs (id, id, ...), either orientation; edge_type 0 LOCAL, 1 METRIC, 2 APPEARANCE
+  bool addEdges(const std::vector<int32_t> &pairs, const std::vector<int32_t> &strength, const std::vector<int32_t> &edge_type) {
+    const size_t n = pairs.size() / 2;
+    if (!ok_ || pairs.size() % 2 || strength.size() != n || edge_type.size() != n) return false;
+    if (!ctx_.check(svs_map_add_edges(map_, (int)n, pairs.data(), strength.data(), edge_type.data()))) return false;
+    for (size_t i = 0; i < n; ++i) edge_keys_.push_back(std::make_pair(std::min(pairs[2 * i], pairs[2 * i + 1]), std::max(pairs[2 * i], pairs[2 * i + 1])));
+    std::sort(edge_keys_.begin(), edge_keys_.end());
+    return true;
+  }
+  // computeConstraint for a batch (one blocking call); missing: the anchors some request has neither in the window nor among its cached poses, ascending, each
+  // once (at most missing_cap per request) -- the caller's computeAbsolutePose completes them and the call is repeated
+  bool computeConstraints(const std::vector<svs_map_constraint_request> &requests, std::vector<svs_map_constraint_result> *results,
+                          std::vector<int32_t> *missing = nullptr, int missing_cap = 64) {
+    if (!ok_ || !results || missing_cap < 1) return false;
+    results->resize(requests.size());
+    std::vector<int32_t> miss(requests.size() * (size_t)missing_cap, -1);
+    if (!ctx_.check(svs_map_compute_constraints(map_, (int)requests.size(), requests.data(), missing_cap, results->data(), miss.data(), 0, nullptr))) return false;
+    if (missing) {
+      missing->clear();
+      for (size_t i = 0; i < miss.size(); ++i) if (miss[i] >= 0) missing->push_back(miss[i]);
+      std::sort(missing->begin(), missing->end());
+      missing->erase(std::unique(missing->begin(), missing->end()), missing->end());
+    }
+    return true;
+  }
+  // unmargPosesEnteringInnerW (:728-759) and margPosesLeftInnerWindow (:848-904): the pairs are selected here from the edge keys and the two windows (ids, types
+  // 0 INNER / 1 OUTER), then one svs_map_unmarginalize and one storing computeConstraints with kf1 the smaller id.  The map's window flags must be those of the
+  // new window.  cached_ids (ascending) / cached_T12: the caller's computeAbsolutePose results, given to every request
+  bool updateMarginalization(const std::vector<int32_t> &old_ids, const std::vector<int32_t> &old_types, const std::vector<int32_t> &new_ids,
+                             const std::vector<int32_t> &new_types, const std::vector<int32_t> &cached_ids, const std::vector<double> &cached_T12,
+                             std::vector<svs_map_constraint_result> *results, std::vector<int32_t> *missing) {
+    if (!ok_ || old_ids.size() != old_types.size() || new_ids.size() != new_types.size() || cached_T12.size() != 12 * cached_ids.size()) return false;
+    std::vector<int32_t> enter, left;
+    innerPairs(new_ids, new_types, &enter);
+    innerPairs(old_ids, old_types, &left);
+    std::vector<svs_map_constraint_request> req;
+    for (size_t k = 0; k + 1 < left.size(); k += 2) {
+      if (innerIn(new_ids, new_types, left[k]) && innerIn(new_ids, new_types, left[k + 1])) continue;
+      svs_map_constraint_request q;
+      std::memset(&q, 0, sizeof q);
+      q.kf1 = left[k]; q.kf2 = left[k + 1]; q.store = 1; q.n_cached = (int32_t)cached_ids.size();
+      q.cached_ids = cached_ids.empty() ? nullptr : cached_ids.data(); q.cached_T = cached_T12.empty() ? nullptr : cached_T12.data();
+      req.push_back(q);
+    }
+    if (!enter.empty() && !ctx_.check(svs_map_unmarginalize(map_, (int)(enter.size() / 2), enter.data()))) return false;
+    std::vector<svs_map_constraint_result> local;
+    return computeConstraints(req, results ? results : &local, missing);
+  }
   int anchorLevel(int point_id) const { return point_id >= 0 && (size_t)point_id < level_.size() ? level_[(size_t)point_id] : 0; }
 
  private:
+  static bool innerIn(const std::vector<int32_t> &ids, const std::vector<int32_t> &types, int32_t id) {
+    for (size_t i = 0; i < ids.size(); ++i) if (ids[i] == id) return types[i] == 0;
+    return false;
+  }
+  // every edge between two INNER keyframes of the window, once, (lo, hi) ascending
+  void innerPairs(const std::vector<int32_t> &ids, const std::vector<int32_t> &types, std::vector<int32_t> *out) const {
+    std::vector<int32_t> inner;
+    for (size_t i = 0; i < ids.size(); ++i) if (types[i] == 0) inner.push_back(ids[i]);
+    std::sort(inner.begin(), inner.end());
+    for (size_t i = 0; i < inner.size(); ++i)
+      for (size_t j = i + 1; j < inner.size(); ++j)
+        if (std::binary_search(edge_keys_.begin(), edge_keys_.end(), std::make_pair(inner[i], inner[j]))) { out->push_back(inner[i]); out->push_back(inner[j]); }
+  }
   const Context &ctx_;
   svs_map *map_;
   std::vector<int8_t> level_;      // anchor_level by point id: MyTrackPoint carries it
+  std::vector<std::pair<int32_t, int32_t> > edge_keys_;      // (lo, hi) of every edge, sorted: what updateMarginalization selects its pairs from
   bool ok_;
 };
 inline bool StereoFrontend::setCandidatesFromMap(BackendMap &map, const std::vector<int32_t> &vertex_ids, const std::vector<int32_t> &slot_keyframe_ids,
@@ -1232,6 +1296,11 @@ class SlamGraphBA {
     }
     svs_ba_params prm = params(opt, false);
     return ctx_.check(svs_ba_window_from_map(ba_, map.get(), (int)ec.size(), ec.data(), &cam, &prm));
+  }
+  // the same with copyContraintsToG2o done from the map's edge table (svs_ba_window_from_map_edges): nothing but a list of indices is uploaded
+  bool copyDataFromMap(BackendMap &map, const OptParams &opt, const svs_cam &cam) {
+    svs_ba_params prm = params(opt, false);
+    return ctx_.check(svs_ba_window_from_map_edges(ba_, map.get(), &cam, &prm));
   }
   bool optimize(svs_ba_stats *stats = nullptr) { return ctx_.check(svs_ba_optimize(ba_, nullptr, nullptr, stats)); }
   // restoreDataFromG2o on the device: one launch, asynchronous

@@ -182,13 +182,26 @@ class SlamGraphOptimizer:
     def windowFromMap(self, resident_map, cons, cam, prm=None):
         """svs_ba_window_from_map: copyDataToG2o device to device.  The window resident_map.prepare_window left in the map becomes this optimizer's problem:
         poses and psi are read from the map now, the edges are assembled from the map's measured observations, only cons (BA_CONSTRAINT_DTYPE with frame ids
-        of the final window) is uploaded.  restoreDataFromG2o then returns the final window's poses and the active points' psi in the map's order."""
-        cons = np.ascontiguousarray(cons if cons is not None else np.zeros(0, BA_CONSTRAINT_DTYPE), BA_CONSTRAINT_DTYPE)
+        of the final window) is uploaded.  restoreDataFromG2o then returns the final window's poses and the active points' psi in the map's order.
+        cons=None: svs_ba_window_from_map_edges -- copyContraintsToG2o from the map's edge table, gathered on the device (an empty array: no constraints)."""
         prm = prm or BaParams.reference_defaults()
         camc = cam if isinstance(cam, Cam) else Cam(cam["f"], cam["cx"], cam["cy"], cam["b"], cam["w"], cam["h"])
-        self.ctx.check(self.ctx.lib.svs_ba_window_from_map(self.h, resident_map.h, len(cons), cons.ctypes.data if len(cons) else None, C.byref(camc), C.byref(prm)))
+        if cons is None:
+            self.ctx.check(self.ctx.lib.svs_ba_window_from_map_edges(self.h, resident_map.h, C.byref(camc), C.byref(prm)))
+        else:
+            cons = np.ascontiguousarray(cons, BA_CONSTRAINT_DTYPE)
+            self.ctx.check(self.ctx.lib.svs_ba_window_from_map(self.h, resident_map.h, len(cons), cons.ctypes.data if len(cons) else None, C.byref(camc), C.byref(prm)))
         self.prm = prm
         self.P, self.L = resident_map.window_shape
+
+    def window_constraints(self):
+        """svs_ba_window_constraints: the handle's constraints (BA_CONSTRAINT_DTYPE, window indices in pose1 / pose2)"""
+        n = C.c_int32()
+        self.ctx.check(self.ctx.lib.svs_ba_window_constraints(self.h, C.byref(n), None))
+        c = np.zeros(n.value, BA_CONSTRAINT_DTYPE)
+        if n.value:
+            self.ctx.check(self.ctx.lib.svs_ba_window_constraints(self.h, C.byref(n), c.ctypes.data))
+        return c
 
     def storeToMap(self, resident_map):
         """svs_ba_store_to_map: restoreDataFromG2o on the device -- the window's poses and invert_depth(psi) go back into the map (one launch, asynchronous)"""

@@ -8,7 +8,7 @@ import ctypes as C
 import os
 import weakref
 
-from .ctypes_types import BaParams, BaStats, Cam, FastGrid, LoopCheck, LoopLocation, LoopLocationResult, LoopResult, MapWindowResult, NbhRequest, NbhResult, PoseOptParams, PoseOptStats, RegMapRequest, RegParams, RegRequest, RegResult, SeedArgs, SeedParams, SeedRequest, StereoParams, SurfParams, VocabParams, VocabResult
+from .ctypes_types import BaParams, BaStats, Cam, FastGrid, LoopCheck, LoopLocation, LoopLocationResult, LoopResult, MapConstraintRequest, MapWindowResult, NbhRequest, NbhResult, PoseOptParams, PoseOptStats, RegMapRequest, RegParams, RegRequest, RegResult, SeedArgs, SeedParams, SeedRequest, StereoParams, SurfParams, VocabParams, VocabResult
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SVS_LIB_PATH") or os.path.join(_HERE, "libscavislam_hip.so")   # override = kernel A/B experiments only
@@ -223,6 +223,15 @@ _SIGS = {
     "svs_map_add_measured_observations": [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
     "svs_map_measured_info": [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)],
     "svs_map_prepare_window": [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.POINTER(MapWindowResult), C.c_void_p, C.c_void_p],
+    "svs_map_reserve_edges": [C.c_void_p, C.c_int],
+    "svs_map_add_edges": [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p],
+    "svs_map_set_constraints": [C.c_void_p, C.c_int, C.c_void_p],
+    "svs_map_unmarginalize": [C.c_void_p, C.c_int, C.c_void_p],
+    "svs_map_get_edges": [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p],
+    "svs_map_edge_info": [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)],
+    "svs_map_compute_constraints": [C.c_void_p, C.c_int, C.POINTER(MapConstraintRequest), C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p],
+    "svs_ba_window_from_map_edges": [C.c_void_p, C.c_void_p, C.POINTER(Cam), C.POINTER(BaParams)],
+    "svs_ba_window_constraints": [C.c_void_p, C.POINTER(C.c_int32), C.c_void_p],
     "svs_ba_window_from_map": [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(Cam), C.POINTER(BaParams)],
     "svs_ba_store_to_map": [C.c_void_p, C.c_void_p],
     "svs_ba_window_edges": [C.c_void_p, C.POINTER(C.c_int32), C.c_void_p],

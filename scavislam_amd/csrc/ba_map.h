@@ -2,6 +2,7 @@
 // svs_ba_store_to_map (ba_window.inc) read and write it.  Neither translation unit reaches into the other's handle.
 #pragma once
 #include "common.h"
+#include <vector>
 
 // the prepared window (device pointers but for h_window_ids): the pieces of the block win_unpack_kernel reads
 struct MapWindowView {
@@ -14,7 +15,16 @@ struct MapWindowView {
   const svs_ba_edge *store; size_t n_store;      // the measured store: ids in .point / .pose, log order
   int kf_hi, pt_hi;                    // every id of the store is below these
   uint64_t serial;                     // of this prepare (no two prepares of a process share one)
+  const int32_t *h_window_types;       // [P] on the host: 0 INNER / 1 OUTER (the extension is OUTER)
+  const svs_map_edge *edges;           // the edge table's records by slot (nullptr without svs_map_reserve_edges)
 };
+
+// copyContraintsToG2o's list for the prepared window from the host's mirror of the edge table, in the order the header states: (i, j, slot, T_21 is the inverse of
+// the stored T_lo_from_hi) per constraint.  SVS_ERR_INVALID (nothing enqueued) without a valid prepared window or where an edge of the list is not marginalised
+int svs_map_window_constraint_list(svs_map *map, std::vector<int4> *out);
+// one launch, asynchronous: record c of d_out = (T_21, info, pose1 = i, pose2 = j) of d_list[c] from the edge table (pose_inv where the list says so; built in
+// map.hip: no contraction, so the inverse is the one svs_map_set_constraints and the NumPy model form)
+int svs_map_gather_constraints(svs_map *map, const int4 *d_list, int C, svs_ba_constraint *d_out);
 
 svs_ctx *svs_map_ctx(svs_map *map);
 // SVS_ERR_INVALID without a valid prepared window (nothing enqueued); else one launch on the context's stream re-reads the window's poses and psi = (x / z,

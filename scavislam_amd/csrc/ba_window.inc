@@ -539,36 +539,51 @@ static int window_assemble(svs_ba *ba, int P, int L, int C, const WinSrc &S, con
 // ---- the window svs_map_prepare_window left in the map (ba_map.h) ---------------------------------------------------------------------------------------
 // copyDataToG2o device to device: ids, anchors, poses and psi are read where the map's kernels wrote them, the store is the map's measured store, and only the
 // constraints are staged.  Everything that can be refused is refused before the handle is touched.
-extern "C" int svs_ba_window_from_map(svs_ba *ba, svs_map *map, int C, const svs_ba_constraint *h_cons, const svs_cam *cam, const svs_ba_params *prm) {
+// from_edges: the constraints are copyContraintsToG2o's list out of the map's edge table (C and h_cons unused), gathered on the device
+static int window_from_map_impl(svs_ba *ba, svs_map *map, int C, const svs_ba_constraint *h_cons, bool from_edges, const svs_cam *cam, const svs_ba_params *prm) {
   svs_ctx *ctx = ba ? ba->ctx : nullptr;
   SVS_REQUIRE(ctx, ba && map && C >= 0 && (C == 0 || h_cons) && cam && prm);
   SVS_REQUIRE(ctx, svs_map_ctx(map) == ctx);          // one context: one stream orders the map's kernels and the assembly
   SVS_REQUIRE(ctx, !ba->comm);                        // single-GPU path, as svs_ba_window_update
   SVS_DEVICE(ctx);
+  std::vector<int4> list;
+  if (from_edges) {                                   // (an edge that is not marginalised, no valid prepared window: nothing enqueued)
+    if (int rc = svs_map_window_constraint_list(map, &list)) return rc;
+    C = (int)list.size();
+  }
   MapWindowView V;
   if (int rc = svs_map_window_view(map, &V)) return rc;      // no valid prepared window: nothing enqueued
   const int P = V.P, L = V.L;
   SVS_REQUIRE(ctx, P >= 1 && P <= SOLVE_MAX_P && L >= 0 && L < (1 << 23) && V.n_store < (size_t)INT_MAX - 1);
   auto t_0 = std::chrono::steady_clock::now();
   std::vector<svs_ba_constraint> cons_idx((size_t)C);
-  for (int c = 0; c < C; ++c) {
+  for (int c = 0; c < C && !from_edges; ++c) {
     cons_idx[c] = h_cons[c];
     int i1 = -1, i2 = -1;
     for (int i = 0; i < P; ++i) { if (V.h_window_ids[i] == h_cons[c].pose1) i1 = i; if (V.h_window_ids[i] == h_cons[c].pose2) i2 = i; }
     SVS_REQUIRE(ctx, i1 >= 0 && i2 >= 0);                   // a constraint of this window names two keyframes of the final window
     cons_idx[c].pose1 = i1; cons_idx[c].pose2 = i2;
   }
+  for (int c = 0; c < C && from_edges; ++c) { cons_idx[c] = svs_ba_constraint{}; cons_idx[c].pose1 = list[c].x; cons_idx[c].pose2 = list[c].y; }      // (the host reads the indices only)
   ba->problem_valid = false; ba->from_map_serial = 0;
   ba->w_cons_idx.swap(cons_idx);
   SVS_HIP(ctx, hipStreamSynchronize(ctx->stream));
   ba->h_stage_used = 0;
-  const size_t cons_bytes = sizeof(svs_ba_constraint) * (size_t)C;
-  { int rc = stage_reserve(ba, cons_bytes + sizeof(int) * (V.n_store / 8 + 8 * (size_t)P) + 16384); if (rc) return rc; }
-  SVS_HIP(ctx, ba->w_in.reserve_keep(cons_bytes + 256, cons_bytes + cons_bytes / 2 + 4096, 0));
-  if (C) {
+  const size_t cons_bytes = sizeof(svs_ba_constraint) * (size_t)C, o_list = (cons_bytes + 255) & ~(size_t)255, list_bytes = from_edges ? sizeof(int4) * (size_t)C : 0,
+               in_bytes = o_list + list_bytes;
+  { int rc = stage_reserve(ba, in_bytes + sizeof(int) * (V.n_store / 8 + 8 * (size_t)P) + 16384); if (rc) return rc; }
+  SVS_HIP(ctx, ba->w_in.reserve_keep(in_bytes + 256, in_bytes + in_bytes / 2 + 4096, 0));
+  if (C && !from_edges) {
     std::memcpy(ba->h_stage.get(), ba->w_cons_idx.data(), cons_bytes);
     ba->h_stage_used = (cons_bytes + 255) & ~(size_t)255;
     SVS_HIP(ctx, hipMemcpyAsync(ba->w_in, ba->h_stage.get(), cons_bytes, hipMemcpyHostToDevice, ctx->stream));
+  }
+  if (C && from_edges) {                              // the integer list crosses the link; the records are written where win_unpack_kernel reads them
+    std::memcpy(ba->h_stage.get(), list.data(), list_bytes);
+    ba->h_stage_used = (list_bytes + 255) & ~(size_t)255;
+    char *IN = static_cast<char *>(ba->w_in.get());
+    SVS_HIP(ctx, hipMemcpyAsync(IN + o_list, ba->h_stage.get(), list_bytes, hipMemcpyHostToDevice, ctx->stream));
+    if (int rc = svs_map_gather_constraints(map, reinterpret_cast<const int4 *>(IN + o_list), C, reinterpret_cast<svs_ba_constraint *>(IN))) return rc;
   }
   WinSrc S;
   S.pids = V.window_ids; S.lids = V.active_ids; S.aids = V.anchor_ids; S.poses = V.poses; S.psi = V.psi; S.obs = nullptr;
@@ -578,6 +593,25 @@ extern "C" int svs_ba_window_from_map(svs_ba *ba, svs_map *map, int C, const svs
   const int rc = window_assemble(ba, P, L, C, S, cam, prm, t_0, std::chrono::steady_clock::now());
   if (rc == SVS_OK) ba->from_map_serial = V.serial;
   return rc;
+}
+
+extern "C" int svs_ba_window_from_map(svs_ba *ba, svs_map *map, int C, const svs_ba_constraint *h_cons, const svs_cam *cam, const svs_ba_params *prm) {
+  return window_from_map_impl(ba, map, C, h_cons, false, cam, prm);
+}
+
+extern "C" int svs_ba_window_from_map_edges(svs_ba *ba, svs_map *map, const svs_cam *cam, const svs_ba_params *prm) {
+  return window_from_map_impl(ba, map, 0, nullptr, true, cam, prm);
+}
+
+extern "C" int svs_ba_window_constraints(svs_ba *ba, int32_t *n, svs_ba_constraint *h_cons) {
+  svs_ctx *ctx = ba ? ba->ctx : nullptr;
+  SVS_REQUIRE(ctx, ba && n && ba->problem_valid);
+  *n = ba->C;
+  if (!h_cons || ba->C == 0) return SVS_OK;
+  SVS_DEVICE(ctx);
+  SVS_HIP(ctx, hipMemcpyAsync(h_cons, ba->d_cons, sizeof(svs_ba_constraint) * (size_t)ba->C, hipMemcpyDeviceToHost, ctx->stream));
+  SVS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return SVS_OK;
 }
 
 extern "C" int svs_ba_store_to_map(svs_ba *ba, svs_map *map) {

@@ -279,3 +279,23 @@ class MapWindowResult(C.Structure):
 
 assert C.sizeof(MapWindowResult) == 16
 MAP_WINDOW_MAX = 256      # the solve's limit on a window's keyframes
+
+
+# ---- back end: the pose graph's edges in the map and their constraints (svs_map_add_edges .. svs_map_compute_constraints)
+MAP_EDGE_DTYPE = np.dtype([("lo", "<i4"), ("hi", "<i4"), ("strength", "<i4"), ("edge_type", "<i4"), ("is_marginalized", "<i4"), ("pad_", "<i4"),
+                           ("T_lo_from_hi", "<f8", 12), ("info", "<f8", 36)])
+MAP_CONSTRAINT_RESULT_DTYPE = np.dtype([("status", "<i4"), ("strength", "<i4"), ("n_missing", "<i4"), ("pad_", "<i4"), ("median", "<f8"), ("norm_dist", "<f8"),
+                                        ("T_12", "<f8", 12), ("info", "<f8", 36)])
+assert MAP_EDGE_DTYPE.itemsize == 408 and MAP_CONSTRAINT_RESULT_DTYPE.itemsize == 416
+EDGE_LOCAL, EDGE_METRIC, EDGE_APPEARANCE = 0, 1, 2
+CONS_OK, CONS_EMPTY, CONS_MISSING_ANCHOR = 0, 1, 2
+MAP_CONS_MAX_REQUESTS = 256
+
+
+class MapConstraintRequest(C.Structure):
+    """svs_map_constraint_request: computeConstraint(kf1, kf2), up to two pose overrides, the caller's cached anchor poses (ids strictly ascending)"""
+    _fields_ = [("kf1", C.c_int32), ("kf2", C.c_int32), ("store", C.c_int32), ("n_override", C.c_int32), ("override_id", C.c_int32 * 2), ("n_cached", C.c_int32),
+                ("pad_", C.c_int32), ("override_T", (C.c_double * 12) * 2), ("cached_ids", C.c_void_p), ("cached_T", C.c_void_p)]
+
+
+assert C.sizeof(MapConstraintRequest) == 240

@@ -15,8 +15,8 @@ import ctypes as C
 
 import numpy as np
 
-from .ctypes_types import (CANDIDATE_DTYPE, KEYFRAME_DTYPE, MAP_WINDOW_MAX, MATCH_RESULT_DTYPE, REG_KF_STATS_DTYPE, REG_LOCAL, REG_LOOP, REG_OK, REG_OVER_CAPACITY,
-                           REG_STAGES, SVS_MAX_CELLS, Cam, MapWindowResult, RegMapRequest, RegParams, RegRequest, RegResult)
+from .ctypes_types import (BA_CONSTRAINT_DTYPE, CANDIDATE_DTYPE, CONS_OK, KEYFRAME_DTYPE, MAP_CONSTRAINT_RESULT_DTYPE, MAP_EDGE_DTYPE, MAP_WINDOW_MAX, MATCH_RESULT_DTYPE, REG_KF_STATS_DTYPE, REG_LOCAL, REG_LOOP, REG_OK, REG_OVER_CAPACITY,
+                           REG_STAGES, SVS_MAX_CELLS, Cam, MapConstraintRequest, MapWindowResult, RegMapRequest, RegParams, RegRequest, RegResult)
 
 
 def keyframe_table(entries):
@@ -193,6 +193,24 @@ class KeyframeRegistrar:
             pass
 
 
+def _inner_pairs_with_edge(window, edge_keys):
+    ids, types = window
+    inner = sorted(int(k) for k, t in zip(ids, types) if int(t) == 0)
+    return [(a, b) for i, a in enumerate(inner) for b in inner[i + 1:] if (a, b) in edge_keys]
+
+
+def entering_inner_pairs(new_window, edge_keys):
+    """unmargPosesEnteringInnerW (slam_graph.cpp:728-759): every edge between two INNER keyframes of the window, once, as (lo, hi) ascending"""
+    return _inner_pairs_with_edge(new_window, edge_keys)
+
+
+def left_inner_pairs(old_window, new_window, edge_keys):
+    """margPosesLeftInnerWindow (:848-904): every edge between two INNER keyframes of the old window of which at least one is not INNER now, once, as (lo, hi)
+    ascending.  The reference computes both orientations and keeps the one its hash order visits last; here kf1 is the smaller id"""
+    inner_now = {int(k) for k, t in zip(*new_window) if int(t) == 0}
+    return [(a, b) for a, b in _inner_pairs_with_edge(old_window, edge_keys) if a not in inner_now or b not in inner_now]
+
+
 class ResidentMap:
     """svs_map: the back end's map in device memory, under the graph's own ids (dense, below the capacities).  Every update is one staged upload, asynchronous
     on the context's stream, and is refused as a whole (SvsError, the map unchanged) on an unknown, repeated or out-of-range id."""
@@ -203,6 +221,7 @@ class ResidentMap:
         ctx.call("svs_map_create", int(max_keyframes), int(max_points), int(max_observations), C.byref(h))
         self.h = h
         self.window_shape = None
+        self.edge_keys = set()               # (lo, hi) of every edge: what update_marginalization selects its pairs from
         ctx.children.add(self)
 
     def _call(self, name, *args):
@@ -292,6 +311,95 @@ class ResidentMap:
         """graph_.double_window(): exactly these keyframes are in the window afterwards"""
         k = np.ascontiguousarray(kf_ids, np.int32).reshape(-1)
         self._call("svs_map_set_window", len(k), k.ctypes.data)
+
+    # ---- the pose graph's edges (EdgeTable, slam_graph.hpp:197-363) and their constraints (computeConstraint, slam_graph.cpp:787-846)
+    def reserve_edges(self, max_edges):
+        """room for the edge table (once); without it every edge call is refused"""
+        self._call("svs_map_reserve_edges", int(max_edges))
+
+    def add_edges(self, pairs, strength, edge_type):
+        """insertEdge for pairs [n, 2] (either orientation); a new edge is not marginalised"""
+        e = np.ascontiguousarray(pairs, np.int32).reshape(-1, 2)
+        s = np.ascontiguousarray(np.broadcast_to(np.asarray(strength, np.int32), (len(e),)))
+        t = np.ascontiguousarray(np.broadcast_to(np.asarray(edge_type, np.int32), (len(e),)))
+        self._call("svs_map_add_edges", len(e), e.ctypes.data, s.ctypes.data, t.ctypes.data)
+        self.edge_keys.update((int(min(a, b)), int(max(a, b))) for a, b in e)
+
+    def set_constraints(self, cons):
+        """setConstraint with the caller's values: BA_CONSTRAINT_DTYPE, pose1 / pose2 name the edge, T_21 = T_pose2_from_pose1; marks the edges marginalised"""
+        c = np.ascontiguousarray(cons, BA_CONSTRAINT_DTYPE).reshape(-1)
+        self._call("svs_map_set_constraints", len(c), c.ctypes.data)
+
+    def unmarginalize(self, pairs):
+        """unMarginalize: clears the flag only"""
+        e = np.ascontiguousarray(pairs, np.int32).reshape(-1, 2)
+        self._call("svs_map_unmarginalize", len(e), e.ctypes.data)
+
+    def get_edges(self, pairs):
+        """blocking read-back of the records (MAP_EDGE_DTYPE: T_lo_from_hi, ONE info for both directions)"""
+        e = np.ascontiguousarray(pairs, np.int32).reshape(-1, 2)
+        out = np.zeros(len(e), MAP_EDGE_DTYPE)
+        self._call("svs_map_get_edges", len(e), e.ctypes.data, out.ctypes.data)
+        return out
+
+    def edge_info(self):
+        """(edges, marginalised edges): the host-side counts"""
+        a, b = C.c_int32(), C.c_int32()
+        self._call("svs_map_edge_info", C.byref(a), C.byref(b))
+        return a.value, b.value
+
+    def compute_constraints(self, requests, missing_cap=16, depth_cap=0):
+        """svs_map_compute_constraints: computeConstraint for a batch, one blocking call.  A request is a dict: kf1, kf2, store (False), overrides ([(id, T[12])], at
+        most two: the request's pose of that keyframe, also as an anchor), cached ({anchor id: T_anchor_from_world[12]}: the caller's computeAbsolutePose results).
+        Returns one dict per request: status (CONS_OK / CONS_EMPTY / CONS_MISSING_ANCHOR), strength, median, norm_dist, T_12 [12], info [36], n_missing, missing
+        (ascending ids, at most missing_cap) and, with depth_cap > 0, depths (ascending point id).  self.raw keeps the three arrays as the library wrote them"""
+        n = len(requests)
+        arr = (MapConstraintRequest * max(n, 1))()
+        keep = []
+        for i, q in enumerate(requests):
+            r = arr[i]
+            r.kf1, r.kf2, r.store = int(q["kf1"]), int(q["kf2"]), int(bool(q.get("store", False)))
+            ov = list(q.get("overrides", ()))
+            if len(ov) > 2:
+                raise ValueError("at most two pose overrides per request")
+            r.n_override = len(ov)
+            for k, (kid, T) in enumerate(ov):
+                r.override_id[k] = int(kid)
+                r.override_T[k][:] = np.asarray(T, np.float64).reshape(12).tolist()
+            cached = q.get("cached") or {}
+            ids = np.array(sorted(int(k) for k in cached), np.int32)
+            T = np.ascontiguousarray([np.asarray(cached[int(k)], np.float64).reshape(12) for k in ids], np.float64).reshape(len(ids), 12)
+            keep.append((ids, T))
+            r.n_cached = len(ids)
+            r.cached_ids, r.cached_T = (ids.ctypes.data, T.ctypes.data) if len(ids) else (None, None)
+        res = np.zeros(n, MAP_CONSTRAINT_RESULT_DTYPE)
+        missing = np.full((n, int(missing_cap)), -1, np.int32)
+        depths = np.zeros((n, int(depth_cap)), np.float64)
+        self._call("svs_map_compute_constraints", n, arr, int(missing_cap), res.ctypes.data, missing.ctypes.data if missing_cap else None, int(depth_cap),
+                   depths.ctypes.data if depth_cap else None)
+        self.raw = dict(results=res, missing=missing, depths=depths)
+        out = []
+        for i in range(n):
+            o = dict(status=int(res[i]["status"]), strength=int(res[i]["strength"]), n_missing=int(res[i]["n_missing"]), median=float(res[i]["median"]),
+                     norm_dist=float(res[i]["norm_dist"]), T_12=res[i]["T_12"].copy(), info=res[i]["info"].copy(),
+                     missing=missing[i, :min(int(res[i]["n_missing"]), int(missing_cap))].copy())
+            if depth_cap:
+                o["depths"] = depths[i, :o["strength"] if o["status"] == CONS_OK else 0].copy()
+            out.append(o)
+        return out
+
+    def update_marginalization(self, old_window, new_window, cached=None, missing_cap=64):
+        """unmargPosesEnteringInnerW (slam_graph.cpp:728-759) and margPosesLeftInnerWindow (:848-904): windows are (ids, types) with 0 INNER / 1 OUTER, the pairs are
+        selected on the host from the edge keys; one unmarginalize, then one storing compute_constraints.  The map's window flags must be those of new_window
+        (computeConstraint asks double_window_ for an anchor's pose).  Returns (results, missing): `missing` is the sorted union of the anchors some request
+        lacked -- the caller adds their computeAbsolutePose results to `cached` and repeats; a repeat unmarginalises and recomputes the same pairs"""
+        enter = entering_inner_pairs(new_window, self.edge_keys)
+        left = left_inner_pairs(old_window, new_window, self.edge_keys)
+        if enter:
+            self.unmarginalize(enter)
+        res = self.compute_constraints([dict(kf1=a, kf2=b, store=True, cached=cached) for a, b in left], missing_cap=missing_cap) if left else []
+        missing = sorted({int(k) for o in res for k in o["missing"]})
+        return res, missing
 
     def info(self):
         """(keyframes, points, distinct observations)"""
