@@ -128,7 +128,8 @@ int svs_ctx_sync(svs_ctx *ctx);
    point with the lean scan), "mo_legacy" (1: the record-walking motion-only kernel), "fe_overlap" (default 1: the one-call
    front end enqueues FAST / block matching on a side stream beside the dense tracker; 0: everything on the context's stream),
    "xcd_swizzle" (default 1: tile kernels whose neighbours share image lines -- FAST score, pyramid, block matching, the four-points-per-wave matcher -- take their
-   blocks in XCD-contiguous order; 0: the dispatcher's round robin),
+   blocks in XCD-contiguous order; 0: the dispatcher's round robin), "fast_floor" (default 1: the FAST score kernel scores and lists only from the lowest threshold a
+   cell's stored threshold lets the detection reach; 0: from the lowest threshold any cell can take),
    "trk_balance" (default 1: batches of two or more streams per CU launch the tracker's workgroups in the order of the LM work their streams needed in the
    last frame; 0: stream order; larger values count as 1; initial value from SVS_TRK_BALANCE), "trk_split" (default 10: in batches of more than one stream
    per CU, which run the flat tracker kernel, a stream still iterating after that many trials on the finest level is

@@ -32,6 +32,8 @@ struct svs_ctx {
   int mo_spec = 1;            // "mo_spec": calcFastMotionOnly's trials behind a rejection run a chi2-only sweep (the full one follows if the trial is accepted after all); 0: always full
   int fe_fuse_tail = 1;       // "fe_fuse_tail": the one-call front end runs the gate and the dense clouds inside the refinement kernel (0: four more launches)
   int match_order = 1;        // "match_order": match_kernel3 takes the points of a stream in image order (counting sort by cell of the predicted position), 0: list order
+  int fast_floor = 1;         // "fast_floor": the FAST score kernel pre-tests, scores and lists from each cell's own floor up (its stored threshold less what the frame's
+                              // trials can lower it by, fast.hip); 0: from the global t_lo up (A/B runs and tests).  Results identical.
   int fe_pipeline = 1;        // "fe_pipeline" (read at svs_frontend_create and per call): svs_frontend_process_frames on caller-owned device frames builds the pyramid
                               // of frame N+1 on the side stream while frame N's pose refinement / gate / cloud run (frontend.hip).  Results identical.
   int fe_overlap = 1;         // "fe_overlap": the one-call front end runs FAST / block matching on a side stream beside the dense tracker (0: one stream)

@@ -17,6 +17,7 @@ struct FastListView {
 };
 FastListView svs_fast_list_view_internal(const svs_fast *f);
 // the persistent per-cell thresholds (cell_grid2d()): cell c of level l of slot s at thr[s * ncell_total + cell_base[l] + c].  register.hip writes a request's stored
-// thresholds there on the device (what svs_fast_set_thresholds does from the host); a threshold below t_lo would ask for scores that are not kept
+// thresholds there on the device (what svs_fast_set_thresholds does from the host); a threshold below t_lo would ask for scores that are not kept.  The score kernel
+// derives each cell's score floor from these words when it runs (fast.hip, "fast_floor"), so a write that is ordered before the detection is all it takes
 struct FastThrView { int *thr; int ncell_total, t_lo; int cell_base[SVS_NUM_PYR_LEVELS], ncell[SVS_NUM_PYR_LEVELS]; int n_levels, batch; };
 FastThrView svs_fast_thr_view_internal(svs_fast *f);
