@@ -1002,7 +1002,7 @@ int svs_map_info(svs_map *map, int32_t *n_keyframes, int32_t *n_points, int32_t 
 int svs_map_add_measured_observations(svs_map *map, int n, const int32_t *h_point_ids, const int32_t *h_kf_ids, const double *h_center /* [n][3] */,
                                       const int32_t *h_level /* [n] */);
 int svs_map_measured_info(svs_map *map, int32_t *n_measured, int32_t *n_unmeasured);
-/* computeActivePointsAndExtendOuterWindow (slam_graph.cpp:599-663) on the device.  The caller keeps computeInitialDoubleWin and the edge_table_: it passes W0 =
+/* computeActivePointsAndExtendOuterWindow (slam_graph.cpp:599-663) on the device.  The caller may keep computeInitialDoubleWin and the edge_table_ (svs_map_prepare_window_from_root finds both on the device): it passes W0 =
    double_window_ before the extension (ids, types 0 INNER / 1 OUTER, in its order) and the edge_table_ entries with at least one end in an INNER keyframe of W0,
    in either orientation.  The reference extends double_window_ only at the end (:662), so its result is a statement about sets:
      1. point p is ACTIVE iff some INNER keyframe F of W0 has p in its feature_table and either anchor(p) is in W0 or (F, anchor(p)) is among the pairs.  A point
@@ -1055,9 +1055,9 @@ int svs_map_edge_info(svs_map *map, int32_t *n_edges, int32_t *n_marginalized);
 /* computeConstraint (slam_graph.cpp:787-846) for a batch of keyframe pairs, one workgroup per request, as a statement that does not depend on hash order:
      common points   the points of kf1's feature_table that are also in kf2's, in ascending point id;
      anchor pose     of a common point: a pose override of the request if the anchor is named there; else the map's pose if the anchor has SVS_REG_KF_IN_WINDOW
-                     (double_window_, :809-813); else its entry in the request's cached list (the caller's computeAbsolutePose results -- shortestPathToWindow
-                     is a graph search and stays with the caller); else the request ends with SVS_CONS_MISSING_ANCHOR and returns the missing anchor ids
-                     ascending, each once, up to missing_cap, with n_missing = their total count: the caller walks its graph for exactly those and calls again;
+                     (double_window_, :809-813); else its entry in the request's cached list (computeAbsolutePose results: the caller's own, or those of
+                     svs_map_absolute_poses, which runs shortestPathToWindow on the map); else the request ends with SVS_CONS_MISSING_ANCHOR and returns the missing anchor ids
+                     ascending, each once, up to missing_cap, with n_missing = their total count: the caller asks svs_map_absolute_poses (or walks its own graph) for exactly those and calls again;
      depth           d = || T1 inv(T_anchor) xyz_anchor || evaluated right to left on the vector: pose_act(T1, pose_act(pose_inv(T_anchor), xyz)), rows
                      ((a0 b0 + a1 b1) + a2 b2) + t, no contraction, sqrt((x x + y y) + z z) in f64;
      strength        the number of common points;
@@ -1096,6 +1096,55 @@ typedef struct {
 int svs_map_compute_constraints(svs_map *map, int n_requests, const svs_map_constraint_request *req, int missing_cap, svs_map_constraint_result *h_res,
                                 int32_t *h_missing, int depth_cap, double *h_depths);
 
+/* ---- the pose graph's walks on the map: computeInitialDoubleWin (slam_graph.cpp:555-596), framesInNeighborhood (:105-140), shortestPathToWindow +
+   computeAbsolutePose (:64-103, :762-782), reinitializePoses (:665-725).  All four are one breadth-first search that pushes a vertex's neighbours in
+   neighbor_ids_ordered_by_strength.rbegin() .. rend() order and drops duplicates at pop.  Two facts make it a function of the edge table alone:
+     1. ADJACENCY COMES FROM THE EDGE TABLE.  Every insertion into neighbor_ids_ordered_by_strength (:222-225, :442-445) is paired with an insertEdge of the same
+        strength, the strength is never updated, and a multimap keeps equal keys in insertion order.  The reverse walk of a keyframe's neighbours is therefore its
+        edges in DESCENDING (strength, edge slot), the slot being the svs_map_add_edges log order; findNeighborsOfRoot (backend.cpp:287-309) walks the same row
+        forwards.  The device keeps these rows as a CSR over keyframe ids, rebuilt by the first walk behind an svs_map_add_edges (count, scan, fill, a rank sort
+        per row that is correct for a row of any length).
+     2. VISITED-AT-POP EQUALS VISITED-AT-PUSH.  With a FIFO queue the order in which vertices are first popped is the order in which they are first pushed, and
+        the copy that is processed carries the path, parent, parent pose and mark of the first pusher.  So the visit order is "frontier in order, each frontier
+        vertex's row in order, first claim wins": a minimum over (visit index of the claimer, rank in its row), which no arrival order of an atomic changes.
+   One workgroup per request; a request's bytes do not depend on the rest of its batch.  Every call is BLOCKING: one staged upload, at most the adjacency rebuild
+   plus one launch (svs_map_prepare_window_from_root: plus svs_map_prepare_window's two and a second download), one download.  Refused as a whole before anything
+   is uploaded -- SVS_ERR_INVALID: an unknown id, inner_size < 1 or >= double_size, size < 1; SVS_ERR_CAPACITY: more than SVS_MAP_WALK_MAX_REQUESTS requests,
+   double_size > window_cap, a cap above 16384 (svs_map_prepare_window_from_root: window_cap > 256).  A map without svs_map_reserve_edges has no edges: every
+   walk ends at its root.
+   svs_map_initial_windows: per root the keyframes in visit order up to double_size (the walk stops exactly there, inside a row or a level, or earlier when the
+     component is exhausted); the first inner_size visited are INNER (0), the rest OUTER (1).  h_ids / h_type [n][window_cap], -1 behind a request's count.
+   svs_map_frames_in_neighborhood: the same search over the keyframes that have SVS_REG_KF_IN_WINDOW: a keyframe outside the window is skipped and not expanded,
+     a root outside it gives count 0; at most `size` ids.  The reference returns a hash set; here the ids come in VISIT ORDER, h_ids [n][size], -1 behind the
+     count, directly usable as h_walk_kf of svs_reg_register_map_batch.
+   svs_map_absolute_poses: per keyframe x the path x .. w to the first keyframe w in visit order that is in the window (recognised before it would be expanded; x
+     itself in the window: path length 1, T = its stored pose unchanged), then T = pose(w) and, from the back of the path to its front,
+     T = pose_mul(rel(new, cur), T) with rel(1, 2) = getRelativePose_1_from_2 (:271-286): the edge's stored pose where is_marginalized is set (T_lo_from_hi
+     when 1 is lo, pose_inv of it when 1 is hi), else pose_mul(pose(1), pose_inv(pose(2))); f64, rows ((a0 b0 + a1 b1) + a2 b2) + t, no contraction.
+     h_status SVS_WALK_OK / SVS_WALK_NO_PATH (no window keyframe in x's component: the reference asserts; T zero, path length 0); h_path_len optional; h_T
+     [n][12]; h_path [n][path_cap] (optional with path_cap 0): the first path_cap ids of the path from x, -1 behind them.
+   svs_map_reinitialize_poses: the search from root_id over the keyframes that have SVS_REG_KF_IN_WINDOW (the new, extended window; others are skipped, not
+     expanded, not marked).  A keyframe with a parent takes T = pose_mul(rel(me, parent), T_parent) if it or an ancestor is loop_id (-1: none), or if it is not
+     among h_old_window; T_parent and the parent's pose inside rel are the parent's after its own update (level by level).  The root is never changed.  Writes
+     the map's poses as svs_map_set_poses would; h_changed [changed_cap] (optional with 0): the changed ids in visit order, -1 behind them; *h_n_changed their
+     total count.
+   svs_map_get_poses: BLOCKING read-back of T_me_from_world [n][12] of the named keyframes.
+   svs_map_prepare_window_from_root: the first two steps of prepareForOptimization (:297-298) from the root alone: the initial window is found on the device, the
+     "edge_table_ entries with at least one end in an INNER keyframe" are the adjacency rows of its INNER keyframes, left on the device, and svs_map_prepare_window's
+     two kernels run on them unchanged: result, window lists, flags and the prepared window are byte for byte those of svs_map_prepare_window called with that W0
+     (visit order) and those pairs.  Everything else as svs_map_prepare_window states. */
+enum { SVS_WALK_OK = 0, SVS_WALK_NO_PATH = 1 };
+enum { SVS_MAP_WALK_MAX_REQUESTS = 256 };
+int svs_map_initial_windows(svs_map *map, int n, const int32_t *h_root_ids, int inner_size, int double_size, int window_cap, int32_t *h_count, int32_t *h_ids,
+                            int32_t *h_type);
+int svs_map_frames_in_neighborhood(svs_map *map, int n, const int32_t *h_root_ids, int size, int32_t *h_count, int32_t *h_ids);
+int svs_map_absolute_poses(svs_map *map, int n, const int32_t *h_kf_ids, int path_cap, int32_t *h_status, int32_t *h_path_len, double *h_T, int32_t *h_path);
+int svs_map_reinitialize_poses(svs_map *map, int32_t root_id, int32_t loop_id, int n_old, const int32_t *h_old_window, int changed_cap, int32_t *h_n_changed,
+                               int32_t *h_changed);
+int svs_map_get_poses(svs_map *map, int n, const int32_t *h_kf_ids, double *h_poses);
+int svs_map_prepare_window_from_root(svs_map *map, int32_t root_id, int inner_size, int double_size, int set_window_flags, int window_cap,
+                                     svs_map_window_result *h_res, int32_t *h_window_ids, int32_t *h_window_type);
+
 /* A request by ids.  The device builds the svs_reg_request of the stateless call from the map:
      1. source points.  SVS_REG_LOCAL: every point with at least one observation in a keyframe of h_walk_kf that is not the root and not in h_direct_kf
         (:481-497; the root is a direct neighbour, :433-449).  SVS_REG_LOOP: every point observed by h_walk_kf[0], the query keyframe (:853-858).  Each point
@@ -1112,7 +1161,7 @@ typedef struct {
   int32_t root_kf;                     /* id */
   int32_t n_walk, n_direct;            /* each <= the registrar's max_keyframes; SVS_REG_LOOP: n_walk >= 1 */
   double T_root_from_world[12];
-  const int32_t *h_walk_kf;            /* HOST [n_walk]: framesInNeighborhood(root) / the query keyframe */
+  const int32_t *h_walk_kf;            /* HOST [n_walk]: framesInNeighborhood(root) (the caller's, or svs_map_frames_in_neighborhood's) / the query keyframe */
   const int32_t *h_direct_kf;          /* HOST [n_direct]: directNeighborsOf(root); the root need not be listed */
 } svs_reg_map_request;
 /* BLOCKING: one staged upload of ids, one download, no host synchronisation in between (the first call behind an svs_map_add_observations also rebuilds the
@@ -1137,7 +1186,7 @@ int svs_reg_register_map_batch(svs_reg *reg, svs_map *map, int n_requests, const
         anchor_obs_pyr, anchor_level, point_id = its id.
      2. vertex set.  The ids of h_vertex_kf in the given order; behind them, in ascending id, the anchors of rule 1's points that are not among them.  Each with
         T_me_from_world AS THE MAP STORES IT: for a keyframe outside the window the reference calls computeAbsolutePose (:363) -- the caller keeps the map's pose
-        of such a keyframe current through svs_map_set_poses.
+        of such a keyframe current through svs_map_set_poses (it may take it from svs_map_absolute_poses instead of a graph of its own).
      3. slots.  kf_index of a record of rule 1 is the slot s with h_slot_kf[s] == the anchor's id, -1 when no slot holds it (the matcher answers -1 with
         SVS_MATCH_NO_ANCHOR, matcher.cpp:336-339).  An entry of h_slot_kf that is < 0, or an id that is no keyframe of the map, holds no anchor.
      4. the stream's list becomes: the n_head head records in n_head_groups groups (as svs_frontend_set_candidates_grouped takes groups 0 .. G-2), then rule 1's

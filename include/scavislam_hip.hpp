@@ -940,6 +940,7 @@ class BackendMap {
                           std::vector<int32_t> *missing = nullptr, int missing_cap = 64) {
     if (!ok_ || !results || missing_cap < 1) return false;
     results->resize(requests.size());
+    if (requests.empty()) { if (missing) missing->clear(); return true; }      // (nothing to ask: an empty vector has no data() to pass)
     std::vector<int32_t> miss(requests.size() * (size_t)missing_cap, -1);
     if (!ctx_.check(svs_map_compute_constraints(map_, (int)requests.size(), requests.data(), missing_cap, results->data(), miss.data(), 0, nullptr))) return false;
     if (missing) {
@@ -973,6 +974,91 @@ class BackendMap {
     std::vector<svs_map_constraint_result> local;
     return computeConstraints(req, results ? results : &local, missing);
   }
+  // ---- the pose graph's walks on the device (svs_map_initial_windows .. svs_map_prepare_window_from_root): ids come in the visit order of the reference's queue
+  bool computeInitialDoubleWin(int root_id, int inner_window_size, int double_window_size, std::vector<int32_t> *window, std::vector<int32_t> *types) {
+    if (!ok_ || !window || !types || double_window_size < 1) return false;
+    int32_t root = root_id, count = 0;
+    std::vector<int32_t> ids((size_t)double_window_size), ty((size_t)double_window_size);
+    if (!ctx_.check(svs_map_initial_windows(map_, 1, &root, inner_window_size, double_window_size, double_window_size, &count, ids.data(), ty.data()))) return false;
+    window->assign(ids.begin(), ids.begin() + count); types->assign(ty.begin(), ty.begin() + count);
+    return true;
+  }
+  bool framesInNeighborhood(int root_id, int size_of_neighborhood, std::vector<int32_t> *ids) {
+    if (!ok_ || !ids || size_of_neighborhood < 1) return false;
+    int32_t root = root_id, count = 0;
+    std::vector<int32_t> out((size_t)size_of_neighborhood);
+    if (!ctx_.check(svs_map_frames_in_neighborhood(map_, 1, &root, size_of_neighborhood, &count, out.data()))) return false;
+    ids->assign(out.begin(), out.begin() + count);
+    return true;
+  }
+  // computeAbsolutePose for a batch: T12 [n][12], status SVS_WALK_OK / SVS_WALK_NO_PATH (T zero) per id; at most SVS_MAP_WALK_MAX_REQUESTS ids per device call
+  bool computeAbsolutePoses(const std::vector<int32_t> &kf_ids, std::vector<double> *T12, std::vector<int32_t> *status) {
+    if (!ok_ || !T12 || !status) return false;
+    T12->assign(12 * kf_ids.size(), 0.0); status->assign(kf_ids.size(), SVS_WALK_NO_PATH);
+    for (size_t at = 0; at < kf_ids.size(); at += SVS_MAP_WALK_MAX_REQUESTS) {
+      const int n = (int)std::min(kf_ids.size() - at, (size_t)SVS_MAP_WALK_MAX_REQUESTS);
+      if (!ctx_.check(svs_map_absolute_poses(map_, n, kf_ids.data() + at, 0, status->data() + at, nullptr, T12->data() + 12 * at, nullptr))) return false;
+    }
+    return true;
+  }
+  // false also where no path leads to the window (the reference asserts)
+  bool computeAbsolutePose(int x_id, double T_x_from_w[12]) {
+    std::vector<double> T; std::vector<int32_t> st;
+    if (!computeAbsolutePoses(std::vector<int32_t>(1, x_id), &T, &st) || st[0] != SVS_WALK_OK) return false;
+    std::copy(T.begin(), T.end(), T_x_from_w);
+    return true;
+  }
+  // reinitializePoses over the keyframes of the map's window; changed (optional): the ids whose pose was rewritten, in visit order
+  bool reinitializePoses(int root_id, const std::vector<int32_t> &old_window, int loop_id, std::vector<int32_t> *changed = nullptr) {
+    if (!ok_) return false;
+    int32_t n_kf = 0, n_changed = 0;
+    if (!ctx_.check(svs_map_info(map_, &n_kf, nullptr, nullptr))) return false;
+    std::vector<int32_t> out((size_t)std::max(n_kf, 1));
+    if (!ctx_.check(svs_map_reinitialize_poses(map_, root_id, loop_id, (int)old_window.size(), old_window.empty() ? nullptr : old_window.data(), n_kf, &n_changed,
+                                               out.data()))) return false;
+    if (changed) changed->assign(out.begin(), out.begin() + std::min(n_changed, n_kf));
+    return true;
+  }
+  void setWindowSizes(int inner_window_size, int double_window_size) { inner_size_ = inner_window_size; double_size_ = double_window_size; }
+  // SlamGraph::prepareForOptimization (:288-310) from the root alone: the window from the root on the device, reinitializePoses against the window this object
+  // prepared last, then updateMarginalization, whose missing anchors computeAbsolutePoses answers until none that has a path is left.  window / types: the final
+  // window.  false: refused, the final window exceeds 256 keyframes, or it holds fewer than two (:303)
+  bool prepareForOptimization(int root_id, int loop_id, std::vector<int32_t> *window, std::vector<int32_t> *types, int *n_active = nullptr,
+                              std::vector<svs_map_constraint_result> *results = nullptr, std::vector<int32_t> *missing = nullptr) {
+    if (!ok_ || !window || !types) return false;
+    svs_map_window_result r;
+    std::vector<int32_t> ids(256), ty(256);
+    if (!ctx_.check(svs_map_prepare_window_from_root(map_, root_id, inner_size_, double_size_, 1, 256, &r, ids.data(), ty.data()))) return false;
+    if (r.n_active < 0) return false;
+    ids.resize((size_t)r.n_window); ty.resize((size_t)r.n_window);
+    if (n_active) *n_active = r.n_active;
+    const std::vector<int32_t> old_ids = window_ids_, old_types = window_types_;
+    window_ids_ = ids; window_types_ = ty;
+    *window = ids; *types = ty;
+    if (!reinitializePoses(root_id, old_ids, loop_id)) return false;
+    if (ids.size() < 2) return false;
+    std::vector<int32_t> cached_ids, miss;
+    std::vector<double> cached_T;
+    for (;;) {
+      if (!updateMarginalization(old_ids, old_types, ids, ty, cached_ids, cached_T, results, &miss)) return false;
+      std::vector<double> T; std::vector<int32_t> st;
+      if (miss.empty() || !computeAbsolutePoses(miss, &T, &st)) break;
+      std::vector<std::pair<int32_t, size_t> > all;      // (id, where its pose lies: cached_T below `old`, T above)
+      const size_t old = cached_ids.size();
+      for (size_t i = 0; i < old; ++i) all.push_back(std::make_pair(cached_ids[i], i));
+      for (size_t i = 0; i < miss.size(); ++i) if (st[i] == SVS_WALK_OK) all.push_back(std::make_pair(miss[i], old + i));
+      if (all.size() == old) break;                      // no path for any of them: the caller sees them in `missing`
+      std::sort(all.begin(), all.end());
+      std::vector<int32_t> nid; std::vector<double> nT;
+      for (size_t i = 0; i < all.size(); ++i) {
+        const double *src = all[i].second < old ? &cached_T[12 * all[i].second] : &T[12 * (all[i].second - old)];
+        nid.push_back(all[i].first); nT.insert(nT.end(), src, src + 12);
+      }
+      cached_ids.swap(nid); cached_T.swap(nT);
+    }
+    if (missing) *missing = miss;
+    return true;
+  }
   int anchorLevel(int point_id) const { return point_id >= 0 && (size_t)point_id < level_.size() ? level_[(size_t)point_id] : 0; }
 
  private:
@@ -993,6 +1079,8 @@ class BackendMap {
   svs_map *map_;
   std::vector<int8_t> level_;      // anchor_level by point id: MyTrackPoint carries it
   std::vector<std::pair<int32_t, int32_t> > edge_keys_;      // (lo, hi) of every edge, sorted: what updateMarginalization selects its pairs from
+  std::vector<int32_t> window_ids_, window_types_;           // the window prepareForOptimization(root_id, loop_id) prepared last: the next call's old_window
+  int inner_size_ = 25, double_size_ = 200;                  // backend.cpp:141-144
   bool ok_;
 };
 inline bool StereoFrontend::setCandidatesFromMap(BackendMap &map, const std::vector<int32_t> &vertex_ids, const std::vector<int32_t> &slot_keyframe_ids,

@@ -230,6 +230,12 @@ _SIGS = {
     "svs_map_get_edges": [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p],
     "svs_map_edge_info": [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)],
     "svs_map_compute_constraints": [C.c_void_p, C.c_int, C.POINTER(MapConstraintRequest), C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p],
+    "svs_map_initial_windows": [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p],
+    "svs_map_frames_in_neighborhood": [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p],
+    "svs_map_absolute_poses": [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
+    "svs_map_reinitialize_poses": [C.c_void_p, C.c_int32, C.c_int32, C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_int32), C.c_void_p],
+    "svs_map_get_poses": [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p],
+    "svs_map_prepare_window_from_root": [C.c_void_p, C.c_int32, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(MapWindowResult), C.c_void_p, C.c_void_p],
     "svs_ba_window_from_map_edges": [C.c_void_p, C.c_void_p, C.POINTER(Cam), C.POINTER(BaParams)],
     "svs_ba_window_constraints": [C.c_void_p, C.POINTER(C.c_int32), C.c_void_p],
     "svs_ba_window_from_map": [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(Cam), C.POINTER(BaParams)],

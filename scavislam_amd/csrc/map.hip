@@ -15,10 +15,13 @@
 //   map_edge_* / map_cons_kernel   the pose graph's edges (EdgeTable, slam_graph.hpp:197-363: one record per undirected edge, T_lo_from_hi and one Lambda) and
 //                   computeConstraint (slam_graph.cpp:787-846) with one workgroup per keyframe pair -- common points as an ordered bitmap compaction, depths in f64,
 //                   the median by a radix select over the doubles' bit patterns, setConstraint in the same launch; map_edge_gather is copyContraintsToG2o
+//   map_walk.inc        the pose graph's walks (computeInitialDoubleWin, framesInNeighborhood, shortestPathToWindow + computeAbsolutePose, reinitializePoses): a
+//                   strength-ordered adjacency built from the edge records and one level-synchronous breadth-first search per request
 // Integer and copy work throughout (but for the three divisions of invert_depth and the f64 geometry of map_cons_kernel); the host keeps the id sets and the set of pairs, so every refusal happens before anything is uploaded.
 #include "reg_map.h"
 #include "nbh_map.h"
 #include "ba_map.h"
+#include "walk_map.h"
 #include "pose.h"
 #include <string.h>
 #include <algorithm>
@@ -955,6 +958,8 @@ struct svs_map {
   std::vector<int32_t> kf_nobs;
   DevBuf<double> d_depth; DevBuf<int32_t> d_common;
   DevBuf<uint8_t> d_dn; PinnedBuf<uint8_t> h_dn;
+  // the pose graph's walks (map_walk.inc): the strength-ordered adjacency and the searches' work space
+  MapWalkState walk;
   ~svs_map() {      // (before the members go, also when create gives up)
     if (ctx) { (void)hipSetDevice(ctx->device); (void)hipStreamSynchronize(ctx->stream); }
   }
@@ -1308,37 +1313,18 @@ size_t map_win_bytes(const svs_map *m) {
 uint64_t next_win_serial() { static uint64_t s = 0; return __atomic_add_fetch(&s, 1, __ATOMIC_RELAXED); }
 }  // namespace
 
-extern "C" int svs_map_prepare_window(svs_map *m, int n0, const int32_t *h_kf_ids, const int32_t *h_kf_type, int n_pairs, const int32_t *h_edge_pairs,
-                                      int set_window_flags, int window_cap, svs_map_window_result *h_res, int32_t *h_window_ids, int32_t *h_window_type) {
-  svs_ctx *ctx = m ? m->ctx : nullptr;
-  SVS_REQUIRE(ctx, m && n0 >= 1 && h_kf_ids && h_kf_type && n_pairs >= 0 && (n_pairs == 0 || h_edge_pairs) && window_cap >= 1 && h_res);
-  MAP_CAPACITY(ctx, n0 <= window_cap && window_cap <= MAP_WIN_MAX);
-  if (int rc = map_check_ids(m, n0, h_kf_ids, m->kf_in, m->max_kf, true)) return rc;
-  int n_inner = 0;
-  for (int i = 0; i < n0; ++i) { SVS_REQUIRE(ctx, h_kf_type[i] == 0 || h_kf_type[i] == 1); n_inner += h_kf_type[i] == 0; }
-  SVS_REQUIRE(ctx, n_inner >= 1);
-  for (int i = 0; i < 2 * n_pairs; ++i) SVS_REQUIRE(ctx, svs_map_has_keyframe(m, h_edge_pairs[i]));
-  if (m->n_unmeasured > 0) { ctx->err = "svs_map_prepare_window: the map holds observations without a measurement (svs_map_add_observations)"; return SVS_ERR_INVALID; }
-  SVS_DEVICE(ctx);
+// the block of the prepared window and the pinned twin of its head
+static int map_win_reserve(svs_map *m) {
+  svs_ctx *ctx = m->ctx;
   if (!m->d_win) SVS_HIP(ctx, m->d_win.alloc(map_win_bytes(m)));
   if (m->h_win.bytes() < WIN_HEAD_END - WIN_O_RES) SVS_HIP(ctx, m->h_win.alloc(WIN_HEAD_END - WIN_O_RES));
-  if (int rc = map_prepare_walk(m, 1)) return rc;
-  // one staged upload: W0's ids | types | the INNER ones | the pairs
-  const size_t o_types = up_align(sizeof(int32_t) * (size_t)n0), o_inner = o_types + up_align(sizeof(int32_t) * (size_t)n0),
-               o_pairs = o_inner + up_align(sizeof(int32_t) * (size_t)n_inner), bytes = o_pairs + sizeof(int32_t) * 2 * (size_t)n_pairs;
-  uint8_t *hs;
-  if (int rc = map_stage(m, bytes, &hs)) return rc;
-  memcpy(hs, h_kf_ids, sizeof(int32_t) * (size_t)n0);
-  memcpy(hs + o_types, h_kf_type, sizeof(int32_t) * (size_t)n0);
-  { int32_t *inner = reinterpret_cast<int32_t *>(hs + o_inner); for (int i = 0, k = 0; i < n0; ++i) if (h_kf_type[i] == 0) inner[k++] = h_kf_ids[i]; }
-  if (n_pairs) memcpy(hs + o_pairs, h_edge_pairs, sizeof(int32_t) * 2 * (size_t)n_pairs);
-  if (int rc = map_upload(m, m->d_up, bytes)) return rc;
+  return SVS_OK;
+}
+
+// from W0, its INNER keyframes and the pairs on the device (A.ids, A.types, A.inner, A.pairs, A.n0, A.n_pairs) to the prepared window: two launches, one download
+static int map_win_finish(svs_map *m, const MapWinK &A, int n_inner, int window_cap, svs_map_window_result *h_res, int32_t *h_window_ids, int32_t *h_window_type) {
+  svs_ctx *ctx = m->ctx;
   m->win_valid = false;                // from here on the block holds the new window, or nothing
-  MapWinK A = map_win_pieces(m);
-  const uint8_t *U = m->d_up.get();
-  A.ids = reinterpret_cast<const int32_t *>(U); A.types = reinterpret_cast<const int32_t *>(U + o_types); A.inner = reinterpret_cast<const int32_t *>(U + o_inner);
-  A.pairs = reinterpret_cast<const int32_t *>(U + o_pairs);
-  A.n0 = n0; A.n_pairs = n_pairs; A.window_cap = window_cap; A.set_flags = set_window_flags != 0;
   const MapK M = m->view();
   const int n_words = (m->pt_hi + 31) >> 5;
   SVS_HIP(ctx, hipMemsetAsync(m->d_win.get() + WIN_O_EXT, 0, WIN_O_WID - WIN_O_EXT, ctx->stream));      // the extension bitmap and the result
@@ -1360,6 +1346,38 @@ extern "C" int svs_map_prepare_window(svs_map *m, int n0, const int32_t *h_kf_id
   m->win_ids.assign(wid, wid + R.n_window); m->win_types.assign(wtype, wtype + R.n_window);
   m->win_P = R.n_window; m->win_L = R.n_active; m->win_serial = next_win_serial(); m->win_valid = true;
   return SVS_OK;
+}
+
+extern "C" int svs_map_prepare_window(svs_map *m, int n0, const int32_t *h_kf_ids, const int32_t *h_kf_type, int n_pairs, const int32_t *h_edge_pairs,
+                                      int set_window_flags, int window_cap, svs_map_window_result *h_res, int32_t *h_window_ids, int32_t *h_window_type) {
+  svs_ctx *ctx = m ? m->ctx : nullptr;
+  SVS_REQUIRE(ctx, m && n0 >= 1 && h_kf_ids && h_kf_type && n_pairs >= 0 && (n_pairs == 0 || h_edge_pairs) && window_cap >= 1 && h_res);
+  MAP_CAPACITY(ctx, n0 <= window_cap && window_cap <= MAP_WIN_MAX);
+  if (int rc = map_check_ids(m, n0, h_kf_ids, m->kf_in, m->max_kf, true)) return rc;
+  int n_inner = 0;
+  for (int i = 0; i < n0; ++i) { SVS_REQUIRE(ctx, h_kf_type[i] == 0 || h_kf_type[i] == 1); n_inner += h_kf_type[i] == 0; }
+  SVS_REQUIRE(ctx, n_inner >= 1);
+  for (int i = 0; i < 2 * n_pairs; ++i) SVS_REQUIRE(ctx, svs_map_has_keyframe(m, h_edge_pairs[i]));
+  if (m->n_unmeasured > 0) { ctx->err = "svs_map_prepare_window: the map holds observations without a measurement (svs_map_add_observations)"; return SVS_ERR_INVALID; }
+  SVS_DEVICE(ctx);
+  if (int rc = map_win_reserve(m)) return rc;
+  if (int rc = map_prepare_walk(m, 1)) return rc;
+  // one staged upload: W0's ids | types | the INNER ones | the pairs
+  const size_t o_types = up_align(sizeof(int32_t) * (size_t)n0), o_inner = o_types + up_align(sizeof(int32_t) * (size_t)n0),
+               o_pairs = o_inner + up_align(sizeof(int32_t) * (size_t)n_inner), bytes = o_pairs + sizeof(int32_t) * 2 * (size_t)n_pairs;
+  uint8_t *hs;
+  if (int rc = map_stage(m, bytes, &hs)) return rc;
+  memcpy(hs, h_kf_ids, sizeof(int32_t) * (size_t)n0);
+  memcpy(hs + o_types, h_kf_type, sizeof(int32_t) * (size_t)n0);
+  { int32_t *inner = reinterpret_cast<int32_t *>(hs + o_inner); for (int i = 0, k = 0; i < n0; ++i) if (h_kf_type[i] == 0) inner[k++] = h_kf_ids[i]; }
+  if (n_pairs) memcpy(hs + o_pairs, h_edge_pairs, sizeof(int32_t) * 2 * (size_t)n_pairs);
+  if (int rc = map_upload(m, m->d_up, bytes)) return rc;
+  MapWinK A = map_win_pieces(m);
+  const uint8_t *U = m->d_up.get();
+  A.ids = reinterpret_cast<const int32_t *>(U); A.types = reinterpret_cast<const int32_t *>(U + o_types); A.inner = reinterpret_cast<const int32_t *>(U + o_inner);
+  A.pairs = reinterpret_cast<const int32_t *>(U + o_pairs);
+  A.n0 = n0; A.n_pairs = n_pairs; A.window_cap = window_cap; A.set_flags = set_window_flags != 0;
+  return map_win_finish(m, A, n_inner, window_cap, h_res, h_window_ids, h_window_type);
 }
 
 bool svs_map_window_is(const svs_map *m, uint64_t serial) { return m && m->win_valid && m->win_serial == serial; }
@@ -1639,3 +1657,5 @@ extern "C" int svs_map_compute_constraints(svs_map *m, int n, const svs_map_cons
   }
   return SVS_OK;
 }
+
+#include "map_walk.inc"

@@ -289,6 +289,8 @@ MAP_CONSTRAINT_RESULT_DTYPE = np.dtype([("status", "<i4"), ("strength", "<i4"), 
 assert MAP_EDGE_DTYPE.itemsize == 408 and MAP_CONSTRAINT_RESULT_DTYPE.itemsize == 416
 EDGE_LOCAL, EDGE_METRIC, EDGE_APPEARANCE = 0, 1, 2
 CONS_OK, CONS_EMPTY, CONS_MISSING_ANCHOR = 0, 1, 2
+WALK_OK, WALK_NO_PATH = 0, 1          # svs_map_absolute_poses
+MAP_WALK_MAX_REQUESTS = 256           # requests of one walk call
 MAP_CONS_MAX_REQUESTS = 256
 
 

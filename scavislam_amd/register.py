@@ -15,8 +15,8 @@ import ctypes as C
 
 import numpy as np
 
-from .ctypes_types import (BA_CONSTRAINT_DTYPE, CANDIDATE_DTYPE, CONS_OK, KEYFRAME_DTYPE, MAP_CONSTRAINT_RESULT_DTYPE, MAP_EDGE_DTYPE, MAP_WINDOW_MAX, MATCH_RESULT_DTYPE, REG_KF_STATS_DTYPE, REG_LOCAL, REG_LOOP, REG_OK, REG_OVER_CAPACITY,
-                           REG_STAGES, SVS_MAX_CELLS, Cam, MapConstraintRequest, MapWindowResult, RegMapRequest, RegParams, RegRequest, RegResult)
+from .ctypes_types import (BA_CONSTRAINT_DTYPE, CANDIDATE_DTYPE, CONS_OK, KEYFRAME_DTYPE, MAP_CONSTRAINT_RESULT_DTYPE, MAP_EDGE_DTYPE, MAP_WALK_MAX_REQUESTS, MAP_WINDOW_MAX, MATCH_RESULT_DTYPE, REG_KF_STATS_DTYPE, REG_LOCAL, REG_LOOP, REG_OK, REG_OVER_CAPACITY,
+                           REG_STAGES, SVS_MAX_CELLS, WALK_OK, Cam, MapConstraintRequest, MapWindowResult, RegMapRequest, RegParams, RegRequest, RegResult)
 
 
 def keyframe_table(entries):
@@ -222,6 +222,7 @@ class ResidentMap:
         self.h = h
         self.window_shape = None
         self.edge_keys = set()               # (lo, hi) of every edge: what update_marginalization selects its pairs from
+        self.edge_log = []                   # (a, b, strength) in slot order: what neighbors_of_root orders the root's row by
         ctx.children.add(self)
 
     def _call(self, name, *args):
@@ -324,6 +325,7 @@ class ResidentMap:
         t = np.ascontiguousarray(np.broadcast_to(np.asarray(edge_type, np.int32), (len(e),)))
         self._call("svs_map_add_edges", len(e), e.ctypes.data, s.ctypes.data, t.ctypes.data)
         self.edge_keys.update((int(min(a, b)), int(max(a, b))) for a, b in e)
+        self.edge_log += [(int(a), int(b), int(st)) for (a, b), st in zip(e, s)]
 
     def set_constraints(self, cons):
         """setConstraint with the caller's values: BA_CONSTRAINT_DTYPE, pose1 / pose2 name the edge, T_21 = T_pose2_from_pose1; marks the edges marginalised"""
@@ -388,18 +390,105 @@ class ResidentMap:
             out.append(o)
         return out
 
-    def update_marginalization(self, old_window, new_window, cached=None, missing_cap=64):
+    def update_marginalization(self, old_window, new_window, cached=None, missing_cap=64, resolve_missing=False):
         """unmargPosesEnteringInnerW (slam_graph.cpp:728-759) and margPosesLeftInnerWindow (:848-904): windows are (ids, types) with 0 INNER / 1 OUTER, the pairs are
         selected on the host from the edge keys; one unmarginalize, then one storing compute_constraints.  The map's window flags must be those of new_window
         (computeConstraint asks double_window_ for an anchor's pose).  Returns (results, missing): `missing` is the sorted union of the anchors some request
-        lacked -- the caller adds their computeAbsolutePose results to `cached` and repeats; a repeat unmarginalises and recomputes the same pairs"""
+        lacked -- the caller adds their computeAbsolutePose results to `cached` and repeats; a repeat unmarginalises and recomputes the same pairs.
+        resolve_missing=True answers `missing` itself through absolute_poses and repeats until no request lacks an anchor it can find a path for"""
         enter = entering_inner_pairs(new_window, self.edge_keys)
         left = left_inner_pairs(old_window, new_window, self.edge_keys)
         if enter:
             self.unmarginalize(enter)
         res = self.compute_constraints([dict(kf1=a, kf2=b, store=True, cached=cached) for a, b in left], missing_cap=missing_cap) if left else []
         missing = sorted({int(k) for o in res for k in o["missing"]})
+        if resolve_missing:
+            cached = dict(cached or {})
+            while missing:
+                poses = [o for at in range(0, len(missing), MAP_WALK_MAX_REQUESTS) for o in self.absolute_poses(missing[at:at + MAP_WALK_MAX_REQUESTS])]
+                found = {k: o["T"] for k, o in zip(missing, poses) if o["status"] == WALK_OK}
+                if not found:
+                    break                    # no path to the window (the reference asserts): the caller sees them in `missing`
+                cached.update(found)
+                res = self.compute_constraints([dict(kf1=a, kf2=b, store=True, cached=cached) for a, b in left], missing_cap=missing_cap)
+                missing = sorted({int(k) for o in res for k in o["missing"]})
         return res, missing
+
+    # ---- the pose graph's walks (slam_graph.cpp:64-140, :555-596, :665-725, :762-782): visit order is that of the reference's queue, see include/scavislam_hip.h
+    def initial_windows(self, roots, inner_size, double_size, window_cap=None):
+        """computeInitialDoubleWin per root -> [(ids in visit order, types 0 INNER / 1 OUTER)]"""
+        r = np.ascontiguousarray(roots, np.int32).reshape(-1)
+        cap = int(double_size if window_cap is None else window_cap)
+        count = np.zeros(len(r), np.int32)
+        ids, types = np.full((len(r), max(cap, 1)), -1, np.int32), np.full((len(r), max(cap, 1)), -1, np.int32)
+        self._call("svs_map_initial_windows", len(r), r.ctypes.data, int(inner_size), int(double_size), cap, count.ctypes.data, ids.ctypes.data, types.ctypes.data)
+        self.raw = dict(count=count, ids=ids, types=types)
+        return [(ids[i, :count[i]].copy(), types[i, :count[i]].copy()) for i in range(len(r))]
+
+    def frames_in_neighborhood(self, roots, size):
+        """framesInNeighborhood per root -> [ids in visit order]: usable as walk_kf of Registrar.register_map_batch"""
+        r = np.ascontiguousarray(roots, np.int32).reshape(-1)
+        count = np.zeros(len(r), np.int32)
+        ids = np.full((len(r), max(int(size), 1)), -1, np.int32)
+        self._call("svs_map_frames_in_neighborhood", len(r), r.ctypes.data, int(size), count.ctypes.data, ids.ctypes.data)
+        self.raw = dict(count=count, ids=ids)
+        return [ids[i, :count[i]].copy() for i in range(len(r))]
+
+    def absolute_poses(self, kf_ids, path_cap=0):
+        """shortestPathToWindow + computeAbsolutePose per keyframe -> [dict(status WALK_OK / WALK_NO_PATH, path_len, T [12], path (the first path_cap ids))]"""
+        k = np.ascontiguousarray(kf_ids, np.int32).reshape(-1)
+        cap = int(path_cap)
+        status, plen = np.zeros(len(k), np.int32), np.zeros(len(k), np.int32)
+        T = np.zeros((len(k), 12), np.float64)
+        path = np.full((len(k), cap), -1, np.int32)
+        self._call("svs_map_absolute_poses", len(k), k.ctypes.data, cap, status.ctypes.data, plen.ctypes.data, T.ctypes.data, path.ctypes.data if cap else None)
+        self.raw = dict(status=status, path_len=plen, T=T, path=path)
+        return [dict(status=int(status[i]), path_len=int(plen[i]), T=T[i].copy(), path=path[i, :min(int(plen[i]), cap)].copy()) for i in range(len(k))]
+
+    def reinitialize_poses(self, root_id, old_window, loop_id=-1, changed_cap=None):
+        """reinitializePoses over the keyframes in the (new) window; writes the map's poses -> (changed ids in visit order, their total count)"""
+        old = np.ascontiguousarray(old_window, np.int32).reshape(-1)
+        cap = int(self.info()[0] if changed_cap is None else changed_cap)
+        n = C.c_int32()
+        changed = np.full(max(cap, 1), -1, np.int32)
+        self._call("svs_map_reinitialize_poses", int(root_id), int(loop_id), len(old), old.ctypes.data if len(old) else None, cap, C.byref(n),
+                   changed.ctypes.data if cap else None)
+        return changed[:min(n.value, cap)].copy(), n.value
+
+    def get_poses(self, kf_ids):
+        """blocking read-back of T_me_from_world [n, 12]"""
+        k = np.ascontiguousarray(kf_ids, np.int32).reshape(-1)
+        T = np.zeros((len(k), 12), np.float64)
+        self._call("svs_map_get_poses", len(k), k.ctypes.data, T.ctypes.data)
+        return T
+
+    def prepare_window_from_root(self, root_id, inner_size, double_size, set_window_flags=True, window_cap=MAP_WINDOW_MAX):
+        """prepare_window with the initial window and the pairs found on the device from root_id; the same return values"""
+        cap = int(window_cap)
+        res = MapWindowResult()
+        wid, wtype = np.full(max(cap, 1), -1, np.int32), np.full(max(cap, 1), -1, np.int32)
+        self._call("svs_map_prepare_window_from_root", int(root_id), int(inner_size), int(double_size), int(bool(set_window_flags)), cap, C.byref(res),
+                   wid.ctypes.data, wtype.ctypes.data)
+        n = res.n_window if res.n_active >= 0 else 0
+        self.window_shape = (res.n_window, res.n_active) if res.n_active >= 0 else None
+        return res, wid[:n].copy(), wtype[:n].copy()
+
+    def neighbors_of_root(self, root_id, max_num_neighbors):
+        """findNeighborsOfRoot (backend.cpp:287-309) on the host's mirror of the edges: the root's row in ASCENDING (strength, slot), in-window keyframes only.
+        The reference compares its count before it increments it, so up to max_num_neighbors + 1 ids come back"""
+        root = int(root_id)
+        row = sorted((s, slot, b if a == root else a) for slot, (a, b, s) in enumerate(self.edge_log) if root in (a, b))
+        ids = np.array([u for _, _, u in row], np.int32)
+        if not len(ids):
+            return ids
+        in_window = [w for at in range(0, len(ids), MAP_WALK_MAX_REQUESTS) for w in self.frames_in_neighborhood(ids[at:at + MAP_WALK_MAX_REQUESTS], 1)]
+        out = []
+        for u, w in zip(ids.tolist(), in_window):
+            if len(w):
+                out.append(u)
+                if len(out) > int(max_num_neighbors):
+                    break
+        return np.array(out, np.int32)
 
     def info(self):
         """(keyframes, points, distinct observations)"""
