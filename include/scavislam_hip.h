@@ -1145,6 +1145,78 @@ int svs_map_get_poses(svs_map *map, int n, const int32_t *h_kf_ids, double *h_po
 int svs_map_prepare_window_from_root(svs_map *map, int32_t root_id, int inner_size, int double_size, int set_window_flags, int window_cap,
                                      svs_map_window_result *h_res, int32_t *h_window_ids, int32_t *h_window_type);
 
+/* ---- inserting a keyframe: SlamGraph::addKeyframe (slam_graph.cpp:143-186) with computeStrength (:467-552), addNewPointsToMap (:358-397), addNewObsToOldPoints
+   (:400-420) and addNewEdges(LOCAL) (:423-465) on the map, as a statement free of hash order.
+   computeStrength.  E = the track entries whose global_id is a point of the map, in list order (an id listed twice counts twice).  The keys of the table are the
+     anchors of all new points and every keyframe in the observer row of an entry of E.  No entry in E: strength(f) = the new points anchored in f.  Else, with
+     h = max(covis_thr / 2, 1): an entry is LEFT if center[0] < half_width (a double against an int) else RIGHT, and TOP if center[1] < half_height else BOTTOM;
+     t_q(f) = the list index of the h-th entry of E that f observes in class q; a key that lacks one of the four has strength 0; otherwise
+     strength(f) = the number of entries at or behind max_q t_q(f) that f observes.  (The reference zeroes the table after EVERY track point, :532-550; the four
+     counts only grow, which makes this closed form its outcome.)  The key table comes in ASCENDING KEYFRAME ID, at most SVS_MAP_ADDKF_MAX_NEIGHBORS keys: more
+     are only known on the device, and the result then carries n_keys, over_capacity = 1 and nothing else (keys zero, masks zero).
+   svs_map_compute_strength: BLOCKING, the map unchanged.  h_keys [SVS_MAP_ADDKF_MAX_NEIGHBORS] (zero behind n_keys): strength BEFORE the clamp of oldkey, the
+     four class totals, edge = 0.  h_track_exists [n_track] (optional).  SVS_ERR_INVALID: an unknown anchor_id, covis_thr < 0.
+   svs_map_add_keyframe: BLOCKING, the whole addKeyframe for one keyframe:
+     1. strength(oldkey) = max(strength(oldkey), covis_thr); h_keys holds the table AFTER this clamp, edge = 1 where strength >= covis_thr.
+     2. the new keyframe (pyramid, disparity, thresholds as svs_map_add_keyframes takes them; args->keyframe.T_anchor_from_w is ignored) with
+        T_newkey_from_world = pose_mul(T_newkey_from_oldkey, T_oldkey_from_world), formed on the device in f64 without contraction; it is outside the window.
+     3. every new point, in list order, whose anchor has strength >= covis_thr (h_new_kept) becomes a point (xyz_anchor, anchor_id, anchor_obs_pyr, anchor_level;
+        normal_anchor is not stored) and brings the pairs (point, newkey) measured by feat_center / feat_level and (point, anchor) measured by
+        anchor_obs_pyr * 2^anchor_level at anchor_level.
+     4. every entry of E adds the pair (global_id, newkey) with its centre and level; the first occurrence of an id wins.
+     5. every key with edge = 1, in ASCENDING KEY ID (the reference: unordered_map order; this order decides the edge slots), gets the LOCAL edge (key, newkey) of
+        that strength, then computeConstraint(key, newkey) with setConstraint: h_cons [SVS_MAP_ADDKF_MAX_NEIGHBORS] takes one result per new edge in that order,
+        h_missing [SVS_MAP_ADDKF_MAX_NEIGHBORS][missing_cap] their missing anchors under the rules of svs_map_compute_constraints (only the first n_edges entries
+        / rows of the two are written; arrays of min(keyframes of the map, SVS_MAP_ADDKF_MAX_NEIGHBORS) entries are enough), args->cached_ids / cached_T as its
+        requests have them.  An edge whose constraint ends SVS_CONS_EMPTY or SVS_CONS_MISSING_ANCHOR exists with T and info zero and not marginalised, as
+        svs_map_add_edges leaves it: the caller completes it through svs_map_absolute_poses and a storing svs_map_compute_constraints.
+     The map afterwards equals, byte for byte, one built by svs_map_add_keyframes, svs_map_add_points (the kept points in list order),
+     svs_map_add_measured_observations (per kept point (point, newkey) then (point, anchor); then the first occurrences of E), svs_map_add_edges and one storing
+     svs_map_compute_constraints.  One staged upload of the records, one small download (key table, masks), a second staged block of integers, the CSR rebuild,
+     the constraint launch, one download.
+     Refused before anything is uploaded, the map unchanged -- SVS_ERR_INVALID: an unknown oldkey, newkey present, an unknown anchor_id, a point_id already in the
+     map or twice in the list or equal to a track global_id, a level outside 0 .. SVS_NUM_PYR_LEVELS - 1, covis_thr < 0, an oldkey that is no key of the table (no
+     new point anchored there and no pair (existing track point, oldkey)); SVS_ERR_CAPACITY: an id beyond the
+     capacities, fewer than 2 n_new + n_track free observations, fewer than min(keyframes of the map, SVS_MAP_ADDKF_MAX_NEIGHBORS) free edges.  More than
+     SVS_MAP_ADDKF_MAX_NEIGHBORS keys: SVS_OK with over_capacity = 1, the map unchanged.
+   svs_map_add_first_keyframe: addFirstKeyframe (:255-268): identity pose; SVS_ERR_INVALID unless the map holds no keyframe.
+   svs_map_get_points / svs_map_get_feature_table: BLOCKING read-backs (what cloneDrawData reads).  get_points: the stored records (kf_index = the anchor's id) of
+     points of the map.  get_feature_table: the points of kf_id's feature_table in ASCENDING POINT ID, *h_count their number (only the first cap are written), and
+     per point the measurement record of the measured store; a pair that came without a measurement has obs and info zero and anchor = -1. */
+enum { SVS_MAP_ADDKF_MAX_NEIGHBORS = 1024 };
+typedef struct {                       /* NewTwoViewPoint, data_structures.h */
+  double xyz_anchor[3];
+  double anchor_obs_pyr[3];
+  double feat_center[3];               /* feat_newkey.center */
+  int32_t point_id, anchor_id, anchor_level, feat_level;
+  int32_t pad_[2];
+} svs_map_new_point;                   /* 96 bytes */
+typedef struct {                       /* TrackPoint: global_id, feat */
+  double center[3];
+  int32_t global_id, level;
+} svs_map_track_point;                 /* 32 bytes */
+typedef struct { int32_t kf_id, strength, n_left, n_right, n_top, n_bottom, edge, pad_; } svs_map_key;
+typedef struct { int32_t n_keys, m, over_capacity, n_edges; } svs_map_strength_result;
+typedef struct {
+  int32_t newkey_id, oldkey_id, covis_thr, half_width, half_height, disp_stride, n_new, n_track;
+  double T_newkey_from_oldkey[12];
+  svs_keyframe keyframe;
+  const float *disp;                   /* DEVICE, level 0 */
+  const int32_t *fast_thr;             /* HOST [SVS_NUM_PYR_LEVELS][SVS_MAX_CELLS] */
+  const svs_map_new_point *new_points; /* HOST [n_new] */
+  const svs_map_track_point *track_points;      /* HOST [n_track] */
+  const int32_t *cached_ids;           /* HOST [n_cached] strictly ascending */
+  const double *cached_T;              /* HOST [n_cached][12] */
+  int32_t n_cached, pad_;
+} svs_map_add_keyframe_args;
+int svs_map_compute_strength(svs_map *map, int n_new, const svs_map_new_point *h_new, int n_track, const svs_map_track_point *h_track, int covis_thr, int half_width,
+                             int half_height, svs_map_strength_result *h_res, svs_map_key *h_keys, int32_t *h_track_exists);
+int svs_map_add_keyframe(svs_map *map, const svs_map_add_keyframe_args *args, int missing_cap, svs_map_strength_result *h_res, svs_map_key *h_keys,
+                         int32_t *h_new_kept, int32_t *h_track_exists, svs_map_constraint_result *h_cons, int32_t *h_missing);
+int svs_map_add_first_keyframe(svs_map *map, int32_t id, const svs_keyframe *h_keyframe, const float *disp, int32_t disp_stride, const int32_t *h_fast_thr);
+int svs_map_get_points(svs_map *map, int n, const int32_t *h_ids, svs_candidate_point *h_out);
+int svs_map_get_feature_table(svs_map *map, int32_t kf_id, int cap, int32_t *h_count, int32_t *h_point_ids, svs_ba_edge *h_meas);
+
 /* A request by ids.  The device builds the svs_reg_request of the stateless call from the map:
      1. source points.  SVS_REG_LOCAL: every point with at least one observation in a keyframe of h_walk_kf that is not the root and not in h_direct_kf
         (:481-497; the root is a direct neighbour, :433-449).  SVS_REG_LOOP: every point observed by h_walk_kf[0], the query keyframe (:853-858).  Each point

@@ -1059,9 +1059,77 @@ class BackendMap {
     if (missing) *missing = miss;
     return true;
   }
+  // ---- SlamGraph::addFirstKeyframe / addKeyframe (slam_graph.cpp:255-268, :143-186) on the device: svs_map_add_first_keyframe / svs_map_add_keyframe ----
+  // keyframe.kf: the device pyramid (its pose is ignored: identity); frame: d_disp / disp_stride / cell_grid2d
+  bool addFirstKeyframe(const RegistrationKeyframe &keyframe, const RegistrationFrame &frame) {
+    if (!ok_) return false;
+    std::vector<int32_t> thr;
+    thresholds(frame, &thr);
+    return ctx_.check(svs_map_add_first_keyframe(map_, keyframe.frame_id, &keyframe.kf, frame.d_disp, frame.disp_stride, thr.data()));
+  }
+  struct AddKeyframeResult {
+    std::vector<std::pair<int, int> > neighborid_to_strength;      // ascending id, after the clamp of oldkey
+    std::vector<int32_t> new_neighbors;                            // the keys that got an edge (key, newkey), ascending: their slots follow this order
+    std::vector<svs_map_constraint_result> constraints;            // one per new edge
+    std::vector<int32_t> missing;                                  // anchors some new edge lacked, ascending, each once: computeAbsolutePoses + computeConstraints complete them
+    std::vector<uint8_t> new_kept, track_exists;
+    std::vector<int32_t> exclude_set;                              // addKeyframeToPlaceRecog (backend.cpp:407-430): newkey and its new neighbours
+    bool do_loop_detection, over_capacity;
+  };
+  // newkey.kf: the device pyramid (its pose is ignored: T_newkey_from_oldkey * T_oldkey_from_world is formed on the device); covis_thr = graph_.covis_thr(),
+  // cam: the level-0 camera (half sizes as computeStrength takes them, :480-481).  cached_ids (ascending) / cached_T12: the caller's computeAbsolutePose
+  // results.  false: refused as a whole (Context::error); out->over_capacity: more than SVS_MAP_ADDKF_MAX_NEIGHBORS keys, the map unchanged
+  bool addKeyframe(int oldkey_id, const RegistrationKeyframe &newkey, const RegistrationFrame &frame, const double T_newkey_from_oldkey[12],
+                   const std::vector<svs_map_new_point> &newpoint_list, const std::vector<svs_map_track_point> &trackpoint_list, int covis_thr, const svs_cam &cam,
+                   AddKeyframeResult *out, const std::vector<int32_t> &cached_ids = std::vector<int32_t>(), const std::vector<double> &cached_T12 = std::vector<double>(),
+                   int missing_cap = 64) {
+    if (!ok_ || !out || cached_T12.size() != 12 * cached_ids.size() || missing_cap < 1) return false;
+    std::vector<int32_t> thr;
+    thresholds(frame, &thr);
+    svs_map_add_keyframe_args a;
+    std::memset(&a, 0, sizeof a);
+    a.newkey_id = newkey.frame_id; a.oldkey_id = oldkey_id; a.covis_thr = covis_thr; a.half_width = (int)(cam.w * 0.5); a.half_height = (int)(cam.h * 0.5);
+    a.disp_stride = frame.disp_stride; a.n_new = (int32_t)newpoint_list.size(); a.n_track = (int32_t)trackpoint_list.size();
+    std::memcpy(a.T_newkey_from_oldkey, T_newkey_from_oldkey, sizeof a.T_newkey_from_oldkey);
+    a.keyframe = newkey.kf; a.disp = frame.d_disp; a.fast_thr = thr.data();
+    a.new_points = newpoint_list.empty() ? nullptr : newpoint_list.data(); a.track_points = trackpoint_list.empty() ? nullptr : trackpoint_list.data();
+    a.n_cached = (int32_t)cached_ids.size(); a.cached_ids = cached_ids.empty() ? nullptr : cached_ids.data(); a.cached_T = cached_T12.empty() ? nullptr : cached_T12.data();
+    svs_map_strength_result r;
+    int32_t n_kf = 0;
+    if (!ctx_.check(svs_map_info(map_, &n_kf, nullptr, nullptr))) return false;
+    const size_t edge_cap = (size_t)std::max(1, std::min((int)n_kf, (int)SVS_MAP_ADDKF_MAX_NEIGHBORS));      // every key is a keyframe of the map
+    std::vector<svs_map_key> keys(SVS_MAP_ADDKF_MAX_NEIGHBORS);
+    std::vector<int32_t> kept(newpoint_list.size() + 1), exists(trackpoint_list.size() + 1), miss(edge_cap * missing_cap, -1);
+    std::vector<svs_map_constraint_result> cons(edge_cap);
+    if (!ctx_.check(svs_map_add_keyframe(map_, &a, missing_cap, &r, keys.data(), kept.data(), exists.data(), cons.data(), miss.data()))) return false;
+    *out = AddKeyframeResult();
+    out->over_capacity = r.over_capacity != 0; out->do_loop_detection = false;
+    if (out->over_capacity) return true;
+    out->exclude_set.push_back(newkey.frame_id);
+    for (int i = 0; i < r.n_keys; ++i) {
+      out->neighborid_to_strength.push_back(std::make_pair((int)keys[(size_t)i].kf_id, (int)keys[(size_t)i].strength));
+      if (!keys[(size_t)i].edge) continue;
+      out->new_neighbors.push_back(keys[(size_t)i].kf_id); out->exclude_set.push_back(keys[(size_t)i].kf_id);
+      edge_keys_.push_back(std::make_pair(std::min(keys[(size_t)i].kf_id, (int32_t)newkey.frame_id), std::max(keys[(size_t)i].kf_id, (int32_t)newkey.frame_id)));
+    }
+    std::sort(edge_keys_.begin(), edge_keys_.end());
+    out->constraints.assign(cons.begin(), cons.begin() + r.n_edges);
+    for (size_t i = 0; i < (size_t)r.n_edges * missing_cap; ++i) if (miss[i] >= 0) out->missing.push_back(miss[i]);
+    std::sort(out->missing.begin(), out->missing.end());
+    out->missing.erase(std::unique(out->missing.begin(), out->missing.end()), out->missing.end());
+    out->new_kept.assign(kept.begin(), kept.begin() + newpoint_list.size()); out->track_exists.assign(exists.begin(), exists.begin() + trackpoint_list.size());
+    for (size_t i = 0; i < newpoint_list.size(); ++i) if (kept[i]) level_[(size_t)newpoint_list[i].point_id] = (int8_t)newpoint_list[i].anchor_level;
+    out->do_loop_detection = (int)out->exclude_set.size() < n_kf + 1;
+    return true;
+  }
   int anchorLevel(int point_id) const { return point_id >= 0 && (size_t)point_id < level_.size() ? level_[(size_t)point_id] : 0; }
 
  private:
+  static void thresholds(const RegistrationFrame &frame, std::vector<int32_t> *thr) {
+    thr->assign((size_t)SVS_NUM_PYR_LEVELS * SVS_MAX_CELLS, 25);
+    for (int l = 0; l < SVS_NUM_PYR_LEVELS; ++l)
+      for (size_t c = 0; c < frame.cell_grid2d[l].size() && c < SVS_MAX_CELLS; ++c) (*thr)[(size_t)l * SVS_MAX_CELLS + c] = frame.cell_grid2d[l][c];
+  }
   static bool innerIn(const std::vector<int32_t> &ids, const std::vector<int32_t> &types, int32_t id) {
     for (size_t i = 0; i < ids.size(); ++i) if (ids[i] == id) return types[i] == 0;
     return false;

@@ -8,7 +8,7 @@ import ctypes as C
 import os
 import weakref
 
-from .ctypes_types import BaParams, BaStats, Cam, FastGrid, LoopCheck, LoopLocation, LoopLocationResult, LoopResult, MapConstraintRequest, MapWindowResult, NbhRequest, NbhResult, PoseOptParams, PoseOptStats, RegMapRequest, RegParams, RegRequest, RegResult, SeedArgs, SeedParams, SeedRequest, StereoParams, SurfParams, VocabParams, VocabResult
+from .ctypes_types import BaParams, BaStats, Cam, FastGrid, LoopCheck, LoopLocation, LoopLocationResult, LoopResult, MapAddKeyframeArgs, MapConstraintRequest, MapStrengthResult, MapWindowResult, NbhRequest, NbhResult, PoseOptParams, PoseOptStats, RegMapRequest, RegParams, RegRequest, RegResult, SeedArgs, SeedParams, SeedRequest, StereoParams, SurfParams, VocabParams, VocabResult
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SVS_LIB_PATH") or os.path.join(_HERE, "libscavislam_hip.so")   # override = kernel A/B experiments only
@@ -236,6 +236,11 @@ _SIGS = {
     "svs_map_reinitialize_poses": [C.c_void_p, C.c_int32, C.c_int32, C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_int32), C.c_void_p],
     "svs_map_get_poses": [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p],
     "svs_map_prepare_window_from_root": [C.c_void_p, C.c_int32, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(MapWindowResult), C.c_void_p, C.c_void_p],
+    "svs_map_compute_strength": [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(MapStrengthResult), C.c_void_p, C.c_void_p],
+    "svs_map_add_keyframe": [C.c_void_p, C.POINTER(MapAddKeyframeArgs), C.c_int, C.POINTER(MapStrengthResult), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
+    "svs_map_add_first_keyframe": [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p],
+    "svs_map_get_points": [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p],
+    "svs_map_get_feature_table": [C.c_void_p, C.c_int32, C.c_int, C.POINTER(C.c_int32), C.c_void_p, C.c_void_p],
     "svs_ba_window_from_map_edges": [C.c_void_p, C.c_void_p, C.POINTER(Cam), C.POINTER(BaParams)],
     "svs_ba_window_constraints": [C.c_void_p, C.POINTER(C.c_int32), C.c_void_p],
     "svs_ba_window_from_map": [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(Cam), C.POINTER(BaParams)],

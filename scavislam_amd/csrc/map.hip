@@ -17,6 +17,8 @@
 //                   the median by a radix select over the doubles' bit patterns, setConstraint in the same launch; map_edge_gather is copyContraintsToG2o
 //   map_walk.inc        the pose graph's walks (computeInitialDoubleWin, framesInNeighborhood, shortestPathToWindow + computeAbsolutePose, reinitializePoses): a
 //                   strength-ordered adjacency built from the edge records and one level-synchronous breadth-first search per request
+//   map_addkf.inc       inserting a keyframe (SlamGraph::addKeyframe): computeStrength as counting passes over the track points' observer rows with one workgroup per
+//                   call, the kept points and measured pairs compacted by prefix sums, the new edges' constraints through map_cons_kernel; two read-backs
 // Integer and copy work throughout (but for the three divisions of invert_depth and the f64 geometry of map_cons_kernel); the host keeps the id sets and the set of pairs, so every refusal happens before anything is uploaded.
 #include "reg_map.h"
 #include "nbh_map.h"
@@ -1659,3 +1661,4 @@ extern "C" int svs_map_compute_constraints(svs_map *m, int n, const svs_map_cons
 }
 
 #include "map_walk.inc"
+#include "map_addkf.inc"

@@ -301,3 +301,34 @@ class MapConstraintRequest(C.Structure):
 
 
 assert C.sizeof(MapConstraintRequest) == 240
+
+
+# ---- back end: inserting a keyframe into the map (svs_map_compute_strength, svs_map_add_keyframe, svs_map_get_points, svs_map_get_feature_table)
+MAP_ADDKF_MAX_NEIGHBORS = 1024
+MAP_NEW_POINT_DTYPE = np.dtype([("xyz_anchor", "<f8", 3), ("anchor_obs_pyr", "<f8", 3), ("feat_center", "<f8", 3), ("point_id", "<i4"), ("anchor_id", "<i4"),
+                                ("anchor_level", "<i4"), ("feat_level", "<i4"), ("pad_", "<i4", 2)])
+MAP_TRACK_POINT_DTYPE = np.dtype([("center", "<f8", 3), ("global_id", "<i4"), ("level", "<i4")])
+MAP_KEY_DTYPE = np.dtype([("kf_id", "<i4"), ("strength", "<i4"), ("n_left", "<i4"), ("n_right", "<i4"), ("n_top", "<i4"), ("n_bottom", "<i4"), ("edge", "<i4"),
+                          ("pad_", "<i4")])
+assert MAP_NEW_POINT_DTYPE.itemsize == 96 and MAP_TRACK_POINT_DTYPE.itemsize == 32 and MAP_KEY_DTYPE.itemsize == 32
+
+
+class MapStrengthResult(C.Structure):
+    """svs_map_strength_result"""
+    _fields_ = [("n_keys", C.c_int32), ("m", C.c_int32), ("over_capacity", C.c_int32), ("n_edges", C.c_int32)]
+
+
+class KeyframeC(C.Structure):
+    """svs_keyframe (KEYFRAME_DTYPE as a ctypes structure)"""
+    _fields_ = [("T_anchor_from_w", C.c_double * 12), ("pyr", C.c_void_p * 3), ("stride", C.c_int32 * 3), ("pad_", C.c_int32)]
+
+
+class MapAddKeyframeArgs(C.Structure):
+    """svs_map_add_keyframe_args"""
+    _fields_ = [("newkey_id", C.c_int32), ("oldkey_id", C.c_int32), ("covis_thr", C.c_int32), ("half_width", C.c_int32), ("half_height", C.c_int32),
+                ("disp_stride", C.c_int32), ("n_new", C.c_int32), ("n_track", C.c_int32), ("T_newkey_from_oldkey", C.c_double * 12), ("keyframe", KeyframeC),
+                ("disp", C.c_void_p), ("fast_thr", C.c_void_p), ("new_points", C.c_void_p), ("track_points", C.c_void_p), ("cached_ids", C.c_void_p),
+                ("cached_T", C.c_void_p), ("n_cached", C.c_int32), ("pad_", C.c_int32)]
+
+
+assert C.sizeof(KeyframeC) == 136 and C.sizeof(MapAddKeyframeArgs) == 32 + 96 + 136 + 48 + 8

@@ -15,8 +15,8 @@ import ctypes as C
 
 import numpy as np
 
-from .ctypes_types import (BA_CONSTRAINT_DTYPE, CANDIDATE_DTYPE, CONS_OK, KEYFRAME_DTYPE, MAP_CONSTRAINT_RESULT_DTYPE, MAP_EDGE_DTYPE, MAP_WALK_MAX_REQUESTS, MAP_WINDOW_MAX, MATCH_RESULT_DTYPE, REG_KF_STATS_DTYPE, REG_LOCAL, REG_LOOP, REG_OK, REG_OVER_CAPACITY,
-                           REG_STAGES, SVS_MAX_CELLS, WALK_OK, Cam, MapConstraintRequest, MapWindowResult, RegMapRequest, RegParams, RegRequest, RegResult)
+from .ctypes_types import (BA_CONSTRAINT_DTYPE, BA_EDGE_DTYPE, CANDIDATE_DTYPE, CONS_OK, KEYFRAME_DTYPE, MAP_ADDKF_MAX_NEIGHBORS, MAP_CONS_MAX_REQUESTS, MAP_CONSTRAINT_RESULT_DTYPE, MAP_EDGE_DTYPE, MAP_KEY_DTYPE, MAP_NEW_POINT_DTYPE, MAP_TRACK_POINT_DTYPE, MAP_WALK_MAX_REQUESTS, MAP_WINDOW_MAX, MATCH_RESULT_DTYPE, REG_KF_STATS_DTYPE, REG_LOCAL, REG_LOOP, REG_OK, REG_OVER_CAPACITY,
+                           REG_STAGES, SVS_MAX_CELLS, WALK_OK, Cam, MapAddKeyframeArgs, MapConstraintRequest, MapStrengthResult, MapWindowResult, RegMapRequest, RegParams, RegRequest, RegResult)
 
 
 def keyframe_table(entries):
@@ -489,6 +489,136 @@ class ResidentMap:
                 if len(out) > int(max_num_neighbors):
                     break
         return np.array(out, np.int32)
+
+    # ---- inserting a keyframe (SlamGraph::addKeyframe, slam_graph.cpp:143-186; computeStrength :467-552): see include/scavislam_hip.h
+    @staticmethod
+    def _fast_thr(per_level):
+        thr = np.full((3, SVS_MAX_CELLS), 25, np.int32)
+        for l in range(3):
+            t = np.asarray(per_level[l], np.int32).reshape(-1)
+            if len(t) > SVS_MAX_CELLS:
+                raise ValueError("at most SVS_MAX_CELLS thresholds per level")
+            thr[l, :len(t)] = t
+        return thr
+
+    def _strength_out(self, res, keys, exists):
+        n = 0 if res.over_capacity else res.n_keys
+        self.raw = dict(keys=keys, track_exists=exists, n_keys=res.n_keys, m=res.m, over_capacity=res.over_capacity)
+        return dict(n_keys=int(res.n_keys), m=int(res.m), over_capacity=bool(res.over_capacity), keys=keys[:n].copy(), track_exists=exists.astype(bool),
+                    neighborid_to_strength={int(k["kf_id"]): int(k["strength"]) for k in keys[:n]})
+
+    def compute_strength(self, new_points, track_points, covis_thr, half_width, half_height):
+        """computeStrength on the device, the map unchanged: new_points MAP_NEW_POINT_DTYPE (anchor_id is read), track_points MAP_TRACK_POINT_DTYPE.  Returns a
+        dict: keys (MAP_KEY_DTYPE, ascending kf_id: strength before the clamp of oldkey, the four class totals), neighborid_to_strength, track_exists, m, n_keys,
+        over_capacity (more than MAP_ADDKF_MAX_NEIGHBORS keys: only n_keys is known)"""
+        np_ = np.ascontiguousarray(new_points, MAP_NEW_POINT_DTYPE).reshape(-1)
+        tp = np.ascontiguousarray(track_points, MAP_TRACK_POINT_DTYPE).reshape(-1)
+        res = MapStrengthResult()
+        keys = np.zeros(MAP_ADDKF_MAX_NEIGHBORS, MAP_KEY_DTYPE)
+        exists = np.zeros(len(tp), np.int32)
+        self._call("svs_map_compute_strength", len(np_), np_.ctypes.data if len(np_) else None, len(tp), tp.ctypes.data if len(tp) else None, int(covis_thr),
+                   int(half_width), int(half_height), C.byref(res), keys.ctypes.data, exists.ctypes.data if len(tp) else None)
+        return self._strength_out(res, keys, exists)
+
+    def add_first_keyframe(self, kf_id, kf, disp, fast_thr):
+        """addFirstKeyframe: identity pose; refused unless the map is empty.  kf: one KEYFRAME_DTYPE record (its pose is ignored), disp (device pointer, stride)"""
+        k = np.ascontiguousarray(kf, KEYFRAME_DTYPE).reshape(-1)[:1].copy()
+        thr = self._fast_thr(fast_thr)
+        self._call("svs_map_add_first_keyframe", int(kf_id), k.ctypes.data, C.c_void_p(int(disp[0])), int(disp[1]), thr.ctypes.data)
+
+    def add_keyframe(self, newkey_id, oldkey_id, T_newkey_from_oldkey, kf, disp, fast_thr, new_points, track_points, covis_thr, half_width, half_height,
+                     cached=None, missing_cap=16, resolve_missing=False):
+        """SlamGraph::addKeyframe in one blocking call (svs_map_add_keyframe).  kf: one KEYFRAME_DTYPE record (pyramid; its pose is ignored), disp: (device
+        pointer, stride), fast_thr: per level; new_points MAP_NEW_POINT_DTYPE, track_points MAP_TRACK_POINT_DTYPE; cached {anchor id: T[12]} as compute_constraints
+        takes it.  Returns a dict: keys / neighborid_to_strength (AFTER the clamp of oldkey; keys["edge"] marks the new edges), new_kept, track_exists, m,
+        over_capacity (then the map is unchanged), edges [(key, newkey)], edge_results (one dict per new edge as compute_constraints returns them), missing
+        (sorted union), exclude_set and do_loop_detection (addKeyframeToPlaceRecog, backend.cpp:407-430).  resolve_missing=True completes the edges that lacked
+        an anchor through absolute_poses and a storing compute_constraints, as update_marginalization does"""
+        np_ = np.ascontiguousarray(new_points, MAP_NEW_POINT_DTYPE).reshape(-1)
+        tp = np.ascontiguousarray(track_points, MAP_TRACK_POINT_DTYPE).reshape(-1)
+        k = np.ascontiguousarray(kf, KEYFRAME_DTYPE).reshape(-1)[0]
+        thr = self._fast_thr(fast_thr)
+        cached = cached or {}
+        cids = np.array(sorted(int(c) for c in cached), np.int32)
+        cT = np.ascontiguousarray([np.asarray(cached[int(c)], np.float64).reshape(12) for c in cids], np.float64).reshape(len(cids), 12)
+        a = MapAddKeyframeArgs()
+        a.newkey_id, a.oldkey_id, a.covis_thr, a.half_width, a.half_height = int(newkey_id), int(oldkey_id), int(covis_thr), int(half_width), int(half_height)
+        a.disp_stride, a.n_new, a.n_track = int(disp[1]), len(np_), len(tp)
+        a.T_newkey_from_oldkey[:] = np.asarray(T_newkey_from_oldkey, np.float64).reshape(12).tolist()
+        a.keyframe.pyr[:] = [int(p) for p in k["pyr"]]
+        a.keyframe.stride[:] = [int(v) for v in k["stride"]]
+        a.disp, a.fast_thr = int(disp[0]), thr.ctypes.data
+        a.new_points, a.track_points = (np_.ctypes.data if len(np_) else None), (tp.ctypes.data if len(tp) else None)
+        a.cached_ids, a.cached_T, a.n_cached = (cids.ctypes.data if len(cids) else None), (cT.ctypes.data if len(cids) else None), len(cids)
+        res = MapStrengthResult()
+        keys = np.zeros(MAP_ADDKF_MAX_NEIGHBORS, MAP_KEY_DTYPE)
+        kept, exists = np.zeros(len(np_), np.int32), np.zeros(len(tp), np.int32)
+        n_kf = self.info()[0]
+        edge_cap = max(1, min(n_kf, MAP_ADDKF_MAX_NEIGHBORS))      # every key is a keyframe of the map; the library writes the first n_edges entries only
+        cons = np.zeros(edge_cap, MAP_CONSTRAINT_RESULT_DTYPE)
+        cap = int(missing_cap)
+        missing = np.full((edge_cap, cap), -1, np.int32)
+        self._call("svs_map_add_keyframe", C.byref(a), cap, C.byref(res), keys.ctypes.data, kept.ctypes.data if len(np_) else None,
+                   exists.ctypes.data if len(tp) else None, cons.ctypes.data, missing.ctypes.data if cap else None)
+        out = self._strength_out(res, keys, exists)
+        raw = dict(self.raw, new_kept=kept, results=cons, missing=missing)      # as the library wrote them (resolve_missing's calls leave their own behind)
+        out["new_kept"] = kept.astype(bool)
+        nbrs = [int(q["kf_id"]) for q in out["keys"] if q["edge"]]
+        out["edges"] = [(q, int(newkey_id)) for q in nbrs]
+        results = []
+        for i in range(len(nbrs)):
+            results.append(dict(status=int(cons[i]["status"]), strength=int(cons[i]["strength"]), n_missing=int(cons[i]["n_missing"]), median=float(cons[i]["median"]),
+                                norm_dist=float(cons[i]["norm_dist"]), T_12=cons[i]["T_12"].copy(), info=cons[i]["info"].copy(),
+                                missing=missing[i, :min(int(cons[i]["n_missing"]), cap)].copy()))
+        if not out["over_capacity"]:
+            self.window_shape = None
+            self.edge_keys.update((min(q, int(newkey_id)), max(q, int(newkey_id))) for q in nbrs)
+            self.edge_log += [(q, int(newkey_id), int(s["strength"])) for q, s in zip(nbrs, (x for x in out["keys"] if x["edge"]))]
+        miss = sorted({int(v) for o in results for v in o["missing"]})
+        if resolve_missing:
+            results, miss = self.complete_constraints(out["edges"], results, cached, missing_cap=max(cap, 1))
+        self.raw = raw
+        out["edge_results"], out["missing"] = results, miss
+        out["exclude_set"] = {int(newkey_id)} | set(nbrs)
+        out["do_loop_detection"] = len(out["exclude_set"]) < n_kf + (0 if out["over_capacity"] else 1)      # (against vertex_table().size() after the insertion)
+        return out
+
+    def complete_constraints(self, pairs, results, cached=None, missing_cap=16):
+        """the edges of `pairs` whose result lacks anchors: their poses through absolute_poses, then a storing compute_constraints, until no request lacks an
+        anchor that has a path to the window (update_marginalization's resolve_missing) -> (results, the anchors still missing)"""
+        results, cached = list(results), dict(cached or {})
+        miss = sorted({int(v) for o in results for v in o["missing"]})
+        while miss:
+            poses = [o for at in range(0, len(miss), MAP_WALK_MAX_REQUESTS) for o in self.absolute_poses(miss[at:at + MAP_WALK_MAX_REQUESTS])]
+            found = {q: o["T"] for q, o in zip(miss, poses) if o["status"] == WALK_OK}
+            if not found:
+                break                        # no path to the window (the reference asserts): the caller sees them in `missing`
+            cached.update(found)
+            todo = [i for i, o in enumerate(results) if o["n_missing"]]
+            for at in range(0, len(todo), MAP_CONS_MAX_REQUESTS):
+                part = todo[at:at + MAP_CONS_MAX_REQUESTS]
+                again = self.compute_constraints([dict(kf1=pairs[i][0], kf2=pairs[i][1], store=True, cached=cached) for i in part], missing_cap=missing_cap)
+                for i, o in zip(part, again):
+                    results[i] = o
+            miss = sorted({int(v) for o in results for v in o["missing"]})
+        return results, miss
+
+    def get_points(self, point_ids):
+        """blocking read-back of the stored point records (CANDIDATE_DTYPE, kf_index = the anchor's id)"""
+        p = np.ascontiguousarray(point_ids, np.int32).reshape(-1)
+        out = np.zeros(len(p), CANDIDATE_DTYPE)
+        self._call("svs_map_get_points", len(p), p.ctypes.data, out.ctypes.data)
+        return out
+
+    def get_feature_table(self, kf_id, cap=None):
+        """blocking read-back of a keyframe's feature_table -> (point ids ascending, BA_EDGE_DTYPE measurement records, the table's length).  A pair without a
+        measurement has obs and info zero and anchor = -1"""
+        cap = int(self.info()[1] if cap is None else cap)
+        n = C.c_int32()
+        ids, rec = np.full(max(cap, 1), -1, np.int32), np.zeros(max(cap, 1), BA_EDGE_DTYPE)
+        self._call("svs_map_get_feature_table", int(kf_id), cap, C.byref(n), ids.ctypes.data, rec.ctypes.data)
+        k = min(n.value, cap)
+        return ids[:k].copy(), rec[:k].copy(), n.value
 
     def info(self):
         """(keyframes, points, distinct observations)"""
