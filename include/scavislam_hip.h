@@ -877,7 +877,9 @@ int svs_surf_stage_times(svs_surf *s, float *ms);
    (:201-219, 830-1001) share one shape -- project map points into a root keyframe (pointsVisibleInRoot :472-546 / the loop at :853-893), matchAndAlign
    (:725-784), gate and count (keyframesToRegister :615-722 / :904-961) -- and run here for a batch of requests as ONE chain of launches on the context's
    stream: one staged upload, one download, no host round trip in between.  The graph bookkeeping around the call (framesInNeighborhood, the hash-set
-   deduplication of the point walk, registerKeyframes / addLoopClosure, new_edges_) stays with the caller; the MONO / Sim3 branches are not covered.
+   deduplication of the point walk, registerKeyframes / addLoopClosure, new_edges_) stays with the caller of this stateless call -- on the resident map the walk
+   is svs_map_frames_in_neighborhood, the registration svs_reg_register_map_batch and registerKeyframes / addLoopClosure svs_reg_commit, all below; the MONO /
+   Sim3 branches are not covered.
    The cull and the counting are restated in tests/register_model.py (backend.cpp is not among the reference-compiled pins); the
    matcher, the refinement and the gate inequality are the entry points above.
    Chain, per request:
@@ -1248,6 +1250,69 @@ typedef struct {
 int svs_reg_register_map_batch(svs_reg *reg, svs_map *map, int n_requests, const svs_reg_map_request *req, const svs_reg_params *prm, svs_reg_result *h_res,
                                int32_t *h_cand_src, svs_match_result *h_matches, int32_t *h_status_pass1, int32_t *h_accepted, svs_reg_kf_stats *h_kf_stats,
                                svs_match_result *h_matches_pass1, int32_t *h_cand_point_id, int32_t *h_kf_ids, int32_t *h_n_kf);
+
+/* ---- committing a registration or a loop closure into the map: SlamGraph::registerKeyframes (slam_graph.cpp:188-205) and SlamGraph::addLoopClosure (:207-251)
+   with addNewObsToOldPoints (:400-420) and addNewEdges(METRIC) (:423-465), where Backend::localRegisterFrame (backend.cpp:601-604) and globalLoopClosure
+   (:964-971) end.  As a statement free of hash order, for request i of the registrar's last svs_reg_register_map_batch on the map:
+     T_new = pose_mul(res[i].T_newroot_from_oldroot, req[i].T_root_from_world), f64, rows ((a0 b0 + a1 b1) + a2 b2) + t, no contraction, formed on the device
+     (:601-602, :964-966; the loop request's T_root_from_world already is inverse(T_query_from_loop) * T_query_from_w).
+   SVS_REG_LOCAL with status SVS_REG_OK:
+     track list    the candidates with accepted != 0 whose source point has, in its observer row, at least one table entry with qualifies != 0; in candidate
+                   order, which is ascending point id.  (The reference's list holds a point once per qualifying observer, :714-718; feature_table.insert keeps the
+                   first and all copies carry one feature, so each point appears once here.)  Feature = ImageFeature<3>(uvu, anchor_level): centre = obs of the
+                   second match's record, level = the candidate's anchor_level (:663-664).
+     pairs         every track point whose pair (point, root) is not yet in the map adds it with that measurement, as svs_map_add_measured_observations records
+                   it (info from the level); a pair already present keeps what it has.
+     edges         every qualifying keyframe gets, in ASCENDING KEYFRAME ID (the reference: unordered_map order; this order decides the edge slots, as in
+                   svs_map_add_keyframe), the edge (keyframe, root) of type METRIC (1) with strength = its svs_reg_kf_stats.strength, then computeConstraint(keyframe,
+                   root) + setConstraint with the root's pose overridden by T_new for that computation only (:197-204).  The stored pose of the root is unchanged.
+   SVS_REG_LOOP with status SVS_REG_OK (entry 0 qualifies), loop = the request's root, query = h_walk_kf[0]:
+     track list    every accepted candidate (:945-950), in candidate order; pairs (point, loop) as above.
+     edge          one edge (query, loop) of type APPEARANCE (2), strength = the number of accepted candidates (slam_graph.cpp:214: the list's length, not the number
+                   of new pairs), then computeConstraint(loop, query) with loop overridden by T_new (:233-250).
+   Any other status: SVS_OK, committed = 0 in the result, the map unchanged.
+   The constraints follow every rule of svs_map_compute_constraints: the cached anchor list comes with the call, missing anchors are reported per edge up to
+   missing_cap, an edge that ends SVS_CONS_MISSING_ANCHOR exists with T and info zero and is not marginalised, as svs_map_add_keyframe leaves it (the caller
+   completes it through svs_map_absolute_poses and a storing svs_map_compute_constraints with the same override).  SVS_CONS_EMPTY cannot occur: each new edge has
+   at least covis_thr common points once the pairs are in.
+   svs_reg_commit: BLOCKING.  The lists are taken where the registration left them on the device (candidate records, accepted flags, the second match's records,
+     observer rows, keyframe statistics, table ids): one launch builds the track list and the edge list there, one small download (counts, track point ids,
+     edge list), the host decides every refusal and the mask of new pairs, one staged block of integers, append by prefix sums, svs_map_add_edges' kernel, the
+     CSR rebuild, svs_map_compute_constraints' kernel, one download: one more host synchronisation than the registration alone.  ONE request per call; several
+     requests of one batch may be committed one after the other, each with what the registration computed (nothing is recomputed; the mask of new pairs is taken
+     against the map as it is then).  Any later registration call on the handle ends the batch.  At most the registrar's max_keyframes qualifying keyframes.
+     Outputs: h_res; h_edge_kf / h_edge_strength [max_keyframes] (optional): the other end of every new edge (LOOP: the query) and its strength, -1 / 0 behind
+     n_edges; h_cons [max_keyframes] and h_missing [max_keyframes][missing_cap]: the first n_edges entries / rows are written; h_track_point_ids / h_track_added
+     [track_cap] (optional): the track list's point ids and whether each brought a new pair, -1 / 0 behind n_track.
+   svs_map_register_keyframes / svs_map_add_loop_closure: BLOCKING, the reference's two functions with the caller's own lists, through the same apply path (the
+     track list goes up in the staged block).  registerKeyframes applies addNewEdges' test strength >= covis_thr; the neighbours that pass get their edges in
+     ascending id.  A track entry whose global_id is no point of the map is skipped (:411-414); the first occurrence of an id wins; h_track_added [n_track]
+     (optional) says 0 / 1 per entry.  addLoopClosure: pairs go to loop_id, the edge is (root_id, loop_id) with strength n_track.  h_edge_kf [n_neighbors]
+     (optional), h_cons [n_neighbors] / [1], h_missing rows likewise.
+   Refused before the map changes, map and registrar untouched -- SVS_ERR_INVALID: the handle's last registration was not a map batch on this map (or there is
+   none), request_index outside it, a request already committed, an edge that is already present (the reference asserts in insertEdge), an unknown keyframe id,
+   a neighbour twice or equal to the root, root_id == loop_id, a level outside 0 .. SVS_NUM_PYR_LEVELS - 1, a cached list that is not strictly ascending;
+   SVS_ERR_CAPACITY: fewer free observations than track points, fewer free edges than edges to add, track_cap below n_track when h_track_point_ids or
+   h_track_added is given. */
+typedef struct {
+  int32_t committed;                   /* 1: the map took the request; 0: nothing committed */
+  int32_t mode;                        /* SVS_REG_LOCAL / SVS_REG_LOOP */
+  int32_t root_id;                     /* the keyframe that took the pairs: the root / the loop keyframe */
+  int32_t other_id;                    /* SVS_REG_LOOP: the query keyframe; else -1 */
+  int32_t n_track, n_pairs_added, n_edges;
+  int32_t status;                      /* svs_reg_commit: the request's svs_reg_result.status; the explicit calls: 0 */
+  double T_new[12];                    /* the override of root_id in the constraints */
+} svs_reg_commit_result;               /* 128 bytes */
+int svs_reg_commit(svs_reg *reg, svs_map *map, int request_index, int n_cached, const int32_t *h_cached_ids, const double *h_cached_T, int missing_cap,
+                   svs_reg_commit_result *h_res, int32_t *h_edge_kf, int32_t *h_edge_strength, svs_map_constraint_result *h_cons, int32_t *h_missing, int track_cap,
+                   int32_t *h_track_point_ids, int32_t *h_track_added);
+int svs_map_register_keyframes(svs_map *map, int32_t root_id, const double *T_newroot_from_w, int n_neighbors, const int32_t *h_neighbor_ids,
+                               const int32_t *h_strength, int covis_thr, int n_track, const svs_map_track_point *h_track, int n_cached, const int32_t *h_cached_ids,
+                               const double *h_cached_T, int missing_cap, svs_reg_commit_result *h_res, int32_t *h_edge_kf, svs_map_constraint_result *h_cons,
+                               int32_t *h_missing, int32_t *h_track_added);
+int svs_map_add_loop_closure(svs_map *map, int32_t root_id, int32_t loop_id, const double *T_newloop_from_w, int n_track, const svs_map_track_point *h_track,
+                             int n_cached, const int32_t *h_cached_ids, const double *h_cached_T, int missing_cap, svs_reg_commit_result *h_res,
+                             svs_map_constraint_result *h_cons, int32_t *h_missing, int32_t *h_track_added);
 
 /* ---- front end: a stream's neighbourhood list built from the map.  Backend::computeNeighborhood (backend.cpp:244-386) from the vertex list onwards: the caller
    names the keyframes addPoseToNeighborhood(root) + findNeighborsOfRoot(root, 10) chose (the ordering by strength and the double_window test stay with it, as

@@ -1122,6 +1122,69 @@ class BackendMap {
     out->do_loop_detection = (int)out->exclude_set.size() < n_kf + 1;
     return true;
   }
+  // ---- SlamGraph::registerKeyframes / addLoopClosure (slam_graph.cpp:188-251) on the device: svs_map_register_keyframes / svs_map_add_loop_closure, and what
+  // BackendRegistration::localRegisterFrame(map, ..) / globalLoopClosure(map, ..) get from svs_reg_commit
+  struct CommitResult {
+    svs_reg_commit_result result;                                  // committed, the keyframe that took the pairs, T_new, the counts
+    std::vector<int32_t> new_neighbors;                            // the other end of every new edge, ascending: their slots follow this order
+    std::vector<svs_map_constraint_result> constraints;            // one per new edge
+    std::vector<int32_t> missing;                                  // anchors some new edge lacked, ascending, each once
+    std::vector<uint8_t> track_added;
+  };
+  // neighborid_to_strength: (frame_id, strength), any order; addNewEdges' test strength >= covis_thr is applied on the way.  false: refused as a whole
+  bool registerKeyframes(int root_id, const double T_newroot_from_w[12], const std::vector<std::pair<int, int> > &neighborid_to_strength,
+                         const std::vector<svs_map_track_point> &trackpoint_list, int covis_thr, CommitResult *out,
+                         const std::vector<int32_t> &cached_ids = std::vector<int32_t>(), const std::vector<double> &cached_T12 = std::vector<double>(), int missing_cap = 64) {
+    if (!ok_ || !out || cached_T12.size() != 12 * cached_ids.size() || missing_cap < 1) return false;
+    const size_t n = neighborid_to_strength.size();
+    std::vector<int32_t> ids(n + 1), st(n + 1), ekf(n + 1, -1), miss((n + 1) * missing_cap, -1), added(trackpoint_list.size() + 1);
+    for (size_t i = 0; i < n; ++i) { ids[i] = neighborid_to_strength[i].first; st[i] = neighborid_to_strength[i].second; }
+    std::vector<svs_map_constraint_result> cons(n + 1);
+    *out = CommitResult();
+    if (!ctx_.check(svs_map_register_keyframes(map_, root_id, T_newroot_from_w, (int)n, ids.data(), st.data(), covis_thr, (int)trackpoint_list.size(),
+                                               trackpoint_list.empty() ? nullptr : trackpoint_list.data(), (int)cached_ids.size(), cached_ids.empty() ? nullptr : cached_ids.data(),
+                                               cached_T12.empty() ? nullptr : cached_T12.data(), missing_cap, &out->result, ekf.data(), cons.data(), miss.data(), added.data())))
+      return false;
+    committed(out, ekf.data(), cons.data(), miss.data(), missing_cap, added.data(), trackpoint_list.size());
+    return true;
+  }
+  // root_id: the query keyframe; the pairs go to loop_id, the APPEARANCE edge (root_id, loop_id) has strength trackpoint_list.size()
+  bool addLoopClosure(int root_id, int loop_id, const double T_newloop_from_w[12], const std::vector<svs_map_track_point> &trackpoint_list, CommitResult *out,
+                      const std::vector<int32_t> &cached_ids = std::vector<int32_t>(), const std::vector<double> &cached_T12 = std::vector<double>(), int missing_cap = 64) {
+    if (!ok_ || !out || cached_T12.size() != 12 * cached_ids.size() || missing_cap < 1) return false;
+    std::vector<int32_t> miss((size_t)missing_cap, -1), added(trackpoint_list.size() + 1);
+    svs_map_constraint_result cons;
+    const int32_t other = root_id;
+    *out = CommitResult();
+    if (!ctx_.check(svs_map_add_loop_closure(map_, root_id, loop_id, T_newloop_from_w, (int)trackpoint_list.size(), trackpoint_list.empty() ? nullptr : trackpoint_list.data(),
+                                             (int)cached_ids.size(), cached_ids.empty() ? nullptr : cached_ids.data(), cached_T12.empty() ? nullptr : cached_T12.data(),
+                                             missing_cap, &out->result, &cons, miss.data(), added.data())))
+      return false;
+    committed(out, &other, &cons, miss.data(), missing_cap, added.data(), trackpoint_list.size());
+    return true;
+  }
+  // the result of a commit call into *out, and this object's edge keys (BackendRegistration calls it behind svs_reg_commit)
+  void committed(CommitResult *out, const int32_t *edge_kf, const svs_map_constraint_result *cons, const int32_t *miss, int missing_cap, const int32_t *added, size_t n_added) {
+    const int n_e = out->result.n_edges;
+    out->new_neighbors.assign(edge_kf, edge_kf + n_e);
+    out->constraints.assign(cons, cons + n_e);
+    for (int e = 0; e < n_e; ++e)
+      edge_keys_.push_back(std::make_pair(std::min(edge_kf[e], out->result.root_id), std::max(edge_kf[e], out->result.root_id)));
+    std::sort(edge_keys_.begin(), edge_keys_.end());
+    for (size_t i = 0; i < (size_t)n_e * missing_cap; ++i) if (miss[i] >= 0) out->missing.push_back(miss[i]);
+    std::sort(out->missing.begin(), out->missing.end());
+    out->missing.erase(std::unique(out->missing.begin(), out->missing.end()), out->missing.end());
+    out->track_added.assign(added, added + n_added);
+  }
+  // directNeighborsOf (backend.cpp:433-449) from this object's edge keys: the frame itself and every keyframe it shares an edge with
+  std::vector<int32_t> directNeighborsOf(int frame_id) const {
+    std::vector<int32_t> out(1, frame_id);
+    for (size_t i = 0; i < edge_keys_.size(); ++i) {
+      if (edge_keys_[i].first == frame_id) out.push_back(edge_keys_[i].second);
+      else if (edge_keys_[i].second == frame_id) out.push_back(edge_keys_[i].first);
+    }
+    return out;
+  }
   int anchorLevel(int point_id) const { return point_id >= 0 && (size_t)point_id < level_.size() ? level_[(size_t)point_id] : 0; }
 
  private:
@@ -1260,6 +1323,54 @@ class BackendRegistration {
       trackpoint_list->push_back(track_point(p, matches_[(size_t)i]));
     }
     return true;
+  }
+  // bool Backend::localRegisterFrame(int rootframe_id) on a device-resident map, to its end: the walk (framesInNeighborhood over directNeighborsOf(root).size() +
+  // num_frames_to_check keyframes, :552-561), the registration and the commit (svs_reg_commit: registerKeyframes on the device).  true: the graph was updated
+  bool localRegisterFrame(BackendMap &map, int rootframe_id, BackendMap::CommitResult *out = nullptr, int num_frames_to_check = 40,
+                          const std::vector<int32_t> &cached_ids = std::vector<int32_t>(), const std::vector<double> &cached_T12 = std::vector<double>()) {
+    if (!ok_ || !map.ok()) return false;
+    const std::vector<int32_t> direct = map.directNeighborsOf(rootframe_id);
+    std::vector<int32_t> walk;
+    const int size = std::min((int)direct.size() + num_frames_to_check, max_keyframes_);
+    if (!map.framesInNeighborhood(rootframe_id, size, &walk)) return false;
+    double T_root[12];
+    const int32_t root = rootframe_id;
+    if (!ctx_.check(svs_map_get_poses(map.get(), 1, &root, T_root))) return false;
+    if (!registerFrames(map, SVS_REG_LOCAL, rootframe_id, T_root, walk, direct, nullptr, nullptr, nullptr)) return false;
+    return commit(map, out, cached_ids, cached_T12);
+  }
+  // bool Backend::globalLoopClosure(const DetectedLoop&): T_loop_from_world = inverse(T_query_from_loop) * T_query_from_world is formed here (:845) as the library's
+  // kernels form a pose product (rows ((a0 b0 + a1 b1) + a2 b2) + t)
+  bool globalLoopClosure(BackendMap &map, int query_keyframe_id, int loop_keyframe_id, const double T_query_from_loop[12], BackendMap::CommitResult *out = nullptr,
+                         const std::vector<int32_t> &cached_ids = std::vector<int32_t>(), const std::vector<double> &cached_T12 = std::vector<double>()) {
+    if (!ok_ || !map.ok()) return false;
+    double Tq[12], Ti[12], T_loop[12];
+    const int32_t query = query_keyframe_id;
+    if (!ctx_.check(svs_map_get_poses(map.get(), 1, &query, Tq))) return false;
+    for (int i = 0; i < 3; ++i) {
+      for (int j = 0; j < 3; ++j) Ti[4 * i + j] = T_query_from_loop[4 * j + i];
+      Ti[4 * i + 3] = -((T_query_from_loop[i] * T_query_from_loop[3] + T_query_from_loop[4 + i] * T_query_from_loop[7]) + T_query_from_loop[8 + i] * T_query_from_loop[11]);
+    }
+    for (int i = 0; i < 3; ++i)
+      for (int j = 0; j < 4; ++j)
+        T_loop[4 * i + j] = ((Ti[4 * i] * Tq[j] + Ti[4 * i + 1] * Tq[4 + j]) + Ti[4 * i + 2] * Tq[8 + j]) + (j == 3 ? Ti[4 * i + 3] : 0.0);
+    const std::vector<int32_t> walk(1, query_keyframe_id);
+    if (!registerFrames(map, SVS_REG_LOOP, loop_keyframe_id, T_loop, walk, std::vector<int32_t>(), nullptr, nullptr, nullptr)) return false;
+    return commit(map, out, cached_ids, cached_T12);
+  }
+  // registerKeyframes / addLoopClosure for the request registerFrames ran last (svs_reg_commit)
+  bool commit(BackendMap &map, BackendMap::CommitResult *out, const std::vector<int32_t> &cached_ids = std::vector<int32_t>(),
+              const std::vector<double> &cached_T12 = std::vector<double>(), int missing_cap = 64) {
+    if (!ok_ || !map.ok() || cached_T12.size() != 12 * cached_ids.size() || missing_cap < 1) return false;
+    BackendMap::CommitResult r;
+    std::vector<int32_t> ekf((size_t)max_keyframes_, -1), miss((size_t)max_keyframes_ * missing_cap, -1), added((size_t)max_points_ + 1, 0);
+    std::vector<svs_map_constraint_result> cons((size_t)max_keyframes_);
+    if (!ctx_.check(svs_reg_commit(reg_, map.get(), 0, (int)cached_ids.size(), cached_ids.empty() ? nullptr : cached_ids.data(), cached_T12.empty() ? nullptr : cached_T12.data(),
+                                   missing_cap, &r.result, ekf.data(), nullptr, cons.data(), miss.data(), max_points_, nullptr, added.data())))
+      return false;
+    map.committed(&r, ekf.data(), cons.data(), miss.data(), missing_cap, added.data(), (size_t)r.result.n_track);
+    if (out) *out = r;
+    return r.result.committed != 0;
   }
   const std::vector<int32_t> &lastPointIds() const { return point_ids_; }          // registerFrames: per candidate
   const std::vector<int32_t> &lastKeyframeIds() const { return kf_ids_; }          // registerFrames: per table entry

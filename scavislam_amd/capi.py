@@ -8,7 +8,7 @@ import ctypes as C
 import os
 import weakref
 
-from .ctypes_types import BaParams, BaStats, Cam, FastGrid, LoopCheck, LoopLocation, LoopLocationResult, LoopResult, MapAddKeyframeArgs, MapConstraintRequest, MapStrengthResult, MapWindowResult, NbhRequest, NbhResult, PoseOptParams, PoseOptStats, RegMapRequest, RegParams, RegRequest, RegResult, SeedArgs, SeedParams, SeedRequest, StereoParams, SurfParams, VocabParams, VocabResult
+from .ctypes_types import BaParams, BaStats, Cam, FastGrid, LoopCheck, LoopLocation, LoopLocationResult, LoopResult, MapAddKeyframeArgs, MapConstraintRequest, MapStrengthResult, MapWindowResult, NbhRequest, NbhResult, PoseOptParams, PoseOptStats, RegCommitResult, RegMapRequest, RegParams, RegRequest, RegResult, SeedArgs, SeedParams, SeedRequest, StereoParams, SurfParams, VocabParams, VocabResult
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SVS_LIB_PATH") or os.path.join(_HERE, "libscavislam_hip.so")   # override = kernel A/B experiments only
@@ -248,6 +248,12 @@ _SIGS = {
     "svs_ba_window_edges": [C.c_void_p, C.POINTER(C.c_int32), C.c_void_p],
     "svs_reg_register_map_batch": [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(RegMapRequest), C.POINTER(RegParams), C.POINTER(RegResult), C.c_void_p, C.c_void_p,
                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
+    "svs_reg_commit": [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(RegCommitResult), C.c_void_p, C.c_void_p, C.c_void_p,
+                       C.c_void_p, C.c_int, C.c_void_p, C.c_void_p],
+    "svs_map_register_keyframes": [C.c_void_p, C.c_int32, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
+                                   C.c_int, C.POINTER(RegCommitResult), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
+    "svs_map_add_loop_closure": [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
+                                 C.POINTER(RegCommitResult), C.c_void_p, C.c_void_p, C.c_void_p],
     "svs_frontend_set_candidates_from_map": [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(NbhRequest), C.c_int, C.c_int, C.POINTER(NbhResult), C.c_void_p, C.c_void_p,
                                              C.c_void_p, C.c_void_p],
     "svs_ba_create": [C.c_void_p, C.POINTER(C.c_void_p)],

@@ -19,6 +19,8 @@
 //                   strength-ordered adjacency built from the edge records and one level-synchronous breadth-first search per request
 //   map_addkf.inc       inserting a keyframe (SlamGraph::addKeyframe): computeStrength as counting passes over the track points' observer rows with one workgroup per
 //                   call, the kept points and measured pairs compacted by prefix sums, the new edges' constraints through map_cons_kernel; two read-backs
+//   map_commit.inc      registerKeyframes / addLoopClosure: a device track list and an edge list applied to the map (the new pairs appended by prefix sums, the
+//                   edges through map_edge_add_kernel, their constraints through map_cons_kernel with the pose override)
 // Integer and copy work throughout (but for the three divisions of invert_depth and the f64 geometry of map_cons_kernel); the host keeps the id sets and the set of pairs, so every refusal happens before anything is uploaded.
 #include "reg_map.h"
 #include "nbh_map.h"
@@ -932,6 +934,7 @@ __global__ __launch_bounds__(MB_THREADS) void map_cons_kernel(MapK M, MapConsK A
 struct svs_map {
   svs_ctx *ctx = nullptr;
   int max_kf = 0, max_pt = 0, max_obs = 0;
+  uint64_t serial = 0;                                      // of this map among all that were created (svs_reg_commit: is it the map of the last batch)
   // the host's share: the id sets, the frames (where FAST and the matcher read a root), the set of pairs
   std::vector<uint8_t> kf_in, pt_in;
   std::vector<MapRootView> kf_view;
@@ -981,6 +984,7 @@ struct svs_map {
 };
 
 svs_ctx *svs_map_ctx(svs_map *map) { return map ? map->ctx : nullptr; }
+uint64_t svs_map_serial(const svs_map *map) { return map ? map->serial : 0; }
 bool svs_map_has_keyframe(const svs_map *map, int32_t id) { return map && id >= 0 && id < map->max_kf && map->kf_in[id]; }
 void svs_map_root_view(const svs_map *map, int32_t id, MapRootView *out) { *out = map->kf_view[id]; }
 
@@ -991,6 +995,7 @@ extern "C" int svs_map_create(svs_ctx *ctx, int max_keyframes, int max_points, i
   SVS_DEVICE(ctx);
   std::unique_ptr<svs_map> m(new svs_map());
   m->ctx = ctx; m->max_kf = max_keyframes; m->max_pt = max_points; m->max_obs = max_observations;
+  { static uint64_t made = 0; m->serial = __atomic_add_fetch(&made, 1, __ATOMIC_RELAXED); }
   m->kf_in.assign(max_keyframes, 0); m->pt_in.assign(max_points, 0);
   m->kf_view.resize(max_keyframes);
   m->kf_nobs.assign(max_keyframes, 0);
@@ -1662,3 +1667,4 @@ extern "C" int svs_map_compute_constraints(svs_map *m, int n, const svs_map_cons
 
 #include "map_walk.inc"
 #include "map_addkf.inc"
+#include "map_commit.inc"

@@ -37,3 +37,24 @@ bool svs_map_has_keyframe(const svs_map *map, int32_t id);
 void svs_map_root_view(const svs_map *map, int32_t id, MapRootView *out);
 // rebuilds the CSR views when the log has grown, then one workgroup per request builds what MapBuildDst names; asynchronous on the context's stream
 int svs_map_build_requests(svs_map *map, int n_requests, const MapBuildDst &dst);
+
+// registerKeyframes / addLoopClosure as one apply path (map_commit.inc): a track list of (point id, centre, level) records plus an edge list.  svs_reg_commit has
+// the track list on the device (d_track) and its ids downloaded (h_track_ids); the explicit calls give h_track, which goes up in the staged block.
+struct MapCommit {
+  int32_t pair_kf;                     // the keyframe that takes the pairs and whose pose T_new overrides: the root / the loop keyframe
+  double T_new[12];
+  int n_track;
+  const svs_map_track_point *d_track;  // DEVICE [n_track], or nullptr: h_track is staged
+  const svs_map_track_point *h_track;  // HOST [n_track] (d_track == nullptr)
+  const int32_t *h_track_ids;          // HOST [n_track] (d_track != nullptr)
+  int n_edges; const int32_t *h_edge_kf, *h_edge_strength; int edge_type;      // the edges (h_edge_kf[e], pair_kf)
+  bool other_first;                    // computeConstraint(h_edge_kf[e], pair_kf) (registerKeyframes) or (pair_kf, h_edge_kf[e]) (addLoopClosure)
+  int n_cached; const int32_t *h_cached_ids; const double *h_cached_T; int missing_cap;
+  svs_map_constraint_result *h_cons; int32_t *h_missing;      // [n_edges] / [n_edges][missing_cap]
+  int32_t *h_track_added;              // [n_track], optional
+  int32_t n_pairs_added;               // out
+};
+// every refusal happens before the map changes; BLOCKING
+int svs_map_apply_commit(svs_map *map, MapCommit *c);
+// distinguishes two maps that lived at one address
+uint64_t svs_map_serial(const svs_map *map);

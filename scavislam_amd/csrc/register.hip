@@ -16,6 +16,8 @@
 // Not pinned by the reference's binaries (backend.cpp is not among them): the yardstick of the cull and the counting is tests/register_model.py.
 // svs_reg_register_map_batch (at the end) runs the same chain (reg_chain) behind requests that the device-resident map (map.hip, reg_map.h) builds from ids in this
 // handle's staging block; the stateless call stages them from the host.
+// svs_reg_commit (behind it) is registerKeyframes / addLoopClosure for one request of such a batch: reg_commit_kernel builds the track list and the edge list from the
+// chain's outputs where they lie, the map applies them (map_commit.inc through reg_map.h).
 #include "common.h"
 #include "fast_view.h"
 #include "gate.h"
@@ -23,6 +25,7 @@
 #include "reg_map.h"
 #include <string.h>
 #include <algorithm>
+#include <vector>
 
 namespace {
 constexpr int RC_THREADS = 512;
@@ -275,6 +278,106 @@ __global__ __launch_bounds__(RG_THREADS) void reg_gate_kernel(RegK K) {
   }
 }
 
+// ---- svs_reg_commit: what registerKeyframes / addLoopClosure take (backend.cpp:601-604, :714-718, :945-971), from where the chain left it.  ONE workgroup for the one
+// request: the qualifying table entries as an LDS bitmap, per accepted candidate a walk of its observer row against that bitmap, the kept candidates compacted IN
+// CANDIDATE ORDER by wave ballots and popcount prefixes (the waves' counts meet in LDS, a running offset over the chunks: no arrival order decides a byte), the
+// qualifying entries likewise (entry 0 is the root, which never qualifies in LOCAL mode; the entries behind it ascend with their ids), T_new by one lane.
+constexpr int CM_THREADS = 256;
+struct reg_commit_hdr { int32_t n_track, n_edges, mode, status; double T_new[12]; int32_t pad_[4]; };      // 128 bytes
+struct RegCommitK {
+  int r, KB, SB, OB, NP; size_t cand_b;
+  const reg_hdr *hdr; const svs_reg_result *res; const svs_match_result *m2; const int32_t *accepted, *cand_src, *obs_begin, *obs_kf, *pid, *kfid;
+  const svs_reg_kf_stats *kfst; const svs_candidate_point *cand;
+  int query;                                  // SVS_REG_LOOP: h_walk_kf[0]
+  reg_commit_hdr *out; int32_t *edge_kf, *edge_str, *ids; svs_map_track_point *track;      // [KB], [KB], [NP], [NP]
+};
+
+// the exclusive prefix of `keep` over the workgroup and the workgroup's count; every lane calls it (two barriers inside)
+__device__ __forceinline__ int cm_rank(bool keep, int *s_w, int &total) {
+  const unsigned long long b = __ballot(keep);
+  const int lane = lane_id(), wave = threadIdx.x >> 6;
+  if (lane == 0) s_w[wave] = __popcll(b);
+  __syncthreads();
+  int off = 0, tot = 0;
+#pragma unroll
+  for (int w = 0; w < CM_THREADS / 64; ++w) { const int k = s_w[w]; off += w < wave ? k : 0; tot += k; }
+  __syncthreads();
+  total = tot;
+  return off + __popcll(b & ((1ull << lane) - 1ull));
+}
+
+__global__ __launch_bounds__(CM_THREADS) void reg_commit_kernel(RegCommitK K) {
+  __shared__ uint32_t s_q[REG_MAX_KF / 32];
+  __shared__ int s_w[CM_THREADS / 64];
+  const int tid = threadIdx.x, r = K.r;
+  const reg_hdr &H = K.hdr[r];
+  const svs_reg_result &R = K.res[r];
+  const int mode = H.mode, status = R.status;
+  if (status != SVS_REG_OK) {                                      // block-uniform: nothing to commit
+    if (tid == 0) { reg_commit_hdr o{}; o.mode = mode; o.status = status; *K.out = o; }
+    return;
+  }
+  const int n_kf = min(max(H.n_kf, 0), K.KB), n_cand = min(max(R.n_candidates, 0), K.NP);
+  const svs_reg_kf_stats *kfst = K.kfst + (size_t)r * K.KB;
+  if (tid < REG_MAX_KF / 32) s_q[tid] = 0;
+  __syncthreads();
+  // a. the qualifying entries: the bitmap, and (LOCAL) the edge list in ascending entry = ascending id
+  int n_edges = 0;
+  for (int k0 = 0; k0 < n_kf; k0 += CM_THREADS) {                  // block-uniform; n_kf <= KB <= REG_MAX_KF
+    const int k = k0 + tid;
+    const bool q = k < n_kf && kfst[k].qualifies != 0;
+    if (q) atomicOr(&s_q[k >> 5], 1u << (k & 31));
+    int tot;
+    const int pos = n_edges + cm_rank(q && mode == SVS_REG_LOCAL, s_w, tot);      // < KB
+    if (q && mode == SVS_REG_LOCAL) { K.edge_kf[pos] = K.kfid[(size_t)r * K.KB + k]; K.edge_str[pos] = kfst[k].strength; }
+    n_edges += tot;
+  }
+  __syncthreads();
+  // b. the track list, in candidate order
+  const int32_t *accepted = K.accepted + (size_t)r * K.NP, *cand_src = K.cand_src + (size_t)r * K.NP, *pid = K.pid + (size_t)r * K.NP;
+  const int32_t *ob = K.obs_begin + (size_t)r * (K.SB + 1), *ok = K.obs_kf + (size_t)r * K.OB;
+  const svs_match_result *m2 = K.m2 + (size_t)r * K.NP;
+  const svs_candidate_point *cand = K.cand + (size_t)r * K.cand_b;
+  int n_track = 0;
+  for (int i0 = 0; i0 < n_cand; i0 += CM_THREADS) {                // block-uniform
+    const int i = i0 + tid;
+    bool keep = false;
+    int si = -1;
+    if (i < n_cand && accepted[i] != 0) {
+      si = cand_src[i];
+      if ((unsigned)si < (unsigned)K.SB) {
+        if (mode == SVS_REG_LOOP) keep = true;
+        else {
+          const int e0 = max(ob[si], 0), e1 = min(ob[si + 1], K.OB);
+          for (int e = e0; e < e1; ++e) { const int kf = ok[e]; keep |= (unsigned)kf < (unsigned)n_kf && ((s_q[kf >> 5] >> (kf & 31)) & 1u); }
+        }
+      }
+    }
+    int tot;
+    const int pos = n_track + cm_rank(keep, s_w, tot);             // < n_cand <= NP
+    if (keep) {
+      svs_map_track_point t;
+      t.center[0] = m2[i].obs[0]; t.center[1] = m2[i].obs[1]; t.center[2] = m2[i].obs[2];
+      t.global_id = pid[si]; t.level = cand[i].anchor_level;
+      K.track[pos] = t;
+      K.ids[pos] = t.global_id;
+    }
+    n_track += tot;
+  }
+  if (tid == 0) {
+    if (mode == SVS_REG_LOOP) { K.edge_kf[0] = K.query; K.edge_str[0] = n_track; n_edges = 1; }      // (:214: the list's length)
+    reg_commit_hdr o{};
+    o.n_track = n_track; o.n_edges = n_edges; o.mode = mode; o.status = status;
+    double T[12], Tr[12], Tn[12];
+#pragma unroll
+    for (int k = 0; k < 12; ++k) { T[k] = R.T_newroot_from_oldroot[k]; Tr[k] = H.T_root[k]; }
+    pose_mul(T, Tr, Tn);
+#pragma unroll
+    for (int k = 0; k < 12; ++k) o.T_new[k] = Tn[k];
+    *K.out = o;
+  }
+}
+
 size_t reg_align(size_t v) { return (v + 255) & ~(size_t)255; }
 
 #define REG_CAPACITY(ctx, cond)                                                                           \
@@ -342,6 +445,11 @@ struct svs_reg {
   DevBuf<svs_pose_opt_stats> d_st;     // [2][max_req]
   DevBuf<uint8_t> d_pyr[SVS_NUM_PYR_LEVELS]; int stride[SVS_NUM_PYR_LEVELS] = {0, 0, 0};
   DevBuf<float> d_disp;
+  // svs_reg_commit: the kernel's block (header | edge ids | edge strengths | track point ids | track records) and its pinned twin up to the records; the last
+  // registration if it was a map batch
+  DevBuf<uint8_t> d_commit; PinnedBuf<uint8_t> h_commit;
+  svs_map *batch_map = nullptr; uint64_t batch_serial = 0; int batch_R = 0;
+  std::vector<int32_t> batch_query; std::vector<uint8_t> batch_done;
   int timing = 0; owned::Event ev[SVS_REG_STAGES + 1]; float stage_ms[SVS_REG_STAGES] = {0, 0, 0, 0, 0, 0, 0};
   ~svs_reg() {      // (before the members go, also when create gives up)
     if (ctx) { (void)hipSetDevice(ctx->device); (void)hipStreamSynchronize(ctx->stream); }
@@ -373,6 +481,14 @@ static void reg_fastgrid_for_level(int w, int h, int level, svs_fastgrid *g) {  
   for (int i = 0; i < SVS_MAX_CELLS; ++i) g->thr[i] = 25;
 }
 
+struct CommitLayout { size_t edge_kf, edge_str, ids, track, bytes; };
+static CommitLayout commit_layout(int KB, int NP) {
+  CommitLayout C;
+  C.edge_kf = sizeof(reg_commit_hdr); C.edge_str = C.edge_kf + reg_align((size_t)KB * 4); C.ids = C.edge_str + reg_align((size_t)KB * 4);
+  C.track = C.ids + reg_align((size_t)NP * 4); C.bytes = C.track + (size_t)NP * sizeof(svs_map_track_point);
+  return C;
+}
+
 static int reg_alloc(svs_reg *g) {
   svs_ctx *ctx = g->ctx;
   const size_t R = (size_t)g->max_req;
@@ -394,6 +510,9 @@ static int reg_alloc(svs_reg *g) {
   }
   SVS_HIP(ctx, g->d_disp.alloc(R * g->stride[0] * g->cams[0].h));
   for (int i = 0; i <= SVS_REG_STAGES; ++i) SVS_HIP(ctx, g->ev[i].create());
+  const CommitLayout CL = commit_layout(g->max_kf, std::max(g->max_pts, 1));
+  SVS_HIP(ctx, g->d_commit.alloc(CL.bytes));
+  SVS_HIP(ctx, g->h_commit.alloc(CL.track));
   return SVS_OK;
 }
 
@@ -557,6 +676,7 @@ extern "C" int svs_reg_register_batch(svs_reg *g, int n_requests, const svs_reg_
   }
   if (n_requests == 0) return SVS_OK;
   SVS_DEVICE(ctx);
+  g->batch_map = nullptr;              // (svs_reg_commit: the handle's last registration is no map batch)
   const int R = n_requests, NP = std::max(SB, 1);
   RegLayout L;
   L.set((size_t)R, (size_t)KB, (size_t)SB, (size_t)OB, (size_t)NP);
@@ -659,6 +779,7 @@ extern "C" int svs_reg_register_map_batch(svs_reg *g, svs_map *map, int n_reques
   }
   if (R == 0) return SVS_OK;
   SVS_DEVICE(ctx);
+  g->batch_map = nullptr;              // the previous batch ends here; this one can be committed once it has run
   RegLayout L;
   L.set((size_t)R, (size_t)KB, (size_t)SB, (size_t)OB, (size_t)NP, true);
   // ---- stage the ids
@@ -731,5 +852,81 @@ extern "C" int svs_reg_register_map_batch(svs_reg *g, svs_map *map, int n_reques
     if (h_kf_ids) { memcpy(h_kf_ids + r * MK, ho + L.kfid + (size_t)r * KB * 4, nk * 4); std::fill(h_kf_ids + r * MK + nk, h_kf_ids + (r + 1) * MK, -1); }
     if (h_n_kf) h_n_kf[r] = (int32_t)nk;
   }
+  g->batch_query.assign((size_t)R, -1);
+  for (int r = 0; r < R; ++r) if (req[r].mode == SVS_REG_LOOP) g->batch_query[(size_t)r] = req[r].h_walk_kf[0];
+  g->batch_done.assign((size_t)R, 0);
+  g->batch_map = map; g->batch_serial = svs_map_serial(map); g->batch_R = R;
+  return SVS_OK;
+}
+
+// ---- registerKeyframes / addLoopClosure for one request of that batch: reg_commit_kernel leaves the track list and the edge list on the device, the map applies them
+extern "C" int svs_reg_commit(svs_reg *g, svs_map *map, int request_index, int n_cached, const int32_t *h_cached_ids, const double *h_cached_T, int missing_cap,
+                              svs_reg_commit_result *h_res, int32_t *h_edge_kf, int32_t *h_edge_strength, svs_map_constraint_result *h_cons, int32_t *h_missing,
+                              int track_cap, int32_t *h_track_point_ids, int32_t *h_track_added) {
+  svs_ctx *ctx = g ? g->ctx : nullptr;
+  SVS_REQUIRE(ctx, g && map && svs_map_ctx(map) == ctx && h_res && h_cons && missing_cap >= 0 && (missing_cap == 0 || h_missing) && track_cap >= 0);
+  SVS_REQUIRE(ctx, g->batch_map == map && g->batch_serial == svs_map_serial(map));      // the last registration was a map batch on this map
+  SVS_REQUIRE(ctx, request_index >= 0 && request_index < g->batch_R && !g->batch_done[(size_t)request_index]);
+  SVS_DEVICE(ctx);
+  const int r = request_index, KB = g->max_kf, SB = g->max_pts, OB = g->max_obs, NP = std::max(SB, 1);
+  RegLayout L;
+  L.set((size_t)g->batch_R, (size_t)KB, (size_t)SB, (size_t)OB, (size_t)NP, true);
+  const CommitLayout CL = commit_layout(KB, NP);
+  const uint8_t *di = g->d_in, *dout = g->d_out;
+  uint8_t *dc = g->d_commit;
+  RegCommitK K{};
+  K.r = r; K.KB = KB; K.SB = SB; K.OB = OB; K.NP = NP; K.cand_b = (size_t)NP;
+  K.hdr = reinterpret_cast<const reg_hdr *>(di + L.hdr); K.res = reinterpret_cast<const svs_reg_result *>(dout + L.res);
+  K.m2 = reinterpret_cast<const svs_match_result *>(dout + L.m2); K.accepted = reinterpret_cast<const int32_t *>(dout + L.acc);
+  K.cand_src = reinterpret_cast<const int32_t *>(dout + L.csrc); K.obs_begin = reinterpret_cast<const int32_t *>(di + L.ob);
+  K.obs_kf = reinterpret_cast<const int32_t *>(di + L.ok); K.pid = reinterpret_cast<const int32_t *>(dout + L.pid); K.kfid = reinterpret_cast<const int32_t *>(dout + L.kfid);
+  K.kfst = reinterpret_cast<const svs_reg_kf_stats *>(dout + L.kfst); K.cand = g->d_cand;
+  K.query = g->batch_query[(size_t)r];
+  K.out = reinterpret_cast<reg_commit_hdr *>(dc); K.edge_kf = reinterpret_cast<int32_t *>(dc + CL.edge_kf); K.edge_str = reinterpret_cast<int32_t *>(dc + CL.edge_str);
+  K.ids = reinterpret_cast<int32_t *>(dc + CL.ids); K.track = reinterpret_cast<svs_map_track_point *>(dc + CL.track);
+  hipLaunchKernelGGL(reg_commit_kernel, dim3(1), dim3(CM_THREADS), 0, ctx->stream, K);
+  SVS_LAUNCH_CHECK(ctx);
+  SVS_HIP(ctx, hipMemcpyAsync(g->h_commit, g->d_commit, CL.track, hipMemcpyDeviceToHost, ctx->stream));      // the counts, the edge list, the track point ids
+  SVS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  const uint8_t *hc = g->h_commit;
+  const reg_commit_hdr H = *reinterpret_cast<const reg_commit_hdr *>(hc);
+  const int32_t *ekf = reinterpret_cast<const int32_t *>(hc + CL.edge_kf), *est = reinterpret_cast<const int32_t *>(hc + CL.edge_str), *ids = reinterpret_cast<const int32_t *>(hc + CL.ids);
+  const bool meta_over = H.status == SVS_REG_OK && (H.n_track < 0 || H.n_track > NP || H.n_edges < 0 || H.n_edges > KB);
+  SVS_REQUIRE(ctx, !meta_over);
+  svs_reg_commit_result out;
+  memset(&out, 0, sizeof out);
+  out.mode = H.mode; out.root_id = reinterpret_cast<const map_req *>(g->h_in.get() + L.mreq)[r].root; out.other_id = H.mode == SVS_REG_LOOP ? g->batch_query[(size_t)r] : -1;
+  out.status = H.status;
+  const bool lists = h_track_point_ids || h_track_added;
+  if (H.status == SVS_REG_OK) {
+    REG_CAPACITY(ctx, !lists || track_cap >= H.n_track);
+    MapCommit c{};
+    c.pair_kf = out.root_id; memcpy(c.T_new, H.T_new, sizeof c.T_new);
+    c.n_track = H.n_track; c.d_track = K.track; c.h_track_ids = ids;
+    c.n_edges = H.n_edges; c.h_edge_kf = ekf; c.h_edge_strength = est;
+    c.edge_type = H.mode == SVS_REG_LOOP ? 2 : 1; c.other_first = H.mode != SVS_REG_LOOP;
+    c.n_cached = n_cached; c.h_cached_ids = h_cached_ids; c.h_cached_T = h_cached_T; c.missing_cap = missing_cap;
+    c.h_cons = h_cons; c.h_missing = h_missing;
+    std::vector<int32_t> added((size_t)H.n_track, 0);
+    c.h_track_added = added.data();
+    if (int rc = svs_map_apply_commit(map, &c)) return rc;
+    g->batch_done[(size_t)r] = 1;
+    out.committed = 1; out.n_track = H.n_track; out.n_pairs_added = c.n_pairs_added; out.n_edges = H.n_edges;
+    memcpy(out.T_new, H.T_new, sizeof out.T_new);
+    for (int i = 0; i < track_cap; ++i) {
+      if (h_track_point_ids) h_track_point_ids[i] = i < H.n_track ? ids[i] : -1;
+      if (h_track_added) h_track_added[i] = i < H.n_track ? added[(size_t)i] : 0;
+    }
+  } else {
+    for (int i = 0; i < track_cap; ++i) {
+      if (h_track_point_ids) h_track_point_ids[i] = -1;
+      if (h_track_added) h_track_added[i] = 0;
+    }
+  }
+  for (int e = 0; e < KB; ++e) {
+    if (h_edge_kf) h_edge_kf[e] = e < out.n_edges ? ekf[e] : -1;
+    if (h_edge_strength) h_edge_strength[e] = e < out.n_edges ? est[e] : 0;
+  }
+  *h_res = out;
   return SVS_OK;
 }

@@ -318,6 +318,15 @@ class MapStrengthResult(C.Structure):
     _fields_ = [("n_keys", C.c_int32), ("m", C.c_int32), ("over_capacity", C.c_int32), ("n_edges", C.c_int32)]
 
 
+class RegCommitResult(C.Structure):
+    """svs_reg_commit_result: what svs_reg_commit / svs_map_register_keyframes / svs_map_add_loop_closure did to the map"""
+    _fields_ = [("committed", C.c_int32), ("mode", C.c_int32), ("root_id", C.c_int32), ("other_id", C.c_int32), ("n_track", C.c_int32),
+                ("n_pairs_added", C.c_int32), ("n_edges", C.c_int32), ("status", C.c_int32), ("T_new", C.c_double * 12)]
+
+
+assert C.sizeof(RegCommitResult) == 128
+
+
 class KeyframeC(C.Structure):
     """svs_keyframe (KEYFRAME_DTYPE as a ctypes structure)"""
     _fields_ = [("T_anchor_from_w", C.c_double * 12), ("pyr", C.c_void_p * 3), ("stride", C.c_int32 * 3), ("pad_", C.c_int32)]

@@ -4,19 +4,21 @@
                                                                                keyframesToRegister :615-722)
   KeyframeRegistrar.loop_closure(requests)    <- Backend::globalLoopClosure    backend.cpp:830-1001
 
-A request is one root keyframe with the candidate map points the caller's graph walk found (framesInNeighborhood, the hash-set deduplication, registerKeyframes /
-addLoopClosure stay with the caller).  A batch of requests is ONE library call: one staged upload, one chain of launches, one download.  There is no CPU path:
-every call goes to svs_reg_* of the HIP library.
+A request of the stateless calls is one root keyframe with the candidate map points the caller's graph walk found (framesInNeighborhood, the hash-set deduplication,
+registerKeyframes / addLoopClosure stay with that caller; on a ResidentMap they are frames_in_neighborhood, register_map_batch and commit).  A batch of requests is
+ONE library call: one staged upload, one chain of launches, one download.  There is no CPU path: every call goes to svs_reg_* of the HIP library.
 
   ResidentMap                                  the map on the device (svs_map_*): keyframes, points and feature_table pairs under the graph's ids, updated incrementally
   KeyframeRegistrar.register_map_batch(map, requests)   the same registration with a request named by ids: the point walk of pointsVisibleInRoot runs on the device
+  KeyframeRegistrar.commit(map, i)             registerKeyframes / addLoopClosure for request i of that batch, from the lists the registration left on the device
+  ResidentMap.register_keyframes / add_loop_closure     the same two functions with the caller's own lists
 """
 import ctypes as C
 
 import numpy as np
 
 from .ctypes_types import (BA_CONSTRAINT_DTYPE, BA_EDGE_DTYPE, CANDIDATE_DTYPE, CONS_OK, KEYFRAME_DTYPE, MAP_ADDKF_MAX_NEIGHBORS, MAP_CONS_MAX_REQUESTS, MAP_CONSTRAINT_RESULT_DTYPE, MAP_EDGE_DTYPE, MAP_KEY_DTYPE, MAP_NEW_POINT_DTYPE, MAP_TRACK_POINT_DTYPE, MAP_WALK_MAX_REQUESTS, MAP_WINDOW_MAX, MATCH_RESULT_DTYPE, REG_KF_STATS_DTYPE, REG_LOCAL, REG_LOOP, REG_OK, REG_OVER_CAPACITY,
-                           REG_STAGES, SVS_MAX_CELLS, WALK_OK, Cam, MapAddKeyframeArgs, MapConstraintRequest, MapStrengthResult, MapWindowResult, RegMapRequest, RegParams, RegRequest, RegResult)
+                           REG_STAGES, SVS_MAX_CELLS, WALK_OK, Cam, MapAddKeyframeArgs, MapConstraintRequest, MapStrengthResult, MapWindowResult, RegCommitResult, RegMapRequest, RegParams, RegRequest, RegResult)
 
 
 def keyframe_table(entries):
@@ -68,6 +70,7 @@ class KeyframeRegistrar:
         self.h = h
         ctx.children.add(self)
         self.raw = None      # the full-length rows of the last call (tests: byte comparisons)
+        self.commit_raw = None   # the arrays of the last commit as the library wrote them
 
     def _request(self, q, mode, keep):
         r = RegRequest()
@@ -172,6 +175,25 @@ class KeyframeRegistrar:
     def loop_closure(self, requests, **kw):
         return self.register_batch(requests, [REG_LOOP] * len(requests), **kw)
 
+    def commit(self, resident_map, index, cached=None, missing_cap=16, resolve_missing=True):
+        """registerKeyframes / addLoopClosure for request `index` of the last register_map_batch on resident_map, with the lists taken where the registration left
+        them on the device (svs_reg_commit).  Returns a dict: committed (False: the request's status was not REG_OK, the map is unchanged), mode, root_id (the
+        keyframe that took the pairs), other_id (loop mode: the query keyframe), T_new [12], track_point_ids, track_added, n_pairs_added, edges [(kf1, kf2) as
+        computeConstraint took them], edge_strength, edge_results (as compute_constraints returns them) and missing.  resolve_missing=True completes the edges that
+        lacked an anchor through absolute_poses and a storing compute_constraints, as ResidentMap.add_keyframe does"""
+        cids, cT = _cached_arrays(cached)
+        MK, MP, cap = self.max_keyframes, max(self.max_points, 1), int(missing_cap)
+        res = RegCommitResult()
+        ekf, est = np.full(MK, -1, np.int32), np.zeros(MK, np.int32)
+        cons = np.zeros(MK, MAP_CONSTRAINT_RESULT_DTYPE)
+        missing = np.full((MK, cap), -1, np.int32)
+        tid, tadd = np.full(MP, -1, np.int32), np.zeros(MP, np.int32)
+        self.ctx.check(self.ctx.lib.svs_reg_commit(self.h, resident_map.h, int(index), len(cids), cids.ctypes.data if len(cids) else None,
+                                                   cT.ctypes.data if len(cids) else None, cap, C.byref(res), ekf.ctypes.data, est.ctypes.data, cons.ctypes.data,
+                                                   missing.ctypes.data if cap else None, MP, tid.ctypes.data, tadd.ctypes.data))
+        self.commit_raw = dict(result=bytes(res), edge_kf=ekf, edge_strength=est, results=cons, missing=missing, track_point_ids=tid, track_added=tadd)
+        return resident_map._commit_out(res, ekf, est, cons, missing, tid[:res.n_track].copy(), tadd[:res.n_track].astype(bool), cached, cap, resolve_missing)
+
     def set_timing(self, on=True):
         self.ctx.check(self.ctx.lib.svs_reg_set_timing(self.h, int(on)))
 
@@ -191,6 +213,14 @@ class KeyframeRegistrar:
             self.close()
         except Exception:
             pass
+
+
+def _cached_arrays(cached):
+    """{anchor id: T[12]} -> (ids ascending, T [n, 12]) as the library takes a cached list"""
+    cached = cached or {}
+    ids = np.array(sorted(int(c) for c in cached), np.int32)
+    T = np.ascontiguousarray([np.asarray(cached[int(c)], np.float64).reshape(12) for c in ids], np.float64).reshape(len(ids), 12)
+    return ids, T
 
 
 def _inner_pairs_with_edge(window, edge_keys):
@@ -583,9 +613,10 @@ class ResidentMap:
         out["do_loop_detection"] = len(out["exclude_set"]) < n_kf + (0 if out["over_capacity"] else 1)      # (against vertex_table().size() after the insertion)
         return out
 
-    def complete_constraints(self, pairs, results, cached=None, missing_cap=16):
+    def complete_constraints(self, pairs, results, cached=None, missing_cap=16, overrides=()):
         """the edges of `pairs` whose result lacks anchors: their poses through absolute_poses, then a storing compute_constraints, until no request lacks an
-        anchor that has a path to the window (update_marginalization's resolve_missing) -> (results, the anchors still missing)"""
+        anchor that has a path to the window (update_marginalization's resolve_missing) -> (results, the anchors still missing).  overrides: the pose overrides
+        every repeated request carries (registerKeyframes / addLoopClosure: the root at its new pose)"""
         results, cached = list(results), dict(cached or {})
         miss = sorted({int(v) for o in results for v in o["missing"]})
         while miss:
@@ -597,11 +628,70 @@ class ResidentMap:
             todo = [i for i, o in enumerate(results) if o["n_missing"]]
             for at in range(0, len(todo), MAP_CONS_MAX_REQUESTS):
                 part = todo[at:at + MAP_CONS_MAX_REQUESTS]
-                again = self.compute_constraints([dict(kf1=pairs[i][0], kf2=pairs[i][1], store=True, cached=cached) for i in part], missing_cap=missing_cap)
+                again = self.compute_constraints([dict(kf1=pairs[i][0], kf2=pairs[i][1], store=True, cached=cached, overrides=overrides) for i in part],
+                                                 missing_cap=missing_cap)
                 for i, o in zip(part, again):
                     results[i] = o
             miss = sorted({int(v) for o in results for v in o["missing"]})
         return results, miss
+
+    # ---- committing a registration or a loop closure (SlamGraph::registerKeyframes / addLoopClosure, slam_graph.cpp:188-251): see include/scavislam_hip.h
+    def _commit_out(self, res, ekf, est, cons, missing, track_ids, track_added, cached, cap, resolve_missing):
+        """the result of one of the three commit calls as a dict; follows the edge mirrors and completes the missing anchors"""
+        n_e = int(res.n_edges)
+        pair_kf, T_new = int(res.root_id), np.array(res.T_new, np.float64)
+        others = [int(k) for k in ekf[:n_e]]
+        edges = [(pair_kf, o) if res.mode == REG_LOOP else (o, pair_kf) for o in others]      # (kf1, kf2) of computeConstraint
+        results = [dict(status=int(cons[i]["status"]), strength=int(cons[i]["strength"]), n_missing=int(cons[i]["n_missing"]), median=float(cons[i]["median"]),
+                        norm_dist=float(cons[i]["norm_dist"]), T_12=cons[i]["T_12"].copy(), info=cons[i]["info"].copy(),
+                        missing=missing[i, :min(int(cons[i]["n_missing"]), cap)].copy()) for i in range(n_e)]
+        if res.committed:
+            if res.n_pairs_added:
+                self.window_shape = None
+            self.edge_keys.update((min(o, pair_kf), max(o, pair_kf)) for o in others)
+            self.edge_log += [(o, pair_kf, int(s)) for o, s in zip(others, est[:n_e])]
+        miss = sorted({int(v) for o in results for v in o["missing"]})
+        if resolve_missing and miss:
+            results, miss = self.complete_constraints(edges, results, cached, missing_cap=max(cap, 1), overrides=[(pair_kf, T_new)])
+        return dict(committed=bool(res.committed), status=int(res.status), mode=int(res.mode), root_id=pair_kf, other_id=int(res.other_id), T_new=T_new,
+                    n_track=int(res.n_track), n_pairs_added=int(res.n_pairs_added), track_point_ids=track_ids, track_added=track_added, edges=edges,
+                    edge_strength=[int(s) for s in est[:n_e]], edge_results=results, missing=miss)
+
+    def register_keyframes(self, root_id, T_newroot_from_w, neighborid_to_strength, track_points, covis_thr, cached=None, missing_cap=16, resolve_missing=True):
+        """SlamGraph::registerKeyframes with the caller's own lists (svs_map_register_keyframes): neighborid_to_strength {keyframe id: strength} (addNewEdges' test
+        strength >= covis_thr is applied here; the edges come in ascending id), track_points MAP_TRACK_POINT_DTYPE.  Returns what KeyframeRegistrar.commit returns"""
+        tp = np.ascontiguousarray(track_points, MAP_TRACK_POINT_DTYPE).reshape(-1)
+        nb = np.array([int(k) for k in neighborid_to_strength], np.int32)
+        st = np.array([int(neighborid_to_strength[k]) for k in neighborid_to_strength], np.int32)
+        T = np.ascontiguousarray(T_newroot_from_w, np.float64).reshape(12)
+        cids, cT = _cached_arrays(cached)
+        cap, n = int(missing_cap), max(len(nb), 1)
+        res = RegCommitResult()
+        ekf, cons, missing, added = np.full(n, -1, np.int32), np.zeros(n, MAP_CONSTRAINT_RESULT_DTYPE), np.full((n, cap), -1, np.int32), np.zeros(len(tp), np.int32)
+        self._call("svs_map_register_keyframes", int(root_id), T.ctypes.data, len(nb), nb.ctypes.data if len(nb) else None, st.ctypes.data if len(nb) else None,
+                   int(covis_thr), len(tp), tp.ctypes.data if len(tp) else None, len(cids), cids.ctypes.data if len(cids) else None,
+                   cT.ctypes.data if len(cids) else None, cap, C.byref(res), ekf.ctypes.data, cons.ctypes.data, missing.ctypes.data if cap else None,
+                   added.ctypes.data if len(tp) else None)
+        by_id = {int(k): int(v) for k, v in zip(nb, st)}
+        est = np.array([by_id[int(k)] for k in ekf[:res.n_edges]], np.int32)
+        self.raw = dict(result=bytes(res), edge_kf=ekf, results=cons, missing=missing, track_added=added)
+        return self._commit_out(res, ekf, est, cons, missing, tp["global_id"].copy(), added.astype(bool), cached, cap, resolve_missing)
+
+    def add_loop_closure(self, root_id, loop_id, T_newloop_from_w, track_points, cached=None, missing_cap=16, resolve_missing=True):
+        """SlamGraph::addLoopClosure with the caller's own list (svs_map_add_loop_closure): the pairs go to loop_id, the APPEARANCE edge (root_id, loop_id) has
+        strength len(track_points).  Returns what KeyframeRegistrar.commit returns"""
+        tp = np.ascontiguousarray(track_points, MAP_TRACK_POINT_DTYPE).reshape(-1)
+        T = np.ascontiguousarray(T_newloop_from_w, np.float64).reshape(12)
+        cids, cT = _cached_arrays(cached)
+        cap = int(missing_cap)
+        res = RegCommitResult()
+        cons, missing, added = np.zeros(1, MAP_CONSTRAINT_RESULT_DTYPE), np.full((1, cap), -1, np.int32), np.zeros(len(tp), np.int32)
+        self._call("svs_map_add_loop_closure", int(root_id), int(loop_id), T.ctypes.data, len(tp), tp.ctypes.data if len(tp) else None, len(cids),
+                   cids.ctypes.data if len(cids) else None, cT.ctypes.data if len(cids) else None, cap, C.byref(res), cons.ctypes.data,
+                   missing.ctypes.data if cap else None, added.ctypes.data if len(tp) else None)
+        self.raw = dict(result=bytes(res), results=cons, missing=missing, track_added=added)
+        return self._commit_out(res, np.array([int(root_id)], np.int32), np.array([len(tp)], np.int32), cons, missing, tp["global_id"].copy(), added.astype(bool),
+                                cached, cap, resolve_missing)
 
     def get_points(self, point_ids):
         """blocking read-back of the stored point records (CANDIDATE_DTYPE, kf_index = the anchor's id)"""
