@@ -412,7 +412,7 @@ int svs_pointcloud_full_pose(svs_ctx *ctx, const double *d_T, const svs_cam *cam
 /* ---- one call per frame: replaces the data-parallel part of StereoFrontend::processFrame(bool*) / processFirstFrame()
    (stereo_frontend.h:88-95, stereo_frontend.cpp:110-131,183-306) for one camera stream, HOST buffers in and out.  The stages are
    the entry points above, chained on the context's stream with no host round trip in between; keyframe switching / dropping and
-   list building stay with the caller (stereo_frontend.cpp:265-296). -----------------------------------------------------------*/
+   list building (stereo_frontend.cpp:265-296) are decided by svs_frontend_decide_keyframes below and applied by the caller. ----*/
 typedef struct {
   int32_t fast_trials;                 /* 6 (stereo_frontend.cpp:232); the first frame uses one less (:118) */
   int32_t search_radius, thr_mean, thr_std;      /* 8, 22, 10 (:989-1004, CPU build) */
@@ -595,7 +595,8 @@ typedef struct {
    of the frame processed last, the gate records and point statistics of the last step.  Ordered behind that step on the context's stream; one staged upload of
    the requests, one download of all records (with more than 1 MiB of output rows the counts come first and the records follow as one strided copy of the
    longest list's width; what a row of h_out holds behind its own records is then unspecified).  BLOCKING.  h_out [n][cap_per_request], h_n_new [n][3].  Works for the one-stream and the batch front end.
-   Building the candidate lists from the records stays with the caller (stereo_frontend.cpp:265-296) */
+   The add_flags of a dropped frame and the lists behind it (stereo_frontend.cpp:265-296) come from svs_frontend_decide_keyframes; putting the seeded records
+   into newpoint_map is the caller's */
 int svs_frontend_seed_keyframes(svs_frontend *fe, int n, const svs_seed_request *req, const svs_seed_params *prm, svs_candidate_point *h_out, int cap_per_request,
                                 int32_t *h_n_new);
 
@@ -1362,6 +1363,120 @@ typedef struct {
    max_points, kf_index of an unkept slot); SVS_ERR_CAPACITY: more than 64 groups; SVS_ERR_UNSUPPORTED: max_keyframes above 32767. */
 int svs_frontend_set_candidates_from_map(svs_frontend *fe, svs_map *map, int n_requests, const svs_nbh_request *req, int refresh_poses, int vertex_cap,
                                          svs_nbh_result *h_res, int32_t *h_point_id, int32_t *h_vertex_id, double *h_vertex_T, svs_candidate_point *h_records);
+
+/* ---- front end: the keyframe logic behind a step -- processMatchedPoints' two lists (stereo_frontend.cpp:859-968), shallWeSwitchKeyframe (:446-510),
+   shallWeDropNewKeyframe (:512-528) and the bookkeeping of addNewKeyframe (:316-415) -- decided on the device from what the step left there: one workgroup per
+   stream, one launch for the batch, one small decision record per stream and the two AddToOptimzer lists in the record types svs_map_add_keyframe takes.  The
+   stage READS the front end's state only (pose, clouds, keyframe slots and candidate lists are untouched); the caller applies a decision through
+   svs_frontend_keep_keyframe_of, svs_frontend_recompute_cloud, svs_frontend_seed_keyframes and svs_map_add_keyframe.  Restated in tests/keyframe_model.py.
+   Per stream.  Inputs: the n match, candidate and gate records of the last step, its svs_point_stats, the refined T_cur_from_actkey, tracking_ok; a VERTEX TABLE
+   of V <= SVS_KF_MAX_VERTICES entries in the caller's order (neighborhood_->vertex_map), each with its keyframe id, T_me_from_w and a feature set F(v) -- either a
+   range of the stream's staged, strictly ascending id array, or "the map's" (set_begin = SVS_KF_SET_MAP): the points whose observer row in the resident map holds
+   the keyframe AS THE MAP IS AT THE CALL (a departure: the reference snapshots feat_map when the neighbourhood is computed; without a map such a set is empty);
+   the index `act` of the active keyframe's vertex; the indices of its strength_to_neighbors vertices (distinct, not act); the slot table slot_kf[max_keyframes]
+   (the keyframe id kept in each slot, -1 for none, as in svs_nbh_request).  The reference's containers are hash tables; every order below is canonical:
+     0. tracking_ok == 0 (:243), or a table the device finds malformed (V, act, a neighbour index or a set range out of bounds): valid = 0, every other field of
+        the record zero, no list written.
+     1. lists.  A = the records with status == SVS_MATCH_OK and accepted != 0, in ascending record index (obs_list's order); those with is_new != 0 form the new
+        list, the others the track list.  A new entry: xyz_anchor, anchor_obs_pyr, anchor_level, point_id from the candidate, anchor_id = slot_kf[kf_index] (-1 for a
+        kf_index outside the table), feat_center = obs, feat_level = anchor_level.  A track entry: center = obs, global_id = point_id, level = anchor_level.  Beside
+        each list the record index of every entry (the caller prunes newpoint_map with it, :360-365).  n_new and n_track are always reported.
+     2. switch.  For every v != act: T_diff(v) = pose_mul(pose_mul(T_cur_from_actkey, T_act_from_w), pose_inv(T_v_from_w)) (f64, rows summed left to right, no
+        contraction), dist(v) = sqrt((tx tx + ty ty) + tz tz).  closest = the v of least (dist, table index) among dist(v) < 0.5 * (double)parallax_thr (strict; a
+        NaN is never less); closest_index / closest_id / closest_dist report it (-1 / -1 / 0.0 when there is none).  shared = the track entries whose global_id is
+        in F(closest), an id listed twice counting twice.  decision = SVS_KF_SWITCH iff closest exists and shared > switch_min_shared; T_cur_after = T_diff(closest).
+     3. drop, only without a switch.  featureless = the num_points_grid2x2 cells below featureless_cell_min; av_track_length = sum_track_length /
+        (double)num_track_points (0 / 0: the quiet NaN 0x7ff8000000000000, which compares false).  decision = SVS_KF_DROP iff featureless > featureless_corners_thr,
+        or the norm of T_cur_from_actkey's translation (as in rule 2) > (double)parallax_thr, or av_track_length > max_av_track_length; else SVS_KF_KEEP with
+        T_cur_after = T_cur_from_actkey.  (With a switch both figures are reported as zero.)
+     4. new keyframe, only for SVS_KF_DROP.  add_flags[k] = num_points_grid3x3[k] <= min_num_points; T_newkey_from_w = pose_mul(T_cur_from_actkey, T_act_from_w);
+        T_cur_after = the identity.  num_matches(k) = the new entries with anchor_id k (k >= 0), plus -- for k = act's id and the ids of act's neighbour vertices
+        only -- the track entries in F(k).  strength_to_neighbors = the keys with num_matches > covis_thr in ascending (count, keyframe id) (the reference's
+        multimap leaves equal counts in hash order): n_strength, strength_kf, strength_count.  More than SVS_KF_MAX_STRENGTH keys: over_capacity = 1, the list
+        empty (n_strength = 0), everything else valid.
+     5. a stream's outputs are a function of that stream's inputs alone: not of the batch, of repetition, or of whether a set was staged or read from a map
+        with the same content.  Compaction is by ballot popcounts and a workgroup prefix, counts are integer sums: no arrival order decides an output. */
+#define SVS_KF_MAX_VERTICES 64
+#define SVS_KF_MAX_STRENGTH 64
+#define SVS_KF_MAX_SLOTS 1024
+#define SVS_KF_SET_MAP (-1)
+enum { SVS_KF_KEEP = 0, SVS_KF_SWITCH = 1, SVS_KF_DROP = 2 };
+typedef struct {
+  float parallax_thr;                  /* ui.parallax_thr (0.75f; a pangolin::Var<float>) */
+  int32_t switch_min_shared;           /* 100 (:503) */
+  int32_t featureless_cell_min;        /* 15 (:519) */
+  int32_t featureless_corners_thr;     /* params_.new_keyframe_featuerless_corners_thr (2) */
+  double max_av_track_length;          /* 75. (:527) */
+  int32_t covis_thr;                   /* params_.covis_thr (15); >= 0 */
+  int32_t min_num_points;              /* ui.min_num_points (25) */
+} svs_keyframe_decide_params;          /* 32 bytes */
+void svs_keyframe_decide_params_default(svs_keyframe_decide_params *p);
+typedef struct {
+  double T_me_from_w[12];
+  int32_t kf_id;
+  int32_t set_begin, set_count;        /* F(v) = ids[set_begin .. set_begin + set_count) of the stream's staged array, or set_begin = SVS_KF_SET_MAP */
+  int32_t pad_;
+} svs_kf_vertex;                       /* 112 bytes */
+typedef struct {
+  int32_t n_vertex, act, n_neighbors, pad_;
+  int32_t neighbors[SVS_KF_MAX_VERTICES];      /* vertex indices of act's strength_to_neighbors */
+} svs_kf_table;                        /* 272 bytes */
+typedef struct {
+  int32_t valid, decision, n_new, n_track;
+  int32_t closest_index, closest_id, shared, featureless;
+  double closest_dist, av_track_length;
+  double T_cur_after[12];
+  double T_newkey_from_w[12];
+  int32_t add_flags[9];                /* [i * 3 + j] */
+  int32_t n_strength, over_capacity, pad_;
+  int32_t strength_kf[SVS_KF_MAX_STRENGTH];
+  int32_t strength_count[SVS_KF_MAX_STRENGTH];
+} svs_keyframe_decision;               /* 800 bytes */
+typedef struct {                       /* all pointers DEVICE; stream b at + b * (its batch stride) elements */
+  const svs_match_result *d_res; size_t res_bstride;
+  const svs_candidate_point *d_pts; size_t pts_bstride;
+  const svs_gated_point *d_gated; size_t gated_bstride;
+  const svs_point_stats *d_stats;      /* [batch] */
+  const double *d_T_cur_from_actkey;   /* [batch][12] */
+  const int32_t *d_tracking_ok;        /* [batch] */
+  const int32_t *d_n;                  /* [batch] records of each stream (at most n), or NULL: n for all */
+  int32_t n, batch;
+  const svs_kf_table *d_table;         /* [batch] */
+  const svs_kf_vertex *d_vertex; size_t vertex_bstride;      /* [batch][vertex_bstride]; vertex_bstride <= SVS_KF_MAX_VERTICES bounds n_vertex */
+  const int32_t *d_set_ids; size_t set_bstride;              /* [batch][set_bstride]: the staged id arrays */
+  const int32_t *d_slot_kf; size_t slot_bstride;             /* [batch][slot_bstride], max_keyframes entries read */
+  int32_t max_keyframes, pad_;         /* <= SVS_KF_MAX_SLOTS */
+  svs_map *map;                        /* the map behind SVS_KF_SET_MAP sets (same context), or NULL */
+} svs_keyframe_decide_args;
+/* stateless, ASYNCHRONOUS on the context's stream (a map whose log has grown rebuilds its CSR views first).  d_dec [batch]; d_new / d_track / d_new_rec /
+   d_track_rec [batch][cap]: the lists and their record indices (entries behind a list's count are left as they were).  SVS_ERR_CAPACITY: cap < n, vertex_bstride
+   above SVS_KF_MAX_VERTICES; SVS_ERR_UNSUPPORTED: max_keyframes above SVS_KF_MAX_SLOTS; SVS_ERR_INVALID: a missing pointer, covis_thr < 0, a map of another context */
+int svs_keyframe_decide(svs_ctx *ctx, const svs_keyframe_decide_args *a, const svs_keyframe_decide_params *prm, svs_keyframe_decision *d_dec,
+                        svs_map_new_point *d_new, svs_map_track_point *d_track, int32_t *d_new_rec, int32_t *d_track_rec, int cap);
+/* a stream's vertex table, resident until it is set again.  One staged upload and one scatter launch for all requests; everything is checked first. */
+typedef struct {
+  int32_t stream, n_vertex, act, n_neighbors;
+  const int32_t *h_vertex_kf;          /* HOST [n_vertex]: keyframe ids */
+  const double *h_vertex_T;            /* HOST [n_vertex][12]: T_me_from_w */
+  const int32_t *h_set_begin;          /* HOST [n_vertex]: start of F(v) in h_set_ids, or SVS_KF_SET_MAP */
+  const int32_t *h_set_count;          /* HOST [n_vertex] (ignored for SVS_KF_SET_MAP) */
+  const int32_t *h_set_ids;            /* HOST [n_set_ids]; every range strictly ascending */
+  const int32_t *h_neighbors;          /* HOST [n_neighbors]: vertex indices */
+  const int32_t *h_slot_kf;            /* HOST [max_keyframes] */
+  int32_t n_set_ids, pad_;
+} svs_vertex_request;
+/* SVS_ERR_INVALID, nothing uploaded: a stream out of range or named twice, n_vertex < 1, an id twice in a table, act or a neighbour index out of range, a
+   neighbour equal to act or listed twice, a set range outside h_set_ids or not strictly ascending, a slot entry >= 0 for a slot that was never kept, a call
+   between svs_frontend_submit_frame and _wait_frame.  SVS_ERR_CAPACITY: more than SVS_KF_MAX_VERTICES vertices (the front end's vertex_cap), more than
+   16 * max_points staged ids.  SVS_ERR_UNSUPPORTED: a front end with more than SVS_KF_MAX_SLOTS keyframe slots. */
+int svs_frontend_set_vertex_table(svs_frontend *fe, int n_requests, const svs_vertex_request *req);
+/* BLOCKING.  The decision of every stream from the last step's device state and the resident vertex tables: one launch, one download of all decision records
+   (h_dec [n_streams]), then the list rows -- want_lists = 1: of the streams whose decision is SVS_KF_DROP, 2: of every valid stream, 0: none -- as one strided
+   copy per array and run of consecutive such streams into h_new / h_track / h_new_rec / h_track_rec [n_streams][cap] (rows of other streams and entries behind
+   a list's count are not written).  `map` may be NULL unless a table names SVS_KF_SET_MAP.  SVS_ERR_INVALID: the last frame call was not a step, a candidate list
+   was set since (the SVS_SEED_MORE rule), a stream without a vertex table; SVS_ERR_CAPACITY: want_lists != 0 and cap below the step's record count. */
+int svs_frontend_decide_keyframes(svs_frontend *fe, svs_map *map, const svs_keyframe_decide_params *prm, int want_lists, svs_keyframe_decision *h_dec,
+                                  svs_map_new_point *h_new, svs_map_track_point *h_track, int32_t *h_new_rec, int32_t *h_track_rec, int cap);
 
 /* ---- multi-GPU: the library-owned collective of the landmark-sharded back-end.  The reference has no
    distributed code; one process per GPU each creates a context and a communicator (RCCL, bound at run time) --------------*/

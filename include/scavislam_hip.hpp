@@ -483,7 +483,7 @@ class DenseTrackerGpu {
 };
 
 // StereoFrontend::processFrame(bool*) / processFirstFrame() (stereo_frontend.h:88-95): the data-parallel part of a frame in ONE blocking call with
-// host buffers in and out; the caller keeps the reference's bookkeeping (keyframe switch / drop, list building) and uses the returned records.
+// host buffers in and out; the keyframe switch / drop decision and the AddToOptimzer lists behind it come from decideKeyframes, the caller applies them.
 class BackendMap;
 struct FrontendVertex { int frame_id; double T_me_from_w[12]; };      // an entry of neighborhood_->vertex_map: the id and the pose (the edge strengths stay with the caller)
 class StereoFrontend {
@@ -584,6 +584,46 @@ class StereoFrontend {
   bool addMorePointsToOtherFrame(int new_keyframe_id, const double T_newkey_from_cur[12], int first_point_id, uint64_t seed,
                                  std::vector<svs_candidate_point> *newpoints, int32_t num_points[3], const svs_seed_params *prm = nullptr) {
     return seed_(SVS_SEED_MORE, new_keyframe_id, T_newkey_from_cur, first_point_id, seed, newpoints, num_points, prm);
+  }
+  // neighborhood_->vertex_map as the keyframe decision reads it (svs_frontend_set_vertex_table): per vertex its pose and its feat_map as an ascending id list
+  // (feature_ids[v]) or, where from_map[v] is set, the observer rows of the resident map; active = the index of actkey_id's vertex, neighbor_indices = the
+  // vertices of its strength_to_neighbors, slot_keyframe_ids as in setCandidatesFromMap.  Resident until set again
+  bool setVertexTable(const std::vector<FrontendVertex> &vertex_map, const std::vector<std::vector<int32_t> > &feature_ids, const std::vector<char> &from_map,
+                      int active, const std::vector<int32_t> &neighbor_indices, const std::vector<int32_t> &slot_keyframe_ids) {
+    const size_t V = vertex_map.size();
+    if (feature_ids.size() != V || (int)slot_keyframe_ids.size() != max_keyframes_) return false;
+    std::vector<int32_t> ids(V), begin(V), count(V), all;
+    std::vector<double> T(12 * V);
+    for (size_t v = 0; v < V; ++v) {
+      ids[v] = vertex_map[v].frame_id;
+      for (int i = 0; i < 12; ++i) T[12 * v + i] = vertex_map[v].T_me_from_w[i];
+      const bool m = v < from_map.size() && from_map[v];
+      begin[v] = m ? SVS_KF_SET_MAP : (int32_t)all.size(); count[v] = m ? 0 : (int32_t)feature_ids[v].size();
+      if (!m) all.insert(all.end(), feature_ids[v].begin(), feature_ids[v].end());
+    }
+    svs_vertex_request q;
+    std::memset(&q, 0, sizeof q);
+    q.stream = 0; q.n_vertex = (int32_t)V; q.act = active; q.n_neighbors = (int32_t)neighbor_indices.size();
+    q.h_vertex_kf = ids.data(); q.h_vertex_T = T.data(); q.h_set_begin = begin.data(); q.h_set_count = count.data(); q.h_set_ids = all.data();
+    q.h_neighbors = neighbor_indices.data(); q.h_slot_kf = slot_keyframe_ids.data(); q.n_set_ids = (int32_t)all.size();
+    return ctx_.check(svs_frontend_set_vertex_table(fe_, 1, &q));
+  }
+  // stereo_frontend.cpp:265-296 as ONE call behind processFrame: processMatchedPoints' AddToOptimzer lists, shallWeSwitchKeyframe, shallWeDropNewKeyframe and
+  // addNewKeyframe's add_flags / T_newkey_from_w / strength_to_neighbors (svs_frontend_decide_keyframes).  The lists (and the record index of every entry, for
+  // pruning newpoint_map) come back for a dropped frame, or for every tracked frame with always_lists.  map: the resident map behind from_map sets, or NULL
+  static svs_keyframe_decide_params decideParams() { svs_keyframe_decide_params p; svs_keyframe_decide_params_default(&p); return p; }
+  bool decideKeyframes(svs_map *map, svs_keyframe_decision *dec, std::vector<svs_map_new_point> *new_points, std::vector<svs_map_track_point> *track_points,
+                       std::vector<int32_t> *new_records, std::vector<int32_t> *track_records, bool always_lists = false,
+                       const svs_keyframe_decide_params *prm = nullptr) {
+    const svs_keyframe_decide_params p = prm ? *prm : decideParams();
+    const size_t cap = (size_t)(n_ > 0 ? n_ : 1);
+    new_points->resize(cap); track_points->resize(cap); new_records->resize(cap); track_records->resize(cap);
+    const bool ok = ctx_.check(svs_frontend_decide_keyframes(fe_, map, &p, always_lists ? 2 : 1, dec, new_points->data(), track_points->data(), new_records->data(),
+                                                             track_records->data(), (int)cap));
+    const bool have = ok && dec->valid && (always_lists || dec->decision == SVS_KF_DROP);
+    new_points->resize(have ? (size_t)dec->n_new : 0); new_records->resize(new_points->size());
+    track_points->resize(have ? (size_t)dec->n_track : 0); track_records->resize(track_points->size());
+    return ok;
   }
   svs_frontend *handle() const { return fe_; }
 

@@ -8,7 +8,7 @@ import ctypes as C
 import os
 import weakref
 
-from .ctypes_types import BaParams, BaStats, Cam, FastGrid, LoopCheck, LoopLocation, LoopLocationResult, LoopResult, MapAddKeyframeArgs, MapConstraintRequest, MapStrengthResult, MapWindowResult, NbhRequest, NbhResult, PoseOptParams, PoseOptStats, RegCommitResult, RegMapRequest, RegParams, RegRequest, RegResult, SeedArgs, SeedParams, SeedRequest, StereoParams, SurfParams, VocabParams, VocabResult
+from .ctypes_types import BaParams, BaStats, Cam, FastGrid, KeyframeDecideArgs, KeyframeDecideParams, LoopCheck, LoopLocation, LoopLocationResult, LoopResult, MapAddKeyframeArgs, MapConstraintRequest, MapStrengthResult, MapWindowResult, NbhRequest, NbhResult, PoseOptParams, PoseOptStats, RegCommitResult, RegMapRequest, RegParams, RegRequest, RegResult, SeedArgs, SeedParams, SeedRequest, StereoParams, SurfParams, VertexRequest, VocabParams, VocabResult
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SVS_LIB_PATH") or os.path.join(_HERE, "libscavislam_hip.so")   # override = kernel A/B experiments only
@@ -256,6 +256,11 @@ _SIGS = {
                                  C.POINTER(RegCommitResult), C.c_void_p, C.c_void_p, C.c_void_p],
     "svs_frontend_set_candidates_from_map": [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(NbhRequest), C.c_int, C.c_int, C.POINTER(NbhResult), C.c_void_p, C.c_void_p,
                                              C.c_void_p, C.c_void_p],
+    "svs_keyframe_decide": [C.c_void_p, C.POINTER(KeyframeDecideArgs), C.POINTER(KeyframeDecideParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                            C.c_int],
+    "svs_frontend_set_vertex_table": [C.c_void_p, C.c_int, C.POINTER(VertexRequest)],
+    "svs_frontend_decide_keyframes": [C.c_void_p, C.c_void_p, C.POINTER(KeyframeDecideParams), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                      C.c_int],
     "svs_ba_create": [C.c_void_p, C.POINTER(C.c_void_p)],
     "svs_ba_destroy": [C.c_void_p],
     "svs_ba_set_problem": [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
@@ -288,7 +293,7 @@ _SIGS = {
                             C.POINTER(C.c_int32)],
     "svs_ba_graph_stats": [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)],
 }
-EXPORTS = sorted(list(_SIGS) + ["svs_ctx_stream", "svs_last_error", "svs_api_version", "svs_pose_opt_params_default", "svs_seed_params_default", "svs_reg_params_default", "svs_vocab_params_default", "svs_surf_params_default"])
+EXPORTS = sorted(list(_SIGS) + ["svs_ctx_stream", "svs_last_error", "svs_api_version", "svs_pose_opt_params_default", "svs_keyframe_decide_params_default", "svs_seed_params_default", "svs_reg_params_default", "svs_vocab_params_default", "svs_surf_params_default"])
 API_VERSION = 9      # SVS_API_VERSION of include/scavislam_hip.h this binding was written against
 
 
@@ -317,6 +322,8 @@ def load():
         lib.svs_pose_opt_params_default.restype = None
         lib.svs_seed_params_default.argtypes = [C.c_void_p]
         lib.svs_seed_params_default.restype = None
+        lib.svs_keyframe_decide_params_default.argtypes = [C.c_void_p]
+        lib.svs_keyframe_decide_params_default.restype = None
         lib.svs_reg_params_default.argtypes = [C.c_void_p]
         lib.svs_reg_params_default.restype = None
         lib.svs_vocab_params_default.argtypes = [C.c_void_p]

@@ -13,11 +13,12 @@
 //   -> processMatchedPoints (reprojection gate + PointStatistics)                                :245-262, :834-974
 //   -> computeDensePointCloudCpu / Gpu at the refined pose                                       :298-302
 //   -> one download of {pose, pass count, match records, gate records, statistics}.
-// What stays with the caller is the reference's bookkeeping: keyframe switching / dropping (:265-296), list building, new
-// point seeding.  The object owns the device copies of the previous frame (pyramid + reference cloud), the keyframes it was
+// Behind a step, svs_frontend_decide_keyframes (keyframe.hip) takes the keyframe switch / drop decision (:265-296) and builds the
+// AddToOptimzer lists from the same device state; applying the decision stays with the caller.  The object owns the device copies of the previous frame (pyramid + reference cloud), the keyframes it was
 // told to keep (Frame::clone, keyframes.h:72-83), the candidate points (ap_map) and the FAST threshold state -- per stream.
 #include "common.h"
 #include "fast_view.h"
+#include "keyframe.h"
 #include "nbh_map.h"
 #include "pose.h"
 #include "seed.h"
@@ -164,6 +165,13 @@ struct svs_frontend {
   PinnedBuf<uint8_t> h_seed; DevBuf<uint8_t> d_seed;
   // svs_frontend_set_candidates_from_map: the staged requests and, behind them, what comes back; grown on demand
   PinnedBuf<uint8_t> h_nbh; DevBuf<uint8_t> d_nbh;
+  // the keyframe decision (svs_frontend_set_vertex_table / svs_frontend_decide_keyframes, keyframe.hip): the streams' resident vertex tables, the staging block
+  // of the setter, the decision records and list rows; all allocated with the first table
+  std::vector<uint8_t> vt_set;          // [B]: the stream has a table
+  DevBuf<svs_kf_table> d_vt_tab; DevBuf<svs_kf_vertex> d_vt_vtx; DevBuf<int32_t> d_vt_slot, d_vt_ids;
+  PinnedBuf<uint8_t> h_vt; DevBuf<uint8_t> d_vt_up;
+  DevBuf<svs_keyframe_decision> d_kd_dec; DevBuf<svs_map_new_point> d_kd_new; DevBuf<svs_map_track_point> d_kd_track; DevBuf<int32_t> d_kd_new_rec, d_kd_track_rec;
+  PinnedBuf<svs_keyframe_decision> h_kd_dec;
   // drains the streams and takes the detector / block matcher along before the members above go (also when create gives up half way)
   ~svs_frontend() {
     (void)hipStreamSynchronize(ctx->stream);
@@ -1193,5 +1201,150 @@ extern "C" int svs_frontend_seed_keyframes(svs_frontend *fe, int n, const svs_se
     SVS_HIP(ctx, hipMemcpy2DAsync(h_out, pitch, fe->d_seed + off_rec, pitch, sizeof(svs_candidate_point) * (size_t)longest, (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
     SVS_HIP(ctx, hipStreamSynchronize(ctx->stream));
   }
+  return SVS_OK;
+}
+
+/* neighborhood_->vertex_map of a stream as the keyframe decision reads it (keyframe.hip; the contract is in the header): everything is checked on the host first,
+   then one staged upload (requests, tables, vertices, slot tables, id arrays) and one scatter launch into the stream-indexed resident tables. */
+extern "C" int svs_frontend_set_vertex_table(svs_frontend *fe, int n_requests, const svs_vertex_request *req) {
+  svs_ctx *ctx = fe ? fe->ctx : nullptr;
+  SVS_REQUIRE(ctx, fe && n_requests >= 0 && (n_requests == 0 || req) && !fe->submitted);
+  const int B = fe->B, S = fe->max_keyframes, R = n_requests;
+  if (S > SVS_KF_MAX_SLOTS) { ctx->err = "svs_frontend_set_vertex_table: more than SVS_KF_MAX_SLOTS keyframe slots"; return SVS_ERR_UNSUPPORTED; }
+  const size_t set_cap = (size_t)16 * fe->max_points;
+  std::vector<uint8_t> seen((size_t)B, 0);
+  size_t total_ids = 0;
+  for (int r = 0; r < R; ++r) {
+    const svs_vertex_request &q = req[r];
+    SVS_REQUIRE(ctx, q.stream >= 0 && q.stream < B && !seen[q.stream]);
+    seen[q.stream] = 1;
+    SVS_REQUIRE(ctx, q.n_vertex >= 1 && q.h_vertex_kf && q.h_vertex_T && q.h_set_begin && q.h_set_count && q.h_slot_kf && q.n_set_ids >= 0 && (q.n_set_ids == 0 || q.h_set_ids));
+    if (q.n_vertex > SVS_KF_MAX_VERTICES) { ctx->err = "svs_frontend_set_vertex_table: more than SVS_KF_MAX_VERTICES vertices"; return SVS_ERR_CAPACITY; }
+    if ((size_t)q.n_set_ids > set_cap) { ctx->err = "svs_frontend_set_vertex_table: more than 16 * max_points staged ids"; return SVS_ERR_CAPACITY; }
+    SVS_REQUIRE(ctx, q.act >= 0 && q.act < q.n_vertex && q.n_neighbors >= 0 && q.n_neighbors < q.n_vertex && (q.n_neighbors == 0 || q.h_neighbors));
+    for (int v = 0; v < q.n_vertex; ++v) {
+      for (int u = 0; u < v; ++u) SVS_REQUIRE(ctx, q.h_vertex_kf[u] != q.h_vertex_kf[v]);
+      if (q.h_set_begin[v] == SVS_KF_SET_MAP) continue;
+      const int beg = q.h_set_begin[v], cnt = q.h_set_count[v];
+      SVS_REQUIRE(ctx, beg >= 0 && cnt >= 0 && (size_t)beg + (size_t)cnt <= (size_t)q.n_set_ids);
+      for (int i = 1; i < cnt; ++i) SVS_REQUIRE(ctx, q.h_set_ids[beg + i - 1] < q.h_set_ids[beg + i]);
+    }
+    for (int k = 0; k < q.n_neighbors; ++k) {
+      SVS_REQUIRE(ctx, q.h_neighbors[k] >= 0 && q.h_neighbors[k] < q.n_vertex && q.h_neighbors[k] != q.act);
+      for (int j = 0; j < k; ++j) SVS_REQUIRE(ctx, q.h_neighbors[j] != q.h_neighbors[k]);
+    }
+    for (int s = 0; s < S; ++s) SVS_REQUIRE(ctx, q.h_slot_kf[s] < 0 || fe->kept[(size_t)q.stream * S + s]);
+    total_ids += (size_t)q.n_set_ids;
+  }
+  if (R == 0) return SVS_OK;
+  SVS_DEVICE(ctx);
+  if (!fe->d_vt_tab) {      // the resident tables, the decision records and the list rows come with the first table
+    const size_t Bz = (size_t)B, mp = (size_t)fe->max_points;
+    SVS_HIP(ctx, fe->d_vt_tab.alloc(Bz));
+    SVS_HIP(ctx, fe->d_vt_vtx.alloc(Bz * SVS_KF_MAX_VERTICES));
+    SVS_HIP(ctx, fe->d_vt_slot.alloc(Bz * S));
+    SVS_HIP(ctx, fe->d_vt_ids.alloc(Bz * set_cap));
+    SVS_HIP(ctx, fe->d_kd_dec.alloc(Bz));
+    SVS_HIP(ctx, fe->d_kd_new.alloc(Bz * mp));
+    SVS_HIP(ctx, fe->d_kd_track.alloc(Bz * mp));
+    SVS_HIP(ctx, fe->d_kd_new_rec.alloc(Bz * mp));
+    SVS_HIP(ctx, fe->d_kd_track_rec.alloc(Bz * mp));
+    SVS_HIP(ctx, fe->h_kd_dec.alloc(Bz));
+    fe->vt_set.assign(Bz, 0);
+  }
+  auto up16 = [](size_t v) { return (v + 15) & ~(size_t)15; };
+  const size_t off_tab = up16(sizeof(kfd_up) * (size_t)R), off_vtx = up16(off_tab + sizeof(svs_kf_table) * (size_t)R);
+  const size_t off_slot = up16(off_vtx + sizeof(svs_kf_vertex) * SVS_KF_MAX_VERTICES * (size_t)R), off_ids = up16(off_slot + sizeof(int32_t) * (size_t)S * R);
+  const size_t bytes = off_ids + sizeof(int32_t) * total_ids;
+  if (fe->h_vt.bytes() < bytes) {      // (the last call's upload has been waited for: it ends with a synchronisation)
+    SVS_HIP(ctx, fe->h_vt.alloc_bytes(bytes * 2));
+    SVS_HIP(ctx, fe->d_vt_up.alloc_bytes(bytes * 2));
+  }
+  __builtin_memset(fe->h_vt, 0, off_ids);
+  kfd_up *hu = reinterpret_cast<kfd_up *>(fe->h_vt.get());
+  svs_kf_table *ht = reinterpret_cast<svs_kf_table *>(fe->h_vt + off_tab);
+  svs_kf_vertex *hv = reinterpret_cast<svs_kf_vertex *>(fe->h_vt + off_vtx);
+  int32_t *hs = reinterpret_cast<int32_t *>(fe->h_vt + off_slot), *hi = reinterpret_cast<int32_t *>(fe->h_vt + off_ids);
+  size_t ids_off = 0;
+  for (int r = 0; r < R; ++r) {
+    const svs_vertex_request &q = req[r];
+    hu[r].stream = q.stream; hu[r].n_ids = q.n_set_ids; hu[r].ids_off = (int32_t)ids_off;
+    ht[r].n_vertex = q.n_vertex; ht[r].act = q.act; ht[r].n_neighbors = q.n_neighbors;
+    for (int k = 0; k < q.n_neighbors; ++k) ht[r].neighbors[k] = q.h_neighbors[k];
+    for (int v = 0; v < q.n_vertex; ++v) {
+      svs_kf_vertex &x = hv[(size_t)r * SVS_KF_MAX_VERTICES + v];
+      for (int i = 0; i < 12; ++i) x.T_me_from_w[i] = q.h_vertex_T[12 * v + i];
+      const bool from_map = q.h_set_begin[v] == SVS_KF_SET_MAP;
+      x.kf_id = q.h_vertex_kf[v]; x.set_begin = q.h_set_begin[v]; x.set_count = from_map ? 0 : q.h_set_count[v];
+    }
+    __builtin_memcpy(hs + (size_t)r * S, q.h_slot_kf, sizeof(int32_t) * (size_t)S);
+    if (q.n_set_ids) __builtin_memcpy(hi + ids_off, q.h_set_ids, sizeof(int32_t) * (size_t)q.n_set_ids);
+    ids_off += (size_t)q.n_set_ids;
+  }
+  SVS_REQUIRE(ctx, ids_off < ((size_t)1 << 31));
+  SVS_HIP(ctx, hipMemcpyAsync(fe->d_vt_up, fe->h_vt, bytes, hipMemcpyHostToDevice, ctx->stream));
+  KfdScatter sc{};
+  sc.up = reinterpret_cast<const kfd_up *>(fe->d_vt_up.get());
+  sc.tab = reinterpret_cast<const svs_kf_table *>(fe->d_vt_up + off_tab);
+  sc.vtx = reinterpret_cast<const svs_kf_vertex *>(fe->d_vt_up + off_vtx);
+  sc.slot = reinterpret_cast<const int32_t *>(fe->d_vt_up + off_slot);
+  sc.ids = reinterpret_cast<const int32_t *>(fe->d_vt_up + off_ids);
+  sc.d_tab = fe->d_vt_tab; sc.d_vtx = fe->d_vt_vtx; sc.d_slot = fe->d_vt_slot; sc.d_ids = fe->d_vt_ids; sc.S = S; sc.set_cap = (int)set_cap;
+  if (int rc = svs_keyframe_scatter_tables(ctx, R, sc)) return rc;
+  SVS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  for (int r = 0; r < R; ++r) fe->vt_set[req[r].stream] = 1;
+  return SVS_OK;
+}
+
+/* stereo_frontend.cpp:265-296 for every stream, from the device state of the last step and the resident vertex tables: one launch (keyframe.hip), one download of
+   the decision records, then the list rows of the streams that need them -- one strided copy per array and run of consecutive such streams. */
+extern "C" int svs_frontend_decide_keyframes(svs_frontend *fe, svs_map *map, const svs_keyframe_decide_params *prm, int want_lists, svs_keyframe_decision *h_dec,
+                                             svs_map_new_point *h_new, svs_map_track_point *h_track, int32_t *h_new_rec, int32_t *h_track_rec, int cap) {
+  svs_ctx *ctx = fe ? fe->ctx : nullptr;
+  SVS_REQUIRE(ctx, fe && prm && h_dec && fe->have_prev && !fe->submitted && want_lists >= 0 && want_lists <= 2);
+  SVS_REQUIRE(ctx, fe->n_gated >= 0);      // gate records and point statistics of a step on the list that is still on the device (the SVS_SEED_MORE rule)
+  const int B = fe->B;
+  SVS_REQUIRE(ctx, (int)fe->vt_set.size() == B);
+  for (int b = 0; b < B; ++b) SVS_REQUIRE(ctx, fe->vt_set[b]);
+  SVS_REQUIRE(ctx, !want_lists || (h_new && h_track && h_new_rec && h_track_rec));
+  if (want_lists && cap < fe->n_gated) { ctx->err = "svs_frontend_decide_keyframes: cap below the step's record count"; return SVS_ERR_CAPACITY; }
+  SVS_DEVICE(ctx);
+  const size_t mp = (size_t)fe->max_points;
+  svs_keyframe_decide_args a{};
+  a.d_res = fe->d_res; a.res_bstride = mp; a.d_pts = fe->d_pts; a.pts_bstride = mp; a.d_gated = fe->d_gated; a.gated_bstride = mp;
+  a.d_stats = fe->d_ptstats; a.d_T_cur_from_actkey = fe->d_small; a.n = fe->n_gated; a.batch = B;
+  a.d_table = fe->d_vt_tab; a.d_vertex = fe->d_vt_vtx; a.vertex_bstride = SVS_KF_MAX_VERTICES;
+  a.d_set_ids = fe->d_vt_ids; a.set_bstride = (size_t)16 * mp; a.d_slot_kf = fe->d_vt_slot; a.slot_bstride = (size_t)fe->max_keyframes; a.max_keyframes = fe->max_keyframes;
+  a.map = map;
+  KfdFrontendSrc fs{fe->d_pstats, fe->d_passes, fe->prm.min_matches};
+  if (int rc = svs_keyframe_decide_launch(ctx, &a, prm, &fs, fe->d_kd_dec, fe->d_kd_new, fe->d_kd_track, fe->d_kd_new_rec, fe->d_kd_track_rec, fe->max_points)) return rc;
+  SVS_HIP(ctx, hipMemcpyAsync(fe->h_kd_dec, fe->d_kd_dec, sizeof(svs_keyframe_decision) * (size_t)B, hipMemcpyDeviceToHost, ctx->stream));
+  SVS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  __builtin_memcpy(h_dec, fe->h_kd_dec, sizeof(svs_keyframe_decision) * (size_t)B);
+  if (!want_lists) return SVS_OK;
+  auto wanted = [&](int b) { return h_dec[b].valid && (want_lists == 2 || h_dec[b].decision == SVS_KF_DROP); };
+  bool any = false;
+  for (int b0 = 0; b0 < B;) {
+    if (!wanted(b0)) { ++b0; continue; }
+    int b1 = b0, wn = 0, wt = 0;      // the run [b0, b1) and its longest lists
+    for (; b1 < B && wanted(b1); ++b1) { wn = std::max(wn, (int)h_dec[b1].n_new); wt = std::max(wt, (int)h_dec[b1].n_track); }
+    SVS_REQUIRE(ctx, wn <= cap && wt <= cap);
+    const size_t rows = (size_t)(b1 - b0), o = (size_t)b0;
+    if (wn) {
+      SVS_HIP(ctx, hipMemcpy2DAsync(h_new + o * cap, sizeof(svs_map_new_point) * (size_t)cap, fe->d_kd_new + o * mp, sizeof(svs_map_new_point) * mp,
+                                    sizeof(svs_map_new_point) * (size_t)wn, rows, hipMemcpyDeviceToHost, ctx->stream));
+      SVS_HIP(ctx, hipMemcpy2DAsync(h_new_rec + o * cap, sizeof(int32_t) * (size_t)cap, fe->d_kd_new_rec + o * mp, sizeof(int32_t) * mp, sizeof(int32_t) * (size_t)wn, rows,
+                                    hipMemcpyDeviceToHost, ctx->stream));
+    }
+    if (wt) {
+      SVS_HIP(ctx, hipMemcpy2DAsync(h_track + o * cap, sizeof(svs_map_track_point) * (size_t)cap, fe->d_kd_track + o * mp, sizeof(svs_map_track_point) * mp,
+                                    sizeof(svs_map_track_point) * (size_t)wt, rows, hipMemcpyDeviceToHost, ctx->stream));
+      SVS_HIP(ctx, hipMemcpy2DAsync(h_track_rec + o * cap, sizeof(int32_t) * (size_t)cap, fe->d_kd_track_rec + o * mp, sizeof(int32_t) * mp, sizeof(int32_t) * (size_t)wt, rows,
+                                    hipMemcpyDeviceToHost, ctx->stream));
+    }
+    any = any || wn || wt;
+    b0 = b1;
+  }
+  if (any) SVS_HIP(ctx, hipStreamSynchronize(ctx->stream));
   return SVS_OK;
 }

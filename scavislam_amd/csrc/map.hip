@@ -26,6 +26,7 @@
 #include "nbh_map.h"
 #include "ba_map.h"
 #include "walk_map.h"
+#include "kf_map.h"
 #include "pose.h"
 #include <string.h>
 #include <algorithm>
@@ -1285,6 +1286,13 @@ int svs_map_build_requests(svs_map *m, int n_requests, const MapBuildDst &dst) {
   if (int rc = map_prepare_walk(m, n_requests)) return rc;
   hipLaunchKernelGGL(map_build_kernel, dim3(n_requests), dim3(MB_THREADS), 0, ctx->stream, m->view(), dst);
   SVS_LAUNCH_CHECK(ctx);
+  return SVS_OK;
+}
+
+// kf_map.h: the observer rows for the keyframe decision's membership tests (keyframe.hip), current with the log
+int svs_map_observer_view(svs_map *m, MapObsView *out) {
+  if (int rc = map_prepare_walk(m, 0)) return rc;
+  out->pt_begin = m->d_pt_begin; out->pt_rows = m->d_pt_rows; out->pt_hi = m->pt_hi;
   return SVS_OK;
 }
 

@@ -341,3 +341,45 @@ class MapAddKeyframeArgs(C.Structure):
 
 
 assert C.sizeof(KeyframeC) == 136 and C.sizeof(MapAddKeyframeArgs) == 32 + 96 + 136 + 48 + 8
+
+
+# ---- front end: the keyframe switch / drop decision behind a step (svs_keyframe_decide, svs_frontend_set_vertex_table, svs_frontend_decide_keyframes)
+KF_MAX_VERTICES, KF_MAX_STRENGTH, KF_MAX_SLOTS, KF_SET_MAP = 64, 64, 1024, -1
+KF_KEEP, KF_SWITCH, KF_DROP = 0, 1, 2
+KF_VERTEX_DTYPE = np.dtype([("T_me_from_w", "<f8", 12), ("kf_id", "<i4"), ("set_begin", "<i4"), ("set_count", "<i4"), ("pad_", "<i4")])
+KF_TABLE_DTYPE = np.dtype([("n_vertex", "<i4"), ("act", "<i4"), ("n_neighbors", "<i4"), ("pad_", "<i4"), ("neighbors", "<i4", KF_MAX_VERTICES)])
+KEYFRAME_DECISION_DTYPE = np.dtype([("valid", "<i4"), ("decision", "<i4"), ("n_new", "<i4"), ("n_track", "<i4"), ("closest_index", "<i4"), ("closest_id", "<i4"),
+                                    ("shared", "<i4"), ("featureless", "<i4"), ("closest_dist", "<f8"), ("av_track_length", "<f8"), ("T_cur_after", "<f8", 12),
+                                    ("T_newkey_from_w", "<f8", 12), ("add_flags", "<i4", 9), ("n_strength", "<i4"), ("over_capacity", "<i4"), ("pad_", "<i4"),
+                                    ("strength_kf", "<i4", KF_MAX_STRENGTH), ("strength_count", "<i4", KF_MAX_STRENGTH)])
+assert KF_VERTEX_DTYPE.itemsize == 112 and KF_TABLE_DTYPE.itemsize == 272 and KEYFRAME_DECISION_DTYPE.itemsize == 800
+
+
+class KeyframeDecideParams(C.Structure):
+    """svs_keyframe_decide_params: ui.parallax_thr (a float), the count of shallWeSwitchKeyframe (:503), the cell minimum and corner count of
+    shallWeDropNewKeyframe (:519, :525), its track-length bound (:527), params_.covis_thr, ui.min_num_points"""
+    _fields_ = [("parallax_thr", C.c_float), ("switch_min_shared", C.c_int32), ("featureless_cell_min", C.c_int32), ("featureless_corners_thr", C.c_int32),
+                ("max_av_track_length", C.c_double), ("covis_thr", C.c_int32), ("min_num_points", C.c_int32)]
+
+    @classmethod
+    def reference(cls):
+        return cls(0.75, 100, 15, 2, 75.0, 15, 25)
+
+
+class KeyframeDecideArgs(C.Structure):
+    """svs_keyframe_decide_args: device pointers of a batch of streams"""
+    _fields_ = [("d_res", C.c_void_p), ("res_bstride", C.c_size_t), ("d_pts", C.c_void_p), ("pts_bstride", C.c_size_t), ("d_gated", C.c_void_p),
+                ("gated_bstride", C.c_size_t), ("d_stats", C.c_void_p), ("d_T_cur_from_actkey", C.c_void_p), ("d_tracking_ok", C.c_void_p), ("d_n", C.c_void_p),
+                ("n", C.c_int32), ("batch", C.c_int32), ("d_table", C.c_void_p), ("d_vertex", C.c_void_p), ("vertex_bstride", C.c_size_t),
+                ("d_set_ids", C.c_void_p), ("set_bstride", C.c_size_t), ("d_slot_kf", C.c_void_p), ("slot_bstride", C.c_size_t), ("max_keyframes", C.c_int32),
+                ("pad_", C.c_int32), ("map", C.c_void_p)]
+
+
+class VertexRequest(C.Structure):
+    """svs_vertex_request: one stream's vertex table for svs_frontend_set_vertex_table (host pointers)"""
+    _fields_ = [("stream", C.c_int32), ("n_vertex", C.c_int32), ("act", C.c_int32), ("n_neighbors", C.c_int32), ("h_vertex_kf", C.c_void_p),
+                ("h_vertex_T", C.c_void_p), ("h_set_begin", C.c_void_p), ("h_set_count", C.c_void_p), ("h_set_ids", C.c_void_p), ("h_neighbors", C.c_void_p),
+                ("h_slot_kf", C.c_void_p), ("n_set_ids", C.c_int32), ("pad_", C.c_int32)]
+
+
+assert C.sizeof(KeyframeDecideParams) == 32 and C.sizeof(KeyframeDecideArgs) == 160 and C.sizeof(VertexRequest) == 80

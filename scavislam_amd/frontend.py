@@ -836,6 +836,64 @@ class StereoFrontend:
         self.ctx.check(self.ctx.lib.svs_frontend_seed_keyframes(self.h, n, req, C.byref(prm), out.ctypes.data, cap, cnt.ctypes.data))
         return [(out[r, :int(cnt[r].sum())].copy(), cnt[r].copy()) for r in range(n)]
 
+    def setVertexTable(self, requests):
+        """neighborhood_->vertex_map of a stream as the keyframe decision reads it (svs_frontend_set_vertex_table); resident until set again.  requests: dicts
+        with stream, vertex_kf (ids), vertex_T ([V][12] T_me_from_w), sets (per vertex an iterable of point ids -- its feat_map -- or the string "map": the
+        observer rows of the resident map handed to decideKeyframes), act (index of the active keyframe's vertex), neighbors (vertex indices of its
+        strength_to_neighbors), slot_kf (the keyframe id kept in each slot, -1 for none)"""
+        from .ctypes_types import KF_SET_MAP, VertexRequest
+        n = len(requests)
+        arr = (VertexRequest * max(n, 1))()
+        keep = []
+        for r, q in zip(arr, requests):
+            kf = np.ascontiguousarray(q["vertex_kf"], np.int32).reshape(-1)
+            T = np.ascontiguousarray(q["vertex_T"], np.float64).reshape(len(kf), 12)
+            begin, count, ids = np.zeros(len(kf), np.int32), np.zeros(len(kf), np.int32), []
+            for v, s in enumerate(q["sets"]):
+                if isinstance(s, str):
+                    begin[v] = KF_SET_MAP
+                else:
+                    s = sorted(set(int(i) for i in s))
+                    begin[v], count[v] = len(ids), len(s)
+                    ids += s
+            ids = np.array(ids, np.int32)
+            nbr = np.ascontiguousarray(q.get("neighbors", []), np.int32).reshape(-1)
+            slot = np.ascontiguousarray(q["slot_kf"], np.int32).reshape(-1)
+            if len(slot) != self.max_keyframes or len(q["sets"]) != len(kf):
+                raise ValueError("slot_kf needs one entry per keyframe slot of the front end, sets one entry per vertex")
+            keep += [kf, T, begin, count, ids, nbr, slot]
+            r.stream, r.n_vertex, r.act, r.n_neighbors, r.n_set_ids = int(q.get("stream", 0)), len(kf), int(q["act"]), len(nbr), len(ids)
+            r.h_vertex_kf, r.h_vertex_T, r.h_set_begin, r.h_set_count = kf.ctypes.data, T.ctypes.data, begin.ctypes.data, count.ctypes.data
+            r.h_set_ids, r.h_neighbors, r.h_slot_kf = (ids.ctypes.data if len(ids) else None), (nbr.ctypes.data if len(nbr) else None), slot.ctypes.data
+        self.ctx.check(self.ctx.lib.svs_frontend_set_vertex_table(self.h, n, arr))
+
+    def decideKeyframes(self, resident_map=None, params=None, want_lists=1):
+        """stereo_frontend.cpp:265-296 for every stream, decided on the device behind processFrame(s) (svs_frontend_decide_keyframes): the AddToOptimzer lists of
+        processMatchedPoints, shallWeSwitchKeyframe, shallWeDropNewKeyframe and addNewKeyframe's add_flags / T_newkey_from_w / strength_to_neighbors.  Returns one
+        dict per stream: dec (a KEYFRAME_DECISION_DTYPE record) and, for the streams whose lists were fetched (want_lists = 1: the dropped ones, 2: every tracked
+        one, 0: none), new (MAP_NEW_POINT_DTYPE), track (MAP_TRACK_POINT_DTYPE), new_rec / track_rec (the record index of every entry); None otherwise"""
+        from .ctypes_types import KEYFRAME_DECISION_DTYPE, KF_DROP, MAP_NEW_POINT_DTYPE, MAP_TRACK_POINT_DTYPE, KeyframeDecideParams
+        prm = params or KeyframeDecideParams.reference()
+        B, cap = self.n_streams, max(max(self.n_points), 1)
+        dec = np.zeros(B, KEYFRAME_DECISION_DTYPE)
+        if want_lists:
+            new, track = np.zeros((B, cap), MAP_NEW_POINT_DTYPE), np.zeros((B, cap), MAP_TRACK_POINT_DTYPE)
+            new_rec, track_rec = np.zeros((B, cap), np.int32), np.zeros((B, cap), np.int32)
+            ptrs = [a.ctypes.data for a in (new, track, new_rec, track_rec)]
+        else:
+            ptrs = [None] * 4
+        self.ctx.check(self.ctx.lib.svs_frontend_decide_keyframes(self.h, resident_map.h if resident_map is not None else None, C.byref(prm), int(want_lists),
+                                                                  dec.ctypes.data, *ptrs, cap))
+        out = []
+        for b in range(B):
+            d = dec[b]
+            o = dict(dec=d, new=None, track=None, new_rec=None, track_rec=None)
+            if want_lists and d["valid"] and (want_lists == 2 or d["decision"] == KF_DROP):
+                nn, nt = int(d["n_new"]), int(d["n_track"])
+                o.update(new=new[b, :nn].copy(), track=track[b, :nt].copy(), new_rec=new_rec[b, :nn].copy(), track_rec=track_rec[b, :nt].copy())
+            out.append(o)
+        return out
+
     def cloud_host(self, level, stream=0):
         """reference cloud (quarter grid; full resolution in the CUDA build) the last frame left for the next one"""
         clouds = (C.c_void_p * 3)()
