@@ -118,7 +118,13 @@ __device__ __forceinline__ void taps_u8_wait(TapRows &t) {
   if constexpr (ASM) {
     // (the four are the youngest requests of the lane, so the count that covers them is zero.  The compiler does not count them: a wait of its own in between
     // would be for something older and only wait longer -- the caller puts nothing there that reads memory)
-    asm("s_waitcnt vmcnt(0)" : "+v"(t.w[0]), "+v"(t.w[1]), "+v"(t.w[2]), "+v"(t.w[3]));
+    // The wait is the BUILTIN, not a line of inline asm: the compiler's wait-count bookkeeping sees a builtin and knows that every request of its own -- the sweep's
+    // deferred term store and the prefetch of the next sample -- is complete behind it.  With the wait hidden in asm it carried the prefetched previous-frame byte
+    // of the peeled first trip as "still in flight" into the sample loop and waited vmcnt(1) for it in front of every trip's taps: behind the trip's own store and
+    // prefetch loads that made two of them complete before the taps were issued -- two memory round trips per sample, one after the other (profiles/tracker_prefetch.md;
+    // tools/tracker_loop_isa.py checks the ISA).  The empty asm statement keeps the four registers defined HERE, not at the loads.
+    __builtin_amdgcn_s_waitcnt(0x0f70);      // vmcnt(0) (bits 3:0 and 15:14), expcnt and lgkmcnt left open
+    asm volatile("" : "+v"(t.w[0]), "+v"(t.w[1]), "+v"(t.w[2]), "+v"(t.w[3]));
     __builtin_amdgcn_sched_barrier(0);
   }
 }

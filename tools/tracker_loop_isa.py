@@ -3,9 +3,14 @@
 
 Has csrc/Makefile write the gfx950 assembly of dense.hip (build/dense.s: the unit's own flags, device only), finds the loop over the
 samples in every function that inlines track_pass (the tracker kernels) and prints, per loop: instructions per trip by class,
-the function's VGPRs / scratch / occupancy, the order in which the trip issues its memory operations and waits for them, and a verdict:
+the function's VGPRs / scratch / occupancy, the order in which the trip issues its memory operations and waits for them, and two verdicts:
 
     do all tap loads of a sample (the four rows of its 4 x 4 neighbourhood in the u8 image) go out before the first wait that covers one of them?
+
+    does any vmcnt wait between the trip's first memory request (the deferred term store, the prefetch of the next sample's cloud point and
+    previous-frame byte) and its first tap load force requests of THIS trip to complete?  vmcnt(N) leaves at most the N youngest requests open, loads and
+    stores in one queue: behind k requests of the trip it makes k - N of them complete before the taps are even issued -- the prefetch is then no
+    prefetch, and a trip pays two memory round trips one after the other (profiles/tracker_prefetch.md).
 
 A tracker whose taps are waited for row by row pays one memory round trip per row and sample; the compiler chose that once, silently, at the
 128-register limit of the big-batch kernels (profiles/tracker_taps.md).  tests/test_tracker_isa_cpu.py holds the two hot instantiations to the verdict.
@@ -198,8 +203,18 @@ def analyse_loop(ins):
     res = dict(instructions=len(ins), classes=counts, memory_order=mem_order, tap_loads=len(taps), scratch_in_loop=sum(1 for s in ins if s.startswith("scratch_")),
                f64_fma=sum(1 for s in ins if re.match(r"^v_(fma|fmac)_f64", s)))
     if not taps:
-        res.update(verdict=None, first_wait=None, taps_before_wait=0, dest_untouched=None)
+        res.update(verdict=None, first_wait=None, taps_before_wait=0, dest_untouched=None, prefetch_waits=[], prefetch_forced=0, prefetch_verdict=None)
         return res
+    # waits between the trip's first memory request and its first tap load: how many of the trip's own requests each forces to complete
+    first_mem = next(k for k, s in enumerate(ins) if is_vm_op(s))
+    waits = []
+    for p in range(first_mem + 1, taps[0]):
+        n = vmcnt_of(ins[p])
+        if n is not None:
+            issued = sum(1 for q in range(first_mem, p) if is_vm_op(ins[q]))
+            waits.append(dict(wait="vmcnt(%d)" % n, issued=issued, forced=max(0, issued - n)))
+    forced = max([w["forced"] for w in waits] or [0])
+    res.update(prefetch_waits=waits, prefetch_forced=forced, prefetch_verdict=forced == 0)
     # the first wait behind the first tap load that covers one of the tap loads: vmcnt(N) leaves at most the N youngest requests open
     first_wait, covered_at = None, None
     for p in range(taps[0] + 1, len(ins)):
@@ -244,21 +259,24 @@ def analyse(asm_text):
                 a["header"] = head
                 loops.append(a)
         out.append(dict(name=name, mangled=mangled, vgpr=info.get("NumVgprs"), sgpr=info.get("NumSgprs"), scratch=info.get("ScratchSize"), occupancy=info.get("Occupancy"),
-                        hot=name in HOT, loops=loops, verdict=all(l["verdict"] is not False for l in loops)))
+                        hot=name in HOT, loops=loops, verdict=all(l["verdict"] is not False for l in loops),
+                        prefetch_verdict=all(l["prefetch_verdict"] is not False for l in loops)))
     out.sort(key=lambda r: (not r["hot"], r["name"]))
     return out
 
 
 def render(records, title):
     o = ["## " + title, ""]
-    o.append("| function | VGPR | scratch B | occupancy | sample loops | taps before the first wait that covers one | nothing touches their registers until then | scratch in the loop | verdict |")
-    o.append("|---|---|---|---|---|---|---|---|---|")
+    o.append("| function | VGPR | scratch B | occupancy | sample loops | taps before the first wait that covers one | nothing touches their registers until then | scratch in the loop | verdict | own requests a wait in front of the taps forces | verdict |")
+    o.append("|---|---|---|---|---|---|---|---|---|---|---|")
     for r in records:
         taps = ", ".join("%d of %d" % (l["taps_before_wait"], l["tap_loads"]) for l in r["loops"])
         unt = ", ".join({True: "yes", False: "NO", None: "-"}[l["dest_untouched"]] for l in r["loops"])
         scr = ", ".join(str(l["scratch_in_loop"]) for l in r["loops"])
-        o.append("| `%s`%s | %s | %s | %s | %d | %s | %s | %s | %s |" % (r["name"], " **(hot)**" if r["hot"] else "", r["vgpr"], r["scratch"], r["occupancy"] if r["occupancy"] is not None else "-",
-                                                                     len(r["loops"]), taps, unt, scr, "ok" if r["verdict"] else "**FAILS**"))
+        frc = ", ".join("-" if l["prefetch_verdict"] is None else "%d (%s)" % (l["prefetch_forced"], " ".join(w["wait"] for w in l["prefetch_waits"]) or "no wait") for l in r["loops"])
+        o.append("| `%s`%s | %s | %s | %s | %d | %s | %s | %s | %s | %s | %s |" % (r["name"], " **(hot)**" if r["hot"] else "", r["vgpr"], r["scratch"], r["occupancy"] if r["occupancy"] is not None else "-",
+                                                                     len(r["loops"]), taps, unt, scr, "ok" if r["verdict"] else "**FAILS**", frc,
+                                                                     "ok" if r["prefetch_verdict"] else "**FAILS**"))
     o.append("")
     for r in records:
         if not r["hot"]:
@@ -272,6 +290,10 @@ def render(records, title):
             o.append("")
             o.append("verdict: %s (%d of %d tap loads in front of the first covering wait, %s; %d instructions between the last of them and that wait)"
                      % ("ok" if l["verdict"] else "FAILS", l["taps_before_wait"], l["tap_loads"], l["first_wait"], l.get("between_issue_and_wait", 0)))
+            o.append("")
+            o.append("waits between the trip's first memory request and its first tap load: %s -- verdict: %s"
+                     % (", ".join("%s behind %d requests of the trip forces %d of them" % (w["wait"], w["issued"], w["forced"]) for w in l["prefetch_waits"]) or "none",
+                        "ok" if l["prefetch_verdict"] else "FAILS"))
             o.append("")
     return "\n".join(o)
 
@@ -301,7 +323,7 @@ def main():
     else:
         print(render(rec, "tracker sample loops: " + (a.rev or a.asm or a.src_root or "working tree")))
     hot = [r for r in rec if r["hot"]]
-    return 0 if len(hot) == len(HOT) and all(r["verdict"] for r in hot) else 1
+    return 0 if len(hot) == len(HOT) and all(r["verdict"] and r["prefetch_verdict"] for r in hot) else 1
 
 
 if __name__ == "__main__":
