@@ -1478,6 +1478,73 @@ int svs_frontend_set_vertex_table(svs_frontend *fe, int n_requests, const svs_ve
 int svs_frontend_decide_keyframes(svs_frontend *fe, svs_map *map, const svs_keyframe_decide_params *prm, int want_lists, svs_keyframe_decision *h_dec,
                                   svs_map_new_point *h_new, svs_map_track_point *h_track, int32_t *h_new_rec, int32_t *h_track_rec, int cap);
 
+/* ---- front end: a stream's whole neighbourhood from a root id.  Backend::computeNeighborhood(root_id) (backend.cpp:244-309, :347-386) and the order in which
+   processMatchedPoints visits newpoint_map (stereo_frontend.cpp:989-1029), joined on the device: findNeighborsOfRoot on the map's strength-ordered adjacency,
+   svs_frontend_set_candidates_from_map's point / anchor walk, svs_map_absolute_poses' search for the vertices outside the window, the edge-strength matrix, the
+   active keyframe's strength_to_neighbors, the head's groups put into that order, and svs_frontend_set_vertex_table's resident table -- nothing comes back to
+   the host in between, and THE MAP IS ONLY READ (computeAbsolutePose does not store its result either).  The reference's orders are those of hash containers;
+   every order below is canonical.  Per request:
+     1. neighbours of the root.  The root's edges in ASCENDING (strength, edge slot) -- its adjacency row walked backwards -- of which only those whose other
+        end has SVS_REG_KF_IN_WINDOW count; the reference compares its count before it increments it (:304-306), so up to max_num_neighbors + 1 ids are taken.
+        The vertex list is the root followed by these ids.  A root without SVS_REG_KF_IN_WINDOW (the reference asserts INNER): root_outside_window = 1, every
+        other field of the result zero, the stream untouched.
+     2. points, anchors, slots: rules 1-3 of svs_frontend_set_candidates_from_map for that vertex list, byte for byte.
+     3. poses of the vertex set.  A vertex with SVS_REG_KF_IN_WINDOW: the map's stored pose.  Any other: exactly the T svs_map_absolute_poses returns for it;
+        with SVS_WALK_NO_PATH the stored pose, counted in n_no_path.
+     4. the active keyframe.  act_index = the place of act_id in the vertex set, or -1.  strength_to_neighbors(act) = every other vertex with an edge to act in
+        the map's edge table (any type, marginalised or not), in ASCENDING (strength, keyframe id), as vertex indices; empty when act_index = -1.
+     5. edge-strength matrix [vertex_cap][vertex_cap] (:261-282): the strength of edge (i, j); -1 where there is none, on the diagonal and behind the set.
+     6. the stream's list: the n_fixed_groups leading head groups unchanged (newpoint_map[actkey_id]); then the keyed groups (group g >= n_fixed_groups is
+        newpoint_map[h_head_group_kf[g]]) whose key is in rule 4's list, in that list's order, an empty one included; keyed groups whose key is not in it are
+        left out and their records counted in n_head_dropped; then rule 2's records as the last group.  Group ends, group count (n_groups), new-record count
+        (n_head_kept) and the 0xff tail as rule 4 of svs_frontend_set_candidates_from_map.
+     7. slot poses (refresh_poses != 0): a slot whose keyframe is in the vertex set takes rule 3's pose, any other slot that names a keyframe of the map the
+        map's pose; they come back for the front end's host mirror.
+     8. the stream's resident vertex table, written on the device as svs_frontend_set_vertex_table writes it from rule 2's ids, rule 3's poses, every set
+        SVS_KF_SET_MAP, act = act_index, neighbors = rule 4's list and h_slot_kf.  With act_index = -1 the table has act = -1 and no neighbours:
+        svs_frontend_decide_keyframes then reports valid = 0 for the stream (its rule 0); the candidate list is still written.
+     9. all or nothing.  over_capacity = 1 leaves list, group ends, counts, slot poses and vertex table as they were; SVS_OK, other requests unaffected.  Found
+        in this order: (a) the vertex list of rule 1 above vertex_cap: n_vertex = its length, n_points = the fixed groups' records, the rest zero; (b) the fixed
+        groups' records plus the map points above max_points: n_points = their sum, n_map_points, the rest zero (the points are not read); (c) the vertex set
+        above vertex_cap: as (b) plus n_vertex, n_no_slot; (d) the kept head plus the map points above max_points: every count as found, n_points = their sum.
+    10. a request's bytes are a function of that request and of the map's content (an edge's slot is part of it): not of the rest of the batch, of repetition
+        or of any arrival order.  Compaction is by ballots, popcounts and prefixes; orderings are rank sorts over unique keys. */
+typedef struct {
+  int32_t stream, root_id, act_id, max_num_neighbors;   /* the reference passes 10 */
+  int32_t n_head, n_head_groups, n_fixed_groups, pad_;   /* 1 <= n_fixed_groups <= n_head_groups */
+  const int32_t *h_slot_kf;            /* HOST [the front end's max_keyframes], as in svs_nbh_request */
+  const int32_t *h_head_group_end;     /* HOST [n_head_groups] */
+  const svs_candidate_point *h_head;   /* HOST [n_head] */
+  const int32_t *h_head_group_kf;      /* HOST [n_head_groups]: the key of every group g >= n_fixed_groups (the entries before are not read) */
+} svs_nbr_request;                     /* 64 bytes */
+typedef struct {
+  int32_t n_points, n_map_points, n_vertex, n_no_slot, over_capacity;      /* as svs_nbh_result */
+  int32_t root_outside_window;
+  int32_t n_root_neighbors;            /* rule 1: ids taken */
+  int32_t n_no_path;                   /* rule 3 */
+  int32_t act_index, n_act_neighbors;  /* rule 4 */
+  int32_t n_head_kept, n_head_dropped; /* rule 6: records */
+  int32_t n_groups;                    /* rule 6: groups of the written list, the map's included */
+  int32_t pad_[3];
+} svs_nbr_result;                      /* 64 bytes */
+/* BLOCKING: one staged upload (requests, slot tables, head records), at most the map's CSR and adjacency rebuilds plus four launches (selection and point walk;
+   the list of vertices outside the window with its count, built on the device; the searches, a grid sized to an upper bound whose idle workgroups leave at
+   once; poses, ranking, matrix, head and tables), one download.  Outputs, each optional, HOST: h_res [n_requests]; h_point_id [n_requests][max_points],
+   h_vertex_id [n_requests][vertex_cap], h_vertex_T [n_requests][vertex_cap][12] as svs_frontend_set_candidates_from_map returns them (rule 3's poses);
+   h_act_neighbors [n_requests][vertex_cap]: rule 4's vertex indices, -1 behind them; h_strength [n_requests][vertex_cap][vertex_cap]: rule 5; rows of a
+   request over capacity or with its root outside the window: -1 / zeros.  For tests: h_records as svs_frontend_set_candidates_from_map; h_table [n_requests]
+   and h_vertex [n_requests][SVS_KF_MAX_VERTICES]: the svs_kf_table / svs_kf_vertex rows of the request's stream as they lie on the device behind the call;
+   h_slot_T [n_requests][max_keyframes][12]: the poses rule 7 wrote into the stream's slots, zeros for every other slot, without a refresh and for a request
+   that left its stream untouched.
+   Refused before anything is uploaded, all state unchanged -- SVS_ERR_INVALID: between svs_frontend_submit_frame and _wait_frame; fe and map on different
+   contexts; a stream out of range or named twice; root_id or act_id no keyframe of the map; max_num_neighbors < 0; vertex_cap outside 1 ..
+   SVS_KF_MAX_VERTICES; a slot table or head svs_frontend_set_candidates_from_map would refuse; n_fixed_groups outside 1 .. n_head_groups; a key that is no
+   keyframe of the map or on two keyed groups; SVS_ERR_CAPACITY: more than 64 groups; SVS_ERR_UNSUPPORTED: max_keyframes above SVS_KF_MAX_SLOTS. */
+int svs_frontend_set_neighborhood_from_root(svs_frontend *fe, svs_map *map, int n_requests, const svs_nbr_request *req, int refresh_poses, int vertex_cap,
+                                            svs_nbr_result *h_res, int32_t *h_point_id, int32_t *h_vertex_id, double *h_vertex_T, int32_t *h_act_neighbors,
+                                            int32_t *h_strength, svs_candidate_point *h_records, svs_kf_table *h_table, svs_kf_vertex *h_vertex,
+                                            double *h_slot_T);
+
 /* ---- multi-GPU: the library-owned collective of the landmark-sharded back-end.  The reference has no
    distributed code; one process per GPU each creates a context and a communicator (RCCL, bound at run time) --------------*/
 typedef struct { char bytes[128]; } svs_unique_id;      /* = ncclUniqueId */

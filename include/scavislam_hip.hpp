@@ -556,6 +556,16 @@ class StereoFrontend {
   inline bool setCandidatesFromMap(BackendMap &map, const std::vector<int32_t> &vertex_ids, const std::vector<int32_t> &slot_keyframe_ids,
                                    const std::vector<svs_candidate_point> &newpoints, const std::vector<int32_t> &newpoint_group_end, bool refresh_poses,
                                    svs_nbh_result *res, std::vector<int32_t> *point_ids, std::vector<FrontendVertex> *vertex_map, int vertex_cap = 64);
+  // Backend::computeNeighborhood(root_id) whole (backend.cpp:244-386) on the device-resident map, which is only read (svs_frontend_set_neighborhood_from_root):
+  // findNeighborsOfRoot, the points and anchors, computeAbsolutePose for the vertices outside the window, the active keyframe's strength_to_neighbors, the
+  // candidate list with the new-point groups in that order, the slot poses and the resident vertex table of decideKeyframes.  newpoints / newpoint_group_end:
+  // newpoint_map as groups; the first n_fixed_groups are newpoint_map[actkey_id], every later group g is newpoint_map[newpoint_group_keyframe[g]] and is left
+  // out when that keyframe is no neighbour of the active one.  act_neighbors: vertex_map indices of strength_to_neighbors(actkey).  false: refused, root outside
+  // the window or over capacity (see *res; the stream is then as before).  Defined behind BackendMap
+  inline bool setNeighborhoodFromMap(BackendMap &map, int32_t root_id, int32_t actkey_id, const std::vector<int32_t> &slot_keyframe_ids,
+                                     const std::vector<svs_candidate_point> &newpoints, const std::vector<int32_t> &newpoint_group_end, int n_fixed_groups,
+                                     const std::vector<int32_t> &newpoint_group_keyframe, bool refresh_poses, svs_nbr_result *res, std::vector<int32_t> *point_ids,
+                                     std::vector<FrontendVertex> *vertex_map, std::vector<int32_t> *act_neighbors, int max_num_neighbors = 10, int vertex_cap = 64);
   // computeFastCorners' outputs of the frame processed last (stereo_frontend.cpp:656-679): the corner list of a level in the order FastGrid inserts it into the
   // quadtree (cells row-major, corners of a cell row-major), corners per cell, and the persistent thresholds as they stand now (the CellGrid2d snapshot a Frame keeps)
   bool fastCorners(int level, std::vector<Corner> *corners, std::vector<int32_t> *cell_counts, std::vector<int32_t> *thresholds) {
@@ -1272,6 +1282,39 @@ inline bool StereoFrontend::setCandidatesFromMap(BackendMap &map, const std::vec
   if (r.over_capacity) return false;
   n_ = r.n_points;
   if (point_ids) point_ids->assign(pid.begin(), pid.begin() + r.n_points);
+  if (vertex_map) {
+    vertex_map->resize((size_t)r.n_vertex);
+    for (int i = 0; i < r.n_vertex; ++i) { (*vertex_map)[(size_t)i].frame_id = vid[(size_t)i]; std::memcpy((*vertex_map)[(size_t)i].T_me_from_w, &vT[(size_t)i * 12], 12 * sizeof(double)); }
+  }
+  return true;
+}
+inline bool StereoFrontend::setNeighborhoodFromMap(BackendMap &map, int32_t root_id, int32_t actkey_id, const std::vector<int32_t> &slot_keyframe_ids,
+                                                   const std::vector<svs_candidate_point> &newpoints, const std::vector<int32_t> &newpoint_group_end, int n_fixed_groups,
+                                                   const std::vector<int32_t> &newpoint_group_keyframe, bool refresh_poses, svs_nbr_result *res,
+                                                   std::vector<int32_t> *point_ids, std::vector<FrontendVertex> *vertex_map, std::vector<int32_t> *act_neighbors,
+                                                   int max_num_neighbors, int vertex_cap) {
+  if (!ok_ || !map.ok() || (int)slot_keyframe_ids.size() != max_keyframes_ || vertex_cap < 1) return false;
+  const std::vector<int32_t> one_group(1, (int32_t)newpoints.size());
+  const bool grouped = !newpoint_group_end.empty();
+  const std::vector<int32_t> &ge = grouped ? newpoint_group_end : one_group;
+  if (grouped && newpoint_group_keyframe.size() != ge.size()) return false;
+  svs_nbr_request q;
+  std::memset(&q, 0, sizeof q);
+  q.stream = 0; q.root_id = root_id; q.act_id = actkey_id; q.max_num_neighbors = max_num_neighbors;
+  q.n_head = (int32_t)newpoints.size(); q.n_head_groups = (int32_t)ge.size(); q.n_fixed_groups = grouped ? n_fixed_groups : 1;
+  q.h_slot_kf = slot_keyframe_ids.data(); q.h_head_group_end = ge.data(); q.h_head = newpoints.empty() ? nullptr : newpoints.data();
+  q.h_head_group_kf = grouped ? newpoint_group_keyframe.data() : nullptr;
+  svs_nbr_result r;
+  std::vector<int32_t> pid((size_t)max_points_), vid((size_t)vertex_cap), nbr((size_t)vertex_cap);
+  std::vector<double> vT((size_t)vertex_cap * 12);
+  if (!ctx_.check(svs_frontend_set_neighborhood_from_root(fe_, map.get(), 1, &q, refresh_poses ? 1 : 0, vertex_cap, &r, pid.data(), vid.data(), vT.data(), nbr.data(),
+                                                          nullptr, nullptr, nullptr, nullptr, nullptr)))
+    return false;
+  if (res) *res = r;
+  if (r.over_capacity || r.root_outside_window) return false;
+  n_ = r.n_points;
+  if (point_ids) point_ids->assign(pid.begin(), pid.begin() + r.n_points);
+  if (act_neighbors) act_neighbors->assign(nbr.begin(), nbr.begin() + r.n_act_neighbors);
   if (vertex_map) {
     vertex_map->resize((size_t)r.n_vertex);
     for (int i = 0; i < r.n_vertex; ++i) { (*vertex_map)[(size_t)i].frame_id = vid[(size_t)i]; std::memcpy((*vertex_map)[(size_t)i].T_me_from_w, &vT[(size_t)i * 12], 12 * sizeof(double)); }

@@ -8,7 +8,7 @@ import ctypes as C
 import os
 import weakref
 
-from .ctypes_types import BaParams, BaStats, Cam, FastGrid, KeyframeDecideArgs, KeyframeDecideParams, LoopCheck, LoopLocation, LoopLocationResult, LoopResult, MapAddKeyframeArgs, MapConstraintRequest, MapStrengthResult, MapWindowResult, NbhRequest, NbhResult, PoseOptParams, PoseOptStats, RegCommitResult, RegMapRequest, RegParams, RegRequest, RegResult, SeedArgs, SeedParams, SeedRequest, StereoParams, SurfParams, VertexRequest, VocabParams, VocabResult
+from .ctypes_types import BaParams, BaStats, Cam, FastGrid, KeyframeDecideArgs, KeyframeDecideParams, LoopCheck, LoopLocation, LoopLocationResult, LoopResult, MapAddKeyframeArgs, MapConstraintRequest, MapStrengthResult, MapWindowResult, NbhRequest, NbhResult, NbrRequest, NbrResult, PoseOptParams, PoseOptStats, RegCommitResult, RegMapRequest, RegParams, RegRequest, RegResult, SeedArgs, SeedParams, SeedRequest, StereoParams, SurfParams, VertexRequest, VocabParams, VocabResult
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SVS_LIB_PATH") or os.path.join(_HERE, "libscavislam_hip.so")   # override = kernel A/B experiments only
@@ -256,6 +256,8 @@ _SIGS = {
                                  C.POINTER(RegCommitResult), C.c_void_p, C.c_void_p, C.c_void_p],
     "svs_frontend_set_candidates_from_map": [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(NbhRequest), C.c_int, C.c_int, C.POINTER(NbhResult), C.c_void_p, C.c_void_p,
                                              C.c_void_p, C.c_void_p],
+    "svs_frontend_set_neighborhood_from_root": [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(NbrRequest), C.c_int, C.c_int, C.POINTER(NbrResult), C.c_void_p, C.c_void_p,
+                                                C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
     "svs_keyframe_decide": [C.c_void_p, C.POINTER(KeyframeDecideArgs), C.POINTER(KeyframeDecideParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                             C.c_int],
     "svs_frontend_set_vertex_table": [C.c_void_p, C.c_int, C.POINTER(VertexRequest)],

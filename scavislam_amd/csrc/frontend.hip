@@ -20,6 +20,7 @@
 #include "fast_view.h"
 #include "keyframe.h"
 #include "nbh_map.h"
+#include "nbr_map.h"
 #include "pose.h"
 #include "seed.h"
 #include <string.h>
@@ -1204,6 +1205,29 @@ extern "C" int svs_frontend_seed_keyframes(svs_frontend *fe, int n, const svs_se
   return SVS_OK;
 }
 
+// the resident vertex tables, the decision records and the list rows come with the first table (tables, vertices and slot tables zeroed: a stream's rows can be
+// read back before they were ever set)
+static int fe_vt_reserve(svs_frontend *fe) {
+  svs_ctx *ctx = fe->ctx;
+  if (fe->d_vt_tab) return SVS_OK;
+  const size_t Bz = (size_t)fe->B, mp = (size_t)fe->max_points, S = (size_t)fe->max_keyframes;
+  SVS_HIP(ctx, fe->d_vt_tab.alloc(Bz));
+  SVS_HIP(ctx, fe->d_vt_vtx.alloc(Bz * SVS_KF_MAX_VERTICES));
+  SVS_HIP(ctx, fe->d_vt_slot.alloc(Bz * S));
+  SVS_HIP(ctx, fe->d_vt_ids.alloc(Bz * 16 * mp));
+  SVS_HIP(ctx, fe->d_kd_dec.alloc(Bz));
+  SVS_HIP(ctx, fe->d_kd_new.alloc(Bz * mp));
+  SVS_HIP(ctx, fe->d_kd_track.alloc(Bz * mp));
+  SVS_HIP(ctx, fe->d_kd_new_rec.alloc(Bz * mp));
+  SVS_HIP(ctx, fe->d_kd_track_rec.alloc(Bz * mp));
+  SVS_HIP(ctx, fe->h_kd_dec.alloc(Bz));
+  SVS_HIP(ctx, hipMemsetAsync(fe->d_vt_tab, 0, sizeof(svs_kf_table) * Bz, ctx->stream));
+  SVS_HIP(ctx, hipMemsetAsync(fe->d_vt_vtx, 0, sizeof(svs_kf_vertex) * Bz * SVS_KF_MAX_VERTICES, ctx->stream));
+  SVS_HIP(ctx, hipMemsetAsync(fe->d_vt_slot, 0, sizeof(int32_t) * Bz * S, ctx->stream));
+  fe->vt_set.assign(Bz, 0);
+  return SVS_OK;
+}
+
 /* neighborhood_->vertex_map of a stream as the keyframe decision reads it (keyframe.hip; the contract is in the header): everything is checked on the host first,
    then one staged upload (requests, tables, vertices, slot tables, id arrays) and one scatter launch into the stream-indexed resident tables. */
 extern "C" int svs_frontend_set_vertex_table(svs_frontend *fe, int n_requests, const svs_vertex_request *req) {
@@ -1238,20 +1262,7 @@ extern "C" int svs_frontend_set_vertex_table(svs_frontend *fe, int n_requests, c
   }
   if (R == 0) return SVS_OK;
   SVS_DEVICE(ctx);
-  if (!fe->d_vt_tab) {      // the resident tables, the decision records and the list rows come with the first table
-    const size_t Bz = (size_t)B, mp = (size_t)fe->max_points;
-    SVS_HIP(ctx, fe->d_vt_tab.alloc(Bz));
-    SVS_HIP(ctx, fe->d_vt_vtx.alloc(Bz * SVS_KF_MAX_VERTICES));
-    SVS_HIP(ctx, fe->d_vt_slot.alloc(Bz * S));
-    SVS_HIP(ctx, fe->d_vt_ids.alloc(Bz * set_cap));
-    SVS_HIP(ctx, fe->d_kd_dec.alloc(Bz));
-    SVS_HIP(ctx, fe->d_kd_new.alloc(Bz * mp));
-    SVS_HIP(ctx, fe->d_kd_track.alloc(Bz * mp));
-    SVS_HIP(ctx, fe->d_kd_new_rec.alloc(Bz * mp));
-    SVS_HIP(ctx, fe->d_kd_track_rec.alloc(Bz * mp));
-    SVS_HIP(ctx, fe->h_kd_dec.alloc(Bz));
-    fe->vt_set.assign(Bz, 0);
-  }
+  if (int rc = fe_vt_reserve(fe)) return rc;
   auto up16 = [](size_t v) { return (v + 15) & ~(size_t)15; };
   const size_t off_tab = up16(sizeof(kfd_up) * (size_t)R), off_vtx = up16(off_tab + sizeof(svs_kf_table) * (size_t)R);
   const size_t off_slot = up16(off_vtx + sizeof(svs_kf_vertex) * SVS_KF_MAX_VERTICES * (size_t)R), off_ids = up16(off_slot + sizeof(int32_t) * (size_t)S * R);
@@ -1346,5 +1357,145 @@ extern "C" int svs_frontend_decide_keyframes(svs_frontend *fe, svs_map *map, con
     b0 = b1;
   }
   if (any) SVS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return SVS_OK;
+}
+
+/* a stream's whole neighbourhood from a root id (map.hip through nbr_map.h; the contract is in the header): everything is checked on the host first, then one
+   staged upload, the map's four launches writing d_pts / d_group_end / d_n_groups / d_n_new / d_kfs and the resident vertex tables in place, one download from
+   which the host state follows */
+extern "C" int svs_frontend_set_neighborhood_from_root(svs_frontend *fe, svs_map *map, int n_requests, const svs_nbr_request *req, int refresh_poses, int vertex_cap,
+                                                       svs_nbr_result *h_res, int32_t *h_point_id, int32_t *h_vertex_id, double *h_vertex_T, int32_t *h_act_neighbors,
+                                                       int32_t *h_strength, svs_candidate_point *h_records, svs_kf_table *h_table, svs_kf_vertex *h_vertex,
+                                                       double *h_slot_T) {
+  svs_ctx *ctx = fe ? fe->ctx : nullptr;
+  SVS_REQUIRE(ctx, fe && map && svs_map_ctx(map) == ctx && !fe->submitted && n_requests >= 0 && n_requests <= fe->B && (n_requests == 0 || req) && vertex_cap >= 1 &&
+                       vertex_cap <= SVS_KF_MAX_VERTICES);
+  if (fe->max_keyframes > SVS_KF_MAX_SLOTS) { ctx->err = "svs_frontend_set_neighborhood_from_root: more than SVS_KF_MAX_SLOTS keyframe slots"; return SVS_ERR_UNSUPPORTED; }
+  const int R = n_requests, B = fe->B, K = fe->max_keyframes, MP = fe->max_points, VB = vertex_cap;
+  size_t n_head = 0;
+  {
+    std::vector<uint8_t> named((size_t)B, 0);
+    std::vector<int32_t> sorted;
+    for (int r = 0; r < R; ++r) {
+      const svs_nbr_request &q = req[r];
+      SVS_REQUIRE(ctx, q.stream >= 0 && q.stream < B && !named[q.stream]);
+      named[q.stream] = 1;
+      SVS_REQUIRE(ctx, svs_map_has_keyframe(map, q.root_id) && svs_map_has_keyframe(map, q.act_id) && q.max_num_neighbors >= 0);
+      SVS_REQUIRE(ctx, q.h_slot_kf && q.n_head >= 0 && q.n_head <= MP && (q.n_head == 0 || q.h_head) && q.n_head_groups >= 1 && q.h_head_group_end);
+      if (q.n_head_groups + 1 > MAX_GROUPS) { ctx->err = "svs_frontend_set_neighborhood_from_root: more than 64 groups"; return SVS_ERR_CAPACITY; }
+      SVS_REQUIRE(ctx, q.n_fixed_groups >= 1 && q.n_fixed_groups <= q.n_head_groups && (q.n_fixed_groups == q.n_head_groups || q.h_head_group_kf));
+      const uint8_t *kept = fe->kept.data() + (size_t)q.stream * K;
+      sorted.clear();
+      for (int s = 0; s < K; ++s)
+        if (q.h_slot_kf[s] >= 0) { SVS_REQUIRE(ctx, kept[s]); sorted.push_back(q.h_slot_kf[s]); }
+      std::sort(sorted.begin(), sorted.end());
+      SVS_REQUIRE(ctx, std::adjacent_find(sorted.begin(), sorted.end()) == sorted.end());
+      SVS_REQUIRE(ctx, q.h_head_group_end[q.n_head_groups - 1] == q.n_head);
+      for (int g = 0; g < q.n_head_groups; ++g) SVS_REQUIRE(ctx, q.h_head_group_end[g] >= (g ? q.h_head_group_end[g - 1] : 0));
+      for (int i = 0; i < q.n_head; ++i) SVS_REQUIRE(ctx, q.h_head[i].kf_index < 0 || (q.h_head[i].kf_index < K && kept[q.h_head[i].kf_index]));
+      sorted.clear();
+      for (int g = q.n_fixed_groups; g < q.n_head_groups; ++g) { SVS_REQUIRE(ctx, svs_map_has_keyframe(map, q.h_head_group_kf[g])); sorted.push_back(q.h_head_group_kf[g]); }
+      std::sort(sorted.begin(), sorted.end());
+      SVS_REQUIRE(ctx, std::adjacent_find(sorted.begin(), sorted.end()) == sorted.end());
+      n_head += (size_t)q.n_head;
+    }
+  }
+  if (R == 0) return SVS_OK;
+  SVS_DEVICE(ctx);
+  if (int rc = fe_vt_reserve(fe)) return rc;
+  auto al = [](size_t v) { return (v + 15) & ~(size_t)15; };
+  const size_t Rz = (size_t)R, n_ids = Rz * 2 * K;
+  const size_t o_ids = al(Rz * sizeof(nbr_req)), o_head = o_ids + al(n_ids * sizeof(int32_t)), in_bytes = o_head + n_head * sizeof(svs_candidate_point);
+  const size_t o_res = al(in_bytes), o_slot = o_res + Rz * sizeof(svs_nbr_result), o_vT = o_slot + Rz * K * 12 * sizeof(double), o_vid = o_vT + Rz * VB * 12 * sizeof(double),
+               o_act = o_vid + al(Rz * VB * sizeof(int32_t)), o_str = o_act + al(Rz * VB * sizeof(int32_t)), o_pid = o_str + al(Rz * VB * VB * sizeof(int32_t)),
+               down_end = o_pid + al(Rz * MP * sizeof(int32_t));
+  const size_t o_hdr = down_end, o_mid = o_hdr + Rz * VB * sizeof(int4), o_list = o_mid + Rz * sizeof(nbr_mid), o_mpid = o_list + al(Rz * VB * sizeof(int2)),
+               o_wv = o_mpid + al(Rz * MP * sizeof(int32_t)), o_woff = o_wv + al(Rz * VB * sizeof(int32_t)), bytes = o_woff + al((Rz + 1) * sizeof(int32_t));
+  if (fe->h_nbh.bytes() < bytes) {      // (no call is in flight: this one is blocking)
+    SVS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    SVS_HIP(ctx, fe->h_nbh.alloc(bytes * 2));
+    SVS_HIP(ctx, fe->d_nbh.alloc(bytes * 2));
+  }
+  uint8_t *hs = fe->h_nbh, *ds = fe->d_nbh;
+  nbr_req *hq = reinterpret_cast<nbr_req *>(hs);
+  int32_t *ids = reinterpret_cast<int32_t *>(hs + o_ids);
+  svs_candidate_point *head = reinterpret_cast<svs_candidate_point *>(hs + o_head);
+  size_t at_head = 0;
+  for (int r = 0; r < R; ++r) {
+    const svs_nbr_request &q = req[r];
+    nbr_req &s = hq[r];
+    memset(&s, 0, sizeof s);
+    s.stream = q.stream; s.root = q.root_id; s.act = q.act_id; s.max_nn = q.max_num_neighbors;
+    s.n_head = q.n_head; s.n_groups = q.n_head_groups; s.n_fixed = q.n_fixed_groups; s.prev_len = fe->n_points[q.stream];
+    s.slot_off = (int32_t)((size_t)r * 2 * K); s.slot_raw_off = s.slot_off + K;
+    for (int k = 0; k < K; ++k) { ids[s.slot_off + k] = svs_map_has_keyframe(map, q.h_slot_kf[k]) ? q.h_slot_kf[k] : -1; ids[s.slot_raw_off + k] = q.h_slot_kf[k]; }
+    s.head_off = (int32_t)at_head;
+    if (q.n_head) memcpy(head + at_head, q.h_head, (size_t)q.n_head * sizeof(svs_candidate_point));
+    at_head += (size_t)q.n_head;
+    for (int g = 0; g < q.n_head_groups; ++g) { s.group_end[g] = q.h_head_group_end[g]; s.group_kf[g] = g >= q.n_fixed_groups ? q.h_head_group_kf[g] : -1; }
+  }
+  SVS_HIP(ctx, hipMemcpyAsync(ds, hs, in_bytes, hipMemcpyHostToDevice, ctx->stream));
+  MapNbrDst D{};
+  D.req = reinterpret_cast<const nbr_req *>(ds); D.ids = reinterpret_cast<const int32_t *>(ds + o_ids); D.head = reinterpret_cast<const svs_candidate_point *>(ds + o_head);
+  D.R = R; D.VB = VB;
+  D.pts = fe->d_pts; D.max_points = MP; D.group_end = fe->d_group_end; D.n_groups = fe->d_n_groups; D.n_new = fe->d_n_new; D.kfs = fe->d_kfs; D.max_keyframes = K;
+  D.vt_tab = fe->d_vt_tab; D.vt_vtx = fe->d_vt_vtx; D.vt_slot = fe->d_vt_slot;
+  D.refresh = refresh_poses ? 1 : 0;
+  D.res = reinterpret_cast<svs_nbr_result *>(ds + o_res); D.slot_T = reinterpret_cast<double *>(ds + o_slot);
+  D.vertex_T = reinterpret_cast<double *>(ds + o_vT); D.vertex_id = reinterpret_cast<int32_t *>(ds + o_vid);
+  D.act_nb = reinterpret_cast<int32_t *>(ds + o_act); D.strength = reinterpret_cast<int32_t *>(ds + o_str); D.point_id = reinterpret_cast<int32_t *>(ds + o_pid);
+  D.walk_hdr = reinterpret_cast<int4 *>(ds + o_hdr); D.mid = reinterpret_cast<nbr_mid *>(ds + o_mid); D.walk_list = reinterpret_cast<int2 *>(ds + o_list);
+  D.map_pid = reinterpret_cast<int32_t *>(ds + o_mpid); D.walk_v = reinterpret_cast<int32_t *>(ds + o_wv); D.walk_off = reinterpret_cast<int32_t *>(ds + o_woff);
+  if (int rc = svs_map_build_root_neighborhoods(map, D)) return rc;
+  const size_t down_to = h_point_id ? down_end : h_strength ? o_pid : h_act_neighbors ? o_str : h_vertex_id ? o_act : h_vertex_T ? o_vid : o_vT;
+  SVS_HIP(ctx, hipMemcpyAsync(hs + o_res, ds + o_res, down_to - o_res, hipMemcpyDeviceToHost, ctx->stream));
+  if (h_records) SVS_HIP(ctx, hipMemcpyAsync(h_records, fe->d_pts, sizeof(svs_candidate_point) * (size_t)MP * B, hipMemcpyDeviceToHost, ctx->stream));
+  for (int r = 0; r < R && (h_table || h_vertex); ++r) {
+    const size_t b = (size_t)req[r].stream;
+    if (h_table) SVS_HIP(ctx, hipMemcpyAsync(h_table + r, fe->d_vt_tab + b, sizeof(svs_kf_table), hipMemcpyDeviceToHost, ctx->stream));
+    if (h_vertex)
+      SVS_HIP(ctx, hipMemcpyAsync(h_vertex + (size_t)r * SVS_KF_MAX_VERTICES, fe->d_vt_vtx + b * SVS_KF_MAX_VERTICES, sizeof(svs_kf_vertex) * SVS_KF_MAX_VERTICES,
+                                  hipMemcpyDeviceToHost, ctx->stream));
+  }
+  SVS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  // ---- the host state follows the download
+  const svs_nbr_result *res = reinterpret_cast<const svs_nbr_result *>(hs + o_res);
+  bool any = false;
+  for (int r = 0; r < R; ++r) {
+    const svs_nbr_request &q = req[r];
+    const bool none = res[r].over_capacity != 0 || res[r].root_outside_window != 0;
+    if (h_res) h_res[r] = res[r];
+    auto row = [&](int32_t *dst, size_t off, size_t n) {
+      if (!dst) return;
+      if (none) std::fill(dst + (size_t)r * n, dst + (size_t)(r + 1) * n, -1);
+      else memcpy(dst + (size_t)r * n, hs + off + (size_t)r * n * sizeof(int32_t), n * sizeof(int32_t));
+    };
+    row(h_point_id, o_pid, (size_t)MP);
+    row(h_vertex_id, o_vid, (size_t)VB);
+    row(h_act_neighbors, o_act, (size_t)VB);
+    row(h_strength, o_str, (size_t)VB * VB);
+    if (h_vertex_T) {
+      if (none) memset(h_vertex_T + (size_t)r * VB * 12, 0, (size_t)VB * 12 * sizeof(double));
+      else memcpy(h_vertex_T + (size_t)r * VB * 12, hs + o_vT + (size_t)r * VB * 12 * sizeof(double), (size_t)VB * 12 * sizeof(double));
+    }
+    if (h_slot_T) {
+      if (none) memset(h_slot_T + (size_t)r * K * 12, 0, (size_t)K * 12 * sizeof(double));
+      else memcpy(h_slot_T + (size_t)r * K * 12, hs + o_slot + (size_t)r * K * 12 * sizeof(double), (size_t)K * 12 * sizeof(double));
+    }
+    if (none) continue;
+    any = true;
+    fe->n_points[q.stream] = res[r].n_points; fe->n_new_records[q.stream] = res[r].n_head_kept;
+    fe->max_groups_used = std::max(fe->max_groups_used, (int)res[r].n_groups);
+    fe->vt_set[q.stream] = 1;
+    if (refresh_poses) {
+      const double *sT = reinterpret_cast<const double *>(hs + o_slot) + (size_t)r * K * 12;
+      for (int k = 0; k < K; ++k)
+        if (svs_map_has_keyframe(map, q.h_slot_kf[k])) memcpy(fe->h_kfs[(size_t)q.stream * K + k].T_anchor_from_w, sT + (size_t)k * 12, 12 * sizeof(double));
+    }
+  }
+  if (any) {
+    fe->n_launch = *std::max_element(fe->n_points.begin(), fe->n_points.end());
+    fe->n_gated = -1;      // the last step's gate records no longer belong to the list on the device
+  }
   return SVS_OK;
 }

@@ -16,7 +16,9 @@
 //                   computeConstraint (slam_graph.cpp:787-846) with one workgroup per keyframe pair -- common points as an ordered bitmap compaction, depths in f64,
 //                   the median by a radix select over the doubles' bit patterns, setConstraint in the same launch; map_edge_gather is copyContraintsToG2o
 //   map_walk.inc        the pose graph's walks (computeInitialDoubleWin, framesInNeighborhood, shortestPathToWindow + computeAbsolutePose, reinitializePoses): a
-//                   strength-ordered adjacency built from the edge records and one level-synchronous breadth-first search per request
+//                   strength-ordered adjacency built from the edge records and one level-synchronous breadth-first search per request; behind them the four
+//                   map_nbr_* kernels of a front-end stream's whole neighbourhood from a root id (nbr_map.h): findNeighborsOfRoot, nbh_collect below, the searches
+//                   from a device-built list, then poses, strength_to_neighbors, the strength matrix, the head's order, the list and the resident vertex table
 //   map_addkf.inc       inserting a keyframe (SlamGraph::addKeyframe): computeStrength as counting passes over the track points' observer rows with one workgroup per
 //                   call, the kept points and measured pairs compacted by prefix sums, the new edges' constraints through map_cons_kernel; two read-backs
 //   map_commit.inc      registerKeyframes / addLoopClosure: a device track list and an edge list applied to the map (the new pairs appended by prefix sums, the
@@ -24,6 +26,7 @@
 // Integer and copy work throughout (but for the three divisions of invert_depth and the f64 geometry of map_cons_kernel); the host keeps the id sets and the set of pairs, so every refusal happens before anything is uploaded.
 #include "reg_map.h"
 #include "nbh_map.h"
+#include "nbr_map.h"
 #include "ba_map.h"
 #include "walk_map.h"
 #include "kf_map.h"
@@ -383,16 +386,13 @@ __device__ __forceinline__ void wave_or_by_word(uint32_t *mark, int word, uint32
 // The same sets as above -- the given vertices and the anchors as LDS bitmaps over keyframe ids, the points as the request's row of M.mark, ascending ids by
 // popcounts and prefixes -- and a table id -> slot of the stream in LDS.  Everything that decides whether the request fits (the point count, the vertex count) is
 // known before the first write into the front end's tables: a request over capacity returns with those untouched.
-__global__ __launch_bounds__(MB_THREADS) void map_nbh_kernel(MapK M, MapNbhDst D) {
-  __shared__ uint32_t s_vert[MAP_KF_WORDS], s_anch[MAP_KF_WORDS];
-  __shared__ int16_t s_slot[MAP_MAX_KF];                           // -1: no slot of the stream holds the keyframe
-  __shared__ int s_w[MB_THREADS / 64];
-  const int r = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const nbh_req &Q = D.req[r];
-  const int b = Q.stream, n_vertex = Q.n_vertex, n_head = Q.n_head, G = Q.n_groups, MP = D.max_points, K = D.max_keyframes;
-  const int32_t *vertex = D.ids + Q.vertex_off, *slot_kf = D.ids + Q.slot_off;
-  uint32_t *mark = M.mark + (size_t)r * M.mark_b;
-  int32_t *point_id = D.point_id + (size_t)r * MP;
+// steps a-f of the neighbourhood of a vertex list, shared by map_nbh_kernel and map_nbr_collect_kernel (map_walk.inc): the points observed by the list's keyframes
+// as ascending ids in ids_row[id_off ..] (what lies at or behind ids_row[cap] is only counted), their anchors, and the anchors that are not in the list ("extra":
+// this lane's word of that bitmap, `rank` the set bits in the words before it).  Every lane of the workgroup calls it (barriers inside)
+struct NbhSets { int n_map, n_no_slot, n_extra, rank; uint32_t extra; bool over_points; };
+__device__ __forceinline__ NbhSets nbh_collect(const MapK &M, uint32_t *mark, int32_t *ids_row, int id_off, int cap, const int32_t *vertex, int n_vertex,
+                                               const int32_t *slot_kf, int K, uint32_t *s_vert, uint32_t *s_anch, int16_t *s_slot, int *s_w) {
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int n_words = (M.pt_hi + 31) >> 5;                      // <= mark_b
   // a. empty sets
   s_vert[tid] = 0; s_anch[tid] = 0;
@@ -413,39 +413,55 @@ __global__ __launch_bounds__(MB_THREADS) void map_nbh_kernel(MapK M, MapNbhDst D
     }
   }
   __syncthreads();
-  // d. the set bits in ascending order, behind the head's ids; what does not fit is only counted
+  // d. the set bits in ascending order; what does not fit is only counted
+  NbhSets S;
   int n_map = 0;
   for (int base = 0; base < n_words; base += MB_THREADS) {      // block-uniform trip count
     const int w = base + tid;
     uint32_t bits = w < n_words ? __hip_atomic_load(&mark[w], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0u;
     int tot;
-    int pos = n_head + n_map + block_excl_scan(__popc(bits), s_w, tot);
+    int pos = id_off + n_map + block_excl_scan(__popc(bits), s_w, tot);
     while (bits) {
       const int bit = __ffs((int)bits) - 1;
       bits &= bits - 1;
-      if (pos < MP) point_id[pos] = (w << 5) + bit;
+      if (pos < cap) ids_row[pos] = (w << 5) + bit;
       ++pos;
     }
     n_map += tot;
   }
-  const int total = n_head + n_map;
-  const bool over_points = total > MP;
+  S.n_map = n_map;
+  S.over_points = id_off + n_map > cap;
   __syncthreads();
   // e. their anchors (:374-384), and how many of them the stream holds no slot for
   int c = 0;
-  if (!over_points)
+  if (!S.over_points)
     for (int i = tid; i < n_map; i += MB_THREADS) {
-      const int a = M.pt[point_id[n_head + i]].kf_index;
+      const int a = M.pt[ids_row[id_off + i]].kf_index;
       if ((unsigned)a < (unsigned)MAP_MAX_KF) atomicOr(&s_anch[a >> 5], 1u << (a & 31));
       if ((unsigned)a >= (unsigned)MAP_MAX_KF || s_slot[a] < 0) ++c;
     }
-  int n_no_slot;
-  (void)block_excl_scan(c, s_w, n_no_slot);                      // (its barriers also complete s_anch)
+  (void)block_excl_scan(c, s_w, S.n_no_slot);                    // (its barriers also complete s_anch)
+  // f. the anchors that are not among the given vertices, ascending
+  S.extra = s_anch[tid] & ~s_vert[tid];
+  S.rank = block_excl_scan(__popc(S.extra), s_w, S.n_extra);
+  return S;
+}
+
+__global__ __launch_bounds__(MB_THREADS) void map_nbh_kernel(MapK M, MapNbhDst D) {
+  __shared__ uint32_t s_vert[MAP_KF_WORDS], s_anch[MAP_KF_WORDS];
+  __shared__ int16_t s_slot[MAP_MAX_KF];                           // -1: no slot of the stream holds the keyframe
+  __shared__ int s_w[MB_THREADS / 64];
+  const int r = blockIdx.x, tid = threadIdx.x;
+  const nbh_req &Q = D.req[r];
+  const int b = Q.stream, n_vertex = Q.n_vertex, n_head = Q.n_head, G = Q.n_groups, MP = D.max_points, K = D.max_keyframes;
+  const int32_t *vertex = D.ids + Q.vertex_off, *slot_kf = D.ids + Q.slot_off;
+  int32_t *point_id = D.point_id + (size_t)r * MP;
+  const NbhSets S = nbh_collect(M, M.mark + (size_t)r * M.mark_b, point_id, n_head, MP, vertex, n_vertex, slot_kf, K, s_vert, s_anch, s_slot, s_w);
+  const int n_map = S.n_map, total = n_head + n_map, n_no_slot = S.n_no_slot, rank = S.rank;
+  const bool over_points = S.over_points;
+  uint32_t extra = S.extra;
   // f. the vertex set: the given ids, behind them the anchors that are not among them, ascending
-  uint32_t extra = s_anch[tid] & ~s_vert[tid];
-  int n_extra;
-  const int rank = block_excl_scan(__popc(extra), s_w, n_extra);
-  const int n_vert = over_points ? 0 : n_vertex + n_extra;
+  const int n_vert = over_points ? 0 : n_vertex + S.n_extra;
   if (over_points || n_vert > D.VB) {                            // block-uniform: nothing of the stream has been touched
     if (tid == 0) {
       svs_nbh_result R{};

@@ -271,6 +271,26 @@ class NbhResult(C.Structure):
 assert C.sizeof(NbhRequest) == 48 and C.sizeof(NbhResult) == 32
 
 
+# ---- front end: a stream's whole neighbourhood from a root id (svs_frontend_set_neighborhood_from_root)
+class NbrRequest(C.Structure):
+    """svs_nbr_request: the stream, the root and the active keyframe by id, findNeighborsOfRoot's cap, the stream's slot table, the head's groups (the first
+    n_fixed_groups stay, every later one is keyed by a keyframe id)"""
+    _fields_ = [("stream", C.c_int32), ("root_id", C.c_int32), ("act_id", C.c_int32), ("max_num_neighbors", C.c_int32), ("n_head", C.c_int32),
+                ("n_head_groups", C.c_int32), ("n_fixed_groups", C.c_int32), ("pad_", C.c_int32), ("h_slot_kf", C.c_void_p), ("h_head_group_end", C.c_void_p),
+                ("h_head", C.c_void_p), ("h_head_group_kf", C.c_void_p)]
+
+
+class NbrResult(C.Structure):
+    """svs_nbr_result"""
+    _fields_ = [("n_points", C.c_int32), ("n_map_points", C.c_int32), ("n_vertex", C.c_int32), ("n_no_slot", C.c_int32), ("over_capacity", C.c_int32),
+                ("root_outside_window", C.c_int32), ("n_root_neighbors", C.c_int32), ("n_no_path", C.c_int32), ("act_index", C.c_int32),
+                ("n_act_neighbors", C.c_int32), ("n_head_kept", C.c_int32), ("n_head_dropped", C.c_int32), ("n_groups", C.c_int32), ("pad_", C.c_int32 * 3)]
+
+
+NBR_RESULT_FIELDS = tuple(f for f, _ in NbrResult._fields_ if f != "pad_")
+assert C.sizeof(NbrRequest) == 64 and C.sizeof(NbrResult) == 64
+
+
 # ---- back end: the double window's BA problem from the map (svs_map_prepare_window)
 class MapWindowResult(C.Structure):
     """svs_map_window_result: final window, W0, active points (-1: the final window exceeded window_cap), upper bound of the window's edges"""

@@ -698,6 +698,61 @@ class StereoFrontend:
             out.append(o)
         return out
 
+    def setNeighborhoodFromMap(self, resident_map, requests, refresh_poses=True, vertex_cap=64, want_records=False, want_tables=False):
+        """Backend::computeNeighborhood(root_id) whole (backend.cpp:244-386) on the device-resident map, which is only read: findNeighborsOfRoot, the point and
+        anchor walk, computeAbsolutePose for the vertices outside the window, the active keyframe's strength_to_neighbors, the head's groups put into that order
+        (stereo_frontend.cpp:1007-1029), the stream's list, slot poses and resident vertex table (svs_frontend_set_neighborhood_from_root).
+        requests: dicts with stream, root_id, act_id, slot_kf and optionally max_num_neighbors (10), head (CANDIDATE_DTYPE) with head_group_end (default: one
+        group), n_fixed_groups (default: all) and head_group_kf (per group the keyframe id that keys it; read from n_fixed_groups on).  Returns one dict per
+        request: the svs_nbr_result fields, point_ids, vertex_ids / vertex_T, act_neighbors (vertex indices), strength ([n_vertex][n_vertex], -1: no edge);
+        want_records adds `table` (the whole candidate table), want_tables `kf_table` / `kf_vertex` (the stream's resident rows, KF_TABLE_DTYPE / KF_VERTEX_DTYPE
+        [KF_MAX_VERTICES]).  A request over capacity or with its root outside the window leaves its stream untouched"""
+        from .ctypes_types import KF_MAX_VERTICES, KF_TABLE_DTYPE, KF_VERTEX_DTYPE, NBR_RESULT_FIELDS, NbrRequest, NbrResult
+        n = len(requests)
+        arr = (NbrRequest * max(n, 1))()
+        keep = []
+        for r, q in zip(arr, requests):
+            slot = np.ascontiguousarray(q["slot_kf"], np.int32).reshape(-1)
+            head = np.ascontiguousarray(q.get("head", np.zeros(0, CANDIDATE_DTYPE)), CANDIDATE_DTYPE).reshape(-1)
+            ge = np.ascontiguousarray(q.get("head_group_end", [len(head)]), np.int32).reshape(-1)
+            gk = np.ascontiguousarray(q.get("head_group_kf", [-1] * len(ge)), np.int32).reshape(-1)
+            if len(slot) != self.max_keyframes or len(gk) != len(ge):
+                raise ValueError("slot_kf needs one entry per keyframe slot of the front end, head_group_kf one per head group")
+            keep += [slot, head, ge, gk]
+            r.stream, r.root_id, r.act_id, r.max_num_neighbors = int(q.get("stream", 0)), int(q["root_id"]), int(q["act_id"]), int(q.get("max_num_neighbors", 10))
+            r.n_head, r.n_head_groups, r.n_fixed_groups = len(head), len(ge), int(q.get("n_fixed_groups", len(ge)))
+            r.h_slot_kf, r.h_head_group_end, r.h_head, r.h_head_group_kf = slot.ctypes.data, ge.ctypes.data, head.ctypes.data if len(head) else None, gk.ctypes.data
+        res = (NbrResult * max(n, 1))()
+        mp, m = self.max_points, max(n, 1)
+        pid, vid, vT = np.empty((m, mp), np.int32), np.empty((m, vertex_cap), np.int32), np.empty((m, vertex_cap, 12), np.float64)
+        act, strength = np.empty((m, vertex_cap), np.int32), np.empty((m, vertex_cap, vertex_cap), np.int32)
+        table = np.empty((self.n_streams, mp), CANDIDATE_DTYPE) if want_records else None
+        tab = np.empty(m, KF_TABLE_DTYPE) if want_tables else None
+        vtx = np.empty((m, KF_MAX_VERTICES), KF_VERTEX_DTYPE) if want_tables else None
+        slot_T = np.empty((m, self.max_keyframes, 12), np.float64)
+        ptr = lambda a: a.ctypes.data if a is not None else None
+        self.ctx.check(self.ctx.lib.svs_frontend_set_neighborhood_from_root(self.h, resident_map.h, n, arr, int(bool(refresh_poses)), int(vertex_cap), res, ptr(pid), ptr(vid),
+                                                                            ptr(vT), ptr(act), ptr(strength), ptr(table), ptr(tab), ptr(vtx), ptr(slot_T)))
+        out = []
+        for i in range(n):
+            o = {f: int(getattr(res[i], f)) for f in NBR_RESULT_FIELDS}
+            ok = not (o["over_capacity"] or o["root_outside_window"])
+            if ok:
+                self.n_points[arr[i].stream] = o["n_points"]
+            nv = o["n_vertex"] if ok else 0
+            o["point_ids"] = pid[i, :o["n_points"] if ok else 0].copy()
+            o["vertex_ids"], o["vertex_T"] = vid[i, :nv].copy(), vT[i, :nv].copy()
+            o["act_neighbors"] = act[i, :o["n_act_neighbors"] if ok else 0].copy()
+            o["strength"] = strength[i, :nv, :nv].copy()
+            o["slot_T"] = slot_T[i].copy()                      # what the refresh wrote, zeros elsewhere
+            o["raw"] = (bytes(res[i]), pid[i].tobytes(), vid[i].tobytes(), vT[i].tobytes(), act[i].tobytes(), strength[i].tobytes())      # full rows (tests)
+            if want_records:
+                o["table"] = table
+            if want_tables:
+                o["kf_table"], o["kf_vertex"] = tab[i].copy(), vtx[i].copy()
+            out.append(o)
+        return out
+
     def stagingView(self):
         """numpy views (left u8 [h, w], right u8 [h, w], disp f32 [h, w]) of the pinned buffers the next frame is staged in: a frame written into
         them and passed on as it is needs no host-side copy"""
