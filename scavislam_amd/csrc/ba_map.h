@@ -1,4 +1,4 @@
-// ba_map.h -- what ba.hip and map.hip share: the window svs_map_prepare_window leaves in the device-resident map (map.hip), as svs_ba_window_from_map /
+// ba_map.h -- what ba.hip and map.hip share: the window svs_map_prepare_window leaves in the device-resident map (map.hip: map_window.inc), as svs_ba_window_from_map /
 // svs_ba_store_to_map (ba_window.inc) read and write it.  Neither translation unit reaches into the other's handle.
 #pragma once
 #include "common.h"
@@ -23,7 +23,7 @@ struct MapWindowView {
 // the stored T_lo_from_hi) per constraint.  SVS_ERR_INVALID (nothing enqueued) without a valid prepared window or where an edge of the list is not marginalised
 int svs_map_window_constraint_list(svs_map *map, std::vector<int4> *out);
 // one launch, asynchronous: record c of d_out = (T_21, info, pose1 = i, pose2 = j) of d_list[c] from the edge table (pose_inv where the list says so; built in
-// map.hip: no contraction, so the inverse is the one svs_map_set_constraints and the NumPy model form)
+// map.hip (map_edges.inc): no contraction, so the inverse is the one svs_map_set_constraints and the NumPy model form)
 int svs_map_gather_constraints(svs_map *map, const int4 *d_list, int C, svs_ba_constraint *d_out);
 
 svs_ctx *svs_map_ctx(svs_map *map);

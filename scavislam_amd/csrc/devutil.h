@@ -111,6 +111,13 @@ __device__ __forceinline__ T wave_sum(T v) {
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
   return v;
 }
+// wave64 inclusive prefix sum: lane l returns v of lanes 0 .. l
+__device__ __forceinline__ int wave_incl_scan(int v) {
+  const int lane = lane_id();
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) { const int t = __shfl_up(v, o, 64); if (lane >= o) v += t; }
+  return v;
+}
 
 // value of lane `lane` of a 64-bit quantity: a readlane of each half (lane is wave-uniform; a compile-time constant after unrolling where that matters)
 __device__ __forceinline__ double lane_bcast(double v, int lane) {

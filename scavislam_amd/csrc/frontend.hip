@@ -436,7 +436,7 @@ extern "C" int svs_frontend_set_candidates_all(svs_frontend *fe, const svs_candi
   return SVS_OK;
 }
 
-/* a stream's neighbourhood list from the device-resident map (map.hip through nbh_map.h; the contract is in the header): everything is checked on the host first,
+/* a stream's neighbourhood list from the device-resident map (map.hip: map_nbh.inc, through nbh_map.h; the contract is in the header): everything is checked on the host first,
    then one staged upload, the map's walk writing d_pts / d_group_end / d_n_groups / d_n_new / d_kfs in place, one download from which the host state follows */
 extern "C" int svs_frontend_set_candidates_from_map(svs_frontend *fe, svs_map *map, int n_requests, const svs_nbh_request *req, int refresh_poses, int vertex_cap,
                                                     svs_nbh_result *h_res, int32_t *h_point_id, int32_t *h_vertex_id, double *h_vertex_T,
@@ -1360,7 +1360,7 @@ extern "C" int svs_frontend_decide_keyframes(svs_frontend *fe, svs_map *map, con
   return SVS_OK;
 }
 
-/* a stream's whole neighbourhood from a root id (map.hip through nbr_map.h; the contract is in the header): everything is checked on the host first, then one
+/* a stream's whole neighbourhood from a root id (map.hip: map_nbh.inc, through nbr_map.h; the contract is in the header): everything is checked on the host first, then one
    staged upload, the map's four launches writing d_pts / d_group_end / d_n_groups / d_n_new / d_kfs and the resident vertex tables in place, one download from
    which the host state follows */
 extern "C" int svs_frontend_set_neighborhood_from_root(svs_frontend *fe, svs_map *map, int n_requests, const svs_nbr_request *req, int refresh_poses, int vertex_cap,

@@ -1,4 +1,4 @@
-// kf_map.h -- what keyframe.hip and map.hip share: the by-point observer rows of the device-resident map (map.hip) as a read-only view, and the membership test
+// kf_map.h -- what keyframe.hip and map.hip share: the by-point observer rows of the device-resident map (map.hip: map_csr.inc) as a read-only view, and the membership test
 // "is point p in the feature_table of keyframe k" the keyframe decision (keyframe.hip) makes on them.  Neither translation unit reaches into the other's handle.
 #pragma once
 #include "common.h"

@@ -1,4 +1,4 @@
-// map_addkf.inc -- inserting a keyframe into the resident map (SlamGraph::addKeyframe, slam_graph.cpp:143-186), included by map.hip behind map_walk.inc.
+// map_addkf.inc -- inserting a keyframe into the resident map (SlamGraph::addKeyframe, slam_graph.cpp:143-186), included by map.hip behind map_window.inc.
 //   map_strength_kernel      computeStrength (:467-552) as the closed form of include/scavislam_hip.h, one workgroup per call: the keys are an LDS bitmap over
 //                            keyframe ids (new points' anchors, observer rows of the track points), popcount prefixes give the ascending key list and id -> rank,
 //                            everything per key is an LDS table of 1024 entries.  t_q(f), "the index of the h-th track entry f observes in class q", is found by
@@ -8,7 +8,6 @@
 //   map_addkf_apply_kernel   addNewPointsToMap / addNewObsToOldPoints (:358-420) from the block the strength kernel read: the kept points and the kept measurement
 //                            records are compacted by prefix sums into the point store, the pair log and the measured store in the order the twin calls would
 //                            give them; the new keyframe's pose is pose_mul(T_newkey_from_oldkey, T_oldkey_from_world) formed here.
-//   map_get_points_kernel / map_feature_table_kernel      the two read-backs.
 // The edges go through map_edge_add_kernel and their constraints through map_cons_kernel, both unchanged.
 namespace {
 constexpr int AK_MAX_KEYS = SVS_MAP_ADDKF_MAX_NEIGHBORS;
@@ -48,14 +47,7 @@ __device__ __forceinline__ void ak_for_each(const MapK &M, const MapStrK &A, F f
 #pragma unroll
     for (int k = 0; k < AK_UNROLL; ++k) {
       const int i = i0 + k * MB_THREADS + tid;
-      for (int e = ob[k]; e < oe[k]; e += 4) {
-        int kf[4];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) kf[q] = e + q < oe[k] ? M.pt_rows[e + q] : -1;
-#pragma unroll
-        for (int q = 0; q < 4; ++q)
-          if ((unsigned)kf[q] < (unsigned)MAP_MAX_KF) f(i, lr[k], tb[k], kf[q]);
-      }
+      row_each(M.pt_rows, ob[k], oe[k], [&](int kf) { if ((unsigned)kf < (unsigned)MAP_MAX_KF) f(i, lr[k], tb[k], kf); });
     }
   }
 }
@@ -67,7 +59,7 @@ __global__ __launch_bounds__(MB_THREADS) void map_strength_kernel(MapK M, MapStr
   __shared__ int s_str[AK_MAX_KEYS], s_tstar[AK_MAX_KEYS];
   __shared__ int s_w[MB_THREADS / 64];
   const int tid = threadIdx.x;
-  auto rank_of = [&](int id) { return s_rank[id >> 5] + __popc(s_bm[id >> 5] & ((1u << (id & 31)) - 1u)); };
+  auto rank_of = [&](int id) { return bit_rank(s_bm, s_rank, id); };
   // a. empty tables
   s_bm[tid] = 0;
   for (int r = tid; r < AK_MAX_KEYS; r += MB_THREADS) {
@@ -77,8 +69,8 @@ __global__ __launch_bounds__(MB_THREADS) void map_strength_kernel(MapK M, MapStr
   }
   __syncthreads();
   // b. the keys: anchors of the new points (ids the host has checked), observers of E; m = |E|
-  for (int i = tid; i < A.n_new; i += MB_THREADS) { const int a = A.np[i].anchor_id; if ((unsigned)a < (unsigned)MAP_MAX_KF) atomicOr(&s_bm[a >> 5], 1u << (a & 31)); }
-  ak_for_each(M, A, [&](int, int, int, int kf) { atomicOr(&s_bm[kf >> 5], 1u << (kf & 31)); });
+  for (int i = tid; i < A.n_new; i += MB_THREADS) { const int a = A.np[i].anchor_id; if ((unsigned)a < (unsigned)MAP_MAX_KF) bit_set(s_bm, a); }
+  ak_for_each(M, A, [&](int, int, int, int kf) { bit_set(s_bm, kf); });
   int mine = 0;
   for (int i = tid; i < A.n_track; i += MB_THREADS) mine += A.tflag[i] & 1;
   int m;
@@ -137,20 +129,15 @@ __global__ __launch_bounds__(MB_THREADS) void map_strength_kernel(MapK M, MapStr
   __syncthreads();
   // g. the table in ascending id: a lane's own word; the clamp of oldkey and the edge mark where the call inserts
   int n_edge_mine = 0;
-  {
-    uint32_t b2 = bits;
-    for (int r = rank; b2; ++r) {                                 // r < n_keys <= AK_MAX_KEYS
-      const int id = (tid << 5) + __ffs((int)b2) - 1;
-      b2 &= b2 - 1;
-      int s = s_str[r];
-      if (A.clamp && id == A.oldkey) s = max(s, A.thr);
-      s_str[r] = s;
-      const int edge = (A.clamp && s >= A.thr) ? 1 : 0;
-      n_edge_mine += edge;
-      svs_map_key &K = A.keys[r];
-      K.kf_id = id; K.strength = s; K.edge = edge; K.pad_ = 0;
-    }
-  }
+  for_each_set_bit(bits, tid << 5, rank, [&](int id, int r) {      // r < n_keys <= AK_MAX_KEYS
+    int s = s_str[r];
+    if (A.clamp && id == A.oldkey) s = max(s, A.thr);
+    s_str[r] = s;
+    const int edge = (A.clamp && s >= A.thr) ? 1 : 0;
+    n_edge_mine += edge;
+    svs_map_key &K = A.keys[r];
+    K.kf_id = id; K.strength = s; K.edge = edge; K.pad_ = 0;
+  });
   for (int r = n_keys + tid; r < AK_MAX_KEYS; r += MB_THREADS) {
     int4 *z = reinterpret_cast<int4 *>(A.keys + r);
     z[0] = make_int4(0, 0, 0, 0); z[1] = make_int4(0, 0, 0, 0);
@@ -226,68 +213,6 @@ __global__ __launch_bounds__(MB_THREADS) void map_addkf_apply_kernel(MapK M, Map
     n_tr += tot;
   }
 }
-
-__global__ __launch_bounds__(256) void map_get_points_kernel(MapK M, const int32_t *__restrict__ ids, int n, svs_candidate_point *__restrict__ out) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= n) return;
-  const int4 *s4 = reinterpret_cast<const int4 *>(M.pt + ids[i]);
-  int4 *d4 = reinterpret_cast<int4 *>(out + i);
-  d4[0] = s4[0]; d4[1] = s4[1]; d4[2] = s4[2]; d4[3] = s4[3];
-}
-
-struct MapFtK { int kf, cap, n_meas; const svs_ba_edge *meas; int32_t *count, *ids; svs_ba_edge *rec; };
-
-// one workgroup: the keyframe's row as a bitmap over point ids (row 0 of M.mark), ascending ids by popcount prefixes, then the measured store is searched for
-// the keyframe's records, each placed by a binary search of its point in that list
-__global__ __launch_bounds__(MB_THREADS) void map_feature_table_kernel(MapK M, MapFtK A) {
-  __shared__ int s_w[MB_THREADS / 64];
-  const int tid = threadIdx.x;
-  uint32_t *mark = M.mark;
-  const int n_words = (M.pt_hi + 31) >> 5;                        // <= mark_b
-  for (int i = tid; i < n_words; i += MB_THREADS) mark[i] = 0;
-  __syncthreads();
-  const int e1 = M.kf_begin[A.kf + 1];
-  for (int e = M.kf_begin[A.kf] + tid; e < e1; e += MB_THREADS) {
-    const int p = M.kf_rows[e];
-    if ((unsigned)p < (unsigned)M.pt_hi) atomicOr(&mark[p >> 5], 1u << (p & 31));
-  }
-  __syncthreads();
-  int n = 0;
-  for (int base = 0; base < n_words; base += MB_THREADS) {        // block-uniform trip count
-    const int w = base + tid;
-    uint32_t bits = w < n_words ? __hip_atomic_load(&mark[w], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0u;
-    int tot;
-    int pos = n + block_excl_scan(__popc(bits), s_w, tot);
-    while (bits) {
-      const int b = __ffs((int)bits) - 1;
-      bits &= bits - 1;
-      if (pos < A.cap) A.ids[pos] = (w << 5) + b;
-      ++pos;
-    }
-    n += tot;
-  }
-  const int n_c = min(n, A.cap);
-  __syncthreads();
-  for (int i = tid; i < n_c; i += MB_THREADS) {
-    svs_ba_edge e;
-    e.obs[0] = e.obs[1] = e.obs[2] = 0.0; e.info[0] = e.info[1] = e.info[2] = 0.0;
-    e.point = A.ids[i]; e.pose = A.kf; e.anchor = -1; e.pad_ = 0;
-    A.rec[i] = e;
-  }
-  __syncthreads();
-  for (int i = tid; i < A.n_meas; i += MB_THREADS) {
-    const int4 *s4 = reinterpret_cast<const int4 *>(A.meas + i);
-    const int4 q = s4[3];                                          // point, pose, anchor, pad_
-    if (q.y != A.kf) continue;
-    int lo = 0, hi = n_c;
-    while (lo < hi) { const int mid = (lo + hi) >> 1; if (A.ids[mid] < q.x) lo = mid + 1; else hi = mid; }
-    if (lo < n_c && A.ids[lo] == q.x) {
-      int4 *d4 = reinterpret_cast<int4 *>(A.rec + lo);
-      d4[0] = s4[0]; d4[1] = s4[1]; d4[2] = s4[2]; d4[3] = q;
-    }
-  }
-  if (tid == 0) *A.count = n;
-}
 }  // namespace
 
 // ---- host side -----------------------------------------------------------------------------------------------------------------------------------------------
@@ -307,47 +232,43 @@ static int addkf_check_lists(svs_map *m, int n_new, const svs_map_new_point *np,
   return SVS_OK;
 }
 
-// the pieces of the two blocks: upload [head, written by the caller] | new points | track points | flags; download result | keys | kept
-struct AddkfBlocks { size_t o_np, o_tp, o_flag, up_end, o_keys, o_kept, dn_end; };
-static AddkfBlocks addkf_blocks(size_t head, int n_new, int n_track) {
-  AddkfBlocks B{};
-  B.o_np = up_align(head); B.o_tp = B.o_np + up_align((size_t)n_new * sizeof(svs_map_new_point)); B.o_flag = B.o_tp + (size_t)n_track * sizeof(svs_map_track_point);
-  B.up_end = up_align(B.o_flag + (size_t)n_track * sizeof(int32_t));
-  B.o_keys = sizeof(svs_map_strength_result); B.o_kept = B.o_keys + (size_t)AK_MAX_KEYS * sizeof(svs_map_key);
-  B.dn_end = up_align(B.o_kept + (size_t)n_new * sizeof(int32_t));
-  return B;
-}
+// the first part of the two blocks: upload [the keyframe record of svs_map_add_keyframe] | new points | track points | flags; download result | keys | kept.
+// svs_map_add_keyframe declares its second part behind them; up_end / dn_end are where that begins
+struct AddkfBlocks {
+  MapUp up; MapDn dn;
+  MapPiece<kf_up> kf; MapPiece<svs_map_new_point> np; MapPiece<svs_map_track_point> tp; MapPiece<int32_t> flag;
+  MapPiece<svs_map_strength_result> res; MapPiece<svs_map_key> keys; MapPiece<int32_t> kept;
+  size_t up_end, dn_end;
+  AddkfBlocks(svs_map *m, bool with_kf, int n_new, int n_track) : up(m), dn(m) {
+    kf = up.piece<kf_up>(with_kf ? 1 : 0); np = up.piece<svs_map_new_point>(n_new); tp = up.piece<svs_map_track_point>(n_track); flag = up.piece<int32_t>(n_track);
+    up_end = up.end_aligned();
+    res = dn.piece<svs_map_strength_result>(1); keys = dn.piece<svs_map_key>(AK_MAX_KEYS); kept = dn.piece<int32_t>(n_new);
+    dn_end = dn.end_aligned();
+  }
+};
 
 // copies the lists into the staged block (the caller has reserved it and written its head), uploads, runs the strength kernel into the download block and waits
-static int addkf_strength(svs_map *m, const AddkfBlocks &B, int n_new, const svs_map_new_point *np, int n_track, const svs_map_track_point *tp,
-                          const std::vector<int32_t> &flag, int thr, int half_w, int half_h, int oldkey, bool clamp) {
+static int addkf_strength(svs_map *m, AddkfBlocks &B, const svs_map_new_point *np, const svs_map_track_point *tp, const std::vector<int32_t> &flag, int thr, int half_w,
+                          int half_h, int oldkey, bool clamp) {
   svs_ctx *ctx = m->ctx;
-  uint8_t *hs = m->h_up;
-  if (n_new) memcpy(hs + B.o_np, np, (size_t)n_new * sizeof(svs_map_new_point));
-  if (n_track) { memcpy(hs + B.o_tp, tp, (size_t)n_track * sizeof(svs_map_track_point)); memcpy(hs + B.o_flag, flag.data(), (size_t)n_track * sizeof(int32_t)); }
+  B.up.put(B.np, np); B.up.put(B.tp, tp); B.up.put(B.flag, flag.data());
   if (B.up_end)
-    if (int rc = map_upload(m, m->d_up, B.up_end)) return rc;
+    if (int rc = B.up.upload(0, B.up_end)) return rc;
   MapStrK A{};
-  const uint8_t *U = m->d_up.get();
-  A.np = reinterpret_cast<const svs_map_new_point *>(U + B.o_np); A.tp = reinterpret_cast<const svs_map_track_point *>(U + B.o_tp);
-  A.tflag = reinterpret_cast<const int32_t *>(U + B.o_flag);
-  A.n_new = n_new; A.n_track = n_track; A.thr = thr; A.half_w = half_w; A.half_h = half_h; A.oldkey = oldkey; A.clamp = clamp ? 1 : 0;
-  uint8_t *D = m->d_dn.get();
-  A.res = reinterpret_cast<svs_map_strength_result *>(D); A.keys = reinterpret_cast<svs_map_key *>(D + B.o_keys);
-  A.kept = clamp ? reinterpret_cast<int32_t *>(D + B.o_kept) : nullptr;
+  A.np = B.up.dev(B.np); A.tp = B.up.dev(B.tp); A.tflag = B.up.dev(B.flag);
+  A.n_new = (int)B.np.n; A.n_track = (int)B.tp.n; A.thr = thr; A.half_w = half_w; A.half_h = half_h; A.oldkey = oldkey; A.clamp = clamp ? 1 : 0;
+  A.res = B.dn.dev(B.res); A.keys = B.dn.dev(B.keys); A.kept = clamp ? B.dn.dev(B.kept) : nullptr;
   hipLaunchKernelGGL(map_strength_kernel, dim3(1), dim3(MB_THREADS), 0, ctx->stream, m->view(), A);
   SVS_LAUNCH_CHECK(ctx);
-  SVS_HIP(ctx, hipMemcpyAsync(m->h_dn, m->d_dn, B.dn_end, hipMemcpyDeviceToHost, ctx->stream));
-  SVS_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  return SVS_OK;
+  return B.dn.download(0, B.dn_end);
 }
 
 // the key table and the exists mask as the caller gets them
-static void addkf_outputs(const svs_map *m, const AddkfBlocks &B, const std::vector<int32_t> &flag, svs_map_strength_result *h_res, svs_map_key *h_keys, int32_t *h_exists) {
-  const svs_map_strength_result R = *reinterpret_cast<const svs_map_strength_result *>(m->h_dn.get());
+static void addkf_outputs(const AddkfBlocks &B, const std::vector<int32_t> &flag, svs_map_strength_result *h_res, svs_map_key *h_keys, int32_t *h_exists) {
+  const svs_map_strength_result R = *B.dn.host(B.res);
   *h_res = R;
   if (R.over_capacity) memset(h_keys, 0, (size_t)AK_MAX_KEYS * sizeof(svs_map_key));
-  else memcpy(h_keys, m->h_dn.get() + B.o_keys, (size_t)AK_MAX_KEYS * sizeof(svs_map_key));
+  else B.dn.get(B.keys, h_keys);
   if (h_exists)
     for (size_t i = 0; i < flag.size(); ++i) h_exists[i] = R.over_capacity ? 0 : (flag[i] & 1);
 }
@@ -359,13 +280,12 @@ extern "C" int svs_map_compute_strength(svs_map *m, int n_new, const svs_map_new
   std::vector<int32_t> flag;
   if (int rc = addkf_check_lists(m, n_new, h_new, n_track, h_track, covis_thr, &flag)) return rc;
   SVS_DEVICE(ctx);
-  const AddkfBlocks B = addkf_blocks(0, n_new, n_track);
-  if (int rc = map_dn_reserve(m, B.dn_end)) return rc;
+  AddkfBlocks B(m, false, n_new, n_track);
+  if (int rc = B.dn.reserve(B.dn_end)) return rc;
   if (int rc = map_prepare_walk(m, 1)) return rc;
-  uint8_t *hs;
-  if (int rc = map_stage(m, std::max<size_t>(B.up_end, 16), &hs)) return rc;
-  if (int rc = addkf_strength(m, B, n_new, h_new, n_track, h_track, flag, covis_thr, half_width, half_height, -1, false)) return rc;
-  addkf_outputs(m, B, flag, h_res, h_keys, h_track_exists);
+  if (int rc = B.up.reserve(std::max<size_t>(B.up_end, 16))) return rc;
+  if (int rc = addkf_strength(m, B, h_new, h_track, flag, covis_thr, half_width, half_height, -1, false)) return rc;
+  addkf_outputs(B, flag, h_res, h_keys, h_track_exists);
   return SVS_OK;
 }
 
@@ -422,26 +342,29 @@ extern "C" int svs_map_add_keyframe(svs_map *m, const svs_map_add_keyframe_args 
   SVS_DEVICE(ctx);
   // ---- room for both blocks in both directions: nothing is reallocated between the two uploads -------------------------------------------------------------------
   if (!m->d_meas) SVS_HIP(ctx, m->d_meas.alloc((size_t)m->max_obs));
-  const AddkfBlocks B = addkf_blocks(sizeof(kf_up), n_new, n_track);
-  const size_t o_edge = B.up_end, o_req = o_edge + up_align((size_t)edge_bound * sizeof(edge_up)), o_cid = o_req + up_align((size_t)edge_bound * sizeof(cons_req)),
-               o_cT = o_cid + up_align((size_t)a->n_cached * sizeof(int32_t)), up_bytes = o_cT + (size_t)a->n_cached * 12 * sizeof(double);
-  const size_t o_cons = B.dn_end, o_miss = o_cons + (size_t)edge_bound * sizeof(svs_map_constraint_result),
-               dn_bytes = up_align(o_miss + (size_t)edge_bound * missing_cap * sizeof(int32_t));
-  if (int rc = map_dn_reserve(m, dn_bytes)) return rc;
+  AddkfBlocks B(m, true, n_new, n_track);
+  MapUp &up = B.up;
+  MapDn &dn = B.dn;
+  const auto edges = up.piece<edge_up>(edge_bound);
+  const auto reqs = up.piece<cons_req>(edge_bound);
+  const auto cached_ids = up.piece<int32_t>(a->n_cached);
+  const auto cached_T = up.piece<double>(12 * (size_t)a->n_cached);
+  const auto cons = dn.piece<svs_map_constraint_result>(edge_bound);
+  const auto missing = dn.piece<int32_t>((size_t)edge_bound * missing_cap);
+  if (int rc = dn.reserve(dn.end_aligned())) return rc;
   if (int rc = map_prepare_walk(m, 1)) return rc;
-  uint8_t *hs;
-  if (int rc = map_stage(m, up_bytes, &hs)) return rc;
+  if (int rc = up.reserve()) return rc;
   // ---- the first block: the keyframe record | new points | track points | flags; the strength kernel; the small download -------------------------------------------
   {
-    kf_up &u = *reinterpret_cast<kf_up *>(hs);
+    kf_up &u = *up.host(B.kf);
     u.id = newkey; u.disp_stride = a->disp_stride; u.disp = a->disp; u.kf = a->keyframe; u.kf.pad_ = 0;
     memset(u.kf.T_anchor_from_w, 0, sizeof u.kf.T_anchor_from_w);
     memcpy(u.thr, a->fast_thr, sizeof u.thr);
   }
-  if (int rc = addkf_strength(m, B, n_new, a->new_points, n_track, a->track_points, flag, thr, a->half_width, a->half_height, oldkey, true)) return rc;
-  addkf_outputs(m, B, flag, h_res, h_keys, h_track_exists);
+  if (int rc = addkf_strength(m, B, a->new_points, a->track_points, flag, thr, a->half_width, a->half_height, oldkey, true)) return rc;
+  addkf_outputs(B, flag, h_res, h_keys, h_track_exists);
   const svs_map_strength_result R = *h_res;
-  const int32_t *kept = reinterpret_cast<const int32_t *>(m->h_dn.get() + B.o_kept);
+  const int32_t *kept = dn.host(B.kept);
   for (int i = 0; i < n_new; ++i) h_new_kept[i] = R.over_capacity ? 0 : kept[i];
   if (R.over_capacity) return SVS_OK;                             // the map unchanged
   if (R.n_edges > edge_bound) { ctx->err = "svs_map_add_keyframe: the device found more edges than the map has keyframes"; return SVS_ERR_CAPACITY; }
@@ -468,8 +391,8 @@ extern "C" int svs_map_add_keyframe(svs_map *m, const svs_map_add_keyframe_args 
   // ---- the second block, integers: the edge records | the constraint requests | the cached ids and poses ----------------------------------------------------------------
   size_t n_rows = 0;
   {
-    edge_up *eu = reinterpret_cast<edge_up *>(hs + o_edge);
-    cons_req *cr = reinterpret_cast<cons_req *>(hs + o_req);
+    edge_up *eu = up.host(edges);
+    cons_req *cr = up.host(reqs);
     int e = 0;
     for (int r = 0; r < R.n_keys; ++r) {
       if (!h_keys[r].edge) continue;
@@ -484,26 +407,21 @@ extern "C" int svs_map_add_keyframe(svs_map *m, const svs_map_add_keyframe_args 
       ++e;
     }
     m->n_edges += n_e;
-    if (a->n_cached) { memcpy(hs + o_cid, a->cached_ids, (size_t)a->n_cached * sizeof(int32_t)); memcpy(hs + o_cT, a->cached_T, (size_t)a->n_cached * 12 * sizeof(double)); }
+    up.put(cached_ids, a->cached_ids); up.put(cached_T, a->cached_T);
   }
-  uint8_t *U = m->d_up.get();
-  if (up_bytes > o_edge) {
-    SVS_HIP(ctx, hipMemcpyAsync(U + o_edge, hs + o_edge, up_bytes - o_edge, hipMemcpyHostToDevice, ctx->stream));
-    SVS_HIP(ctx, hipEventRecord(m->up_ev, ctx->stream));
-    m->up_pending = true;
-  }
+  if (up.end > edges.off)
+    if (int rc = up.upload(edges.off, up.end)) return rc;
   // ---- apply: the keyframe, the points and pairs, the edges ----------------------------------------------------------------------------------------------------------
   {
     const MapK M = m->view();
-    hipLaunchKernelGGL(map_scatter_kf_kernel, dim3(1), dim3(256), 0, ctx->stream, M, reinterpret_cast<const kf_up *>(U), 1);
+    hipLaunchKernelGGL(map_scatter_kf_kernel, dim3(1), dim3(256), 0, ctx->stream, M, up.dev(B.kf), 1);
     MapApplyK A{};
-    A.np = reinterpret_cast<const svs_map_new_point *>(U + B.o_np); A.tp = reinterpret_cast<const svs_map_track_point *>(U + B.o_tp);
-    A.tflag = reinterpret_cast<const int32_t *>(U + B.o_flag); A.kept = reinterpret_cast<const int32_t *>(m->d_dn.get() + B.o_kept);
+    A.np = up.dev(B.np); A.tp = up.dev(B.tp); A.tflag = up.dev(B.flag); A.kept = dn.dev(B.kept);
     A.n_new = n_new; A.n_track = n_track; A.oldkey = oldkey; A.newkey = newkey;
     memcpy(A.T_rel, a->T_newkey_from_oldkey, sizeof A.T_rel);
     A.log_tail = m->d_log.get() + log0; A.meas_tail = m->d_meas.get() + meas0;
     hipLaunchKernelGGL(map_addkf_apply_kernel, dim3(1), dim3(MB_THREADS), 0, ctx->stream, M, A);
-    if (n_e) hipLaunchKernelGGL(map_edge_add_kernel, dim3(div_up(n_e, 4)), dim3(256), 0, ctx->stream, m->d_edges.get(), reinterpret_cast<const edge_up *>(U + o_edge), n_e);
+    if (n_e) hipLaunchKernelGGL(map_edge_add_kernel, dim3(div_up(n_e, 4)), dim3(256), 0, ctx->stream, m->d_edges.get(), up.dev(edges), n_e);
     SVS_LAUNCH_CHECK(ctx);
   }
   if (n_e == 0) { SVS_HIP(ctx, hipStreamSynchronize(ctx->stream)); return SVS_OK; }
@@ -516,60 +434,15 @@ extern "C" int svs_map_add_keyframe(svs_map *m, const svs_map_add_keyframe_args 
   }
   if (int rc = map_prepare_walk(m, n_e)) return rc;
   MapConsK C{};
-  C.req = reinterpret_cast<const cons_req *>(U + o_req); C.cached_ids = reinterpret_cast<const int32_t *>(U + o_cid); C.cached_T = reinterpret_cast<const double *>(U + o_cT);
-  C.res = reinterpret_cast<svs_map_constraint_result *>(m->d_dn.get() + o_cons); C.missing = reinterpret_cast<int32_t *>(m->d_dn.get() + o_miss); C.missing_cap = missing_cap;
+  C.req = up.dev(reqs); C.cached_ids = up.dev(cached_ids); C.cached_T = up.dev(cached_T);
+  C.res = dn.dev(cons); C.missing = dn.dev(missing); C.missing_cap = missing_cap;
   C.depth = m->d_depth; C.common = m->d_common; C.edges = m->d_edges;
   hipLaunchKernelGGL(map_cons_kernel, dim3(n_e), dim3(MB_THREADS), 0, ctx->stream, m->view(), C);
   SVS_LAUNCH_CHECK(ctx);
-  const size_t got = o_miss + (size_t)n_e * missing_cap * sizeof(int32_t) - o_cons;
-  SVS_HIP(ctx, hipMemcpyAsync(m->h_dn.get() + o_cons, m->d_dn.get() + o_cons, got, hipMemcpyDeviceToHost, ctx->stream));
-  SVS_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  memcpy(h_cons, m->h_dn.get() + o_cons, (size_t)n_e * sizeof(svs_map_constraint_result));
-  if (missing_cap) memcpy(h_missing, m->h_dn.get() + o_miss, (size_t)n_e * missing_cap * sizeof(int32_t));
+  if (int rc = dn.download(cons.off, missing.off + (size_t)n_e * missing_cap * sizeof(int32_t))) return rc;      // what the n_e edges wrote of the room for edge_bound
+  memcpy(h_cons, dn.host(cons), (size_t)n_e * sizeof(svs_map_constraint_result));
+  if (missing_cap) memcpy(h_missing, dn.host(missing), (size_t)n_e * missing_cap * sizeof(int32_t));
   for (int e = 0; e < n_e; ++e)
     if (h_cons[e].status == SVS_CONS_OK) { m->edge_marg[(size_t)slot0 + e] = 1; ++m->n_marg; }
-  return SVS_OK;
-}
-
-extern "C" int svs_map_get_points(svs_map *m, int n, const int32_t *h_ids, svs_candidate_point *h_out) {
-  svs_ctx *ctx = m ? m->ctx : nullptr;
-  SVS_REQUIRE(ctx, m && n >= 0 && (n == 0 || (h_ids && h_out)));
-  for (int i = 0; i < n; ++i) SVS_REQUIRE(ctx, h_ids[i] >= 0 && h_ids[i] < m->max_pt && m->pt_in[h_ids[i]]);
-  if (n == 0) return SVS_OK;
-  SVS_DEVICE(ctx);
-  const size_t bytes = (size_t)n * sizeof(svs_candidate_point);
-  if (int rc = map_dn_reserve(m, bytes)) return rc;
-  uint8_t *hs;
-  if (int rc = map_stage(m, (size_t)n * sizeof(int32_t), &hs)) return rc;
-  memcpy(hs, h_ids, (size_t)n * sizeof(int32_t));
-  if (int rc = map_upload(m, m->d_up, (size_t)n * sizeof(int32_t))) return rc;
-  hipLaunchKernelGGL(map_get_points_kernel, dim3(div_up(n, 256)), dim3(256), 0, ctx->stream, m->view(), reinterpret_cast<const int32_t *>(m->d_up.get()), n,
-                     reinterpret_cast<svs_candidate_point *>(m->d_dn.get()));
-  SVS_LAUNCH_CHECK(ctx);
-  SVS_HIP(ctx, hipMemcpyAsync(m->h_dn, m->d_dn, bytes, hipMemcpyDeviceToHost, ctx->stream));
-  SVS_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  memcpy(h_out, m->h_dn.get(), bytes);
-  return SVS_OK;
-}
-
-extern "C" int svs_map_get_feature_table(svs_map *m, int32_t kf_id, int cap, int32_t *h_count, int32_t *h_point_ids, svs_ba_edge *h_meas) {
-  svs_ctx *ctx = m ? m->ctx : nullptr;
-  SVS_REQUIRE(ctx, m && h_count && cap >= 0 && (cap == 0 || (h_point_ids && h_meas)) && svs_map_has_keyframe(m, kf_id));
-  MAP_CAPACITY(ctx, cap <= m->max_pt);
-  SVS_DEVICE(ctx);
-  const size_t o_ids = 16, o_rec = o_ids + up_align((size_t)cap * sizeof(int32_t)), bytes = o_rec + (size_t)cap * sizeof(svs_ba_edge);
-  if (int rc = map_dn_reserve(m, bytes)) return rc;
-  if (int rc = map_prepare_walk(m, 1)) return rc;
-  MapFtK A{};
-  A.kf = kf_id; A.cap = cap; A.n_meas = m->n_meas; A.meas = m->d_meas;
-  A.count = reinterpret_cast<int32_t *>(m->d_dn.get()); A.ids = reinterpret_cast<int32_t *>(m->d_dn.get() + o_ids); A.rec = reinterpret_cast<svs_ba_edge *>(m->d_dn.get() + o_rec);
-  hipLaunchKernelGGL(map_feature_table_kernel, dim3(1), dim3(MB_THREADS), 0, ctx->stream, m->view(), A);
-  SVS_LAUNCH_CHECK(ctx);
-  SVS_HIP(ctx, hipMemcpyAsync(m->h_dn, m->d_dn, bytes, hipMemcpyDeviceToHost, ctx->stream));
-  SVS_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  const int n = *reinterpret_cast<const int32_t *>(m->h_dn.get()), n_c = std::min(n, cap);
-  *h_count = n;
-  for (int i = 0; i < cap; ++i) h_point_ids[i] = i < n_c ? reinterpret_cast<const int32_t *>(m->h_dn.get() + o_ids)[i] : -1;
-  if (cap) { memcpy(h_meas, m->h_dn.get() + o_rec, (size_t)n_c * sizeof(svs_ba_edge)); memset(h_meas + n_c, 0, (size_t)(cap - n_c) * sizeof(svs_ba_edge)); }
   return SVS_OK;
 }

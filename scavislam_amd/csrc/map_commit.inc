@@ -74,13 +74,18 @@ int svs_map_apply_commit(svs_map *m, MapCommit *c) {
   SVS_DEVICE(ctx);
   // ---- room: the staged block (track records of an explicit call | mask | edge records | constraint requests | cached ids and poses), the download block --------
   if (!m->d_meas) SVS_HIP(ctx, m->d_meas.alloc((size_t)m->max_obs));
-  const size_t o_mask = c->d_track ? 0 : up_align((size_t)n_track * sizeof(svs_map_track_point)), o_edge = o_mask + up_align((size_t)n_track * sizeof(int32_t)),
-               o_req = o_edge + up_align((size_t)n_e * sizeof(edge_up)), o_cid = o_req + up_align((size_t)n_e * sizeof(cons_req)),
-               o_cT = o_cid + up_align((size_t)c->n_cached * sizeof(int32_t)), up_bytes = o_cT + (size_t)c->n_cached * 12 * sizeof(double);
-  const size_t o_miss = (size_t)n_e * sizeof(svs_map_constraint_result), dn_bytes = up_align(o_miss + (size_t)n_e * missing_cap * sizeof(int32_t));
-  if (int rc = map_dn_reserve(m, std::max<size_t>(dn_bytes, 16))) return rc;
-  uint8_t *hs;
-  if (int rc = map_stage(m, std::max<size_t>(up_bytes, 16), &hs)) return rc;
+  MapUp up(m);
+  const auto track = up.piece<svs_map_track_point>(c->d_track ? 0 : n_track);
+  const auto p_mask = up.piece<int32_t>(n_track);
+  const auto edges = up.piece<edge_up>(n_e);
+  const auto reqs = up.piece<cons_req>(n_e);
+  const auto cached_ids = up.piece<int32_t>(c->n_cached);
+  const auto cached_T = up.piece<double>(12 * (size_t)c->n_cached);
+  MapDn dn(m);
+  const auto cons = dn.piece<svs_map_constraint_result>(n_e);
+  const auto missing = dn.piece<int32_t>((size_t)n_e * missing_cap);
+  if (int rc = dn.reserve(std::max<size_t>(dn.end_aligned(), 16))) return rc;
+  if (int rc = up.reserve(16)) return rc;
   // ---- the host's mirrors --------------------------------------------------------------------------------------------------------------------------------------
   const int log0 = m->n_obs, meas0 = m->n_meas, slot0 = m->n_edges;
   for (int i = 0; i < n_track; ++i) {
@@ -93,10 +98,9 @@ int svs_map_apply_commit(svs_map *m, MapCommit *c) {
   // ---- the staged block ----------------------------------------------------------------------------------------------------------------------------------------
   size_t n_rows = 0;
   {
-    if (!c->d_track && n_track) memcpy(hs, c->h_track, (size_t)n_track * sizeof(svs_map_track_point));
-    if (n_track) memcpy(hs + o_mask, mask.data(), (size_t)n_track * sizeof(int32_t));
-    edge_up *eu = reinterpret_cast<edge_up *>(hs + o_edge);
-    cons_req *cr = reinterpret_cast<cons_req *>(hs + o_req);
+    up.put(track, c->h_track); up.put(p_mask, mask.data());
+    edge_up *eu = up.host(edges);
+    cons_req *cr = up.host(reqs);
     for (int e = 0; e < n_e; ++e) {
       const int o = c->h_edge_kf[e], kf1 = c->other_first ? o : kf, kf2 = c->other_first ? kf : o;
       eu[e].slot = slot0 + e; eu[e].lo = std::min(o, kf); eu[e].hi = std::max(o, kf); eu[e].strength = c->h_edge_strength[e]; eu[e].type = c->edge_type; eu[e].pad_ = 0;
@@ -109,19 +113,18 @@ int svs_map_apply_commit(svs_map *m, MapCommit *c) {
       m->edge_slot[edge_key(o, kf)] = slot0 + e; m->edge_marg[(size_t)slot0 + e] = 0;
     }
     m->n_edges += n_e;
-    if (c->n_cached) { memcpy(hs + o_cid, c->h_cached_ids, (size_t)c->n_cached * sizeof(int32_t)); memcpy(hs + o_cT, c->h_cached_T, (size_t)c->n_cached * 12 * sizeof(double)); }
+    up.put(cached_ids, c->h_cached_ids); up.put(cached_T, c->h_cached_T);
   }
-  if (up_bytes)
-    if (int rc = map_upload(m, m->d_up, up_bytes)) return rc;
-  uint8_t *U = m->d_up.get();
+  if (up.end)
+    if (int rc = up.upload()) return rc;
   // ---- apply: the pairs, the edges -------------------------------------------------------------------------------------------------------------------------------
   if (n_add) {
     MapCommitK A{};
-    A.tp = c->d_track ? c->d_track : reinterpret_cast<const svs_map_track_point *>(U); A.mask = reinterpret_cast<const int32_t *>(U + o_mask);
+    A.tp = c->d_track ? c->d_track : up.dev(track); A.mask = up.dev(p_mask);
     A.n_track = n_track; A.kf = kf; A.log_tail = m->d_log.get() + log0; A.meas_tail = m->d_meas.get() + meas0;
     hipLaunchKernelGGL(map_commit_append_kernel, dim3(1), dim3(MB_THREADS), 0, ctx->stream, A);
   }
-  if (n_e) hipLaunchKernelGGL(map_edge_add_kernel, dim3(div_up(n_e, 4)), dim3(256), 0, ctx->stream, m->d_edges.get(), reinterpret_cast<const edge_up *>(U + o_edge), n_e);
+  if (n_e) hipLaunchKernelGGL(map_edge_add_kernel, dim3(div_up(n_e, 4)), dim3(256), 0, ctx->stream, m->d_edges.get(), up.dev(edges), n_e);
   SVS_LAUNCH_CHECK(ctx);
   c->n_pairs_added = n_add;
   if (c->h_track_added)
@@ -136,15 +139,14 @@ int svs_map_apply_commit(svs_map *m, MapCommit *c) {
   }
   if (int rc = map_prepare_walk(m, n_e)) return rc;
   MapConsK C{};
-  C.req = reinterpret_cast<const cons_req *>(U + o_req); C.cached_ids = reinterpret_cast<const int32_t *>(U + o_cid); C.cached_T = reinterpret_cast<const double *>(U + o_cT);
-  C.res = reinterpret_cast<svs_map_constraint_result *>(m->d_dn.get()); C.missing = reinterpret_cast<int32_t *>(m->d_dn.get() + o_miss); C.missing_cap = missing_cap;
+  C.req = up.dev(reqs); C.cached_ids = up.dev(cached_ids); C.cached_T = up.dev(cached_T);
+  C.res = dn.dev(cons); C.missing = dn.dev(missing); C.missing_cap = missing_cap;
   C.depth = m->d_depth; C.common = m->d_common; C.edges = m->d_edges;
   hipLaunchKernelGGL(map_cons_kernel, dim3(n_e), dim3(MB_THREADS), 0, ctx->stream, m->view(), C);
   SVS_LAUNCH_CHECK(ctx);
-  SVS_HIP(ctx, hipMemcpyAsync(m->h_dn, m->d_dn, o_miss + (size_t)n_e * missing_cap * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
-  SVS_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  memcpy(c->h_cons, m->h_dn.get(), (size_t)n_e * sizeof(svs_map_constraint_result));
-  if (missing_cap) memcpy(c->h_missing, m->h_dn.get() + o_miss, (size_t)n_e * missing_cap * sizeof(int32_t));
+  if (int rc = dn.download()) return rc;
+  dn.get(cons, c->h_cons);
+  dn.get(missing, c->h_missing);
   for (int e = 0; e < n_e; ++e)
     if (c->h_cons[e].status == SVS_CONS_OK) { m->edge_marg[(size_t)slot0 + e] = 1; ++m->n_marg; }
   return SVS_OK;

@@ -1,4 +1,4 @@
-// nbh_map.h -- what frontend.hip and map.hip share: the request by which a front-end stream asks the device-resident map (map.hip) for its neighbourhood list
+// nbh_map.h -- what frontend.hip and map.hip share: the request by which a front-end stream asks the device-resident map (map.hip: map_nbh.inc) for its neighbourhood list
 // (Backend::computeNeighborhood from the vertex list onwards, backend.cpp:311-386), and the places of the front end's own tables the map's walk writes.
 // Neither translation unit reaches into the other's handle.
 #pragma once

@@ -1,5 +1,5 @@
 // nbr_map.h -- what frontend.hip and map.hip share for svs_frontend_set_neighborhood_from_root: the request by which a front-end stream asks the device-resident
-// map (map.hip) for its whole neighbourhood from a root id (Backend::computeNeighborhood, backend.cpp:244-386), and the places of the front end's own tables the
+// map (map.hip: map_nbh.inc) for its whole neighbourhood from a root id (Backend::computeNeighborhood, backend.cpp:244-386), and the places of the front end's own tables the
 // map's kernels write -- the candidate list and keyframe slots as in nbh_map.h, and the resident vertex table of the keyframe decision (keyframe.h).
 // Neither translation unit reaches into the other's handle.
 #pragma once

@@ -1,5 +1,5 @@
 // reg_map.h -- what register.hip and map.hip share: the request record the registration chain reads, and the interface through which the device-resident
-// map (map.hip) builds such records, with their tables, in the registrar's own staging block.
+// map (map.hip: map_request.inc) builds such records, with their tables, in the registrar's own staging block.
 #pragma once
 #include "common.h"
 

@@ -14,7 +14,7 @@
 // A request that left at an exit has its candidate records turned into kf_index = -1, which the matcher answers with SVS_MATCH_NO_ANCHOR: the later stages
 // run over it and find nothing.  Requests of a batch are padded to the longest source list with such records.
 // Not pinned by the reference's binaries (backend.cpp is not among them): the yardstick of the cull and the counting is tests/register_model.py.
-// svs_reg_register_map_batch (at the end) runs the same chain (reg_chain) behind requests that the device-resident map (map.hip, reg_map.h) builds from ids in this
+// svs_reg_register_map_batch (at the end) runs the same chain (reg_chain) behind requests that the device-resident map (map.hip: map_request.inc, through reg_map.h) builds from ids in this
 // handle's staging block; the stateless call stages them from the host.
 // svs_reg_commit (behind it) is registerKeyframes / addLoopClosure for one request of such a batch: reg_commit_kernel builds the track list and the edge list from the
 // chain's outputs where they lie, the map applies them (map_commit.inc through reg_map.h).
@@ -741,7 +741,7 @@ extern "C" int svs_reg_register_batch(svs_reg *g, int n_requests, const svs_reg_
   return SVS_OK;
 }
 
-// ---- requests by ids against a device-resident map (map.hip): the staged bytes are the id lists, the map's walk builds the tables where the stateless call stages
+// ---- requests by ids against a device-resident map (map.hip: map_request.inc): the staged bytes are the id lists, the map's walk builds the tables where the stateless call stages
 // them -- at the handle's capacities, since the sizes are only known on the device; a request's outputs do not depend on the padding -- and the chain above runs
 extern "C" int svs_reg_register_map_batch(svs_reg *g, svs_map *map, int n_requests, const svs_reg_map_request *req, const svs_reg_params *prm, svs_reg_result *h_res,
                                           int32_t *h_cand_src, svs_match_result *h_matches, int32_t *h_status_pass1, int32_t *h_accepted,

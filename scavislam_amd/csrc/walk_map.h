@@ -1,5 +1,5 @@
 // walk_map.h -- what map.hip keeps for the pose graph's walks (map_walk.inc): the strength-ordered adjacency of the keyframes, built on the device from the edge
-// records, and the work space of the breadth-first searches.  map.hip holds one MapWalkState and includes map_walk.inc behind its own exports; nothing else
+// records, and the work space of the breadth-first searches.  map.hip holds one MapWalkState and includes map_walk.inc behind map_edges.inc; nothing else
 // sees either.
 #pragma once
 #include "common.h"

@@ -413,6 +413,45 @@ def test_every_refusal_leaves_the_map_unchanged(gpu_ctx, blank):
 
 
 @pytest.mark.gpu
+def test_feature_table_at_the_edges_of_the_bitmap_words_and_of_the_compaction_block(gpu_ctx, blank):
+    """The read-back lists a bitmap over point ids, one trip per 512 words of 32 ids: its second trip starts at point id 16384.  A few dozen points with ids on
+    both sides of every word edge and of that block edge, measured and unmeasured pairs mixed; the whole table, and every capacity below its length (the entries
+    at or behind it are counted, not written), against the pairs as they were given (records: slam_graph.cpp:1010-1015 through ba_map_model.info_from_level)"""
+    import ba_map_model as BM
+    from scavislam_amd.ctypes_types import BA_EDGE_DTYPE, CANDIDATE_DTYPE
+    from scavislam_amd.register import ResidentMap
+    MAXP, KF, OTHER = 20000, 40, 3
+    pt_ids = [0, 31, 32, 63, 64, 16383, 16384, 16385, MAXP - 1] + list(range(100, 124))
+    rng = np.random.default_rng(5)
+    d = ResidentMap(gpu_ctx[0], max_keyframes=64, max_points=MAXP, max_observations=256)
+    try:
+        d.add_keyframes([OTHER, KF], _kf_records(blank, [AM.I12] * 2), [_disp(blank)] * 2, [THR] * 2)
+        pts = np.zeros(len(pt_ids), CANDIDATE_DTYPE)
+        pts["xyz_anchor"], pts["kf_index"] = [0.0, 0.0, 4.0], OTHER
+        d.add_points(pt_ids, pts)
+        mine = [p for i, p in enumerate(pt_ids) if i < 9 or i % 3]                       # every edge id, two thirds of the rest
+        measured = [p for i, p in enumerate(mine) if i % 4 != 1]
+        center, level = rng.uniform(1, 600, (len(measured), 3)), rng.integers(0, 3, len(measured)).astype(np.int32)
+        order = rng.permutation(len(measured))
+        d.add_measured_observations([measured[i] for i in order], [KF] * len(measured), center[order], level[order])
+        d.add_observations([p for p in mine if p not in measured], [KF] * (len(mine) - len(measured)))
+        d.add_measured_observations(pt_ids[::2], [OTHER] * len(pt_ids[::2]), np.ones((len(pt_ids[::2]), 3)), np.zeros(len(pt_ids[::2]), np.int32))
+        want = np.zeros(len(mine), BA_EDGE_DTYPE)
+        want["point"], want["pose"], want["anchor"] = sorted(mine), KF, -1
+        for p, c, l in zip(measured, center, level):
+            i = sorted(mine).index(p)
+            want["obs"][i], want["info"][i], want["anchor"][i] = c, BM.info_from_level([l])[0], 0
+        at = sorted(mine).index(16384)                                                    # the first id of the lister's second trip
+        assert max(mine) == MAXP - 1 and {16383, 16385} <= set(mine) and set(measured) & {16384, 16385, MAXP - 1}
+        for cap in (None, len(mine), len(mine) - 1, at + 1, at, at - 1, 1, 0):
+            ids, rec, n = d.get_feature_table(KF, cap)
+            k = len(mine) if cap is None else cap
+            assert n == len(mine) and ids.tolist() == sorted(mine)[:k] and rec.tobytes() == want[:k].tobytes(), cap
+    finally:
+        d.close()
+
+
+@pytest.mark.gpu
 def test_cpp_adaptor_add_keyframe(gpu_ctx, tmp_path):
     """tests/cpp/addkf_smoke.cpp: BackendMap::addFirstKeyframe / addKeyframe"""
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))

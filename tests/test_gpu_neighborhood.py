@@ -186,7 +186,7 @@ def test_built_list_equals_the_model(list_fe, both, scene, missing):
 
 
 # ---- 2. the bitmaps' word and block edges ------------------------------------------------------------------------------------------------------------------------
-def test_ids_at_the_edges_of_the_bitmap_words_and_of_the_compaction_block(gpu_ctx, device_scene, list_fe, scene):
+def test_ids_at_the_edges_of_the_bitmap_words_and_of_the_compaction_block(gpu_ctx, device_scene, list_fe, frames, scene):
     from test_gpu_register_map import DeviceMap
     MAXP, MAXK = 20000, 16384
     kf_ids = [0, 31, 32, MAXK - 1]
@@ -208,6 +208,13 @@ def test_ids_at_the_edges_of_the_bitmap_words_and_of_the_compaction_block(gpu_ct
         for vertex in ([0], [31], [32], [MAXK - 1], [31, MAXK - 1], [32, 0, 31, MAXK - 1]):
             outs, wants = _check(list_fe, dmap, model, [_request(0, vertex, slots)])
         assert set(pt_ids) == set(int(p) for p in wants[0]["point_ids"]) and wants[0]["n_no_slot"] > 0      # the last list reaches every point
+        # a list that ends inside the compaction's second trip (room for 31 of the 33: id 16384 would be the last to fit): counted, over capacity, nothing written
+        small = _make_fe(gpu_ctx[0], frames, scene, {k: M.I12 for k in MM.scene_ids(scene)}, max_points=31)
+        try:
+            outs, wants = _check(small, dmap, model, [_request(0, [32, 0, 31, MAXK - 1], slots)])
+            assert wants[0]["over_capacity"] and outs[0]["n_map_points"] == len(pt_ids)
+        finally:
+            small.close()
     finally:
         dmap.close()
 

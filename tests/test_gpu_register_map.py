@@ -281,6 +281,50 @@ def test_a_request_over_the_registrars_capacity_is_answered_alone(gpu_ctx, scene
         reg.close()
 
 
+def test_point_ids_at_the_edges_of_the_bitmap_words_and_of_the_compaction_block(gpu_ctx, registrar, device_scene, scene):
+    """The source list is a bitmap over point ids, listed one trip per 512 words of 32 ids: the second trip starts at point id 16384.  The scene's first 33 points
+    under ids on both sides of every word edge and of that block edge, in a map with room for 20 000 points: both modes against the stateless call, and a registrar
+    whose source capacity ends inside the second trip (31 of 33: the entry of id 16384 is the last one written) is answered over capacity"""
+    from scavislam_amd.ctypes_types import REG_OVER_CAPACITY
+    from scavislam_amd.register import KeyframeRegistrar
+    MAXP = 20000
+    pt_ids = [0, 31, 32, 63, 64, 16383, 16384, 16385, MAXP - 1] + list(range(100, 124))
+    ids = MM.scene_ids(scene)
+    n = len(ids)
+    model, dmap = MM.MapModel(), DeviceMap(gpu_ctx[0], device_scene, scene, max_keyframes=64, max_points=MAXP, max_observations=4096)
+    small = None
+    try:
+        pts = np.array(scene["src"][:len(pt_ids)])
+        pts["kf_index"] = [ids[int(e)] for e in pts["kf_index"]]
+        op, ok = [], []
+        for i, p in enumerate(pt_ids):
+            for e in scene["obs_kf"][scene["obs_begin"][i]:scene["obs_begin"][i + 1]]:
+                op.append(p); ok.append(ids[int(e)])
+            op.append(p); ok.append(MM.ALL_ID)
+        for m in (model, dmap):
+            m.add_keyframes(ids + [MM.ALL_ID], [scene["kf_T"][e] for e in range(n)] + [scene["kf_T"][1]], entry=list(range(n)) + [1])
+            m.add_points(pt_ids, pts)
+            m.add_observations(op, ok)
+            m.set_window([ids[e] for e in range(n) if int(scene["flags"][e]) & M.IN_WINDOW])
+        qs = [MM.scene_request(scene, M.LOCAL), MM.scene_request(scene, M.LOOP)]
+        for q in qs:                                                                     # every point is a source point of either request
+            assert model.source_points(q["mode"], q["root_kf"], q["walk_kf"], q["direct_kf"]) == sorted(pt_ids)
+        outs, _ = _check_against_stateless(registrar, device_scene, model, dmap, scene, qs)
+        assert all(o.status != REG_OVER_CAPACITY for o in outs) and {16384, 16385, MAXP - 1} & set(int(p) for p in outs[0].point_ids)
+        small = KeyframeRegistrar(gpu_ctx[0], CAM, max_requests=2, max_points=31, max_keyframes=8, max_observers=4096)
+        outs, raws, lists = _by_map(small, dmap, qs)
+        for i in range(2):
+            res = np.frombuffer(raws[i][0], np.int32)
+            assert outs[i].status == REG_OVER_CAPACITY and res[0] == REG_OVER_CAPACITY and not res[1:].any()
+            for blob in raws[i][1:] + lists[i][:2]:
+                assert not np.frombuffer(blob, np.uint8).any()
+            assert lists[i][2] == 0
+    finally:
+        if small is not None:
+            small.close()
+        dmap.close()
+
+
 # ---- 6. refusals -----------------------------------------------------------------------------------------------------------------------------------------------------
 def test_refused_updates_and_requests_leave_the_map_as_it_was(gpu_ctx, registrar, device_scene, scene, both):
     from scavislam_amd.capi import SvsError
