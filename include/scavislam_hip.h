@@ -264,7 +264,10 @@ typedef struct {           /* OptimizerStatistics, pose_optimizer.h:59-98 */
   double initial_chi2, chi2, max_err;
   int32_t num_obs;
   int32_t status;          /* 0 ok; 1 empty observation list (the reference asserts); 2 residual became NaN (the reference throws);
-                              3 fewer than min_obs observations: nothing done */
+                              3 fewer than min_obs observations: nothing done (num_obs and initial_chi2 == chi2, max_err of the list at the pose as given).
+                              Status 1 and 3 leave d_T_io untouched.  Status 2 stores the last ACCEPTED pose and its chi2 / max_err; the reference throws and the
+                              test suite's CPU restatement of the loop hands back the INPUT pose.  The two coincide where the NaN is in the input (an observation or a point),
+                              the one case the tests cover: no trial is ever accepted then */
 } svs_pose_opt_stats;
 /* obs_list / point_list = the SVS_MATCH_OK entries of d_results[b][0..n) in order (several svs_match outputs may be
    concatenated, as matchAndTrack appends into one TrackData); d_T_io[b][12] = T_cur_from_actkey in/out */

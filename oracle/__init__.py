@@ -468,6 +468,35 @@ def motion_only(results, cam, T, prm=None):
     return Tio.reshape(3, 4), st
 
 
+# svs_mo_trial: one LM trial of svs_ref_motion_only_trace
+MO_TRIAL_DTYPE = np.dtype([("chi2", "<f8"), ("new_chi2", "<f8"), ("rho", "<f8"), ("step", "<f8"), ("b_max", "<f8"), ("delta", "<f8", 6),
+                           ("accepted", "<i4"), ("pad_", "<i4")])
+assert MO_TRIAL_DTYPE.itemsize == 96
+MO_TIE = 1e-11      # |rho| <= MO_TIE * chi2: an accept test that another summation order may decide the other way
+
+
+def motion_only_trace(results, cam, T, prm=None):
+    """motion_only() reporting its LM trials: returns (T_new 3x4, PoseOptStats, MO_TRIAL_DTYPE[number of trials]).  T_new and the statistics are the bits of
+    motion_only(): the same loop (svs_ref_motion_only_trace)."""
+    prm = prm or PoseOptParams.reference()
+    res = np.ascontiguousarray(results, MATCH_RESULT_DTYPE)
+    Tio = np.array(T, np.float64).reshape(12).copy()
+    st = PoseOptStats()
+    cap = 6 * max(int(prm.num_iter), 0) + 6      # an iteration ends after at most five rejections and one accepted trial
+    trials = np.zeros(cap, MO_TRIAL_DTYPE)
+    nt = C.c_int(0)
+    lib().svs_ref_motion_only_trace(_p(res), len(res), C.byref(cam), C.byref(prm), _p(Tio), C.byref(st), _p(trials), cap, C.byref(nt))
+    assert nt.value <= cap
+    return Tio.reshape(3, 4), st, trials[:nt.value].copy()
+
+
+def motion_only_exposure(trials):
+    """the largest step among the trials whose accept test is a near-tie (|rho| <= MO_TIE * chi2), 0 if there is none: how far the final pose may differ between
+    two exact-arithmetic equals of the loop"""
+    tie = np.abs(trials["rho"]) <= MO_TIE * trials["chi2"]
+    return float(trials["step"][tie].max()) if tie.any() else 0.0
+
+
 def ref_motion_only(results, cam, T, prm=None):
     """The reference's own PoseOptimizer::calcFastMotionOnly (oracle/_ref/libsvs_ref_pose.so); same arguments as motion_only()."""
     prm = prm or PoseOptParams.reference()

@@ -322,6 +322,19 @@ typedef struct {           /* OptimizerStatistics, pose_optimizer.h:59-98 */
 } svs_pose_opt_stats;
 int svs_ref_motion_only(const svs_match_result *res, int n, const svs_cam *cam, const svs_pose_opt_params *prm, double *T_io,
                         svs_pose_opt_stats *st);
+/* The same loop, reporting its LM trials: one record per trial in order, at most `cap` of them stored, *n_trials = how many the loop made
+   (a status-2 exit stores no record for the NaN trial).  The records read the loop and decide nothing in it: results are the bits of
+   svs_ref_motion_only, which is this function without a record array.  A trial with |rho| <= 1e-11 chi2 is one whose accept test any other
+   summation order may decide the other way; `step` of the largest such trial is how far the final pose may then differ. */
+typedef struct {
+  double chi2, new_chi2, rho;   /* accept test: rho = chi2 - new_chi2 > 0 */
+  double step;                  /* max |delta_c| of the trial's step */
+  double b_max;                 /* max |B_c| of its right-hand side */
+  double delta[6];              /* the step itself: T_trial = exp(delta) T */
+  int32_t accepted, pad_;
+} svs_mo_trial;
+int svs_ref_motion_only_trace(const svs_match_result *res, int n, const svs_cam *cam, const svs_pose_opt_params *prm, double *T_io,
+                              svs_pose_opt_stats *st, svs_mo_trial *trials, int cap, int *n_trials);
 
 /* ---- StereoFrontend::processMatchedPoints (stereo_frontend.cpp:834-974): reprojection gate at the refined pose,
    PointStatistics counters, pyramid-level positions, track-length sum; serial, in obs_list order ---------------- */

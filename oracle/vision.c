@@ -901,11 +901,12 @@ static double mo_weighted_sq(double *f, int robust, double b) {      /* f *= w; 
   }
   return f[0] * f[0] + f[1] * f[1] + f[2] * f[2];
 }
-int svs_ref_motion_only(const svs_match_result *res, int n, const svs_cam *cam, const svs_pose_opt_params *prm, double *T_io,
-                        svs_pose_opt_stats *st) {
+int svs_ref_motion_only_trace(const svs_match_result *res, int n, const svs_cam *cam, const svs_pose_opt_params *prm, double *T_io,
+                              svs_pose_opt_stats *st, svs_mo_trial *trials, int cap, int *n_trials) {
   const double EPS = 1e-10;
   double T[12], Tn[12], chi2 = 0, max_err = 0, norm_max_A = 0, nu = 2;
-  int num_obs = 0, stop = 0, trial = 0;
+  int num_obs = 0, stop = 0, trial = 0, nt = 0;
+  if (n_trials) *n_trials = 0;
   memcpy(T, T_io, sizeof T);
   for (int i = 0; i < n; ++i) {
     if (res[i].status != SVS_MATCH_OK) continue;
@@ -951,6 +952,17 @@ int svs_ref_motion_only(const svs_match_result *res, int n, const svs_cam *cam, 
       }
       if (isnan(new_chi2)) { st->status = 2; st->chi2 = chi2; st->max_err = max_err; return 2; }      /* throw runtime_error("Res is NaN!") */
       rho = chi2 - new_chi2;
+      if (trials && nt < cap) {                               /* the record reads the trial; it decides nothing */
+        svs_mo_trial *t = &trials[nt];
+        t->chi2 = chi2; t->new_chi2 = new_chi2; t->rho = rho; t->step = 0; t->b_max = 0; t->accepted = rho > 0; t->pad_ = 0;
+        for (int c = 0; c < 6; ++c) {
+          if (fabs(delta[c]) > t->step) t->step = fabs(delta[c]);
+          if (fabs(B[c]) > t->b_max) t->b_max = fabs(B[c]);
+          t->delta[c] = delta[c];
+        }
+      }
+      ++nt;
+      if (n_trials) *n_trials = nt;
       if (rho > 0) {
         memcpy(T, Tn, sizeof T);
         chi2 = new_chi2; max_err = new_max_err;
@@ -970,6 +982,10 @@ int svs_ref_motion_only(const svs_match_result *res, int n, const svs_cam *cam, 
   memcpy(T_io, T, sizeof T);
   st->chi2 = chi2; st->max_err = max_err;
   return 0;
+}
+int svs_ref_motion_only(const svs_match_result *res, int n, const svs_cam *cam, const svs_pose_opt_params *prm, double *T_io,
+                        svs_pose_opt_stats *st) {
+  return svs_ref_motion_only_trace(res, n, cam, prm, T_io, st, NULL, 0, NULL);
 }
 
 /* StereoFrontend::processMatchedPoints, stereo_frontend.cpp:834-974.  The list/hash-map/draw bookkeeping of the original

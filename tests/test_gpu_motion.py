@@ -5,24 +5,9 @@ import ctypes as C
 import numpy as np
 import pytest
 
+from motion_cases import synthetic_results as _synthetic_results      # (the generator moved there: tests/test_gpu_motion_edges.py builds its cases from it too)
+
 pytestmark = pytest.mark.gpu
-
-
-def _synthetic_results(rng, cam, T_true, n, outliers=0.1, n_fail=30):
-    """matcher-like result records: points in the active keyframe frame, stereo observations in the current frame."""
-    from scavislam_amd.ctypes_types import MATCH_RESULT_DTYPE
-    res = np.zeros(n, MATCH_RESULT_DTYPE)
-    xyz = np.stack([rng.uniform(-3, 3, n), rng.uniform(-1.5, 1.5, n), rng.uniform(2.5, 15, n)], 1)
-    p = xyz @ T_true[:, :3].T + T_true[:, 3]
-    u = p[:, 0] / p[:, 2] * cam["f"] + cam["cx"]
-    v = p[:, 1] / p[:, 2] * cam["f"] + cam["cy"]
-    ur = (p[:, 0] - cam["b"]) / p[:, 2] * cam["f"] + cam["cx"]
-    obs = np.stack([u, v, ur], 1) + rng.normal(0, 0.4, (n, 3))
-    bad = rng.random(n) < outliers
-    obs[bad] += rng.uniform(-25, 25, (bad.sum(), 3))
-    res["obs"], res["xyz_actkey"] = obs, xyz
-    res["status"][rng.choice(n, n_fail, replace=False)] = rng.integers(1, 7, n_fail)      # matcher rejections are skipped
-    return res
 
 
 def _run(gpu_ctx, cam, res_batch, T0, prm=None):
@@ -45,8 +30,8 @@ def _run(gpu_ctx, cam, res_batch, T0, prm=None):
 
 @pytest.mark.parametrize("shape,n", [("fused", 400), ("fused", 2600), ("legacy", 400)])
 def test_motion_only_matches_oracle(gpu_ctx, shape, n):
-    """the fused kernel with lists short and longer than what its registers hold (4 observations per lane of 512: the rest is re-read through the index
-    list), and the record-walking kernel of rounds 1-2"""
+    """the fused kernel with lists short and longer than what its registers hold (6 observations per lane of 256 = 1536: the rest is re-read through the
+    index list), and the record-walking kernel of rounds 1-2.  (The edges of both: tests/test_gpu_motion_edges.py.)"""
     import oracle as O
     from scavislam_amd import synth
     rng = np.random.default_rng(17)
