@@ -54,8 +54,7 @@ struct LevelArgs {
 
 // The same with the address space of every pointer spelled out (global memory).  The flat tracker kernel's sweep takes its operands out of LDS
 // (track_pass_from_lds), and a pointer that has been through memory is a flat pointer to the compiler -- every access a flat_load that also probes the LDS
-// aperture and counts on both wait counters.
-#define SVS_AS1 __attribute__((address_space(1)))
+// aperture and counts on both wait counters (SVS_AS1: devutil.h).
 typedef float svs_f4 __attribute__((ext_vector_type(4)));
 struct LevelArgsG {
   const SVS_AS1 float *cloud; const SVS_AS1 uint8_t *prev; const SVS_AS1 float *cur, *dx, *dy;

@@ -136,6 +136,18 @@ __device__ __forceinline__ void wave_lds_sync() { __builtin_amdgcn_wave_barrier(
 template <class T>
 __device__ __forceinline__ T ld_unaligned(const uint8_t *p) { T v; __builtin_memcpy(&v, p, sizeof(T)); return v; }
 
+// A pointer with its address space spelled out: SVS_AS1 global memory, SVS_AS3 the LDS.  A pointer that has been through memory, the LDS or an asm statement is a
+// flat pointer to the compiler -- every access a flat_load that also probes the LDS aperture and counts on BOTH wait counters, so that a wait for the LDS waits for the
+// memory requests in flight as well.  With the address space in the type the access is a global_load (vmcnt alone) or a ds_read (lgkmcnt alone) whatever the pointer
+// has been through.
+#define SVS_AS1 __attribute__((address_space(1)))
+#define SVS_AS3 __attribute__((address_space(3)))
+template <class T>
+__device__ __forceinline__ T ld_unaligned(const SVS_AS1 uint8_t *p) {
+  typedef T unaligned_t __attribute__((aligned(1)));
+  return *(const SVS_AS1 unaligned_t *)p;
+}
+
 // index i of an axis of n samples under cv::BORDER_REFLECT_101
 __device__ __forceinline__ int reflect101(int i, int n) {
   if (n == 1) return 0;
