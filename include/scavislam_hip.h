@@ -124,8 +124,8 @@ int svs_ctx_sync(svs_ctx *ctx);
    tracker, "trk_regs" its register budget (1: one workgroup per CU, 2: two), "full_nwg" workgroups per stream of the
    full-resolution tracker.  The environment (SVS_TRK_NWG, SVS_TRK_ONE_PER_CU / SVS_TRK_TWO_PER_CU, SVS_FULL_NWG) only
    supplies the initial values, read once by svs_ctx_create.  A/B switches between kernels that return the same results:
-   "match_legacy" (0: four candidate points per wave where the search window allows it, 1: the round-1/2 kernel, 2: one wave per
-   point with the lean scan), "mo_legacy" (1: the record-walking motion-only kernel), "fe_overlap" (default 1: the one-call
+   "match_legacy" (0: four candidate points per wave where the search window allows it, 1: match_kernel, the round-1/2 kernel, 2: match_kernel2,
+   one wave per point with the lean scan, where windows are narrower than a FAST cell), "mo_legacy" (1: the record-walking motion-only kernel), "fe_overlap" (default 1: the one-call
    front end enqueues FAST / block matching on a side stream beside the dense tracker; 0: everything on the context's stream),
    "xcd_swizzle" (default 1: tile kernels whose neighbours share image lines -- FAST score, pyramid, block matching, the four-points-per-wave matcher -- take their
    blocks in XCD-contiguous order; 0: the dispatcher's round robin), "fast_floor" (default 1: the FAST score kernel scores and lists only from the lowest threshold a

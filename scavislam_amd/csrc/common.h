@@ -28,7 +28,7 @@ struct svs_ctx {
   int trk_balance = 1;        // "trk_balance" / SVS_TRK_BALANCE, big batches (dense.hip, BAL): 1 = grid order by the last frame's LM work, 0 = stream order
   int trk_regs = 0;           // SVS_TRK_ONE_PER_CU (1) / SVS_TRK_TWO_PER_CU (2): register budget of that tracker (0 = automatic)
   int full_nwg = 0;           // SVS_FULL_NWG: workgroups per stream of the full-resolution tracker (0 = automatic)
-  int match_legacy = 0;       // "match_legacy": 0 = four points per wave (match_kernel3), 1 = the round-1/2 kernel (one wave per point, ballots), 2 = one wave per point with the lean scan
+  int match_legacy = 0;       // "match_legacy": 0 = four points per wave (match_kernel3, match_group.inc), 1 = the round-1/2 kernel (match_kernel: one wave per point, ballots), 2 = one wave per point with the lean scan (match_kernel2; both in match_wave.inc)
   int mo_spec = 1;            // "mo_spec": calcFastMotionOnly's trials behind a rejection run a chi2-only sweep (the full one follows if the trial is accepted after all); 0: always full
   int fe_fuse_tail = 1;       // "fe_fuse_tail": the one-call front end runs the gate and the dense clouds inside the refinement kernel (0: four more launches)
   int match_order = 1;        // "match_order": match_kernel3 takes the points of a stream in image order (counting sort by cell of the predicted position), 0: list order
@@ -46,7 +46,7 @@ struct svs_ctx {
                               // stream's FAST no longer finds the tail to run in), 2.63 at K = 10
   int trk_cont_slots = 0;     // "trk_cont_slots": workgroup slots the continuation launch sizes itself for (0: two per CU)
   // set by the one-call front end around svs_match (few keyframes): the tracked pose / the active keyframe's pose per stream, from which the matcher's prediction kernel forms
-  // T_cur_from_w / T_w_from_actkey and the per-keyframe relative poses itself (match.hip) -- two small launches less between tracker and matcher
+  // T_cur_from_w / T_w_from_actkey and the per-keyframe relative poses itself (match_predict.inc) -- two small launches less between tracker and matcher
   const double *match_src_T = nullptr, *match_src_Ta = nullptr;
   DevBuf<void> seq_buf;                                   // the per-pass term buffers of both modes
   DevBuf<unsigned> seq_stats;                             // device: [0] exact float sums formed, [1] of those by the fallback chain (svs_ctx_get_stat)

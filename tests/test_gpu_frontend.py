@@ -183,9 +183,11 @@ def test_matcher_bit_exact(gpu_ctx, scene_frames, radius, thr_mean, thr_std, leg
         assert set(np.unique(ref["status"])) >= {0, 1, 2, 3}
 
 
-def test_matcher_tie_break_follows_quadtree_order(gpu_ctx):
+@pytest.mark.parametrize("legacy", [0, 1, 2])
+def test_matcher_tie_break_follows_quadtree_order(gpu_ctx, legacy):
     """Periodic texture => many candidates with identical ZNSSD; the winner must be the first one
-    in QuadTree::query DFS order (SURVEY.md B-3), which the kernel reproduces with quadrant keys."""
+    in QuadTree::query DFS order (SURVEY.md B-3), which the kernel reproduces with quadrant keys: every kernel its own way
+    (`match_legacy` 0: quad_less inside a 16-lane group; 1 and 2: quad_key per lane and across the wave)."""
     import oracle as O
     from scavislam_amd import synth
     from scavislam_amd.ctypes_types import CANDIDATE_DTYPE
@@ -209,7 +211,11 @@ def test_matcher_tie_break_follows_quadtree_order(gpu_ctx):
         pts[k]["xyz_anchor"] = ((u0 - cam["cx"]) / cam["f"] * z, (v0 - cam["cy"]) / cam["f"] * z, z)
         pts[k]["anchor_obs_pyr"] = (u0, v0, u0 - 6.0)
     gm = GuidedMatcher(ctx, fr, fg)
-    res = gm.match([(fr.pyr, 0, I.reshape(12))], I.reshape(12), I.reshape(12), pts, thr_std=0)[0]
+    ctx.set_option("match_legacy", legacy)
+    try:
+        res = gm.match([(fr.pyr, 0, I.reshape(12))], I.reshape(12), I.reshape(12), pts, thr_std=0)[0]
+    finally:
+        ctx.set_option("match_legacy", 0)
     pyr = O.build_pyramid(img)
     trees = []
     for l in range(3):
