@@ -1548,6 +1548,120 @@ int svs_frontend_set_neighborhood_from_root(svs_frontend *fe, svs_map *map, int 
                                             int32_t *h_strength, svs_candidate_point *h_records, svs_kf_table *h_table, svs_kf_vertex *h_vertex,
                                             double *h_slot_T);
 
+/* ---- front end: newpoint_map on the device.  StereoFrontend::newpoint_map (stereo_frontend.h:125) is a hash map from keyframe id to a list of candidate points; it
+   is seeded at stereo_frontend.cpp:808 (push_front), pruned at :360-365 (every list, remove_if over the matched new points of the last step, only on a drop) and
+   handed to the matcher at :989-1029 (the active keyframe's list, then the lists of its strength_to_neighbors in that order).  Each stream of a front end gets a
+   STORE that holds it: an ordered sequence of GROUPS in creation order, each with a unique key kf_id >= 0 and its svs_candidate_point records in list order.  On
+   the device the records of a stream lie packed, group behind group, in store order; a table of (key, count) per group lies beside them, and the front end keeps a
+   host mirror of that table -- never of a record -- from which every refusal below is decided before anything is uploaded or launched.  Restated in
+   tests/newpoint_model.py.  The reference's map is a hash container; every order below is canonical:
+     1. reserve.  svs_frontend_newpoints_reserve sets record_cap (records per stream) and group_cap (groups per stream, <= SVS_NEWPOINTS_MAX_GROUPS) once and
+        allocates; a front end that never reserves allocates nothing, and every other call of this block is refused on it.
+     2. put.  SVS_NEWPOINTS_PREPEND: the n given records, already in list order, go in front of the records of group kf_id; SVS_NEWPOINTS_REPLACE: they become its
+        records.  An absent key creates the group at the END of the store, also with n = 0.  The records are stored as given (kf_index included; see rule 6).
+        Requests apply in request order; several may name one stream or one group.
+     3. seed.  svs_frontend_seed_newpoints runs svs_frontend_seed_keyframes' problems (both modes, its SVS_SEED_MORE rule) and prepends the records request r would
+        have returned there to group h_kf_id[r] of the request's stream, device to device, in request order behind one another (rule 2's PREPEND).
+     4. prune.  P = the point_id of every record i of the last step with status == SVS_MATCH_OK, accepted != 0 and i < the list's new-record count (the "new list" of
+        rule 1 of svs_keyframe_decide, matched_new_feat at :922-925).  Every record of every group of the stream whose point_id is in P is removed; the others keep
+        their order (remove_if is stable); a group stays, also when it becomes empty.  Matching is by id, not by remembered list positions: a store changed between
+        hand-over and prune is pruned all the same.  n_removed and every group's record count come back.
+     5. drop.  svs_frontend_newpoints_drop_groups removes the named groups with their records; the other groups keep their order.  (The reference never erases a
+        list; this keeps a long run under group_cap, and which groups go is the caller's decision.)  A key that is absent or named twice counts once or not at all:
+        n_found = the groups removed.
+     6. hand-over.  The stream's candidate list becomes group h_keys[0], group h_keys[1], ... (an absent key: an empty group), then the caller's n_tail tail records
+        (neighborhood_->point_list) as the last group.  A head record of group k gets kf_index = the slot s with h_slot_kf[s] == k, -1 when no slot holds k (an entry
+        < 0 holds nothing); the stored kf_index is not used.  Tail records are taken as given.  Group ends, the group count n_keys + 1, the new-record count (the
+        head's records) and the 0xff tail behind the list follow rule 4 of svs_frontend_set_candidates_from_map.  The store is not changed.
+     7. all or nothing.  A refused call changes nothing, on the host or on the device.  A hand-over request whose total exceeds max_points comes back with
+        over_capacity = 1, its stream untouched, n_points / n_head as found; the call returns SVS_OK and the other requests are unaffected.
+     8. a stream's bytes are a function of the calls made for that stream, in their order: not of the rest of a batch, of batch position or of repetition.
+        Compaction is by ballots, popcounts and a workgroup prefix, group by group and chunk by chunk, reads complete before writes: no atomic decides a position. */
+#define SVS_NEWPOINTS_MAX_GROUPS 64
+enum { SVS_NEWPOINTS_PREPEND = 0, SVS_NEWPOINTS_REPLACE = 1 };
+/* SVS_ERR_INVALID, nothing changed: record_cap < 1, group_cap outside 1 .. SVS_NEWPOINTS_MAX_GROUPS, a second reserve, between svs_frontend_submit_frame and _wait_frame */
+int svs_frontend_newpoints_reserve(svs_frontend *fe, int record_cap, int group_cap);
+typedef struct {
+  int32_t stream, kf_id, mode, n;      /* mode: SVS_NEWPOINTS_PREPEND / _REPLACE */
+  const svs_candidate_point *h_records;        /* HOST [n], list order */
+} svs_newpoints_put_request;           /* 24 bytes */
+/* BLOCKING: one staged upload, one launch (one workgroup per stream named).  Refused, nothing changed -- SVS_ERR_INVALID: no reserve, a stream out of range, kf_id < 0,
+   an unknown mode, n < 0, records missing, between submit_frame and wait_frame; SVS_ERR_CAPACITY: a stream would hold more than group_cap groups or more than
+   record_cap records behind ANY of its requests (every stream of the call then stays as it was) */
+int svs_frontend_newpoints_put(svs_frontend *fe, int n_requests, const svs_newpoints_put_request *req);
+/* BLOCKING.  h_kf_id [n]: the group of each request; h_n_new [n][3] as svs_frontend_seed_keyframes returns it; h_out [n][cap_per_request] (may be NULL; for tests):
+   the records as that call returns them.  Refused, nothing changed: whatever svs_frontend_seed_keyframes refuses; SVS_ERR_INVALID: no reserve, kf_id < 0;
+   SVS_ERR_CAPACITY: more than group_cap groups, or a stream's records plus THE MOST its requests can produce (the sum over the levels of (num_max_points >> l) + 1
+   each) above record_cap -- the counts are known on the device only, so the bound is taken before the launch */
+int svs_frontend_seed_newpoints(svs_frontend *fe, int n, const svs_seed_request *req, const int32_t *h_kf_id, const svs_seed_params *prm, int32_t *h_n_new,
+                                svs_candidate_point *h_out, int cap_per_request);
+typedef struct {                       /* all pointers DEVICE; entry b works on stream s = d_stream ? d_stream[b] : b, whose rows lie at + s * (the batch stride) elements */
+  const svs_match_result *d_res; size_t res_bstride;
+  const svs_candidate_point *d_pts; size_t pts_bstride;
+  const svs_gated_point *d_gated; size_t gated_bstride;
+  const int32_t *d_n;                  /* [streams] records of each stream's step (at most n), or NULL: n for all */
+  const int32_t *d_n_new;              /* [streams] the new-record count of each stream's list */
+  int32_t n, batch;
+  svs_candidate_point *d_store; size_t store_bstride;        /* [streams][store_bstride]: the groups' records back to back, in store order; compacted in place */
+  int32_t *d_group_count; size_t group_bstride;               /* [streams][group_bstride]: records per group, in and out; group_bstride <= SVS_NEWPOINTS_MAX_GROUPS bounds n_groups */
+  const int32_t *d_n_groups;           /* [streams] */
+  const int32_t *d_stream;             /* [batch] distinct streams, or NULL */
+} svs_newpoints_prune_args;            /* 120 bytes */
+/* rule 4, stateless, ASYNCHRONOUS on the context's stream: one workgroup per entry, one launch.  d_n_removed [batch].  A group table the device finds malformed (a
+   count < 0, counts summing above store_bstride, n_groups outside 0 .. group_bstride) is cut where it leaves its row: nothing outside the stream's rows is read
+   or written.  SVS_ERR_INVALID: a missing pointer, n or batch < 0; SVS_ERR_CAPACITY: group_bstride above SVS_NEWPOINTS_MAX_GROUPS; SVS_ERR_UNSUPPORTED: n above
+   8192 (P is held, sorted, in LDS) */
+int svs_newpoints_prune(svs_ctx *ctx, const svs_newpoints_prune_args *a, int32_t *d_n_removed);
+/* the same for the named streams from the front end's own state (the records of the last step, the stores).  BLOCKING; h_n_removed [n_streams],
+   h_group_count [n_streams][SVS_NEWPOINTS_MAX_GROUPS] (may be NULL; zeros behind a stream's groups).  SVS_ERR_INVALID, nothing changed: no reserve, a stream out of
+   range or named twice, the last frame call was not a step or a candidate list was set since (the SVS_SEED_MORE rule), between submit_frame and wait_frame */
+int svs_frontend_newpoints_prune(svs_frontend *fe, int n_streams, const int32_t *h_streams, int32_t *h_n_removed, int32_t *h_group_count);
+typedef struct {
+  int32_t stream, n_keys;
+  const int32_t *h_keys;               /* HOST [n_keys] */
+} svs_newpoints_drop_request;          /* 16 bytes */
+/* rule 5.  BLOCKING, h_n_found [n_requests]; requests apply in order.  SVS_ERR_INVALID, nothing changed: no reserve, a stream out of range, n_keys < 0 */
+int svs_frontend_newpoints_drop_groups(svs_frontend *fe, int n_requests, const svs_newpoints_drop_request *req, int32_t *h_n_found);
+/* the stores of the named streams AS THEY LIE ON THE DEVICE (host mirrors, tests).  BLOCKING.  h_n_groups [n_streams]; h_keys / h_counts [n_streams]
+   [SVS_NEWPOINTS_MAX_GROUPS] in store order (-1 / 0 behind a stream's groups); h_records [n_streams][record_cap], each optional: a stream's records back to back in store
+   order, behind them whatever the device holds.  SVS_ERR_INVALID: no reserve, a stream out of range */
+int svs_frontend_newpoints_get(svs_frontend *fe, int n_streams, const int32_t *h_streams, int32_t *h_n_groups, int32_t *h_keys, int32_t *h_counts,
+                               svs_candidate_point *h_records);
+typedef struct {
+  int32_t stream, n_keys, n_tail, pad_;        /* 1 <= n_keys <= SVS_NEWPOINTS_MAX_GROUPS - 1 */
+  const int32_t *h_keys;               /* HOST [n_keys]: the active keyframe's id, then its strength_to_neighbors in order */
+  const int32_t *h_slot_kf;            /* HOST [the front end's max_keyframes], as in svs_nbh_request */
+  const svs_candidate_point *h_tail;   /* HOST [n_tail]: kf_index = a kept slot, or < 0 */
+} svs_newpoints_list_request;          /* 40 bytes */
+typedef struct {
+  int32_t n_points;                    /* records of the stream's list: n_head + n_tail */
+  int32_t n_head;                      /* records taken from the store */
+  int32_t n_groups;                    /* n_keys + 1 */
+  int32_t n_no_slot;                   /* head records with kf_index = -1 */
+  int32_t over_capacity;               /* rule 7 */
+  int32_t pad_[3];
+} svs_newpoints_list_result;           /* 32 bytes */
+/* rule 6.  BLOCKING: one staged upload (requests, tail records), one launch (one workgroup per request).  h_res [n_requests] (may be NULL); h_records [n_streams]
+   [max_points] and h_group_end [n_streams][SVS_NEWPOINTS_MAX_GROUPS] (may be NULL; for tests): the front end's whole candidate table and its rows of group ends
+   behind the call.  Refused before anything is uploaded, all state unchanged --
+   SVS_ERR_INVALID: no reserve, between submit_frame and wait_frame, a stream out of range or named twice, n_keys < 1, a key < 0 or named twice, a slot-table entry
+   >= 0 for a slot that was never kept or one id in two slots, n_tail < 0 or above max_points, a tail record with the kf_index of an unkept slot;
+   SVS_ERR_CAPACITY: more than SVS_NEWPOINTS_MAX_GROUPS - 1 keys */
+int svs_frontend_set_candidates_from_newpoints(svs_frontend *fe, int n_requests, const svs_newpoints_list_request *req, svs_newpoints_list_result *h_res,
+                                               svs_candidate_point *h_records, int32_t *h_group_end);
+
+/* svs_frontend_set_neighborhood_from_root with the head taken from the stores: the same request and result types, the four head fields of every request (n_head,
+   n_head_groups, n_fixed_groups and the three head pointers) zero / NULL.  Every rule of that call holds unchanged, with these readings: rule 6's fixed group is the
+   store's group act_id (an empty group when the store has none), its keyed groups are all other groups of the stream's store with their keys -- a key that is no
+   keyframe of the map, or no neighbour of act, is left out and counted in n_head_dropped; a head record takes its kf_index as in rule 6 of the block above (the slot
+   that holds its group's keyframe among the slots that name a keyframe of the map, else -1).  The stores are only read; no record goes up or comes down.  Refused as
+   that call refuses (a head cannot be malformed here), and SVS_ERR_INVALID: no reserve, a head field set; SVS_ERR_CAPACITY: the store's groups, act's and the map's
+   are more than 64 */
+int svs_frontend_set_neighborhood_from_store(svs_frontend *fe, svs_map *map, int n_requests, const svs_nbr_request *req, int refresh_poses, int vertex_cap,
+                                             svs_nbr_result *h_res, int32_t *h_point_id, int32_t *h_vertex_id, double *h_vertex_T, int32_t *h_act_neighbors,
+                                             int32_t *h_strength, svs_candidate_point *h_records, svs_kf_table *h_table, svs_kf_vertex *h_vertex,
+                                             double *h_slot_T);
+
 /* ---- multi-GPU: the library-owned collective of the landmark-sharded back-end.  The reference has no
    distributed code; one process per GPU each creates a context and a communicator (RCCL, bound at run time) --------------*/
 typedef struct { char bytes[128]; } svs_unique_id;      /* = ncclUniqueId */

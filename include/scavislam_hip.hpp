@@ -492,7 +492,20 @@ class StereoFrontend {
       : ctx_(c), fe_(nullptr), max_points_(max_points), max_keyframes_(max_keyframes) {
     ok_ = c.check(svs_frontend_create(c.get(), &cam, &prm, max_points, max_keyframes, &fe_));
   }
+  // n_streams independent front ends whose stages run as one launch each (svs_frontend_create_batch): frames in device memory through processFirstFrames /
+  // processFrames below; the host-buffer calls (processFirstFrame, processFrame, ...) need n_streams == 1.  The resident new-point calls take the stream
+  StereoFrontend(const Context &c, const svs_cam &cam, const svs_frontend_params &prm, int max_points, int max_keyframes, int n_streams)
+      : ctx_(c), fe_(nullptr), max_points_(max_points), max_keyframes_(max_keyframes), n_streams_(n_streams) {
+    ok_ = c.check(svs_frontend_create_batch(c.get(), &cam, &prm, max_points, max_keyframes, n_streams, &fe_));
+  }
   ~StereoFrontend() { if (fe_) svs_frontend_destroy(fe_); }
+  int streams() const { return n_streams_; }
+  bool processFirstFrames(const svs_frames_dev *frames) { return ctx_.check(svs_frontend_first_frames(fe_, frames)); }
+  // asynchronous; poses [n_streams][12]
+  bool processFrames(const svs_frames_dev *frames, const double *T_cur_from_actkey, const double *T_actkey_from_w) {
+    return ctx_.check(svs_frontend_process_frames(fe_, frames, T_cur_from_actkey, T_actkey_from_w));
+  }
+  bool keepKeyframes(int slot, const double *T_kf_from_w) { return ctx_.check(svs_frontend_keep_keyframes(fe_, slot, T_kf_from_w)); }
   StereoFrontend(const StereoFrontend &) = delete;
   StereoFrontend &operator=(const StereoFrontend &) = delete;
   // cuda_build: the reference compiled with SCAVISLAM_CUDA_SUPPORT (full-resolution denseTrackingGpu, matcher search radius 4, stereo_frontend.cpp:1043-1047);
@@ -635,9 +648,108 @@ class StereoFrontend {
     track_points->resize(have ? (size_t)dec->n_track : 0); track_records->resize(track_points->size());
     return ok;
   }
+  // ---- newpoint_map on the device (scavislam_hip.h: "front end: newpoint_map on the device"; stereo_frontend.cpp:360-365, :808, :989-1029).  The store keeps one
+  // group of records per keyframe id; nothing of it lives on the host.  reserveNewpoints once, before the first of the calls below
+  bool reserveNewpoints(int record_cap, int group_cap = SVS_NEWPOINTS_MAX_GROUPS) {
+    if (!ctx_.check(svs_frontend_newpoints_reserve(fe_, record_cap, group_cap))) return false;
+    record_cap_ = record_cap;
+    return true;
+  }
+  // records already in list order in front of newpoint_map[keyframe_id] (replace: in its place); an absent key creates the list
+  bool putNewpoints(int keyframe_id, const std::vector<svs_candidate_point> &records, bool replace = false, int stream = 0) {
+    svs_newpoints_put_request q;
+    std::memset(&q, 0, sizeof q);
+    q.stream = stream; q.kf_id = keyframe_id; q.mode = replace ? SVS_NEWPOINTS_REPLACE : SVS_NEWPOINTS_PREPEND; q.n = (int32_t)records.size(); q.h_records = records.data();
+    return ctx_.check(svs_frontend_newpoints_put(fe_, 1, &q));
+  }
+  // addNewPoints / addMorePoints / addMorePointsToOtherFrame whose records stay on the device: newpoint_map[new_keyframe_id].push_front(...) there (:808).
+  // Arguments as the calls above take them, and the stream of a batch front end; only num_points comes back.  The store does not use the records' kf_index (the
+  // hand-over writes the slot that holds the group's keyframe): as in the calls above it carries new_keyframe_id, and a read-back through newpoints() shows that id
+  bool addNewPointsResident(int new_keyframe_id, int first_point_id, uint64_t seed, int32_t num_points[3], const svs_seed_params *prm = nullptr, int stream = 0) {
+    for (int l = 0; l < 3; ++l) num_points[l] = 0;
+    return seedResident_(SVS_SEED_FIRST, new_keyframe_id, nullptr, first_point_id, seed, num_points, prm, stream);
+  }
+  bool addMorePointsResident(int new_keyframe_id, int first_point_id, uint64_t seed, int32_t num_points[3], const svs_seed_params *prm = nullptr, int stream = 0) {
+    return seedResident_(SVS_SEED_MORE, new_keyframe_id, nullptr, first_point_id, seed, num_points, prm, stream);
+  }
+  bool addMorePointsToOtherFrameResident(int new_keyframe_id, const double T_newkey_from_cur[12], int first_point_id, uint64_t seed, int32_t num_points[3],
+                                         const svs_seed_params *prm = nullptr, int stream = 0) {
+    return seedResident_(SVS_SEED_MORE, new_keyframe_id, T_newkey_from_cur, first_point_id, seed, num_points, prm, stream);
+  }
+  // addNewKeyframe's remove_if over every list of the map (:360-365), from the records the step left on the device; behind processFrame, before the next list is set
+  bool pruneNewpoints(int32_t *n_removed = nullptr, int stream = 0) {
+    const int32_t st = stream;
+    int32_t removed = 0;
+    if (!ctx_.check(svs_frontend_newpoints_prune(fe_, 1, &st, &removed, nullptr))) return false;
+    if (n_removed) *n_removed = removed;
+    return true;
+  }
+  // ... of the named streams of a batch front end in one launch (the streams whose step dropped); n_removed: one count per stream named
+  bool pruneNewpoints(const std::vector<int32_t> &streams, std::vector<int32_t> *n_removed) {
+    std::vector<int32_t> removed(streams.size() ? streams.size() : 1);
+    if (!ctx_.check(svs_frontend_newpoints_prune(fe_, (int)streams.size(), streams.data(), removed.data(), nullptr))) return false;
+    removed.resize(streams.size());
+    if (n_removed) *n_removed = removed;
+    return true;
+  }
+  bool dropNewpointGroups(const std::vector<int32_t> &keyframe_ids, int32_t *n_found = nullptr, int stream = 0) {
+    svs_newpoints_drop_request q;
+    std::memset(&q, 0, sizeof q);
+    q.stream = stream; q.n_keys = (int32_t)keyframe_ids.size(); q.h_keys = keyframe_ids.data();
+    int32_t found = 0;
+    if (!ctx_.check(svs_frontend_newpoints_drop_groups(fe_, 1, &q, &found))) return false;
+    if (n_found) *n_found = found;
+    return true;
+  }
+  // the store read back: the lists' keyframe ids and lengths in store order, and (records != NULL) their records back to back
+  bool newpoints(std::vector<int32_t> *keyframe_ids, std::vector<int32_t> *counts, std::vector<svs_candidate_point> *records = nullptr, int stream_index = 0) {
+    const int32_t stream = stream_index;
+    int32_t n_groups = 0;
+    keyframe_ids->assign(SVS_NEWPOINTS_MAX_GROUPS, -1); counts->assign(SVS_NEWPOINTS_MAX_GROUPS, 0);
+    if (records) records->resize((size_t)(record_cap_ > 0 ? record_cap_ : 1));
+    if (!ctx_.check(svs_frontend_newpoints_get(fe_, 1, &stream, &n_groups, keyframe_ids->data(), counts->data(), records ? records->data() : nullptr))) return false;
+    keyframe_ids->resize((size_t)n_groups); counts->resize((size_t)n_groups);
+    size_t total = 0;
+    for (size_t g = 0; g < counts->size(); ++g) total += (size_t)(*counts)[g];
+    if (records) records->resize(total);
+    return true;
+  }
+  // matchAndTrack's lists (:989-1029) with the head taken from the store: list_keyframe_ids = actkey_id, then its strength_to_neighbors in order; point_list =
+  // neighborhood_->point_list; slot_keyframe_ids as in setCandidatesFromMap.  false: refused, or over capacity (res->over_capacity; the list is then as before)
+  bool setCandidatesFromNewpoints(const std::vector<int32_t> &list_keyframe_ids, const std::vector<int32_t> &slot_keyframe_ids,
+                                  const std::vector<svs_candidate_point> &point_list, svs_newpoints_list_result *res = nullptr, int stream = 0) {
+    if ((int)slot_keyframe_ids.size() != max_keyframes_) return false;
+    svs_newpoints_list_request q;
+    std::memset(&q, 0, sizeof q);
+    q.stream = stream; q.n_keys = (int32_t)list_keyframe_ids.size(); q.n_tail = (int32_t)point_list.size();
+    q.h_keys = list_keyframe_ids.data(); q.h_slot_kf = slot_keyframe_ids.data(); q.h_tail = point_list.data();
+    svs_newpoints_list_result r;
+    std::memset(&r, 0, sizeof r);
+    const bool ok = ctx_.check(svs_frontend_set_candidates_from_newpoints(fe_, 1, &q, &r, nullptr, nullptr));
+    if (res) *res = r;
+    if (ok && !r.over_capacity && stream == 0) n_ = r.n_points;
+    return ok && !r.over_capacity;
+  }
+  // setNeighborhoodFromMap with the head taken from the stream's store (svs_frontend_set_neighborhood_from_store): newpoint_map[actkey_id] is the fixed group, every
+  // other list of the store a keyed one; no new-point record goes up.  Defined behind BackendMap
+  inline bool setNeighborhoodFromStore(BackendMap &map, int32_t root_id, int32_t actkey_id, const std::vector<int32_t> &slot_keyframe_ids, bool refresh_poses,
+                                       svs_nbr_result *res, std::vector<int32_t> *point_ids, std::vector<FrontendVertex> *vertex_map,
+                                       std::vector<int32_t> *act_neighbors, int max_num_neighbors = 10, int vertex_cap = 64, int stream = 0);
   svs_frontend *handle() const { return fe_; }
 
  private:
+  bool seedResident_(int mode, int kf, const double *T, int first_point_id, uint64_t seed, int32_t num_points[3], const svs_seed_params *prm, int stream) {
+    const svs_seed_params p = prm ? *prm : seedParams();
+    svs_seed_request q;
+    std::memset(&q, 0, sizeof q);
+    q.stream = stream; q.mode = mode; q.kf_index = kf; q.first_point_id = first_point_id; q.seed = seed;
+    for (int i = 0; i < 12; ++i) q.T_newkey_from_cur[i] = T ? T[i] : (i % 5 == 0 ? 1.0 : 0.0);
+    const int32_t key = kf;
+    int32_t n[3] = {0, 0, 0};
+    if (!ctx_.check(svs_frontend_seed_newpoints(fe_, 1, &q, &key, &p, n, nullptr, 0))) return false;
+    for (int l = 0; l < 3; ++l) num_points[l] += n[l];
+    return true;
+  }
   bool seed_(int mode, int kf, const double *T, int first_point_id, uint64_t seed, std::vector<svs_candidate_point> *out, int32_t num_points[3],
              const svs_seed_params *prm) {
     const svs_seed_params p = prm ? *prm : seedParams();
@@ -659,6 +771,8 @@ class StereoFrontend {
   bool ok_;
   int n_ = 0;
   int max_points_, max_keyframes_;
+  int record_cap_ = 0;
+  int n_streams_ = 1;
 };
 
 // The per-pixel input conversions of FrameGrabber<StereoCamera> (frame_grabber.cpp:125-186, frame_grabber-impl.cpp:93-152) on device frames of n streams:
@@ -1313,6 +1427,32 @@ inline bool StereoFrontend::setNeighborhoodFromMap(BackendMap &map, int32_t root
   if (res) *res = r;
   if (r.over_capacity || r.root_outside_window) return false;
   n_ = r.n_points;
+  if (point_ids) point_ids->assign(pid.begin(), pid.begin() + r.n_points);
+  if (act_neighbors) act_neighbors->assign(nbr.begin(), nbr.begin() + r.n_act_neighbors);
+  if (vertex_map) {
+    vertex_map->resize((size_t)r.n_vertex);
+    for (int i = 0; i < r.n_vertex; ++i) { (*vertex_map)[(size_t)i].frame_id = vid[(size_t)i]; std::memcpy((*vertex_map)[(size_t)i].T_me_from_w, &vT[(size_t)i * 12], 12 * sizeof(double)); }
+  }
+  return true;
+}
+inline bool StereoFrontend::setNeighborhoodFromStore(BackendMap &map, int32_t root_id, int32_t actkey_id, const std::vector<int32_t> &slot_keyframe_ids,
+                                                     bool refresh_poses, svs_nbr_result *res, std::vector<int32_t> *point_ids, std::vector<FrontendVertex> *vertex_map,
+                                                     std::vector<int32_t> *act_neighbors, int max_num_neighbors, int vertex_cap, int stream) {
+  if (!ok_ || !map.ok() || (int)slot_keyframe_ids.size() != max_keyframes_ || vertex_cap < 1) return false;
+  svs_nbr_request q;
+  std::memset(&q, 0, sizeof q);
+  q.stream = stream; q.root_id = root_id; q.act_id = actkey_id; q.max_num_neighbors = max_num_neighbors;
+  q.h_slot_kf = slot_keyframe_ids.data();
+  svs_nbr_result r;
+  std::memset(&r, 0, sizeof r);
+  std::vector<int32_t> pid((size_t)max_points_), vid((size_t)vertex_cap), nbr((size_t)vertex_cap);
+  std::vector<double> vT((size_t)vertex_cap * 12);
+  if (!ctx_.check(svs_frontend_set_neighborhood_from_store(fe_, map.get(), 1, &q, refresh_poses ? 1 : 0, vertex_cap, &r, pid.data(), vid.data(), vT.data(), nbr.data(),
+                                                           nullptr, nullptr, nullptr, nullptr, nullptr)))
+    return false;
+  if (res) *res = r;
+  if (r.over_capacity || r.root_outside_window) return false;
+  if (stream == 0) n_ = r.n_points;
   if (point_ids) point_ids->assign(pid.begin(), pid.begin() + r.n_points);
   if (act_neighbors) act_neighbors->assign(nbr.begin(), nbr.begin() + r.n_act_neighbors);
   if (vertex_map) {

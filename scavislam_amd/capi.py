@@ -8,7 +8,7 @@ import ctypes as C
 import os
 import weakref
 
-from .ctypes_types import BaParams, BaStats, Cam, FastGrid, KeyframeDecideArgs, KeyframeDecideParams, LoopCheck, LoopLocation, LoopLocationResult, LoopResult, MapAddKeyframeArgs, MapConstraintRequest, MapStrengthResult, MapWindowResult, NbhRequest, NbhResult, NbrRequest, NbrResult, PoseOptParams, PoseOptStats, RegCommitResult, RegMapRequest, RegParams, RegRequest, RegResult, SeedArgs, SeedParams, SeedRequest, StereoParams, SurfParams, VertexRequest, VocabParams, VocabResult
+from .ctypes_types import BaParams, BaStats, Cam, FastGrid, KeyframeDecideArgs, KeyframeDecideParams, LoopCheck, LoopLocation, LoopLocationResult, LoopResult, MapAddKeyframeArgs, MapConstraintRequest, MapStrengthResult, MapWindowResult, NbhRequest, NbhResult, NbrRequest, NbrResult, NewpointsDropRequest, NewpointsListRequest, NewpointsListResult, NewpointsPruneArgs, NewpointsPutRequest, PoseOptParams, PoseOptStats, RegCommitResult, RegMapRequest, RegParams, RegRequest, RegResult, SeedArgs, SeedParams, SeedRequest, StereoParams, SurfParams, VertexRequest, VocabParams, VocabResult
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SVS_LIB_PATH") or os.path.join(_HERE, "libscavislam_hip.so")   # override = kernel A/B experiments only
@@ -258,11 +258,21 @@ _SIGS = {
                                              C.c_void_p, C.c_void_p],
     "svs_frontend_set_neighborhood_from_root": [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(NbrRequest), C.c_int, C.c_int, C.POINTER(NbrResult), C.c_void_p, C.c_void_p,
                                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
+    "svs_frontend_set_neighborhood_from_store": [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(NbrRequest), C.c_int, C.c_int, C.POINTER(NbrResult), C.c_void_p, C.c_void_p,
+                                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
     "svs_keyframe_decide": [C.c_void_p, C.POINTER(KeyframeDecideArgs), C.POINTER(KeyframeDecideParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                             C.c_int],
     "svs_frontend_set_vertex_table": [C.c_void_p, C.c_int, C.POINTER(VertexRequest)],
     "svs_frontend_decide_keyframes": [C.c_void_p, C.c_void_p, C.POINTER(KeyframeDecideParams), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                       C.c_int],
+    "svs_frontend_newpoints_reserve": [C.c_void_p, C.c_int, C.c_int],
+    "svs_frontend_newpoints_put": [C.c_void_p, C.c_int, C.POINTER(NewpointsPutRequest)],
+    "svs_frontend_seed_newpoints": [C.c_void_p, C.c_int, C.POINTER(SeedRequest), C.c_void_p, C.POINTER(SeedParams), C.c_void_p, C.c_void_p, C.c_int],
+    "svs_newpoints_prune": [C.c_void_p, C.POINTER(NewpointsPruneArgs), C.c_void_p],
+    "svs_frontend_newpoints_prune": [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p],
+    "svs_frontend_newpoints_drop_groups": [C.c_void_p, C.c_int, C.POINTER(NewpointsDropRequest), C.c_void_p],
+    "svs_frontend_newpoints_get": [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
+    "svs_frontend_set_candidates_from_newpoints": [C.c_void_p, C.c_int, C.POINTER(NewpointsListRequest), C.POINTER(NewpointsListResult), C.c_void_p, C.c_void_p],
     "svs_ba_create": [C.c_void_p, C.POINTER(C.c_void_p)],
     "svs_ba_destroy": [C.c_void_p],
     "svs_ba_set_problem": [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p,

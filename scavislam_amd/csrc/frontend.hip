@@ -21,6 +21,7 @@
 #include "keyframe.h"
 #include "nbh_map.h"
 #include "nbr_map.h"
+#include "newpoints.h"
 #include "pose.h"
 #include "seed.h"
 #include <string.h>
@@ -173,6 +174,13 @@ struct svs_frontend {
   PinnedBuf<uint8_t> h_vt; DevBuf<uint8_t> d_vt_up;
   DevBuf<svs_keyframe_decision> d_kd_dec; DevBuf<svs_map_new_point> d_kd_new; DevBuf<svs_map_track_point> d_kd_track; DevBuf<int32_t> d_kd_new_rec, d_kd_track_rec;
   PinnedBuf<svs_keyframe_decision> h_kd_dec;
+  // the resident newpoint_map (svs_frontend_newpoints_*, frontend_newpoints.inc / newpoints.hip): per stream a row of records with its groups packed in store order,
+  // a scratch row, the (key, count) table; the host mirrors the TABLES (never a record) and decides every refusal from them.  Nothing is allocated before
+  // svs_frontend_newpoints_reserve
+  int np_rcap = 0, np_gcap = 0;
+  DevBuf<svs_candidate_point> d_np_rec, d_np_tmp; DevBuf<int32_t> d_np_key, d_np_cnt, d_np_ng, d_np_removed;
+  std::vector<int32_t> np_key, np_cnt, np_ng;      // [B][64], [B][64], [B]
+  PinnedBuf<uint8_t> h_np; DevBuf<uint8_t> d_np;   // staging block of the calls, grown on demand
   // drains the streams and takes the detector / block matcher along before the members above go (also when create gives up half way)
   ~svs_frontend() {
     (void)hipStreamSynchronize(ctx->stream);
@@ -1108,13 +1116,24 @@ extern "C" int svs_frontend_dense_records(svs_frontend *fe, int stream, svs_dens
   return SVS_OK;
 }
 
+namespace {
+// svs_frontend_seed_newpoints' part in the call: what is checked beside the requests before anything is uploaded, and what is enqueued behind the seed kernel on its
+// outputs (records [n][cap], counts [n][3], both on the device)
+struct SeedSink {
+  virtual int check() = 0;
+  virtual int enqueue(const svs_candidate_point *d_rec, const int32_t *d_cnt, int cap) = 0;
+  virtual ~SeedSink() = default;
+};
+}  // namespace
+
 /* addNewPoints / addMorePoints (stereo_frontend.cpp:682-823) for n requests from the device state the last first_frame(s) / process_frame(s) call left behind:
    the corner lists of its detection, its disparity, and for SVS_SEED_MORE its gate records and point statistics (seed.hip).  One staged upload (problems, streams,
    the callers' orders), the kernels, one download (counts and records). */
-extern "C" int svs_frontend_seed_keyframes(svs_frontend *fe, int n, const svs_seed_request *req, const svs_seed_params *prm, svs_candidate_point *h_out,
-                                           int cap_per_request, int32_t *h_n_new) {
+// (shared by svs_frontend_seed_keyframes and svs_frontend_seed_newpoints; h_out may be NULL with a sink: only the counts come back then)
+static int fe_seed_keyframes(svs_frontend *fe, int n, const svs_seed_request *req, const svs_seed_params *prm, svs_candidate_point *h_out, int cap_per_request,
+                             int32_t *h_n_new, SeedSink *sink) {
   svs_ctx *ctx = fe ? fe->ctx : nullptr;
-  SVS_REQUIRE(ctx, fe && n >= 0 && (n == 0 || (req && h_out && h_n_new)) && prm && fe->have_prev && !fe->submitted && fe->last_disp);
+  SVS_REQUIRE(ctx, fe && n >= 0 && (n == 0 || (req && (h_out || sink) && h_n_new)) && prm && fe->have_prev && !fe->submitted && fe->last_disp);
   SVS_REQUIRE(ctx, prm->n_levels >= 1 && prm->n_levels <= fe->prm.n_levels && prm->num_max_points >= 0 && prm->num_max_points <= 65536);
   if (cap_per_request < svs_seed_max_records(prm)) {
     ctx->err = "svs_frontend_seed_keyframes: cap_per_request below the sum over the levels of (num_max_points >> l) + 1";
@@ -1135,6 +1154,7 @@ extern "C" int svs_frontend_seed_keyframes(svs_frontend *fe, int n, const svs_se
       if (q.h_order[l]) ob[l] = std::max(ob[l], (size_t)q.n_order[l]);
     }
   }
+  if (sink) if (int rc = sink->check()) return rc;
   SVS_DEVICE(ctx);
   // staging block: problems | streams | orders of level 0, 1, 2 ; device block: the same, then counts [n][3] (padded to 64 bytes) | records [n][cap]
   auto up64 = [](size_t v) { return (v + 63) & ~(size_t)63; };
@@ -1144,7 +1164,7 @@ extern "C" int svs_frontend_seed_keyframes(svs_frontend *fe, int n, const svs_se
   const size_t off_cnt = in_bytes, off_rec = up64(off_cnt + sizeof(int32_t) * 3 * (size_t)n);
   const size_t out_bytes = (off_rec - off_cnt) + sizeof(svs_candidate_point) * (size_t)cap_per_request * (size_t)n, d_bytes = off_cnt + out_bytes;
   // small results go home in one copy through the pinned block; big ones as the counts, then one strided copy of the longest list's width into the caller's array
-  const bool one_copy = out_bytes <= ((size_t)1 << 20);
+  const bool one_copy = h_out && out_bytes <= ((size_t)1 << 20);
   const size_t h_bytes = std::max(in_bytes, one_copy ? out_bytes : off_rec - off_cnt);
   if (fe->h_seed.bytes() < h_bytes || fe->d_seed.bytes() < d_bytes) SVS_HIP(ctx, hipStreamSynchronize(ctx->stream));
   if (fe->h_seed.bytes() < h_bytes) SVS_HIP(ctx, fe->h_seed.alloc_bytes(h_bytes));
@@ -1185,6 +1205,9 @@ extern "C" int svs_frontend_seed_keyframes(svs_frontend *fe, int n, const svs_se
   if (int rc = svs_seed_launch(ctx, &a, prm, &fs, any_generated, reinterpret_cast<svs_candidate_point *>(fe->d_seed + off_rec), cap_per_request,
                                reinterpret_cast<int32_t *>(fe->d_seed + off_cnt)))
     return rc;
+  if (sink)
+    if (int rc = sink->enqueue(reinterpret_cast<const svs_candidate_point *>(fe->d_seed + off_rec), reinterpret_cast<const int32_t *>(fe->d_seed + off_cnt), cap_per_request))
+      return rc;
   SVS_HIP(ctx, hipMemcpyAsync(fe->h_seed, fe->d_seed + off_cnt, one_copy ? out_bytes : off_rec - off_cnt, hipMemcpyDeviceToHost, ctx->stream));
   SVS_HIP(ctx, hipStreamSynchronize(ctx->stream));
   __builtin_memcpy(h_n_new, fe->h_seed, sizeof(int32_t) * 3 * (size_t)n);
@@ -1197,12 +1220,19 @@ extern "C" int svs_frontend_seed_keyframes(svs_frontend *fe, int n, const svs_se
       const int m = h_n_new[3 * r] + h_n_new[3 * r + 1] + h_n_new[3 * r + 2];
       if (m > 0) __builtin_memcpy(h_out + (size_t)r * cap_per_request, rec + (size_t)r * cap_per_request, sizeof(svs_candidate_point) * (size_t)m);
     }
-  } else if (longest > 0) {      // (behind a request's own count the caller's rows receive what the device block held there: unspecified)
+  } else if (h_out && longest > 0) {      // (behind a request's own count the caller's rows receive what the device block held there: unspecified)
     const size_t pitch = sizeof(svs_candidate_point) * (size_t)cap_per_request;
     SVS_HIP(ctx, hipMemcpy2DAsync(h_out, pitch, fe->d_seed + off_rec, pitch, sizeof(svs_candidate_point) * (size_t)longest, (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
     SVS_HIP(ctx, hipStreamSynchronize(ctx->stream));
   }
   return SVS_OK;
+}
+
+extern "C" int svs_frontend_seed_keyframes(svs_frontend *fe, int n, const svs_seed_request *req, const svs_seed_params *prm, svs_candidate_point *h_out,
+                                           int cap_per_request, int32_t *h_n_new) {
+  svs_ctx *ctx = fe ? fe->ctx : nullptr;
+  SVS_REQUIRE(ctx, n <= 0 || h_out);
+  return fe_seed_keyframes(fe, n, req, prm, h_out, cap_per_request, h_n_new, nullptr);
 }
 
 // the resident vertex tables, the decision records and the list rows come with the first table (tables, vertices and slot tables zeroed: a stream's rows can be
@@ -1363,11 +1393,13 @@ extern "C" int svs_frontend_decide_keyframes(svs_frontend *fe, svs_map *map, con
 /* a stream's whole neighbourhood from a root id (map.hip: map_nbh.inc, through nbr_map.h; the contract is in the header): everything is checked on the host first, then one
    staged upload, the map's four launches writing d_pts / d_group_end / d_n_groups / d_n_new / d_kfs and the resident vertex tables in place, one download from
    which the host state follows */
-extern "C" int svs_frontend_set_neighborhood_from_root(svs_frontend *fe, svs_map *map, int n_requests, const svs_nbr_request *req, int refresh_poses, int vertex_cap,
-                                                       svs_nbr_result *h_res, int32_t *h_point_id, int32_t *h_vertex_id, double *h_vertex_T, int32_t *h_act_neighbors,
-                                                       int32_t *h_strength, svs_candidate_point *h_records, svs_kf_table *h_table, svs_kf_vertex *h_vertex,
-                                                       double *h_slot_T) {
+// (from_store: svs_frontend_set_neighborhood_from_store -- the head is the stream's new-point store as it lies on the device: its group of act_id is the fixed
+// group, every other group a keyed one; nothing of a head is staged)
+static int fe_set_neighborhood(svs_frontend *fe, svs_map *map, int n_requests, const svs_nbr_request *req, int refresh_poses, int vertex_cap, svs_nbr_result *h_res,
+                               int32_t *h_point_id, int32_t *h_vertex_id, double *h_vertex_T, int32_t *h_act_neighbors, int32_t *h_strength,
+                               svs_candidate_point *h_records, svs_kf_table *h_table, svs_kf_vertex *h_vertex, double *h_slot_T, bool from_store) {
   svs_ctx *ctx = fe ? fe->ctx : nullptr;
+  SVS_REQUIRE(ctx, !from_store || (fe && fe->np_rcap > 0));
   SVS_REQUIRE(ctx, fe && map && svs_map_ctx(map) == ctx && !fe->submitted && n_requests >= 0 && n_requests <= fe->B && (n_requests == 0 || req) && vertex_cap >= 1 &&
                        vertex_cap <= SVS_KF_MAX_VERTICES);
   if (fe->max_keyframes > SVS_KF_MAX_SLOTS) { ctx->err = "svs_frontend_set_neighborhood_from_root: more than SVS_KF_MAX_SLOTS keyframe slots"; return SVS_ERR_UNSUPPORTED; }
@@ -1381,6 +1413,19 @@ extern "C" int svs_frontend_set_neighborhood_from_root(svs_frontend *fe, svs_map
       SVS_REQUIRE(ctx, q.stream >= 0 && q.stream < B && !named[q.stream]);
       named[q.stream] = 1;
       SVS_REQUIRE(ctx, svs_map_has_keyframe(map, q.root_id) && svs_map_has_keyframe(map, q.act_id) && q.max_num_neighbors >= 0);
+      if (from_store) {      // the four head fields are the store's to fill; the written list holds at most the store's groups, act's (also when absent) and the map's
+        SVS_REQUIRE(ctx, q.h_slot_kf && q.n_head == 0 && q.n_head_groups == 0 && q.n_fixed_groups == 0 && !q.h_head_group_end && !q.h_head && !q.h_head_group_kf);
+        bool have_act = false;
+        for (int g = 0; g < fe->np_ng[q.stream]; ++g) have_act = have_act || fe->np_key[(size_t)q.stream * MAX_GROUPS + g] == q.act_id;
+        if (fe->np_ng[q.stream] + (have_act ? 0 : 1) + 1 > MAX_GROUPS) { ctx->err = "svs_frontend_set_neighborhood_from_store: more than 64 groups"; return SVS_ERR_CAPACITY; }
+        const uint8_t *kept = fe->kept.data() + (size_t)q.stream * K;
+        sorted.clear();
+        for (int s = 0; s < K; ++s)
+          if (q.h_slot_kf[s] >= 0) { SVS_REQUIRE(ctx, kept[s]); sorted.push_back(q.h_slot_kf[s]); }
+        std::sort(sorted.begin(), sorted.end());
+        SVS_REQUIRE(ctx, std::adjacent_find(sorted.begin(), sorted.end()) == sorted.end());
+        continue;
+      }
       SVS_REQUIRE(ctx, q.h_slot_kf && q.n_head >= 0 && q.n_head <= MP && (q.n_head == 0 || q.h_head) && q.n_head_groups >= 1 && q.h_head_group_end);
       if (q.n_head_groups + 1 > MAX_GROUPS) { ctx->err = "svs_frontend_set_neighborhood_from_root: more than 64 groups"; return SVS_ERR_CAPACITY; }
       SVS_REQUIRE(ctx, q.n_fixed_groups >= 1 && q.n_fixed_groups <= q.n_head_groups && (q.n_fixed_groups == q.n_head_groups || q.h_head_group_kf));
@@ -1429,6 +1474,14 @@ extern "C" int svs_frontend_set_neighborhood_from_root(svs_frontend *fe, svs_map
     s.n_head = q.n_head; s.n_groups = q.n_head_groups; s.n_fixed = q.n_fixed_groups; s.prev_len = fe->n_points[q.stream];
     s.slot_off = (int32_t)((size_t)r * 2 * K); s.slot_raw_off = s.slot_off + K;
     for (int k = 0; k < K; ++k) { ids[s.slot_off + k] = svs_map_has_keyframe(map, q.h_slot_kf[k]) ? q.h_slot_kf[k] : -1; ids[s.slot_raw_off + k] = q.h_slot_kf[k]; }
+    if (from_store) {      // the stream's groups in store order; act's group is the fixed one -- an empty group behind the others when the store has none
+      const int32_t *key = &fe->np_key[(size_t)q.stream * MAX_GROUPS], *cnt = &fe->np_cnt[(size_t)q.stream * MAX_GROUPS];
+      int G = fe->np_ng[q.stream], at = 0, f = -1;
+      for (int g = 0; g < G; ++g) { at += cnt[g]; s.group_end[g] = at; s.group_kf[g] = key[g]; if (key[g] == q.act_id) f = g; }
+      if (f < 0) { f = G; s.group_end[G] = at; s.group_kf[G] = q.act_id; ++G; }
+      s.n_head = at; s.n_groups = G; s.n_fixed = 1; s.fixed_at = 1 + f;
+      continue;
+    }
     s.head_off = (int32_t)at_head;
     if (q.n_head) memcpy(head + at_head, q.h_head, (size_t)q.n_head * sizeof(svs_candidate_point));
     at_head += (size_t)q.n_head;
@@ -1437,6 +1490,7 @@ extern "C" int svs_frontend_set_neighborhood_from_root(svs_frontend *fe, svs_map
   SVS_HIP(ctx, hipMemcpyAsync(ds, hs, in_bytes, hipMemcpyHostToDevice, ctx->stream));
   MapNbrDst D{};
   D.req = reinterpret_cast<const nbr_req *>(ds); D.ids = reinterpret_cast<const int32_t *>(ds + o_ids); D.head = reinterpret_cast<const svs_candidate_point *>(ds + o_head);
+  if (from_store) { D.head = fe->d_np_rec; D.head_stride = fe->np_rcap; D.from_store = 1; }
   D.R = R; D.VB = VB;
   D.pts = fe->d_pts; D.max_points = MP; D.group_end = fe->d_group_end; D.n_groups = fe->d_n_groups; D.n_new = fe->d_n_new; D.kfs = fe->d_kfs; D.max_keyframes = K;
   D.vt_tab = fe->d_vt_tab; D.vt_vtx = fe->d_vt_vtx; D.vt_slot = fe->d_vt_slot;
@@ -1499,3 +1553,21 @@ extern "C" int svs_frontend_set_neighborhood_from_root(svs_frontend *fe, svs_map
   }
   return SVS_OK;
 }
+
+extern "C" int svs_frontend_set_neighborhood_from_root(svs_frontend *fe, svs_map *map, int n_requests, const svs_nbr_request *req, int refresh_poses, int vertex_cap,
+                                                       svs_nbr_result *h_res, int32_t *h_point_id, int32_t *h_vertex_id, double *h_vertex_T, int32_t *h_act_neighbors,
+                                                       int32_t *h_strength, svs_candidate_point *h_records, svs_kf_table *h_table, svs_kf_vertex *h_vertex,
+                                                       double *h_slot_T) {
+  return fe_set_neighborhood(fe, map, n_requests, req, refresh_poses, vertex_cap, h_res, h_point_id, h_vertex_id, h_vertex_T, h_act_neighbors, h_strength, h_records,
+                             h_table, h_vertex, h_slot_T, false);
+}
+
+extern "C" int svs_frontend_set_neighborhood_from_store(svs_frontend *fe, svs_map *map, int n_requests, const svs_nbr_request *req, int refresh_poses, int vertex_cap,
+                                                        svs_nbr_result *h_res, int32_t *h_point_id, int32_t *h_vertex_id, double *h_vertex_T, int32_t *h_act_neighbors,
+                                                        int32_t *h_strength, svs_candidate_point *h_records, svs_kf_table *h_table, svs_kf_vertex *h_vertex,
+                                                        double *h_slot_T) {
+  return fe_set_neighborhood(fe, map, n_requests, req, refresh_poses, vertex_cap, h_res, h_point_id, h_vertex_id, h_vertex_T, h_act_neighbors, h_strength, h_records,
+                             h_table, h_vertex, h_slot_T, true);
+}
+
+#include "frontend_newpoints.inc"

@@ -130,6 +130,13 @@ __global__ __launch_bounds__(MB_THREADS) void map_nbh_kernel(MapK M, MapNbhDst D
 //                            and leaves at once when there is none; T goes straight into the request's row of vertex poses
 //   map_nbr_finish_kernel    one workgroup per request: the poses, the active keyframe's neighbours as a rank sort over (strength, id), the strength matrix, the
 //                            head's groups in that order, then everything map_nbh_kernel writes and the stream's resident vertex table
+// the records of a request's fixed groups: the leading n_fixed groups, or group fixed_at - 1 alone
+__device__ __forceinline__ int nbr_fixed_records(const nbr_req &Q) {
+  if (Q.fixed_at == 0) return Q.group_end[Q.n_fixed - 1];
+  const int f = Q.fixed_at - 1;
+  return Q.group_end[f] - (f ? Q.group_end[f - 1] : 0);
+}
+
 __global__ __launch_bounds__(MB_THREADS) void map_nbr_collect_kernel(MapK M, MapWalkK W, MapNbrDst D) {
   __shared__ uint32_t s_vert[MAP_KF_WORDS], s_anch[MAP_KF_WORDS];
   __shared__ int16_t s_slot[MAP_MAX_KF];
@@ -158,7 +165,7 @@ __global__ __launch_bounds__(MB_THREADS) void map_nbr_collect_kernel(MapK M, Map
   const int n_nb = max_nn < n_in ? max_nn + 1 : n_in;            // (max_nn + 1 is formed only where it is at most n_in)
   const int n_given = 1 + n_nb;
   if (tid == 0) vid[0] = root;                                     // VB >= 1
-  const int n_fixed_rec = Q.group_end[Q.n_fixed - 1];
+  const int n_fixed_rec = nbr_fixed_records(Q);
   if (n_given > VB) {                                              // block-uniform, rule 9 (a)
     if (tid == 0) { nbr_mid m{}; m.status = NBR_OVER; m.n_given = n_given; m.n_vert = n_given; Mid = m; }
     return;
@@ -229,6 +236,7 @@ __global__ __launch_bounds__(MB_THREADS) void map_nbr_finish_kernel(MapK M, MapW
   __shared__ double s_T[SVS_KF_MAX_VERTICES][12];
   __shared__ int s_actn[SVS_KF_MAX_VERTICES];                      // rule 4: vertex indices in order
   __shared__ int s_gsrc[NBH_MAX_GROUPS], s_gend[NBH_MAX_GROUPS];   // rule 6, by group of the written head: where its records were staged, one past its last record
+  __shared__ int s_gkey[NBH_MAX_GROUPS];                           // ... and its key (read for a head that comes from the store)
   __shared__ int s_cnt[4];                                         // n_no_path, n_actn, groups of the written head, its records
   const int r = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, VB = D.VB, MP = D.max_points, K = D.max_keyframes;
   const nbr_req &Q = D.req[r];
@@ -238,7 +246,7 @@ __global__ __launch_bounds__(MB_THREADS) void map_nbr_finish_kernel(MapK M, MapW
     if (tid == 0) {
       if (mid.status == NBR_ROOT_OUTSIDE) R.root_outside_window = 1;
       else {
-        R.over_capacity = 1; R.n_map_points = mid.n_map; R.n_points = Q.group_end[Q.n_fixed - 1] + mid.n_map; R.n_vertex = mid.n_vert; R.n_no_slot = mid.n_no_slot;
+        R.over_capacity = 1; R.n_map_points = mid.n_map; R.n_points = nbr_fixed_records(Q) + mid.n_map; R.n_vertex = mid.n_vert; R.n_no_slot = mid.n_no_slot;
         R.n_root_neighbors = mid.n_given - 1;
       }
       D.res[r] = R;
@@ -298,26 +306,29 @@ __global__ __launch_bounds__(MB_THREADS) void map_nbr_finish_kernel(MapK M, MapW
     // d. rule 6: lane g is head group g.  Fixed groups stay; a keyed group goes behind them at the place of its key in rule 4's list, which is the rank
     // lane j of this wave has just found for vertex j
     int place = -1;                                                // among the written groups: fixed g -> g, keyed -> n_fixed + its rank among the kept
-    const int j = lane >= n_fixed && lane < G ? (int)s_vidx[Q.group_kf[lane]] : NBR_NO_VERTEX;
+    const int fx = Q.fixed_at - 1;                                 // >= 0: the head is the stream's store, group fx (the active keyframe's) is the fixed one
+    const bool is_fixed = fx >= 0 ? lane == fx : lane < n_fixed;
+    const int gkey = lane < G ? Q.group_kf[lane] : -1;             // (a store's key need not be a keyframe of the map: such a group is left out)
+    const int j = lane < G && !is_fixed && (unsigned)gkey < (unsigned)MAP_MAX_KF ? (int)s_vidx[gkey] : NBR_NO_VERTEX;
     const int rank_j = __shfl(has ? rank : -1, j & 63, 64);
-    const int where = lane >= G ? -1 : lane < n_fixed ? -2 : j != NBR_NO_VERTEX ? rank_j : -1;
+    const int where = lane >= G ? -1 : is_fixed ? -2 : j != NBR_NO_VERTEX ? rank_j : -1;
     const bool keyed_kept = where >= 0;
     int before = 0;
     for (int u = 0; u < 64; ++u) {
       const int wu = __shfl(where, u, 64);
       before += wu >= 0 && wu < where ? 1 : 0;
     }
-    if (where == -2) place = lane; else if (keyed_kept) place = n_fixed + before;
+    if (where == -2) place = fx >= 0 ? 0 : lane; else if (keyed_kept) place = n_fixed + before;
     const int n_out = n_fixed + __popcll(__ballot(keyed_kept));
     const int gb = lane < G && lane > 0 ? Q.group_end[lane - 1] : 0, sz = lane < G ? Q.group_end[lane] - gb : 0;
     // sizes by place, their inclusive prefix: one wave
-    int mine_src = 0, mine_sz = 0;
+    int mine_src = 0, mine_sz = 0, mine_key = -1;
     for (int u = 0; u < 64; ++u) {
-      const int pu = __shfl(place, u, 64), su = __shfl(gb, u, 64), zu = __shfl(sz, u, 64);
-      if (pu == lane) { mine_src = su; mine_sz = zu; }
+      const int pu = __shfl(place, u, 64), su = __shfl(gb, u, 64), zu = __shfl(sz, u, 64), ku = __shfl(gkey, u, 64);
+      if (pu == lane) { mine_src = su; mine_sz = zu; mine_key = ku; }
     }
     const int end = wave_incl_scan(lane < n_out ? mine_sz : 0);
-    if (lane < n_out) { s_gsrc[lane] = mine_src; s_gend[lane] = end; }
+    if (lane < n_out) { s_gsrc[lane] = mine_src; s_gend[lane] = end; s_gkey[lane] = mine_key; }
     const int kept = __shfl(end, 63, 64);
     if (lane == 0) { s_cnt[2] = n_out; s_cnt[3] = kept; }
   }
@@ -345,7 +356,7 @@ __global__ __launch_bounds__(MB_THREADS) void map_nbr_finish_kernel(MapK M, MapW
   // g. the stream's list: the head's groups at their places, the map's records with the anchor's slot, 0xff up to the previous length
   svs_candidate_point *pts = D.pts + (size_t)b * MP;
   int4 *d4 = reinterpret_cast<int4 *>(pts);
-  const svs_candidate_point *head = D.head + Q.head_off;
+  const svs_candidate_point *head = D.head + (size_t)Q.stream * D.head_stride + Q.head_off;
   const int4 *h4 = reinterpret_cast<const int4 *>(head);
   int32_t *point_id = D.point_id + (size_t)r * MP;
   const int32_t *map_pid = D.map_pid + (size_t)r * MP;
@@ -354,7 +365,9 @@ __global__ __launch_bounds__(MB_THREADS) void map_nbr_finish_kernel(MapK M, MapW
     int g = 0;
     while (s_gend[g] <= rec) ++g;                                  // rec < n_kept = s_gend[n_out - 1]
     const int src = s_gsrc[g] + rec - (g ? s_gend[g - 1] : 0);
-    d4[i] = h4[(size_t)src * 4 + (i & 3)];
+    int4 q = h4[(size_t)src * 4 + (i & 3)];
+    if (D.from_store && (i & 3) == 3) q.y = (unsigned)s_gkey[g] < (unsigned)MAP_MAX_KF ? (int)s_slot[s_gkey[g]] : -1;      // kf_index: the slot that holds the group's keyframe
+    d4[i] = q;
     if ((i & 3) == 0) point_id[rec] = head[src].point_id;
   }
   for (int i = tid; i < n_map; i += MB_THREADS) {

@@ -12,9 +12,10 @@ enum { NBR_OK = 0, NBR_ROOT_OUTSIDE = 1, NBR_OVER = 2 };
 struct nbr_req {
   int32_t stream, root, act, max_nn;
   int32_t n_head, n_groups, n_fixed, prev_len;        // n_groups: the head's groups; prev_len: records of the stream's list before the call
-  int32_t slot_off, slot_raw_off, head_off, pad_;
+  int32_t slot_off, slot_raw_off, head_off;
+  int32_t fixed_at;                                   // 0: the n_fixed leading groups are the fixed ones; 1 + f (the head is a stream's store, n_fixed = 1): group f alone is fixed
   int32_t group_end[NBH_MAX_GROUPS];                  // the head's group ends, then zeros
-  int32_t group_kf[NBH_MAX_GROUPS];                   // the key of every group behind the fixed ones
+  int32_t group_kf[NBH_MAX_GROUPS];                   // the key of every group behind the fixed ones (with fixed_at: of every group)
 };
 
 // what the first launch leaves for the later ones, per request
@@ -26,6 +27,8 @@ struct nbr_mid {
 
 struct MapNbrDst {
   const nbr_req *req; const int32_t *ids; const svs_candidate_point *head;      // staged
+  int head_stride, from_store;    // the head of request Q lies at head + Q.stream * head_stride + Q.head_off; from the front end's new-point store (newpoints.h):
+                                  // head = its record rows, head_stride = record_cap, and a head record's kf_index is written as the slot of its group's key
   int R, VB;
   // the front end's tables: rows per STREAM
   svs_candidate_point *pts; int max_points;

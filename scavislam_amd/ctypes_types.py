@@ -403,3 +403,42 @@ class VertexRequest(C.Structure):
 
 
 assert C.sizeof(KeyframeDecideParams) == 32 and C.sizeof(KeyframeDecideArgs) == 160 and C.sizeof(VertexRequest) == 80
+
+
+# ---- front end: newpoint_map on the device (svs_frontend_newpoints_*, svs_newpoints_prune, svs_frontend_seed_newpoints, svs_frontend_set_candidates_from_newpoints)
+NEWPOINTS_MAX_GROUPS = 64
+NEWPOINTS_PREPEND, NEWPOINTS_REPLACE = 0, 1
+
+
+class NewpointsPutRequest(C.Structure):
+    """svs_newpoints_put_request: a group's records from the host"""
+    _fields_ = [("stream", C.c_int32), ("kf_id", C.c_int32), ("mode", C.c_int32), ("n", C.c_int32), ("h_records", C.c_void_p)]
+
+
+class NewpointsPruneArgs(C.Structure):
+    """svs_newpoints_prune_args: device pointers of a batch of streams"""
+    _fields_ = [("d_res", C.c_void_p), ("res_bstride", C.c_size_t), ("d_pts", C.c_void_p), ("pts_bstride", C.c_size_t), ("d_gated", C.c_void_p),
+                ("gated_bstride", C.c_size_t), ("d_n", C.c_void_p), ("d_n_new", C.c_void_p), ("n", C.c_int32), ("batch", C.c_int32),
+                ("d_store", C.c_void_p), ("store_bstride", C.c_size_t), ("d_group_count", C.c_void_p), ("group_bstride", C.c_size_t),
+                ("d_n_groups", C.c_void_p), ("d_stream", C.c_void_p)]
+
+
+class NewpointsDropRequest(C.Structure):
+    """svs_newpoints_drop_request"""
+    _fields_ = [("stream", C.c_int32), ("n_keys", C.c_int32), ("h_keys", C.c_void_p)]
+
+
+class NewpointsListRequest(C.Structure):
+    """svs_newpoints_list_request: the hand-over of one stream (host pointers)"""
+    _fields_ = [("stream", C.c_int32), ("n_keys", C.c_int32), ("n_tail", C.c_int32), ("pad_", C.c_int32), ("h_keys", C.c_void_p), ("h_slot_kf", C.c_void_p),
+                ("h_tail", C.c_void_p)]
+
+
+class NewpointsListResult(C.Structure):
+    _fields_ = [("n_points", C.c_int32), ("n_head", C.c_int32), ("n_groups", C.c_int32), ("n_no_slot", C.c_int32), ("over_capacity", C.c_int32),
+                ("pad_", C.c_int32 * 3)]
+
+
+NEWPOINTS_LIST_RESULT_FIELDS = tuple(f for f, _ in NewpointsListResult._fields_ if f != "pad_")
+assert C.sizeof(NewpointsPutRequest) == 24 and C.sizeof(NewpointsPruneArgs) == 120 and C.sizeof(NewpointsDropRequest) == 16
+assert C.sizeof(NewpointsListRequest) == 40 and C.sizeof(NewpointsListResult) == 32

@@ -698,7 +698,15 @@ class StereoFrontend:
             out.append(o)
         return out
 
-    def setNeighborhoodFromMap(self, resident_map, requests, refresh_poses=True, vertex_cap=64, want_records=False, want_tables=False):
+    def setNeighborhoodFromStore(self, resident_map, requests, refresh_poses=True, vertex_cap=64, want_records=False, want_tables=False):
+        """setNeighborhoodFromMap with the head taken from the streams' new-point stores (svs_frontend_set_neighborhood_from_store): the store's group act_id is the
+        fixed group, every other group a keyed one.  requests: dicts with stream, root_id, act_id, slot_kf and optionally max_num_neighbors; no head field.  Returns
+        what setNeighborhoodFromMap returns"""
+        if any(k in q for q in requests for k in ("head", "head_group_end", "n_fixed_groups", "head_group_kf")):
+            raise ValueError("the head comes from the store")
+        return self.setNeighborhoodFromMap(resident_map, requests, refresh_poses, vertex_cap, want_records, want_tables, _from_store=True)
+
+    def setNeighborhoodFromMap(self, resident_map, requests, refresh_poses=True, vertex_cap=64, want_records=False, want_tables=False, _from_store=False):
         """Backend::computeNeighborhood(root_id) whole (backend.cpp:244-386) on the device-resident map, which is only read: findNeighborsOfRoot, the point and
         anchor walk, computeAbsolutePose for the vertices outside the window, the active keyframe's strength_to_neighbors, the head's groups put into that order
         (stereo_frontend.cpp:1007-1029), the stream's list, slot poses and resident vertex table (svs_frontend_set_neighborhood_from_root).
@@ -720,8 +728,11 @@ class StereoFrontend:
                 raise ValueError("slot_kf needs one entry per keyframe slot of the front end, head_group_kf one per head group")
             keep += [slot, head, ge, gk]
             r.stream, r.root_id, r.act_id, r.max_num_neighbors = int(q.get("stream", 0)), int(q["root_id"]), int(q["act_id"]), int(q.get("max_num_neighbors", 10))
+            r.h_slot_kf = slot.ctypes.data
+            if _from_store and "head" not in q:
+                continue
             r.n_head, r.n_head_groups, r.n_fixed_groups = len(head), len(ge), int(q.get("n_fixed_groups", len(ge)))
-            r.h_slot_kf, r.h_head_group_end, r.h_head, r.h_head_group_kf = slot.ctypes.data, ge.ctypes.data, head.ctypes.data if len(head) else None, gk.ctypes.data
+            r.h_head_group_end, r.h_head, r.h_head_group_kf = ge.ctypes.data, head.ctypes.data if len(head) else None, gk.ctypes.data
         res = (NbrResult * max(n, 1))()
         mp, m = self.max_points, max(n, 1)
         pid, vid, vT = np.empty((m, mp), np.int32), np.empty((m, vertex_cap), np.int32), np.empty((m, vertex_cap, 12), np.float64)
@@ -731,7 +742,8 @@ class StereoFrontend:
         vtx = np.empty((m, KF_MAX_VERTICES), KF_VERTEX_DTYPE) if want_tables else None
         slot_T = np.empty((m, self.max_keyframes, 12), np.float64)
         ptr = lambda a: a.ctypes.data if a is not None else None
-        self.ctx.check(self.ctx.lib.svs_frontend_set_neighborhood_from_root(self.h, resident_map.h, n, arr, int(bool(refresh_poses)), int(vertex_cap), res, ptr(pid), ptr(vid),
+        call = self.ctx.lib.svs_frontend_set_neighborhood_from_store if _from_store else self.ctx.lib.svs_frontend_set_neighborhood_from_root
+        self.ctx.check(call(self.h, resident_map.h, n, arr, int(bool(refresh_poses)), int(vertex_cap), res, ptr(pid), ptr(vid),
                                                                             ptr(vT), ptr(act), ptr(strength), ptr(table), ptr(tab), ptr(vtx), ptr(slot_T)))
         out = []
         for i in range(n):
@@ -864,16 +876,11 @@ class StereoFrontend:
         T = np.ascontiguousarray(np.broadcast_to(T, (self.n_streams, 12)))
         self.ctx.check(self.ctx.lib.svs_frontend_recompute_cloud(self.h, T.ctypes.data))
 
-    def seedKeyframes(self, requests, params=None, cap=None):
-        """addNewPoints / addMorePoints (stereo_frontend.cpp:682-823) for a list of new keyframes from the state the last frame left on the device.
-        requests: dicts with stream, mode (SEED_FIRST / SEED_MORE), kf_index, first_point_id and optionally T_newkey_from_cur (default: identity), seed,
-        order (three index arrays into the levels' corner lists; absent: the generated order).  Returns a list of (CANDIDATE_DTYPE records in the
-        reference's list order, counts per level)."""
-        from .ctypes_types import SeedParams, SeedRequest
-        prm = params or SeedParams.reference(n_levels=min(3, self.params.n_levels or 3))
-        cap = prm.max_records() if cap is None else int(cap)
-        n = len(requests)
-        req = (SeedRequest * max(n, 1))()
+    @staticmethod
+    def _seed_requests(requests):
+        """the svs_seed_request array of seedKeyframes / seedNewpoints, and the arrays it points into"""
+        from .ctypes_types import SeedRequest
+        req = (SeedRequest * max(len(requests), 1))()
         keep = []
         for r, q in zip(req, requests):
             r.stream, r.mode, r.kf_index, r.first_point_id = int(q.get("stream", 0)), int(q["mode"]), int(q.get("kf_index", 0)), int(q.get("first_point_id", 0))
@@ -886,6 +893,18 @@ class StereoFrontend:
                     o = np.ascontiguousarray(o, np.int32)
                     keep.append(o)
                     r.h_order[l], r.n_order[l] = o.ctypes.data, len(o)
+        return req, keep
+
+    def seedKeyframes(self, requests, params=None, cap=None):
+        """addNewPoints / addMorePoints (stereo_frontend.cpp:682-823) for a list of new keyframes from the state the last frame left on the device.
+        requests: dicts with stream, mode (SEED_FIRST / SEED_MORE), kf_index, first_point_id and optionally T_newkey_from_cur (default: identity), seed,
+        order (three index arrays into the levels' corner lists; absent: the generated order).  Returns a list of (CANDIDATE_DTYPE records in the
+        reference's list order, counts per level)."""
+        from .ctypes_types import SeedParams
+        prm = params or SeedParams.reference(n_levels=min(3, self.params.n_levels or 3))
+        cap = prm.max_records() if cap is None else int(cap)
+        n = len(requests)
+        req, keep = self._seed_requests(requests)
         out = np.zeros((max(n, 1), max(cap, 1)), CANDIDATE_DTYPE)
         cnt = np.zeros((max(n, 1), 3), np.int32)
         self.ctx.check(self.ctx.lib.svs_frontend_seed_keyframes(self.h, n, req, C.byref(prm), out.ctypes.data, cap, cnt.ctypes.data))
@@ -946,6 +965,118 @@ class StereoFrontend:
             if want_lists and d["valid"] and (want_lists == 2 or d["decision"] == KF_DROP):
                 nn, nt = int(d["n_new"]), int(d["n_track"])
                 o.update(new=new[b, :nn].copy(), track=track[b, :nt].copy(), new_rec=new_rec[b, :nn].copy(), track_rec=track_rec[b, :nt].copy())
+            out.append(o)
+        return out
+
+    # ---- newpoint_map on the device (svs_frontend_newpoints_*: stereo_frontend.cpp:360-365, :808, :989-1029; the rules are in the header)
+    def reserveNewpoints(self, record_cap, group_cap=64):
+        """once: room for record_cap records in at most group_cap groups (keyframes) per stream"""
+        self.ctx.check(self.ctx.lib.svs_frontend_newpoints_reserve(self.h, int(record_cap), int(group_cap)))
+        self.newpoint_record_cap = int(record_cap)
+
+    def putNewpoints(self, requests):
+        """groups from the host.  requests: dicts with stream, kf_id, records (CANDIDATE_DTYPE, list order) and mode (NEWPOINTS_PREPEND, the default, or
+        NEWPOINTS_REPLACE); an absent key creates its group at the end of the stream's store"""
+        from .ctypes_types import NEWPOINTS_PREPEND, NewpointsPutRequest
+        n = len(requests)
+        arr = (NewpointsPutRequest * max(n, 1))()
+        keep = []
+        for r, q in zip(arr, requests):
+            rec = np.ascontiguousarray(q.get("records", np.zeros(0, CANDIDATE_DTYPE)), CANDIDATE_DTYPE).reshape(-1)
+            keep.append(rec)
+            r.stream, r.kf_id, r.mode, r.n = int(q.get("stream", 0)), int(q["kf_id"]), int(q.get("mode", NEWPOINTS_PREPEND)), len(rec)
+            r.h_records = rec.ctypes.data if len(rec) else None
+        self.ctx.check(self.ctx.lib.svs_frontend_newpoints_put(self.h, n, arr))
+
+    def seedNewpoints(self, requests, params=None, want_records=False):
+        """seedKeyframes whose records stay on the device: request r's records are prepended to group kf_id of its stream.  requests: seedKeyframes' dicts plus
+        kf_id.  Returns the counts per level of every request ([n][3]); want_records (tests): a list of (records, counts) as seedKeyframes returns it"""
+        from .ctypes_types import SeedParams
+        prm = params or SeedParams.reference(n_levels=min(3, self.params.n_levels or 3))
+        cap = prm.max_records()
+        n = len(requests)
+        req, keep = self._seed_requests(requests)
+        kf = np.array([int(q["kf_id"]) for q in requests], np.int32).reshape(-1)
+        out = np.zeros((max(n, 1), max(cap, 1)), CANDIDATE_DTYPE) if want_records else None
+        cnt = np.zeros((max(n, 1), 3), np.int32)
+        self.ctx.check(self.ctx.lib.svs_frontend_seed_newpoints(self.h, n, req, kf.ctypes.data if n else None, C.byref(prm), cnt.ctypes.data,
+                                                                out.ctypes.data if want_records else None, cap))
+        if want_records:
+            return [(out[r, :int(cnt[r].sum())].copy(), cnt[r].copy()) for r in range(n)]
+        return cnt[:n].copy()
+
+    def pruneNewpoints(self, streams=None):
+        """behind a step that drops (stereo_frontend.cpp:360-365): the matched new points of the last step leave every group of the named streams (default: all).
+        Returns one (n_removed, counts per group in store order) per stream named"""
+        from .ctypes_types import NEWPOINTS_MAX_GROUPS
+        st = np.ascontiguousarray(range(self.n_streams) if streams is None else streams, np.int32).reshape(-1)
+        n = len(st)
+        removed, counts = np.zeros(max(n, 1), np.int32), np.zeros((max(n, 1), NEWPOINTS_MAX_GROUPS), np.int32)
+        self.ctx.check(self.ctx.lib.svs_frontend_newpoints_prune(self.h, n, st.ctypes.data, removed.ctypes.data, counts.ctypes.data))
+        return [(int(removed[i]), counts[i].copy()) for i in range(n)]
+
+    def dropNewpointGroups(self, requests):
+        """requests: dicts with stream and keys; returns the number of groups each removed"""
+        from .ctypes_types import NewpointsDropRequest
+        n = len(requests)
+        arr = (NewpointsDropRequest * max(n, 1))()
+        keep = []
+        for r, q in zip(arr, requests):
+            keys = np.ascontiguousarray(q["keys"], np.int32).reshape(-1)
+            keep.append(keys)
+            r.stream, r.n_keys, r.h_keys = int(q.get("stream", 0)), len(keys), keys.ctypes.data if len(keys) else None
+        found = np.zeros(max(n, 1), np.int32)
+        self.ctx.check(self.ctx.lib.svs_frontend_newpoints_drop_groups(self.h, n, arr, found.ctypes.data))
+        return [int(f) for f in found[:n]]
+
+    def newpoints(self, streams=None, want_records=True):
+        """the stores as they lie on the device: per stream named (default: all) a dict with keys, counts (store order), records (the groups back to back) and raw
+        (the full table rows and the whole record row as bytes: tests)"""
+        from .ctypes_types import NEWPOINTS_MAX_GROUPS as G
+        st = np.ascontiguousarray(range(self.n_streams) if streams is None else streams, np.int32).reshape(-1)
+        n, cap = len(st), self.newpoint_record_cap
+        ng, keys, counts = np.zeros(max(n, 1), np.int32), np.zeros((max(n, 1), G), np.int32), np.zeros((max(n, 1), G), np.int32)
+        rec = np.zeros((max(n, 1), cap), CANDIDATE_DTYPE) if want_records else None
+        self.ctx.check(self.ctx.lib.svs_frontend_newpoints_get(self.h, n, st.ctypes.data, ng.ctypes.data, keys.ctypes.data, counts.ctypes.data,
+                                                               rec.ctypes.data if want_records else None))
+        out = []
+        for i in range(n):
+            g = int(ng[i])
+            o = dict(keys=keys[i, :g].copy(), counts=counts[i, :g].copy(), raw=(int(ng[i]), keys[i].tobytes(), counts[i].tobytes()))
+            if want_records:
+                o["records"] = rec[i, :int(counts[i, :g].sum())].copy()
+            out.append(o)
+        return out
+
+    def setCandidatesFromNewpoints(self, requests, want_records=False):
+        """matchAndTrack's lists (stereo_frontend.cpp:989-1029) with the head taken from the stores.  requests: dicts with stream, keys (the active keyframe's id,
+        then its strength_to_neighbors in order), slot_kf (the keyframe id kept in each slot, -1 for none) and optionally tail (CANDIDATE_DTYPE: the
+        neighbourhood's point_list).  Returns one dict of the svs_newpoints_list_result fields per request; want_records adds `table` and `group_end`, the whole candidate table and its rows of group ends"""
+        from .ctypes_types import NEWPOINTS_LIST_RESULT_FIELDS, NewpointsListRequest, NewpointsListResult
+        n = len(requests)
+        arr = (NewpointsListRequest * max(n, 1))()
+        keep = []
+        for r, q in zip(arr, requests):
+            keys = np.ascontiguousarray(q["keys"], np.int32).reshape(-1)
+            slot = np.ascontiguousarray(q["slot_kf"], np.int32).reshape(-1)
+            tail = np.ascontiguousarray(q.get("tail", np.zeros(0, CANDIDATE_DTYPE)), CANDIDATE_DTYPE).reshape(-1)
+            if len(slot) != self.max_keyframes:
+                raise ValueError("slot_kf needs one entry per keyframe slot of the front end")
+            keep += [keys, slot, tail]
+            r.stream, r.n_keys, r.n_tail = int(q.get("stream", 0)), len(keys), len(tail)
+            r.h_keys, r.h_slot_kf, r.h_tail = keys.ctypes.data if len(keys) else None, slot.ctypes.data, tail.ctypes.data if len(tail) else None
+        res = (NewpointsListResult * max(n, 1))()
+        table = np.empty((self.n_streams, self.max_points), CANDIDATE_DTYPE) if want_records else None
+        ends = np.empty((self.n_streams, 64), np.int32) if want_records else None
+        self.ctx.check(self.ctx.lib.svs_frontend_set_candidates_from_newpoints(self.h, n, arr, res, table.ctypes.data if want_records else None,
+                                                                               ends.ctypes.data if want_records else None))
+        out = []
+        for i in range(n):
+            o = {f: int(getattr(res[i], f)) for f in NEWPOINTS_LIST_RESULT_FIELDS}
+            if not o["over_capacity"]:
+                self.n_points[arr[i].stream] = o["n_points"]
+            if want_records:
+                o["table"], o["group_end"] = table, ends
             out.append(o)
         return out
 
