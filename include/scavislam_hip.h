@@ -245,6 +245,28 @@ typedef struct {
    tie-break order are those of QuadTree::query. d_out: [n_batch][n_pts] */
 int svs_match(svs_ctx *ctx, const svs_match_args *a, svs_fast *f, svs_match_result *d_out);
 
+/* ---- optional sub-pixel refinement of a match: GuidedMatcher::subpixelAccuracy (matcher.cpp:241-309), which returnBestMatch calls (:198) and whose body the
+   reference keeps behind `#if 0`.  For every record with status SVS_MATCH_OK: a 2-D Gauss-Newton alignment of the current image's 8 x 8 patch at the integer match
+   (u, v) to the warped key patch (warpAffinve at half size 5, central-difference gradients, bilinear taps as interpolateMat_8u), at most `iterations` steps, stopped
+   once a step is below `eps` on both axes; then createObervation at the refined f32 position (the disparity is read at its truncation).  tests/subpix_model.py is
+   the definition, bit for bit.  Outcomes per record (svs_subpix_info::state):
+     REFINED    obs rewritten from (u + dx, v + dy)
+     NO_DISP    no positive disparity at the truncated refined position: status becomes SVS_MATCH_NO_DISP, obs stays
+     SINGULAR   the key patch's normal matrix has det <= 0 (no texture, or a pure edge): the record stays as it is (the reference's live behaviour, :306)
+     SHIFT      an iterate left [-max_shift, max_shift]^2, or (u, v) lies outside the matcher's own margin isInFrame(uv, 6) -- nothing is read then: the record stays
+     UNTOUCHED  status was not SVS_MATCH_OK: the record is read no further than its status and not written
+   u, v, znssd and xyz_actkey never change.  The solve of the 2 x 2 system is f64 (the reference's dead code: Eigen's f32 ldlt) -- a declared departure.
+   Not covered: the registrar's two matches (svs_reg_*) and warpPatchProjective. */
+typedef struct { int32_t iterations; float max_shift; float eps; int32_t pad_; } svs_subpix_params;  /* defaults 8, 1.5f, 0.03f */
+void svs_subpix_params_default(svs_subpix_params *p);
+enum { SVS_SUBPIX_REFINED = 0, SVS_SUBPIX_UNTOUCHED, SVS_SUBPIX_SINGULAR, SVS_SUBPIX_SHIFT, SVS_SUBPIX_NO_DISP };
+typedef struct { float dx, dy; int32_t n_iter, state; } svs_subpix_info;   /* dx, dy: the offset the observation was made with (NO_DISP: asked for with); 0 where the
+                                                                              record was kept.  n_iter: the Gauss-Newton steps computed, the refused one included */
+/* refines d_results [n_batch][n_pts] (a->out_bstride apart) in place; a = the arguments svs_match was called with (its corners are not needed); d_info optional, laid
+   out like d_results.  Asynchronous on the context's stream, like svs_match.  Refused (SVS_ERR_INVALID, nothing launched): max_shift outside (0, 2] -- with it every
+   tap lies inside the image, columns u - 6 .. u + 6 --, iterations outside 1 .. 16, eps < 0. */
+int svs_match_subpixel(svs_ctx *ctx, const svs_match_args *a, const svs_subpix_params *prm, svs_match_result *d_results, svs_subpix_info *d_info);
+
 /* ---- motion-only refinement: replaces BA_SE3_XYZ_STEREO::calcFastMotionOnly (pose_optimizer.h:134-298) as
    called behind the matcher at stereo_frontend.cpp:1058-1063 ------------------------------------------------*/
 typedef struct {
@@ -508,6 +530,14 @@ int svs_frontend_process_frames(svs_frontend *fe, const svs_frames_dev *in, cons
 /* blocking downloads after svs_frontend_process_frames: everything of one stream; refined poses [n_streams][12] + tracking flags of all (NULL = not wanted) */
 int svs_frontend_results(svs_frontend *fe, int stream, svs_frame_result *out, svs_match_result *h_matches, svs_gated_point *h_gated);
 int svs_frontend_poses(svs_frontend *fe, double *h_T_cur_from_actkey, int32_t *h_tracking_ok);
+/* sub-pixel matches (svs_match_subpixel): the front end's steps run the pass behind their matcher from the next step on -- one launch between the matcher and
+   matchAndTrack's cut, which therefore counts the observations left after the refinement (the reference refines inside match); the refinement, the gate and the
+   records handed out see the refined observations.  prm == NULL switches it off (the state of a new front end): a step then runs exactly what it ran before the
+   option existed.  Parameters are refused as svs_match_subpixel refuses them; not between submit_frame and wait_frame. */
+int svs_frontend_set_subpixel(svs_frontend *fe, const svs_subpix_params *prm);
+/* blocking: the svs_subpix_info records of one stream's last step, n_points of them (index = candidate index).  Refused while the option is off, and before a
+   step has matched with it on. */
+int svs_frontend_subpixel_info(svs_frontend *fe, int stream, svs_subpix_info *h_info);
 /* profiling: hipEvents between the stages of the following process_frame(s) / submit_frame calls (off by default: an event costs ~4 us of stream time).
    svs_frontend_stage_times (blocking): ms[SVS_FRONTEND_STAGES] of the last such call, in the order of the reference's per_mon_ stages
    (stereo_frontend.cpp:190-302): preprocess (upload or copy + pyramid), dense tracking, stereo, fast, match, pose refinement (calcFastMotionOnly),

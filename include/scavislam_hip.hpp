@@ -209,28 +209,51 @@ class GuidedMatcher {
     const size_t n = ap_map.size();
     results->assign(n, svs_match_result());
     if (n == 0) return true;
-    double Tcw[12], Twk[12];
-    mul(T_cur_from_actkey, T_actkey_from_w, Tcw);     // matcher.cpp:330
-    inv(T_actkey_from_w, Twk);                        // matcher.cpp:328
-    DeviceBuffer<svs_keyframe> d_kf(ctx_, keyframes.size());
-    DeviceBuffer<svs_candidate_point> d_pts(ctx_, n);
-    DeviceBuffer<double> d_T(ctx_, 24);
-    DeviceBuffer<svs_match_result> d_out(ctx_, n);
-    double TT[24];
-    std::memcpy(TT, Tcw, sizeof Tcw); std::memcpy(TT + 12, Twk, sizeof Twk);
-    if (!d_kf.upload(keyframes.data(), keyframes.size()) || !d_pts.upload(ap_map.data(), n) || !d_T.upload(TT, 24)) return false;
-    svs_match_args a;
-    std::memset(&a, 0, sizeof a);
-    a.d_kfs = d_kf.get(); a.n_kf = (int32_t)keyframes.size(); a.d_pts = d_pts.get(); a.n_pts = (int32_t)n;
-    a.d_T_cur_from_w = d_T.get(); a.d_T_w_from_actkey = d_T.get() + 12;
-    for (int l = 0; l < SVS_NUM_PYR_LEVELS; ++l) { a.d_cur_pyr[l] = cur_frame.pyr(l); a.cur_stride[l] = cur_frame.stride(l); a.cam_vec[l] = cam_vec[l]; }
-    a.d_disp = cur_frame.disp(); a.disp_stride = cur_frame.stride(0);
-    a.search_radius = SEARCHRADIUS; a.thr_mean = thr_mean; a.thr_std = thr_std; a.n_batch = 1;
-    if (!ctx_.check(svs_match(ctx_.get(), &a, feature_tree.handle(), d_out.get()))) return false;
-    return d_out.download(results->data(), n);
+    Call c(ctx_, keyframes, T_cur_from_actkey, T_actkey_from_w, cur_frame, cam_vec, ap_map, SEARCHRADIUS, thr_mean, thr_std);
+    if (!c.ok || !ctx_.check(svs_match(ctx_.get(), &c.a, feature_tree.handle(), c.out.get()))) return false;
+    return c.out.download(results->data(), n);
+  }
+  // subpixelAccuracy (matcher.cpp:241-309; returnBestMatch calls it, the reference keeps its body behind `#if 0`) on the records match() returned for the same
+  // arguments: the SVS_MATCH_OK records get their observation from the refined position (or become SVS_MATCH_NO_DISP), in place; info: one record per result,
+  // optional.  See svs_match_subpixel.
+  bool refineSubpixel(const std::vector<svs_keyframe> &keyframes, const double T_cur_from_actkey[12], const double T_actkey_from_w[12], const FrameDev &cur_frame,
+                      const svs_cam cam_vec[SVS_NUM_PYR_LEVELS], const std::vector<svs_candidate_point> &ap_map, const svs_subpix_params &prm,
+                      std::vector<svs_match_result> *results, std::vector<svs_subpix_info> *info = 0) {
+    const size_t n = ap_map.size();
+    if (results->size() != n) return false;
+    if (info) info->assign(n, svs_subpix_info());
+    if (n == 0) return true;
+    Call c(ctx_, keyframes, T_cur_from_actkey, T_actkey_from_w, cur_frame, cam_vec, ap_map, 0, 0, 0);
+    DeviceBuffer<svs_subpix_info> d_info(ctx_, info ? n : 0);
+    if (!c.ok || !c.out.upload(results->data(), n)) return false;
+    if (!ctx_.check(svs_match_subpixel(ctx_.get(), &c.a, &prm, c.out.get(), info ? d_info.get() : 0))) return false;
+    return c.out.download(results->data(), n) && (!info || d_info.download(info->data(), n));
   }
 
  private:
+  // the device copies of one call's tables and the svs_match_args over them
+  struct Call {
+    DeviceBuffer<svs_keyframe> kf;
+    DeviceBuffer<svs_candidate_point> pts;
+    DeviceBuffer<double> T;
+    DeviceBuffer<svs_match_result> out;
+    svs_match_args a;
+    bool ok;
+    Call(const Context &ctx, const std::vector<svs_keyframe> &keyframes, const double T_cur_from_actkey[12], const double T_actkey_from_w[12], const FrameDev &cur_frame,
+         const svs_cam cam_vec[SVS_NUM_PYR_LEVELS], const std::vector<svs_candidate_point> &ap_map, int SEARCHRADIUS, int thr_mean, int thr_std)
+        : kf(ctx, keyframes.size()), pts(ctx, ap_map.size()), T(ctx, 24), out(ctx, ap_map.size()) {
+      double TT[24];
+      mul(T_cur_from_actkey, T_actkey_from_w, TT);     // matcher.cpp:330
+      inv(T_actkey_from_w, TT + 12);                   // matcher.cpp:328
+      ok = kf.upload(keyframes.data(), keyframes.size()) && pts.upload(ap_map.data(), ap_map.size()) && T.upload(TT, 24);
+      std::memset(&a, 0, sizeof a);
+      a.d_kfs = kf.get(); a.n_kf = (int32_t)keyframes.size(); a.d_pts = pts.get(); a.n_pts = (int32_t)ap_map.size();
+      a.d_T_cur_from_w = T.get(); a.d_T_w_from_actkey = T.get() + 12;
+      for (int l = 0; l < SVS_NUM_PYR_LEVELS; ++l) { a.d_cur_pyr[l] = cur_frame.pyr(l); a.cur_stride[l] = cur_frame.stride(l); a.cam_vec[l] = cam_vec[l]; }
+      a.d_disp = cur_frame.disp(); a.disp_stride = cur_frame.stride(0);
+      a.search_radius = SEARCHRADIUS; a.thr_mean = thr_mean; a.thr_std = thr_std; a.n_batch = 1;
+    }
+  };
   static void mul(const double *A, const double *B, double *C) {
     for (int i = 0; i < 3; ++i) { for (int j = 0; j < 4; ++j) C[4 * i + j] = A[4 * i] * B[j] + A[4 * i + 1] * B[4 + j] + A[4 * i + 2] * B[8 + j]; C[4 * i + 3] += A[4 * i + 3]; }
   }
@@ -561,6 +584,12 @@ class StereoFrontend {
     return res->tracking_ok != 0;
   }
   bool recomputeDensePointCloud(const double T_cur_from_actkey[12]) { return ctx_.check(svs_frontend_recompute_cloud(fe_, T_cur_from_actkey)); }
+  // sub-pixel matches from the next step on (one stream or a batch): GuidedMatcher::refineSubpixel's pass behind the step's matcher; prm == 0 switches it off again
+  bool setSubpixelAccuracy(const svs_subpix_params *prm) { return ctx_.check(svs_frontend_set_subpixel(fe_, prm)); }
+  bool subpixelInfo(std::vector<svs_subpix_info> *info, int n_points, int stream = 0) {      // the last step's records of one stream; refused while the option is off
+    info->assign((size_t)(n_points > 0 ? n_points : 0), svs_subpix_info());
+    return ctx_.check(svs_frontend_subpixel_info(fe_, stream, info->data()));
+  }
   // Backend::computeNeighborhood (backend.cpp:244-386) from the vertex list onwards, on the device-resident map: neighborhood_->point_list is written into the
   // candidate list behind the new-point groups (setCandidateLists' groups 0 .. G-2: newpoints / newpoint_group_end), neighborhood_->vertex_map comes back as ids
   // and poses, and with refresh_poses every slot of slot_keyframe_ids that names a keyframe of the map takes the map's pose.  vertex_ids: the root first, then

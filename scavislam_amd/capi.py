@@ -8,7 +8,7 @@ import ctypes as C
 import os
 import weakref
 
-from .ctypes_types import BaParams, BaStats, Cam, FastGrid, KeyframeDecideArgs, KeyframeDecideParams, LoopCheck, LoopLocation, LoopLocationResult, LoopResult, MapAddKeyframeArgs, MapConstraintRequest, MapStrengthResult, MapWindowResult, NbhRequest, NbhResult, NbrRequest, NbrResult, NewpointsDropRequest, NewpointsListRequest, NewpointsListResult, NewpointsPruneArgs, NewpointsPutRequest, PoseOptParams, PoseOptStats, RegCommitResult, RegMapRequest, RegParams, RegRequest, RegResult, SeedArgs, SeedParams, SeedRequest, StereoParams, SurfParams, VertexRequest, VocabParams, VocabResult
+from .ctypes_types import BaParams, BaStats, Cam, FastGrid, KeyframeDecideArgs, KeyframeDecideParams, LoopCheck, LoopLocation, LoopLocationResult, LoopResult, MapAddKeyframeArgs, MapConstraintRequest, MapStrengthResult, MapWindowResult, NbhRequest, NbhResult, NbrRequest, NbrResult, NewpointsDropRequest, NewpointsListRequest, NewpointsListResult, NewpointsPruneArgs, NewpointsPutRequest, PoseOptParams, PoseOptStats, RegCommitResult, RegMapRequest, RegParams, RegRequest, RegResult, SeedArgs, SeedParams, SeedRequest, StereoParams, SubpixParams, SurfParams, VertexRequest, VocabParams, VocabResult
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SVS_LIB_PATH") or os.path.join(_HERE, "libscavislam_hip.so")   # override = kernel A/B experiments only
@@ -120,6 +120,9 @@ _SIGS = {
     "svs_fast_device_view": [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_int32), C.POINTER(C.c_size_t), C.POINTER(C.c_int32),
                              C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)],
     "svs_match": [C.c_void_p, C.POINTER(MatchArgs), C.c_void_p, C.c_void_p],
+    "svs_match_subpixel": [C.c_void_p, C.POINTER(MatchArgs), C.POINTER(SubpixParams), C.c_void_p, C.c_void_p],
+    "svs_frontend_set_subpixel": [C.c_void_p, C.POINTER(SubpixParams)],
+    "svs_frontend_subpixel_info": [C.c_void_p, C.c_int, C.c_void_p],
     "svs_pointcloud_cpu_sem": [C.c_void_p, C.c_void_p, C.c_int, C.c_size_t, C.POINTER(Cam), C.c_int,
                                C.c_void_p, C.c_void_p, C.c_size_t, C.c_int],
     "svs_dense_pass_cpu_sem": [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_size_t,
@@ -305,7 +308,7 @@ _SIGS = {
                             C.POINTER(C.c_int32)],
     "svs_ba_graph_stats": [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)],
 }
-EXPORTS = sorted(list(_SIGS) + ["svs_ctx_stream", "svs_last_error", "svs_api_version", "svs_pose_opt_params_default", "svs_keyframe_decide_params_default", "svs_seed_params_default", "svs_reg_params_default", "svs_vocab_params_default", "svs_surf_params_default"])
+EXPORTS = sorted(list(_SIGS) + ["svs_ctx_stream", "svs_last_error", "svs_api_version", "svs_pose_opt_params_default", "svs_keyframe_decide_params_default", "svs_seed_params_default", "svs_reg_params_default", "svs_vocab_params_default", "svs_surf_params_default", "svs_subpix_params_default"])
 API_VERSION = 9      # SVS_API_VERSION of include/scavislam_hip.h this binding was written against
 
 
@@ -342,6 +345,8 @@ def load():
         lib.svs_vocab_params_default.restype = None
         lib.svs_surf_params_default.argtypes = [C.c_void_p]
         lib.svs_surf_params_default.restype = None
+        lib.svs_subpix_params_default.argtypes = [C.c_void_p]
+        lib.svs_subpix_params_default.restype = None
         if lib.svs_api_version() != API_VERSION:
             raise SvsError(f"{LIB_PATH} was built with SVS_API_VERSION {lib.svs_api_version()}, this binding expects {API_VERSION}: rebuild (__graft_entry__.build())")
         _LIB = lib

@@ -48,6 +48,9 @@ struct svs_ctx {
   // set by the one-call front end around svs_match (few keyframes): the tracked pose / the active keyframe's pose per stream, from which the matcher's prediction kernel forms
   // T_cur_from_w / T_w_from_actkey and the per-keyframe relative poses itself (match_predict.inc) -- two small launches less between tracker and matcher
   const double *match_src_T = nullptr, *match_src_Ta = nullptr;
+  // left by svs_match: its prediction records in match_scratch ([batch][pts]); valid until the next call that takes match_scratch (match.hip)
+  void *match_pred = nullptr;
+  int match_pred_batch = 0, match_pred_pts = 0;
   DevBuf<void> seq_buf;                                   // the per-pass term buffers of both modes
   DevBuf<unsigned> seq_stats;                             // device: [0] exact float sums formed, [1] of those by the fallback chain (svs_ctx_get_stat)
   owned::Event spin_ev;              // "a device-filling kernel of mine has finished" (svs_spin_enter / svs_spin_leave)
@@ -139,6 +142,13 @@ int svs_motion_only_gate_cloud(svs_ctx *ctx, const svs_match_result *d_results, 
 int svs_process_matched_points_dev(svs_ctx *ctx, const svs_match_result *d_results, const svs_candidate_point *d_pts, int n, size_t res_bstride,
                                    size_t pts_bstride, const int32_t *d_n_new_records, const svs_cam *cam, const double *d_T, float max_reproj_error,
                                    svs_gated_point *d_gated, size_t gated_bstride, svs_point_stats *d_stats, int batch);
+
+// what svs_match_subpixel and svs_frontend_set_subpixel accept: with max_shift in (0, 2] every tap of the pass lies inside the image (NaNs fail every compare)
+inline bool svs_subpix_params_ok(const svs_subpix_params *p) {
+  return p->iterations >= 1 && p->iterations <= 16 && p->max_shift > 0.f && p->max_shift <= 2.f && p->eps >= 0.f;
+}
+// internal: svs_match_subpixel right behind svs_match(ctx, a, ...), on the prediction records that call left (match.hip)
+int svs_match_subpixel_behind_match(svs_ctx *ctx, const svs_match_args *a, const svs_subpix_params *prm, svs_match_result *d_results, svs_subpix_info *d_info);
 
 // internal: the dense clouds of the three levels in one launch (motion.hip)
 int svs_pointcloud_cpu_sem_levels(svs_ctx *ctx, const float *d_disp, int disp_stride, size_t disp_bstride, const svs_cam *cams, const double *d_T, float *const *d_cloud,

@@ -165,6 +165,12 @@ struct svs_frontend {
   // since the last first frame, or the list was replaced behind the step), staging blocks grown on demand
   int n_gated = -1;
   PinnedBuf<uint8_t> h_seed; DevBuf<uint8_t> d_seed;
+  // optional sub-pixel refinement of the matches (svs_frontend_set_subpixel; match.hip: match_subpix.inc): one launch behind the matcher while `subpix` is set.
+  // d_subpix_info [B][max_points] is allocated when the option is first switched on; subpix_n = records per stream the last step's pass covered, -1: none
+  bool subpix = false;
+  svs_subpix_params subpix_prm{};
+  DevBuf<svs_subpix_info> d_subpix_info;
+  int subpix_n = -1;
   // svs_frontend_set_candidates_from_map: the staged requests and, behind them, what comes back; grown on demand
   PinnedBuf<uint8_t> h_nbh; DevBuf<uint8_t> d_nbh;
   // the keyframe decision (svs_frontend_set_vertex_table / svs_frontend_decide_keyframes, keyframe.hip): the streams' resident vertex tables, the staging block
@@ -770,6 +776,8 @@ int frontend_chain(svs_frontend *fe, bool first, DispView dv, bool ext_frames = 
       rc = svs_match(ctx, &ma, F, fe->d_res);
       ctx->match_src_T = ctx->match_src_Ta = nullptr;
       if (rc) return rc;
+      // the reference refines inside match (returnBestMatch, matcher.cpp:198-204): the cut below counts the observations that are left after the refinement
+      if (fe->subpix && (rc = svs_match_subpixel_behind_match(ctx, &ma, &fe->subpix_prm, fe->d_res, fe->d_subpix_info))) return rc;
       if (fe->max_groups_used > 2) {
         hipLaunchKernelGGL(frontend_group_cut_kernel, dim3(B), dim3(256), 0, ctx->stream, fe->d_res, (size_t)fe->max_points, (const int32_t *)fe->d_group_end,
                            (const int32_t *)fe->d_n_groups, fe->prm.num_max_points);
@@ -820,6 +828,7 @@ int frontend_chain(svs_frontend *fe, bool first, DispView dv, bool ext_frames = 
   if (pipe) { SVS_HIP(ctx, hipEventRecord(fe->ev_late[par], ctx->stream)); ++fe->pipe_run; }
   fe->last_disp = dv.p; fe->last_dstride = dv.stride; fe->last_dbstride = dv.bstride;
   fe->n_gated = first ? -1 : n;
+  fe->subpix_n = fe->subpix && !first && n > 0 ? n : -1;
   return SVS_OK;
 }
 void frontend_rotate(svs_frontend *fe) {
@@ -971,6 +980,32 @@ extern "C" int svs_frontend_results(svs_frontend *fe, int stream, svs_frame_resu
   SVS_HIP(ctx, hipStreamSynchronize(ctx->stream));
   fill_result(fe, small.data(), stream, out);
   if (out->dense_passes < 0) { ctx->err = "dense tracker: workgroups of one stream not co-resident (device busy); frame not tracked, call may be repeated"; return SVS_ERR_BUSY; }
+  return SVS_OK;
+}
+
+/* the sub-pixel pass behind the matcher, from the next step on; prm == NULL: off */
+extern "C" int svs_frontend_set_subpixel(svs_frontend *fe, const svs_subpix_params *prm) {
+  svs_ctx *ctx = fe ? fe->ctx : nullptr;
+  SVS_REQUIRE(ctx, fe && !fe->submitted);
+  if (!prm) { fe->subpix = false; fe->subpix_n = -1; return SVS_OK; }
+  SVS_REQUIRE(ctx, svs_subpix_params_ok(prm));
+  SVS_DEVICE(ctx);
+  if (!fe->d_subpix_info) SVS_HIP(ctx, fe->d_subpix_info.alloc((size_t)fe->max_points * fe->B));
+  fe->subpix_prm = *prm; fe->subpix = true;
+  return SVS_OK;
+}
+/* blocking: the svs_subpix_info records of one stream's last step (n_points of them) */
+extern "C" int svs_frontend_subpixel_info(svs_frontend *fe, int stream, svs_subpix_info *h_info) {
+  svs_ctx *ctx = fe ? fe->ctx : nullptr;
+  SVS_REQUIRE(ctx, fe && stream >= 0 && stream < fe->B && !fe->submitted);
+  SVS_REQUIRE(ctx, fe->subpix && fe->subpix_n >= 0);      // refused while the option is off, and before a step has run the pass
+  SVS_DEVICE(ctx);
+  const int n = std::min(fe->n_points[stream], fe->subpix_n);
+  if (n > 0) {
+    SVS_REQUIRE(ctx, h_info);
+    SVS_HIP(ctx, hipMemcpyAsync(h_info, fe->d_subpix_info + (size_t)stream * fe->max_points, sizeof(svs_subpix_info) * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+  }
+  SVS_HIP(ctx, hipStreamSynchronize(ctx->stream));
   return SVS_OK;
 }
 

@@ -12,6 +12,7 @@
 //   match_wave.inc      ONE WAVEFRONT per point, the steps written once: match_kernel (any grid and radius; option "match_legacy" 1) and match_kernel2 (the lean
 //                       scan, windows narrower than a cell; windows wider than 17, and "match_legacy" 2); the readers of the corner bitmap
 //   match_group.inc     match_kernel3: FOUR points per wave, 16 lanes each (windows up to 17 x 17, narrower than a cell): the default
+//   match_subpix.inc    the optional sub-pixel refinement of the OK records (svs_match_subpixel; subpixelAccuracy, matcher.cpp:241-309): ONE WAVEFRONT per record
 // In all three matchers the quadtree of the reference is replaced by a scan of the (2R+1)^2 search window in the corner bitmap of fast.hip (a pixel is a
 // candidate iff its score clears the emit threshold of its cell); the winner is the minimum ZNSSD, and the reference's tie-break (first hit in QuadTree::query
 // DFS order, strict '<') is reproduced with quadrant keys computed only on ties -- bit-exact without building a tree.
@@ -21,6 +22,7 @@
 
 #include "fast_view.h"
 #include "pose.h"
+#include "subpix_core.h"
 #include <algorithm>
 
 namespace {
@@ -74,6 +76,7 @@ constexpr int M3_GROUPS = 16;                      // match_kernel3: points per 
 #include "match_order.inc"
 #include "match_wave.inc"
 #include "match_group.inc"
+#include "match_subpix.inc"
 
 }  // namespace
 
@@ -150,5 +153,34 @@ extern "C" int svs_match(svs_ctx *ctx, const svs_match_args *a, svs_fast *f, svs
   else if (lean) hipLaunchKernelGGL(match_kernel2, grid, block, 0, ctx->stream, M, d_out);
   else hipLaunchKernelGGL(match_kernel, grid, block, 0, ctx->stream, M, d_out);
   SVS_LAUNCH_CHECK(ctx);
+  ctx->match_pred = M.pred; ctx->match_pred_batch = a->n_batch; ctx->match_pred_pts = a->n_pts;      // for the front end's sub-pixel pass (svs_match_subpixel_behind_match)
   return SVS_OK;
+}
+
+extern "C" void svs_subpix_params_default(svs_subpix_params *p) {
+  if (!p) return;
+  p->iterations = 8; p->max_shift = 1.5f; p->eps = 0.03f; p->pad_ = 0;
+}
+// what both entries refuse, before any allocation or launch; *empty: nothing to do
+static int subpix_check(svs_ctx *ctx, const svs_match_args *a, const svs_subpix_params *prm, const svs_match_result *d_results, bool *empty) {
+  SVS_REQUIRE(ctx, ctx && a && prm);
+  SVS_REQUIRE(ctx, svs_subpix_params_ok(prm));
+  SVS_REQUIRE(ctx, a->n_pts >= 0 && a->n_batch >= 1);
+  *empty = a->n_pts == 0;
+  SVS_REQUIRE(ctx, *empty || d_results);
+  return SVS_OK;
+}
+extern "C" int svs_match_subpixel(svs_ctx *ctx, const svs_match_args *a, const svs_subpix_params *prm, svs_match_result *d_results, svs_subpix_info *d_info) {
+  bool empty;
+  if (const int rc = subpix_check(ctx, a, prm, d_results, &empty)) return rc;
+  SVS_DEVICE(ctx);
+  return empty ? SVS_OK : subpix_run(ctx, a, prm, nullptr, d_results, d_info);
+}
+// internal (the front end): the same pass right behind svs_match(ctx, a, ...) on the same context, reading the prediction records that call left in the scratch
+int svs_match_subpixel_behind_match(svs_ctx *ctx, const svs_match_args *a, const svs_subpix_params *prm, svs_match_result *d_results, svs_subpix_info *d_info) {
+  bool empty;
+  if (const int rc = subpix_check(ctx, a, prm, d_results, &empty)) return rc;
+  if (empty) return SVS_OK;
+  SVS_REQUIRE(ctx, ctx->match_pred && ctx->match_pred_batch == a->n_batch && ctx->match_pred_pts == a->n_pts);
+  return subpix_run(ctx, a, prm, static_cast<PointPred *>(ctx->match_pred), d_results, d_info);
 }

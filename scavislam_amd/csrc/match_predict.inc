@@ -1,5 +1,5 @@
 // match_predict.inc -- the per-point scalar part of the guided matcher: relative poses per (stream, keyframe) and one PointPred per candidate point; included first
-// by match.hip.  match_pose_kernel, match_predict_kernel<FUSE>; d_in_frame and d_warp_f are theirs alone.  Whichever kernel forms the poses also writes the level
+// by match.hip.  match_pose_kernel, match_predict_kernel<FUSE>; d_in_frame and d_warp_f are theirs alone, d_affine_inv is shared with match_subpix.inc.  Whichever kernel forms the poses also writes the level
 // table match_kernel3 reads (LevelTab).
 
 __device__ __forceinline__ bool d_in_frame(const svs_cam &c, int u, int v, int border) {
@@ -11,6 +11,17 @@ __device__ __forceinline__ void d_warp_f(const double *T, double depth, const sv
   pose_act(T, p, q);
   o[0] = cam.f * (q[0] / q[2]) + cam.cx;
   o[1] = cam.f * (q[1] / q[2]) + cam.cy;
+}
+// the inverse of warpAffinve's local affine A (matcher.cpp:411-426) at the point's anchor observation; match_predict_kernel, and subpix_predict_kernel of match_subpix.inc
+__device__ __forceinline__ void d_affine_inv(const double *T_cur_from_anchor, const svs_candidate_point &ap, const svs_cam &cam, double *inv) {
+  // f(uv), f(uv + e_x), f(uv + e_y) (matcher.cpp:411-413); x + 0.0 is exact
+  double f0[2], fu[2], fv[2];
+  d_warp_f(T_cur_from_anchor, ap.xyz_anchor[2], cam, ap.anchor_obs_pyr[0] + 0.0, ap.anchor_obs_pyr[1] + 0.0, f0);
+  d_warp_f(T_cur_from_anchor, ap.xyz_anchor[2], cam, ap.anchor_obs_pyr[0] + 1.0, ap.anchor_obs_pyr[1] + 0.0, fu);
+  d_warp_f(T_cur_from_anchor, ap.xyz_anchor[2], cam, ap.anchor_obs_pyr[0] + 0.0, ap.anchor_obs_pyr[1] + 1.0, fv);
+  const double a00 = fu[0] - f0[0], a01 = fu[1] - f0[1], a10 = fv[0] - f0[0], a11 = fv[1] - f0[1];
+  const double invdet = 1.0 / (a00 * a11 - a01 * a10);
+  inv[0] = a11 * invdet; inv[1] = -a01 * invdet; inv[2] = -a10 * invdet; inv[3] = a00 * invdet;
 }
 
 // The two relative poses a candidate needs depend only on (camera stream, anchor keyframe), not on
@@ -108,14 +119,7 @@ __global__ __launch_bounds__(64) void match_predict_kernel(MatchParams M) {
     else if (!(fabs(uv0) < 1e9) || !(fabs(uv1) < 1e9)) pr.status = SVS_MATCH_NONE;
     if (pr.status == SVS_MATCH_OK) {
       pr.ui = (int)uv0; pr.vi = (int)uv1;
-      // f(uv), f(uv + e_x), f(uv + e_y) (matcher.cpp:411-413); x + 0.0 is exact
-      double f0[2], fu[2], fv[2];
-      d_warp_f(T_cur_from_anchor, ap.xyz_anchor[2], cam, ap.anchor_obs_pyr[0] + 0.0, ap.anchor_obs_pyr[1] + 0.0, f0);
-      d_warp_f(T_cur_from_anchor, ap.xyz_anchor[2], cam, ap.anchor_obs_pyr[0] + 1.0, ap.anchor_obs_pyr[1] + 0.0, fu);
-      d_warp_f(T_cur_from_anchor, ap.xyz_anchor[2], cam, ap.anchor_obs_pyr[0] + 0.0, ap.anchor_obs_pyr[1] + 1.0, fv);
-      const double a00 = fu[0] - f0[0], a01 = fu[1] - f0[1], a10 = fv[0] - f0[0], a11 = fv[1] - f0[1];
-      const double invdet = 1.0 / (a00 * a11 - a01 * a10);
-      pr.inv[0] = a11 * invdet; pr.inv[1] = -a01 * invdet; pr.inv[2] = -a10 * invdet; pr.inv[3] = a00 * invdet;
+      d_affine_inv(T_cur_from_anchor, ap, cam, pr.inv);
       double T_actkey_from_anchor[12];
 #pragma unroll
       for (int i = 0; i < 12; ++i) T_actkey_from_anchor[i] = kfT[12 + i];

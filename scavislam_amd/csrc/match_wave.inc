@@ -32,10 +32,10 @@ __device__ __forceinline__ unsigned quad_key(int px, int py, int W, int H) {
 // ---- the wave-per-point steps ------------------------------------------------------------------------------------------------------------------------------
 // warpAffinve (matcher.cpp:403-458): only the centre 8x8 of the reference's 10x10 warp is ever read (KEY_PATCH, matcher.cpp:376-381) and every warped
 // pixel depends on its own coordinates alone: lane = pixel (row lane>>3, column lane&7) of that centre, one pass, the value stays in a register.
-__device__ __forceinline__ int key_pixel(const double *inv, const double *key_uv, const uint8_t *kimg, int kstride, int W, int H, int lane) {
+// (key_pixel_at: pixel (ix, iy) of the 10 x 10 warp, 0 .. 9 each -- the sub-pixel pass, match_subpix.inc, also forms the border)
+__device__ __forceinline__ int key_pixel_at(const double *inv, const double *key_uv, const uint8_t *kimg, int kstride, int W, int H, int ix, int iy) {
   const double i00 = inv[0], i01 = inv[1], i10 = inv[2], i11 = inv[3];
   const double key_u = key_uv[0], key_v = key_uv[1];
-  const int iy = (lane >> 3) + 1, ix = (lane & 7) + 1;
   const double dx = ix - 5, dy = iy - 5;
   const double r0 = (i00 * dx + i01 * dy) + key_u;
   const double r1 = (i10 * dx + i11 * dy) + key_v;
@@ -52,6 +52,9 @@ __device__ __forceinline__ int key_pixel(const double *inv, const double *key_uv
     val = (uint8_t)(s < 255. ? s : 255.);
   }
   return val;
+}
+__device__ __forceinline__ int key_pixel(const double *inv, const double *key_uv, const uint8_t *kimg, int kstride, int W, int H, int lane) {
+  return key_pixel_at(inv, key_uv, kimg, kstride, W, H, (lane & 7) + 1, (lane >> 3) + 1);
 }
 // the key patch of a wave: its texture sums (wave-uniform) and the patch as 16 packed dwords (8 rows x 2), wave-uniform too
 struct KeyPatch { int sumA, sumAA; uint32_t d[16]; };

@@ -442,3 +442,18 @@ class NewpointsListResult(C.Structure):
 NEWPOINTS_LIST_RESULT_FIELDS = tuple(f for f, _ in NewpointsListResult._fields_ if f != "pad_")
 assert C.sizeof(NewpointsPutRequest) == 24 and C.sizeof(NewpointsPruneArgs) == 120 and C.sizeof(NewpointsDropRequest) == 16
 assert C.sizeof(NewpointsListRequest) == 40 and C.sizeof(NewpointsListResult) == 32
+
+
+# ---- matcher: optional sub-pixel refinement of a match (svs_match_subpixel, svs_frontend_set_subpixel)
+class SubpixParams(C.Structure):
+    """svs_subpix_params: Gauss-Newton steps at most, the bound on |offset| per axis (in (0, 2]), the step size below which the iteration stops"""
+    _fields_ = [("iterations", C.c_int32), ("max_shift", C.c_float), ("eps", C.c_float), ("pad_", C.c_int32)]
+
+    @classmethod
+    def default(cls, iterations=8, max_shift=1.5, eps=0.03):
+        return cls(iterations, max_shift, eps, 0)
+
+
+SUBPIX_INFO_DTYPE = np.dtype([("dx", "<f4"), ("dy", "<f4"), ("n_iter", "<i4"), ("state", "<i4")])
+SUBPIX_REFINED, SUBPIX_UNTOUCHED, SUBPIX_SINGULAR, SUBPIX_SHIFT, SUBPIX_NO_DISP = range(5)
+assert C.sizeof(SubpixParams) == 16 and SUBPIX_INFO_DTYPE.itemsize == 16

@@ -23,8 +23,8 @@ import torch
 
 from . import capi
 from .ctypes_types import (CANDIDATE_DTYPE, DENSE_LM_RECORD_DTYPE, DENSE_SUMS_DTYPE, GATED_POINT_DTYPE, KEYFRAME_DTYPE, MATCH_RESULT_DTYPE,
-                           POINT_STATS_DTYPE, Cam,
-                           FastGrid as FastGridPOD, PoseOptParams, PoseOptStats, StereoParams, level_cams)
+                           POINT_STATS_DTYPE, SUBPIX_INFO_DTYPE, Cam,
+                           FastGrid as FastGridPOD, PoseOptParams, PoseOptStats, StereoParams, SubpixParams, level_cams)
 
 NUM_PYR_LEVELS = 3  # global.h:107
 
@@ -271,6 +271,20 @@ class GuidedMatcher:
     def download(self):
         self.ctx.sync()
         return self._keep[4].cpu().numpy().view(MATCH_RESULT_DTYPE).reshape(self.frame.batch, self._n)
+
+    def refineSubpixel(self, a, iterations=8, max_shift=1.5, eps=0.03, want_info=True):
+        """subpixelAccuracy (matcher.cpp:241-309) on the records the last launch(a) left on the device, in place (svs_match_subpixel); asynchronous.  Returns the
+        SUBPIX_INFO_DTYPE [batch, n] records (blocking) if wanted; download() hands out the refined records."""
+        prm = SubpixParams.default(iterations, max_shift, eps)
+        d_info = None
+        if want_info:
+            with torch.cuda.stream(self.frame.stream):
+                d_info = torch.zeros(self.frame.batch * self._n * SUBPIX_INFO_DTYPE.itemsize, dtype=torch.uint8, device=self._keep[4].device)
+        self.ctx.call("svs_match_subpixel", C.byref(a), C.byref(prm), self._keep[4].data_ptr(), d_info.data_ptr() if want_info else None)
+        if not want_info:
+            return None
+        self.ctx.sync()
+        return d_info.cpu().numpy().view(SUBPIX_INFO_DTYPE).reshape(self.frame.batch, self._n)
 
 
 class PoseOptimizer:
@@ -852,6 +866,21 @@ class StereoFrontend:
         ok = np.zeros(self.n_streams, np.int32)
         self.ctx.check(self.ctx.lib.svs_frontend_poses(self.h, T.ctypes.data, ok.ctypes.data))
         return T.reshape(-1, 3, 4), ok
+
+    def setSubpixel(self, iterations=8, max_shift=1.5, eps=0.03):
+        """sub-pixel matches from the next step on (svs_frontend_set_subpixel): the refinement pass of GuidedMatcher.refineSubpixel behind the step's matcher.
+        setSubpixel(None) switches it off (the state of a new front end)."""
+        if iterations is None:
+            self.ctx.check(self.ctx.lib.svs_frontend_set_subpixel(self.h, None))
+        else:
+            prm = SubpixParams.default(iterations, max_shift, eps)
+            self.ctx.check(self.ctx.lib.svs_frontend_set_subpixel(self.h, C.byref(prm)))
+
+    def subpixelInfo(self, stream=0):
+        """SUBPIX_INFO_DTYPE [n_points] of the stream's last step (blocking); refused while the option is off"""
+        info = np.zeros(self.n_points[stream], SUBPIX_INFO_DTYPE)
+        self.ctx.check(self.ctx.lib.svs_frontend_subpixel_info(self.h, stream, info.ctypes.data))
+        return info
 
     STAGES = ("preprocess", "dense_tracking", "stereo", "fast", "match", "pose_refinement", "process_points", "pointcloud")
 
