@@ -1252,6 +1252,31 @@ int svs_map_add_keyframe(svs_map *map, const svs_map_add_keyframe_args *args, in
 int svs_map_add_first_keyframe(svs_map *map, int32_t id, const svs_keyframe *h_keyframe, const float *disp, int32_t disp_stride, const int32_t *h_fast_thr);
 int svs_map_get_points(svs_map *map, int n, const int32_t *h_ids, svs_candidate_point *h_out);
 int svs_map_get_feature_table(svs_map *map, int32_t kf_id, int cap, int32_t *h_count, int32_t *h_point_ids, svs_ba_edge *h_meas);
+/* svs_map_get_keyframe: a DIAGNOSTIC read-back (tests, debugging; nothing of the library or of the integration needs it).  BLOCKING: what the map stores of one keyframe -- the record (pose, pyramid pointers and strides), the disparity's device
+   address and stride, the thresholds [SVS_NUM_PYR_LEVELS][SVS_MAX_CELLS]; every output optional.  SVS_ERR_INVALID: no keyframe of the map. */
+int svs_map_get_keyframe(svs_map *map, int32_t kf_id, svs_keyframe *h_keyframe, const float **h_disp, int32_t *h_disp_stride, int32_t *h_fast_thr);
+/* svs_map_add_keyframe_dev: BLOCKING.  svs_map_add_keyframe with the two lists in DEVICE memory of the map's context (d_new [args->n_new], d_track
+   [args->n_track], 8-byte aligned, complete on the context's stream and unchanged until the call returns; args->new_points / track_points are ignored).  Steps
+   1-5 above hold unchanged, the six outputs are those of svs_map_add_keyframe for the same lists, and the map afterwards is byte for byte the map that call
+   builds.  No list record crosses the bus: one workgroup decides on the device what the host-list call decides about the records on the host, in front of the
+   unchanged strength kernel; ONE download (status, the id columns of the host's mirrors, flags, result, key table, kept mask), the block of integers up, the
+   apply and edge kernels, the CSR rebuild, the constraint launch, the final download -- one blocking round trip fewer than svs_map_add_keyframe.  The records may
+   hold any bits: every id is range-checked on the device before it indexes anything.
+   Refusals, the map unchanged.  PRECEDENCE: first what the arguments and the map's counts decide, in this order -- SVS_ERR_INVALID: covis_thr < 0, a negative
+   count, a missing pointer; SVS_ERR_CAPACITY: a list of 2^24 entries or more; SVS_ERR_INVALID: an unknown oldkey, newkey < 0; SVS_ERR_CAPACITY: newkey beyond
+   the capacity; SVS_ERR_INVALID: newkey present, a missing frame pointer, a threshold outside 10 .. 255, unordered cached ids; SVS_ERR_CAPACITY: fewer than
+   2 n_new + n_track free observations, fewer than min(keyframes of the map, SVS_MAP_ADDKF_MAX_NEIGHBORS) free edges.  Then what the records decide, in the order
+   svs_map_add_keyframe meets it, each phase by its entry of LEAST list index: (1) an anchor_id that is no keyframe: SVS_ERR_INVALID; (2) the new entries, per
+   entry point_id < 0: SVS_ERR_INVALID, point_id beyond the capacity: SVS_ERR_CAPACITY, a point of the map or equal to an earlier new entry's id:
+   SVS_ERR_INVALID, a level outside 0 .. SVS_NUM_PYR_LEVELS - 1: SVS_ERR_INVALID; (3) a track entry with such a level, or whose global_id (inside the capacity) is
+   a new point_id of the call: SVS_ERR_INVALID (a track id that is negative or beyond the capacity names no point and is not refused); (4) an oldkey that is no
+   key of the table: SVS_ERR_INVALID.  A call that breaks only rules about the records therefore returns what svs_map_add_keyframe returns for the same lists;
+   one that also breaks a count rule returns that rule's status here, where svs_map_add_keyframe, which reads the records first, may return the records'.
+   The first such call of a map (and the first after the map's keyframe or point set was changed by any other call) uploads the two id sets as bitmaps,
+   (max_points + 16384) / 8 bytes; a map fed through this call keeps them current on the device.  Restated in tests/commit_kf_model.py. */
+int svs_map_add_keyframe_dev(svs_map *map, const svs_map_add_keyframe_args *args, const svs_map_new_point *d_new, const svs_map_track_point *d_track,
+                             int missing_cap, svs_map_strength_result *h_res, svs_map_key *h_keys, int32_t *h_new_kept, int32_t *h_track_exists,
+                             svs_map_constraint_result *h_cons, int32_t *h_missing);
 
 /* A request by ids.  The device builds the svs_reg_request of the stateless call from the map:
      1. source points.  SVS_REG_LOCAL: every point with at least one observation in a keyframe of h_walk_kf that is not the root and not in h_direct_kf
@@ -1510,6 +1535,31 @@ int svs_frontend_set_vertex_table(svs_frontend *fe, int n_requests, const svs_ve
    was set since (the SVS_SEED_MORE rule), a stream without a vertex table; SVS_ERR_CAPACITY: want_lists != 0 and cap below the step's record count. */
 int svs_frontend_decide_keyframes(svs_frontend *fe, svs_map *map, const svs_keyframe_decide_params *prm, int want_lists, svs_keyframe_decision *h_dec,
                                   svs_map_new_point *h_new, svs_map_track_point *h_track, int32_t *h_new_rec, int32_t *h_track_rec, int cap);
+/* svs_frontend_commit_keyframe: BLOCKING.  Applies the SVS_KF_DROP decision of ONE stream: svs_map_add_keyframe_dev on the lists where the stream's last
+   svs_frontend_decide_keyframes left them (n_new / n_track of its decision record), so no list record reaches the host.  From the front end come
+     the keyframe record: the pyramid pointers and strides of keyframe slot `slot` of the stream (the caller has kept the frame there,
+       svs_frontend_keep_keyframe_of, and leaves the slot alone while the map names it: the map points at the front end's memory, and at `disp`, whose lifetime is
+       the caller's, as with svs_map_add_keyframe);
+     T_newkey_from_oldkey: the step's refined T_cur_from_actkey of the stream, bit-equal to what svs_frontend_results returns;
+     the thresholds, with h_fast_thr NULL: the stream's persistent FAST thresholds as the detector holds them after the step, [SVS_NUM_PYR_LEVELS][SVS_MAX_CELLS]
+       with the cells beyond a level's grid at 25 (what the reference clones into the keyframe as cell_grid2d).
+   Pose and thresholds ride to the host on the call's first download; nothing else is copied.  Outputs and refusals are svs_map_add_keyframe_dev's (h_new_kept
+   [n_new], h_track_exists [n_track] of the decision record; arrays of max_points entries are enough).  SVS_ERR_INVALID, nothing done: a stream or slot out of
+   range, no svs_frontend_decide_keyframes since the stream's last step, a decision that is not valid or not SVS_KF_DROP, a candidate list set or a frame
+   submitted since (the conditions svs_frontend_decide_keyframes checks), a svs_frontend_recompute_cloud since the step (it overwrites the refined poses of ALL
+   streams, which are what a commit inserts: a batch caller commits its drops BEFORE it re-makes the clouds of the streams that switched or dropped), a slot that
+   was never kept, a map of another context.  The front end's state is only read: a commit changes nothing a later step, decision or commit of another stream
+   sees. */
+typedef struct {
+  int32_t stream, slot, newkey_id, oldkey_id, covis_thr, half_width, half_height, disp_stride;
+  const float *disp;                   /* DEVICE, level 0 */
+  const int32_t *h_fast_thr;           /* HOST [SVS_NUM_PYR_LEVELS][SVS_MAX_CELLS], or NULL: the detector's */
+  const int32_t *cached_ids;           /* HOST [n_cached] strictly ascending */
+  const double *cached_T;              /* HOST [n_cached][12] */
+  int32_t n_cached, pad_;
+} svs_commit_keyframe_request;         /* 72 bytes */
+int svs_frontend_commit_keyframe(svs_frontend *fe, svs_map *map, const svs_commit_keyframe_request *req, int missing_cap, svs_map_strength_result *h_res,
+                                 svs_map_key *h_keys, int32_t *h_new_kept, int32_t *h_track_exists, svs_map_constraint_result *h_cons, int32_t *h_missing);
 
 /* ---- front end: a stream's whole neighbourhood from a root id.  Backend::computeNeighborhood(root_id) (backend.cpp:244-309, :347-386) and the order in which
    processMatchedPoints visits newpoint_map (stereo_frontend.cpp:989-1029), joined on the device: findNeighborsOfRoot on the map's strength-ordered adjacency,

@@ -508,6 +508,15 @@ class DenseTrackerGpu {
 // StereoFrontend::processFrame(bool*) / processFirstFrame() (stereo_frontend.h:88-95): the data-parallel part of a frame in ONE blocking call with
 // host buffers in and out; the keyframe switch / drop decision and the AddToOptimzer lists behind it come from decideKeyframes, the caller applies them.
 class BackendMap;
+struct MapAddKeyframeResult {      // BackendMap::AddKeyframeResult: what addKeyframe did (StereoFrontend::addNewKeyframeToMap names it in front of BackendMap)
+  std::vector<std::pair<int, int> > neighborid_to_strength;      // ascending id, after the clamp of oldkey
+  std::vector<int32_t> new_neighbors;                            // the keys that got an edge (key, newkey), ascending: their slots follow this order
+  std::vector<svs_map_constraint_result> constraints;            // one per new edge
+  std::vector<int32_t> missing;                                  // anchors some new edge lacked, ascending, each once: computeAbsolutePoses + computeConstraints complete them
+  std::vector<uint8_t> new_kept, track_exists;
+  std::vector<int32_t> exclude_set;                              // addKeyframeToPlaceRecog (backend.cpp:407-430): newkey and its new neighbours
+  bool do_loop_detection, over_capacity;
+};
 struct FrontendVertex { int frame_id; double T_me_from_w[12]; };      // an entry of neighborhood_->vertex_map: the id and the pose (the edge strengths stay with the caller)
 class StereoFrontend {
  public:
@@ -764,6 +773,14 @@ class StereoFrontend {
   inline bool setNeighborhoodFromStore(BackendMap &map, int32_t root_id, int32_t actkey_id, const std::vector<int32_t> &slot_keyframe_ids, bool refresh_poses,
                                        svs_nbr_result *res, std::vector<int32_t> *point_ids, std::vector<FrontendVertex> *vertex_map,
                                        std::vector<int32_t> *act_neighbors, int max_num_neighbors = 10, int vertex_cap = 64, int stream = 0);
+  // addNewKeyframe's hand-over to the back end (stereo_frontend.cpp:316-415) for a stream whose decision is SVS_KF_DROP, as ONE call (svs_frontend_commit_keyframe):
+  // the keyframe kept in `slot` enters the map as newkey_id with the lists where decideKeyframes left them on the device, the step's refined T_cur_from_actkey
+  // as T_newkey_from_oldkey and the detector's thresholds as cell_grid2d; no list record reaches the host.  dec: the stream's decision record (its n_new /
+  // n_track size the outputs); frame.d_disp / disp_stride: the keyframe's level-0 disparity, which like the slot stays alive while the map names it
+  // (frame.cell_grid2d is not read).  One-stream and batch front ends alike (stream).  Defined behind BackendMap
+  inline bool addNewKeyframeToMap(BackendMap &map, int slot, int newkey_id, int oldkey_id, const svs_keyframe_decision &dec, const float *d_disp, int disp_stride,
+                                  int covis_thr, const svs_cam &cam, MapAddKeyframeResult *out, const std::vector<int32_t> &cached_ids = std::vector<int32_t>(),
+                                  const std::vector<double> &cached_T12 = std::vector<double>(), int missing_cap = 64, int stream = 0);
   svs_frontend *handle() const { return fe_; }
 
  private:
@@ -1260,15 +1277,7 @@ class BackendMap {
     thresholds(frame, &thr);
     return ctx_.check(svs_map_add_first_keyframe(map_, keyframe.frame_id, &keyframe.kf, frame.d_disp, frame.disp_stride, thr.data()));
   }
-  struct AddKeyframeResult {
-    std::vector<std::pair<int, int> > neighborid_to_strength;      // ascending id, after the clamp of oldkey
-    std::vector<int32_t> new_neighbors;                            // the keys that got an edge (key, newkey), ascending: their slots follow this order
-    std::vector<svs_map_constraint_result> constraints;            // one per new edge
-    std::vector<int32_t> missing;                                  // anchors some new edge lacked, ascending, each once: computeAbsolutePoses + computeConstraints complete them
-    std::vector<uint8_t> new_kept, track_exists;
-    std::vector<int32_t> exclude_set;                              // addKeyframeToPlaceRecog (backend.cpp:407-430): newkey and its new neighbours
-    bool do_loop_detection, over_capacity;
-  };
+  typedef MapAddKeyframeResult AddKeyframeResult;
   // newkey.kf: the device pyramid (its pose is ignored: T_newkey_from_oldkey * T_oldkey_from_world is formed on the device); covis_thr = graph_.covis_thr(),
   // cam: the level-0 camera (half sizes as computeStrength takes them, :480-481).  cached_ids (ascending) / cached_T12: the caller's computeAbsolutePose
   // results.  false: refused as a whole (Context::error); out->over_capacity: more than SVS_MAP_ADDKF_MAX_NEIGHBORS keys, the map unchanged
@@ -1295,26 +1304,45 @@ class BackendMap {
     std::vector<int32_t> kept(newpoint_list.size() + 1), exists(trackpoint_list.size() + 1), miss(edge_cap * missing_cap, -1);
     std::vector<svs_map_constraint_result> cons(edge_cap);
     if (!ctx_.check(svs_map_add_keyframe(map_, &a, missing_cap, &r, keys.data(), kept.data(), exists.data(), cons.data(), miss.data()))) return false;
-    *out = AddKeyframeResult();
-    out->over_capacity = r.over_capacity != 0; out->do_loop_detection = false;
-    if (out->over_capacity) return true;
-    out->exclude_set.push_back(newkey.frame_id);
-    for (int i = 0; i < r.n_keys; ++i) {
-      out->neighborid_to_strength.push_back(std::make_pair((int)keys[(size_t)i].kf_id, (int)keys[(size_t)i].strength));
-      if (!keys[(size_t)i].edge) continue;
-      out->new_neighbors.push_back(keys[(size_t)i].kf_id); out->exclude_set.push_back(keys[(size_t)i].kf_id);
-      edge_keys_.push_back(std::make_pair(std::min(keys[(size_t)i].kf_id, (int32_t)newkey.frame_id), std::max(keys[(size_t)i].kf_id, (int32_t)newkey.frame_id)));
-    }
-    std::sort(edge_keys_.begin(), edge_keys_.end());
-    out->constraints.assign(cons.begin(), cons.begin() + r.n_edges);
-    for (size_t i = 0; i < (size_t)r.n_edges * missing_cap; ++i) if (miss[i] >= 0) out->missing.push_back(miss[i]);
-    std::sort(out->missing.begin(), out->missing.end());
-    out->missing.erase(std::unique(out->missing.begin(), out->missing.end()), out->missing.end());
-    out->new_kept.assign(kept.begin(), kept.begin() + newpoint_list.size()); out->track_exists.assign(exists.begin(), exists.begin() + trackpoint_list.size());
-    for (size_t i = 0; i < newpoint_list.size(); ++i) if (kept[i]) level_[(size_t)newpoint_list[i].point_id] = (int8_t)newpoint_list[i].anchor_level;
-    out->do_loop_detection = (int)out->exclude_set.size() < n_kf + 1;
+    addKeyframeResult_(r, keys, kept, exists, cons, miss, newpoint_list.size(), trackpoint_list.size(), newkey.frame_id, n_kf, missing_cap, out);
+    for (size_t i = 0; !out->over_capacity && i < newpoint_list.size(); ++i) if (kept[i]) level_[(size_t)newpoint_list[i].point_id] = (int8_t)newpoint_list[i].anchor_level;
     return true;
   }
+  // addKeyframe with the two lists in DEVICE memory of the map's context (svs_map_add_keyframe_dev): d_newpoint_list [n_new], d_trackpoint_list [n_track], complete
+  // on the context's stream.  No list record crosses the bus and every refusal about the records is decided on the device; *out is what the call above gives.
+  // The records never reach this object: anchorLevel() of a point inserted this way reads 0 until setAnchorLevel tells it
+  bool addKeyframe(int oldkey_id, const RegistrationKeyframe &newkey, const RegistrationFrame &frame, const double T_newkey_from_oldkey[12],
+                   const svs_map_new_point *d_newpoint_list, int n_new, const svs_map_track_point *d_trackpoint_list, int n_track, int covis_thr, const svs_cam &cam,
+                   AddKeyframeResult *out, const std::vector<int32_t> &cached_ids = std::vector<int32_t>(), const std::vector<double> &cached_T12 = std::vector<double>(),
+                   int missing_cap = 64) {
+    if (!ok_ || !out || n_new < 0 || n_track < 0 || cached_T12.size() != 12 * cached_ids.size() || missing_cap < 1) return false;
+    std::vector<int32_t> thr;
+    thresholds(frame, &thr);
+    svs_map_add_keyframe_args a;
+    std::memset(&a, 0, sizeof a);
+    a.newkey_id = newkey.frame_id; a.oldkey_id = oldkey_id; a.covis_thr = covis_thr; a.half_width = (int)(cam.w * 0.5); a.half_height = (int)(cam.h * 0.5);
+    a.disp_stride = frame.disp_stride; a.n_new = n_new; a.n_track = n_track;
+    std::memcpy(a.T_newkey_from_oldkey, T_newkey_from_oldkey, sizeof a.T_newkey_from_oldkey);
+    a.keyframe = newkey.kf; a.disp = frame.d_disp; a.fast_thr = thr.data();
+    a.n_cached = (int32_t)cached_ids.size(); a.cached_ids = cached_ids.empty() ? nullptr : cached_ids.data(); a.cached_T = cached_T12.empty() ? nullptr : cached_T12.data();
+    AddKeyframeCall_ c(this, (size_t)n_new, (size_t)n_track, missing_cap);
+    if (!c.ok || !ctx_.check(svs_map_add_keyframe_dev(map_, &a, d_newpoint_list, d_trackpoint_list, missing_cap, &c.r, c.keys.data(), c.kept.data(), c.exists.data(),
+                                                      c.cons.data(), c.miss.data())))
+      return false;
+    addKeyframeResult_(c.r, c.keys, c.kept, c.exists, c.cons, c.miss, (size_t)n_new, (size_t)n_track, newkey.frame_id, c.n_kf, missing_cap, out);
+    return true;
+  }
+  // StereoFrontend::addNewKeyframeToMap's half on this side (svs_frontend_commit_keyframe): the request names stream, slot, ids and the disparity; the lists, the
+  // pyramid, the pose and the thresholds are the front end's.  n_new / n_track: of the stream's decision record
+  bool addKeyframeFromFrontend(svs_frontend *fe, const svs_commit_keyframe_request &q, int n_new, int n_track, AddKeyframeResult *out, int missing_cap = 64) {
+    if (!ok_ || !out || !fe || n_new < 0 || n_track < 0 || missing_cap < 1) return false;
+    AddKeyframeCall_ c(this, (size_t)n_new, (size_t)n_track, missing_cap);
+    if (!c.ok || !ctx_.check(svs_frontend_commit_keyframe(fe, map_, &q, missing_cap, &c.r, c.keys.data(), c.kept.data(), c.exists.data(), c.cons.data(), c.miss.data())))
+      return false;
+    addKeyframeResult_(c.r, c.keys, c.kept, c.exists, c.cons, c.miss, (size_t)n_new, (size_t)n_track, q.newkey_id, c.n_kf, missing_cap, out);
+    return true;
+  }
+  void setAnchorLevel(int point_id, int anchor_level) { if (point_id >= 0 && (size_t)point_id < level_.size()) level_[(size_t)point_id] = (int8_t)anchor_level; }
   // ---- SlamGraph::registerKeyframes / addLoopClosure (slam_graph.cpp:188-251) on the device: svs_map_register_keyframes / svs_map_add_loop_closure, and what
   // BackendRegistration::localRegisterFrame(map, ..) / globalLoopClosure(map, ..) get from svs_reg_commit
   struct CommitResult {
@@ -1402,6 +1430,42 @@ class BackendMap {
   const Context &ctx_;
   svs_map *map_;
   std::vector<int8_t> level_;      // anchor_level by point id: MyTrackPoint carries it
+  // the output arrays of one svs_map_add_keyframe* call, sized as the header asks
+  struct AddKeyframeCall_ {
+    svs_map_strength_result r;
+    int32_t n_kf;
+    bool ok;
+    std::vector<svs_map_key> keys;
+    std::vector<int32_t> kept, exists, miss;
+    std::vector<svs_map_constraint_result> cons;
+    AddKeyframeCall_(BackendMap *m, size_t n_new, size_t n_track, int missing_cap) : n_kf(0), keys(SVS_MAP_ADDKF_MAX_NEIGHBORS), kept(n_new + 1), exists(n_track + 1) {
+      ok = m->ctx_.check(svs_map_info(m->map_, &n_kf, nullptr, nullptr));
+      const size_t edge_cap = (size_t)std::max(1, std::min((int)n_kf, (int)SVS_MAP_ADDKF_MAX_NEIGHBORS));      // every key is a keyframe of the map
+      miss.assign(edge_cap * (size_t)missing_cap, -1); cons.resize(edge_cap);
+    }
+  };
+  // what a svs_map_add_keyframe* call left in its arrays, as AddKeyframeResult; the new edges join edge_keys_
+  void addKeyframeResult_(const svs_map_strength_result &r, const std::vector<svs_map_key> &keys, const std::vector<int32_t> &kept, const std::vector<int32_t> &exists,
+                          const std::vector<svs_map_constraint_result> &cons, const std::vector<int32_t> &miss, size_t n_new, size_t n_track, int newkey_id, int n_kf,
+                          int missing_cap, AddKeyframeResult *out) {
+    *out = AddKeyframeResult();
+    out->over_capacity = r.over_capacity != 0; out->do_loop_detection = false;
+    if (out->over_capacity) return;
+    out->exclude_set.push_back(newkey_id);
+    for (int i = 0; i < r.n_keys; ++i) {
+      out->neighborid_to_strength.push_back(std::make_pair((int)keys[(size_t)i].kf_id, (int)keys[(size_t)i].strength));
+      if (!keys[(size_t)i].edge) continue;
+      out->new_neighbors.push_back(keys[(size_t)i].kf_id); out->exclude_set.push_back(keys[(size_t)i].kf_id);
+      edge_keys_.push_back(std::make_pair(std::min(keys[(size_t)i].kf_id, (int32_t)newkey_id), std::max(keys[(size_t)i].kf_id, (int32_t)newkey_id)));
+    }
+    std::sort(edge_keys_.begin(), edge_keys_.end());
+    out->constraints.assign(cons.begin(), cons.begin() + r.n_edges);
+    for (size_t i = 0; i < (size_t)r.n_edges * missing_cap; ++i) if (miss[i] >= 0) out->missing.push_back(miss[i]);
+    std::sort(out->missing.begin(), out->missing.end());
+    out->missing.erase(std::unique(out->missing.begin(), out->missing.end()), out->missing.end());
+    out->new_kept.assign(kept.begin(), kept.begin() + n_new); out->track_exists.assign(exists.begin(), exists.begin() + n_track);
+    out->do_loop_detection = (int)out->exclude_set.size() < n_kf + 1;
+  }
   std::vector<std::pair<int32_t, int32_t> > edge_keys_;      // (lo, hi) of every edge, sorted: what updateMarginalization selects its pairs from
   std::vector<int32_t> window_ids_, window_types_;           // the window prepareForOptimization(root_id, loop_id) prepared last: the next call's old_window
   int inner_size_ = 25, double_size_ = 200;                  // backend.cpp:141-144
@@ -1489,6 +1553,17 @@ inline bool StereoFrontend::setNeighborhoodFromStore(BackendMap &map, int32_t ro
     for (int i = 0; i < r.n_vertex; ++i) { (*vertex_map)[(size_t)i].frame_id = vid[(size_t)i]; std::memcpy((*vertex_map)[(size_t)i].T_me_from_w, &vT[(size_t)i * 12], 12 * sizeof(double)); }
   }
   return true;
+}
+inline bool StereoFrontend::addNewKeyframeToMap(BackendMap &map, int slot, int newkey_id, int oldkey_id, const svs_keyframe_decision &dec, const float *d_disp,
+                                                int disp_stride, int covis_thr, const svs_cam &cam, MapAddKeyframeResult *out, const std::vector<int32_t> &cached_ids,
+                                                const std::vector<double> &cached_T12, int missing_cap, int stream) {
+  if (!ok_ || !map.ok() || cached_T12.size() != 12 * cached_ids.size()) return false;
+  svs_commit_keyframe_request q;
+  std::memset(&q, 0, sizeof q);
+  q.stream = stream; q.slot = slot; q.newkey_id = newkey_id; q.oldkey_id = oldkey_id; q.covis_thr = covis_thr;
+  q.half_width = (int)(cam.w * 0.5); q.half_height = (int)(cam.h * 0.5); q.disp_stride = disp_stride; q.disp = d_disp;
+  q.n_cached = (int32_t)cached_ids.size(); q.cached_ids = cached_ids.empty() ? nullptr : cached_ids.data(); q.cached_T = cached_T12.empty() ? nullptr : cached_T12.data();
+  return map.addKeyframeFromFrontend(fe_, q, dec.n_new, dec.n_track, out, missing_cap);
 }
 class BackendRegistration {
  public:

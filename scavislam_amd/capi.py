@@ -8,7 +8,7 @@ import ctypes as C
 import os
 import weakref
 
-from .ctypes_types import BaParams, BaStats, Cam, FastGrid, KeyframeDecideArgs, KeyframeDecideParams, LoopCheck, LoopLocation, LoopLocationResult, LoopResult, MapAddKeyframeArgs, MapConstraintRequest, MapStrengthResult, MapWindowResult, NbhRequest, NbhResult, NbrRequest, NbrResult, NewpointsDropRequest, NewpointsListRequest, NewpointsListResult, NewpointsPruneArgs, NewpointsPutRequest, PoseOptParams, PoseOptStats, RegCommitResult, RegMapRequest, RegParams, RegRequest, RegResult, SeedArgs, SeedParams, SeedRequest, StereoParams, SubpixParams, SurfParams, VertexRequest, VocabParams, VocabResult
+from .ctypes_types import BaParams, BaStats, Cam, CommitKeyframeRequest, FastGrid, KeyframeDecideArgs, KeyframeDecideParams, LoopCheck, LoopLocation, LoopLocationResult, LoopResult, MapAddKeyframeArgs, MapConstraintRequest, MapStrengthResult, MapWindowResult, NbhRequest, NbhResult, NbrRequest, NbrResult, NewpointsDropRequest, NewpointsListRequest, NewpointsListResult, NewpointsPruneArgs, NewpointsPutRequest, PoseOptParams, PoseOptStats, RegCommitResult, RegMapRequest, RegParams, RegRequest, RegResult, SeedArgs, SeedParams, SeedRequest, StereoParams, SubpixParams, SurfParams, VertexRequest, VocabParams, VocabResult
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SVS_LIB_PATH") or os.path.join(_HERE, "libscavislam_hip.so")   # override = kernel A/B experiments only
@@ -241,8 +241,11 @@ _SIGS = {
     "svs_map_prepare_window_from_root": [C.c_void_p, C.c_int32, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(MapWindowResult), C.c_void_p, C.c_void_p],
     "svs_map_compute_strength": [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(MapStrengthResult), C.c_void_p, C.c_void_p],
     "svs_map_add_keyframe": [C.c_void_p, C.POINTER(MapAddKeyframeArgs), C.c_int, C.POINTER(MapStrengthResult), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
+    "svs_map_add_keyframe_dev": [C.c_void_p, C.POINTER(MapAddKeyframeArgs), C.c_void_p, C.c_void_p, C.c_int, C.POINTER(MapStrengthResult), C.c_void_p, C.c_void_p, C.c_void_p,
+                                 C.c_void_p, C.c_void_p],
     "svs_map_add_first_keyframe": [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p],
     "svs_map_get_points": [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p],
+    "svs_map_get_keyframe": [C.c_void_p, C.c_int32, C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_int32), C.c_void_p],
     "svs_map_get_feature_table": [C.c_void_p, C.c_int32, C.c_int, C.POINTER(C.c_int32), C.c_void_p, C.c_void_p],
     "svs_ba_window_from_map_edges": [C.c_void_p, C.c_void_p, C.POINTER(Cam), C.POINTER(BaParams)],
     "svs_ba_window_constraints": [C.c_void_p, C.POINTER(C.c_int32), C.c_void_p],
@@ -268,6 +271,8 @@ _SIGS = {
     "svs_frontend_set_vertex_table": [C.c_void_p, C.c_int, C.POINTER(VertexRequest)],
     "svs_frontend_decide_keyframes": [C.c_void_p, C.c_void_p, C.POINTER(KeyframeDecideParams), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                       C.c_int],
+    "svs_frontend_commit_keyframe": [C.c_void_p, C.c_void_p, C.POINTER(CommitKeyframeRequest), C.c_int, C.POINTER(MapStrengthResult), C.c_void_p, C.c_void_p, C.c_void_p,
+                                     C.c_void_p, C.c_void_p],
     "svs_frontend_newpoints_reserve": [C.c_void_p, C.c_int, C.c_int],
     "svs_frontend_newpoints_put": [C.c_void_p, C.c_int, C.POINTER(NewpointsPutRequest)],
     "svs_frontend_seed_newpoints": [C.c_void_p, C.c_int, C.POINTER(SeedRequest), C.c_void_p, C.POINTER(SeedParams), C.c_void_p, C.c_void_p, C.c_int],

@@ -21,6 +21,7 @@
 #include "keyframe.h"
 #include "nbh_map.h"
 #include "nbr_map.h"
+#include "addkf_map.h"
 #include "newpoints.h"
 #include "pose.h"
 #include "seed.h"
@@ -180,6 +181,11 @@ struct svs_frontend {
   PinnedBuf<uint8_t> h_vt; DevBuf<uint8_t> d_vt_up;
   DevBuf<svs_keyframe_decision> d_kd_dec; DevBuf<svs_map_new_point> d_kd_new; DevBuf<svs_map_track_point> d_kd_track; DevBuf<int32_t> d_kd_new_rec, d_kd_track_rec;
   PinnedBuf<svs_keyframe_decision> h_kd_dec;
+  // svs_frontend_commit_keyframe: the steps counted, the count the records in h_kd_dec were decided at (kd_have: there are any), and the pinned block the pose and
+  // the thresholds of the committed stream come home in
+  // pose_replaced: svs_frontend_recompute_cloud has overwritten the step's refined poses since the step (they are what a commit would insert)
+  uint64_t step_serial = 0, kd_serial = 0; bool kd_have = false, pose_replaced = false;
+  PinnedBuf<uint8_t> h_ck;
   // the resident newpoint_map (svs_frontend_newpoints_*, frontend_newpoints.inc / newpoints.hip): per stream a row of records with its groups packed in store order,
   // a scratch row, the (key, count) table; the host mirrors the TABLES (never a record) and decides every refusal from them.  Nothing is allocated before
   // svs_frontend_newpoints_reserve
@@ -828,6 +834,7 @@ int frontend_chain(svs_frontend *fe, bool first, DispView dv, bool ext_frames = 
   if (pipe) { SVS_HIP(ctx, hipEventRecord(fe->ev_late[par], ctx->stream)); ++fe->pipe_run; }
   fe->last_disp = dv.p; fe->last_dstride = dv.stride; fe->last_dbstride = dv.bstride;
   fe->n_gated = first ? -1 : n;
+  ++fe->step_serial; fe->pose_replaced = false;
   fe->subpix_n = fe->subpix && !first && n > 0 ? n : -1;
   return SVS_OK;
 }
@@ -1090,6 +1097,7 @@ extern "C" int svs_frontend_recompute_cloud(svs_frontend *fe, const double *T_cu
   SVS_DEVICE(ctx);
   SVS_HIP(ctx, hipStreamSynchronize(ctx->stream));
   SVS_HIP(ctx, hipMemcpy(fe->d_small, T_cur_from_actkey, sizeof(double) * 12 * fe->B, hipMemcpyHostToDevice));
+  fe->pose_replaced = true;            // (svs_frontend_commit_keyframe: the step's refined poses are gone, for every stream)
   const float *disp = fe->last_disp;      // the disparity the frame processed last was given (the caller's buffer, if it passed one) or produced
   SVS_REQUIRE(ctx, disp);
   for (int l = 0; l < 3; ++l) {
@@ -1397,6 +1405,7 @@ extern "C" int svs_frontend_decide_keyframes(svs_frontend *fe, svs_map *map, con
   SVS_HIP(ctx, hipMemcpyAsync(fe->h_kd_dec, fe->d_kd_dec, sizeof(svs_keyframe_decision) * (size_t)B, hipMemcpyDeviceToHost, ctx->stream));
   SVS_HIP(ctx, hipStreamSynchronize(ctx->stream));
   __builtin_memcpy(h_dec, fe->h_kd_dec, sizeof(svs_keyframe_decision) * (size_t)B);
+  fe->kd_serial = fe->step_serial; fe->kd_have = true;
   if (!want_lists) return SVS_OK;
   auto wanted = [&](int b) { return h_dec[b].valid && (want_lists == 2 || h_dec[b].decision == SVS_KF_DROP); };
   bool any = false;
@@ -1423,6 +1432,49 @@ extern "C" int svs_frontend_decide_keyframes(svs_frontend *fe, svs_map *map, con
   }
   if (any) SVS_HIP(ctx, hipStreamSynchronize(ctx->stream));
   return SVS_OK;
+}
+
+/* applying a stream's SVS_KF_DROP decision (map.hip: map_addkf_dev.inc, through addkf_map.h; the contract is in the header): the lists stay where the decision left
+   them, the kept slot gives the keyframe record, and the step's pose and the detector's thresholds come home on the map call's first download -- their copies are
+   enqueued here, into a pinned block the map call reads behind that download.  The front end's state is only read. */
+extern "C" int svs_frontend_commit_keyframe(svs_frontend *fe, svs_map *map, const svs_commit_keyframe_request *q, int missing_cap, svs_map_strength_result *h_res,
+                                            svs_map_key *h_keys, int32_t *h_new_kept, int32_t *h_track_exists, svs_map_constraint_result *h_cons, int32_t *h_missing) {
+  svs_ctx *ctx = fe ? fe->ctx : nullptr;
+  SVS_REQUIRE(ctx, fe && map && q && fe->have_prev && !fe->submitted);
+  SVS_REQUIRE(ctx, svs_map_ctx(map) == ctx);
+  SVS_REQUIRE(ctx, q->stream >= 0 && q->stream < fe->B && q->slot >= 0 && q->slot < fe->max_keyframes);
+  SVS_REQUIRE(ctx, fe->n_gated >= 0 && fe->kd_have && fe->kd_serial == fe->step_serial);      // a decision on the step and the list that are still on the device
+  SVS_REQUIRE(ctx, !fe->pose_replaced);                            // ... and the step's refined pose with them: no svs_frontend_recompute_cloud since the step
+  const svs_keyframe_decision &dec = fe->h_kd_dec[q->stream];
+  SVS_REQUIRE(ctx, dec.valid && dec.decision == SVS_KF_DROP);
+  const size_t idx = (size_t)q->stream * fe->max_keyframes + q->slot, mp = (size_t)fe->max_points;
+  SVS_REQUIRE(ctx, fe->kept[idx]);
+  SVS_REQUIRE(ctx, dec.n_new >= 0 && dec.n_track >= 0 && (size_t)dec.n_new <= mp && (size_t)dec.n_track <= mp);
+  const FastThrView tv = svs_fast_thr_view_internal(fe->fast);
+  for (int l = 0; l < tv.n_levels; ++l) SVS_REQUIRE(ctx, tv.ncell[l] <= SVS_MAX_CELLS);      // (before the first copy is enqueued)
+  SVS_DEVICE(ctx);
+  constexpr size_t thr_bytes = sizeof(int32_t) * SVS_NUM_PYR_LEVELS * SVS_MAX_CELLS, T_bytes = sizeof(double) * 12;
+  if (!fe->h_ck) SVS_HIP(ctx, fe->h_ck.alloc(T_bytes + thr_bytes));
+  double *h_T = reinterpret_cast<double *>(fe->h_ck.get());
+  int32_t *h_thr = reinterpret_cast<int32_t *>(fe->h_ck + T_bytes);
+  SVS_HIP(ctx, hipMemcpyAsync(h_T, fe->d_small + 12 * (size_t)q->stream, T_bytes, hipMemcpyDeviceToHost, ctx->stream));
+  if (!q->h_fast_thr) {
+    for (int k = 0; k < SVS_NUM_PYR_LEVELS * SVS_MAX_CELLS; ++k) h_thr[k] = 25;
+    for (int l = 0; l < tv.n_levels; ++l) {
+      SVS_HIP(ctx, hipMemcpyAsync(h_thr + (size_t)l * SVS_MAX_CELLS, tv.thr + (size_t)q->stream * tv.ncell_total + tv.cell_base[l], sizeof(int32_t) * (size_t)tv.ncell[l],
+                                  hipMemcpyDeviceToHost, ctx->stream));
+    }
+  }
+  svs_map_add_keyframe_args a{};
+  a.newkey_id = q->newkey_id; a.oldkey_id = q->oldkey_id; a.covis_thr = q->covis_thr; a.half_width = q->half_width; a.half_height = q->half_height;
+  a.disp_stride = q->disp_stride; a.n_new = dec.n_new; a.n_track = dec.n_track;
+  a.keyframe = fe->h_kfs[idx];
+  a.disp = q->disp; a.fast_thr = q->h_fast_thr;
+  a.cached_ids = q->cached_ids; a.cached_T = q->cached_T; a.n_cached = q->n_cached;
+  const MapKeyframeLists L{fe->d_kd_new + (size_t)q->stream * mp, fe->d_kd_track + (size_t)q->stream * mp, h_T, q->h_fast_thr ? nullptr : h_thr};
+  const int rc = svs_map_add_keyframe_lists(map, &a, L, missing_cap, h_res, h_keys, h_new_kept, h_track_exists, h_cons, h_missing);
+  if (rc) (void)hipStreamSynchronize(ctx->stream);                 // (a refusal in front of the download: the copies above have landed before the block is reused)
+  return rc;
 }
 
 /* a stream's whole neighbourhood from a root id (map.hip: map_nbh.inc, through nbr_map.h; the contract is in the header): everything is checked on the host first, then one

@@ -13,15 +13,18 @@
 //   map_nbh.inc       a front-end stream's neighbourhood: from a vertex list (nbh_map.h: nbh_collect, map_nbh_kernel) and from a root id (nbr_map.h: map_nbr_*)
 //   map_window.inc    the double window's BA problem (ba_map.h): map_win_mark / list / gather / store, svs_map_prepare_window and _from_root
 //   map_addkf.inc     inserting a keyframe (SlamGraph::addKeyframe): computeStrength by counting passes, the kept points and pairs by prefix sums
+//   map_addkf_dev.inc the same insertion with the two lists in device memory: the refusals about the records, the track flags and the id columns by one workgroup
 //   map_commit.inc    registerKeyframes / addLoopClosure: a device track list and an edge list applied to the map
 // Integer and copy work throughout (but for the three divisions of invert_depth and the f64 geometry of map_cons_kernel); the host keeps the id sets and the set of
-// pairs, so every refusal happens before anything is uploaded; no atomic decides a value or an order, so every result is a function of the map's content alone.
+// pairs, so every refusal happens before anything is uploaded (map_addkf_dev.inc alone decides refusals about records it never sees on the device, from bitmap copies
+// of the id sets, before anything is written); no atomic decides a value or an order, so every result is a function of the map's content alone.
 #include "reg_map.h"
 #include "nbh_map.h"
 #include "nbr_map.h"
 #include "ba_map.h"
 #include "walk_map.h"
 #include "kf_map.h"
+#include "addkf_map.h"
 #include "pose.h"
 #include <string.h>
 #include <algorithm>
@@ -92,6 +95,10 @@ struct svs_map {
   std::vector<int32_t> kf_nobs;
   DevBuf<double> d_depth; DevBuf<int32_t> d_common;
   DevBuf<uint8_t> d_dn; PinnedBuf<uint8_t> h_dn;
+  // svs_map_add_keyframe_dev (map_addkf_dev.inc): the id sets as bitmaps on the device, the counts they were written at, the row over point ids its check kernel
+  // leaves as it found it; all allocated with the first such call
+  DevBuf<uint32_t> d_in_pt, d_in_kf; PinnedBuf<uint32_t> h_in; int in_n_kf = -1, in_n_pt = -1;
+  DevBuf<int32_t> d_first;
   // the pose graph's walks (map_walk.inc): the strength-ordered adjacency and the searches' work space
   MapWalkState walk;
   ~svs_map() {      // (before the members go, also when create gives up)
@@ -283,4 +290,5 @@ static int map_check_ids(svs_map *m, int n, const int32_t *ids, const std::vecto
 #include "map_nbh.inc"
 #include "map_window.inc"
 #include "map_addkf.inc"
+#include "map_addkf_dev.inc"
 #include "map_commit.inc"

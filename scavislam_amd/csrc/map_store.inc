@@ -58,6 +58,15 @@ __global__ __launch_bounds__(256) void map_get_points_kernel(MapK M, const int32
   copy_rec64(out + i, M.pt + ids[i]);
 }
 
+// what the map holds of one keyframe: the record (136 bytes as 17 words of 8), the disparity's address and stride, the thresholds
+struct kf_dn { svs_keyframe kf; const float *disp; int32_t disp_stride, pad_; int32_t thr[THR_N]; };
+__global__ __launch_bounds__(256) void map_get_kf_kernel(MapK M, int id, kf_dn *out) {
+  const int t = threadIdx.x;
+  for (int k = t; k < THR_N; k += 256) out->thr[k] = M.kf_thr[(size_t)id * THR_N + k];
+  if (t < 17) reinterpret_cast<long long *>(&out->kf)[t] = reinterpret_cast<const long long *>(M.kf + id)[t];
+  if (t == 17) { out->disp = M.kf_disp[id]; out->disp_stride = M.kf_dstride[id]; out->pad_ = 0; }
+}
+
 struct MapFtK { int kf, cap, n_meas; const svs_ba_edge *meas; int32_t *count, *ids; svs_ba_edge *rec; };
 
 // one workgroup: the keyframe's row as a bitmap over point ids (row 0 of M.mark), ascending ids by popcount prefixes, then the measured store is searched for
@@ -299,6 +308,24 @@ extern "C" int svs_map_get_points(svs_map *m, int n, const int32_t *h_ids, svs_c
   return map_read_back(m, n, h_ids, 1, h_out, [&](const int32_t *ids, svs_candidate_point *out) {
     hipLaunchKernelGGL(map_get_points_kernel, dim3(div_up(n, 256)), dim3(256), 0, ctx->stream, m->view(), ids, n, out);
   });
+}
+
+extern "C" int svs_map_get_keyframe(svs_map *m, int32_t kf_id, svs_keyframe *h_keyframe, const float **h_disp, int32_t *h_disp_stride, int32_t *h_fast_thr) {
+  svs_ctx *ctx = m ? m->ctx : nullptr;
+  SVS_REQUIRE(ctx, m && svs_map_has_keyframe(m, kf_id));
+  SVS_DEVICE(ctx);
+  MapDn dn(m);
+  const auto rec = dn.piece<kf_dn>(1);
+  if (int rc = dn.reserve()) return rc;
+  hipLaunchKernelGGL(map_get_kf_kernel, dim3(1), dim3(256), 0, ctx->stream, m->view(), kf_id, dn.dev(rec));
+  SVS_LAUNCH_CHECK(ctx);
+  if (int rc = dn.download()) return rc;
+  const kf_dn &r = *dn.host(rec);
+  if (h_keyframe) *h_keyframe = r.kf;
+  if (h_disp) *h_disp = r.disp;
+  if (h_disp_stride) *h_disp_stride = r.disp_stride;
+  if (h_fast_thr) memcpy(h_fast_thr, r.thr, sizeof r.thr);
+  return SVS_OK;
 }
 
 extern "C" int svs_map_get_feature_table(svs_map *m, int32_t kf_id, int cap, int32_t *h_count, int32_t *h_point_ids, svs_ba_edge *h_meas) {

@@ -363,6 +363,16 @@ class MapAddKeyframeArgs(C.Structure):
 assert C.sizeof(KeyframeC) == 136 and C.sizeof(MapAddKeyframeArgs) == 32 + 96 + 136 + 48 + 8
 
 
+class CommitKeyframeRequest(C.Structure):
+    """svs_commit_keyframe_request: one stream's SVS_KF_DROP decision applied to the map (svs_frontend_commit_keyframe)"""
+    _fields_ = [("stream", C.c_int32), ("slot", C.c_int32), ("newkey_id", C.c_int32), ("oldkey_id", C.c_int32), ("covis_thr", C.c_int32), ("half_width", C.c_int32),
+                ("half_height", C.c_int32), ("disp_stride", C.c_int32), ("disp", C.c_void_p), ("h_fast_thr", C.c_void_p), ("cached_ids", C.c_void_p),
+                ("cached_T", C.c_void_p), ("n_cached", C.c_int32), ("pad_", C.c_int32)]
+
+
+assert C.sizeof(CommitKeyframeRequest) == 72
+
+
 # ---- front end: the keyframe switch / drop decision behind a step (svs_keyframe_decide, svs_frontend_set_vertex_table, svs_frontend_decide_keyframes)
 KF_MAX_VERTICES, KF_MAX_STRENGTH, KF_MAX_SLOTS, KF_SET_MAP = 64, 64, 1024, -1
 KF_KEEP, KF_SWITCH, KF_DROP = 0, 1, 2

@@ -987,6 +987,7 @@ class StereoFrontend:
             ptrs = [None] * 4
         self.ctx.check(self.ctx.lib.svs_frontend_decide_keyframes(self.h, resident_map.h if resident_map is not None else None, C.byref(prm), int(want_lists),
                                                                   dec.ctypes.data, *ptrs, cap))
+        self._last_dec = dec.copy()
         out = []
         for b in range(B):
             d = dec[b]
@@ -996,6 +997,26 @@ class StereoFrontend:
                 o.update(new=new[b, :nn].copy(), track=track[b, :nt].copy(), new_rec=new_rec[b, :nn].copy(), track_rec=track_rec[b, :nt].copy())
             out.append(o)
         return out
+
+    def commitKeyframe(self, resident_map, stream, slot, newkey_id, oldkey_id, disp, covis_thr, half_width, half_height, fast_thr=None, cached=None, missing_cap=16,
+                       resolve_missing=False):
+        """applies the SVS_KF_DROP decision of `stream` (svs_frontend_commit_keyframe): the keyframe kept in `slot` enters resident_map as newkey_id, with the
+        lists where the last decideKeyframes left them on the device, the step's refined T_cur_from_actkey as T_newkey_from_oldkey and -- fast_thr None -- the
+        detector's persistent thresholds.  disp: (device pointer, stride) of the level-0 disparity, which, like the slot, the caller leaves alone while the map
+        names it.  Returns what ResidentMap.add_keyframe returns; SvsError with nothing done unless the stream's last decision is a drop on the step and the
+        candidate list that are still on the device"""
+        from .ctypes_types import CommitKeyframeRequest
+        dec = getattr(self, "_last_dec", None)
+        n_new, n_track = (int(dec[stream]["n_new"]), int(dec[stream]["n_track"])) if dec is not None and 0 <= stream < len(dec) else (self.max_points, self.max_points)
+
+        def call(a, outs):
+            q = CommitKeyframeRequest()
+            q.stream, q.slot, q.newkey_id, q.oldkey_id, q.covis_thr, q.half_width, q.half_height = int(stream), int(slot), a.newkey_id, a.oldkey_id, a.covis_thr, a.half_width, a.half_height
+            q.disp_stride, q.disp, q.h_fast_thr, q.cached_ids, q.cached_T, q.n_cached = a.disp_stride, a.disp, a.fast_thr, a.cached_ids, a.cached_T, a.n_cached
+            self.ctx.check(self.ctx.lib.svs_frontend_commit_keyframe(self.h, resident_map.h, C.byref(q), *outs))
+
+        return resident_map._add_keyframe(newkey_id, oldkey_id, None, None, disp, fast_thr, n_new, n_track, covis_thr, half_width, half_height, cached, missing_cap,
+                                          resolve_missing, call=call)
 
     # ---- newpoint_map on the device (svs_frontend_newpoints_*: stereo_frontend.cpp:360-365, :808, :989-1029; the rules are in the header)
     def reserveNewpoints(self, record_cap, group_cap=64):

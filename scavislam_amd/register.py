@@ -566,30 +566,52 @@ class ResidentMap:
         an anchor through absolute_poses and a storing compute_constraints, as update_marginalization does"""
         np_ = np.ascontiguousarray(new_points, MAP_NEW_POINT_DTYPE).reshape(-1)
         tp = np.ascontiguousarray(track_points, MAP_TRACK_POINT_DTYPE).reshape(-1)
-        k = np.ascontiguousarray(kf, KEYFRAME_DTYPE).reshape(-1)[0]
-        thr = self._fast_thr(fast_thr)
+        return self._add_keyframe(newkey_id, oldkey_id, T_newkey_from_oldkey, kf, disp, fast_thr, len(np_), len(tp), covis_thr, half_width, half_height, cached,
+                                  missing_cap, resolve_missing, host=(np_, tp))
+
+    def add_keyframe_dev(self, newkey_id, oldkey_id, T_newkey_from_oldkey, kf, disp, fast_thr, d_new, n_new, d_track, n_track, covis_thr, half_width, half_height,
+                         cached=None, missing_cap=16, resolve_missing=False):
+        """add_keyframe with the two lists in device memory of the map's context (svs_map_add_keyframe_dev): d_new / d_track are device addresses of n_new
+        MAP_NEW_POINT_DTYPE / n_track MAP_TRACK_POINT_DTYPE records, complete on the context's stream.  No list record crosses the bus; every refusal about the
+        records is decided on the device.  Returns what add_keyframe returns"""
+        return self._add_keyframe(newkey_id, oldkey_id, T_newkey_from_oldkey, kf, disp, fast_thr, int(n_new), int(n_track), covis_thr, half_width, half_height, cached,
+                                  missing_cap, resolve_missing, dev=(int(d_new) if n_new else 0, int(d_track) if n_track else 0))
+
+    def _add_keyframe(self, newkey_id, oldkey_id, T_newkey_from_oldkey, kf, disp, fast_thr, n_new, n_track, covis_thr, half_width, half_height, cached, missing_cap,
+                      resolve_missing, host=None, dev=None, call=None):
+        """the two calls above, and StereoFrontend.commitKeyframe (call: the library call, given the output arrays)"""
+        k = np.ascontiguousarray(kf, KEYFRAME_DTYPE).reshape(-1)[0] if kf is not None else None
+        thr = self._fast_thr(fast_thr) if fast_thr is not None else None
         cached = cached or {}
         cids = np.array(sorted(int(c) for c in cached), np.int32)
         cT = np.ascontiguousarray([np.asarray(cached[int(c)], np.float64).reshape(12) for c in cids], np.float64).reshape(len(cids), 12)
         a = MapAddKeyframeArgs()
         a.newkey_id, a.oldkey_id, a.covis_thr, a.half_width, a.half_height = int(newkey_id), int(oldkey_id), int(covis_thr), int(half_width), int(half_height)
-        a.disp_stride, a.n_new, a.n_track = int(disp[1]), len(np_), len(tp)
-        a.T_newkey_from_oldkey[:] = np.asarray(T_newkey_from_oldkey, np.float64).reshape(12).tolist()
-        a.keyframe.pyr[:] = [int(p) for p in k["pyr"]]
-        a.keyframe.stride[:] = [int(v) for v in k["stride"]]
-        a.disp, a.fast_thr = int(disp[0]), thr.ctypes.data
-        a.new_points, a.track_points = (np_.ctypes.data if len(np_) else None), (tp.ctypes.data if len(tp) else None)
+        a.disp_stride, a.n_new, a.n_track = int(disp[1]), n_new, n_track
+        if call is None:
+            a.T_newkey_from_oldkey[:] = np.asarray(T_newkey_from_oldkey, np.float64).reshape(12).tolist()
+            a.keyframe.pyr[:] = [int(p) for p in k["pyr"]]
+            a.keyframe.stride[:] = [int(v) for v in k["stride"]]
+        a.disp, a.fast_thr = int(disp[0]), (thr.ctypes.data if thr is not None else None)
+        if host is not None:
+            a.new_points, a.track_points = (host[0].ctypes.data if n_new else None), (host[1].ctypes.data if n_track else None)
         a.cached_ids, a.cached_T, a.n_cached = (cids.ctypes.data if len(cids) else None), (cT.ctypes.data if len(cids) else None), len(cids)
         res = MapStrengthResult()
         keys = np.zeros(MAP_ADDKF_MAX_NEIGHBORS, MAP_KEY_DTYPE)
-        kept, exists = np.zeros(len(np_), np.int32), np.zeros(len(tp), np.int32)
+        kept, exists = np.zeros(n_new, np.int32), np.zeros(n_track, np.int32)
         n_kf = self.info()[0]
         edge_cap = max(1, min(n_kf, MAP_ADDKF_MAX_NEIGHBORS))      # every key is a keyframe of the map; the library writes the first n_edges entries only
         cons = np.zeros(edge_cap, MAP_CONSTRAINT_RESULT_DTYPE)
         cap = int(missing_cap)
         missing = np.full((edge_cap, cap), -1, np.int32)
-        self._call("svs_map_add_keyframe", C.byref(a), cap, C.byref(res), keys.ctypes.data, kept.ctypes.data if len(np_) else None,
-                   exists.ctypes.data if len(tp) else None, cons.ctypes.data, missing.ctypes.data if cap else None)
+        outs = (cap, C.byref(res), keys.ctypes.data, kept.ctypes.data if n_new else None, exists.ctypes.data if n_track else None, cons.ctypes.data,
+                missing.ctypes.data if cap else None)
+        if call is not None:
+            call(a, outs)
+        elif dev is not None:
+            self._call("svs_map_add_keyframe_dev", C.byref(a), C.c_void_p(dev[0]), C.c_void_p(dev[1]), *outs)
+        else:
+            self._call("svs_map_add_keyframe", C.byref(a), *outs)
         out = self._strength_out(res, keys, exists)
         raw = dict(self.raw, new_kept=kept, results=cons, missing=missing)      # as the library wrote them (resolve_missing's calls leave their own behind)
         out["new_kept"] = kept.astype(bool)
@@ -699,6 +721,13 @@ class ResidentMap:
         out = np.zeros(len(p), CANDIDATE_DTYPE)
         self._call("svs_map_get_points", len(p), p.ctypes.data, out.ctypes.data)
         return out
+
+    def get_keyframe(self, kf_id):
+        """blocking read-back of what the map stores of a keyframe -> (one KEYFRAME_DTYPE record, (disparity device pointer, stride), thresholds [3][SVS_MAX_CELLS])"""
+        kf, thr = np.zeros(1, KEYFRAME_DTYPE), np.zeros((3, SVS_MAX_CELLS), np.int32)
+        disp, stride = C.c_void_p(), C.c_int32()
+        self._call("svs_map_get_keyframe", int(kf_id), kf.ctypes.data, C.byref(disp), C.byref(stride), thr.ctypes.data)
+        return kf[0], (disp.value or 0, stride.value), thr
 
     def get_feature_table(self, kf_id, cap=None):
         """blocking read-back of a keyframe's feature_table -> (point ids ascending, BA_EDGE_DTYPE measurement records, the table's length).  A pair without a
