@@ -646,10 +646,11 @@ extern "C" int svs_preprocess_gpu_sem(svs_ctx *ctx, const uint8_t *d_src, int w,
                                       float *const *d_img, float *const *d_dx, float *const *d_dy, const int32_t *fstride,
                                       const size_t *f_bstride, int levels, int batch) {
   SVS_REQUIRE(ctx, ctx && d_src && d_img && d_dx && d_dy && fstride && f_bstride && w > 0 && h > 0 && levels >= 1 && levels <= 3 && batch >= 1);
+  // every level is checked before the first launch: a call that is rejected has written nothing
+  for (int l = 0, lw = w; l < levels; ++l, lw = (lw + 1) / 2) SVS_REQUIRE(ctx, d_img[l] && d_dx[l] && d_dy[l] && fstride[l] >= lw);
   SVS_DEVICE(ctx);
   int lw = w, lh = h;
   for (int l = 0; l < levels; ++l) {
-    SVS_REQUIRE(ctx, d_img[l] && d_dx[l] && d_dy[l] && fstride[l] >= lw);
     const dim3 grid(div_up(lw, 64), div_up(lh, 4), batch);
     if (l == 0)
       hipLaunchKernelGGL(convert_f32_kernel, grid, dim3(256), 0, ctx->stream, d_src, w, h, sstride, s_bstride, d_img[0], fstride[0], f_bstride[0]);

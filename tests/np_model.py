@@ -65,6 +65,35 @@ def sobel(img_f32):
     return p[1:-1, 2:] - p[1:-1, :-2], p[2:, 1:-1] - p[:-2, 1:-1]
 
 
+def _reflect101_index(i, n):
+    """BORDER_REFLECT_101 of any integer index: the reflected axis has period 2 n - 2 (n = 1: every index is 0)."""
+    if n == 1:
+        return np.zeros_like(i)
+    i = np.mod(i, 2 * n - 2)
+    return np.where(i >= n, 2 * n - 2 - i, i)
+
+
+def pyr_down_f32(img):
+    """5x5 binomial on f32 the way the CUDA branch's pyrDown is restated: columns (the vertical pass) first, then rows, taps 1/16 4/16 6/16 4/16 1/16 added in
+    ascending order in float32, REFLECT_101 however often the index has to be reflected, output size (n + 1) // 2."""
+    k = np.array([0.0625, 0.25, 0.375, 0.25, 0.0625], np.float32)
+    a = np.asarray(img, np.float32)
+    for axis in (0, 1):
+        n = a.shape[axis]
+        idx = _reflect101_index(2 * np.arange((n + 1) // 2)[:, None] + np.arange(-2, 3)[None, :], n)
+        acc = k[0] * np.take(a, idx[:, 0], axis=axis)
+        for t in range(1, 5):
+            acc = acc + k[t] * np.take(a, idx[:, t], axis=axis)
+        a = acc.astype(np.float32)
+    return a
+
+
+def deriv_replicate(img_f32):
+    """central differences I(x+1) - I(x-1), I(y+1) - I(y-1) with replicated borders, no scaling"""
+    p = np.pad(np.asarray(img_f32, np.float32), 1, mode="edge")
+    return p[1:-1, 2:] - p[1:-1, :-2], p[2:, 1:-1] - p[:-2, 1:-1]
+
+
 def hat(w):
     return np.array([[0, -w[2], w[1]], [w[2], 0, -w[0]], [-w[1], w[0], 0]])
 

@@ -26,9 +26,7 @@ def test_pyramid_and_sobel_bit_exact(gpu_ctx, w, h):
     cam = dict(synth.CAM_DEFAULT, w=w, h=h)
     imgs = [synth.noise_image(w, h, 11 + i) for i in range(2)]
     if (w, h) == (322, 242):           # odd level sizes exercise REFLECT_101 on both borders
-        from scavislam_amd.frontend import FramePyramid
         import torch
-        fr = FramePyramid(ctx, stream, dict(cam, w=320, h=240), batch=1, with_float=False)
         # direct C-ABI call on an odd-sized image
         src = torch.as_tensor(imgs[0]).cuda()
         dst = torch.zeros(((h + 1) // 2, (w + 1) // 2), dtype=torch.uint8, device="cuda")
@@ -36,6 +34,15 @@ def test_pyramid_and_sobel_bit_exact(gpu_ctx, w, h):
         ctx.call("svs_pyr_down_u8", src.data_ptr(), w, h, w, w * h, dst.data_ptr(), (w + 1) // 2, 0, 1)
         ctx.sync()
         assert np.array_equal(dst.cpu().numpy(), O.pyr_down_u8(imgs[0]))
+        # convert + Sobel on the image (322 columns: the last group of 4 is partial) and on its 161 x 121 level (tight rows of 161 floats: no row is 16-byte pitched)
+        for lvl in (src, dst):
+            lh, lw = lvl.shape
+            out = torch.zeros((3, lh, lw), dtype=torch.float32, device="cuda")
+            torch.cuda.synchronize()
+            ctx.call("svs_convert_sobel_f32", lvl.data_ptr(), lw, lh, lw, 0, out[0].data_ptr(), out[1].data_ptr(), out[2].data_ptr(), lw, 0, 1)
+            ctx.sync()
+            for got, ref in zip(out.cpu().numpy(), O.convert_sobel(lvl.cpu().numpy())):
+                assert np.array_equal(got, ref), (lw, lh)
         return
     fr = _frame(ctx, stream, cam, imgs)
     ctx.sync()
