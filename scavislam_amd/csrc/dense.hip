@@ -150,16 +150,20 @@ __device__ __forceinline__ void taps_u8(P img, int stride, float u, float v, flo
 }
 
 // loop body of dense_tracking.cpp:229-261 (chi2) / :278-331 (H, b), one sample.
-// Branch-free (invalid samples are predicated to zero contributions and a safe address) so that the
-// unrolled caller can keep the cloud load and the 12 bilinear taps of several samples in flight:
-// the pass is bound by gather latency, not by bytes.
+// Every load is unconditional (an invalid sample taps a safe address) so that the caller can keep the cloud
+// load and the bilinear taps of several samples in flight: the pass is bound by gather latency, not by bytes.
+// What an invalid sample would add to the sums is skipped under one `if (ok)` behind the taps.
 // the two T-independent loads of a sample (stored 3D point, previous-frame intensity): issued one trip ahead by track_pass
 struct SampleIn { float4 c4; uint8_t prev; };
+// A grid position past the level's end (the prefetch of a lane's last trip) reads the level's FIRST sample instead: an address that is always there, and no
+// constants to materialise per trip.  What comes back is then some other sample's data, c4.w included -- whoever may consume such a sample masks it with its own
+// in_range (sample_cpu_sem starts `ok` from it: the TM == 0 sweep); the TM != 0 sweeps run a trip only for i < n and never consume one.
 template <class LA>
 __device__ __forceinline__ SampleIn sample_load(const LA &L, int u, int v, int cw, bool in_range) {
   SampleIn s;
-  s.c4 = in_range ? load_f4(L.cloud + 4u * (__umul24(v, cw) + (unsigned)u)) : make_float4(0.f, 0.f, 1.f, -1.f);
-  s.prev = L.prev[__umul24((in_range ? v : 0) * 4, L.pstride) + (unsigned)((in_range ? u : 0) * 4)];
+  const int us = in_range ? u : 0, vs = in_range ? v : 0;
+  s.c4 = load_f4(L.cloud + 4u * (__umul24(vs, cw) + (unsigned)us));
+  s.prev = L.prev[__umul24(vs * 4, L.pstride) + (unsigned)(us * 4)];
   return s;
 }
 // (rcp_rn / div_rn, one refined reciprocal for x / z, y / z and the Jacobian: devutil.h)
@@ -188,33 +192,43 @@ __device__ __forceinline__ void sample_cpu_sem(const LA &L, const double *T, con
   const float ip = ip_lut ? ip_lut[in.prev] : (float)((1. / 255.) * in.prev);
   TapRows taps;
   if constexpr (U8SRC) taps_u8_issue<TRK_TAPS_ASM>(L.cur8, L.c8stride, uvx, uvy, taps);
-  const double zs = ok ? z : 1.0, xs = ok ? x : 0.0, ys = ok ? y : 0.0;
+  // (x, y, rz as they are, valid sample or not: what an invalid lane forms from them below is garbage that nothing reads -- see `if (ok)`)
+  const double xs = x, ys = y;
   // transformations.h:117-139 frame_jac_xyz2uv.  One reciprocal instead of eight f64 divisions and
   // fused multiply-adds in the 27 accumulations: the pass is f64-issue bound on its CU, and H/b only
   // need 1e-9 relative agreement with the serial oracle (uv above stays division-exact because the
   // in-frame test and the tap addresses must match bit for bit).
   // (every fused multiply-add written out: left to the compiler's contraction the two instantiations of this function -- f32 pyramids / u8 source -- fused
   // different pairs, and their sums, which the tests hold bit-identical, drifted apart with every unrelated change to the kernel)
-  const double f = L.cam.f, iz = ok ? rz : 1.0, iz2 = iz * iz, fx = f * iz, xz = xs * iz2 * f, yz = ys * iz2 * f;
-  float ic, g8x = 0.f, g8y = 0.f;
+  double f = L.cam.f, iz = rz, iz2 = iz * iz, fx = f * iz, xz = xs * iz2 * f, yz = ys * iz2 * f;
+  // (only the accumulation under `if (ok)` reads these three, and the optimiser would sink them in there, behind the wait: the empty statement keeps them here,
+  // under the taps' round trip)
+  if constexpr (U8SRC && JAC) asm volatile("" : "+v"(fx), "+v"(xz), "+v"(yz));
+  float ic, g8x = 0.f, g8y = 0.f;     // (the bilinear dx, dy of either source; the loads of the f32 pyramids unconditional like the u8 taps)
   if constexpr (U8SRC) { taps_u8_wait<TRK_TAPS_ASM>(taps); taps_u8_finish(taps, uvx, uvy, ic, g8x, g8y); }
-  else ic = interp32f(L.cur, L.fstride, uvx, uvy);
-  const double r0[6] = {-fx, 0, xz, xz * ys, -__builtin_fma(xz, xs, f), ys * fx};
-  const double r1[6] = {0, -fx, yz, __builtin_fma(yz, ys, f), -(yz * xs), -(xs * fx)};
+  else {
+    ic = interp32f(L.cur, L.fstride, uvx, uvy);
+    if (JAC) { g8x = interp32f(L.dx, L.fstride, uvx, uvy); g8y = interp32f(L.dy, L.fstride, uvx, uvy); }
+  }
   float res = ip - ic;
   // dense_tracking.cpp:299-300 `if (res > 0.1) res = 0.1; if (res < -0.1) res = -0.1;` on a float res: the comparisons are made in double against the double 0.1,
   // which lies between 0.1f and the float below it, so `res > 0.1` is `res >= 0.1f` and the assignment stores 0.1f -- min / max with +-0.1f, bit for bit
   // (res is never NaN: both images are finite), two instructions instead of two conversions and two f64 compares
   res = fminf(fmaxf(res, -0.1f), 0.1f);
-  if (!ok) res = 0.f;
-  a.v[27] += (double)(res * res);
   // the term of the reference's `float chi2 += res*res` (0 where the reference skips the sample: x + 0 is exact)
-  if constexpr (TM != 0) *term_out = res * res;
+  if constexpr (TM != 0) *term_out = ok ? res * res : 0.f;
   a.n += ok ? 1 : 0;
-  if (JAC) {
-    const float gx = ok ? (float)(0.5 * (U8SRC ? g8x : interp32f(L.dx, L.fstride, uvx, uvy))) : 0.f;
-    const float gy = ok ? (float)(0.5 * (U8SRC ? g8y : interp32f(L.dy, L.fstride, uvx, uvy))) : 0.f;
-    {
+  // An invalid sample is SKIPPED, not added as zeros (one exec mask instead of a select per operand).  The sums keep their bits: the masked form added
+  // fma(+-0, +-0, acc) to H and b and acc + 0.0 to chi2, which leaves every acc but -0 as it is, and no accumulator is ever -0 -- each starts at +0, x + y
+  // of opposite signs that cancel exactly rounds to +0, and a product small enough to round to -0 would need |J| < 1e-150 (J is a half u8 gradient, >= 1e-17
+  // where it is not 0, times a camera-geometry factor).  (The tap loads above stay unconditional, at the safe position.)
+  if (ok) {
+    a.v[27] += (double)(res * res);
+    if (JAC) {
+      const double r0[6] = {-fx, 0, xz, xz * ys, -__builtin_fma(xz, xs, f), ys * fx};
+      const double r1[6] = {0, -fx, yz, __builtin_fma(yz, ys, f), -(yz * xs), -(xs * fx)};
+      const float gx = (float)(0.5 * g8x);
+      const float gy = (float)(0.5 * g8y);
       double J[6];
       J[0] = gx * r0[0];
       J[1] = gy * r1[1];
@@ -358,12 +372,11 @@ __device__ __forceinline__ void track_pass(const LA &L_in, const double *T_in, d
     if constexpr (TM == 1) { if (pend) *pend_p = pend_t; }
     if constexpr (TM == 2) { if (pend) __hip_atomic_store(pend_p, pend_t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
   };
-  for (; i < n; i += STEP) {
+  // one trip: the term store of the trip before, the prefetch of the next sample into `nxt`, the sample in `cur`
+  auto trip = [&](const SampleIn (&cur)[TRK_UNROLL], SampleIn (&nxt)[TRK_UNROLL]) {
     if constexpr (TM != 0) { flush(); pend = t_buf != nullptr; }
-    SampleIn cur[TRK_UNROLL];
 #pragma unroll
     for (int q = 0; q < TRK_UNROLL; ++q) {
-      cur[q] = nxt[q];
       pu[q] += su; pv[q] += sv;
       if (pu[q] >= cw) { pu[q] -= cw; ++pv[q]; }
       const bool in = pv[q] < ch;
@@ -374,7 +387,17 @@ __device__ __forceinline__ void track_pass(const LA &L_in, const double *T_in, d
       if constexpr (TM != 0) sample_cpu_sem<JAC, U8SRC, TM, LA>(L, T, cur[q], true, a, ip_lut, &pend_t);      // (i < n: in range)
       else sample_cpu_sem<JAC, U8SRC, 0, LA>(L, T, cur[q], i + q * TRK_THREADS * nwg < n, a, ip_lut);
     }
-  }
+    i += STEP;
+  };
+  // Two trips per iteration on two register sets -- `nxt` consumed while `alt` is in flight, then the reverse --, so that no trip copies its prefetched sample
+  // into a "current" one (five moves per sample); one more trip behind the loop for a lane with an odd count.  Same samples, same order, in every lane.
+  SampleIn alt[TRK_UNROLL];
+  // (the first sample's own operands, which its projection needs at once, waited for HERE, in the builtin form the compiler's bookkeeping reads: entered with
+  // them "in flight" the loop would wait for them behind the trip's store and prefetch -- vmcnt(2) in every trip, which completes the trip's own store in front of
+  // its taps; see taps_u8_wait)
+  if constexpr (U8SRC) __builtin_amdgcn_s_waitcnt(0x0f70);
+  while (i + STEP < n) { trip(nxt, alt); trip(alt, nxt); }      // (both trips in range; i + STEP is far below 2^31)
+  if (i < n) trip(nxt, alt);
   if constexpr (TM != 0) flush();
   block_reduce<TRK_THREADS / 64>(a, s_part, s_out);
 }
@@ -882,7 +905,9 @@ __global__ __launch_bounds__(TRK_THREADS, 2) void dense_track_cpu_sem_kernel(Tra
     tb[0] = SEQ ? reinterpret_cast<float *>(G.part) + (size_t)slot * G.fail_off : (G.terms ? G.terms + (size_t)slot * 2 * G.terms_b : nullptr);
     tb[1] = SEQ ? tb[0] : (G.terms ? tb[0] + G.terms_b : nullptr);
     int cur = 0;
-    sweep_at(s_T, tb[cur]);        // chi2 (dense_tracking.cpp:229-261) + H,b of iteration 0
+    // (inlined by hand -- and with it the trial sweep below, then the lambda's one remaining use: with two trips per iteration the sweep is past the inliner's
+    // own threshold, and left alone both sweeps of this kernel became calls of one out-of-line copy built for 246 / 214 registers)
+    [[clang::always_inline]] sweep_at(s_T, tb[cur]);        // chi2 (dense_tracking.cpp:229-261) + H,b of iteration 0
     if (!solo) all_workgroups();
     if (MULTI && s_failed) { failed = true; break; }
     ++passes;

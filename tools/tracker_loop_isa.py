@@ -12,6 +12,10 @@ the function's VGPRs / scratch / occupancy, the order in which the trip issues i
     stores in one queue: behind k requests of the trip it makes k - N of them complete before the taps are even issued -- the prefetch is then no
     prefetch, and a trip pays two memory round trips one after the other (profiles/tracker_prefetch.md).
 
+It also reports the function's LDS and, per loop, the vector-ALU instructions per processed sample (f64, f32, integer, quarter-rate, moves / selects; one
+f64 reciprocal -- one projection -- marks a sample).  The sweep runs two trips per iteration on alternating register sets (profiles/tracker_sweep.md): such a
+loop is listed as one entry per trip, each held to both verdicts on its own, and its per-sample count is the loop's count over its samples.
+
 A tracker whose taps are waited for row by row pays one memory round trip per row and sample; the compiler chose that once, silently, at the
 128-register limit of the big-batch kernels (profiles/tracker_taps.md).  tests/test_tracker_isa_cpu.py holds the two hot instantiations to the verdict.
 
@@ -86,7 +90,7 @@ def split_functions(text):
                 info = {}
                 j = i + 1
                 while j < len(lines) and not re.match(r"^(_Z\w+):", lines[j]) and j < i + 80:
-                    mi = re.match(r"^; (\w+): (\d+)\s*$", lines[j])
+                    mi = re.match(r"^; (\w+): (\d+)\s*(bytes/workgroup.*)?$", lines[j])      # ("; LDSByteSize: 17744 bytes/workgroup (compile time only)")
                     if mi:
                         info[mi.group(1)] = int(mi.group(2))
                     j += 1
@@ -245,8 +249,29 @@ def analyse_loop(ins):
     return res
 
 
+VALU_CLASSES = ("f64", "f32", "integer", "quarter-rate", "moves/selects")
+
+
+def split_trips(ins):
+    """The trips of a loop that handles several samples per iteration (track_pass runs two, on alternating register sets), in order.  A trip ends with the wait that
+    covers its four tap loads plus what follows up to the next memory request; a loop of one sample, or of an f32 source (no tap loads), is one trip."""
+    taps = [k for k, s in enumerate(ins) if is_tap_load(s)]
+    if len(taps) <= 4 or len(taps) % 4:
+        return [ins]
+    cuts = [0]
+    for g in range(4, len(taps), 4):
+        k = taps[g - 1] + 1
+        while k < taps[g] and vmcnt_of(ins[k]) is None:      # the wait behind the trip before
+            k += 1
+        while k < taps[g] and not is_vm_op(ins[k]):           # its arithmetic
+            k += 1
+        cuts.append(k)
+    return [ins[a:b] for a, b in zip(cuts, cuts[1:] + [len(ins)])]
+
+
 def analyse(asm_text):
-    """One record per function that inlines the tracker's sweep: name, resources, its sample loops."""
+    """One record per function that inlines the tracker's sweep: name, resources, its sample loops.  A loop of several samples per iteration gives one entry per
+    trip (each held to the tap and wait verdicts on its own); `valu_per_sample` is the whole loop's vector-ALU count over the samples it handles."""
     out = []
     for mangled, body, info in split_functions(asm_text):
         name = pretty_name(mangled)
@@ -254,12 +279,19 @@ def analyse(asm_text):
             continue
         loops = []
         for head, ins in loops_of(body):
-            a = analyse_loop(ins)
-            if a["f64_fma"] >= 27 and not any(x.startswith("s_swappc") for x in ins):      # the 27 accumulations of H and b and no call: a loop over samples
-                a["header"] = head
+            whole = analyse_loop(ins)
+            if whole["f64_fma"] < 27 or any(x.startswith("s_swappc") for x in ins):      # the 27 accumulations of H and b and no call: a loop over samples
+                continue
+            samples = max(1, sum(1 for s in ins if s.startswith("v_rcp_f64")))             # one projection (one f64 reciprocal) per sample
+            valu = sum(whole["classes"][c] for c in VALU_CLASSES)
+            trips = split_trips(ins)
+            for t, part in enumerate(trips):
+                a = whole if len(trips) == 1 else analyse_loop(part)
+                a.update(header=head if len(trips) == 1 else "%s, trip %d of %d" % (head, t + 1, len(trips)), samples_in_loop=samples,
+                         loop_instructions=len(ins), loop_valu=valu, valu_per_sample=valu / samples, lds_in_loop=whole["classes"]["LDS"])
                 loops.append(a)
         out.append(dict(name=name, mangled=mangled, vgpr=info.get("NumVgprs"), sgpr=info.get("NumSgprs"), scratch=info.get("ScratchSize"), occupancy=info.get("Occupancy"),
-                        hot=name in HOT, loops=loops, verdict=all(l["verdict"] is not False for l in loops),
+                        lds=info.get("LDSByteSize"), hot=name in HOT, loops=loops, verdict=all(l["verdict"] is not False for l in loops),
                         prefetch_verdict=all(l["prefetch_verdict"] is not False for l in loops)))
     out.sort(key=lambda r: (not r["hot"], r["name"]))
     return out
@@ -267,15 +299,16 @@ def analyse(asm_text):
 
 def render(records, title):
     o = ["## " + title, ""]
-    o.append("| function | VGPR | scratch B | occupancy | sample loops | taps before the first wait that covers one | nothing touches their registers until then | scratch in the loop | verdict | own requests a wait in front of the taps forces | verdict |")
-    o.append("|---|---|---|---|---|---|---|---|---|---|---|")
+    o.append("| function | VGPR | scratch B | occupancy | LDS B | VALU per sample | sample loops | taps before the first wait that covers one | nothing touches their registers until then | scratch in the loop | verdict | own requests a wait in front of the taps forces | verdict |")
+    o.append("|---|---|---|---|---|---|---|---|---|---|---|---|---|")
     for r in records:
         taps = ", ".join("%d of %d" % (l["taps_before_wait"], l["tap_loads"]) for l in r["loops"])
         unt = ", ".join({True: "yes", False: "NO", None: "-"}[l["dest_untouched"]] for l in r["loops"])
         scr = ", ".join(str(l["scratch_in_loop"]) for l in r["loops"])
         frc = ", ".join("-" if l["prefetch_verdict"] is None else "%d (%s)" % (l["prefetch_forced"], " ".join(w["wait"] for w in l["prefetch_waits"]) or "no wait") for l in r["loops"])
-        o.append("| `%s`%s | %s | %s | %s | %d | %s | %s | %s | %s | %s | %s |" % (r["name"], " **(hot)**" if r["hot"] else "", r["vgpr"], r["scratch"], r["occupancy"] if r["occupancy"] is not None else "-",
-                                                                     len(r["loops"]), taps, unt, scr, "ok" if r["verdict"] else "**FAILS**", frc,
+        vps = ", ".join(sorted(set("%g" % l["valu_per_sample"] for l in r["loops"]), key=float))
+        o.append("| `%s`%s | %s | %s | %s | %s | %s | %d | %s | %s | %s | %s | %s | %s |" % (r["name"], " **(hot)**" if r["hot"] else "", r["vgpr"], r["scratch"], r["occupancy"] if r["occupancy"] is not None else "-",
+                                                                     r["lds"] if r["lds"] is not None else "-", vps, len(r["loops"]), taps, unt, scr, "ok" if r["verdict"] else "**FAILS**", frc,
                                                                      "ok" if r["prefetch_verdict"] else "**FAILS**"))
     o.append("")
     for r in records:
@@ -285,6 +318,9 @@ def render(records, title):
             o.append("### `%s`, sample loop %d of %d (%s)" % (r["name"], k + 1, len(r["loops"]), l["header"]))
             o.append("")
             o.append("%d instructions per trip: " % l["instructions"] + ", ".join("%s %d" % (c, l["classes"][c]) for c in CLASSES if l["classes"][c]))
+            o.append("")
+            o.append("the loop handles %d sample(s) per iteration with %d instructions, %d of them vector ALU: %g VALU per sample"
+                     % (l["samples_in_loop"], l["loop_instructions"], l["loop_valu"], l["valu_per_sample"]))
             o.append("")
             o.append("memory operations and waits in trip order: " + " -> ".join(l["memory_order"]))
             o.append("")
