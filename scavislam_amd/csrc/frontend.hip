@@ -25,8 +25,10 @@
 #include "newpoints.h"
 #include "pose.h"
 #include "seed.h"
+#include "staging.h"
 #include <string.h>
 #include <algorithm>
+#include <type_traits>
 #include <vector>
 
 namespace {
@@ -173,12 +175,12 @@ struct svs_frontend {
   DevBuf<svs_subpix_info> d_subpix_info;
   int subpix_n = -1;
   // svs_frontend_set_candidates_from_map: the staged requests and, behind them, what comes back; grown on demand
-  PinnedBuf<uint8_t> h_nbh; DevBuf<uint8_t> d_nbh;
+  TwinBlock nbh;
   // the keyframe decision (svs_frontend_set_vertex_table / svs_frontend_decide_keyframes, keyframe.hip): the streams' resident vertex tables, the staging block
   // of the setter, the decision records and list rows; all allocated with the first table
   std::vector<uint8_t> vt_set;          // [B]: the stream has a table
   DevBuf<svs_kf_table> d_vt_tab; DevBuf<svs_kf_vertex> d_vt_vtx; DevBuf<int32_t> d_vt_slot, d_vt_ids;
-  PinnedBuf<uint8_t> h_vt; DevBuf<uint8_t> d_vt_up;
+  TwinBlock vt_up;
   DevBuf<svs_keyframe_decision> d_kd_dec; DevBuf<svs_map_new_point> d_kd_new; DevBuf<svs_map_track_point> d_kd_track; DevBuf<int32_t> d_kd_new_rec, d_kd_track_rec;
   PinnedBuf<svs_keyframe_decision> h_kd_dec;
   // svs_frontend_commit_keyframe: the steps counted, the count the records in h_kd_dec were decided at (kd_have: there are any), and the pinned block the pose and
@@ -192,7 +194,7 @@ struct svs_frontend {
   int np_rcap = 0, np_gcap = 0;
   DevBuf<svs_candidate_point> d_np_rec, d_np_tmp; DevBuf<int32_t> d_np_key, d_np_cnt, d_np_ng, d_np_removed;
   std::vector<int32_t> np_key, np_cnt, np_ng;      // [B][64], [B][64], [B]
-  PinnedBuf<uint8_t> h_np; DevBuf<uint8_t> d_np;   // staging block of the calls, grown on demand
+  TwinBlock np;                                    // staging block of the calls, grown on demand
   // drains the streams and takes the detector / block matcher along before the members above go (also when create gives up half way)
   ~svs_frontend() {
     (void)hipStreamSynchronize(ctx->stream);
@@ -204,17 +206,52 @@ struct svs_frontend {
 };
 constexpr int REC_CAP = 64;
 
-static void fastgrid_for_level(int w, int h, int level, svs_fastgrid *g) {      // stereo_frontend.cpp:73-88 + fast_grid.cpp:23-58
-  const int dim = std::max(3 - (int)(level * 0.5), 1);
-  const double inv_fac = 1.0 / (1 << level);
-  const int total = (int)(2000 * inv_fac * inv_fac), per_cell = total / (dim * dim), bound = std::max(per_cell / 3, 10);
-  g->gx = g->gy = dim;
-  g->min_inner = (int)(per_cell - bound * 0.33); g->min_outer = per_cell - bound;
-  g->max_inner = (int)(per_cell + bound * 0.33); g->max_outer = per_cell + bound;
-  g->cell_w = w / dim; g->cell_h = h / dim;
-  g->fast_min = 10; g->fast_max = 40;
-  for (int i = 0; i < SVS_MAX_CELLS; ++i) g->thr[i] = 25;
+namespace {
+// ---- what the list setters share: their checks (every one of a call runs before its first upload) and the tail in which the host state follows the download
+bool all_distinct(std::vector<int32_t> &v) {      // (sorts v)
+  std::sort(v.begin(), v.end());
+  return std::adjacent_find(v.begin(), v.end()) == v.end();
 }
+// every slot a slot table names is one svs_frontend_keep_keyframe has filled, and no keyframe id is named twice
+int fe_check_slot_table(svs_frontend *fe, int stream, const int32_t *h_slot_kf, std::vector<int32_t> &ids) {
+  svs_ctx *ctx = fe->ctx;
+  const uint8_t *kept = fe->kept.data() + (size_t)stream * fe->max_keyframes;
+  ids.clear();
+  for (int s = 0; s < fe->max_keyframes; ++s)
+    if (h_slot_kf[s] >= 0) { SVS_REQUIRE(ctx, kept[s]); ids.push_back(h_slot_kf[s]); }
+  SVS_REQUIRE(ctx, all_distinct(ids));
+  return SVS_OK;
+}
+// group ends rise and the last equals n
+int fe_check_group_ends(svs_ctx *ctx, const int32_t *h_group_end, int n_groups, int n) {
+  SVS_REQUIRE(ctx, h_group_end[n_groups - 1] == n);
+  for (int g = 0; g < n_groups; ++g) SVS_REQUIRE(ctx, h_group_end[g] >= (g ? h_group_end[g - 1] : 0));
+  return SVS_OK;
+}
+// a record must name a keyframe slot that svs_frontend_keep_keyframe has filled (kf_index < 0 = "anchor not in the map", matcher.cpp:336-339)
+int fe_check_anchors(svs_frontend *fe, int stream, const svs_candidate_point *h_pts, int n) {
+  svs_ctx *ctx = fe->ctx;
+  const uint8_t *kept = fe->kept.data() + (size_t)stream * fe->max_keyframes;
+  for (int i = 0; i < n; ++i) SVS_REQUIRE(ctx, h_pts[i].kf_index < 0 || (h_pts[i].kf_index < fe->max_keyframes && kept[h_pts[i].kf_index]));
+  return SVS_OK;
+}
+// a stream's list on the device was replaced
+void fe_lists_changed(svs_frontend *fe) {
+  fe->n_launch = *std::max_element(fe->n_points.begin(), fe->n_points.end());
+  fe->n_gated = -1;      // the last step's gate records no longer belong to the list on the device
+}
+// row r (`per` elements) of a downloaded piece to the caller's optional array; for a request that wrote none: ids -1, poses 0
+template <class T> void fe_row_out(T *dst, const T *src, int r, size_t per, bool none) {
+  if (!dst) return;
+  if (none) memset(dst + (size_t)r * per, std::is_integral<T>::value ? 0xff : 0, per * sizeof(T));
+  else memcpy(dst + (size_t)r * per, src + (size_t)r * per, per * sizeof(T));
+}
+// the mirror of the kept keyframes takes the poses a neighbourhood call refreshed on the device: slot_T [max_keyframes][12] of the request
+void fe_refresh_poses(svs_frontend *fe, const svs_map *map, int stream, const int32_t *h_slot_kf, const double *slot_T) {
+  for (int k = 0; k < fe->max_keyframes; ++k)
+    if (svs_map_has_keyframe(map, h_slot_kf[k])) memcpy(fe->h_kfs[(size_t)stream * fe->max_keyframes + k].T_anchor_from_w, slot_T + (size_t)k * 12, 12 * sizeof(double));
+}
+}  // namespace
 
 extern "C" int svs_frontend_destroy(svs_frontend *fe) {
   if (!fe) return SVS_OK;
@@ -332,12 +369,10 @@ extern "C" int svs_frontend_set_candidates_grouped(svs_frontend *fe, int stream,
   svs_ctx *ctx = fe ? fe->ctx : nullptr;
   SVS_REQUIRE(ctx, fe && stream >= 0 && stream < fe->B && n >= 0 && n <= fe->max_points && (n == 0 || h_pts));
   SVS_REQUIRE(ctx, !fe->submitted);      // between submit_frame and wait_frame the list of the frame in flight is latched (wait_frame sizes its copies by it)
-  SVS_REQUIRE(ctx, h_group_end && n_groups >= 2 && n_groups <= MAX_GROUPS && h_group_end[n_groups - 1] == n);
-  for (int g = 0; g < n_groups; ++g) SVS_REQUIRE(ctx, h_group_end[g] >= (g ? h_group_end[g - 1] : 0));
+  SVS_REQUIRE(ctx, h_group_end && n_groups >= 2 && n_groups <= MAX_GROUPS);
+  if (int rc = fe_check_group_ends(ctx, h_group_end, n_groups, n)) return rc;
   SVS_DEVICE(ctx);
-  // a candidate must name a keyframe slot that svs_frontend_keep_keyframe has filled (kf_index < 0 = "anchor not in the map", matcher.cpp:336-339)
-  for (int i = 0; i < n; ++i)
-    SVS_REQUIRE(ctx, h_pts[i].kf_index < 0 || (h_pts[i].kf_index < fe->max_keyframes && fe->kept[(size_t)stream * fe->max_keyframes + h_pts[i].kf_index]));
+  if (int rc = fe_check_anchors(fe, stream, h_pts, n)) return rc;
   SVS_HIP(ctx, hipStreamSynchronize(ctx->stream));
   svs_candidate_point *dst = fe->d_pts + (size_t)stream * fe->max_points;
   if (n) SVS_HIP(ctx, hipMemcpyAsync(dst, h_pts, sizeof(svs_candidate_point) * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
@@ -349,8 +384,7 @@ extern "C" int svs_frontend_set_candidates_grouped(svs_frontend *fe, int stream,
   SVS_HIP(ctx, hipMemcpyAsync(fe->d_n_new + stream, &h_group_end[n_groups - 2], sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
   SVS_HIP(ctx, hipStreamSynchronize(ctx->stream));      // h_pts may be pageable and reused by the caller
   fe->n_points[stream] = n; fe->n_new_records[stream] = h_group_end[n_groups - 2];
-  fe->n_launch = *std::max_element(fe->n_points.begin(), fe->n_points.end());
-  fe->n_gated = -1;      // the last step's gate records no longer belong to the list on the device
+  fe_lists_changed(fe);
   fe->max_groups_used = std::max(fe->max_groups_used, n_groups);
   return SVS_OK;
 }
@@ -415,16 +449,15 @@ extern "C" int svs_frontend_set_candidates_all(svs_frontend *fe, const svs_candi
   const int B = fe->B;
   size_t total = 0;
   for (int b = 0; b < B; ++b) {
-    SVS_REQUIRE(ctx, h_n[b] >= 0 && h_n[b] <= fe->max_points && h_group_end[(size_t)b * n_groups + n_groups - 1] == h_n[b]);
-    for (int g = 0; g < n_groups; ++g) SVS_REQUIRE(ctx, h_group_end[(size_t)b * n_groups + g] >= (g ? h_group_end[(size_t)b * n_groups + g - 1] : 0));
+    SVS_REQUIRE(ctx, h_n[b] >= 0 && h_n[b] <= fe->max_points);
+    if (int rc = fe_check_group_ends(ctx, h_group_end + (size_t)b * n_groups, n_groups, h_n[b])) return rc;
     total += (size_t)h_n[b];
   }
   SVS_REQUIRE(ctx, total == 0 || h_pts);
   {
     size_t off = 0;
-    for (int b = 0; b < B; ++b)
-      for (int i = 0; i < h_n[b]; ++i, ++off)
-        SVS_REQUIRE(ctx, h_pts[off].kf_index < 0 || (h_pts[off].kf_index < fe->max_keyframes && fe->kept[(size_t)b * fe->max_keyframes + h_pts[off].kf_index]));
+    for (int b = 0; b < B; off += (size_t)h_n[b], ++b)
+      if (int rc = fe_check_anchors(fe, b, h_pts + off, h_n[b])) return rc;
   }
   // the device list is [n_streams][max_points]: lay the records out like that in a pinned block the front end keeps (unused tails = 0xff, "no candidate") and send
   // the first m records of every stream as one strided copy, m = the longest list now or before (what lies behind a stream's list on the device is 0xff: svs_frontend_create, the per-stream setters)
@@ -450,8 +483,7 @@ extern "C" int svs_frontend_set_candidates_all(svs_frontend *fe, const svs_candi
   SVS_HIP(ctx, hipMemcpyAsync(fe->d_n_new, nn.data(), sizeof(int32_t) * B, hipMemcpyHostToDevice, ctx->stream));
   SVS_HIP(ctx, hipStreamSynchronize(ctx->stream));
   for (int b = 0; b < B; ++b) { fe->n_points[b] = h_n[b]; fe->n_new_records[b] = nn[b]; }
-  fe->n_launch = *std::max_element(fe->n_points.begin(), fe->n_points.end());
-  fe->n_gated = -1;      // the last step's gate records no longer belong to the list on the device
+  fe_lists_changed(fe);
   fe->max_groups_used = std::max(fe->max_groups_used, n_groups);
   return SVS_OK;
 }
@@ -478,36 +510,28 @@ extern "C" int svs_frontend_set_candidates_from_map(svs_frontend *fe, svs_map *m
       if (q.n_head_groups + 1 > MAX_GROUPS) { ctx->err = "svs_frontend_set_candidates_from_map: more than 64 groups"; return SVS_ERR_CAPACITY; }
       for (int i = 0; i < q.n_vertex; ++i) SVS_REQUIRE(ctx, svs_map_has_keyframe(map, q.h_vertex_kf[i]));
       sorted.assign(q.h_vertex_kf, q.h_vertex_kf + q.n_vertex);
-      std::sort(sorted.begin(), sorted.end());
-      SVS_REQUIRE(ctx, std::adjacent_find(sorted.begin(), sorted.end()) == sorted.end());
-      const uint8_t *kept = fe->kept.data() + (size_t)q.stream * K;
-      sorted.clear();
-      for (int s = 0; s < K; ++s)
-        if (q.h_slot_kf[s] >= 0) { SVS_REQUIRE(ctx, kept[s]); sorted.push_back(q.h_slot_kf[s]); }
-      std::sort(sorted.begin(), sorted.end());
-      SVS_REQUIRE(ctx, std::adjacent_find(sorted.begin(), sorted.end()) == sorted.end());
-      SVS_REQUIRE(ctx, q.h_head_group_end[q.n_head_groups - 1] == q.n_head);
-      for (int g = 0; g < q.n_head_groups; ++g) SVS_REQUIRE(ctx, q.h_head_group_end[g] >= (g ? q.h_head_group_end[g - 1] : 0));
-      for (int i = 0; i < q.n_head; ++i) SVS_REQUIRE(ctx, q.h_head[i].kf_index < 0 || (q.h_head[i].kf_index < K && kept[q.h_head[i].kf_index]));
+      SVS_REQUIRE(ctx, all_distinct(sorted));
+      if (int rc = fe_check_slot_table(fe, q.stream, q.h_slot_kf, sorted)) return rc;
+      if (int rc = fe_check_group_ends(ctx, q.h_head_group_end, q.n_head_groups, q.n_head)) return rc;
+      if (int rc = fe_check_anchors(fe, q.stream, q.h_head, q.n_head)) return rc;
       n_ids += (size_t)q.n_vertex + (size_t)K;
       n_head += (size_t)q.n_head;
     }
   }
   if (R == 0) return SVS_OK;
   SVS_DEVICE(ctx);
-  auto al = [](size_t v) { return (v + 15) & ~(size_t)15; };
-  const size_t o_ids = al((size_t)R * sizeof(nbh_req)), o_head = o_ids + al(n_ids * sizeof(int32_t)), in_bytes = o_head + n_head * sizeof(svs_candidate_point);
-  const size_t o_res = al(in_bytes), o_slot = o_res + (size_t)R * sizeof(svs_nbh_result), o_vid = o_slot + (size_t)R * K * 12 * sizeof(double),
-               o_vT = o_vid + al((size_t)R * VB * sizeof(int32_t)), o_pid = o_vT + (size_t)R * VB * 12 * sizeof(double), bytes = o_pid + (size_t)R * MP * sizeof(int32_t);
-  if (fe->h_nbh.bytes() < bytes) {      // (no call is in flight: this one is blocking)
-    SVS_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    SVS_HIP(ctx, fe->h_nbh.alloc(bytes * 2));
-    SVS_HIP(ctx, fe->d_nbh.alloc(bytes * 2));
-  }
-  uint8_t *hs = fe->h_nbh, *ds = fe->d_nbh;
-  nbh_req *hq = reinterpret_cast<nbh_req *>(hs);
-  int32_t *ids = reinterpret_cast<int32_t *>(hs + o_ids);
-  svs_candidate_point *head = reinterpret_cast<svs_candidate_point *>(hs + o_head);
+  // the block: what goes up (requests | vertex and slot ids | heads), then what comes back, the optional outputs last
+  Pieces<> row;
+  const size_t Rz = (size_t)R;
+  const auto p_req = row.piece<nbh_req>(Rz); const auto p_ids = row.piece<int32_t>(n_ids); const auto p_head = row.piece<svs_candidate_point>(n_head);
+  const size_t in_end = row.end;
+  const auto p_res = row.piece<svs_nbh_result>(Rz); const auto p_slot = row.piece<double>(Rz * K * 12);
+  const auto p_vid = row.piece<int32_t>(Rz * VB); const auto p_vT = row.piece<double>(Rz * VB * 12); const auto p_pid = row.piece<int32_t>(Rz * MP);
+  TwinBlock &blk = fe->nbh;
+  if (int rc = blk.reserve(ctx, row.end)) return rc;      // (no call is in flight: this one is blocking)
+  nbh_req *hq = blk.host(p_req);
+  int32_t *ids = blk.host(p_ids);
+  svs_candidate_point *head = blk.host(p_head);
   size_t at_id = 0, at_head = 0;
   for (int r = 0; r < R; ++r) {
     const svs_nbh_request &q = req[r];
@@ -525,52 +549,35 @@ extern "C" int svs_frontend_set_candidates_from_map(svs_frontend *fe, svs_map *m
     at_head += (size_t)q.n_head;
     for (int g = 0; g < q.n_head_groups; ++g) s.group_end[g] = q.h_head_group_end[g];
   }
-  SVS_HIP(ctx, hipMemcpyAsync(ds, hs, in_bytes, hipMemcpyHostToDevice, ctx->stream));
+  if (int rc = blk.upload(ctx, 0, in_end)) return rc;
   MapNbhDst D{};
-  D.req = reinterpret_cast<const nbh_req *>(ds); D.ids = reinterpret_cast<const int32_t *>(ds + o_ids); D.head = reinterpret_cast<const svs_candidate_point *>(ds + o_head);
+  D.req = blk.dev(p_req); D.ids = blk.dev(p_ids); D.head = blk.dev(p_head);
   D.pts = fe->d_pts; D.max_points = MP; D.group_end = fe->d_group_end; D.n_groups = fe->d_n_groups; D.n_new = fe->d_n_new; D.kfs = fe->d_kfs; D.max_keyframes = K;
   D.refresh = refresh_poses ? 1 : 0;
-  D.res = reinterpret_cast<svs_nbh_result *>(ds + o_res); D.slot_T = reinterpret_cast<double *>(ds + o_slot);
-  D.vertex_id = reinterpret_cast<int32_t *>(ds + o_vid); D.vertex_T = reinterpret_cast<double *>(ds + o_vT); D.VB = VB;
-  D.point_id = reinterpret_cast<int32_t *>(ds + o_pid);
+  D.res = blk.dev(p_res); D.slot_T = blk.dev(p_slot); D.vertex_id = blk.dev(p_vid); D.vertex_T = blk.dev(p_vT); D.VB = VB; D.point_id = blk.dev(p_pid);
   if (int rc = svs_map_build_neighborhoods(map, R, D)) return rc;
-  const size_t down_end = h_point_id ? bytes : (h_vertex_id || h_vertex_T) ? o_pid : o_vid;
-  SVS_HIP(ctx, hipMemcpyAsync(hs + o_res, ds + o_res, down_end - o_res, hipMemcpyDeviceToHost, ctx->stream));
+  // from the first output piece to the end of the last one a caller asked for
+  const size_t down_end = h_point_id ? p_pid.end() : (h_vertex_id || h_vertex_T) ? p_vT.end() : p_slot.end();
+  if (int rc = blk.download(ctx, p_res.off, down_end)) return rc;
   if (h_records) SVS_HIP(ctx, hipMemcpyAsync(h_records, fe->d_pts, sizeof(svs_candidate_point) * (size_t)MP * B, hipMemcpyDeviceToHost, ctx->stream));
   SVS_HIP(ctx, hipStreamSynchronize(ctx->stream));
   // ---- the host state follows the download
-  const svs_nbh_result *res = reinterpret_cast<const svs_nbh_result *>(hs + o_res);
+  const svs_nbh_result *res = blk.host(p_res);
   bool any = false;
   for (int r = 0; r < R; ++r) {
     const svs_nbh_request &q = req[r];
     const bool over = res[r].over_capacity != 0;
     if (h_res) h_res[r] = res[r];
-    if (h_point_id) {
-      if (over) std::fill(h_point_id + (size_t)r * MP, h_point_id + (size_t)(r + 1) * MP, -1);
-      else memcpy(h_point_id + (size_t)r * MP, hs + o_pid + (size_t)r * MP * sizeof(int32_t), (size_t)MP * sizeof(int32_t));
-    }
-    if (h_vertex_id) {
-      if (over) std::fill(h_vertex_id + (size_t)r * VB, h_vertex_id + (size_t)(r + 1) * VB, -1);
-      else memcpy(h_vertex_id + (size_t)r * VB, hs + o_vid + (size_t)r * VB * sizeof(int32_t), (size_t)VB * sizeof(int32_t));
-    }
-    if (h_vertex_T) {
-      if (over) memset(h_vertex_T + (size_t)r * VB * 12, 0, (size_t)VB * 12 * sizeof(double));
-      else memcpy(h_vertex_T + (size_t)r * VB * 12, hs + o_vT + (size_t)r * VB * 12 * sizeof(double), (size_t)VB * 12 * sizeof(double));
-    }
+    fe_row_out(h_point_id, blk.host(p_pid), r, (size_t)MP, over);
+    fe_row_out(h_vertex_id, blk.host(p_vid), r, (size_t)VB, over);
+    fe_row_out(h_vertex_T, blk.host(p_vT), r, (size_t)VB * 12, over);
     if (over) continue;
     any = true;
     fe->n_points[q.stream] = res[r].n_points; fe->n_new_records[q.stream] = q.n_head;
     fe->max_groups_used = std::max(fe->max_groups_used, q.n_head_groups + 1);
-    if (refresh_poses) {
-      const double *sT = reinterpret_cast<const double *>(hs + o_slot) + (size_t)r * K * 12;
-      for (int k = 0; k < K; ++k)
-        if (svs_map_has_keyframe(map, q.h_slot_kf[k])) memcpy(fe->h_kfs[(size_t)q.stream * K + k].T_anchor_from_w, sT + (size_t)k * 12, 12 * sizeof(double));
-    }
+    if (refresh_poses) fe_refresh_poses(fe, map, q.stream, q.h_slot_kf, blk.host(p_slot) + (size_t)r * K * 12);
   }
-  if (any) {
-    fe->n_launch = *std::max_element(fe->n_points.begin(), fe->n_points.end());
-    fe->n_gated = -1;      // the last step's gate records no longer belong to the list on the device
-  }
+  if (any) fe_lists_changed(fe);
   return SVS_OK;
 }
 
@@ -1199,21 +1206,27 @@ static int fe_seed_keyframes(svs_frontend *fe, int n, const svs_seed_request *re
   }
   if (sink) if (int rc = sink->check()) return rc;
   SVS_DEVICE(ctx);
-  // staging block: problems | streams | orders of level 0, 1, 2 ; device block: the same, then counts [n][3] (padded to 64 bytes) | records [n][cap]
-  auto up64 = [](size_t v) { return (v + 63) & ~(size_t)63; };
-  const size_t off_slot = up64(sizeof(svs_seed_problem) * (size_t)n);
-  size_t off_ord[3], in_bytes = up64(off_slot + sizeof(int32_t) * (size_t)n);
-  for (int l = 0; l < 3; ++l) { off_ord[l] = in_bytes; in_bytes = up64(in_bytes + sizeof(int32_t) * ob[l] * (size_t)n); }
-  const size_t off_cnt = in_bytes, off_rec = up64(off_cnt + sizeof(int32_t) * 3 * (size_t)n);
-  const size_t out_bytes = (off_rec - off_cnt) + sizeof(svs_candidate_point) * (size_t)cap_per_request * (size_t)n, d_bytes = off_cnt + out_bytes;
+  // device block, pieces of 64 bytes' alignment: problems | streams | orders of level 0, 1, 2 ; then counts [n][3] | records [n][cap].  The pinned block is NOT its
+  // twin: it holds the input pieces at the same offsets on the way up and, on the way back, the row `out` = the two output pieces from offset 0 on (the counts piece
+  // begins on a 64-byte boundary, so the records lie as far behind the counts in `out` as on the device and one copy brings both) -- never the megabytes in between
+  const size_t nz = (size_t)n;
+  Pieces<64> dv, out;
+  const auto p_prob = dv.piece<svs_seed_problem>(nz); const auto p_slot = dv.piece<int32_t>(nz);
+  Piece<int32_t> p_ord[3];
+  for (int l = 0; l < 3; ++l) p_ord[l] = dv.piece<int32_t>(ob[l] * nz);
+  const size_t in_bytes = dv.end_aligned();
+  const auto p_cnt = dv.piece<int32_t>(3 * nz); const auto p_rec = dv.piece<svs_candidate_point>((size_t)cap_per_request * nz);
+  const auto h_cnt = out.piece<int32_t>(3 * nz); const auto h_rec = out.piece<svs_candidate_point>((size_t)cap_per_request * nz);
+  const size_t out_bytes = out.end, d_bytes = dv.end;
   // small results go home in one copy through the pinned block; big ones as the counts, then one strided copy of the longest list's width into the caller's array
   const bool one_copy = h_out && out_bytes <= ((size_t)1 << 20);
-  const size_t h_bytes = std::max(in_bytes, one_copy ? out_bytes : off_rec - off_cnt);
+  const size_t h_bytes = std::max(in_bytes, one_copy ? out_bytes : h_rec.off);
   if (fe->h_seed.bytes() < h_bytes || fe->d_seed.bytes() < d_bytes) SVS_HIP(ctx, hipStreamSynchronize(ctx->stream));
   if (fe->h_seed.bytes() < h_bytes) SVS_HIP(ctx, fe->h_seed.alloc_bytes(h_bytes));
   if (fe->d_seed.bytes() < d_bytes) SVS_HIP(ctx, fe->d_seed.alloc_bytes(d_bytes));
-  svs_seed_problem *hp = reinterpret_cast<svs_seed_problem *>(fe->h_seed.get());
-  int32_t *hs = reinterpret_cast<int32_t *>(fe->h_seed + off_slot);
+  uint8_t *const hb = fe->h_seed, *const db = fe->d_seed;
+  svs_seed_problem *hp = piece_at(hb, p_prob);
+  int32_t *hs = piece_at(hb, p_slot);
   for (int r = 0; r < n; ++r) {
     const svs_seed_request &q = req[r];
     svs_seed_problem p{};
@@ -1226,46 +1239,42 @@ static int fe_seed_keyframes(svs_frontend *fe, int n, const svs_seed_request *re
     p.use_order = (q.h_order[0] || q.h_order[1] || q.h_order[2]) ? 1 : 0;
     for (int l = 0; l < prm->n_levels && p.use_order; ++l) {
       p.n_order[l] = q.h_order[l] ? q.n_order[l] : 0;
-      if (p.n_order[l]) __builtin_memcpy(fe->h_seed + off_ord[l] + sizeof(int32_t) * ob[l] * (size_t)r, q.h_order[l], sizeof(int32_t) * (size_t)p.n_order[l]);
+      if (p.n_order[l]) __builtin_memcpy(piece_at(hb, p_ord[l]) + ob[l] * (size_t)r, q.h_order[l], sizeof(int32_t) * (size_t)p.n_order[l]);
     }
     hp[r] = p; hs[r] = q.stream;
   }
-  SVS_HIP(ctx, hipMemcpyAsync(fe->d_seed, fe->h_seed, in_bytes, hipMemcpyHostToDevice, ctx->stream));
+  SVS_HIP(ctx, hipMemcpyAsync(db, hb, in_bytes, hipMemcpyHostToDevice, ctx->stream));
   svs_seed_args a{};
   for (int l = 0; l < prm->n_levels; ++l) {
     a.d_xy[l] = fv.xy[l]; a.xy_bstride[l] = (size_t)fv.cap * 2; a.xy_cap[l] = fv.cap;
     a.d_n[l] = fv.level_total + l; a.n_bstride[l] = (size_t)fv.n_levels;
     a.d_cell_count[l] = fv.count + fv.cell_base[l]; a.cell_bstride[l] = (size_t)fv.ncell_total; a.n_cells[l] = fv.ncell[l];
-    a.d_order[l] = ob[l] ? reinterpret_cast<const int32_t *>(fe->d_seed + off_ord[l]) : nullptr; a.order_bstride[l] = ob[l];
+    a.d_order[l] = ob[l] ? piece_at(db, p_ord[l]) : nullptr; a.order_bstride[l] = ob[l];
   }
   a.d_disp = fe->last_disp; a.disp_stride = fe->last_dstride; a.disp_bstride = fe->last_dbstride;
   a.cam = fe->cams[0];
-  a.d_prob = reinterpret_cast<const svs_seed_problem *>(fe->d_seed.get());
+  a.d_prob = piece_at(db, p_prob);
   a.batch = n;
   SeedFrontendSrc fs{};
-  fs.slot_of = reinterpret_cast<const int32_t *>(fe->d_seed + off_slot);
+  fs.slot_of = piece_at(db, p_slot);
   fs.gated = fe->d_gated; fs.pts = fe->d_pts; fs.res = fe->d_res; fs.rec_b = (size_t)fe->max_points; fs.stats = fe->d_ptstats;
-  if (int rc = svs_seed_launch(ctx, &a, prm, &fs, any_generated, reinterpret_cast<svs_candidate_point *>(fe->d_seed + off_rec), cap_per_request,
-                               reinterpret_cast<int32_t *>(fe->d_seed + off_cnt)))
-    return rc;
-  if (sink)
-    if (int rc = sink->enqueue(reinterpret_cast<const svs_candidate_point *>(fe->d_seed + off_rec), reinterpret_cast<const int32_t *>(fe->d_seed + off_cnt), cap_per_request))
-      return rc;
-  SVS_HIP(ctx, hipMemcpyAsync(fe->h_seed, fe->d_seed + off_cnt, one_copy ? out_bytes : off_rec - off_cnt, hipMemcpyDeviceToHost, ctx->stream));
+  if (int rc = svs_seed_launch(ctx, &a, prm, &fs, any_generated, piece_at(db, p_rec), cap_per_request, piece_at(db, p_cnt))) return rc;
+  if (sink) if (int rc = sink->enqueue(piece_at(db, p_rec), piece_at(db, p_cnt), cap_per_request)) return rc;
+  SVS_HIP(ctx, hipMemcpyAsync(piece_at(hb, h_cnt), piece_at(db, p_cnt), one_copy ? out_bytes : h_rec.off, hipMemcpyDeviceToHost, ctx->stream));
   SVS_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  __builtin_memcpy(h_n_new, fe->h_seed, sizeof(int32_t) * 3 * (size_t)n);
+  __builtin_memcpy(h_n_new, piece_at(hb, h_cnt), h_cnt.bytes());
   int longest = 0;
   for (int r = 0; r < n; ++r) longest = std::max(longest, h_n_new[3 * r] + h_n_new[3 * r + 1] + h_n_new[3 * r + 2]);
   SVS_REQUIRE(ctx, longest <= cap_per_request);
   if (one_copy) {
-    const svs_candidate_point *rec = reinterpret_cast<const svs_candidate_point *>(fe->h_seed + (off_rec - off_cnt));
+    const svs_candidate_point *rec = piece_at(hb, h_rec);
     for (int r = 0; r < n; ++r) {
       const int m = h_n_new[3 * r] + h_n_new[3 * r + 1] + h_n_new[3 * r + 2];
       if (m > 0) __builtin_memcpy(h_out + (size_t)r * cap_per_request, rec + (size_t)r * cap_per_request, sizeof(svs_candidate_point) * (size_t)m);
     }
   } else if (h_out && longest > 0) {      // (behind a request's own count the caller's rows receive what the device block held there: unspecified)
     const size_t pitch = sizeof(svs_candidate_point) * (size_t)cap_per_request;
-    SVS_HIP(ctx, hipMemcpy2DAsync(h_out, pitch, fe->d_seed + off_rec, pitch, sizeof(svs_candidate_point) * (size_t)longest, (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+    SVS_HIP(ctx, hipMemcpy2DAsync(h_out, pitch, piece_at(db, p_rec), pitch, sizeof(svs_candidate_point) * (size_t)longest, (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
     SVS_HIP(ctx, hipStreamSynchronize(ctx->stream));
   }
   return SVS_OK;
@@ -1336,19 +1345,17 @@ extern "C" int svs_frontend_set_vertex_table(svs_frontend *fe, int n_requests, c
   if (R == 0) return SVS_OK;
   SVS_DEVICE(ctx);
   if (int rc = fe_vt_reserve(fe)) return rc;
-  auto up16 = [](size_t v) { return (v + 15) & ~(size_t)15; };
-  const size_t off_tab = up16(sizeof(kfd_up) * (size_t)R), off_vtx = up16(off_tab + sizeof(svs_kf_table) * (size_t)R);
-  const size_t off_slot = up16(off_vtx + sizeof(svs_kf_vertex) * SVS_KF_MAX_VERTICES * (size_t)R), off_ids = up16(off_slot + sizeof(int32_t) * (size_t)S * R);
-  const size_t bytes = off_ids + sizeof(int32_t) * total_ids;
-  if (fe->h_vt.bytes() < bytes) {      // (the last call's upload has been waited for: it ends with a synchronisation)
-    SVS_HIP(ctx, fe->h_vt.alloc_bytes(bytes * 2));
-    SVS_HIP(ctx, fe->d_vt_up.alloc_bytes(bytes * 2));
-  }
-  __builtin_memset(fe->h_vt, 0, off_ids);
-  kfd_up *hu = reinterpret_cast<kfd_up *>(fe->h_vt.get());
-  svs_kf_table *ht = reinterpret_cast<svs_kf_table *>(fe->h_vt + off_tab);
-  svs_kf_vertex *hv = reinterpret_cast<svs_kf_vertex *>(fe->h_vt + off_vtx);
-  int32_t *hs = reinterpret_cast<int32_t *>(fe->h_vt + off_slot), *hi = reinterpret_cast<int32_t *>(fe->h_vt + off_ids);
+  Pieces<> row;
+  const size_t Rz = (size_t)R;
+  const auto p_up = row.piece<kfd_up>(Rz); const auto p_tab = row.piece<svs_kf_table>(Rz); const auto p_vtx = row.piece<svs_kf_vertex>(Rz * SVS_KF_MAX_VERTICES);
+  const auto p_slot = row.piece<int32_t>(Rz * S); const auto p_ids = row.piece<int32_t>(total_ids);
+  TwinBlock &blk = fe->vt_up;
+  if (int rc = blk.reserve(ctx, row.end)) return rc;      // (the last call's upload has been waited for: it ends with a synchronisation)
+  __builtin_memset(blk.h, 0, p_ids.off);
+  kfd_up *hu = blk.host(p_up);
+  svs_kf_table *ht = blk.host(p_tab);
+  svs_kf_vertex *hv = blk.host(p_vtx);
+  int32_t *hs = blk.host(p_slot), *hi = blk.host(p_ids);
   size_t ids_off = 0;
   for (int r = 0; r < R; ++r) {
     const svs_vertex_request &q = req[r];
@@ -1366,13 +1373,9 @@ extern "C" int svs_frontend_set_vertex_table(svs_frontend *fe, int n_requests, c
     ids_off += (size_t)q.n_set_ids;
   }
   SVS_REQUIRE(ctx, ids_off < ((size_t)1 << 31));
-  SVS_HIP(ctx, hipMemcpyAsync(fe->d_vt_up, fe->h_vt, bytes, hipMemcpyHostToDevice, ctx->stream));
+  if (int rc = blk.upload(ctx, 0, row.end)) return rc;
   KfdScatter sc{};
-  sc.up = reinterpret_cast<const kfd_up *>(fe->d_vt_up.get());
-  sc.tab = reinterpret_cast<const svs_kf_table *>(fe->d_vt_up + off_tab);
-  sc.vtx = reinterpret_cast<const svs_kf_vertex *>(fe->d_vt_up + off_vtx);
-  sc.slot = reinterpret_cast<const int32_t *>(fe->d_vt_up + off_slot);
-  sc.ids = reinterpret_cast<const int32_t *>(fe->d_vt_up + off_ids);
+  sc.up = blk.dev(p_up); sc.tab = blk.dev(p_tab); sc.vtx = blk.dev(p_vtx); sc.slot = blk.dev(p_slot); sc.ids = blk.dev(p_ids);
   sc.d_tab = fe->d_vt_tab; sc.d_vtx = fe->d_vt_vtx; sc.d_slot = fe->d_vt_slot; sc.d_ids = fe->d_vt_ids; sc.S = S; sc.set_cap = (int)set_cap;
   if (int rc = svs_keyframe_scatter_tables(ctx, R, sc)) return rc;
   SVS_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -1505,53 +1508,39 @@ static int fe_set_neighborhood(svs_frontend *fe, svs_map *map, int n_requests, c
         bool have_act = false;
         for (int g = 0; g < fe->np_ng[q.stream]; ++g) have_act = have_act || fe->np_key[(size_t)q.stream * MAX_GROUPS + g] == q.act_id;
         if (fe->np_ng[q.stream] + (have_act ? 0 : 1) + 1 > MAX_GROUPS) { ctx->err = "svs_frontend_set_neighborhood_from_store: more than 64 groups"; return SVS_ERR_CAPACITY; }
-        const uint8_t *kept = fe->kept.data() + (size_t)q.stream * K;
-        sorted.clear();
-        for (int s = 0; s < K; ++s)
-          if (q.h_slot_kf[s] >= 0) { SVS_REQUIRE(ctx, kept[s]); sorted.push_back(q.h_slot_kf[s]); }
-        std::sort(sorted.begin(), sorted.end());
-        SVS_REQUIRE(ctx, std::adjacent_find(sorted.begin(), sorted.end()) == sorted.end());
+        if (int rc = fe_check_slot_table(fe, q.stream, q.h_slot_kf, sorted)) return rc;
         continue;
       }
       SVS_REQUIRE(ctx, q.h_slot_kf && q.n_head >= 0 && q.n_head <= MP && (q.n_head == 0 || q.h_head) && q.n_head_groups >= 1 && q.h_head_group_end);
       if (q.n_head_groups + 1 > MAX_GROUPS) { ctx->err = "svs_frontend_set_neighborhood_from_root: more than 64 groups"; return SVS_ERR_CAPACITY; }
       SVS_REQUIRE(ctx, q.n_fixed_groups >= 1 && q.n_fixed_groups <= q.n_head_groups && (q.n_fixed_groups == q.n_head_groups || q.h_head_group_kf));
-      const uint8_t *kept = fe->kept.data() + (size_t)q.stream * K;
-      sorted.clear();
-      for (int s = 0; s < K; ++s)
-        if (q.h_slot_kf[s] >= 0) { SVS_REQUIRE(ctx, kept[s]); sorted.push_back(q.h_slot_kf[s]); }
-      std::sort(sorted.begin(), sorted.end());
-      SVS_REQUIRE(ctx, std::adjacent_find(sorted.begin(), sorted.end()) == sorted.end());
-      SVS_REQUIRE(ctx, q.h_head_group_end[q.n_head_groups - 1] == q.n_head);
-      for (int g = 0; g < q.n_head_groups; ++g) SVS_REQUIRE(ctx, q.h_head_group_end[g] >= (g ? q.h_head_group_end[g - 1] : 0));
-      for (int i = 0; i < q.n_head; ++i) SVS_REQUIRE(ctx, q.h_head[i].kf_index < 0 || (q.h_head[i].kf_index < K && kept[q.h_head[i].kf_index]));
+      if (int rc = fe_check_slot_table(fe, q.stream, q.h_slot_kf, sorted)) return rc;
+      if (int rc = fe_check_group_ends(ctx, q.h_head_group_end, q.n_head_groups, q.n_head)) return rc;
+      if (int rc = fe_check_anchors(fe, q.stream, q.h_head, q.n_head)) return rc;
       sorted.clear();
       for (int g = q.n_fixed_groups; g < q.n_head_groups; ++g) { SVS_REQUIRE(ctx, svs_map_has_keyframe(map, q.h_head_group_kf[g])); sorted.push_back(q.h_head_group_kf[g]); }
-      std::sort(sorted.begin(), sorted.end());
-      SVS_REQUIRE(ctx, std::adjacent_find(sorted.begin(), sorted.end()) == sorted.end());
+      SVS_REQUIRE(ctx, all_distinct(sorted));
       n_head += (size_t)q.n_head;
     }
   }
   if (R == 0) return SVS_OK;
   SVS_DEVICE(ctx);
   if (int rc = fe_vt_reserve(fe)) return rc;
-  auto al = [](size_t v) { return (v + 15) & ~(size_t)15; };
-  const size_t Rz = (size_t)R, n_ids = Rz * 2 * K;
-  const size_t o_ids = al(Rz * sizeof(nbr_req)), o_head = o_ids + al(n_ids * sizeof(int32_t)), in_bytes = o_head + n_head * sizeof(svs_candidate_point);
-  const size_t o_res = al(in_bytes), o_slot = o_res + Rz * sizeof(svs_nbr_result), o_vT = o_slot + Rz * K * 12 * sizeof(double), o_vid = o_vT + Rz * VB * 12 * sizeof(double),
-               o_act = o_vid + al(Rz * VB * sizeof(int32_t)), o_str = o_act + al(Rz * VB * sizeof(int32_t)), o_pid = o_str + al(Rz * VB * VB * sizeof(int32_t)),
-               down_end = o_pid + al(Rz * MP * sizeof(int32_t));
-  const size_t o_hdr = down_end, o_mid = o_hdr + Rz * VB * sizeof(int4), o_list = o_mid + Rz * sizeof(nbr_mid), o_mpid = o_list + al(Rz * VB * sizeof(int2)),
-               o_wv = o_mpid + al(Rz * MP * sizeof(int32_t)), o_woff = o_wv + al(Rz * VB * sizeof(int32_t)), bytes = o_woff + al((Rz + 1) * sizeof(int32_t));
-  if (fe->h_nbh.bytes() < bytes) {      // (no call is in flight: this one is blocking)
-    SVS_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    SVS_HIP(ctx, fe->h_nbh.alloc(bytes * 2));
-    SVS_HIP(ctx, fe->d_nbh.alloc(bytes * 2));
-  }
-  uint8_t *hs = fe->h_nbh, *ds = fe->d_nbh;
-  nbr_req *hq = reinterpret_cast<nbr_req *>(hs);
-  int32_t *ids = reinterpret_cast<int32_t *>(hs + o_ids);
-  svs_candidate_point *head = reinterpret_cast<svs_candidate_point *>(hs + o_head);
+  // the block: what goes up (requests | slot ids | heads), what comes back with the optional outputs last, and behind it the walk's work space, never copied
+  Pieces<> row;
+  const size_t Rz = (size_t)R;
+  const auto p_req = row.piece<nbr_req>(Rz); const auto p_ids = row.piece<int32_t>(Rz * 2 * K); const auto p_head = row.piece<svs_candidate_point>(n_head);
+  const size_t in_end = row.end;
+  const auto p_res = row.piece<svs_nbr_result>(Rz); const auto p_slot = row.piece<double>(Rz * K * 12); const auto p_vT = row.piece<double>(Rz * VB * 12);
+  const auto p_vid = row.piece<int32_t>(Rz * VB); const auto p_act = row.piece<int32_t>(Rz * VB); const auto p_str = row.piece<int32_t>(Rz * VB * VB);
+  const auto p_pid = row.piece<int32_t>(Rz * MP);
+  const auto p_hdr = row.piece<int4>(Rz * VB); const auto p_mid = row.piece<nbr_mid>(Rz); const auto p_list = row.piece<int2>(Rz * VB);
+  const auto p_mpid = row.piece<int32_t>(Rz * MP); const auto p_wv = row.piece<int32_t>(Rz * VB); const auto p_woff = row.piece<int32_t>(Rz + 1);
+  TwinBlock &blk = fe->nbh;
+  if (int rc = blk.reserve(ctx, row.end)) return rc;      // (no call is in flight: this one is blocking)
+  nbr_req *hq = blk.host(p_req);
+  int32_t *ids = blk.host(p_ids);
+  svs_candidate_point *head = blk.host(p_head);
   size_t at_head = 0;
   for (int r = 0; r < R; ++r) {
     const svs_nbr_request &q = req[r];
@@ -1574,22 +1563,21 @@ static int fe_set_neighborhood(svs_frontend *fe, svs_map *map, int n_requests, c
     at_head += (size_t)q.n_head;
     for (int g = 0; g < q.n_head_groups; ++g) { s.group_end[g] = q.h_head_group_end[g]; s.group_kf[g] = g >= q.n_fixed_groups ? q.h_head_group_kf[g] : -1; }
   }
-  SVS_HIP(ctx, hipMemcpyAsync(ds, hs, in_bytes, hipMemcpyHostToDevice, ctx->stream));
+  if (int rc = blk.upload(ctx, 0, in_end)) return rc;
   MapNbrDst D{};
-  D.req = reinterpret_cast<const nbr_req *>(ds); D.ids = reinterpret_cast<const int32_t *>(ds + o_ids); D.head = reinterpret_cast<const svs_candidate_point *>(ds + o_head);
+  D.req = blk.dev(p_req); D.ids = blk.dev(p_ids); D.head = blk.dev(p_head);
   if (from_store) { D.head = fe->d_np_rec; D.head_stride = fe->np_rcap; D.from_store = 1; }
   D.R = R; D.VB = VB;
   D.pts = fe->d_pts; D.max_points = MP; D.group_end = fe->d_group_end; D.n_groups = fe->d_n_groups; D.n_new = fe->d_n_new; D.kfs = fe->d_kfs; D.max_keyframes = K;
   D.vt_tab = fe->d_vt_tab; D.vt_vtx = fe->d_vt_vtx; D.vt_slot = fe->d_vt_slot;
   D.refresh = refresh_poses ? 1 : 0;
-  D.res = reinterpret_cast<svs_nbr_result *>(ds + o_res); D.slot_T = reinterpret_cast<double *>(ds + o_slot);
-  D.vertex_T = reinterpret_cast<double *>(ds + o_vT); D.vertex_id = reinterpret_cast<int32_t *>(ds + o_vid);
-  D.act_nb = reinterpret_cast<int32_t *>(ds + o_act); D.strength = reinterpret_cast<int32_t *>(ds + o_str); D.point_id = reinterpret_cast<int32_t *>(ds + o_pid);
-  D.walk_hdr = reinterpret_cast<int4 *>(ds + o_hdr); D.mid = reinterpret_cast<nbr_mid *>(ds + o_mid); D.walk_list = reinterpret_cast<int2 *>(ds + o_list);
-  D.map_pid = reinterpret_cast<int32_t *>(ds + o_mpid); D.walk_v = reinterpret_cast<int32_t *>(ds + o_wv); D.walk_off = reinterpret_cast<int32_t *>(ds + o_woff);
+  D.res = blk.dev(p_res); D.slot_T = blk.dev(p_slot); D.vertex_T = blk.dev(p_vT); D.vertex_id = blk.dev(p_vid); D.act_nb = blk.dev(p_act); D.strength = blk.dev(p_str);
+  D.point_id = blk.dev(p_pid);
+  D.walk_hdr = blk.dev(p_hdr); D.mid = blk.dev(p_mid); D.walk_list = blk.dev(p_list); D.map_pid = blk.dev(p_mpid); D.walk_v = blk.dev(p_wv); D.walk_off = blk.dev(p_woff);
   if (int rc = svs_map_build_root_neighborhoods(map, D)) return rc;
-  const size_t down_to = h_point_id ? down_end : h_strength ? o_pid : h_act_neighbors ? o_str : h_vertex_id ? o_act : h_vertex_T ? o_vid : o_vT;
-  SVS_HIP(ctx, hipMemcpyAsync(hs + o_res, ds + o_res, down_to - o_res, hipMemcpyDeviceToHost, ctx->stream));
+  // from the first output piece to the end of the last one a caller asked for
+  const size_t down_to = h_point_id ? p_pid.end() : h_strength ? p_str.end() : h_act_neighbors ? p_act.end() : h_vertex_id ? p_vid.end() : h_vertex_T ? p_vT.end() : p_slot.end();
+  if (int rc = blk.download(ctx, p_res.off, down_to)) return rc;
   if (h_records) SVS_HIP(ctx, hipMemcpyAsync(h_records, fe->d_pts, sizeof(svs_candidate_point) * (size_t)MP * B, hipMemcpyDeviceToHost, ctx->stream));
   for (int r = 0; r < R && (h_table || h_vertex); ++r) {
     const size_t b = (size_t)req[r].stream;
@@ -1600,44 +1588,26 @@ static int fe_set_neighborhood(svs_frontend *fe, svs_map *map, int n_requests, c
   }
   SVS_HIP(ctx, hipStreamSynchronize(ctx->stream));
   // ---- the host state follows the download
-  const svs_nbr_result *res = reinterpret_cast<const svs_nbr_result *>(hs + o_res);
+  const svs_nbr_result *res = blk.host(p_res);
   bool any = false;
   for (int r = 0; r < R; ++r) {
     const svs_nbr_request &q = req[r];
     const bool none = res[r].over_capacity != 0 || res[r].root_outside_window != 0;
     if (h_res) h_res[r] = res[r];
-    auto row = [&](int32_t *dst, size_t off, size_t n) {
-      if (!dst) return;
-      if (none) std::fill(dst + (size_t)r * n, dst + (size_t)(r + 1) * n, -1);
-      else memcpy(dst + (size_t)r * n, hs + off + (size_t)r * n * sizeof(int32_t), n * sizeof(int32_t));
-    };
-    row(h_point_id, o_pid, (size_t)MP);
-    row(h_vertex_id, o_vid, (size_t)VB);
-    row(h_act_neighbors, o_act, (size_t)VB);
-    row(h_strength, o_str, (size_t)VB * VB);
-    if (h_vertex_T) {
-      if (none) memset(h_vertex_T + (size_t)r * VB * 12, 0, (size_t)VB * 12 * sizeof(double));
-      else memcpy(h_vertex_T + (size_t)r * VB * 12, hs + o_vT + (size_t)r * VB * 12 * sizeof(double), (size_t)VB * 12 * sizeof(double));
-    }
-    if (h_slot_T) {
-      if (none) memset(h_slot_T + (size_t)r * K * 12, 0, (size_t)K * 12 * sizeof(double));
-      else memcpy(h_slot_T + (size_t)r * K * 12, hs + o_slot + (size_t)r * K * 12 * sizeof(double), (size_t)K * 12 * sizeof(double));
-    }
+    fe_row_out(h_point_id, blk.host(p_pid), r, (size_t)MP, none);
+    fe_row_out(h_vertex_id, blk.host(p_vid), r, (size_t)VB, none);
+    fe_row_out(h_act_neighbors, blk.host(p_act), r, (size_t)VB, none);
+    fe_row_out(h_strength, blk.host(p_str), r, (size_t)VB * VB, none);
+    fe_row_out(h_vertex_T, blk.host(p_vT), r, (size_t)VB * 12, none);
+    fe_row_out(h_slot_T, blk.host(p_slot), r, (size_t)K * 12, none);
     if (none) continue;
     any = true;
     fe->n_points[q.stream] = res[r].n_points; fe->n_new_records[q.stream] = res[r].n_head_kept;
     fe->max_groups_used = std::max(fe->max_groups_used, (int)res[r].n_groups);
     fe->vt_set[q.stream] = 1;
-    if (refresh_poses) {
-      const double *sT = reinterpret_cast<const double *>(hs + o_slot) + (size_t)r * K * 12;
-      for (int k = 0; k < K; ++k)
-        if (svs_map_has_keyframe(map, q.h_slot_kf[k])) memcpy(fe->h_kfs[(size_t)q.stream * K + k].T_anchor_from_w, sT + (size_t)k * 12, 12 * sizeof(double));
-    }
+    if (refresh_poses) fe_refresh_poses(fe, map, q.stream, q.h_slot_kf, blk.host(p_slot) + (size_t)r * K * 12);
   }
-  if (any) {
-    fe->n_launch = *std::max_element(fe->n_points.begin(), fe->n_points.end());
-    fe->n_gated = -1;      // the last step's gate records no longer belong to the list on the device
-  }
+  if (any) fe_lists_changed(fe);
   return SVS_OK;
 }
 

@@ -46,16 +46,7 @@ struct NpEdit {
 
 int np_capacity(svs_ctx *ctx, const char *what) { ctx->err = what; return SVS_ERR_CAPACITY; }
 
-int np_grow(svs_frontend *fe, size_t bytes) {      // (every call of this block ends synchronised: the staging block is free)
-  svs_ctx *ctx = fe->ctx;
-  if (fe->h_np.bytes() >= bytes) return SVS_OK;
-  SVS_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  SVS_HIP(ctx, fe->h_np.alloc_bytes(bytes * 2));
-  SVS_HIP(ctx, fe->d_np.alloc_bytes(bytes * 2));
-  return SVS_OK;
-}
-inline size_t up16(size_t v) { return (v + 15) & ~(size_t)15; }
-
+// (every call of the staging block fe->np ends synchronised: its pinned side is free when the next one reserves it)
 // ops | segments | the `n_staged` records of staged_parts, back to back, into the pinned block, uploaded, and the compose launch behind it
 int np_apply(svs_frontend *fe, const NpEdit &e, size_t n_staged, const std::vector<std::pair<const svs_candidate_point *, int>> &staged_parts,
              const svs_candidate_point *d_seed_out, const int32_t *d_seed_cnt, int seed_cap) {
@@ -64,11 +55,13 @@ int np_apply(svs_frontend *fe, const NpEdit &e, size_t n_staged, const std::vect
   if (n_ops == 0) return SVS_OK;
   size_t n_seg = 0;
   for (const auto &g : e.groups) for (const NpGroup &x : g) n_seg += x.segs.size();
-  const size_t o_seg = up16(sizeof(np_op) * n_ops), o_rec = up16(o_seg + sizeof(np_seg) * n_seg), bytes = o_rec + sizeof(svs_candidate_point) * n_staged;
-  if (int rc = np_grow(fe, bytes)) return rc;
-  np_op *ops = reinterpret_cast<np_op *>(fe->h_np.get());
-  np_seg *segs = reinterpret_cast<np_seg *>(fe->h_np + o_seg);
-  svs_candidate_point *rec = reinterpret_cast<svs_candidate_point *>(fe->h_np + o_rec);
+  Pieces<> row;
+  const auto p_ops = row.piece<np_op>(n_ops); const auto p_seg = row.piece<np_seg>(n_seg); const auto p_rec = row.piece<svs_candidate_point>(n_staged);
+  TwinBlock &blk = fe->np;
+  if (int rc = blk.reserve(ctx, row.end)) return rc;
+  np_op *ops = blk.host(p_ops);
+  np_seg *segs = blk.host(p_seg);
+  svs_candidate_point *rec = blk.host(p_rec);
   size_t at = 0;
   for (size_t i = 0; i < n_ops; ++i) {
     np_op &o = ops[i];
@@ -85,10 +78,9 @@ int np_apply(svs_frontend *fe, const NpEdit &e, size_t n_staged, const std::vect
     if (p.second) memcpy(rec + r, p.first, sizeof(svs_candidate_point) * (size_t)p.second);
     r += (size_t)p.second;
   }
-  SVS_HIP(ctx, hipMemcpyAsync(fe->d_np, fe->h_np, bytes, hipMemcpyHostToDevice, ctx->stream));
+  if (int rc = blk.upload(ctx, 0, row.end)) return rc;
   NpCompose c{};
-  c.ops = reinterpret_cast<const np_op *>(fe->d_np.get()); c.segs = reinterpret_cast<const np_seg *>(fe->d_np + o_seg);
-  c.staged = reinterpret_cast<const svs_candidate_point *>(fe->d_np + o_rec);
+  c.ops = blk.dev(p_ops); c.segs = blk.dev(p_seg); c.staged = blk.dev(p_rec);
   c.seed_out = d_seed_out; c.seed_cnt = d_seed_cnt; c.seed_cap = seed_cap;
   c.rec = fe->d_np_rec; c.tmp = fe->d_np_tmp; c.key = fe->d_np_key; c.cnt = fe->d_np_cnt; c.ng = fe->d_np_ng; c.record_cap = fe->np_rcap;
   return svs_newpoints_compose(ctx, (int)n_ops, c);
@@ -229,21 +221,24 @@ extern "C" int svs_frontend_newpoints_prune(svs_frontend *fe, int n_streams, con
   if (n_streams == 0) return SVS_OK;
   SVS_DEVICE(ctx);
   const size_t B = (size_t)fe->B, mp = (size_t)fe->max_points;
-  const size_t o_rem = up16(sizeof(int32_t) * (size_t)n_streams), o_cnt = o_rem + up16(sizeof(int32_t) * (size_t)n_streams), bytes = o_cnt + sizeof(int32_t) * B * NPG;
-  if (int rc = np_grow(fe, bytes)) return rc;
-  memcpy(fe->h_np, h_streams, sizeof(int32_t) * (size_t)n_streams);
-  SVS_HIP(ctx, hipMemcpyAsync(fe->d_np, fe->h_np, sizeof(int32_t) * (size_t)n_streams, hipMemcpyHostToDevice, ctx->stream));
+  // the streams go up; the removed counts and the whole count table come home into the pinned side from the arrays the kernel writes
+  Pieces<> row;
+  const auto p_str = row.piece<int32_t>((size_t)n_streams); const auto p_rem = row.piece<int32_t>((size_t)n_streams); const auto p_cnt = row.piece<int32_t>(B * NPG);
+  TwinBlock &blk = fe->np;
+  if (int rc = blk.reserve(ctx, row.end)) return rc;
+  memcpy(blk.host(p_str), h_streams, p_str.bytes());
+  if (int rc = blk.upload(ctx, 0, p_str.end())) return rc;
   svs_newpoints_prune_args a{};
   a.d_res = fe->d_res; a.res_bstride = mp; a.d_pts = fe->d_pts; a.pts_bstride = mp; a.d_gated = fe->d_gated; a.gated_bstride = mp;
   a.d_n_new = fe->d_n_new; a.n = fe->n_gated; a.batch = n_streams;
   a.d_store = fe->d_np_rec; a.store_bstride = (size_t)fe->np_rcap; a.d_group_count = fe->d_np_cnt; a.group_bstride = NPG; a.d_n_groups = fe->d_np_ng;
-  a.d_stream = reinterpret_cast<const int32_t *>(fe->d_np.get());
+  a.d_stream = blk.dev(p_str);
   if (int rc = svs_newpoints_prune(ctx, &a, fe->d_np_removed)) return rc;
-  SVS_HIP(ctx, hipMemcpyAsync(fe->h_np + o_rem, fe->d_np_removed, sizeof(int32_t) * (size_t)n_streams, hipMemcpyDeviceToHost, ctx->stream));
-  SVS_HIP(ctx, hipMemcpyAsync(fe->h_np + o_cnt, fe->d_np_cnt, sizeof(int32_t) * B * NPG, hipMemcpyDeviceToHost, ctx->stream));
+  SVS_HIP(ctx, hipMemcpyAsync(blk.host(p_rem), fe->d_np_removed, p_rem.bytes(), hipMemcpyDeviceToHost, ctx->stream));
+  SVS_HIP(ctx, hipMemcpyAsync(blk.host(p_cnt), fe->d_np_cnt, p_cnt.bytes(), hipMemcpyDeviceToHost, ctx->stream));
   SVS_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  const int32_t *cnt = reinterpret_cast<const int32_t *>(fe->h_np + o_cnt);
-  memcpy(h_n_removed, fe->h_np + o_rem, sizeof(int32_t) * (size_t)n_streams);
+  const int32_t *cnt = blk.host(p_cnt);
+  memcpy(h_n_removed, blk.host(p_rem), p_rem.bytes());
   for (int i = 0; i < n_streams; ++i) {
     const size_t s = (size_t)h_streams[i];
     memcpy(&fe->np_cnt[s * NPG], cnt + s * NPG, sizeof(int32_t) * NPG);
@@ -259,18 +254,20 @@ extern "C" int svs_frontend_newpoints_get(svs_frontend *fe, int n_streams, const
   for (int i = 0; i < n_streams; ++i) SVS_REQUIRE(ctx, h_streams[i] >= 0 && h_streams[i] < fe->B);
   if (n_streams == 0) return SVS_OK;
   SVS_DEVICE(ctx);
-  const size_t B = (size_t)fe->B, o_cnt = sizeof(int32_t) * B * NPG, o_ng = 2 * o_cnt, bytes = o_ng + sizeof(int32_t) * B;
-  if (int rc = np_grow(fe, bytes)) return rc;
-  SVS_HIP(ctx, hipMemcpyAsync(fe->h_np, fe->d_np_key, o_cnt, hipMemcpyDeviceToHost, ctx->stream));
-  SVS_HIP(ctx, hipMemcpyAsync(fe->h_np + o_cnt, fe->d_np_cnt, o_cnt, hipMemcpyDeviceToHost, ctx->stream));
-  SVS_HIP(ctx, hipMemcpyAsync(fe->h_np + o_ng, fe->d_np_ng, sizeof(int32_t) * B, hipMemcpyDeviceToHost, ctx->stream));
+  const size_t B = (size_t)fe->B;
+  Pieces<> row;      // the three tables, into the pinned side
+  const auto p_key = row.piece<int32_t>(B * NPG); const auto p_cnt = row.piece<int32_t>(B * NPG); const auto p_ng = row.piece<int32_t>(B);
+  TwinBlock &blk = fe->np;
+  if (int rc = blk.reserve(ctx, row.end)) return rc;
+  SVS_HIP(ctx, hipMemcpyAsync(blk.host(p_key), fe->d_np_key, p_key.bytes(), hipMemcpyDeviceToHost, ctx->stream));
+  SVS_HIP(ctx, hipMemcpyAsync(blk.host(p_cnt), fe->d_np_cnt, p_cnt.bytes(), hipMemcpyDeviceToHost, ctx->stream));
+  SVS_HIP(ctx, hipMemcpyAsync(blk.host(p_ng), fe->d_np_ng, p_ng.bytes(), hipMemcpyDeviceToHost, ctx->stream));
   if (h_records)
     for (int i = 0; i < n_streams; ++i)
       SVS_HIP(ctx, hipMemcpyAsync(h_records + (size_t)i * fe->np_rcap, fe->d_np_rec + (size_t)h_streams[i] * fe->np_rcap, sizeof(svs_candidate_point) * (size_t)fe->np_rcap,
                                   hipMemcpyDeviceToHost, ctx->stream));
   SVS_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  const int32_t *key = reinterpret_cast<const int32_t *>(fe->h_np.get()), *cnt = reinterpret_cast<const int32_t *>(fe->h_np + o_cnt),
-                *ng = reinterpret_cast<const int32_t *>(fe->h_np + o_ng);
+  const int32_t *key = blk.host(p_key), *cnt = blk.host(p_cnt), *ng = blk.host(p_ng);
   for (int i = 0; i < n_streams; ++i) {
     const size_t s = (size_t)h_streams[i];
     if (h_n_groups) h_n_groups[i] = ng[s];
@@ -299,15 +296,9 @@ extern "C" int svs_frontend_set_candidates_from_newpoints(svs_frontend *fe, int 
       SVS_REQUIRE(ctx, q.n_keys >= 1 && q.h_keys && q.h_slot_kf && q.n_tail >= 0 && q.n_tail <= MP && (q.n_tail == 0 || q.h_tail));
       if (q.n_keys > NPG - 1) return np_capacity(ctx, "svs_frontend_set_candidates_from_newpoints: more than 63 keys");
       sorted.assign(q.h_keys, q.h_keys + q.n_keys);
-      std::sort(sorted.begin(), sorted.end());
-      SVS_REQUIRE(ctx, sorted[0] >= 0 && std::adjacent_find(sorted.begin(), sorted.end()) == sorted.end());
-      const uint8_t *kept = fe->kept.data() + (size_t)q.stream * K;
-      sorted.clear();
-      for (int s = 0; s < K; ++s)
-        if (q.h_slot_kf[s] >= 0) { SVS_REQUIRE(ctx, kept[s]); sorted.push_back(q.h_slot_kf[s]); }
-      std::sort(sorted.begin(), sorted.end());
-      SVS_REQUIRE(ctx, std::adjacent_find(sorted.begin(), sorted.end()) == sorted.end());
-      for (int i = 0; i < q.n_tail; ++i) SVS_REQUIRE(ctx, q.h_tail[i].kf_index < 0 || (q.h_tail[i].kf_index < K && kept[q.h_tail[i].kf_index]));
+      SVS_REQUIRE(ctx, all_distinct(sorted) && sorted[0] >= 0);
+      if (int rc = fe_check_slot_table(fe, q.stream, q.h_slot_kf, sorted)) return rc;
+      if (int rc = fe_check_anchors(fe, q.stream, q.h_tail, q.n_tail)) return rc;
       // the groups named, where they lie in the stream's row
       np_list_req s;
       memset(&s, 0, sizeof s);
@@ -339,17 +330,19 @@ extern "C" int svs_frontend_set_candidates_from_newpoints(svs_frontend *fe, int 
   if (R == 0) return SVS_OK;
   SVS_DEVICE(ctx);
   if (!staged.empty()) {
-    const size_t o_tail = up16(sizeof(np_list_req) * staged.size()), bytes = o_tail + sizeof(svs_candidate_point) * n_tail;
-    if (int rc = np_grow(fe, bytes)) return rc;
-    memcpy(fe->h_np, staged.data(), sizeof(np_list_req) * staged.size());
-    svs_candidate_point *tail = reinterpret_cast<svs_candidate_point *>(fe->h_np + o_tail);
+    Pieces<> row;
+    const auto p_req = row.piece<np_list_req>(staged.size()); const auto p_tail = row.piece<svs_candidate_point>(n_tail);
+    TwinBlock &blk = fe->np;
+    if (int rc = blk.reserve(ctx, row.end)) return rc;
+    memcpy(blk.host(p_req), staged.data(), p_req.bytes());
+    svs_candidate_point *tail = blk.host(p_tail);
     for (size_t i = 0; i < staged.size(); ++i) {
       const svs_newpoints_list_request &q = req[staged_r[i]];
       if (q.n_tail) memcpy(tail + staged[i].seg[q.n_keys].off, q.h_tail, sizeof(svs_candidate_point) * (size_t)q.n_tail);
     }
-    SVS_HIP(ctx, hipMemcpyAsync(fe->d_np, fe->h_np, bytes, hipMemcpyHostToDevice, ctx->stream));
+    if (int rc = blk.upload(ctx, 0, row.end)) return rc;
     NpList L{};
-    L.req = reinterpret_cast<const np_list_req *>(fe->d_np.get()); L.staged = reinterpret_cast<const svs_candidate_point *>(fe->d_np + o_tail);
+    L.req = blk.dev(p_req); L.staged = blk.dev(p_tail);
     L.rec = fe->d_np_rec; L.record_cap = fe->np_rcap;
     L.pts = fe->d_pts; L.max_points = MP; L.group_end = fe->d_group_end; L.n_groups = fe->d_n_groups; L.n_new = fe->d_n_new;
     if (int rc = svs_newpoints_list(ctx, (int)staged.size(), L)) return rc;
@@ -362,9 +355,6 @@ extern "C" int svs_frontend_set_candidates_from_newpoints(svs_frontend *fe, int 
     fe->n_points[s] = res[r].n_points; fe->n_new_records[s] = res[r].n_head;
     fe->max_groups_used = std::max(fe->max_groups_used, res[r].n_groups);
   }
-  if (!staged.empty()) {
-    fe->n_launch = *std::max_element(fe->n_points.begin(), fe->n_points.end());
-    fe->n_gated = -1;      // the last step's gate records no longer belong to the list on the device
-  }
+  if (!staged.empty()) fe_lists_changed(fe);
   return SVS_OK;
 }

@@ -26,6 +26,7 @@
 #include "kf_map.h"
 #include "addkf_map.h"
 #include "pose.h"
+#include "staging.h"
 #include <string.h>
 #include <algorithm>
 #include <unordered_map>
@@ -80,8 +81,8 @@ struct svs_map {
   DevBuf<int2> d_log;
   DevBuf<int32_t> d_kf_begin, d_kf_rows, d_pt_begin, d_pt_rows, d_kf_cur, d_pt_cur;
   DevBuf<uint32_t> d_mark; size_t mark_b = 0; int mark_rows = 0;
-  // staging of the updates: one pinned block and its device twin, reused once the upload out of the pinned block has happened
-  PinnedBuf<uint8_t> h_up; DevBuf<uint8_t> d_up; owned::Event up_ev; bool up_pending = false;
+  // staging of the updates: a twin block, its pinned side reused once the upload out of it has happened
+  TwinBlock up; owned::Event up_ev; bool up_pending = false;
   // the measured store (one svs_ba_edge per pair that came with a measurement, log order; allocated with the first of them) and the prepared window
   DevBuf<svs_ba_edge> d_meas; int n_meas = 0, n_unmeasured = 0;
   DevBuf<uint8_t> d_win; PinnedBuf<uint8_t> h_win;           // head (result | window ids | types) | extension bitmap | active ids | anchor ids | poses | psi
@@ -94,7 +95,7 @@ struct svs_map {
   // computeConstraint: the feature_table lengths (what a request's scratch row is sized by), the scratch rows, and the block the blocking calls download
   std::vector<int32_t> kf_nobs;
   DevBuf<double> d_depth; DevBuf<int32_t> d_common;
-  DevBuf<uint8_t> d_dn; PinnedBuf<uint8_t> h_dn;
+  TwinBlock dn;
   // svs_map_add_keyframe_dev (map_addkf_dev.inc): the id sets as bitmaps on the device, the counts they were written at, the row over point ids its check kernel
   // leaves as it found it; all allocated with the first such call
   DevBuf<uint32_t> d_in_pt, d_in_kf; PinnedBuf<uint32_t> h_in; int in_n_kf = -1, in_n_pt = -1;
@@ -175,45 +176,30 @@ extern "C" int svs_map_info(svs_map *map, int32_t *n_keyframes, int32_t *n_point
 }
 
 // ---- staging: one upload and at most one download per call -----------------------------------------------------------------------------------------------------
-// Both blocks are rows of typed pieces that a call declares in order (`auto ids = up.piece<int32_t>(n);`).  Every piece begins at the next multiple of 16 bytes, so
-// the 16-byte device loads keep their alignment; `end` is one past the last piece.  A piece is an offset until the block is reserved -- reserving may move the
-// block -- and then host(p) / dev(p) are its two typed addresses: nothing else computes an offset, so the two sides cannot disagree.
-template <class T> struct MapPiece { size_t off, n; size_t bytes() const { return n * sizeof(T); } };
-struct MapPieces {
-  size_t end = 0;
-  template <class T> MapPiece<T> piece(size_t n) {
-    const size_t o = (end + 15) & ~(size_t)15;
-    end = o + n * sizeof(T);
-    return MapPiece<T>{o, n};
-  }
-  size_t end_aligned() const { return (end + 15) & ~(size_t)15; }
-};
+// Both blocks are twin blocks of the library's staging (staging.h: rows of typed 16-byte-aligned pieces that a call declares in order, host(p) / dev(p) the only
+// addresses), grown to max(2 x bytes, 64 KB).  The handles below add what is the map's own: when the pinned side is free, and the waits.
+template <class T> using MapPiece = Piece<T>;
+using MapPieces = Pieces<>;
+constexpr size_t MAP_STAGE_FLOOR = (size_t)1 << 16;
 
-// the upload: the pinned block h_up and its device twin d_up.  reserve() hands the pinned block over free to be written: the upload out of it that is still in
-// flight has happened, and it holds the pieces; upload() is the call's single hipMemcpyAsync on the map's stream, with the event the next reserve() waits for
+// the upload.  reserve() hands the pinned block over free to be written: the upload out of it that is still in flight has happened, and it holds the pieces;
+// upload() is the call's single hipMemcpyAsync on the map's stream, with the event the next reserve() waits for
 struct MapUp : MapPieces {
   svs_map *m;
   explicit MapUp(svs_map *map) : m(map) {}
   int reserve(size_t at_least = 0) {
     svs_ctx *ctx = m->ctx;
-    const size_t bytes = std::max(end, at_least);
     if (m->up_pending) { SVS_HIP(ctx, hipEventSynchronize(m->up_ev)); m->up_pending = false; }
-    if (m->h_up.bytes() < bytes) {
-      // the device twin may still be read by the scatter of the last update
-      SVS_HIP(ctx, hipStreamSynchronize(ctx->stream));
-      const size_t want = std::max(bytes * 2, (size_t)1 << 16);
-      SVS_HIP(ctx, m->h_up.alloc(want));
-      SVS_HIP(ctx, m->d_up.alloc(want));
-    }
-    return SVS_OK;
+    return m->up.reserve(ctx, std::max(end, at_least), MAP_STAGE_FLOOR);      // (draining: the device twin may still be read by the scatter of the last update)
   }
-  template <class T> T *host(const MapPiece<T> &p) const { return reinterpret_cast<T *>(m->h_up.get() + p.off); }
-  template <class T> const T *dev(const MapPiece<T> &p) const { return reinterpret_cast<const T *>(m->d_up.get() + p.off); }
+  template <class T> T *host(const MapPiece<T> &p) const { return m->up.host(p); }
+  template <class T> const T *dev(const MapPiece<T> &p) const { return m->up.dev(p); }
   template <class T> void put(const MapPiece<T> &p, const T *src) const { if (p.n) memcpy(host(p), src, p.bytes()); }
   // the bytes [from, to) of the block to the same place of the twin, or the whole block to d_dst
   int upload(size_t from, size_t to, void *d_dst = nullptr) {
     svs_ctx *ctx = m->ctx;
-    SVS_HIP(ctx, hipMemcpyAsync(d_dst ? d_dst : m->d_up.get() + from, m->h_up.get() + from, to - from, hipMemcpyHostToDevice, ctx->stream));
+    if (d_dst) SVS_HIP(ctx, hipMemcpyAsync(d_dst, m->up.h.get() + from, to - from, hipMemcpyHostToDevice, ctx->stream));
+    else if (int rc = m->up.upload(ctx, from, to)) return rc;
     SVS_HIP(ctx, hipEventRecord(m->up_ev, ctx->stream));
     m->up_pending = true;
     return SVS_OK;
@@ -221,27 +207,18 @@ struct MapUp : MapPieces {
   int upload(void *d_dst = nullptr) { return upload(0, end, d_dst); }
 };
 
-// the download of the blocking calls: d_dn and its pinned twin h_dn (a new block needs the stream drained of the kernels that write the old one).  The kernels
-// write dev(p); download() copies the block and waits for the stream; then host(p) holds the results
+// the download of the blocking calls (a new block needs the stream drained of the kernels that write the old one).  The kernels write dev(p); download() copies
+// the block and waits for the stream; then host(p) holds the results
 struct MapDn : MapPieces {
   svs_map *m;
   explicit MapDn(svs_map *map) : m(map) {}
-  int reserve(size_t at_least = 0) {
-    svs_ctx *ctx = m->ctx;
-    const size_t bytes = std::max(end, at_least);
-    if (m->d_dn.bytes() >= bytes) return SVS_OK;
-    SVS_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    const size_t want = std::max(bytes * 2, (size_t)1 << 16);
-    SVS_HIP(ctx, m->d_dn.alloc(want));
-    SVS_HIP(ctx, m->h_dn.alloc(want));
-    return SVS_OK;
-  }
-  template <class T> T *dev(const MapPiece<T> &p) const { return reinterpret_cast<T *>(m->d_dn.get() + p.off); }
-  template <class T> const T *host(const MapPiece<T> &p) const { return reinterpret_cast<const T *>(m->h_dn.get() + p.off); }
+  int reserve(size_t at_least = 0) { return m->dn.reserve(m->ctx, std::max(end, at_least), MAP_STAGE_FLOOR); }
+  template <class T> T *dev(const MapPiece<T> &p) const { return m->dn.dev(p); }
+  template <class T> const T *host(const MapPiece<T> &p) const { return m->dn.host(p); }
   template <class T> void get(const MapPiece<T> &p, T *dst) const { if (p.n) memcpy(dst, host(p), p.bytes()); }
   int download(size_t from, size_t to) {
     svs_ctx *ctx = m->ctx;
-    SVS_HIP(ctx, hipMemcpyAsync(m->h_dn.get() + from, m->d_dn.get() + from, to - from, hipMemcpyDeviceToHost, ctx->stream));
+    if (int rc = m->dn.download(ctx, from, to)) return rc;
     SVS_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return SVS_OK;
   }

@@ -469,18 +469,6 @@ extern "C" int svs_reg_destroy(svs_reg *reg) {
   return SVS_OK;
 }
 
-static void reg_fastgrid_for_level(int w, int h, int level, svs_fastgrid *g) {      // stereo_frontend.cpp:73-88 + fast_grid.cpp:23-58
-  const int dim = std::max(3 - (int)(level * 0.5), 1);
-  const double inv_fac = 1.0 / (1 << level);
-  const int total = (int)(2000 * inv_fac * inv_fac), per_cell = total / (dim * dim), bound = std::max(per_cell / 3, 10);
-  g->gx = g->gy = dim;
-  g->min_inner = (int)(per_cell - bound * 0.33); g->min_outer = per_cell - bound;
-  g->max_inner = (int)(per_cell + bound * 0.33); g->max_outer = per_cell + bound;
-  g->cell_w = w / dim; g->cell_h = h / dim;
-  g->fast_min = 10; g->fast_max = 40;
-  for (int i = 0; i < SVS_MAX_CELLS; ++i) g->thr[i] = 25;
-}
-
 struct CommitLayout { size_t edge_kf, edge_str, ids, track, bytes; };
 static CommitLayout commit_layout(int KB, int NP) {
   CommitLayout C;
@@ -530,7 +518,7 @@ extern "C" int svs_reg_create(svs_ctx *ctx, const svs_cam *cam, int max_requests
     const double s = (double)(1 << l);
     g->cams[l] = svs_cam{cam->f / s, cam->cx / s, cam->cy / s, cam->b * (1 << l), (int32_t)(cam->w / s), (int32_t)(cam->h / s)};
     w[l] = g->cams[l].w; h[l] = g->cams[l].h;
-    reg_fastgrid_for_level(w[l], h[l], l, &grids[l]);
+    fastgrid_for_level(w[l], h[l], l, &grids[l]);
     g->ncell[l] = grids[l].gx * grids[l].gy;
   }
   if (int rc = svs_fast_create(ctx, SVS_NUM_PYR_LEVELS, w, h, grids, max_requests, 8192, &g->fast)) return rc;

@@ -327,6 +327,57 @@ def test_a_batch_of_33_equals_each_stream_alone_a_repetition_and_leaves_the_map_
         fe.close()
 
 
+def _vertex_tables(rng, B):
+    """a setVertexTable request per stream: 1 .. 5 vertices, staged sets whose sizes differ from stream to stream"""
+    reqs = []
+    for b in range(B):
+        V = 1 + b % 5
+        reqs.append(dict(stream=b, vertex_kf=[int(k) for k in rng.permutation(200)[:V]], vertex_T=rng.standard_normal((V, 12)), act=b % V,
+                         sets=[[int(i) for i in rng.permutation(5000)[:int(rng.integers(0, 60))]] for _ in range(V)], neighbors=[v for v in range(V) if v != b % V][:3],
+                         slot_kf=slots((25,) if b % 3 == 0 else ())))
+    return reqs
+
+
+def test_a_staging_block_that_grows_in_mid_life(gpu_ctx, frames_of, scene, both):
+    """one request, then 33 that ask for every optional output, then one again, on ONE front end: the blocks start at twice the first call's need, so the second
+    call outgrows them and the third reuses the bigger ones.  setNeighborhoodFromMap: every call against the model, and its outputs and device rows against a fresh
+    front end that makes only that call.  setVertexTable: the resident rows of the streams a call names, read back by a request that leaves its stream untouched,
+    against those of a fresh front end that makes only that call"""
+    model, table, dmap = both
+    B = 33
+    roots = [(HUB, 40, 10), (40, 40, 10), (LONE, LONE, 10), (HUB, HUB, 0), (40, 3, 1), (13, 40, 10), (HUB, 19, 20)]
+    reqs = [_keyed(scene, b, *roots[b % len(roots)], slot_kf=slots((25,) if b % 3 == 0 else ())) for b in range(B)]
+    tabs = _vertex_tables(np.random.default_rng(5), B)
+    key = lambda outs, rq: [(o["raw"], o["slot_T"].tobytes()) + _state(o, q["stream"]) for o, q in zip(outs, rq)]
+
+    def rows(fe, rq):
+        back = fe.setNeighborhoodFromMap(dmap.map, [_q(q["stream"], 7, 7, slot_kf=q["slot_kf"]) for q in rq], want_tables=True)
+        assert all(o["root_outside_window"] == 1 for o in back)
+        return [(o["kf_table"].tobytes(), o["kf_vertex"].tobytes()) for o in back]
+
+    nbr_calls, tab_calls = [[reqs[0]], reqs, [reqs[1]]], [[tabs[0]], tabs, [tabs[1]]]
+    fe = _make_fe(gpu_ctx[0], frames_of, model, B=B)
+    try:
+        got = [key(_check(fe, dmap, model, table, rq)[0], rq) for rq in nbr_calls]
+        assert got[1][0] == got[0][0] and got[2][0] == got[1][1]
+        got_tabs = []
+        for rq in tab_calls:
+            fe.setVertexTable(rq)
+            got_tabs.append(rows(fe, rq))
+        assert got_tabs[1][0] == got_tabs[0][0] and got_tabs[2][0] == got_tabs[1][1] and len(set(got_tabs[1])) == B
+    finally:
+        fe.close()
+    for nq, rq, g, gt in zip(nbr_calls, tab_calls, got, got_tabs):      # (the two calls stage through blocks of their own: one fresh front end serves both)
+        fresh = _make_fe(gpu_ctx[0], frames_of, model, B=B if len(rq) > 1 else 2)
+        try:
+            outs = fresh.setNeighborhoodFromMap(dmap.map, nq, refresh_poses=True, vertex_cap=VCAP, want_records=True, want_tables=True)
+            assert key(outs, nq) == g, f"setNeighborhoodFromMap, {len(nq)} request(s)"
+            fresh.setVertexTable(rq)
+            assert rows(fresh, rq) == gt, f"setVertexTable, {len(rq)} request(s)"
+        finally:
+            fresh.close()
+
+
 # ---- 5. refusals ---------------------------------------------------------------------------------------------------------------------------------------------------
 def test_refused_calls_change_nothing(gpu_ctx, frames_of, host_frames, scene, both):
     from scavislam_amd import capi

@@ -419,6 +419,45 @@ def test_same_bytes_alone_in_a_batch_repeated_and_on_a_map_built_in_another_orde
         second.close()
 
 
+def test_a_staging_block_that_grows_in_mid_life(gpu_ctx, frames, scene, both):
+    """one request, then 33 that ask for every optional output, then one again, on ONE front end of 33 streams: the staging block starts at twice the first call's
+    need, so the second call outgrows it and the third reuses the bigger one.  Every call against the model, and its outputs and device rows against a fresh front
+    end that makes only that call"""
+    import torch
+    from scavislam_amd.frontend import StereoFrontend
+    model, dmap = both
+    B, ids = 33, MM.scene_ids(scene)
+    poses = _poses(model)
+
+    def wide_fe():
+        fe = StereoFrontend(gpu_ctx[0], CAM, max_points=1024, max_keyframes=K, n_streams=B)
+        for s, k in enumerate(ids[1:] + [MM.ROOT_ID]):
+            with torch.cuda.stream(gpu_ctx[1]):
+                fr = {n: t[:1].repeat(B, 1, 1) for n, t in (frames["kf"][s] if s < len(ids) - 1 else frames["act"]).items()}
+            fe.processFirstFrames(**fr)
+            fe.keepKeyframes(s, np.stack([np.asarray(poses[k], np.float64).reshape(12)] * B))
+        return fe
+
+    head, ge = _head(scene)
+    lists = _vertex_lists(scene)
+    reqs = [_request(b, lists[b % len(lists)], NM.slot_table(scene, missing=(ids[4],) if b % 3 == 0 else ()), head if b % 2 == 0 else None, ge if b % 2 == 0 else None)
+            for b in range(B)]
+    calls = [[reqs[0]], reqs, [reqs[1]]]
+    key = lambda outs, rq: [(o["raw"], o["table"][q["stream"]].tobytes()) for o, q in zip(outs, rq)]
+    fe = wide_fe()
+    try:
+        got = [key(_check(fe, dmap, model, rq, refresh=True)[0], rq) for rq in calls]
+        assert got[1][0] == got[0][0] and got[2][0] == got[1][1]
+    finally:
+        fe.close()
+    for rq, g in zip(calls, got):
+        fresh = wide_fe() if len(rq) > 1 else _make_fe(gpu_ctx[0], frames, scene, poses)
+        try:
+            assert key(fresh.setCandidatesFromMap(dmap.map, rq, refresh_poses=True, vertex_cap=VCAP, want_records=True), rq) == g, f"{len(rq)} request(s)"
+        finally:
+            fresh.close()
+
+
 # ---- 9. the C++ adaptor --------------------------------------------------------------------------------------------------------------------------------------------
 def test_cpp_smoke_prints_the_models_counts(gpu_ctx, tmp_path):
     """tests/cpp/neighborhood_smoke.cpp builds a small map of its own (4 keyframes, 40 points, the rule point p is observed by keyframe p % 4 and by its anchor

@@ -349,6 +349,62 @@ def test_hand_over_without_slots_batch_of_33(gpu_ctx):
     fe.close()
 
 
+def test_a_staging_block_that_grows_in_mid_life_batch_of_33(gpu_ctx):
+    """putNewpoints, newpoints and setCandidatesFromNewpoints with one request, then 33, then one again, on ONE front end: the staging block starts at twice the first
+    call's need, so the 33 outgrow it and the third call reuses the bigger block.  Every store against the model; the rows a call names against a fresh front end
+    that makes only that call (a hand-over: behind one put of the same stores)"""
+    rng = np.random.default_rng(6)
+    B, MP = 33, 256
+    rec = lambda n, first, kf=3: NM.random_records(rng, n, first, kf_index=kf)
+    put33 = [dict(stream=b, kf_id=3, records=rec(int(rng.integers(1, 40)), 1000 * b), mode=NM.REPLACE) for b in range(B)]
+    put33 += [dict(stream=b, kf_id=int(k), records=rec(int(rng.integers(0, 40)), 100000 + 1000 * b + 100 * int(k))) for b in range(2, B) for k in rng.permutation([0, 1, 2])[:b % 3]]
+    puts = [[dict(stream=0, kf_id=3, records=rec(5, 70000), mode=NM.REPLACE)], put33, [dict(stream=1, kf_id=3, records=rec(9, 80000), mode=NM.REPLACE)]]
+    slot = [-1] * 4
+    reqs = [dict(stream=b, keys=[int(k) for k in rng.permutation(5)[:int(rng.integers(1, 5))]], slot_kf=slot, tail=rec(int(rng.integers(0, 40)), 90000, kf=-1)) for b in range(B)]
+    lists = [[reqs[0]], [reqs[int(r)] for r in rng.permutation(B)], [reqs[1]]]
+
+    def fresh():
+        fe = bare_frontend(gpu_ctx, B, max_points=MP)
+        fe.reserveNewpoints(500, 8)
+        return fe
+
+    def stores(fe, call):
+        got = fe.newpoints()
+        return [(got[b]["raw"], got[b]["records"].tobytes()) for b in sorted({q["stream"] for q in call})]
+
+    def handed(fe, call):
+        outs = fe.setCandidatesFromNewpoints(call, want_records=True)
+        return [({k: o[k] for k in NM_RESULT}, outs[0]["table"][q["stream"]].tobytes(), outs[0]["group_end"][q["stream"]].tobytes()) for o, q in zip(outs, call)]
+
+    fe = fresh()
+    models = [NM.Store(500, 8) for _ in range(B)]
+    got_put, got_list = [], []
+    for k, call in enumerate(puts):
+        fe.putNewpoints(call)
+        for b in range(B):
+            models[b].put_all([q for q in call if q["stream"] == b])
+        assert_stores(fe, models, f"put call {k}")
+        got_put.append(stores(fe, call))
+    for call in lists:
+        got_list.append(handed(fe, call))
+        for (res, row, _), q in zip(got_list[-1], call):
+            want, ge, want_res = models[q["stream"]].compose(q["keys"], slot, q["tail"], MP)
+            assert res == want_res and not res["over_capacity"] and row[:want.nbytes] == want.tobytes() and set(row[want.nbytes:]) <= {0xFF}, f"stream {q['stream']}"
+    assert_stores(fe, models, "the hand-over changes no store")
+    fe.close()
+    final = [q for q in put33 if q["stream"] != 1] + puts[2]          # one call that leaves every stream's store as the three left it
+    for call, g in zip(puts, got_put):
+        one = fresh()
+        one.putNewpoints(call)
+        assert stores(one, call) == g, f"putNewpoints, {len(call)} request(s)"
+        one.close()
+    for call, g in zip(lists, got_list):
+        one = fresh()
+        one.putNewpoints(final)
+        assert handed(one, call) == g, f"setCandidatesFromNewpoints, {len(call)} request(s)"
+        one.close()
+
+
 # ---- seeding, pruning and the hand-over on a front end that tracks -----------------------------------------------------------------------------------------------
 def tracking_frontend(gpu_ctx, B=2):
     import test_gpu_seed as TS
